@@ -21,6 +21,8 @@ import os
 import sys
 import time
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
@@ -357,6 +359,51 @@ def extra_runs(ex, H, torch):
     return out
 
 
+DUMP_ROWS_TARGET = 1 << 18  # --dump-outputs: about this many sampled result rows ...
+DUMP_ROWS_MAX = 1 << 19     # ... and never more (3 columns x 4 limbs x 8 B per row: 48 MiB)
+
+
+def u64_limbs(a):
+    """uint64 values as float64 [..., 4]: their 16-bit limbs, most significant first.  Exact, and a difference of one in
+    any value stays visible to a comparison with a relative tolerance up to 1e-5."""
+    a = np.asarray(a, dtype=np.uint64)
+    return np.stack([((a >> np.uint64(s)) & np.uint64(0xFFFF)).astype(np.float64) for s in (48, 32, 16, 0)], -1)
+
+
+def dump_outputs(path, res, ex, torch, rows):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, as path/<name>.npy (u64_limbs):
+    n_matches, sum_r, sum_s [4] -- the hmj_result fields every mode fills -- and, when rows=True (--materialize), the
+    result rows (key, rval, sval) as rows.npy [m, 3, 4]: all of them up to DUMP_ROWS_MAX, else the rows whose key's
+    multiplicative hash falls into a fixed 2^-b of its range (about DUMP_ROWS_TARGET rows), in both cases sorted by
+    (key, rval, sval), so that the dump does not depend on the order the join wrote its rows in.  Returns
+    {name: shape}."""
+    os.makedirs(path, exist_ok=True)
+    out = {}
+    for k in ("n_matches", "sum_r", "sum_s"):
+        out[k] = u64_limbs(int(getattr(res, k)))
+    n = int(res.n_matches)
+    if rows and n and res.key:
+        from hashmergejoin_amd.join import _memcpy_d2d
+
+        cols = []
+        for ptr in (res.key, res.rval, res.sval):
+            t = torch.empty(n, dtype=torch.int64, device="cuda:%d" % ex.device)
+            _memcpy_d2d(torch, t, ptr, n * 8)
+            cols.append(t)
+        if n > DUMP_ROWS_MAX:
+            b = max(1, (n // DUMP_ROWS_TARGET - 1).bit_length())  # 2^-b of the hash range: n / 2^b ~ DUMP_ROWS_TARGET
+            h = cols[0] * -7046029254386353131  # 0x9E3779B97F4A7C15 as int64; wraps mod 2^64
+            keep = ((h >> (64 - b)) & ((1 << b) - 1)) == 0  # top b bits of the hash are zero
+            cols = [c[keep] for c in cols]
+        m = np.stack([c.cpu().numpy().view(np.uint64) for c in cols], 1)
+        del cols
+        m = m[np.lexsort((m[:, 2], m[:, 1], m[:, 0]))][:DUMP_ROWS_MAX]
+        out["rows"] = u64_limbs(m)
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    return {k: list(v.shape) for k, v in out.items()}
+
+
 METRIC = "probe-side tuples/s + achieved HBM GB/s, |R|=|S|=2^28 u64 keys"
 
 
@@ -545,7 +592,13 @@ def main():
                     help="wall-clock limit of the whole run; past it every rank is stopped and an error line is printed")
     ap.add_argument("--step-timeout-s", type=float, default=120.0,
                     help="N > 1: deadline of one exchange step inside the library (hmj_comm_set_timeout_ms)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy: n_matches, sum_r, sum_s and, "
+                         "with --materialize on one GPU, a fixed sample of the result rows, sorted (rows.npy); u64 values as "
+                         "float64 16-bit limbs, most significant first (bench.dump_outputs)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(a.gpus, a.timeout_s, steps=a.steps, warmup=a.warmup))  # before anything touches the GPU
@@ -666,6 +719,10 @@ def main():
         t = torch.tensor([dt, probe_ms_slowest], dtype=torch.float64, device=rdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt, probe_ms_slowest = float(t[0].item()), float(t[1].item())
+    dumped = None
+    if a.dump_outputs and rank == 0:  # (distributed: the global result's counts; the rows stay on their ranks)
+        dumped = dump_outputs(a.dump_outputs, res, ex, torch, rows=bool(flags & H.HMJ_MATERIALIZE) and not distributed)
+        torch.cuda.empty_cache()
     assert n_matches == n_total, "every probe row must match exactly once (%d != %d)" % (n_matches, n_total)
 
     exit_code = 0
@@ -775,6 +832,8 @@ def main():
                           "reserve_ms": None if reserve_ms is None else round(reserve_ms, 2),
                           "first_join_ms": None if first_ms is None else round(first_ms, 2)},
         }
+        if dumped is not None:
+            line["dump_outputs"] = {"dir": a.dump_outputs, "shapes": dumped}
         if distributed:
             transport = "rccl" if (backend == "nccl" or force_dist) else "callbacks over " + backend
             owner = {0: "none (one rank: plain local join)", 1: "hash of the key (fallback: separate owner split)",

@@ -8,7 +8,7 @@
  * PARITY PINNED: every function below is checked against the real reference compiled from
  * /root/reference (oracle/_ref/libhmj_ref.so, see oracle/ref_driver.cc) in
  * tests/test_oracle_vs_ref.py, and against committed golden vectors generated from that
- * same compiled reference (tests/golden/, generator script tests/golden/make_golden.py).
+ * same compiled reference (tests/golden/, generator scripts tests/golden/make_golden.py and make_ref_calls.py).
  *
  * Layouts: "aos"  = n x { uint64 key; uint64 val }            (std::pair<u64,u64>, 16 B)
  *          "hkv"  = n x { uint64 hash; uint64 key; uint64 val } (logical order of the

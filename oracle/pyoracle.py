@@ -9,6 +9,7 @@ Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import 
 The product package (hashmergejoin_amd/) never imports it.
 """
 import ctypes as C
+import hashlib
 import os
 
 import numpy as np
@@ -414,3 +415,82 @@ class Reference:
 
     def radix_int_non_inplace_pairs(self, inh, outh, threads):
         self.lib.ref_radix_int_non_inplace_pairs(inh, outh, threads)
+
+
+def _feed(h, x):
+    if isinstance(x, (tuple, list)):
+        h.update(b"(%d" % len(x))
+        for e in x:
+            _feed(h, e)
+        h.update(b")")
+    elif isinstance(x, np.ndarray):
+        a = np.ascontiguousarray(x, dtype=np.uint64)
+        h.update(b"a%r" % (a.shape,))
+        h.update(a.tobytes())
+    elif isinstance(x, (bool, int, np.integer)):
+        h.update(b"i%d" % int(x))
+    elif isinstance(x, str):
+        h.update(b"s%d:" % len(x) + x.encode())
+    elif x is None:
+        h.update(b"n")
+    else:
+        raise TypeError("no digest for %r" % type(x))
+
+
+def digest(x):
+    """128-bit SHA-256 digest (hex) of a result or argument list: ints, uint64 arrays (shape included), strings,
+    None, and tuples / lists of them."""
+    h = hashlib.sha256()
+    _feed(h, x)
+    return h.hexdigest()[:32]
+
+
+class Recorded:
+    """A reference result known only by its digest."""
+
+    def __init__(self, key, dg):
+        self.key, self.digest = key, dg
+
+    def __repr__(self):
+        return "Recorded(%s -> %s)" % (self.key, self.digest)
+
+
+def same(value, result):
+    """value (ours) equals result (a Reference result, or a Recorded one): equal digests."""
+    return digest(value) == (result.digest if isinstance(result, Recorded) else digest(result))
+
+
+class RecordedReference:
+    """The compiled reference's results on a fixed set of calls, kept as digests (tests/golden/ref_calls.json,
+    written by tests/golden/make_ref_calls.py), so that the checks against it run where oracle/_ref/ cannot be built.
+
+    Any Reference method can be called on it.  A call's key is the method name and the digest of its arguments, so
+    inputs that drifted find no record.  With `live` (an available Reference) a call runs the reference, checks its
+    result against the record (record=True: stores it instead) and returns the result; without, it returns the
+    record as a Recorded, which `same` compares.  The keyword column=k keeps only column k of an array result."""
+
+    def __init__(self, calls, live=None, record=False):
+        assert live is not None or not record
+        self.calls, self.live, self.record = calls, live, record
+
+    def __getattr__(self, name):
+        if name.startswith("_") or not callable(getattr(Reference, name, None)):
+            raise AttributeError(name)
+
+        def call(*args, column=None, **kw):
+            key = "%s:%s" % (name, digest([list(args), sorted(kw.items()), column])[:24])
+            if self.live is None:
+                if key not in self.calls:
+                    raise KeyError("no recorded reference result for %s%s: inputs differ from the recorded ones, or the call "
+                                   "is new (python tests/golden/make_ref_calls.py, where oracle/_ref is built)" % (name, key[len(name):]))
+                return Recorded(key, self.calls[key])
+            res = getattr(self.live, name)(*args, **kw)
+            if column is not None:
+                res = res[:, column]
+            if self.record:
+                self.calls[key] = digest(res)
+            else:
+                assert self.calls.get(key) == digest(res), "reference result of %s differs from tests/golden/ref_calls.json" % key
+            return res
+
+        return call

@@ -81,3 +81,18 @@ def test_live_traffic_measurement_gives_way_quietly_without_a_gpu(monkeypatch):
     monkeypatch.setenv("PATH", "/nonexistent")
     monkeypatch.setattr(bench.os.path, "exists", lambda p: False)
     assert bench.measure_traffic_live(20, timeout_s=5.0) == (None, "rocprofv3 not found")
+
+
+def test_dump_outputs_writes_exact_counts(tmp_path):
+    # --dump-outputs: u64 results as float64 16-bit limbs, exact whatever their size
+    import types
+
+    import numpy as np
+
+    bench = load_bench()
+    res = types.SimpleNamespace(n_matches=1 << 28, sum_r=(1 << 64) - 1, sum_s=0x0123456789ABCDEF, key=None)
+    shapes = bench.dump_outputs(str(tmp_path / "d"), res, None, None, rows=False)
+    assert shapes == {"n_matches": [4], "sum_r": [4], "sum_s": [4]}
+    for k in shapes:
+        a = np.load(tmp_path / "d" / (k + ".npy"))
+        assert a.dtype == np.float64 and sum(int(v) << (48 - 16 * i) for i, v in enumerate(a)) == getattr(res, k), (k, a)
