@@ -51,6 +51,16 @@ class JoinResult(C.Structure):
         return {k: int(getattr(self, k)) for k in ("n_matches", "sum_r", "sum_s", "xor_fold", "mix_sum")}
 
 
+# hmj_join_opts.kind (hmj_join_kind_u64_device)
+HMJ_JOIN_INNER, HMJ_JOIN_SEMI, HMJ_JOIN_ANTI, HMJ_JOIN_PROBE_OUTER = 0, 1, 2, 3
+
+
+class JoinOpts(C.Structure):
+    """hmj_join_opts: the kind of a join and its fill value (in), matched / unmatched probe rows (out)."""
+    _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_uint32), ("outer_fill", C.c_uint64),
+                ("n_probe_matched", C.c_uint64), ("n_probe_unmatched", C.c_uint64)]
+
+
 class Timing(C.Structure):
     _fields_ = [("ms_total", C.c_float), ("ms_h2d", C.c_float), ("ms_d2h", C.c_float),
                 ("ms_partition_build", C.c_float), ("ms_partition_probe", C.c_float),
@@ -187,6 +197,8 @@ def load_library():
     L.hmj_abi_version.argtypes = []
     L.hmj_join_u64_device.restype = i
     L.hmj_join_u64_device.argtypes = [vp, vp, u, vp, u, C.c_uint32, C.POINTER(JoinResult)]
+    L.hmj_join_kind_u64_device.restype = i
+    L.hmj_join_kind_u64_device.argtypes = [vp, vp, u, vp, u, C.c_uint32, C.POINTER(JoinOpts), C.POINTER(JoinResult)]
     L.hmj_prepare_build_u64_device.restype = i
     L.hmj_prepare_build_u64_device.argtypes = [vp, vp, u, u]
     L.hmj_join_u64.restype = i

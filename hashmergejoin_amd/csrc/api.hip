@@ -1191,6 +1191,82 @@ static int plan_join(hmj_ctx* c, const void* R, uint64_t n_build, const void* S,
   return HMJ_OK;
 }
 
+// The probe phase of a join kind (hmj_join_kind_u64_device): both relations partitioned (exact passes, probe-only split),
+// then probe_kind_kernel count [-> scan -> write -> order_rows].  `a` holds the partitions; the bitmap of probe row slots is
+// cleared before each pass, so that the count and the write pass emit the same rows.
+static int execute_kind_probe(hmj_ctx* c, hmj::ProbeArgs a, u32 nb, u32 np, uint32_t flags, hmj_result* out, bool to_host,
+                              const u32* v_start, u32 P, u32 Q, u32 Pi, bool split, int low, bool win_ordered) {
+  int rc;
+  const bool materialize = flags & HMJ_MATERIALIZE, first = flags & HMJ_FIRST_WINS;
+  const int kind = (int)c->join_kind;
+  const u64 n_items = split ? Pi : (u64)P * Q;
+  a.extra = (flags & (HMJ_CHECKSUM | HMJ_SUM_PROBE)) ? 1u : 0u;
+  const size_t matched_bytes = ((size_t)np / 32 + 1) * 4;
+  if ((rc = ensure_dev(c, c->matched, matched_bytes)) != HMJ_OK) return rc;
+  a.matched = (u32*)c->matched.p;
+  HIP_TRY(hipMemsetAsync(c->matched.p, 0, matched_bytes, c->stream));
+  const int grid = hmj::probe_default_grid(c->num_cus);
+  int s = span_begin(c, K_PROBE_COUNT, -1);
+  HIP_TRY(hmj::launch_probe_kind(a, materialize ? 1 : 0, kind, first, c->outer_fill, grid, c->stream));
+  span_end(c, s);
+  c->timing.bytes_probe_count = 16ull * ((u64)nb + np);
+  if (materialize) {
+    s = span_begin(c, K_OUT_SCAN, -1);
+    HIP_TRY(hmj::launch_scan_u64((const u64*)c->part_count.p, (u64*)c->part_out_off.p, (u32)n_items, c->stream));
+    span_end(c, s);
+  }
+  u64* h = (u64*)c->h_accum.p;
+  HIP_TRY(hipMemcpyAsync(h, c->accum.p, 8 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (h[hmj::ACC_ERR] & hmj::ERR_PREFIX) return kRetryNoPrefix;
+  out->n_matches = h[hmj::ACC_N];
+  out->sum_r = h[hmj::ACC_SUM_R];
+  out->sum_s = h[hmj::ACC_SUM_S];
+  out->xor_fold = h[hmj::ACC_XOR];
+  out->mix_sum = h[hmj::ACC_MIX];
+  out->sum_probe_all = (flags & HMJ_SUM_PROBE) ? h[hmj::ACC_SUM_P] : 0;
+  c->kind_unmatched = h[hmj::ACC_PAD];  // rows emitted with the fill: the unmatched probe rows (ANTI, OUTER)
+  if (!materialize || out->n_matches == 0) return HMJ_OK;
+  // semi / anti rows have no rval: 16 B per row, unless the ordered epilogue (which sorts three columns) needs zeros there
+  const bool rval_col = kind == HMJ_JOIN_PROBE_OUTER || (flags & HMJ_ORDERED);
+  const size_t bytes = (size_t)out->n_matches * 8;
+  if ((rc = ensure_dev(c, c->out_key, bytes)) != HMJ_OK) return rc;
+  if (rval_col && (rc = ensure_dev(c, c->out_rval, bytes)) != HMJ_OK) return rc;
+  if ((rc = ensure_dev(c, c->out_sval, bytes)) != HMJ_OK) return rc;
+  a.out_key = (u64*)c->out_key.p;
+  a.out_rval = rval_col ? (u64*)c->out_rval.p : nullptr;
+  a.out_sval = (u64*)c->out_sval.p;
+  HIP_TRY(hipMemsetAsync(c->matched.p, 0, matched_bytes, c->stream));
+  s = span_begin(c, K_PROBE_WRITE, -1);
+  HIP_TRY(hmj::launch_probe_kind(a, 2, kind, first, c->outer_fill, grid, c->stream));
+  span_end(c, s);
+  c->timing.bytes_probe_write = 16ull * ((u64)nb + np) + (kind == HMJ_JOIN_PROBE_OUTER ? 24ull : 16ull) * out->n_matches;
+  const u64 *rk = a.out_key, *rr = a.out_rval, *rs = a.out_sval;
+  if (flags & HMJ_ORDERED) {
+    int retry = 0;
+    if ((rc = order_rows(c, v_start, nullptr, nullptr, P, Q, low, out->n_matches, win_ordered, out->n_matches > 2ull * nb, &rk,
+                         &rr, &rs, &retry)) != HMJ_OK)
+      return rc;
+    if (retry) return retry;
+  }
+  if (kind != HMJ_JOIN_PROBE_OUTER) rr = nullptr;
+  if (to_host) {
+    if ((rc = ensure_host(c, c->h_key, bytes, false)) != HMJ_OK) return rc;
+    if (rr && (rc = ensure_host(c, c->h_rval, bytes, false)) != HMJ_OK) return rc;
+    if ((rc = ensure_host(c, c->h_sval, bytes, false)) != HMJ_OK) return rc;
+    s = span_begin(c, K_D2H, -1);
+    HIP_TRY(hipMemcpyAsync(c->h_key.p, rk, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (rr) HIP_TRY(hipMemcpyAsync(c->h_rval.p, rr, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_sval.p, rs, bytes, hipMemcpyDeviceToHost, c->stream));
+    span_end(c, s);
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  out->key = to_host ? (const uint64_t*)c->h_key.p : (const uint64_t*)rk;
+  out->rval = rr ? (to_host ? (const uint64_t*)c->h_rval.p : (const uint64_t*)rr) : nullptr;
+  out->sval = to_host ? (const uint64_t*)c->h_sval.p : (const uint64_t*)rs;
+  return HMJ_OK;
+}
+
 static int execute_join(hmj_ctx* c, const void* R, uint64_t n_build, const void* S, uint64_t n_probe, uint32_t flags,
                         hmj_result* out, bool to_host, const JoinPlan& p) {
   int rc;
@@ -1578,9 +1654,11 @@ static int execute_join(hmj_ctx* c, const void* R, uint64_t n_build, const void*
     const u32 build_slice = 4096u;
     // virtual partitions: at most P + np / slice from probe slices; build slices multiply a partition's count,
     // bounded by giving the table room for 8x that (a larger total makes the split be ignored)
-    u32 build_thr = enumerating ? 6144u : 0u;
-    u32 cap_v = (P + np / slice + 1) * (enumerating ? 8u : 1u);
-    if (enumerating && cap_v < (1u << 18)) cap_v = 1u << 18;  // room for the 256-row slices of build-heavy partitions
+    // (join kinds: never -- a probe row must meet its key's build rows in ONE work item, or its hit / miss status is wrong)
+    const bool build_slices = enumerating && !c->join_kind;
+    u32 build_thr = build_slices ? 6144u : 0u;
+    u32 cap_v = (P + np / slice + 1) * (build_slices ? 8u : 1u);
+    if (build_slices && cap_v < (1u << 18)) cap_v = 1u << 18;  // room for the 256-row slices of build-heavy partitions
     u32* hnv = (u32*)c->h_accum.p;
     u32 *d_vstart = nullptr, *d_rb = nullptr, *d_re = nullptr, *d_sb = nullptr, *d_se = nullptr;
     // The count step reports how many virtual partitions the split needs.  If the table is too small it is
@@ -1671,6 +1749,7 @@ static int execute_join(hmj_ctx* c, const void* R, uint64_t n_build, const void*
     HIP_TRY(hipMemsetAsync(c->matched.p, 0, matched_bytes, c->stream));
   }
 
+  if (c->join_kind) return execute_kind_probe(c, a, nb, np, flags, out, to_host, v_start, P, Q, Pi, split, low, win_ordered);
   s = span_begin(c, K_PROBE_COUNT, -1);
   if (!first && !extra && Q == 1 && Pi >= 2) {
     // pipelined count kernel (with per-partition counts when materialising), then the generic
@@ -2773,18 +2852,19 @@ int join_device(hmj_ctx* c, const void* R, uint64_t n_build, const void* S, uint
   // not the ordered write's wide shape (6144) is run as an ordered one -- ordered rows are a valid answer, and the exact
   // path with split partitions that would run otherwise is slower than the ordered write (2^25 ... 2^26.6 x 2^30 rows:
   // 46-56 ms against 34; profiles/r05af_*).
-  if ((flags & HMJ_MATERIALIZE) && !(flags & HMJ_ORDERED) && !c->prepare_only && c->promote_to_ordered && n_build > 0 &&
+  if ((flags & HMJ_MATERIALIZE) && !(flags & HMJ_ORDERED) && !c->prepare_only && !c->join_kind && c->promote_to_ordered && n_build > 0 &&
       n_probe <= 0xFFFFFFFFull && n_probe >= c->big_join_rows && (double)n_probe >= 2.5 * (double)n_build && c->force_bits < 0) {
     const double P18 = (double)(1u << (2 * hmj::SLAB_MAX_BITS));
     const double hi = fk_probe_rows_hi((double)n_probe / P18, (double)n_probe / (double)n_build, P18);
     if (hi > 5120.0 && hi <= 6144.0) flags |= HMJ_ORDERED;
   }
-  // the workload this call belongs to (a prepared build side: the join it was announced for) and what is known about it
-  memo_for(c, workload_signature(n_build, c->prepare_only ? c->probe_hint : n_probe, flags, 0));
+  // the workload this call belongs to (a prepared build side: the join it was announced for) and what is known about it;
+  // a join kind is a workload of its own (2 + kind): it never changes what inner joins of the same sizes have learnt
+  memo_for(c, workload_signature(n_build, c->prepare_only ? c->probe_hint : n_probe, flags, c->join_kind ? 2 + (int)c->join_kind : 0));
   std::memset(&c->plan, 0, sizeof(c->plan));
   int rc = HMJ_OK, kr_h = 0;
   bool kr_done = false;
-  if (key_ranges_wanted(c, n_build, n_probe, flags, to_host, &kr_h)) {
+  if (!c->join_kind && key_ranges_wanted(c, n_build, n_probe, flags, to_host, &kr_h)) {
     rc = join_by_key_ranges(c, R, n_build, S, n_probe, flags, out, kr_h, &kr_done);
   } else if (c->cat_key.p) {  // (the appended columns of an earlier join by key ranges: results live until the next join)
     free_dev(c->cat_key);
@@ -2807,14 +2887,17 @@ int join_device(hmj_ctx* c, const void* R, uint64_t n_build, const void* S, uint
 }
 static int join_device_planned(hmj_ctx* c, const void* R, uint64_t n_build, const void* S, uint64_t n_probe, uint32_t flags,
                                hmj_result* out, bool to_host) {
-  {
+  // join kinds take only plans whose probe phase is the partition-by-partition walk: exact passes for both relations
+  // (probe-only split, prefix / window / dense-build plans, the ordered epilogue); no table-wide or one-pass formulations
+  const bool kinds = c->join_kind != 0;
+  if (!kinds) {
     bool done = false;
     int rc = try_global_table(c, R, n_build, S, n_probe, flags, out, to_host, &done);
     if (rc != HMJ_OK || done) return rc;
     rc = try_small_build_ordered(c, R, n_build, S, n_probe, flags, out, to_host, &done);
     if (rc != HMJ_OK || done) return rc;
   }
-  bool auto_prefix = true, slab = true, fast_write = true, win_ordered = true, prefix_unsafe = false, slab_probe = true;
+  bool auto_prefix = true, slab = !kinds, fast_write = !kinds, win_ordered = true, prefix_unsafe = false, slab_probe = !kinds;
   if ((flags & HMJ_ORDERED) && c->wm->exact_prefix_joins > 0) {  // (a failed attempt costs more than the pass over the keys)
     c->wm->exact_prefix_joins--;
     prefix_unsafe = true;
@@ -3279,6 +3362,37 @@ int hmj_join_u64_device(hmj_ctx* c, const void* build_aos_dev, uint64_t n_build,
   if (c->profiling) {
     (void)hipStreamSynchronize(c->stream);
     spans_collect(c);
+  }
+  return rc;
+}
+
+int hmj_join_kind_u64_device(hmj_ctx* c, const void* build_aos_dev, uint64_t n_build, const void* probe_aos_dev,
+                             uint64_t n_probe, uint32_t flags, hmj_join_opts* opts, hmj_result* out) {
+  if (!c) return HMJ_E_ARG;
+  if (!opts || !out) return fail(c, HMJ_E_ARG, "opts / out is NULL");
+  if (opts->struct_size < offsetof(hmj_join_opts, outer_fill) + sizeof(opts->outer_fill))
+    return fail(c, HMJ_E_ARG, "hmj_join_opts.struct_size too small");
+  if (opts->kind > HMJ_JOIN_PROBE_OUTER) return fail(c, HMJ_E_ARG, "unknown join kind");
+  if (opts->kind == HMJ_JOIN_INNER) return hmj_join_u64_device(c, build_aos_dev, n_build, probe_aos_dev, n_probe, flags, out);
+  if (n_build > 0xFFFFFFFFull || n_probe > 0xFFFFFFFFull) return fail(c, HMJ_E_ARG, "too many rows");
+  HIP_TRY(hipSetDevice(c->device));
+  spans_reset(c);
+  c->prep.valid = false;  // like any other call, a kind join discards a prepared build side
+  c->join_kind = opts->kind;
+  c->outer_fill = opts->outer_fill;
+  c->kind_unmatched = 0;
+  int st = span_begin(c, K_TOTAL, -1);
+  int rc = join_device(c, build_aos_dev, n_build, probe_aos_dev, n_probe, flags, out, false);
+  span_end(c, st);
+  c->join_kind = 0;
+  if (c->profiling) {
+    (void)hipStreamSynchronize(c->stream);
+    spans_collect(c);
+  }
+  if (rc == HMJ_OK) {
+    const uint64_t unmatched = opts->kind == HMJ_JOIN_SEMI ? n_probe - out->n_matches : c->kind_unmatched;
+    if (opts->struct_size >= offsetof(hmj_join_opts, n_probe_matched) + sizeof(uint64_t)) opts->n_probe_matched = n_probe - unmatched;
+    if (opts->struct_size >= offsetof(hmj_join_opts, n_probe_unmatched) + sizeof(uint64_t)) opts->n_probe_unmatched = unmatched;
   }
   return rc;
 }

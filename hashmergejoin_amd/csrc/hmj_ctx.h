@@ -130,6 +130,10 @@ struct hmj_ctx {
     int low = 0, B = 0;
   } prep;
   bool prepare_only = false;
+  // the join kind of the call in progress (HMJ_JOIN_*; 0 = inner), set only for the duration of hmj_join_kind_u64_device
+  uint32_t join_kind = 0;
+  u64 outer_fill = 0;
+  u64 kind_unmatched = 0;  // out: rows emitted with the fill by the last kind join (ANTI / OUTER)
   // placement of big allocations (ensure_dev, api.hip): candidates are probed with a fill and the fastest kept
   int place_tries = 4;     // candidates per allocation when a search runs (HMJ_PLACE=n); a fresh candidate of 6 GB costs 3-450 ms
   float place_budget_ms = 50.f;  // wall-clock budget of one buffer's search (HMJ_PLACE_BUDGET_MS)

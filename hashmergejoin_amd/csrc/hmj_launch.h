@@ -115,6 +115,11 @@ struct ProbeArgs {
 hipError_t launch_probe(const ProbeArgs& a, int mode, bool first_wins, bool extra, int grid,
                         hipStream_t st);
 int probe_default_grid(int num_cus);
+// join kinds (semi / anti / probe-side outer; kind = HMJ_JOIN_* of hmj.h): the generic walk over contiguous partitions,
+// emitting by hit / miss.  mode 0 / 1 / 2 as launch_probe's; a.matched: one bit per probe row slot, zeroed before each
+// pass; accum[ACC_PAD] (+=) counts the rows emitted with `fill`.  Build slices are not allowed (r_end / s_end may only cut
+// probe rows).  Semi / anti rows carry no rval: a.out_rval may be NULL (else zeros are written).
+hipError_t launch_probe_kind(const ProbeArgs& a, int mode, int kind, bool first_wins, u64 fill, int grid, hipStream_t st);
 hipError_t launch_probe_count_ext(const ProbeArgs& a, u32* irregular, u32* n_irregular, bool slab,
                                   int num_cus, hipStream_t st);
 hipError_t launch_probe_count_slab(const ProbeArgs& a, int num_cus, hipStream_t st);

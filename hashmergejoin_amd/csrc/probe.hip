@@ -495,6 +495,295 @@ __global__ __launch_bounds__(PB_THREADS, PB_THREADS / 256) void probe_kernel(Pro
   }
 }
 
+// ---- join kinds (hmj_join_kind_u64_device): semi, anti and probe-side outer joins --------------------------------------
+// The generic walk above, emitting by a probe row's hit / miss status instead of by pair.  An item builds its build
+// partition's table of DISTINCT keys chunk after chunk (the FIRST form -- aux = the key's first row -- so a hot build key
+// takes one slot; OUTER without first-wins keeps the per-key row list instead) and streams its probe rows past each:
+//   SEMI : a row is emitted at its first hit; with several chunk tables it is claimed in the bitmap and later chunks skip it;
+//   ANTI : one table: emitted on a miss.  Several: hits are marked in the bitmap, and after the last chunk a sweep over the
+//          item's probe rows emits those whose bit is clear;
+//   OUTER: matches are emitted per chunk as the inner kernel does (and marked); unmatched rows as ANTI's are.
+// An empty build partition is one empty table: ANTI and OUTER emit every probe row of the item.
+// Rows are (key, rval, sval): rval = 0 for SEMI / ANTI (written only where a.out_rval is set), `fill` for an unmatched
+// OUTER row.  MODE 0: count + sums, MODE 1: also per-item counts, MODE 2: rows written at part_out_off[w]; 1 and 2 agree
+// row for row (the caller clears the bitmap between them).  Row j of an item is always handled by thread j % PB_THREADS,
+// so only the thread that owns a row tests or sets its bit.  a.extra bit 0: checksums.  accum[ACC_PAD] (MODE 0 / 1):
+// rows emitted with the fill.  Build slices are never given (every probe row must meet its whole build partition).
+constexpr int KIND_SEMI = 1, KIND_ANTI = 2, KIND_OUTER = 3;
+template <int MODE, int KIND, bool FIRST>
+__global__ __launch_bounds__(PB_THREADS, PB_THREADS / 256) void probe_kind_kernel(ProbeArgs a, u64 fill) {
+  constexpr bool LIST = KIND == KIND_OUTER && !FIRST;  // every build row of a key is paired
+  constexpr bool PERSIST = !LIST;                      // rows with a key already in the table take no slot
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  ProbeSmem& sm = *reinterpret_cast<ProbeSmem*>(smem_raw);
+  const Tup* __restrict__ R = static_cast<const Tup*>(a.R);
+  const Tup* __restrict__ S = static_cast<const Tup*>(a.S);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const bool extra = a.extra & 1u;
+
+  u64 acc_n = 0, acc_r = 0, acc_s = 0, acc_x = 0, acc_m = 0, acc_p = 0, acc_u = 0;
+  bool pfx_bad = false;
+  if (MODE == 1 && tid == 0) sm.pcount = 0;
+
+  const u64 items = (u64)a.P * a.Q;
+  for (u64 w = blockIdx.x; w < items; w += gridDim.x) {
+    const u32 p = (u32)(w / a.Q), q = (u32)(w % a.Q);
+    const u32 rb = a.r_off[p], nb = (a.r_end ? a.r_end[p] : a.r_off[p + 1]) - rb;
+    const u32 sb0 = a.s_off[p], np0 = (a.s_end ? a.s_end[p] : a.s_off[p + 1]) - sb0;
+    const u32 lo = (u32)((u64)np0 * q / a.Q), hi = (u32)((u64)np0 * (q + 1) / a.Q);
+    const u32 sb = sb0 + lo, np = hi - lo;
+    u64 pc = 0;
+    u64 run = (MODE == 2) ? a.part_out_off[w] : 0;  // next output row of this item
+    if (np > 0) {
+      const bool multi = nb > PB_CAP;  // (possibly) several tables: hits go through the bitmap
+      // one result row of the count modes
+      auto tally = [&](u64 key, u64 rval, u64 sval) __attribute__((always_inline)) {
+        pc++;
+        acc_r += rval;
+        acc_s += sval;
+        if (extra) {
+          const u64 m = tmix(key, rval, sval);
+          acc_x ^= m;
+          acc_m += m;
+        }
+      };
+      // probe row `row` (its slot in S: the bitmap index) against the current table: m = rows it emits now, first = the
+      // key's first row (FIRST) or list head (LIST), fillrow = it is emitted as unmatched
+      auto look = [&](u64 key, u32 row, u32& m, u32& first, bool& fillrow) __attribute__((always_inline)) {
+        u32 i = sm.head[tab_hash(key)];
+        while (i != NIL && sm.key[i] != key) i = sm.next[i];
+        m = 0;
+        first = NIL;
+        fillrow = false;
+        if (i != NIL) {
+          if (KIND == KIND_SEMI) {
+            m = first_claim(a.matched, multi, row) ? 1u : 0u;
+          } else if (KIND == KIND_ANTI) {
+            if (multi) (void)first_claim(a.matched, true, row);
+          } else if (FIRST) {
+            if (first_claim(a.matched, multi, row)) {
+              m = 1;
+              first = sm.aux[i];
+            }
+          } else {
+            if (multi) (void)first_claim(a.matched, true, row);
+            first = i;
+            for (u32 n = i; n != NIL; n = sm.aux[n]) m++;
+          }
+        } else if (KIND != KIND_SEMI && !multi) {
+          m = 1;
+          fillrow = true;
+        }
+      };
+      // the rval of the k-th row a probe row emits (k < m)
+      auto rval_of = [&](u32 first, bool fillrow) __attribute__((always_inline)) -> u64 {
+        if (KIND != KIND_OUTER) return 0;
+        if (fillrow) return fill;
+        return FIRST ? R[(u64)rb + first].val : sm.val[first];
+      };
+
+      u32 c0 = 0;
+      bool first_table = true;
+      do {  // at least one (possibly empty) table
+        __syncthreads();
+        for (u32 i = tid; i < PB_NB; i += PB_THREADS) sm.head[i] = NIL;
+        if (tid == 0) sm.nslot = 0;
+        __syncthreads();
+        u32 used = 0;
+        while (c0 < nb) {
+          const u32 cn = (nb - c0 < PB_BATCH) ? nb - c0 : PB_BATCH;
+          if (used + cn > PB_CAP) break;
+          Tup t[2];
+#pragma unroll
+          for (int k = 0; k < 2; k++) {
+            const u32 i = k * PB_THREADS + tid;
+            if (i < cn) t[k] = R[(u64)rb + c0 + i];
+          }
+#pragma unroll
+          for (int k = 0; k < 2; k++) {
+            const u32 i = k * PB_THREADS + tid;
+            bool valid = i < cn;
+            const u64 key = t[k].key;
+            if (valid && a.pfx_shift && (key >> a.pfx_shift) != a.pfx_val) pfx_bad = true;
+            if (PERSIST) {
+              // a wave whose rows all carry one key (the hot key of a skewed partition) sends one lane: the leader
+              // holds the smallest position
+              const u64 vm = __ballot(valid);
+              if (__popcll(vm) > 1) {
+                const int leader = __ffsll((long long)vm) - 1;
+                const u64 k0 = __shfl(key, leader, kWave);
+                if (__all(!valid || key == k0)) valid = lane == leader;
+              }
+            }
+            if (valid) {
+              const u32 pos = c0 + i;  // position in the partition = input order (stable partitioning)
+              u32 slot = PERSIST ? NIL : used + i;
+              if (!PERSIST) {
+                sm.key[slot] = key;
+                sm.val[slot] = t[k].val;
+                sm.aux[slot] = NIL;
+              }
+              u32* hp = &sm.head[tab_hash(key)];
+              u32 seen = NIL;
+              for (;;) {
+                const u32 hd = __hip_atomic_load(hp, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                u32 found = NIL;
+                for (u32 n = hd; n != seen; n = sm.next[n])
+                  if (sm.key[n] == key) {
+                    found = n;
+                    break;
+                  }
+                if (found != NIL) {
+                  if (PERSIST) {
+                    if (pos < __hip_atomic_load(&sm.aux[found], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))
+                      atomicMin(&sm.aux[found], pos);
+                  } else {
+                    sm.aux[slot] = atomicExch(&sm.aux[found], slot);
+                  }
+                  break;
+                }
+                if (PERSIST && slot == NIL) {
+                  slot = atomicAdd(&sm.nslot, 1u);
+                  sm.key[slot] = key;
+                  sm.aux[slot] = pos;
+                }
+                sm.next[slot] = (u16)hd;
+                u32 expect = hd;
+                if (__hip_atomic_compare_exchange_strong(hp, &expect, slot, __ATOMIC_RELEASE, __ATOMIC_RELAXED,
+                                                         __HIP_MEMORY_SCOPE_WORKGROUP))
+                  break;
+                seen = hd;
+              }
+            }
+          }
+          c0 += cn;
+          __syncthreads();
+          used = PERSIST ? sm.nslot : used + cn;
+          if (PERSIST) __syncthreads();
+        }
+
+        // ---- probe the table
+        if (MODE != 2) {
+          for (u32 j0 = 0; j0 < np; j0 += PB_THREADS * 4) {
+            Tup t[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+              const u32 j = j0 + k * PB_THREADS + tid;
+              if (j < np) t[k] = S[(u64)sb + j];
+            }
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+              const u32 j = j0 + k * PB_THREADS + tid;
+              if (j < np) {
+                const u64 key = t[k].key, sval = t[k].val;
+                if (first_table) {
+                  if (a.pfx_shift && (key >> a.pfx_shift) != a.pfx_val) pfx_bad = true;
+                  acc_p += sval;
+                }
+                u32 m, first;
+                bool fillrow;
+                look(key, sb + j, m, first, fillrow);
+                if (m) {
+                  if (LIST && !fillrow) {
+                    for (u32 n = first; n != NIL; n = sm.aux[n]) tally(key, sm.val[n], sval);
+                  } else {
+                    tally(key, rval_of(first, fillrow), sval);
+                    if (fillrow) acc_u++;
+                  }
+                }
+              }
+            }
+          }
+        } else {
+          for (u32 j0 = 0; j0 < np; j0 += PB_THREADS) {
+            const u32 j = j0 + tid;
+            u64 key = 0, sval = 0;
+            u32 m = 0, first = NIL;
+            bool fillrow = false;
+            if (j < np) {
+              const Tup t = S[(u64)sb + j];
+              key = t.key;
+              sval = t.val;
+              look(key, sb + j, m, first, fillrow);
+            }
+            u32 tot;
+            const u32 off = block_excl_scan_u32<PB_THREADS>(m, sm.scratch, &tot);
+            if (m) {
+              u64 o = run + off;
+              if (LIST && !fillrow) {
+                for (u32 n = first; n != NIL; n = sm.aux[n], o++) {
+                  a.out_key[o] = key;
+                  a.out_rval[o] = sm.val[n];
+                  a.out_sval[o] = sval;
+                }
+              } else {
+                a.out_key[o] = key;
+                if (a.out_rval) a.out_rval[o] = rval_of(first, fillrow);
+                a.out_sval[o] = sval;
+              }
+            }
+            run += tot;
+          }
+        }
+        first_table = false;
+      } while (c0 < nb);
+
+      // ---- several tables: the rows no table matched (ANTI, OUTER), by their clear bits
+      if (KIND != KIND_SEMI && multi) {
+        for (u32 j0 = 0; j0 < np; j0 += PB_THREADS) {
+          const u32 j = j0 + tid, row = sb + j;
+          u32 m = 0;
+          u64 key = 0, sval = 0;
+          if (j < np && !(__hip_atomic_load(a.matched + (row >> 5), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & (1u << (row & 31)))) {
+            const Tup t = S[(u64)sb + j];
+            key = t.key;
+            sval = t.val;
+            m = 1;
+          }
+          if (MODE != 2) {
+            if (m) {
+              tally(key, KIND == KIND_OUTER ? fill : 0, sval);
+              acc_u++;
+            }
+          } else {
+            u32 tot;
+            const u32 off = block_excl_scan_u32<PB_THREADS>(m, sm.scratch, &tot);
+            if (m) {
+              const u64 o = run + off;
+              a.out_key[o] = key;
+              if (a.out_rval) a.out_rval[o] = KIND == KIND_OUTER ? fill : 0;
+              a.out_sval[o] = sval;
+            }
+            run += tot;
+          }
+        }
+      }
+    }
+
+    acc_n += pc;
+    if (MODE == 1) {
+      const u64 ws = wave_sum_u64(pc);
+      if (lane == 0 && ws) atomicAdd(&sm.pcount, ws);
+      __syncthreads();
+      if (tid == 0) {
+        a.part_count[w] = sm.pcount;
+        sm.pcount = 0;
+      }
+    }
+  }
+
+  if (MODE != 2) {
+    if (__any(pfx_bad) && lane == 0) atomicOr(&a.accum[ACC_ERR], ERR_PREFIX);
+    const u64 wu = wave_sum_u64(acc_u);
+    if (lane == 0 && wu) atomicAdd(&a.accum[ACC_PAD], wu);
+    __syncthreads();
+    if (tid < 8) sm.red[tid] = 0;
+    __syncthreads();
+    const u64 v[6] = {acc_n, acc_r, acc_s, acc_x, acc_m, acc_p};  // ACC_N .. ACC_SUM_P order
+    block_accumulate(sm.red, a.accum, v, 1u << ACC_XOR);
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // Fast path of count mode (the headline: hashjoin_bench.cc:131-133 reduction, no flags).
 // Same build+probe, software-pipelined so HBM latency is never exposed: while partition p is
@@ -2450,6 +2739,37 @@ hipError_t launch_probe(const ProbeArgs& a, int mode, bool first_wins, bool extr
 }
 
 int probe_default_grid(int num_cus) { return num_cus * 4; }
+
+template <int MODE, int KIND, bool FIRST>
+static hipError_t launch_kind_t(const ProbeArgs& a, u64 fill, int grid, hipStream_t st) {
+  static SmemAttrOnce attr_once;
+  if (hipError_t e = ensure_max_smem(attr_once, reinterpret_cast<const void*>(probe_kind_kernel<MODE, KIND, FIRST>), (size_t)sizeof(ProbeSmem)); e != hipSuccess) return e;
+  hipLaunchKernelGGL((probe_kind_kernel<MODE, KIND, FIRST>), dim3(grid), dim3(PB_THREADS), sizeof(ProbeSmem), st, a, fill);
+  return hipGetLastError();
+}
+
+hipError_t launch_probe_kind(const ProbeArgs& a, int mode, int kind, bool first_wins, u64 fill, int grid, hipStream_t st) {
+  // contiguous partitions only (r_off / s_off, optional virtual-partition ends), every operand the mode touches present
+  if (a.r_cnt || a.s_cnt || a.s_ppi || a.item_list || !a.r_off || !a.s_off || !a.matched || mode < 0 || mode > 2 ||
+      kind < KIND_SEMI || kind > KIND_OUTER || (mode == 1 && !a.part_count) ||
+      (mode == 2 && (!a.part_out_off || !a.out_key || !a.out_sval || (kind == KIND_OUTER && !a.out_rval))))
+    return hipErrorInvalidValue;
+  if ((u64)grid > (u64)a.P * a.Q) grid = (int)((u64)a.P * a.Q);
+  if (grid < 1) grid = 1;
+#define HMJ_KIND_DISPATCH(M)                                                                  \
+  if (kind == KIND_SEMI) return launch_kind_t<M, KIND_SEMI, false>(a, fill, grid, st);        \
+  if (kind == KIND_ANTI) return launch_kind_t<M, KIND_ANTI, false>(a, fill, grid, st);        \
+  return first_wins ? launch_kind_t<M, KIND_OUTER, true>(a, fill, grid, st)                   \
+                    : launch_kind_t<M, KIND_OUTER, false>(a, fill, grid, st);
+  if (mode == 0) {
+    HMJ_KIND_DISPATCH(0)
+  } else if (mode == 1) {
+    HMJ_KIND_DISPATCH(1)
+  } else {
+    HMJ_KIND_DISPATCH(2)
+  }
+#undef HMJ_KIND_DISPATCH
+}
 
 hipError_t launch_scan_u64(const u64* in, u64* out_excl, u32 n, hipStream_t st) {
   hipLaunchKernelGGL(scan_u64_kernel, dim3(1), dim3(1024), 0, st, in, out_excl, n);

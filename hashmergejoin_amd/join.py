@@ -136,6 +136,35 @@ class Executor:
         self._check(self.L.hmj_join_u64_device(self.h, C.c_void_p(bp), nb, C.c_void_p(pp), np_, flags, C.byref(res)))
         return res
 
+    def join_kind_device(self, build, probe, kind, flags=0, outer_fill=0):
+        """Semi / anti / probe-side outer join (hmj_join_kind_u64_device; kind = HMJ_JOIN_*).  Returns (JoinResult,
+        {"n_probe_matched": .., "n_probe_unmatched": ..}).  SEMI / ANTI results have no rval column: read them with
+        `probe_rows_to_numpy`; PROBE_OUTER rows with `columns_to_numpy`.  HMJ_JOIN_INNER is join_device (counters 0)."""
+        self._sync_stream()
+        bp, nb = _dev_ptr(build)
+        pp, np_ = _dev_ptr(probe)
+        res = JoinResult()
+        opts = _lib.JoinOpts()
+        opts.struct_size = C.sizeof(_lib.JoinOpts)
+        opts.kind = int(kind)
+        opts.outer_fill = int(outer_fill) & 0xFFFFFFFFFFFFFFFF
+        self._check(self.L.hmj_join_kind_u64_device(self.h, C.c_void_p(bp), nb, C.c_void_p(pp), np_, flags, C.byref(opts),
+                                                    C.byref(res)))
+        return res, {"n_probe_matched": int(opts.n_probe_matched), "n_probe_unmatched": int(opts.n_probe_unmatched)}
+
+    def probe_rows_to_numpy(self, res):
+        """Copy a semi / anti join's device result out as an [n,2] uint64 array of (key, sval)."""
+        n = int(res.n_matches)
+        out = np.empty((n, 2), np.uint64)
+        if n == 0 or not res.key:
+            return out[:0]
+        torch = self._torch
+        tmp = torch.empty(n, dtype=torch.int64, device="cuda:%d" % self.device)
+        for c, ptr in enumerate((res.key, res.sval)):
+            _memcpy_d2d(torch, tmp, ptr, n * 8)
+            out[:, c] = tmp.cpu().numpy().view(np.uint64)
+        return out
+
     def prepare_build(self, build, n_probe_hint):
         """Partition the build side now; the next matching plain-count join_device skips that work."""
         self._sync_stream()

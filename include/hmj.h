@@ -282,6 +282,39 @@ const char* hmj_version(void);
 int hmj_join_u64_device(hmj_ctx* ctx, const void* build_aos_dev, uint64_t n_build,
                         const void* probe_aos_dev, uint64_t n_probe, uint32_t flags,
                         hmj_result* out);
+/* Join kinds other than the inner join: for each PROBE row, by whether its key occurs on the build side.
+ *   HMJ_JOIN_SEMI        each probe row with >= 1 build row of its key, once (EXISTS / IN (subquery));
+ *   HMJ_JOIN_ANTI        each probe row with no build row of its key (NOT EXISTS);
+ *   HMJ_JOIN_PROBE_OUTER the inner rows + one (key, outer_fill, sval) row per unmatched probe row.  With HMJ_FIRST_WINS and
+ *                        outer_fill = 0 this is, row by row, the reference's partitioned probe loop (hashjoin_bench.cc:92-96:
+ *                        r.second + s_tables[i][r.first], operator[] yielding 0 on a miss).
+ * Result columns: SEMI / ANTI produce key and sval (rval is NULL); PROBE_OUTER all three.  Row order is unspecified without
+ * HMJ_ORDERED; with it rows are sorted ascending by (key, rval, sval), or (key, sval) for SEMI / ANTI.
+ * Duplicate probe keys are independent rows.  Duplicate build keys: SEMI emits a probe row once however many partners it
+ * has; PROBE_OUTER pairs it with all of them (with the first only, under HMJ_FIRST_WINS); HMJ_FIRST_WINS does not change
+ * SEMI / ANTI.  n_matches = result rows; sum_r / sum_s and HMJ_CHECKSUM's tmix(key, rval, sval) are taken over result rows
+ * with rval = 0 for SEMI / ANTI rows and rval = outer_fill for unmatched outer rows; HMJ_SUM_PROBE is unchanged.
+ * n_build == 0: ANTI returns the whole probe side, PROBE_OUTER every probe row with the fill.
+ * kind == HMJ_JOIN_INNER: exactly hmj_join_u64_device (path, result, timing); the two counters are not filled.
+ * HMJ_E_ARG: NULL ctx / opts / out, opts->struct_size too small for kind and outer_fill, an unknown kind, more than 2^32-1
+ * rows.  HMJ_E_UNSUPPORTED wherever the inner ordered join returns it.  Like any other call it discards a prepared build
+ * side.  The planner takes only plans whose probe phase is the partition-by-partition walk (DESIGN.md "Join kinds"): no
+ * global / LDS table, one-pass slab walk, unique-key / sorted writes, rank forms, ordered expansion or key ranges, and no
+ * build partition is cut into build slices.  Nothing in the reference's operator corresponds (it has no join kinds).     */
+#define HMJ_JOIN_INNER 0u       /* = hmj_join_u64_device                                                  */
+#define HMJ_JOIN_SEMI 1u        /* each probe row with >= 1 build row of its key, once                     */
+#define HMJ_JOIN_ANTI 2u        /* each probe row with no build row of its key                             */
+#define HMJ_JOIN_PROBE_OUTER 3u /* inner rows + one (key, outer_fill, sval) row per unmatched probe row     */
+typedef struct {
+  uint32_t struct_size;       /* in: sizeof(hmj_join_opts) of the caller's header (size-versioned like hmj_plan_desc) */
+  uint32_t kind;              /* in: HMJ_JOIN_*                                                                      */
+  uint64_t outer_fill;        /* in: rval of an unmatched probe row; 0 = the reference's operator[] default          */
+  uint64_t n_probe_matched;   /* out: probe rows with >= 1 build partner (kinds other than INNER)                     */
+  uint64_t n_probe_unmatched; /* out: n_probe - n_probe_matched                                                      */
+} hmj_join_opts;
+int hmj_join_kind_u64_device(hmj_ctx* ctx, const void* build_aos_dev, uint64_t n_build,
+                             const void* probe_aos_dev, uint64_t n_probe, uint32_t flags,
+                             hmj_join_opts* opts, hmj_result* out);
 /* Partition the build side ahead of the join (e.g. while the probe side is still arriving over
  * xGMI).  One-shot: the NEXT hmj_join_u64_device on this ctx whose build pointer, row count and plan
  * match (count modes and materialising joins of relations of similar size plan alike; a join that plans

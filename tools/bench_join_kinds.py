@@ -1,0 +1,80 @@
+#!/usr/bin/env python3
+"""Time the join kinds (hmj_join_kind_u64_device) beside the inner join of the same relations, in the same process.
+
+One JSON line per (shape, kind, mode): median ms of >= --reps joins after --warmup (HIP events, hmj_last_timing.ms_total),
+the median phase split, the path bits, and the achieved GB/s of the probe phase against its algorithmic bytes
+(16 * (n_build + n_probe) read; materialising: + 16 B per result row for semi / anti, 24 B for inner / outer, written).
+Relations come from the device generators (hmj_gen_build / hmj_gen_probe), so every probe row but every miss_mod-th has
+exactly one build row.
+
+    python tools/bench_join_kinds.py [--reps 20] [--warmup 3] [--shapes 28x28m0,26x26m4,...]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SHAPES = "28x28m0,28x28m4,26x26m0,26x26m4,16x26m0"
+PHASES = ("ms_partition_build", "ms_partition_probe", "ms_probe_count", "ms_out_scan", "ms_probe_write", "ms_order")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--shapes", default=SHAPES)
+    a = ap.parse_args()
+    import torch
+
+    import hashmergejoin_amd as H
+
+    ex = H.Executor(0)
+    ex.set_profiling(True)
+    kinds = (("inner", H.HMJ_JOIN_INNER), ("semi", H.HMJ_JOIN_SEMI), ("anti", H.HMJ_JOIN_ANTI),
+             ("probe_outer", H.HMJ_JOIN_PROBE_OUTER))
+    modes = (("count", 0), ("materialize", H.HMJ_MATERIALIZE))
+    for shape in a.shapes.split(","):
+        lb, rest = shape.split("x")
+        lp, miss = rest.split("m")
+        nb, npb, miss = 1 << int(lb), 1 << int(lp), int(miss)
+        bd, pd = ex.gen_build(nb), ex.gen_probe(npb, nb, miss_mod=miss)
+        torch.cuda.synchronize()
+        inner_ms = {}
+        for mname, mflag in modes:
+            for kname, kind in kinds:
+                ts = []
+                for i in range(a.warmup + a.reps):
+                    r, cnt = ex.join_kind_device(bd, pd, kind, mflag)
+                    if i >= a.warmup:
+                        ts.append(ex.last_timing())
+                n_rows = int(r.n_matches)
+                ms = statistics.median(t["ms_total"] for t in ts)
+                ph = {k: round(statistics.median(t[k] for t in ts), 4) for k in PHASES}
+                if mflag:
+                    probe_ms = ph["ms_probe_count"] + ph["ms_out_scan"] + ph["ms_probe_write"]
+                    row_bytes = 16 if kind in (H.HMJ_JOIN_SEMI, H.HMJ_JOIN_ANTI) else 24
+                    probe_bytes = 16 * (nb + npb) + row_bytes * n_rows
+                else:
+                    probe_ms = ph["ms_probe_count"]
+                    probe_bytes = 16 * (nb + npb)
+                if kind == H.HMJ_JOIN_INNER:
+                    inner_ms[mname] = ms
+                line = {"shape": "2^%s x 2^%s" % (lb, lp), "miss_mod": miss, "kind": kname, "mode": mname,
+                        "ms_median": round(ms, 4), "x_inner": round(ms / inner_ms[mname], 3) if inner_ms.get(mname) else None,
+                        "n_rows": n_rows, "n_probe_matched": cnt["n_probe_matched"], "phases": ph,
+                        "path": hex(ts[-1]["path"]), "radix_bits": ts[-1]["radix_bits"],
+                        "probe_GBps": round(probe_bytes / (probe_ms * 1e6), 1) if probe_ms > 0 else None,
+                        "probe_bytes": probe_bytes, "reps": a.reps}
+                print(json.dumps(line), flush=True)
+        del bd, pd
+        ex.release_result()
+        torch.cuda.empty_cache()
+    ex.close()
+
+
+if __name__ == "__main__":
+    main()
