@@ -61,6 +61,17 @@ class JoinOpts(C.Structure):
                 ("n_probe_matched", C.c_uint64), ("n_probe_unmatched", C.c_uint64)]
 
 
+# hmj_build_join_opts.kind (hmj_join_build_kind_u64_device)
+HMJ_BUILD_SEMI, HMJ_BUILD_ANTI, HMJ_BUILD_OUTER, HMJ_FULL_OUTER = 1, 2, 3, 4
+
+
+class BuildJoinOpts(C.Structure):
+    """hmj_build_join_opts: the build-side kind and its fill values (in), matched / unmatched build and probe rows (out)."""
+    _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_uint32), ("build_fill", C.c_uint64), ("probe_fill", C.c_uint64),
+                ("n_build_matched", C.c_uint64), ("n_build_unmatched", C.c_uint64),
+                ("n_probe_matched", C.c_uint64), ("n_probe_unmatched", C.c_uint64)]
+
+
 class Timing(C.Structure):
     _fields_ = [("ms_total", C.c_float), ("ms_h2d", C.c_float), ("ms_d2h", C.c_float),
                 ("ms_partition_build", C.c_float), ("ms_partition_probe", C.c_float),
@@ -199,6 +210,8 @@ def load_library():
     L.hmj_join_u64_device.argtypes = [vp, vp, u, vp, u, C.c_uint32, C.POINTER(JoinResult)]
     L.hmj_join_kind_u64_device.restype = i
     L.hmj_join_kind_u64_device.argtypes = [vp, vp, u, vp, u, C.c_uint32, C.POINTER(JoinOpts), C.POINTER(JoinResult)]
+    L.hmj_join_build_kind_u64_device.restype = i
+    L.hmj_join_build_kind_u64_device.argtypes = [vp, vp, u, vp, u, C.c_uint32, C.POINTER(BuildJoinOpts), C.POINTER(JoinResult)]
     L.hmj_prepare_build_u64_device.restype = i
     L.hmj_prepare_build_u64_device.argtypes = [vp, vp, u, u]
     L.hmj_join_u64.restype = i

@@ -1191,25 +1191,54 @@ static int plan_join(hmj_ctx* c, const void* R, uint64_t n_build, const void* S,
   return HMJ_OK;
 }
 
+// join_kind of a build-side kind (hmj_join_build_kind_u64_device): kKindBuild + HMJ_BUILD_* (4 .. 7)
+constexpr uint32_t kKindBuild = 3;
+
 // The probe phase of a join kind (hmj_join_kind_u64_device): both relations partitioned (exact passes, probe-only split),
 // then probe_kind_kernel count [-> scan -> write -> order_rows].  `a` holds the partitions; the bitmap of probe row slots is
 // cleared before each pass, so that the count and the write pass emit the same rows.
+// Build-side kinds: the count pass of the walk also marks build rows (c->bmatched, cleared once here: the marks do not
+// depend on the pass), and build_sweep_kernel then counts / writes the build rows by their mark -- its rows of partition p
+// at the end of p's output, so the ordered epilogue sorts them with p's other rows.
 static int execute_kind_probe(hmj_ctx* c, hmj::ProbeArgs a, u32 nb, u32 np, uint32_t flags, hmj_result* out, bool to_host,
                               const u32* v_start, u32 P, u32 Q, u32 Pi, bool split, int low, bool win_ordered) {
   int rc;
   const bool materialize = flags & HMJ_MATERIALIZE, first = flags & HMJ_FIRST_WINS;
   const int kind = (int)c->join_kind;
+  const int bkind = kind > (int)kKindBuild ? kind - (int)kKindBuild : 0;  // HMJ_BUILD_*, 0 = a probe-side kind
+  const bool b_semi_anti = bkind == HMJ_BUILD_SEMI || bkind == HMJ_BUILD_ANTI;
   const u64 n_items = split ? Pi : (u64)P * Q;
   a.extra = (flags & (HMJ_CHECKSUM | HMJ_SUM_PROBE)) ? 1u : 0u;
   const size_t matched_bytes = ((size_t)np / 32 + 1) * 4;
   if ((rc = ensure_dev(c, c->matched, matched_bytes)) != HMJ_OK) return rc;
   a.matched = (u32*)c->matched.p;
   HIP_TRY(hipMemsetAsync(c->matched.p, 0, matched_bytes, c->stream));
+  u32* bmark = nullptr;
+  u64* sweep_n = nullptr;
+  hmj::ProbeArgs sw = a;  // the sweep's operands: a's, with the build bitmap as `matched`
+  const u64 b_fill = b_semi_anti ? 0 : c->build_fill;  // sval of a swept row
+  if (bkind) {
+    const size_t bmark_bytes = ((size_t)nb / 32 + 1) * 4;
+    if ((rc = ensure_dev(c, c->bmatched, bmark_bytes)) != HMJ_OK) return rc;
+    if ((rc = ensure_dev(c, c->bsweep, ((size_t)P + 1) * 8)) != HMJ_OK) return rc;
+    if ((rc = ensure_host(c, c->h_accum, 9 * sizeof(u64))) != HMJ_OK) return rc;
+    bmark = (u32*)c->bmatched.p;
+    sweep_n = (u64*)c->bsweep.p;
+    HIP_TRY(hipMemsetAsync(bmark, 0, bmark_bytes, c->stream));  // (every attempt: a retry partitions anew)
+    HIP_TRY(hipMemsetAsync(sweep_n, 0, 8, c->stream));
+    sw.matched = bmark;
+  }
   const int grid = hmj::probe_default_grid(c->num_cus);
   int s = span_begin(c, K_PROBE_COUNT, -1);
-  HIP_TRY(hmj::launch_probe_kind(a, materialize ? 1 : 0, kind, first, c->outer_fill, grid, c->stream));
+  if (bkind) {
+    HIP_TRY(hmj::launch_probe_build_kind(a, materialize ? 1 : 0, bkind, c->outer_fill, bmark, grid, c->stream));
+    HIP_TRY(hmj::launch_build_sweep(sw, (const u32*)c->r_off.p, P, v_start, sweep_n, materialize ? 1 : 0,
+                                    bkind == HMJ_BUILD_SEMI, b_fill, c->num_cus, c->stream));
+  } else {
+    HIP_TRY(hmj::launch_probe_kind(a, materialize ? 1 : 0, kind, first, c->outer_fill, grid, c->stream));
+  }
   span_end(c, s);
-  c->timing.bytes_probe_count = 16ull * ((u64)nb + np);
+  c->timing.bytes_probe_count = 16ull * ((u64)nb + np) + (bkind ? 16ull * nb + nb / 8 : 0);
   if (materialize) {
     s = span_begin(c, K_OUT_SCAN, -1);
     HIP_TRY(hmj::launch_scan_u64((const u64*)c->part_count.p, (u64*)c->part_out_off.p, (u32)n_items, c->stream));
@@ -1217,6 +1246,7 @@ static int execute_kind_probe(hmj_ctx* c, hmj::ProbeArgs a, u32 nb, u32 np, uint
   }
   u64* h = (u64*)c->h_accum.p;
   HIP_TRY(hipMemcpyAsync(h, c->accum.p, 8 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  if (bkind) HIP_TRY(hipMemcpyAsync(h + 8, sweep_n, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (h[hmj::ACC_ERR] & hmj::ERR_PREFIX) return kRetryNoPrefix;
   out->n_matches = h[hmj::ACC_N];
@@ -1226,21 +1256,34 @@ static int execute_kind_probe(hmj_ctx* c, hmj::ProbeArgs a, u32 nb, u32 np, uint
   out->mix_sum = h[hmj::ACC_MIX];
   out->sum_probe_all = (flags & HMJ_SUM_PROBE) ? h[hmj::ACC_SUM_P] : 0;
   c->kind_unmatched = h[hmj::ACC_PAD];  // rows emitted with the fill: the unmatched probe rows (ANTI, OUTER)
+  c->kind_build_swept = bkind ? h[8] : 0;
   if (!materialize || out->n_matches == 0) return HMJ_OK;
-  // semi / anti rows have no rval: 16 B per row, unless the ordered epilogue (which sorts three columns) needs zeros there
-  const bool rval_col = kind == HMJ_JOIN_PROBE_OUTER || (flags & HMJ_ORDERED);
+  // semi / anti rows have no rval: 16 B per row, unless the ordered epilogue (which sorts three columns) needs zeros there;
+  // build semi / anti rows have no sval, on the same terms
+  const bool rval_col = kind == HMJ_JOIN_PROBE_OUTER || bkind || (flags & HMJ_ORDERED);
+  const bool sval_col = !b_semi_anti || (flags & HMJ_ORDERED);
   const size_t bytes = (size_t)out->n_matches * 8;
   if ((rc = ensure_dev(c, c->out_key, bytes)) != HMJ_OK) return rc;
   if (rval_col && (rc = ensure_dev(c, c->out_rval, bytes)) != HMJ_OK) return rc;
-  if ((rc = ensure_dev(c, c->out_sval, bytes)) != HMJ_OK) return rc;
+  if (sval_col && (rc = ensure_dev(c, c->out_sval, bytes)) != HMJ_OK) return rc;
   a.out_key = (u64*)c->out_key.p;
   a.out_rval = rval_col ? (u64*)c->out_rval.p : nullptr;
-  a.out_sval = (u64*)c->out_sval.p;
+  a.out_sval = sval_col ? (u64*)c->out_sval.p : nullptr;
   HIP_TRY(hipMemsetAsync(c->matched.p, 0, matched_bytes, c->stream));
   s = span_begin(c, K_PROBE_WRITE, -1);
-  HIP_TRY(hmj::launch_probe_kind(a, 2, kind, first, c->outer_fill, grid, c->stream));
+  if (bkind) {
+    if (!b_semi_anti) HIP_TRY(hmj::launch_probe_build_kind(a, 2, bkind, c->outer_fill, nullptr, grid, c->stream));
+    sw.out_key = a.out_key;
+    sw.out_rval = a.out_rval;
+    sw.out_sval = a.out_sval;
+    HIP_TRY(hmj::launch_build_sweep(sw, (const u32*)c->r_off.p, P, v_start, sweep_n, 2, bkind == HMJ_BUILD_SEMI, b_fill,
+                                    c->num_cus, c->stream));
+  } else {
+    HIP_TRY(hmj::launch_probe_kind(a, 2, kind, first, c->outer_fill, grid, c->stream));
+  }
   span_end(c, s);
-  c->timing.bytes_probe_write = 16ull * ((u64)nb + np) + (kind == HMJ_JOIN_PROBE_OUTER ? 24ull : 16ull) * out->n_matches;
+  c->timing.bytes_probe_write = (b_semi_anti ? 0ull : 16ull * ((u64)nb + np)) + (bkind ? 16ull * nb + nb / 8 : 0) +
+                                (kind == HMJ_JOIN_PROBE_OUTER || (bkind && !b_semi_anti) ? 24ull : 16ull) * out->n_matches;
   const u64 *rk = a.out_key, *rr = a.out_rval, *rs = a.out_sval;
   if (flags & HMJ_ORDERED) {
     int retry = 0;
@@ -1249,21 +1292,22 @@ static int execute_kind_probe(hmj_ctx* c, hmj::ProbeArgs a, u32 nb, u32 np, uint
       return rc;
     if (retry) return retry;
   }
-  if (kind != HMJ_JOIN_PROBE_OUTER) rr = nullptr;
+  if (kind != HMJ_JOIN_PROBE_OUTER && !bkind) rr = nullptr;
+  if (b_semi_anti) rs = nullptr;
   if (to_host) {
     if ((rc = ensure_host(c, c->h_key, bytes, false)) != HMJ_OK) return rc;
     if (rr && (rc = ensure_host(c, c->h_rval, bytes, false)) != HMJ_OK) return rc;
-    if ((rc = ensure_host(c, c->h_sval, bytes, false)) != HMJ_OK) return rc;
+    if (rs && (rc = ensure_host(c, c->h_sval, bytes, false)) != HMJ_OK) return rc;
     s = span_begin(c, K_D2H, -1);
     HIP_TRY(hipMemcpyAsync(c->h_key.p, rk, bytes, hipMemcpyDeviceToHost, c->stream));
     if (rr) HIP_TRY(hipMemcpyAsync(c->h_rval.p, rr, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->h_sval.p, rs, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (rs) HIP_TRY(hipMemcpyAsync(c->h_sval.p, rs, bytes, hipMemcpyDeviceToHost, c->stream));
     span_end(c, s);
   }
   HIP_TRY(hipStreamSynchronize(c->stream));
   out->key = to_host ? (const uint64_t*)c->h_key.p : (const uint64_t*)rk;
   out->rval = rr ? (to_host ? (const uint64_t*)c->h_rval.p : (const uint64_t*)rr) : nullptr;
-  out->sval = to_host ? (const uint64_t*)c->h_sval.p : (const uint64_t*)rs;
+  out->sval = rs ? (to_host ? (const uint64_t*)c->h_sval.p : (const uint64_t*)rs) : nullptr;
   return HMJ_OK;
 }
 
@@ -3126,7 +3170,8 @@ void hmj_destroy(hmj_ctx* c) {
                     &c->part_out_off, &c->accum, &c->out_key, &c->out_rval, &c->out_sval,
                     &c->offs64, &c->irregular, &c->ord_key, &c->ord_rval, &c->ord_sval, &c->matched, &c->vparts,
                     &c->slab_a, &c->slab_br, &c->slab_bs, &c->cnt_a, &c->cnt_br, &c->cnt_bs, &c->lookback, &c->gtab, &c->piece_off,
-                    &c->split_r, &c->split_s, &c->split_off, &c->cat_key, &c->cat_rval, &c->cat_sval, &c->msd_off};
+                    &c->split_r, &c->split_s, &c->split_off, &c->cat_key, &c->cat_rval, &c->cat_sval, &c->msd_off,
+                    &c->bmatched, &c->bsweep};
   for (DevBuf* b : devs) free_dev(*b);
   HostBuf* hosts[] = {&c->h_accum, &c->h_key, &c->h_rval, &c->h_sval};
   for (HostBuf* b : hosts) free_host(*b);
@@ -3393,6 +3438,52 @@ int hmj_join_kind_u64_device(hmj_ctx* c, const void* build_aos_dev, uint64_t n_b
     const uint64_t unmatched = opts->kind == HMJ_JOIN_SEMI ? n_probe - out->n_matches : c->kind_unmatched;
     if (opts->struct_size >= offsetof(hmj_join_opts, n_probe_matched) + sizeof(uint64_t)) opts->n_probe_matched = n_probe - unmatched;
     if (opts->struct_size >= offsetof(hmj_join_opts, n_probe_unmatched) + sizeof(uint64_t)) opts->n_probe_unmatched = unmatched;
+  }
+  return rc;
+}
+
+int hmj_join_build_kind_u64_device(hmj_ctx* c, const void* build_aos_dev, uint64_t n_build, const void* probe_aos_dev,
+                                   uint64_t n_probe, uint32_t flags, hmj_build_join_opts* opts, hmj_result* out) {
+  if (!c) return HMJ_E_ARG;
+  if (!opts || !out) return fail(c, HMJ_E_ARG, "opts / out is NULL");
+  auto has = [&](size_t off, size_t size) { return opts->struct_size >= off + size; };
+  if (!has(offsetof(hmj_build_join_opts, kind), sizeof(opts->kind)))
+    return fail(c, HMJ_E_ARG, "hmj_build_join_opts.struct_size too small");
+  const uint32_t kind = opts->kind;
+  if (kind < HMJ_BUILD_SEMI || kind > HMJ_FULL_OUTER) return fail(c, HMJ_E_ARG, "unknown build join kind");
+  const bool outer = kind == HMJ_BUILD_OUTER || kind == HMJ_FULL_OUTER;
+  if ((outer && !has(offsetof(hmj_build_join_opts, build_fill), sizeof(opts->build_fill))) ||
+      (kind == HMJ_FULL_OUTER && !has(offsetof(hmj_build_join_opts, probe_fill), sizeof(opts->probe_fill))))
+    return fail(c, HMJ_E_ARG, "hmj_build_join_opts.struct_size too small");
+  if (outer && (flags & HMJ_FIRST_WINS))
+    return fail(c, HMJ_E_ARG, "HMJ_FIRST_WINS with an outer build kind (a non-first duplicate build row would be neither paired nor unmatched)");
+  if (n_build > 0xFFFFFFFFull || n_probe > 0xFFFFFFFFull) return fail(c, HMJ_E_ARG, "too many rows");
+  flags &= ~(uint32_t)HMJ_FIRST_WINS;  // (does not change build semi / anti)
+  HIP_TRY(hipSetDevice(c->device));
+  spans_reset(c);
+  c->prep.valid = false;  // like any other call, a build kind join discards a prepared build side
+  c->join_kind = kKindBuild + kind;
+  c->outer_fill = kind == HMJ_FULL_OUTER ? opts->probe_fill : 0;
+  c->build_fill = outer ? opts->build_fill : 0;
+  c->kind_unmatched = 0;
+  c->kind_build_swept = 0;
+  int st = span_begin(c, K_TOTAL, -1);
+  int rc = join_device(c, build_aos_dev, n_build, probe_aos_dev, n_probe, flags, out, false);
+  span_end(c, st);
+  c->join_kind = 0;
+  if (c->profiling) {
+    (void)hipStreamSynchronize(c->stream);
+    spans_collect(c);
+  }
+  if (rc == HMJ_OK) {
+    // the sweep emitted the matched build rows (BUILD_SEMI) or the unmatched ones (the others)
+    const uint64_t b_unmatched = kind == HMJ_BUILD_SEMI ? n_build - c->kind_build_swept : c->kind_build_swept;
+    const uint64_t p_unmatched = kind == HMJ_FULL_OUTER ? c->kind_unmatched : 0;
+    const uint64_t v[4] = {n_build - b_unmatched, b_unmatched, kind == HMJ_FULL_OUTER ? n_probe - p_unmatched : 0, p_unmatched};
+    const size_t off[4] = {offsetof(hmj_build_join_opts, n_build_matched), offsetof(hmj_build_join_opts, n_build_unmatched),
+                           offsetof(hmj_build_join_opts, n_probe_matched), offsetof(hmj_build_join_opts, n_probe_unmatched)};
+    for (int k = 0; k < 4; k++)
+      if (has(off[k], sizeof(uint64_t))) std::memcpy(reinterpret_cast<unsigned char*>(opts) + off[k], &v[k], sizeof(uint64_t));
   }
   return rc;
 }

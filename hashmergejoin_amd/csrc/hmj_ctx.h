@@ -105,7 +105,8 @@ struct hmj_ctx {
       out_key, out_rval, out_sval, ord_key, ord_rval, ord_sval, offs64, irregular, matched, vparts,
       slab_a, slab_br, slab_bs, cnt_a, cnt_br, cnt_bs, lookback, gtab, piece_off,
       split_r, split_s, split_off, cat_key, cat_rval, cat_sval,  // joins by key ranges: both relations cut, the appended result columns
-      msd_off;  // the rank forms' build-side sort: partition offsets of its one MSD pass
+      msd_off,  // the rank forms' build-side sort: partition offsets of its one MSD pass
+      bmatched, bsweep;  // build-side kinds: one bit per build row slot; the sweep's row counts ([0] all, [1 + p] partition p)
   HostBuf h_accum, h_key, h_rval, h_sval;
   int host_threads = 0;  // staging threads for pageable input (0 = default)
   std::vector<hipStream_t> up_streams;
@@ -134,6 +135,10 @@ struct hmj_ctx {
   uint32_t join_kind = 0;
   u64 outer_fill = 0;
   u64 kind_unmatched = 0;  // out: rows emitted with the fill by the last kind join (ANTI / OUTER)
+  // build-side kinds (hmj_join_build_kind_u64_device): join_kind = kKindBuild + HMJ_BUILD_*, the sval of an unmatched build
+  // row, and (out) the build rows the last one's sweep emitted
+  u64 build_fill = 0;
+  u64 kind_build_swept = 0;
   // placement of big allocations (ensure_dev, api.hip): candidates are probed with a fill and the fastest kept
   int place_tries = 4;     // candidates per allocation when a search runs (HMJ_PLACE=n); a fresh candidate of 6 GB costs 3-450 ms
   float place_budget_ms = 50.f;  // wall-clock budget of one buffer's search (HMJ_PLACE_BUDGET_MS)

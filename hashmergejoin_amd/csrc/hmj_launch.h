@@ -120,6 +120,18 @@ int probe_default_grid(int num_cus);
 // pass; accum[ACC_PAD] (+=) counts the rows emitted with `fill`.  Build slices are not allowed (r_end / s_end may only cut
 // probe rows).  Semi / anti rows carry no rval: a.out_rval may be NULL (else zeros are written).
 hipError_t launch_probe_kind(const ProbeArgs& a, int mode, int kind, bool first_wins, u64 fill, int grid, hipStream_t st);
+// build-side kinds (kind = HMJ_BUILD_* of hmj.h): the same walk.  Modes 0 / 1 also set, in bmark, the bit of every build
+// row slot whose key a probe row of the item met (bmark is OR-ed into: cleared once per join, not between passes).
+// Mode 2 writes the pairs (BUILD_OUTER) or the outer join's rows (FULL_OUTER, fill = rval of an unmatched probe row);
+// build semi / anti emit nothing from the walk and take no mode 2.  a.matched: the probe-row bitmap, as launch_probe_kind's.
+hipError_t launch_probe_build_kind(const ProbeArgs& a, int mode, int kind, u64 fill, u32* bmark, int grid, hipStream_t st);
+// ... and the sweep that emits build rows by their bit (a.matched = bmark here): set = rows with the bit set (build semi),
+// else the clear ones, as (key, rval, fill).  r_off: the P + 1 offsets of the real partitions; vstart: the split's
+// virtual-partition starts (NULL: items p * a.Q ..).  sweep_n: [0] += rows emitted (modes 0 / 1), [1 + p] = partition p's
+// rows (mode 1; mode 1 also adds them to part_count of p's last item, which mode 2 then fills from its end).  a.out_sval may
+// be NULL.  Counts and sums go to a.accum like the walk's.
+hipError_t launch_build_sweep(const ProbeArgs& a, const u32* r_off, u32 P, const u32* vstart, u64* sweep_n, int mode,
+                              bool set, u64 fill, int num_cus, hipStream_t st);
 hipError_t launch_probe_count_ext(const ProbeArgs& a, u32* irregular, u32* n_irregular, bool slab,
                                   int num_cus, hipStream_t st);
 hipError_t launch_probe_count_slab(const ProbeArgs& a, int num_cus, hipStream_t st);

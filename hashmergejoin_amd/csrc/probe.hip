@@ -509,13 +509,37 @@ __global__ __launch_bounds__(PB_THREADS, PB_THREADS / 256) void probe_kernel(Pro
 // row for row (the caller clears the bitmap between them).  Row j of an item is always handled by thread j % PB_THREADS,
 // so only the thread that owns a row tests or sets its bit.  a.extra bit 0: checksums.  accum[ACC_PAD] (MODE 0 / 1):
 // rows emitted with the fill.  Build slices are never given (every probe row must meet its whole build partition).
-constexpr int KIND_SEMI = 1, KIND_ANTI = 2, KIND_OUTER = 3;
-template <int MODE, int KIND, bool FIRST>
-__global__ __launch_bounds__(PB_THREADS, PB_THREADS / 256) void probe_kind_kernel(ProbeArgs a, u64 fill) {
-  constexpr bool LIST = KIND == KIND_OUTER && !FIRST;  // every build row of a key is paired
+//
+// Build-side kinds (hmj_join_build_kind_u64_device) walk the same way with MARK set (count modes only): every table slot a
+// probe row hits gets an LDS hit flag (placed behind ProbeSmem: the launch asks for PB_CAP more bytes), and once the item's
+// probe rows have passed a table, each build row of that table looks its key up and, if the key's slot was hit, sets its
+// bit in bmark (one bit per row slot of the partitioned build side, global atomics: with probe slices several workgroups
+// mark one partition).  Two more walk kinds serve them:
+//   MARK_ONLY: emits nothing (build semi / anti: the distinct-key table of the FIRST form);
+//   PAIRS    : the inner join's pairs -- OUTER's row lists without its unmatched probe rows (build outer).
+// The full outer join is OUTER (list form) with MARK.  Build rows are emitted afterwards by build_sweep_kernel.
+constexpr int KIND_SEMI = 1, KIND_ANTI = 2, KIND_OUTER = 3, KIND_MARK_ONLY = 4, KIND_PAIRS = 5;
+
+// OR a wave's 64 consecutive row bits (row g0 + lane <-> bit lane of hm) into bitmap bm: the rows need not start at a
+// word boundary, so they touch up to three words, one atomic each (lanes 0..2).
+__device__ __forceinline__ void mark_rows(u32* bm, u32 g0, u64 hm, int lane) {
+  if (hm == 0) return;
+  const u32 sh = g0 & 31;
+  u32 m = 0;
+  if (lane == 0) m = (u32)(hm << sh);
+  else if (lane == 1) m = (u32)(sh ? hm >> (32 - sh) : hm >> 32);
+  else if (lane == 2) m = sh ? (u32)(hm >> (64 - sh)) : 0u;
+  if (m) atomicOr(bm + (g0 >> 5) + lane, m);
+}
+
+template <int MODE, int KIND, bool FIRST, bool MARK = false>
+__global__ __launch_bounds__(PB_THREADS, PB_THREADS / 256) void probe_kind_kernel(ProbeArgs a, u64 fill, u32* __restrict__ bmark) {
+  constexpr bool LIST = (KIND == KIND_OUTER || KIND == KIND_PAIRS) && !FIRST;  // every build row of a key is paired
   constexpr bool PERSIST = !LIST;                      // rows with a key already in the table take no slot
+  static_assert(!MARK || MODE != 2, "build rows are marked in the count pass only");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   ProbeSmem& sm = *reinterpret_cast<ProbeSmem*>(smem_raw);
+  unsigned char* hitf = smem_raw + sizeof(ProbeSmem);  // MARK: one hit flag per table slot
   const Tup* __restrict__ R = static_cast<const Tup*>(a.R);
   const Tup* __restrict__ S = static_cast<const Tup*>(a.S);
   const int tid = threadIdx.x, lane = tid & 63;
@@ -556,10 +580,15 @@ __global__ __launch_bounds__(PB_THREADS, PB_THREADS / 256) void probe_kind_kerne
         first = NIL;
         fillrow = false;
         if (i != NIL) {
-          if (KIND == KIND_SEMI) {
+          if (MARK) hitf[i] = 1;  // (every writer stores 1)
+          if (KIND == KIND_MARK_ONLY) {
+          } else if (KIND == KIND_SEMI) {
             m = first_claim(a.matched, multi, row) ? 1u : 0u;
           } else if (KIND == KIND_ANTI) {
             if (multi) (void)first_claim(a.matched, true, row);
+          } else if (KIND == KIND_PAIRS) {
+            first = i;
+            for (u32 n = i; n != NIL; n = sm.aux[n]) m++;
           } else if (FIRST) {
             if (first_claim(a.matched, multi, row)) {
               m = 1;
@@ -570,7 +599,7 @@ __global__ __launch_bounds__(PB_THREADS, PB_THREADS / 256) void probe_kind_kerne
             first = i;
             for (u32 n = i; n != NIL; n = sm.aux[n]) m++;
           }
-        } else if (KIND != KIND_SEMI && !multi) {
+        } else if ((KIND == KIND_ANTI || KIND == KIND_OUTER) && !multi) {
           m = 1;
           fillrow = true;
         }
@@ -585,8 +614,11 @@ __global__ __launch_bounds__(PB_THREADS, PB_THREADS / 256) void probe_kind_kerne
       u32 c0 = 0;
       bool first_table = true;
       do {  // at least one (possibly empty) table
+        const u32 tab0 = c0;  // the table holds the partition's build rows tab0 .. c0
         __syncthreads();
         for (u32 i = tid; i < PB_NB; i += PB_THREADS) sm.head[i] = NIL;
+        if (MARK)
+          for (u32 i = tid; i < PB_CAP / 4; i += PB_THREADS) reinterpret_cast<u32*>(hitf)[i] = 0;
         if (tid == 0) sm.nslot = 0;
         __syncthreads();
         u32 used = 0;
@@ -725,11 +757,25 @@ __global__ __launch_bounds__(PB_THREADS, PB_THREADS / 256) void probe_kind_kerne
             run += tot;
           }
         }
+        if constexpr (MARK) {  // ---- the table's build rows whose key a probe row hit
+          __syncthreads();
+          for (u32 i0 = tab0; i0 < c0; i0 += PB_THREADS) {
+            const u32 pos = i0 + tid;
+            bool hit = false;
+            if (pos < c0) {
+              const u64 key = LIST ? sm.key[pos - tab0] : R[(u64)rb + pos].key;  // (list form: row pos is slot pos - tab0)
+              u32 i = sm.head[tab_hash(key)];
+              while (i != NIL && sm.key[i] != key) i = sm.next[i];
+              hit = i != NIL && hitf[i];
+            }
+            mark_rows(bmark, rb + i0 + (u32)(tid - lane), __ballot(hit), lane);
+          }
+        }
         first_table = false;
       } while (c0 < nb);
 
       // ---- several tables: the rows no table matched (ANTI, OUTER), by their clear bits
-      if (KIND != KIND_SEMI && multi) {
+      if ((KIND == KIND_ANTI || KIND == KIND_OUTER) && multi) {
         for (u32 j0 = 0; j0 < np; j0 += PB_THREADS) {
           const u32 j = j0 + tid, row = sb + j;
           u32 m = 0;
@@ -781,6 +827,128 @@ __global__ __launch_bounds__(PB_THREADS, PB_THREADS / 256) void probe_kind_kerne
     __syncthreads();
     const u64 v[6] = {acc_n, acc_r, acc_s, acc_x, acc_m, acc_p};  // ACC_N .. ACC_SUM_P order
     block_accumulate(sm.red, a.accum, v, 1u << ACC_XOR);
+  }
+}
+
+// ---- build-side kinds: the sweep that emits build rows by their mark ---------------------------------------------------
+// One workgroup per (real) partition p at a time: the build rows r_off[p] .. r_off[p + 1] -- every row slot exactly once,
+// however many items probed the partition -- stream by in 16-byte loads with their bits of a.matched (the build bitmap the
+// walk set), and a row whose bit equals SET is emitted as (key, rval, fill): SET for build semi, clear for build anti and
+// the outer kinds (fill = 0 for anti, the caller's build_fill for the outer kinds).
+//   MODE 0: counts and sums into the walk's accumulators; sweep_n[0] += rows emitted;
+//   MODE 1: also sweep_n[1 + p] = partition p's rows, added to the count of p's LAST item (part_count, after the walk wrote
+//           it): the scan then places them at the end of p's output, inside the segment the ordered epilogue sorts;
+//   MODE 2: rows written from part_out_off[last + 1] - sweep_n[1 + p] on, in row order (wave compaction: ballot + mbcnt,
+//           the waves' counts through LDS).
+// a.out_sval may be NULL (build semi / anti without HMJ_ORDERED: no sval column).  Items: p * a.Q .. + a.Q, or vstart[p] ..
+// vstart[p + 1] when partitions were split into virtual ones.  The prefix check (a.pfx_shift) covers every build row.
+constexpr int SW_THREADS = 256, SW_U = 4;  // rows per thread in flight
+template <int MODE, bool SET>
+__global__ __launch_bounds__(SW_THREADS) void build_sweep_kernel(ProbeArgs a, const u32* __restrict__ r_off, u32 P,
+                                                                 const u32* __restrict__ vstart, u64* __restrict__ sweep_n,
+                                                                 u64 fill) {
+  constexpr int NW = SW_THREADS / kWave;
+  __shared__ u32 wcnt[2][SW_U * NW];
+  __shared__ u64 red[8];
+  __shared__ u64 pc_s;
+  const Tup* __restrict__ R = static_cast<const Tup*>(a.R);
+  const u32* __restrict__ bm = a.matched;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const bool extra = a.extra & 1u;
+  u64 acc_n = 0, acc_r = 0, acc_s = 0, acc_x = 0, acc_m = 0;
+  bool pfx_bad = false;
+  int buf = 0;
+  if (MODE == 1 && tid == 0) pc_s = 0;
+  if (MODE == 1) __syncthreads();
+  for (u32 p = blockIdx.x; p < P; p += gridDim.x) {
+    const u64 rb = r_off[p], re = r_off[p + 1];
+    const u64 last = vstart ? (u64)vstart[p + 1] - 1 : ((u64)p + 1) * a.Q - 1;  // the partition's last item
+    u64 run = (MODE == 2) ? a.part_out_off[last + 1] - sweep_n[1 + p] : 0;
+    u64 pc = 0;
+    for (u64 i0 = rb; i0 < re; i0 += SW_THREADS * SW_U) {
+      Tup t[SW_U];
+      u32 bw[SW_U];
+      bool e[SW_U];
+#pragma unroll
+      for (int k = 0; k < SW_U; k++) {
+        const u64 i = i0 + k * SW_THREADS + tid;
+        bw[k] = 0;
+        if (i < re) {
+          t[k] = R[i];
+          bw[k] = bm[i >> 5];
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < SW_U; k++) {
+        const u64 i = i0 + k * SW_THREADS + tid;
+        e[k] = i < re && (((bw[k] >> (i & 31)) & 1u) != 0) == SET;
+        if (MODE != 2 && i < re && a.pfx_shift && (t[k].key >> a.pfx_shift) != a.pfx_val) pfx_bad = true;
+      }
+      if (MODE != 2) {
+#pragma unroll
+        for (int k = 0; k < SW_U; k++) {
+          if (e[k]) {
+            pc++;
+            acc_r += t[k].val;
+            acc_s += fill;
+            if (extra) {
+              const u64 m = tmix(t[k].key, t[k].val, fill);
+              acc_x ^= m;
+              acc_m += m;
+            }
+          }
+        }
+      } else {
+        u64 bal[SW_U];
+#pragma unroll
+        for (int k = 0; k < SW_U; k++) {
+          bal[k] = __ballot(e[k]);
+          if (lane == 0) wcnt[buf][k * NW + w] = (u32)__popcll(bal[k]);
+        }
+        // (double-buffered: a wave writes this half again two rounds later, after every wave passed the next barrier)
+        lds_barrier();
+        u32 base[SW_U], s = 0;
+#pragma unroll
+        for (int k = 0; k < SW_U; k++) {
+#pragma unroll
+          for (int ww = 0; ww < NW; ww++) {
+            if (ww == w) base[k] = s;
+            s += wcnt[buf][k * NW + ww];
+          }
+        }
+#pragma unroll
+        for (int k = 0; k < SW_U; k++) {
+          if (e[k]) {
+            const u64 o = run + base[k] + popc_below(bal[k]);
+            a.out_key[o] = t[k].key;
+            a.out_rval[o] = t[k].val;
+            if (a.out_sval) a.out_sval[o] = fill;
+          }
+        }
+        run += s;
+        buf ^= 1;
+      }
+    }
+    acc_n += pc;
+    if (MODE == 1) {
+      const u64 ws = wave_sum_u64(pc);
+      if (lane == 0 && ws) atomicAdd(&pc_s, ws);
+      __syncthreads();
+      if (tid == 0) {
+        sweep_n[1 + p] = pc_s;
+        if (pc_s) a.part_count[last] += pc_s;  // (the walk's count of that item is complete: it ran before)
+        pc_s = 0;
+      }
+      __syncthreads();
+    }
+  }
+  if (MODE != 2) {
+    if (__any(pfx_bad) && lane == 0) atomicOr(&a.accum[ACC_ERR], ERR_PREFIX);
+    if (tid < 8) red[tid] = 0;
+    __syncthreads();
+    const u64 v[6] = {acc_n, acc_r, acc_s, acc_x, acc_m, 0};  // ACC_N .. ACC_SUM_P order
+    block_accumulate(red, a.accum, v, 1u << ACC_XOR);
+    if (tid == 0 && red[0]) atomicAdd(&sweep_n[0], red[0]);
   }
 }
 
@@ -2744,7 +2912,7 @@ template <int MODE, int KIND, bool FIRST>
 static hipError_t launch_kind_t(const ProbeArgs& a, u64 fill, int grid, hipStream_t st) {
   static SmemAttrOnce attr_once;
   if (hipError_t e = ensure_max_smem(attr_once, reinterpret_cast<const void*>(probe_kind_kernel<MODE, KIND, FIRST>), (size_t)sizeof(ProbeSmem)); e != hipSuccess) return e;
-  hipLaunchKernelGGL((probe_kind_kernel<MODE, KIND, FIRST>), dim3(grid), dim3(PB_THREADS), sizeof(ProbeSmem), st, a, fill);
+  hipLaunchKernelGGL((probe_kind_kernel<MODE, KIND, FIRST>), dim3(grid), dim3(PB_THREADS), sizeof(ProbeSmem), st, a, fill, nullptr);
   return hipGetLastError();
 }
 
@@ -2769,6 +2937,65 @@ hipError_t launch_probe_kind(const ProbeArgs& a, int mode, int kind, bool first_
     HMJ_KIND_DISPATCH(2)
   }
 #undef HMJ_KIND_DISPATCH
+}
+
+template <int MODE, int KIND>
+static hipError_t launch_build_kind_t(const ProbeArgs& a, u64 fill, u32* bmark, int grid, hipStream_t st) {
+  // marking in the count modes (the write pass reuses the marks)
+  constexpr bool MARK = MODE != 2;
+  static SmemAttrOnce attr_once;
+  const size_t smem = sizeof(ProbeSmem) + (MARK ? PB_CAP : 0);  // + the hit flags of the marking walk
+  if (hipError_t e = ensure_max_smem(attr_once, reinterpret_cast<const void*>(probe_kind_kernel<MODE, KIND, false, MARK>), smem); e != hipSuccess) return e;
+  hipLaunchKernelGGL((probe_kind_kernel<MODE, KIND, false, MARK>), dim3(grid), dim3(PB_THREADS), smem, st, a, fill, bmark);
+  return hipGetLastError();
+}
+
+hipError_t launch_probe_build_kind(const ProbeArgs& a, int mode, int kind, u64 fill, u32* bmark, int grid, hipStream_t st) {
+  constexpr int B_SEMI = 1, B_ANTI = 2, B_OUTER = 3, B_FULL = 4;  // HMJ_BUILD_* of hmj.h
+  if (a.r_cnt || a.s_cnt || a.s_ppi || a.item_list || !a.r_off || !a.s_off || !a.matched || mode < 0 || mode > 2 ||
+      kind < B_SEMI || kind > B_FULL || (mode != 2 && !bmark) || (mode == 2 && kind <= B_ANTI) || (mode == 1 && !a.part_count) ||
+      (mode == 2 && (!a.part_out_off || !a.out_key || !a.out_rval || !a.out_sval)))
+    return hipErrorInvalidValue;
+  if (mode == 2 && kind == B_FULL) return launch_probe_kind(a, 2, KIND_OUTER, false, fill, grid, st);  // the outer join's rows
+  if ((u64)grid > (u64)a.P * a.Q) grid = (int)((u64)a.P * a.Q);
+  if (grid < 1) grid = 1;
+  if (mode == 2) return launch_build_kind_t<2, KIND_PAIRS>(a, fill, nullptr, grid, st);
+#define HMJ_BKIND_DISPATCH(M)                                                                   \
+  if (kind == B_SEMI || kind == B_ANTI) return launch_build_kind_t<M, KIND_MARK_ONLY>(a, fill, bmark, grid, st); \
+  if (kind == B_OUTER) return launch_build_kind_t<M, KIND_PAIRS>(a, fill, bmark, grid, st);    \
+  return launch_build_kind_t<M, KIND_OUTER>(a, fill, bmark, grid, st);
+  if (mode == 0) {
+    HMJ_BKIND_DISPATCH(0)
+  } else {
+    HMJ_BKIND_DISPATCH(1)
+  }
+#undef HMJ_BKIND_DISPATCH
+}
+
+template <int MODE, bool SET>
+static hipError_t launch_sweep_t(const ProbeArgs& a, const u32* r_off, u32 P, const u32* vstart, u64* sweep_n, u64 fill,
+                                 int grid, hipStream_t st) {
+  hipLaunchKernelGGL((build_sweep_kernel<MODE, SET>), dim3(grid), dim3(SW_THREADS), 0, st, a, r_off, P, vstart, sweep_n, fill);
+  return hipGetLastError();
+}
+
+hipError_t launch_build_sweep(const ProbeArgs& a, const u32* r_off, u32 P, const u32* vstart, u64* sweep_n, int mode,
+                              bool set, u64 fill, int num_cus, hipStream_t st) {
+  if (!r_off || !a.matched || !sweep_n || !a.accum || mode < 0 || mode > 2 || (!vstart && a.Q == 0) ||
+      (mode == 1 && !a.part_count) || (mode == 2 && (!a.part_out_off || !a.out_key || !a.out_rval)))
+    return hipErrorInvalidValue;
+  if (P == 0) return hipSuccess;
+  const int grid = (int)(P < (u32)num_cus * 8u ? P : (u32)num_cus * 8u);
+#define HMJ_SWEEP_DISPATCH(M) \
+  return set ? launch_sweep_t<M, true>(a, r_off, P, vstart, sweep_n, fill, grid, st) : launch_sweep_t<M, false>(a, r_off, P, vstart, sweep_n, fill, grid, st);
+  if (mode == 0) {
+    HMJ_SWEEP_DISPATCH(0)
+  } else if (mode == 1) {
+    HMJ_SWEEP_DISPATCH(1)
+  } else {
+    HMJ_SWEEP_DISPATCH(2)
+  }
+#undef HMJ_SWEEP_DISPATCH
 }
 
 hipError_t launch_scan_u64(const u64* in, u64* out_excl, u32 n, hipStream_t st) {

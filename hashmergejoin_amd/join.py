@@ -165,6 +165,38 @@ class Executor:
             out[:, c] = tmp.cpu().numpy().view(np.uint64)
         return out
 
+    def join_build_kind_device(self, build, probe, kind, flags=0, build_fill=0, probe_fill=0):
+        """Build-side semi / anti / outer join or the full outer join (hmj_join_build_kind_u64_device; kind = HMJ_BUILD_SEMI,
+        HMJ_BUILD_ANTI, HMJ_BUILD_OUTER or HMJ_FULL_OUTER).  Returns (JoinResult, {"n_build_matched", "n_build_unmatched",
+        "n_probe_matched", "n_probe_unmatched"}).  BUILD_SEMI / BUILD_ANTI results have no sval column: read them with
+        `build_rows_to_numpy`; the outer kinds' rows with `columns_to_numpy`."""
+        self._sync_stream()
+        bp, nb = _dev_ptr(build)
+        pp, np_ = _dev_ptr(probe)
+        res = JoinResult()
+        opts = _lib.BuildJoinOpts()
+        opts.struct_size = C.sizeof(_lib.BuildJoinOpts)
+        opts.kind = int(kind)
+        opts.build_fill = int(build_fill) & 0xFFFFFFFFFFFFFFFF
+        opts.probe_fill = int(probe_fill) & 0xFFFFFFFFFFFFFFFF
+        self._check(self.L.hmj_join_build_kind_u64_device(self.h, C.c_void_p(bp), nb, C.c_void_p(pp), np_, flags,
+                                                          C.byref(opts), C.byref(res)))
+        return res, {k: int(getattr(opts, k)) for k in ("n_build_matched", "n_build_unmatched", "n_probe_matched",
+                                                         "n_probe_unmatched")}
+
+    def build_rows_to_numpy(self, res):
+        """Copy a build semi / anti join's device result out as an [n,2] uint64 array of (key, rval)."""
+        n = int(res.n_matches)
+        out = np.empty((n, 2), np.uint64)
+        if n == 0 or not res.key:
+            return out[:0]
+        torch = self._torch
+        tmp = torch.empty(n, dtype=torch.int64, device="cuda:%d" % self.device)
+        for c, ptr in enumerate((res.key, res.rval)):
+            _memcpy_d2d(torch, tmp, ptr, n * 8)
+            out[:, c] = tmp.cpu().numpy().view(np.uint64)
+        return out
+
     def prepare_build(self, build, n_probe_hint):
         """Partition the build side now; the next matching plain-count join_device skips that work."""
         self._sync_stream()

@@ -315,6 +315,44 @@ typedef struct {
 int hmj_join_kind_u64_device(hmj_ctx* ctx, const void* build_aos_dev, uint64_t n_build,
                              const void* probe_aos_dev, uint64_t n_probe, uint32_t flags,
                              hmj_join_opts* opts, hmj_result* out);
+/* Join kinds that answer for each BUILD row whether its key occurs on the probe side, and the full outer join:
+ *   HMJ_BUILD_SEMI  each build row with >= 1 probe row of its key, once (right semi join);
+ *   HMJ_BUILD_ANTI  each build row with no probe row of its key (right anti join);
+ *   HMJ_BUILD_OUTER the inner rows + one (key, rval, build_fill) row per unmatched build row (right outer join);
+ *   HMJ_FULL_OUTER  the inner rows + one (key, probe_fill, sval) row per unmatched probe row + one (key, rval, build_fill)
+ *                   row per unmatched build row -- in one call, where composing it takes two joins.
+ * A build row is matched when its key occurs on the probe side; duplicate build rows are independent rows (each is emitted
+ * by BUILD_SEMI / BUILD_ANTI at most once, however many probe partners it has).  The pair rows of BUILD_OUTER / FULL_OUTER
+ * are exactly the inner join's: every probe row with every build row of its key.  HMJ_FIRST_WINS does not change
+ * BUILD_SEMI / BUILD_ANTI and is HMJ_E_ARG with the outer kinds (a non-first duplicate build row would be neither paired
+ * nor unmatched).  Result columns: BUILD_SEMI / BUILD_ANTI produce key and rval (sval is NULL); the outer kinds all three.
+ * Row order is unspecified without HMJ_ORDERED; with it rows are sorted ascending by (key, rval, sval), or (key, rval) for
+ * BUILD_SEMI / BUILD_ANTI.  n_matches = result rows; sum_r / sum_s and HMJ_CHECKSUM's tmix(key, rval, sval) are taken over
+ * result rows with sval = 0 for build semi / anti rows, sval = build_fill for unmatched build rows and rval = probe_fill for
+ * unmatched probe rows; HMJ_SUM_PROBE is unchanged.  n_probe == 0: BUILD_ANTI, BUILD_OUTER and FULL_OUTER return every
+ * build row; n_build == 0: FULL_OUTER returns every probe row with the fill.
+ * HMJ_E_ARG: NULL ctx / opts / out, opts->struct_size too small for the fields the kind reads, an unknown kind, more than
+ * 2^32-1 rows per side.  HMJ_E_UNSUPPORTED wherever the kind joins return it.  Like any other call it discards a prepared
+ * build side.  Plans as hmj_join_kind_u64_device's (DESIGN.md "Join kinds"): the probe walk marks, in one bit per build row,
+ * the rows whose key a probe row met, and a sweep over the partitioned build side emits build rows by that mark.       */
+#define HMJ_BUILD_SEMI 1u  /* each build row with >= 1 probe row of its key, once          -> (key, rval)          */
+#define HMJ_BUILD_ANTI 2u  /* each build row with no probe row of its key                   -> (key, rval)          */
+#define HMJ_BUILD_OUTER 3u /* inner rows + one (key, rval, build_fill) per unmatched build row                     */
+#define HMJ_FULL_OUTER 4u  /* inner rows + (key, probe_fill, sval) per unmatched probe row
+                                       + (key, rval, build_fill) per unmatched build row                         */
+typedef struct {
+  uint32_t struct_size;       /* in: sizeof(hmj_build_join_opts) of the caller's header (size-versioned like hmj_join_opts) */
+  uint32_t kind;              /* in: HMJ_BUILD_SEMI / _ANTI / _OUTER / HMJ_FULL_OUTER                                    */
+  uint64_t build_fill;        /* in: sval of an unmatched build row (BUILD_OUTER, FULL_OUTER)                            */
+  uint64_t probe_fill;        /* in: rval of an unmatched probe row (FULL_OUTER)                                         */
+  uint64_t n_build_matched;   /* out: build rows with >= 1 probe partner                                                 */
+  uint64_t n_build_unmatched; /* out: n_build - n_build_matched                                                          */
+  uint64_t n_probe_matched;   /* out: FULL_OUTER only (0 otherwise)                                                      */
+  uint64_t n_probe_unmatched; /* out: FULL_OUTER only (0 otherwise)                                                      */
+} hmj_build_join_opts;
+int hmj_join_build_kind_u64_device(hmj_ctx* ctx, const void* build_aos_dev, uint64_t n_build,
+                                   const void* probe_aos_dev, uint64_t n_probe, uint32_t flags,
+                                   hmj_build_join_opts* opts, hmj_result* out);
 /* Partition the build side ahead of the join (e.g. while the probe side is still arriving over
  * xGMI).  One-shot: the NEXT hmj_join_u64_device on this ctx whose build pointer, row count and plan
  * match (count modes and materialising joins of relations of similar size plan alike; a join that plans

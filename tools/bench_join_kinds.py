@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
-"""Time the join kinds (hmj_join_kind_u64_device) beside the inner join of the same relations, in the same process.
+"""Time the join kinds (hmj_join_kind_u64_device, and the build-side kinds of hmj_join_build_kind_u64_device) beside the
+inner join of the same relations, in the same process.
 
 One JSON line per (shape, kind, mode): median ms of >= --reps joins after --warmup (HIP events, hmj_last_timing.ms_total),
 the median phase split, the path bits, and the achieved GB/s of the probe phase against its algorithmic bytes
-(16 * (n_build + n_probe) read; materialising: + 16 B per result row for semi / anti, 24 B for inner / outer, written).
+(16 * (n_build + n_probe) read; materialising: + 16 B per result row for semi / anti, 24 B for inner / outer, written; the
+build-side kinds add the sweep's 16 * n_build + n_build / 8 per pass, and their write pass reads both sides again only where
+the walk writes rows -- build outer, full outer).
 Relations come from the device generators (hmj_gen_build / hmj_gen_probe), so every probe row but every miss_mod-th has
 exactly one build row.
 
-    python tools/bench_join_kinds.py [--reps 20] [--warmup 3] [--shapes 28x28m0,26x26m4,...]
+    python tools/bench_join_kinds.py [--reps 20] [--warmup 3] [--shapes 28x28m0,26x26m4,...] [--kinds full_outer,...]
 """
 import argparse
 import json
@@ -27,6 +30,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--shapes", default=SHAPES)
+    ap.add_argument("--kinds", default="", help="comma-separated kind names to time beside the inner join (default: all)")
     a = ap.parse_args()
     import torch
 
@@ -34,8 +38,13 @@ def main():
 
     ex = H.Executor(0)
     ex.set_profiling(True)
-    kinds = (("inner", H.HMJ_JOIN_INNER), ("semi", H.HMJ_JOIN_SEMI), ("anti", H.HMJ_JOIN_ANTI),
-             ("probe_outer", H.HMJ_JOIN_PROBE_OUTER))
+    # (name, kind, build-side kind): the build-side kinds go through hmj_join_build_kind_u64_device
+    kinds = (("inner", H.HMJ_JOIN_INNER, False), ("semi", H.HMJ_JOIN_SEMI, False), ("anti", H.HMJ_JOIN_ANTI, False),
+             ("probe_outer", H.HMJ_JOIN_PROBE_OUTER, False), ("build_semi", H.HMJ_BUILD_SEMI, True),
+             ("build_anti", H.HMJ_BUILD_ANTI, True), ("build_outer", H.HMJ_BUILD_OUTER, True),
+             ("full_outer", H.HMJ_FULL_OUTER, True))
+    if a.kinds:
+        kinds = tuple(k for k in kinds if k[0] in a.kinds.split(",") or k[0] == "inner")
     modes = (("count", 0), ("materialize", H.HMJ_MATERIALIZE))
     for shape in a.shapes.split(","):
         lb, rest = shape.split("x")
@@ -45,22 +54,31 @@ def main():
         torch.cuda.synchronize()
         inner_ms = {}
         for mname, mflag in modes:
-            for kname, kind in kinds:
+            for kname, kind, bkind in kinds:
                 ts = []
                 for i in range(a.warmup + a.reps):
-                    r, cnt = ex.join_kind_device(bd, pd, kind, mflag)
+                    if bkind:
+                        r, cnt = ex.join_build_kind_device(bd, pd, kind, mflag)
+                    else:
+                        r, cnt = ex.join_kind_device(bd, pd, kind, mflag)
                     if i >= a.warmup:
                         ts.append(ex.last_timing())
                 n_rows = int(r.n_matches)
                 ms = statistics.median(t["ms_total"] for t in ts)
                 ph = {k: round(statistics.median(t[k] for t in ts), 4) for k in PHASES}
+                # build-side kinds: + the sweep (16 B per build row + its bit), once per pass; build semi / anti
+                # need no walk in the write pass
+                sweep = (16 * nb + nb // 8) if bkind else 0
+                semi_anti = kind in ((H.HMJ_BUILD_SEMI, H.HMJ_BUILD_ANTI) if bkind else (H.HMJ_JOIN_SEMI, H.HMJ_JOIN_ANTI))
                 if mflag:
                     probe_ms = ph["ms_probe_count"] + ph["ms_out_scan"] + ph["ms_probe_write"]
-                    row_bytes = 16 if kind in (H.HMJ_JOIN_SEMI, H.HMJ_JOIN_ANTI) else 24
+                    row_bytes = 16 if semi_anti else 24
                     probe_bytes = 16 * (nb + npb) + row_bytes * n_rows
+                    if bkind:
+                        probe_bytes += 2 * sweep + (0 if semi_anti else 16 * (nb + npb))
                 else:
                     probe_ms = ph["ms_probe_count"]
-                    probe_bytes = 16 * (nb + npb)
+                    probe_bytes = 16 * (nb + npb) + sweep
                 if kind == H.HMJ_JOIN_INNER:
                     inner_ms[mname] = ms
                 line = {"shape": "2^%s x 2^%s" % (lb, lp), "miss_mod": miss, "kind": kname, "mode": mname,
