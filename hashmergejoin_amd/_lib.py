@@ -72,6 +72,25 @@ class BuildJoinOpts(C.Structure):
                 ("n_probe_matched", C.c_uint64), ("n_probe_unmatched", C.c_uint64)]
 
 
+# hmj_exchange_kind_opts.side (hmj_exchange_join_kind_u64_device)
+HMJ_KIND_PROBE_SIDE, HMJ_KIND_BUILD_SIDE = 0, 1
+
+
+class KindCounts(C.Structure):
+    """hmj_kind_counts: matched / unmatched probe and build rows of a join kind."""
+    _fields_ = [("n_probe_matched", C.c_uint64), ("n_probe_unmatched", C.c_uint64),
+                ("n_build_matched", C.c_uint64), ("n_build_unmatched", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class ExchangeKindOpts(C.Structure):
+    """hmj_exchange_kind_opts: side, kind and fill values (in), this rank's and the summed counters (out)."""
+    _fields_ = [("struct_size", C.c_uint32), ("side", C.c_uint32), ("kind", C.c_uint32), ("reserved", C.c_uint32),
+                ("probe_fill", C.c_uint64), ("build_fill", C.c_uint64), ("local", KindCounts), ("global", KindCounts)]
+
+
 class Timing(C.Structure):
     _fields_ = [("ms_total", C.c_float), ("ms_h2d", C.c_float), ("ms_d2h", C.c_float),
                 ("ms_partition_build", C.c_float), ("ms_partition_probe", C.c_float),
@@ -240,6 +259,9 @@ def load_library():
     L.hmj_comm_set_message_bytes.argtypes = [vp, u, u]
     L.hmj_exchange_join_u64_device.restype = i
     L.hmj_exchange_join_u64_device.argtypes = [vp, vp, u, vp, u, C.c_uint32, C.POINTER(JoinResult), C.POINTER(JoinResult)]
+    L.hmj_exchange_join_kind_u64_device.restype = i
+    L.hmj_exchange_join_kind_u64_device.argtypes = [vp, vp, u, vp, u, C.c_uint32, C.POINTER(ExchangeKindOpts), C.POINTER(JoinResult),
+                                                    C.POINTER(JoinResult)]
     L.hmj_owner_split_u64_device.restype = i
     L.hmj_owner_split_u64_device.argtypes = [vp, vp, u, i, _U64P, vp, vp]
     L.hmj_last_exchange_info.restype = i

@@ -3012,6 +3012,42 @@ int prepare_build(hmj_ctx* c, const void* R, uint64_t n_build, uint64_t n_probe_
   return rc;
 }
 
+int join_device_kind(hmj_ctx* c, const JoinKind& k, const void* R, uint64_t n_build, const void* S, uint64_t n_probe,
+                     uint32_t flags, hmj_result* out, hmj_kind_counts* counts) {
+  std::memset(counts, 0, sizeof(*counts));
+  if (k.side == HMJ_KIND_PROBE_SIDE && k.kind == HMJ_JOIN_INNER) return join_device(c, R, n_build, S, n_probe, flags, out, false);
+  const bool build_side = k.side == HMJ_KIND_BUILD_SIDE;
+  if (build_side) flags &= ~(uint32_t)HMJ_FIRST_WINS;  // (does not change build semi / anti; the outer kinds refuse it)
+  c->prep.valid = false;  // like any other call, a kind join discards a prepared build side
+  c->join_kind = build_side ? kKindBuild + k.kind : k.kind;
+  c->outer_fill = k.probe_fill;
+  c->build_fill = k.build_fill;
+  c->kind_unmatched = 0;
+  c->kind_build_swept = 0;
+  const int rc = join_device(c, R, n_build, S, n_probe, flags, out, false);
+  const u64 filled = c->kind_unmatched, swept = c->kind_build_swept;
+  c->join_kind = 0;
+  c->outer_fill = c->build_fill = 0;
+  c->kind_unmatched = c->kind_build_swept = 0;
+  if (rc != HMJ_OK) return rc;
+  if (!build_side) {
+    // SEMI emits the matched probe rows, ANTI / PROBE_OUTER fill the unmatched ones
+    const u64 unmatched = k.kind == HMJ_JOIN_SEMI ? n_probe - out->n_matches : filled;
+    counts->n_probe_matched = n_probe - unmatched;
+    counts->n_probe_unmatched = unmatched;
+  } else {
+    // the sweep emitted the matched build rows (BUILD_SEMI) or the unmatched ones (the others)
+    const u64 b_unmatched = k.kind == HMJ_BUILD_SEMI ? n_build - swept : swept;
+    counts->n_build_matched = n_build - b_unmatched;
+    counts->n_build_unmatched = b_unmatched;
+    if (k.kind == HMJ_FULL_OUTER) {
+      counts->n_probe_matched = n_probe - filled;
+      counts->n_probe_unmatched = filled;
+    }
+  }
+  return HMJ_OK;
+}
+
 }  // namespace hmj_host
 
 extern "C" {
@@ -3422,22 +3458,21 @@ int hmj_join_kind_u64_device(hmj_ctx* c, const void* build_aos_dev, uint64_t n_b
   if (n_build > 0xFFFFFFFFull || n_probe > 0xFFFFFFFFull) return fail(c, HMJ_E_ARG, "too many rows");
   HIP_TRY(hipSetDevice(c->device));
   spans_reset(c);
-  c->prep.valid = false;  // like any other call, a kind join discards a prepared build side
-  c->join_kind = opts->kind;
-  c->outer_fill = opts->outer_fill;
-  c->kind_unmatched = 0;
+  JoinKind jk;
+  jk.side = HMJ_KIND_PROBE_SIDE;
+  jk.kind = opts->kind;
+  jk.probe_fill = opts->outer_fill;
+  hmj_kind_counts cnt;
   int st = span_begin(c, K_TOTAL, -1);
-  int rc = join_device(c, build_aos_dev, n_build, probe_aos_dev, n_probe, flags, out, false);
+  int rc = join_device_kind(c, jk, build_aos_dev, n_build, probe_aos_dev, n_probe, flags, out, &cnt);
   span_end(c, st);
-  c->join_kind = 0;
   if (c->profiling) {
     (void)hipStreamSynchronize(c->stream);
     spans_collect(c);
   }
   if (rc == HMJ_OK) {
-    const uint64_t unmatched = opts->kind == HMJ_JOIN_SEMI ? n_probe - out->n_matches : c->kind_unmatched;
-    if (opts->struct_size >= offsetof(hmj_join_opts, n_probe_matched) + sizeof(uint64_t)) opts->n_probe_matched = n_probe - unmatched;
-    if (opts->struct_size >= offsetof(hmj_join_opts, n_probe_unmatched) + sizeof(uint64_t)) opts->n_probe_unmatched = unmatched;
+    if (opts->struct_size >= offsetof(hmj_join_opts, n_probe_matched) + sizeof(uint64_t)) opts->n_probe_matched = cnt.n_probe_matched;
+    if (opts->struct_size >= offsetof(hmj_join_opts, n_probe_unmatched) + sizeof(uint64_t)) opts->n_probe_unmatched = cnt.n_probe_unmatched;
   }
   return rc;
 }
@@ -3458,28 +3493,23 @@ int hmj_join_build_kind_u64_device(hmj_ctx* c, const void* build_aos_dev, uint64
   if (outer && (flags & HMJ_FIRST_WINS))
     return fail(c, HMJ_E_ARG, "HMJ_FIRST_WINS with an outer build kind (a non-first duplicate build row would be neither paired nor unmatched)");
   if (n_build > 0xFFFFFFFFull || n_probe > 0xFFFFFFFFull) return fail(c, HMJ_E_ARG, "too many rows");
-  flags &= ~(uint32_t)HMJ_FIRST_WINS;  // (does not change build semi / anti)
   HIP_TRY(hipSetDevice(c->device));
   spans_reset(c);
-  c->prep.valid = false;  // like any other call, a build kind join discards a prepared build side
-  c->join_kind = kKindBuild + kind;
-  c->outer_fill = kind == HMJ_FULL_OUTER ? opts->probe_fill : 0;
-  c->build_fill = outer ? opts->build_fill : 0;
-  c->kind_unmatched = 0;
-  c->kind_build_swept = 0;
+  JoinKind jk;
+  jk.side = HMJ_KIND_BUILD_SIDE;
+  jk.kind = kind;
+  jk.probe_fill = kind == HMJ_FULL_OUTER ? opts->probe_fill : 0;
+  jk.build_fill = outer ? opts->build_fill : 0;
+  hmj_kind_counts cnt;
   int st = span_begin(c, K_TOTAL, -1);
-  int rc = join_device(c, build_aos_dev, n_build, probe_aos_dev, n_probe, flags, out, false);
+  int rc = join_device_kind(c, jk, build_aos_dev, n_build, probe_aos_dev, n_probe, flags, out, &cnt);
   span_end(c, st);
-  c->join_kind = 0;
   if (c->profiling) {
     (void)hipStreamSynchronize(c->stream);
     spans_collect(c);
   }
   if (rc == HMJ_OK) {
-    // the sweep emitted the matched build rows (BUILD_SEMI) or the unmatched ones (the others)
-    const uint64_t b_unmatched = kind == HMJ_BUILD_SEMI ? n_build - c->kind_build_swept : c->kind_build_swept;
-    const uint64_t p_unmatched = kind == HMJ_FULL_OUTER ? c->kind_unmatched : 0;
-    const uint64_t v[4] = {n_build - b_unmatched, b_unmatched, kind == HMJ_FULL_OUTER ? n_probe - p_unmatched : 0, p_unmatched};
+    const uint64_t v[4] = {cnt.n_build_matched, cnt.n_build_unmatched, cnt.n_probe_matched, cnt.n_probe_unmatched};
     const size_t off[4] = {offsetof(hmj_build_join_opts, n_build_matched), offsetof(hmj_build_join_opts, n_build_unmatched),
                            offsetof(hmj_build_join_opts, n_probe_matched), offsetof(hmj_build_join_opts, n_probe_unmatched)};
     for (int k = 0; k < 4; k++)

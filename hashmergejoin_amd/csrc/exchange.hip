@@ -22,6 +22,7 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -906,6 +907,23 @@ void add_result(hmj_result* acc, const hmj_result& r) {
   acc->sum_probe_all += r.sum_probe_all;
 }
 
+void add_counts(hmj_kind_counts* acc, const hmj_kind_counts& k) {
+  acc->n_probe_matched += k.n_probe_matched;
+  acc->n_probe_unmatched += k.n_probe_unmatched;
+  acc->n_build_matched += k.n_build_matched;
+  acc->n_build_unmatched += k.n_build_unmatched;
+}
+
+// Join kinds in a key range where one relation has no rows: every row of the other is unmatched.  Does the kind emit
+// such probe rows (ANTI, PROBE_OUTER, FULL_OUTER) / such build rows (BUILD_ANTI, BUILD_OUTER, FULL_OUTER)?
+bool emits_lone_probe(const JoinKind& k) {
+  return k.side == HMJ_KIND_PROBE_SIDE ? k.kind == HMJ_JOIN_ANTI || k.kind == HMJ_JOIN_PROBE_OUTER : k.kind == HMJ_FULL_OUTER;
+}
+bool emits_lone_build(const JoinKind& k) { return k.side == HMJ_KIND_BUILD_SIDE && k.kind != HMJ_BUILD_SEMI; }
+// the counters a kind defines (hmj_kind_counts): probe rows for the probe-side kinds and FULL_OUTER, build rows for the build side
+bool counts_probe(const JoinKind& k) { return k.side == HMJ_KIND_PROBE_SIDE ? k.kind != HMJ_JOIN_INNER : k.kind == HMJ_FULL_OUTER; }
+bool counts_build(const JoinKind& k) { return k.side == HMJ_KIND_BUILD_SIDE; }
+
 float kernel_ms(const hmj_timing& t) {
   return t.ms_hist + t.ms_scan + t.ms_scatter + t.ms_offsets + t.ms_probe_count + t.ms_out_scan + t.ms_probe_write + t.ms_order;
 }
@@ -935,21 +953,29 @@ int ensure_round_events(hmj_ctx* c, size_t n) {
 }
 
 // The reduction over all ranks that ends every step; `mine`: this rank's pending error.  All ranks return together.
-int final_reduction(hmj_ctx* c, int mine, const hmj_result* local_out, hmj_result* global_out) {
+// Message: [0] status [1..6] the sums [7..10] the kind counters [11] (side, kind) -- ranks that disagree on the kind all
+// fail with HMJ_E_ARG (the same decision everywhere: every rank sees every word).
+constexpr int kReduceWords = 12;
+int final_reduction(hmj_ctx* c, int mine, const JoinKind& kind, const hmj_result* local_out, const hmj_kind_counts& local_cnt,
+                    hmj_result* global_out, hmj_kind_counts* global_cnt) {
   hmj_comm* m = c->comm;
-  const int G = m->n_ranks;
-  u64 w[7] = {mine == HMJ_OK ? 0ull : (u64)(int64_t)mine, local_out->n_matches, local_out->sum_r, local_out->sum_s,
-              local_out->xor_fold, local_out->mix_sum, local_out->sum_probe_all};
-  if (mine != HMJ_OK) std::memset(w + 1, 0, 6 * sizeof(u64));
-  std::vector<u64> all(7 * (size_t)G), st((size_t)G);
-  int rc = transport_allgather(c, w, all.data(), 7);
+  const int G = m->n_ranks, W = kReduceWords;
+  u64 w[kReduceWords] = {mine == HMJ_OK ? 0ull : (u64)(int64_t)mine, local_out->n_matches, local_out->sum_r, local_out->sum_s,
+                         local_out->xor_fold, local_out->mix_sum, local_out->sum_probe_all,
+                         local_cnt.n_probe_matched, local_cnt.n_probe_unmatched, local_cnt.n_build_matched, local_cnt.n_build_unmatched,
+                         ((u64)kind.side << 32) | kind.kind};
+  if (mine != HMJ_OK) std::memset(w + 1, 0, 10 * sizeof(u64));
+  std::vector<u64> all(W * (size_t)G), st((size_t)G);
+  int rc = transport_allgather(c, w, all.data(), W);
   if (rc != HMJ_OK) return mine != HMJ_OK ? mine : rc;
-  for (int g = 0; g < G; g++) st[g] = all[7 * (size_t)g];
+  for (int g = 0; g < G; g++)
+    if (all[W * (size_t)g + 11] != w[11]) return fail(c, HMJ_E_ARG, "the ranks passed different join kinds (side, kind)");
+  for (int g = 0; g < G; g++) st[g] = all[W * (size_t)g];
   if ((rc = settle(c, mine, st)) != HMJ_OK) return rc;
   if (global_out) {
     std::memset(global_out, 0, sizeof(*global_out));
     for (int g = 0; g < G; g++) {
-      const u64* p = &all[7 * (size_t)g + 1];
+      const u64* p = &all[W * (size_t)g + 1];
       global_out->n_matches += p[0];
       global_out->sum_r += p[1];
       global_out->sum_s += p[2];
@@ -957,6 +983,14 @@ int final_reduction(hmj_ctx* c, int mine, const hmj_result* local_out, hmj_resul
       global_out->mix_sum += p[4];
       global_out->sum_probe_all += p[5];
     }
+  }
+  std::memset(global_cnt, 0, sizeof(*global_cnt));
+  for (int g = 0; g < G; g++) {
+    const u64* p = &all[W * (size_t)g + 7];
+    global_cnt->n_probe_matched += p[0];
+    global_cnt->n_probe_unmatched += p[1];
+    global_cnt->n_build_matched += p[2];
+    global_cnt->n_build_unmatched += p[3];
   }
   return HMJ_OK;
 }
@@ -968,8 +1002,8 @@ float ms_since(std::chrono::steady_clock::time_point t) {
 // ---- digit path: the first radix pass is the owner --------------------------------------------------------
 // compute stream: pre-pass R | pre-pass S | join of round 0 | join of round 1 | ...
 // comm stream   :            | R rounds ..........| S round 0 | S round 1 | ...      (round = a range of digits)
-int exchange_digit_path(hmj_ctx* c, const void* R, u64 nb, const void* S, u64 np, u32 flags, const hmj_digit_plan& plan,
-                        hmj_result* local_out, int* err) {
+int exchange_digit_path(hmj_ctx* c, const void* R, u64 nb, const void* S, u64 np, u32 flags, const JoinKind& kind,
+                        const hmj_digit_plan& plan, hmj_result* local_out, hmj_kind_counts* local_cnt, int* err) {
   hmj_comm* m = c->comm;
   const int G = m->n_ranks, me = m->rank;
   const int ba = plan.digit_bits, low = plan.digit_low;
@@ -1109,6 +1143,7 @@ int exchange_digit_path(hmj_ctx* c, const void* R, u64 nb, const void* S, u64 np
   // right under them (the reference's recursion masks off consumed bits the same way, radix_hash.h:219-220).
   const auto t_local = std::chrono::steady_clock::now();
   std::memset(local_out, 0, sizeof(*local_out));
+  std::memset(local_cnt, 0, sizeof(*local_cnt));
   int lerr = HMJ_OK;
   // The waits for rows from other ranks are HOST waits under the step's deadline (a join cannot start before its rows
   // are there anyway): the compute stream never depends on a peer, so nothing this rank queues on it can block for ever.
@@ -1120,23 +1155,32 @@ int exchange_digit_path(hmj_ctx* c, const void* R, u64 nb, const void* S, u64 np
     lerr = wait_event(c, m->round_ev[r], "an exchange round (probe rows)");
     if (m->broken.load()) return lerr != HMJ_OK ? lerr : give_up(c, "an exchange round (probe rows)");
     if (lerr != HMJ_OK) break;
-    if (ns_ == 0) continue;                              // no probe rows: no result rows, no probe payloads
-    if (nr_ == 0 && !(flags & HMJ_SUM_PROBE)) continue;  // nothing can match (and no probe payload sum is asked for)
+    // A round is joined when it can give result rows or probe payloads: probe rows with build rows to meet (or
+    // HMJ_SUM_PROBE), or rows of one relation alone whose unmatched rows the kind emits.  A skipped round still counts:
+    // every row it has is unmatched.
+    const bool joined = ns_ > 0 ? nr_ > 0 || (flags & HMJ_SUM_PROBE) || emits_lone_probe(kind) : nr_ > 0 && emits_lone_build(kind);
+    if (!joined) {
+      if (counts_probe(kind)) local_cnt->n_probe_unmatched += ns_;
+      if (counts_build(kind)) local_cnt->n_build_unmatched += nr_;
+      continue;
+    }
     hmj_result res;
+    hmj_kind_counts cnt;
     spans_reset(c);
     // count modes: skip the bits the digit consumed (a round of several digits differs in them, which any
     // partition function may ignore); materialising joins (one round) let the planner sample the keys itself
     // (as a MINIMUM: the key sample of the round's join still runs, so sorted shards, hot keys and dense build keys
     //  keep their plans -- forcing prefix_bits switched the sample off)
     if (!materialize) c->min_prefix_bits = 64 - low;
-    const int rc = join_device(c, static_cast<const char*>(m->recv_r.p) + round_off_r[r] * 16, nr_,
-                               static_cast<const char*>(m->recv_s.p) + round_off_s[r] * 16, ns_, flags, &res, false);
+    const int rc = join_device_kind(c, kind, static_cast<const char*>(m->recv_r.p) + round_off_r[r] * 16, nr_,
+                                    static_cast<const char*>(m->recv_s.p) + round_off_s[r] * 16, ns_, flags, &res, &cnt);
     c->min_prefix_bits = 0;
     if (rc != HMJ_OK) {
       lerr = rc;
       break;
     }
     m->info.n_subjoins++;
+    add_counts(local_cnt, cnt);
     if (materialize)
       *local_out = res;  // (one round: the columns of this join)
     else
@@ -1170,7 +1214,8 @@ int exchange_digit_path(hmj_ctx* c, const void* R, u64 nb, const void* S, u64 np
 // ---- owner-split path: hash owner (fallback for keys the digit ranges cannot balance) or key-range owner
 // (HMJ_ORDERED): a separate stable split by owner, then ONE local join of everything this rank received.
 int exchange_owner_path(hmj_ctx* c, const void* build_shard_dev, u64 n_build, const void* probe_shard_dev, u64 n_probe,
-                        u32 flags, const hmj::OwnerFn& own, hmj_result* local_out, int* err) {
+                        u32 flags, const JoinKind& kind, const hmj::OwnerFn& own, hmj_result* local_out, hmj_kind_counts* local_cnt,
+                        int* err) {
   hmj_comm* m = c->comm;
   const int G = m->n_ranks, me = m->rank;
   int rc;
@@ -1301,12 +1346,15 @@ int exchange_owner_path(hmj_ctx* c, const void* build_shard_dev, u64 n_build, co
   spans_reset(c);
   c->sample_build_only = true;
   // count modes (checksums and first-wins included): the build side is partitioned while the probe rows are on
-  // the links -- the plan of a join does not depend on those flags, only materialising joins may plan differently
-  if (lerr == HMJ_OK && !(flags & HMJ_MATERIALIZE)) lerr = prepare_build(c, m->recv_r.p, nr, ns);
+  // the links -- the plan of a join does not depend on those flags, only materialising joins may plan differently.
+  // (Join kinds take no prepared build side: their exact passes partition it, then wait for the probe rounds.)
+  const bool inner = kind.side == HMJ_KIND_PROBE_SIDE && kind.kind == HMJ_JOIN_INNER;
+  if (lerr == HMJ_OK && !(flags & HMJ_MATERIALIZE) && inner) lerr = prepare_build(c, m->recv_r.p, nr, ns);
+  std::memset(local_cnt, 0, sizeof(*local_cnt));
   if (lerr == HMJ_OK) {
     c->arrive_rows.assign(round_end.begin(), round_end.end());
     c->arrive_ev.assign(m->round_ev.begin(), m->round_ev.begin() + rounds_s);
-    lerr = join_device(c, m->recv_r.p, nr, m->recv_s.p, ns, flags, local_out, false);
+    lerr = join_device_kind(c, kind, m->recv_r.p, nr, m->recv_s.p, ns, flags, local_out, local_cnt);
     if (lerr == HMJ_OK) m->info.n_subjoins = 1;
   }
   c->sample_build_only = false;
@@ -1330,13 +1378,11 @@ int exchange_owner_path(hmj_ctx* c, const void* build_shard_dev, u64 n_build, co
   return HMJ_OK;
 }
 
-}  // namespace
-
-extern "C" int hmj_exchange_join_u64_device(hmj_ctx* c, const void* build_shard_dev, uint64_t n_build, const void* probe_shard_dev,
-                                            uint64_t n_probe, uint32_t flags, hmj_result* local_out, hmj_result* global_out) {
-  if (!c) return HMJ_E_ARG;
-  // (argument errors every rank makes alike -- the same program runs everywhere -- return at once)
-  if (!local_out) return fail(c, HMJ_E_ARG, "local_out is NULL");
+// One step of the distributed join under a join kind (hmj_exchange_join_u64_device: HMJ_JOIN_INNER).  The arguments of
+// the kind were checked by the caller; local_cnt / global_cnt: the kind's counters (hmj_kind_counts).
+int exchange_join(hmj_ctx* c, const void* build_shard_dev, uint64_t n_build, const void* probe_shard_dev, uint64_t n_probe,
+                  uint32_t flags, const JoinKind& kind, hmj_result* local_out, hmj_result* global_out, hmj_kind_counts* local_cnt,
+                  hmj_kind_counts* global_cnt) {
   if (!c->comm) return fail(c, HMJ_E_ARG, "no communicator: call hmj_comm_init_rank or hmj_comm_set_transport first");
   HIP_TRY(hipSetDevice(c->device));
   hmj_comm* m = c->comm;
@@ -1349,6 +1395,8 @@ extern "C" int hmj_exchange_join_u64_device(hmj_ctx* c, const void* build_shard_
   if (flags & HMJ_ORDERED) flags |= HMJ_MATERIALIZE;
   std::memset(&m->info, 0, sizeof(m->info));
   std::memset(local_out, 0, sizeof(*local_out));
+  std::memset(local_cnt, 0, sizeof(*local_cnt));
+  std::memset(global_cnt, 0, sizeof(*global_cnt));
   m->info.n_ranks = G;
   const auto t_begin = std::chrono::steady_clock::now();
   // errors that depend on THIS rank's shard are carried to the next collective, where all ranks leave together
@@ -1360,7 +1408,7 @@ extern "C" int hmj_exchange_join_u64_device(hmj_ctx* c, const void* build_shard_
     // one rank owns every key: nothing to exchange, the step is the plain local join
     if (err != HMJ_OK) return err;
     spans_reset(c);
-    int rc = join_device(c, build_shard_dev, n_build, probe_shard_dev, n_probe, flags, local_out, false);
+    int rc = join_device_kind(c, kind, build_shard_dev, n_build, probe_shard_dev, n_probe, flags, local_out, local_cnt);
     if (c->profiling) {
       (void)hipStreamSynchronize(c->stream);
       spans_collect(c);
@@ -1374,6 +1422,7 @@ extern "C" int hmj_exchange_join_u64_device(hmj_ctx* c, const void* build_shard_
       *global_out = *local_out;
       global_out->key = global_out->rval = global_out->sval = nullptr;
     }
+    *global_cnt = *local_cnt;
     m->info.ms_total = m->info.ms_local = ms_since(t_begin);
     m->info.ms_exposed = c->profiling ? std::max(0.f, m->info.ms_total - m->info.ms_kernels) : 0.f;
     return HMJ_OK;
@@ -1396,7 +1445,7 @@ extern "C" int hmj_exchange_join_u64_device(hmj_ctx* c, const void* build_shard_
     std::sort(keys.begin(), keys.end());
     for (int i = 0; i + 1 < G; i++)
       own.spl[i] = keys.empty() ? ~0ull : keys[std::min(keys.size() - 1, keys.size() * (size_t)(i + 1) / (size_t)G)];
-    rc = exchange_owner_path(c, build_shard_dev, n_build, probe_shard_dev, n_probe, flags, own, local_out, &err);
+    rc = exchange_owner_path(c, build_shard_dev, n_build, probe_shard_dev, n_probe, flags, kind, own, local_out, local_cnt, &err);
   } else {
     // rounds: about target_round_bytes per message of the probe side (materialising joins: one round -- their
     // result columns are those of ONE local join)
@@ -1416,20 +1465,65 @@ extern "C" int hmj_exchange_join_u64_device(hmj_ctx* c, const void* build_shard_
     hmj_digit_plan plan;
     if (hmj_exchange_digit_plan(G, smp.keys.data(), smp.keys.size(), (u32)nr64, &plan) != HMJ_OK) return fail(c, HMJ_E_ARG, "digit plan");
     if (plan.usable && m->owner_path == HMJ_OWNER_DIGIT) {
-      rc = exchange_digit_path(c, build_shard_dev, n_build, probe_shard_dev, n_probe, flags, plan, local_out, &err);
+      rc = exchange_digit_path(c, build_shard_dev, n_build, probe_shard_dev, n_probe, flags, kind, plan, local_out, local_cnt, &err);
     } else {
       // a few clusters of keys: no contiguous digit ranges balance the ranks -- the hash owner spreads ANY key set
       own.mode = 1;
       m->info.fallback = plan.usable ? 0 : 1;  // (0: the caller asked for this path, hmj_comm_set_owner_path)
       m->info.sample_max_share = plan.max_share;
-      rc = exchange_owner_path(c, build_shard_dev, n_build, probe_shard_dev, n_probe, flags, own, local_out, &err);
+      rc = exchange_owner_path(c, build_shard_dev, n_build, probe_shard_dev, n_probe, flags, kind, own, local_out, local_cnt, &err);
     }
   }
   if (rc != HMJ_OK) return rc;
 
   // ---- 3. the reduction over all ranks (and the last point a failed local join is reported at)
-  rc = final_reduction(c, err, local_out, global_out);
+  rc = final_reduction(c, err, kind, local_out, *local_cnt, global_out, global_cnt);
   m->info.ms_total = ms_since(t_begin);
   m->info.ms_exposed = c->profiling ? std::max(0.f, m->info.ms_total - m->info.ms_kernels) : 0.f;
+  return rc;
+}
+
+}  // namespace
+
+extern "C" int hmj_exchange_join_u64_device(hmj_ctx* c, const void* build_shard_dev, uint64_t n_build, const void* probe_shard_dev,
+                                            uint64_t n_probe, uint32_t flags, hmj_result* local_out, hmj_result* global_out) {
+  if (!c) return HMJ_E_ARG;
+  // (argument errors every rank makes alike -- the same program runs everywhere -- return at once)
+  if (!local_out) return fail(c, HMJ_E_ARG, "local_out is NULL");
+  hmj_kind_counts lc, gc;
+  return exchange_join(c, build_shard_dev, n_build, probe_shard_dev, n_probe, flags, JoinKind(), local_out, global_out, &lc, &gc);
+}
+
+extern "C" int hmj_exchange_join_kind_u64_device(hmj_ctx* c, const void* build_shard_dev, uint64_t n_build,
+                                                 const void* probe_shard_dev, uint64_t n_probe, uint32_t flags,
+                                                 hmj_exchange_kind_opts* opts, hmj_result* local_out, hmj_result* global_out) {
+  if (!c) return HMJ_E_ARG;
+  // (argument errors every rank makes alike return at once, as for the inner join)
+  if (!opts || !local_out) return fail(c, HMJ_E_ARG, "opts / local_out is NULL");
+  auto has = [&](size_t off, size_t size) { return opts->struct_size >= off + size; };
+  if (!has(offsetof(hmj_exchange_kind_opts, kind), sizeof(opts->kind)))
+    return fail(c, HMJ_E_ARG, "hmj_exchange_kind_opts.struct_size too small");
+  JoinKind k;
+  k.side = opts->side;
+  k.kind = opts->kind;
+  const bool probe_side = k.side == HMJ_KIND_PROBE_SIDE, build_side = k.side == HMJ_KIND_BUILD_SIDE;
+  if (!probe_side && !build_side) return fail(c, HMJ_E_ARG, "unknown join kind side");
+  if ((probe_side && k.kind > HMJ_JOIN_PROBE_OUTER) || (build_side && (k.kind < HMJ_BUILD_SEMI || k.kind > HMJ_FULL_OUTER)))
+    return fail(c, HMJ_E_ARG, "unknown join kind");
+  const bool probe_fill = (probe_side && k.kind == HMJ_JOIN_PROBE_OUTER) || (build_side && k.kind == HMJ_FULL_OUTER);
+  const bool build_fill = build_side && (k.kind == HMJ_BUILD_OUTER || k.kind == HMJ_FULL_OUTER);
+  if ((probe_fill && !has(offsetof(hmj_exchange_kind_opts, probe_fill), sizeof(opts->probe_fill))) ||
+      (build_fill && !has(offsetof(hmj_exchange_kind_opts, build_fill), sizeof(opts->build_fill))))
+    return fail(c, HMJ_E_ARG, "hmj_exchange_kind_opts.struct_size too small");
+  if (build_fill && (flags & HMJ_FIRST_WINS))
+    return fail(c, HMJ_E_ARG, "HMJ_FIRST_WINS with an outer build kind (a non-first duplicate build row would be neither paired nor unmatched)");
+  k.probe_fill = probe_fill ? opts->probe_fill : 0;
+  k.build_fill = build_fill ? opts->build_fill : 0;
+  hmj_kind_counts lc, gc;
+  const int rc = exchange_join(c, build_shard_dev, n_build, probe_shard_dev, n_probe, flags, k, local_out, global_out, &lc, &gc);
+  if (rc == HMJ_OK) {
+    if (has(offsetof(hmj_exchange_kind_opts, local), sizeof(opts->local))) opts->local = lc;
+    if (has(offsetof(hmj_exchange_kind_opts, global), sizeof(opts->global))) opts->global = gc;
+  }
   return rc;
 }

@@ -131,7 +131,7 @@ struct hmj_ctx {
     int low = 0, B = 0;
   } prep;
   bool prepare_only = false;
-  // the join kind of the call in progress (HMJ_JOIN_*; 0 = inner), set only for the duration of hmj_join_kind_u64_device
+  // the join kind of the call in progress (HMJ_JOIN_*; 0 = inner), set only for the duration of join_device_kind
   uint32_t join_kind = 0;
   u64 outer_fill = 0;
   u64 kind_unmatched = 0;  // out: rows emitted with the fill by the last kind join (ANTI / OUTER)
@@ -248,6 +248,17 @@ void span_end(hmj_ctx* c, int id);
 // the whole local join (planning, retries) on device-resident relations
 int join_device(hmj_ctx* c, const void* R, uint64_t n_build, const void* S, uint64_t n_probe, uint32_t flags,
                 hmj_result* out, bool to_host);
+// A join kind: side HMJ_KIND_PROBE_SIDE (kind HMJ_JOIN_*) or HMJ_KIND_BUILD_SIDE (kind HMJ_BUILD_* / HMJ_FULL_OUTER), with the
+// fill values the kind's unmatched rows take (validated by the caller)
+struct JoinKind {
+  uint32_t side = HMJ_KIND_PROBE_SIDE, kind = HMJ_JOIN_INNER;
+  uint64_t probe_fill = 0, build_fill = 0;
+};
+// join_device under a join kind (the kind scope): sets the ctx's kind state, joins, reads the counters back and resets
+// the state on every return path.  HMJ_JOIN_INNER is join_device itself (counters 0).  `counts` as hmj_kind_counts
+// documents them for the kind; filled when HMJ_OK is returned.
+int join_device_kind(hmj_ctx* c, const JoinKind& k, const void* R, uint64_t n_build, const void* S, uint64_t n_probe,
+                     uint32_t flags, hmj_result* out, hmj_kind_counts* counts);
 // one stable radix pass src -> dst (histogram, scan, write-combining scatter); offsets_out: 2^bits + 1 bucket starts
 int radix_pass(hmj_ctx* c, const void* src, void* dst, hmj::u32 n, int shift, int bits, int rel, hmj::u64* offsets_out,
                int pass_index = 0);

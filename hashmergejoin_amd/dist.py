@@ -243,3 +243,11 @@ def distributed_join(ex, r_shard, s_shard, flags=0):
     Returns (local JoinResult for the keys this rank owns, global checks dict)."""
     loc, glob = ex.exchange_join(r_shard, s_shard, flags)
     return loc, glob.checks()
+
+
+def distributed_join_kind(ex, r_shard, s_shard, side, kind, flags=0, probe_fill=0, build_fill=0):
+    """distributed_join for a join kind (hmj_exchange_join_kind_u64_device): side = HMJ_KIND_PROBE_SIDE with an HMJ_JOIN_*
+    kind or HMJ_KIND_BUILD_SIDE with an HMJ_BUILD_* kind / HMJ_FULL_OUTER.  Returns (local JoinResult for the keys this rank
+    owns, global checks dict, {"local": counters, "global": counters})."""
+    loc, glob, counts = ex.exchange_join_kind(r_shard, s_shard, side, kind, flags, probe_fill=probe_fill, build_fill=build_fill)
+    return loc, glob.checks(), counts

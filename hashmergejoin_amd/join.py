@@ -293,6 +293,25 @@ class Executor:
                                                         C.byref(loc), C.byref(glob)))
         return loc, glob
 
+    def exchange_join_kind(self, build_shard, probe_shard, side, kind, flags=0, probe_fill=0, build_fill=0):
+        """Distributed join kind of row shards (collective; hmj_exchange_join_kind_u64_device).  side = HMJ_KIND_PROBE_SIDE
+        (kind HMJ_JOIN_*) or HMJ_KIND_BUILD_SIDE (kind HMJ_BUILD_* / HMJ_FULL_OUTER).  Returns (local JoinResult, global
+        JoinResult, {"local": counters, "global": counters}) with the counters of hmj_kind_counts.  The local columns are
+        read as those of the single-GPU kind: `probe_rows_to_numpy`, `build_rows_to_numpy` or `columns_to_numpy`."""
+        self._sync_stream()
+        bp, nb = _dev_ptr(build_shard)
+        pp, np_ = _dev_ptr(probe_shard)
+        loc, glob = JoinResult(), JoinResult()
+        opts = _lib.ExchangeKindOpts()
+        opts.struct_size = C.sizeof(_lib.ExchangeKindOpts)
+        opts.side = int(side)
+        opts.kind = int(kind)
+        opts.probe_fill = int(probe_fill) & 0xFFFFFFFFFFFFFFFF
+        opts.build_fill = int(build_fill) & 0xFFFFFFFFFFFFFFFF
+        self._check(self.L.hmj_exchange_join_kind_u64_device(self.h, C.c_void_p(bp), nb, C.c_void_p(pp), np_, flags,
+                                                             C.byref(opts), C.byref(loc), C.byref(glob)))
+        return loc, glob, {"local": opts.local.as_dict(), "global": getattr(opts, "global").as_dict()}
+
     def last_exchange_info(self):
         info = _lib.ExchangeInfo()
         self._check(self.L.hmj_last_exchange_info(self.h, C.byref(info)))

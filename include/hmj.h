@@ -353,6 +353,44 @@ typedef struct {
 int hmj_join_build_kind_u64_device(hmj_ctx* ctx, const void* build_aos_dev, uint64_t n_build,
                                    const void* probe_aos_dev, uint64_t n_probe, uint32_t flags,
                                    hmj_build_join_opts* opts, hmj_result* out);
+/* The join kinds of both families across ranks: the collective counterpart of the two entries above, on row shards as
+ * hmj_exchange_join_u64_device takes them (multi-GPU section below: communicator, owners, rounds, errors).
+ * opts->side selects the family: HMJ_KIND_PROBE_SIDE with kind HMJ_JOIN_INNER / _SEMI / _ANTI / _PROBE_OUTER, or
+ * HMJ_KIND_BUILD_SIDE with HMJ_BUILD_SEMI / _ANTI / _OUTER / HMJ_FULL_OUTER.  Each kind means what it means on one GPU --
+ * result columns, fill rules, sums and checksums over result rows, HMJ_SUM_PROBE, what an empty side returns -- with the
+ * relations being the union of every rank's shards.  The exchange gives every key's rows of both relations to one owner
+ * rank; each rank runs the single-GPU kind join on what it owns (per digit round of the digit-owner path, or once on the
+ * owner-split path), so a probe row without a partner in its own rank's build shard is answered against the whole build side.
+ *   local_out  this rank's rows and sums for the keys it owns (materialising flags: device columns owned by the ctx);
+ *   global_out (may be NULL) the sums over all ranks, columns NULL -- as for the inner exchange join;
+ *   opts->local / opts->global  the counters the single-GPU entry of the kind fills (probe counters for SEMI / ANTI /
+ *              PROBE_OUTER, build counters for the build kinds, both for FULL_OUTER), zeros where a kind defines none;
+ *              local over the rows this rank received, global summed over the ranks.
+ * HMJ_ORDERED: each rank's rows are sorted as on one GPU and, concatenated in rank order, are the global order (key-range
+ * owners).  HMJ_FIRST_WINS with PROBE_OUTER is global first-wins under the inner exchange join's rule: rank r's build
+ * shard precedes rank r+1's.  HMJ_KIND_PROBE_SIDE + HMJ_JOIN_INNER is exactly hmj_exchange_join_u64_device (counters 0).
+ * Collective: every rank passes the same flags, side and kind.  HMJ_E_ARG at once, on every rank alike: NULL ctx / opts /
+ * local_out, opts->struct_size too small for the fields the kind reads, an unknown side or kind, HMJ_FIRST_WINS with
+ * BUILD_OUTER or FULL_OUTER.  A rank's own errors travel to the final reduction and all ranks return together; ranks that
+ * disagree on (side, kind) all return HMJ_E_ARG there.                                                                  */
+#define HMJ_KIND_PROBE_SIDE 0u /* kind is HMJ_JOIN_INNER / _SEMI / _ANTI / _PROBE_OUTER                                  */
+#define HMJ_KIND_BUILD_SIDE 1u /* kind is HMJ_BUILD_SEMI / _ANTI / _OUTER or HMJ_FULL_OUTER                              */
+typedef struct {
+  uint64_t n_probe_matched, n_probe_unmatched, n_build_matched, n_build_unmatched;
+} hmj_kind_counts;
+typedef struct {
+  uint32_t struct_size;   /* in: sizeof(hmj_exchange_kind_opts) of the caller's header                                  */
+  uint32_t side;          /* in: HMJ_KIND_PROBE_SIDE / HMJ_KIND_BUILD_SIDE                                              */
+  uint32_t kind;          /* in: a kind of that side                                                                    */
+  uint32_t reserved;      /* in: 0                                                                                      */
+  uint64_t probe_fill;    /* in: rval of an unmatched probe row (PROBE_OUTER, FULL_OUTER)                               */
+  uint64_t build_fill;    /* in: sval of an unmatched build row (BUILD_OUTER, FULL_OUTER)                               */
+  hmj_kind_counts local;  /* out: over the rows this rank received (the keys it owns)                                   */
+  hmj_kind_counts global; /* out: summed over all ranks                                                                 */
+} hmj_exchange_kind_opts;
+int hmj_exchange_join_kind_u64_device(hmj_ctx* ctx, const void* build_shard_dev, uint64_t n_build_shard,
+                                      const void* probe_shard_dev, uint64_t n_probe_shard, uint32_t flags,
+                                      hmj_exchange_kind_opts* opts, hmj_result* local_out, hmj_result* global_out);
 /* Partition the build side ahead of the join (e.g. while the probe side is still arriving over
  * xGMI).  One-shot: the NEXT hmj_join_u64_device on this ctx whose build pointer, row count and plan
  * match (count modes and materialising joins of relations of similar size plan alike; a join that plans

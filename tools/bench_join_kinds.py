@@ -11,6 +11,12 @@ Relations come from the device generators (hmj_gen_build / hmj_gen_probe), so ev
 exactly one build row.
 
     python tools/bench_join_kinds.py [--reps 20] [--warmup 3] [--shapes 28x28m0,26x26m4,...] [--kinds full_outer,...]
+
+--exchange times the distributed form instead (hmj_exchange_join_kind_u64_device beside hmj_exchange_join_u64_device): one
+rank running the whole exchange path over RCCL self send/recv (dist.init_comm_single(ex, self_exchange=True), the route
+HMJ_FORCE_DIST=1 takes), count mode, default shapes 26x26m4,28x28m4.  One JSON line per (shape, kind): the median
+wall-clock ms of a step (the call is synchronous: it returns after the final reduction), the median summed kernel ms of
+its round joins (hmj_exchange_info.ms_kernels, profiling on), rounds and round joins.
 """
 import argparse
 import json
@@ -22,6 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 SHAPES = "28x28m0,28x28m4,26x26m0,26x26m4,16x26m0"
+EXCHANGE_SHAPES = "26x26m4,28x28m4"
 PHASES = ("ms_partition_build", "ms_partition_probe", "ms_probe_count", "ms_out_scan", "ms_probe_write", "ms_order")
 
 
@@ -31,7 +38,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--shapes", default=SHAPES)
     ap.add_argument("--kinds", default="", help="comma-separated kind names to time beside the inner join (default: all)")
+    ap.add_argument("--exchange", action="store_true", help="time the one-rank exchange path (RCCL self send/recv) instead")
     a = ap.parse_args()
+    if a.exchange:
+        return main_exchange(a)
     import torch
 
     import hashmergejoin_amd as H
@@ -90,6 +100,59 @@ def main():
                 print(json.dumps(line), flush=True)
         del bd, pd
         ex.release_result()
+        torch.cuda.empty_cache()
+    ex.close()
+
+
+def main_exchange(a):
+    import time
+
+    import torch
+
+    import hashmergejoin_amd as H
+    from hashmergejoin_amd import dist as hdist
+
+    ex = H.Executor(0)
+    hdist.init_comm_single(ex, self_exchange=True, timeout_s=120.0)
+    ex.set_profiling(True)
+    P, B = H.HMJ_KIND_PROBE_SIDE, H.HMJ_KIND_BUILD_SIDE
+    kinds = (("inner", P, H.HMJ_JOIN_INNER), ("semi", P, H.HMJ_JOIN_SEMI), ("anti", P, H.HMJ_JOIN_ANTI),
+             ("probe_outer", P, H.HMJ_JOIN_PROBE_OUTER), ("build_semi", B, H.HMJ_BUILD_SEMI), ("build_anti", B, H.HMJ_BUILD_ANTI),
+             ("build_outer", B, H.HMJ_BUILD_OUTER), ("full_outer", B, H.HMJ_FULL_OUTER))
+    if a.kinds:
+        kinds = tuple(k for k in kinds if k[0] in a.kinds.split(",") or k[0] == "inner")
+    shapes = a.shapes if a.shapes != SHAPES else EXCHANGE_SHAPES
+    for shape in shapes.split(","):
+        lb, rest = shape.split("x")
+        lp, miss = rest.split("m")
+        nb, npb, miss = 1 << int(lb), 1 << int(lp), int(miss)
+        bd, pd = ex.gen_build(nb), ex.gen_probe(npb, nb, miss_mod=miss)
+        torch.cuda.synchronize()
+        inner_ms = None
+        for kname, side, kind in kinds:
+            walls, infos = [], []
+            for i in range(a.warmup + a.reps):
+                t0 = time.perf_counter()
+                if kind == H.HMJ_JOIN_INNER and side == P:
+                    loc, glob = ex.exchange_join(bd, pd, 0)  # (the inner exchange step itself)
+                    cnt = {"global": {}}
+                else:
+                    loc, glob, cnt = ex.exchange_join_kind(bd, pd, side, kind, 0)
+                t1 = time.perf_counter()
+                if i >= a.warmup:
+                    walls.append((t1 - t0) * 1e3)
+                    infos.append(ex.last_exchange_info())
+            ms = statistics.median(walls)
+            if kname == "inner":
+                inner_ms = ms
+            line = {"exchange": "one rank, RCCL self send/recv", "shape": "2^%s x 2^%s" % (lb, lp), "miss_mod": miss,
+                    "kind": kname, "ms_median": round(ms, 3), "x_inner": round(ms / inner_ms, 3) if inner_ms else None,
+                    "ms_kernels_median": round(statistics.median(i["ms_kernels"] for i in infos), 3),
+                    "rounds": infos[-1]["rounds_probe"], "round_joins": infos[-1]["n_subjoins"],
+                    "owner_mode": infos[-1]["owner_mode"], "n_rows": int(glob.n_matches), "counts": cnt["global"],
+                    "reps": a.reps}
+            print(json.dumps(line), flush=True)
+        del bd, pd
         torch.cuda.empty_cache()
     ex.close()
 
