@@ -20,7 +20,9 @@
 // D4) goes to the GPU as is.  Any other hashable key type (std::string, the reference's KeyValVec)
 // is hashed on the host with std::hash<Key> -- as the reference does -- and joined on the GPU as
 // {hash, row index} rows.  The join itself always runs on the GPU: there is no CPU join path.
-// Errors (the reference has none: assert/UB) surface as std::runtime_error.
+// Errors (the reference has none: assert/UB) surface as std::runtime_error; an exception thrown by the caller's
+// std::hash, ==, < or payload copy on any host thread reaches the caller.  A copy of a join object is independent of its
+// source: it keeps its rows when the source is cleared, reassigned or destroyed.
 //
 // Semantics note: relational equi-join.  Identical to the reference for relations whose keys are
 // unique per relation (what its generator produces, strgen_test.cc:24-33); with duplicate keys
@@ -30,11 +32,13 @@
 #define HASHMERGEJOIN_HIP_HPP 1
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <exception>
 #include <functional>
 #include <iterator>
 #include <memory>
@@ -156,7 +160,10 @@ inline std::uint64_t* hash_scratch(std::size_t words, bool done = false) {
   }
   return buf.get();
 }
-// fn(begin, end) over [0, n) on up to `threads` host threads (the caller's thread takes the last share)
+// fn(begin, end) over [0, n) on up to `threads` host threads (the caller's thread takes the last share).  fn runs the
+// caller's code (std::hash, ==, <, payload copies), which may throw: every share catches, every thread is joined, and
+// then the exception of the lowest share that threw is rethrown on the caller's thread (as the reference's own threads
+// would let it propagate) instead of std::terminate ending the process.
 template <typename Fn>
 inline void parallel_ranges(std::size_t n, unsigned threads, Fn fn) {
   if (threads > 64) threads = 64;
@@ -165,14 +172,28 @@ inline void parallel_ranges(std::size_t n, unsigned threads, Fn fn) {
     return;
   }
   const std::size_t per = (n + threads - 1) / threads;
+  std::vector<std::exception_ptr> err(threads);
   std::vector<std::thread> th;
-  for (unsigned t = 0; t + 1 < threads; t++) {
-    const std::size_t b = (std::size_t)t * per, e = b + per < n ? b + per : n;
-    if (b < e) th.emplace_back(fn, b, e);
+  try {
+    for (unsigned t = 0; t + 1 < threads; t++) {
+      const std::size_t b = (std::size_t)t * per, e = b + per < n ? b + per : n;
+      if (b < e)
+        th.emplace_back([&fn, &err, t, b, e]() {
+          try {
+            fn(b, e);
+          } catch (...) {
+            err[t] = std::current_exception();
+          }
+        });
+    }
+    const std::size_t b = (std::size_t)(threads - 1) * per;
+    if (b < n) fn(b, n);
+  } catch (...) {  // the caller's share, or a thread that could not be started
+    err[threads - 1] = std::current_exception();
   }
-  const std::size_t b = (std::size_t)(threads - 1) * per;
-  if (b < n) fn(b, n);
   for (auto& x : th) x.join();
+  for (auto& e : err)
+    if (e) std::rethrow_exception(e);
 }
 
 template <typename Eq, typename Less>
@@ -180,7 +201,7 @@ inline void join_hashed_rows(const std::vector<std::pair<std::uint64_t, std::uin
                              const std::vector<std::pair<std::uint64_t, std::uint64_t>>& hs, unsigned num_threads,
                              Eq eq, Less less, std::vector<std::uint64_t>& ri, std::vector<std::uint64_t>& si) {
   hmj_ctx* c = thread_ctx();
-  hmj_set_host_threads(c, num_threads > 16 ? 16 : (int)num_threads);
+  check(c, hmj_set_host_threads(c, num_threads > 16 ? 16 : (int)num_threads), "hmj_set_host_threads");
   hmj_result res;
   hmj_rows* rows = nullptr;
   check(c, hmj_join_u64_rows(c, hr.empty() ? nullptr : hr.data(), hr.size(), hs.empty() ? nullptr : hs.data(),
@@ -193,21 +214,16 @@ inline void join_hashed_rows(const std::vector<std::pair<std::uint64_t, std::uin
   // The usual case -- no two different keys share a 64-bit hash, so every pair the GPU found is a pair of equal keys and no
   // hash value occurs twice among the results -- is verified on all host threads (each pair costs two cache misses into the
   // caller's relations: 10^6 pairs took 80 ms on one thread, configs[0]); then the GPU's columns ARE the answer.
-  bool simple = true;
-  {
-    std::vector<char> bad_flag(1, 0);
-    char* bad = bad_flag.data();
-    parallel_ranges(n, num_threads, [&, bad](std::size_t b, std::size_t e) {
-      bool any = false;
-      for (std::size_t k = b; k < e && !any; k++) {
-        if (!eq(res.rval[k], res.sval[k])) any = true;                 // a hash collision between different keys
-        if (k + 1 < n && res.key[k + 1] == res.key[k]) any = true;     // several result rows share a hash value
-      }
-      if (any) *bad = 1;  // (benign race: every writer stores the same value)
-    });
-    simple = *bad == 0;
-  }
-  if (simple) {
+  std::atomic<bool> bad(false);  // set by any thread (relaxed: the threads' joins order it before the read below)
+  parallel_ranges(n, num_threads, [&](std::size_t b, std::size_t e) {
+    bool any = false;
+    for (std::size_t k = b; k < e && !any; k++) {
+      if (!eq(res.rval[k], res.sval[k])) any = true;                 // a hash collision between different keys
+      if (k + 1 < n && res.key[k + 1] == res.key[k]) any = true;     // several result rows share a hash value
+    }
+    if (any) bad.store(true, std::memory_order_relaxed);
+  });
+  if (!bad.load(std::memory_order_relaxed)) {
     ri.assign(res.rval, res.rval + n);
     si.assign(res.sval, res.sval + n);
     return;
@@ -241,23 +257,19 @@ inline void join_hashed_rows(const std::vector<std::pair<std::uint64_t, std::uin
 
 // The same join for a caller that also wants something from every result pair (the string-key operator copies the
 // payloads): in the usual case -- no collision, no repeated hash -- the GPU's columns ARE the answer, so they are kept where
-// they are (pooled host memory, held by `rows`) instead of being copied into vectors, and visit(k, r_row, s_row) runs inside
-// the verification pass, on the thread that has just pulled both rows into its cache (a second pass over 10^6 pairs misses
-// the cache twice per pair again).  prep(n) is called once before the pass.  Otherwise the pairs end up in ri_own / si_own
-// as join_hashed_rows leaves them and `visited` is false: the caller walks them itself.
+// they are (pooled host memory, owned by the hmj_rows) instead of being copied into vectors, and visit(k, r_row, s_row) runs
+// inside the verification pass, on the thread that has just pulled both rows into its cache (a second pass over 10^6 pairs
+// misses the cache twice per pair again).  prep(n) is called once before the pass.  Otherwise the pairs end up in vectors
+// of their own as join_hashed_rows leaves them and `visited` is false: the caller walks them itself.
+// ri / si share ownership of whichever storage holds the indices, so a copy of a HashedJoin stays valid on its own.
 struct HashedJoin {
-  std::shared_ptr<hmj_rows> rows;
-  const std::uint64_t* ri = nullptr;
-  const std::uint64_t* si = nullptr;
+  std::shared_ptr<const std::uint64_t> ri, si;  // n matching row indices each (aliases of the hmj_rows or of the vectors)
   std::size_t n = 0;
-  std::vector<std::uint64_t> ri_own, si_own;
   bool visited = false;
   void clear() {
-    rows.reset();
-    ri = si = nullptr;
+    ri.reset();
+    si.reset();
     n = 0;
-    ri_own.clear();
-    si_own.clear();
     visited = false;
   }
 };
@@ -272,7 +284,7 @@ inline void join_hashed_rows_visit(const std::uint64_t* hr, std::size_t nr, cons
   out.clear();
   const auto tstart = std::chrono::steady_clock::now();
   hmj_ctx* c = thread_ctx();
-  hmj_set_host_threads(c, num_threads > 16 ? 16 : (int)num_threads);
+  check(c, hmj_set_host_threads(c, num_threads > 16 ? 16 : (int)num_threads), "hmj_set_host_threads");
   hmj_result res;
   hmj_rows* rows = nullptr;
   check(c, hmj_join_u64_rows(c, nr ? hr : nullptr, nr, ns ? hs : nullptr, ns, HMJ_MATERIALIZE | HMJ_ORDERED, &res, &rows),
@@ -283,9 +295,8 @@ inline void join_hashed_rows_visit(const std::uint64_t* hr, std::size_t nr, cons
   const auto tj = std::chrono::steady_clock::now();
   prep(n);
   const auto tp = std::chrono::steady_clock::now();
-  std::vector<char> bad_flag(1, 0);
-  char* bad = bad_flag.data();
-  parallel_ranges(n, num_threads, [&, bad](std::size_t b, std::size_t e) {
+  std::atomic<bool> bad(false);  // set by any thread (relaxed: the threads' joins order it before the read below)
+  parallel_ranges(n, num_threads, [&](std::size_t b, std::size_t e) {
     constexpr std::size_t kAhead = 12, kNear = 6;  // stage 0: the rows themselves; stage 1: what they point at (a string's characters)
     for (std::size_t k = b; k < e && k < b + kAhead; k++) touch(0, res.rval[k], res.sval[k]);
     for (std::size_t k = b; k < e && k < b + kNear; k++) touch(1, res.rval[k], res.sval[k]);
@@ -294,7 +305,7 @@ inline void join_hashed_rows_visit(const std::uint64_t* hr, std::size_t nr, cons
       if (k + kNear < e) touch(1, res.rval[k + kNear], res.sval[k + kNear]);
       const std::uint64_t r = res.rval[k], q = res.sval[k];
       if (!eq(r, q) || (k + 1 < n && res.key[k + 1] == res.key[k])) {  // a collision between different keys / a repeated hash
-        *bad = 1;  // (benign race: every writer stores the same value)
+        bad.store(true, std::memory_order_relaxed);
         return;
       }
       visit(k, r, q);
@@ -304,17 +315,18 @@ inline void join_hashed_rows_visit(const std::uint64_t* hr, std::size_t nr, cons
     std::fprintf(stderr, "[hmj drop-in] join of {hash,row} rows %.2f ms (from its start), result arrays %.2f ms, verify + visit %.2f ms\n",
                  std::chrono::duration<double, std::milli>(tj - tstart).count(), std::chrono::duration<double, std::milli>(tp - tj).count(),
                  std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp).count());
-  if (*bad == 0) {
-    out.rows = guard;
-    out.ri = res.rval;
-    out.si = res.sval;
+  if (!bad.load(std::memory_order_relaxed)) {
+    out.ri = std::shared_ptr<const std::uint64_t>(guard, res.rval);
+    out.si = std::shared_ptr<const std::uint64_t>(guard, res.sval);
     out.n = n;
     out.visited = true;
     return;
   }
   // (rare: the general walk of join_hashed_rows over the rows already here)
-  std::vector<std::uint64_t>& ri = out.ri_own;
-  std::vector<std::uint64_t>& si = out.si_own;
+  typedef std::pair<std::vector<std::uint64_t>, std::vector<std::uint64_t>> Indices;
+  const std::shared_ptr<Indices> own = std::make_shared<Indices>();
+  std::vector<std::uint64_t>& ri = own->first;
+  std::vector<std::uint64_t>& si = own->second;
   std::size_t i = 0;
   while (i < n) {
     std::size_t j = i + 1;
@@ -338,8 +350,8 @@ inline void join_hashed_rows_visit(const std::uint64_t* hr, std::size_t nr, cons
     }
     i = j;
   }
-  out.ri = ri.data();
-  out.si = si.data();
+  out.ri = std::shared_ptr<const std::uint64_t>(own, ri.data());
+  out.si = std::shared_ptr<const std::uint64_t>(own, si.data());
   out.n = ri.size();
 }
 }  // namespace hmj_detail
@@ -368,6 +380,11 @@ class HashMergeJoin<RIter, SIter, true> {
 
  public:
   HashMergeJoin() = default;
+  // Copies share the immutable result and stay valid when the source is cleared, reassigned or destroyed.  Declaring
+  // them leaves no implicit move: a move copies too, so a moved-from object still holds its rows instead of a row
+  // count without columns.
+  HashMergeJoin(const HashMergeJoin&) = default;
+  HashMergeJoin& operator=(const HashMergeJoin&) = default;
   // num_threads (hashjoin.h:58) sets the number of host threads that stage the relations for the
   // PCIe copy; the join itself runs on the GPU.
   HashMergeJoin(RIter r_begin, RIter r_end, SIter s_begin, SIter s_end, unsigned int num_threads = 1) {
@@ -376,7 +393,7 @@ class HashMergeJoin<RIter, SIter, true> {
     const void* r_ptr = hmj_detail::relation_rows(r_begin, (std::size_t)r_size, r_stage);
     const void* s_ptr = hmj_detail::relation_rows(s_begin, (std::size_t)s_size, s_stage);
     hmj_ctx* c = hmj_detail::thread_ctx();
-    hmj_set_host_threads(c, num_threads > 16 ? 16 : (int)num_threads);
+    hmj_detail::check(c, hmj_set_host_threads(c, num_threads > 16 ? 16 : (int)num_threads), "hmj_set_host_threads");
     hmj_result res;
     hmj_rows* rows = nullptr;
     hmj_detail::check(c, hmj_join_u64_rows(c, r_ptr, (uint64_t)r_size, s_ptr, (uint64_t)s_size,
@@ -466,6 +483,11 @@ class HashMergeJoin<RIter, SIter, false> {
 
  public:
   HashMergeJoin() = default;
+  // Copies share the immutable result and stay valid when the source is cleared, reassigned or destroyed.  Declaring
+  // them leaves no implicit move: a move copies too, so a moved-from object still holds its rows instead of a row
+  // count without columns.
+  HashMergeJoin(const HashMergeJoin&) = default;
+  HashMergeJoin& operator=(const HashMergeJoin&) = default;
   HashMergeJoin(RIter r_begin, RIter r_end, SIter s_begin, SIter s_end, unsigned int num_threads = 1)
       : _r(r_begin), _s(s_begin) {
     const std::size_t nr = (std::size_t)std::distance(r_begin, r_end), ns = (std::size_t)std::distance(s_begin, s_end);
@@ -528,10 +550,12 @@ class HashMergeJoin<RIter, SIter, false> {
     (void)hmj_detail::hash_scratch(0, true);
     if (!_j.visited) {  // (colliding or repeated hashes: the pairs were walked one by one; their payloads now)
       alloc(_j.n);
+      const std::uint64_t* const ri = _j.ri.get();
+      const std::uint64_t* const si = _j.si.get();
       hmj_detail::parallel_ranges(_j.n, num_threads, [&](std::size_t b, std::size_t e) {
         for (std::size_t k = b; k < e; k++) {
-          rv[k] = r_begin[_j.ri[k]].second;
-          sv[k] = s_begin[_j.si[k]].second;
+          rv[k] = r_begin[ri[k]].second;
+          sv[k] = s_begin[si[k]].second;
         }
       });
     }
@@ -553,7 +577,7 @@ class HashMergeJoin<RIter, SIter, false> {
     bool operator!=(iterator other) const { return _pos != other._pos; }
     std::tuple<Key*, RValue*, SValue*>& operator*() {
       // (the key's ADDRESS in the caller's relation -- nothing of the row is read unless the caller dereferences it)
-      const typename std::iterator_traits<RIter>::value_type& rr = _owner->_r[_owner->_j.ri[_pos]];
+      const typename std::iterator_traits<RIter>::value_type& rr = _owner->_r[_owner->_j.ri.get()[_pos]];
       tmp_val = std::make_tuple(const_cast<Key*>(&rr.first), _owner->_rv.get() + _pos, _owner->_sv.get() + _pos);
       return tmp_val;
     }
@@ -652,7 +676,7 @@ class HashMergeJoin2 {
   }
 
  public:
-  HashMergeJoin2() = default;
+  HashMergeJoin2() = default;  // (copies own their index vectors; a move leaves the source empty)
   HashMergeJoin2(RIter r_begin, RIter r_end, SIter s_begin, SIter s_end, unsigned int num_threads = 1)
       : _r(r_begin), _s(s_begin) {
     sort_in_place(r_begin, (std::size_t)std::distance(r_begin, r_end));  // hashjoin.h:234

@@ -14,6 +14,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "dropin_checks.h"
 #include "hashmergejoin_hip.hpp"
 #include "hmj_oracle.h"
 #include "strgen_restated.h"
@@ -228,7 +229,11 @@ static int run_string_repeats_case(uint64_t nr, uint64_t ns, uint64_t seed) {
       }
     }
   }
-  HashMergeJoin<StrKeyValVec::iterator, StrKeyValVec::iterator> hmj(r.begin(), r.end(), s.begin(), s.end(), 8);
+  // iterated through a copy whose source is gone: the pair-by-pair result must not live in the source
+  typedef HashMergeJoin<StrKeyValVec::iterator, StrKeyValVec::iterator> J;
+  J* src = new J(r.begin(), r.end(), s.begin(), s.end(), 8);
+  J hmj(*src);
+  delete src;
   uint64_t cnt = 0, sum = 0, prev_hash = 0;
   bool ok = true;
   for (auto tuple : hmj) {
@@ -247,6 +252,53 @@ static int run_string_repeats_case(uint64_t nr, uint64_t ns, uint64_t seed) {
                 (unsigned long long)ns, (unsigned long long)cnt, (unsigned long long)want_cnt, (unsigned long long)sum,
                 (unsigned long long)want_sum);
   return ok ? 0 : 1;
+}
+
+// ---- keys whose std::hash sends different keys to the same value (dropin_checks::ModKey: v % Mod): the operator drops the
+// pairs of different keys the GPU pairs up and orders each hash group by key.  Expected pairs by brute force
+// (dropin_checks.h); every copy / move / assignment of the join object is checked against them.
+template <unsigned Mod>
+static int run_colliding_case(uint64_t nr, uint64_t ns, unsigned threads) {
+  using namespace dropin_checks;
+  typedef std::vector<std::pair<ModKey<Mod>, uint64_t>> Rel;
+  Rel r(nr), s(ns);
+  const uint64_t dom = nr + nr / 2 + 1;
+  for (uint64_t i = 0; i < nr; i++) r[i] = std::make_pair(ModKey<Mod>{mix64(mix64(i + 5) % dom)}, 10 * i + 1);
+  for (uint64_t i = 0; i < ns; i++) s[i] = std::make_pair(ModKey<Mod>{mix64(mix64(i + 6) % dom)}, 10 * i + 2);
+  std::vector<ModKey<Mod>> rk, sk;
+  std::vector<uint64_t> rh;
+  for (const auto& row : r) rk.push_back(row.first), rh.push_back((uint64_t)std::hash<ModKey<Mod>>()(row.first));
+  for (const auto& row : s) sk.push_back(row.first);
+  const std::vector<RowPair> want = hashed_pairs(rk, rh, sk);
+  const Rel o_r = {{ModKey<Mod>{1}, 1}, {ModKey<Mod>{1 + Mod}, 2}}, o_s = {{ModKey<Mod>{1 + Mod}, 3}};
+  typedef HashMergeJoin<typename Rel::const_iterator, typename Rel::const_iterator> J;
+  const std::string what = "colliding keys (v % " + std::to_string(Mod) + ") " + std::to_string(nr) + "x" + std::to_string(ns);
+  const int fails = value_semantics<J>(
+      what.c_str(), [&]() { return J(r.cbegin(), r.cend(), s.cbegin(), s.cend(), threads); },
+      [&]() { return J(o_r.cbegin(), o_r.cend(), o_s.cbegin(), o_s.cend()); },
+      [&](J& j) {
+        return hashed_ok(j, want, [&](std::size_t i) { return &r[i].first; }, [&](std::size_t i) { return r[i].second; },
+                         [&](std::size_t q) { return s[q].second; });
+      });
+  std::printf("%s %s: %zu pairs\n", fails ? "FAIL" : "ok", what.c_str(), want.size());
+  return fails;
+}
+
+// ---- copies and assignments of a native join (uint64_t keys, duplicates on both sides)
+static int run_native_copies_case(uint64_t nr, uint64_t ns) {
+  using namespace dropin_checks;
+  KeyValVec r(nr), s(ns);
+  for (uint64_t i = 0; i < nr; i++) r[i] = std::make_pair(mix64(mix64(i + 1) % (nr / 3 + 1)), 1000 * i + 7);
+  for (uint64_t i = 0; i < ns; i++) s[i] = std::make_pair(mix64(mix64(i + 2) % (nr / 3 + 1)), 3 * i + 1);
+  const std::vector<Row3> want = native_rows(r.begin(), r.end(), s.begin(), s.end());
+  const KeyValVec o_r = {{5, 1}, {5, 2}, {6, 3}}, o_s = {{5, 9}, {6, 8}};
+  typedef HashMergeJoin<KeyValVec::const_iterator, KeyValVec::const_iterator> J;
+  const std::string what = "native join copies " + std::to_string(nr) + "x" + std::to_string(ns);
+  const int fails = value_semantics<J>(
+      what.c_str(), [&]() { return J(r.cbegin(), r.cend(), s.cbegin(), s.cend(), 2); },
+      [&]() { return J(o_r.cbegin(), o_r.cend(), o_s.cbegin(), o_s.cend()); }, [&](J& j) { return native_ok(j, want); });
+  std::printf("%s %s: %zu rows\n", fails ? "FAIL" : "ok", what.c_str(), want.size());
+  return fails;
 }
 
 // ---- the reference's benchmark relations themselves: r = create_strvec(n), s = create_strvec(n)
@@ -446,6 +498,9 @@ int main(int argc, char** argv) {
   fails += run_string_repeats_case(10, 100, 4);
   fails += run_string_repeats_case(3000, 20000, 5);
   fails += run_string_repeats_case(100000, 400000, 6);
+  fails += run_colliding_case<7>(1000, 900, 2);
+  fails += run_colliding_case<32749>(1 << 17, 1 << 17, 8);
+  fails += run_native_copies_case(1000, 1000);
   {
     const std::string words_path = argc > 1 ? argv[1] : "tests/golden/words.txt";
     const std::vector<std::string> words = hmj_strgen::load_words(words_path);
