@@ -91,6 +91,28 @@ class ExchangeKindOpts(C.Structure):
                 ("probe_fill", C.c_uint64), ("build_fill", C.c_uint64), ("local", KindCounts), ("global", KindCounts)]
 
 
+class StrRel(C.Structure):
+    """hmj_str_rel: a string-keyed relation on the device (Arrow large_string layout + payloads)."""
+    _fields_ = [("chars", C.c_void_p), ("offsets", C.c_void_p), ("vals", C.c_void_p), ("n", C.c_uint64)]
+
+
+class StrJoinOpts(C.Structure):
+    """hmj_str_join_opts: hash bits (in), pairs of equal hash, dropped collisions and phase times (out)."""
+    _fields_ = [("struct_size", C.c_uint32), ("hash_bits", C.c_uint32), ("n_hash_pairs", C.c_uint64),
+                ("n_collisions", C.c_uint64), ("ms_hash", C.c_float), ("ms_join", C.c_float), ("ms_verify", C.c_float),
+                ("ms_order", C.c_float)]
+
+
+class StrResult(C.Structure):
+    """hmj_str_result: counts and sums as JoinResult (tmix over (hash, rval, sval)); device columns with HMJ_MATERIALIZE."""
+    _fields_ = [("n_matches", C.c_uint64), ("sum_r", C.c_uint64), ("sum_s", C.c_uint64),
+                ("xor_fold", C.c_uint64), ("mix_sum", C.c_uint64), ("sum_probe_all", C.c_uint64),
+                ("hash", C.c_void_p), ("r_row", C.c_void_p), ("s_row", C.c_void_p), ("rval", C.c_void_p), ("sval", C.c_void_p)]
+
+    def checks(self):
+        return {k: int(getattr(self, k)) for k in ("n_matches", "sum_r", "sum_s", "xor_fold", "mix_sum")}
+
+
 class Timing(C.Structure):
     _fields_ = [("ms_total", C.c_float), ("ms_h2d", C.c_float), ("ms_d2h", C.c_float),
                 ("ms_partition_build", C.c_float), ("ms_partition_probe", C.c_float),
@@ -231,6 +253,11 @@ def load_library():
     L.hmj_join_kind_u64_device.argtypes = [vp, vp, u, vp, u, C.c_uint32, C.POINTER(JoinOpts), C.POINTER(JoinResult)]
     L.hmj_join_build_kind_u64_device.restype = i
     L.hmj_join_build_kind_u64_device.argtypes = [vp, vp, u, vp, u, C.c_uint32, C.POINTER(BuildJoinOpts), C.POINTER(JoinResult)]
+    L.hmj_hash_str_device.restype = i
+    L.hmj_hash_str_device.argtypes = [vp, vp, vp, u, C.c_uint32, vp]
+    L.hmj_join_str_device.restype = i
+    L.hmj_join_str_device.argtypes = [vp, C.POINTER(StrRel), C.POINTER(StrRel), C.c_uint32, C.POINTER(StrJoinOpts),
+                                      C.POINTER(StrResult)]
     L.hmj_prepare_build_u64_device.restype = i
     L.hmj_prepare_build_u64_device.argtypes = [vp, vp, u, u]
     L.hmj_join_u64.restype = i

@@ -2904,7 +2904,7 @@ int join_device(hmj_ctx* c, const void* R, uint64_t n_build, const void* S, uint
   }
   // the workload this call belongs to (a prepared build side: the join it was announced for) and what is known about it;
   // a join kind is a workload of its own (2 + kind): it never changes what inner joins of the same sizes have learnt
-  memo_for(c, workload_signature(n_build, c->prepare_only ? c->probe_hint : n_probe, flags, c->join_kind ? 2 + (int)c->join_kind : 0));
+  memo_for(c, workload_signature(n_build, c->prepare_only ? c->probe_hint : n_probe, flags, c->join_kind ? 2 + (int)c->join_kind : c->memo_kind));
   std::memset(&c->plan, 0, sizeof(c->plan));
   int rc = HMJ_OK, kr_h = 0;
   bool kr_done = false;
@@ -3207,7 +3207,8 @@ void hmj_destroy(hmj_ctx* c) {
                     &c->offs64, &c->irregular, &c->ord_key, &c->ord_rval, &c->ord_sval, &c->matched, &c->vparts,
                     &c->slab_a, &c->slab_br, &c->slab_bs, &c->cnt_a, &c->cnt_br, &c->cnt_bs, &c->lookback, &c->gtab, &c->piece_off,
                     &c->split_r, &c->split_s, &c->split_off, &c->cat_key, &c->cat_rval, &c->cat_sval, &c->msd_off,
-                    &c->bmatched, &c->bsweep};
+                    &c->bmatched, &c->bsweep, &c->str_rows_r, &c->str_rows_s, &c->str_flags, &c->str_blk, &c->str_blk_off,
+                    &c->str_hash, &c->str_rrow, &c->str_srow, &c->str_rval, &c->str_sval, &c->str_list, &c->str_runs, &c->str_acc};
   for (DevBuf* b : devs) free_dev(*b);
   HostBuf* hosts[] = {&c->h_accum, &c->h_key, &c->h_rval, &c->h_sval};
   for (HostBuf* b : hosts) free_host(*b);
@@ -3215,6 +3216,8 @@ void hmj_destroy(hmj_ctx* c) {
     if (e) (void)hipEventDestroy(e);
   for (auto& e : c->up_events) (void)hipEventDestroy(e);
   for (auto& e : c->place_ev)
+    if (e) (void)hipEventDestroy(e);
+  for (auto& e : c->str_ev)
     if (e) (void)hipEventDestroy(e);
   for (auto& st : c->up_streams) (void)hipStreamDestroy(st);
   for (auto& e : c->copy_ev) (void)hipEventDestroy(e);
@@ -3675,6 +3678,8 @@ void hmj_release_result(hmj_ctx* c) {
   free_dev(c->ord_key);
   free_dev(c->ord_rval);
   free_dev(c->ord_sval);
+  DevBuf* str_cols[5] = {&c->str_hash, &c->str_rrow, &c->str_srow, &c->str_rval, &c->str_sval};
+  for (DevBuf* b : str_cols) free_dev(*b);
   free_host(c->h_key);
   free_host(c->h_rval);
   free_host(c->h_sval);

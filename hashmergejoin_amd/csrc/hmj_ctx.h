@@ -106,7 +106,13 @@ struct hmj_ctx {
       slab_a, slab_br, slab_bs, cnt_a, cnt_br, cnt_bs, lookback, gtab, piece_off,
       split_r, split_s, split_off, cat_key, cat_rval, cat_sval,  // joins by key ranges: both relations cut, the appended result columns
       msd_off,  // the rank forms' build-side sort: partition offsets of its one MSD pass
-      bmatched, bsweep;  // build-side kinds: one bit per build row slot; the sweep's row counts ([0] all, [1 + p] partition p)
+      bmatched, bsweep,  // build-side kinds: one bit per build row slot; the sweep's row counts ([0] all, [1 + p] partition p)
+      // string joins (strjoin.hip): {hash, row} rows of both relations, pass-1 ballots, per-workgroup survivors and their
+      // offsets, the five result columns, the collision search's rows and runs, its counters
+      str_rows_r, str_rows_s, str_flags, str_blk, str_blk_off, str_hash, str_rrow, str_srow, str_rval, str_sval, str_list,
+      str_runs, str_acc;
+  hipEvent_t str_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // string joins' phase boundaries (profiling)
+  int memo_kind = 0;  // workload-signature kind of plain inner joins run on behalf of another entry (string joins)
   HostBuf h_accum, h_key, h_rval, h_sval;
   int host_threads = 0;  // staging threads for pageable input (0 = default)
   std::vector<hipStream_t> up_streams;

@@ -1,0 +1,618 @@
+// String-key join on the device (hmj_hash_str_device, hmj_join_str_device; include/hmj.h).  The reference joins
+// std::string keys through the same operator template (hashjoin.h:29 KeyValVec, hashjoin_bench.cc:109-143): it orders
+// rows by std::hash of the key and breaks ties on the key (radix_hash.h:86-109).  Here:
+//   1. str_hash_kernel   libstdc++'s _Hash_bytes of every key -> {hash, row} rows (16 bytes, what the u64 join takes);
+//                        a wave's 64 keys are one contiguous byte span, staged in LDS with 16-byte loads;
+//   2. the u64 join      join_device on those rows, HMJ_MATERIALIZE (+ HMJ_ORDERED): pairs of equal hash (hash, r_row, s_row);
+//   3. str_verify_*      one lane per pair: lengths, then bytes, 8 at a time; survivors compacted (stable) with their
+//                        payloads, or only counted / summed in the count modes;
+//   4. collision order   ordered joins only: runs of equal hash whose build keys differ are sorted by key bytes in one
+//                        workgroup each (a run beyond kRunCap rows is HMJ_E_UNSUPPORTED).
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <cstring>
+
+#include "hmj_ctx.h"
+
+using hmj::u32;
+using hmj::u64;
+using namespace hmj_host;
+
+namespace {
+
+#define HIP_TRY(expr)                                           \
+  do {                                                          \
+    hipError_t _e = (expr);                                     \
+    if (_e != hipSuccess) return fail(c, HMJ_E_HIP, #expr, _e); \
+  } while (0)
+
+constexpr u64 kMul = 0xc6a4a7935bd1e995ull;
+constexpr u64 kSeed = 0xc70f6907ull;
+constexpr int SH_THREADS = 256;
+constexpr int SH_WAVES = SH_THREADS / 64;
+constexpr int SH_STAGE = 4096;  // LDS bytes a wave stages its 64 keys in; a longer span: per-lane reads from global memory
+constexpr int SV_THREADS = 256;
+constexpr int kRunCap = 1024;  // rows of one mixed run the collision sort holds (one workgroup)
+constexpr u64 kListCap = 1ull << 22;  // mismatching adjacent rows the collision search records
+// str_acc slots (u64): [0] first row with decreasing offsets (~0 = none), [1] keys with bytes but chars == NULL,
+// [2] mismatch list length, [3] error bits (1 = a mixed run beyond kRunCap, 2 = list overflow), [8..15] ACC_* sums
+enum { SA_BAD_ROW = 0, SA_NULL_CHARS, SA_LIST_N, SA_ERR, SA_ACC = 8, SA_N = 16 };
+
+__device__ __forceinline__ u64 shift_mix(u64 v) { return v ^ (v >> 47); }
+
+// Reads the key bytes at byte position `pos` as little-endian 64-bit words through aligned 8-byte loads (word q = bytes
+// [8q, 8q + 8) of the address space the loader LD sees).  A load never reaches beyond the 8-byte-aligned words that
+// hold key bytes, so no load crosses into a page the key does not touch.
+template <class LD>
+struct KeyReader {
+  LD ld;
+  u64 q;     // aligned word holding the next byte
+  u32 s;     // bit offset of the next byte in that word
+  u64 cur;   // word q (valid when it holds key bytes)
+  u64 left;  // key bytes not yet read
+  __device__ __forceinline__ KeyReader(LD l, u64 pos, u64 len) : ld(l), q(pos >> 3), s((u32)(pos & 7) * 8u), cur(0), left(len) {
+    if (len) cur = ld(q);
+  }
+  // the next 8 bytes (left >= 8)
+  __device__ __forceinline__ u64 word() {
+    u64 d;
+    left -= 8;
+    if (s == 0) {
+      d = cur;
+      q++;
+      if (left) cur = ld(q);
+    } else {
+      const u64 nx = ld(q + 1);
+      d = (cur >> s) | (nx << (64 - s));
+      cur = nx;
+      q++;
+    }
+    return d;
+  }
+  // the last 1..7 bytes (left < 8), zero-extended
+  __device__ __forceinline__ u64 tail() {
+    const u32 t = (u32)left;
+    u64 d = cur >> s;
+    if (s + 8u * t > 64u) d |= ld(q + 1) << (64 - s);
+    left = 0;
+    return d & ((1ull << (8u * t)) - 1ull);
+  }
+};
+struct GlobalLd {
+  __device__ __forceinline__ u64 operator()(u64 q) const { return *reinterpret_cast<const u64*>(q << 3); }
+};
+struct LdsLd {
+  const u64* w;
+  __device__ __forceinline__ u64 operator()(u64 q) const { return w[q]; }
+};
+
+// libstdc++ _Hash_bytes (64-bit size_t), i.e. std::hash<std::string>
+template <class LD>
+__device__ __forceinline__ u64 hash_bytes(LD ld, u64 pos, u64 len) {
+  KeyReader<LD> rd(ld, pos, len);
+  u64 h = kSeed ^ (len * kMul);
+  for (u64 k = len >> 3; k; k--) {
+    const u64 d = shift_mix(rd.word() * kMul) * kMul;
+    h = (h ^ d) * kMul;
+  }
+  if (len & 7) h = (h ^ rd.tail()) * kMul;
+  return shift_mix(shift_mix(h) * kMul);
+}
+
+__device__ __forceinline__ u64 fold_bits(u64 h, u32 bits) { return bits ? h >> (64 - bits) : h; }
+
+// Per wave: 64 consecutive keys, bytes [offsets[i0], offsets[i0 + 64]).  Staged in LDS when the span's aligned 16-byte
+// blocks fit SH_STAGE, else read per lane from global memory.  rows: out = {hash, row} x n, else bare hashes.  vals != NULL: their sum goes to acc[SA_ACC + ACC_SUM_P].
+__global__ __launch_bounds__(SH_THREADS) void str_hash_kernel(const unsigned char* __restrict__ chars, const u64* __restrict__ offsets,
+                                                              u64 n, u32 hash_bits, u64* __restrict__ out, int rows,
+                                                              const u64* __restrict__ vals, u64* __restrict__ acc) {
+  __shared__ u64 stage[SH_WAVES][SH_STAGE / 8 + 2];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const u64 i0 = ((u64)blockIdx.x * SH_WAVES + (u64)w) * 64ull;
+  const u64 i = i0 + (u64)lane;
+  const bool active = i < n;
+  const u64 iend = i0 + 64 < n ? i0 + 64 : n;
+  u64 o0 = 0, o1 = 0, s0 = 0, s1 = 0;
+  if (i0 < n) {
+    const u64 a = offsets[active ? i : n];
+    const u64 e = offsets[iend];
+    const u64 nxt = __shfl_down(a, 1, 64);
+    o0 = a;
+    o1 = lane == 63 ? e : nxt;
+    if (i + 1 == iend) o1 = e;
+    s0 = __shfl(a, 0, 64);
+    s1 = e;
+  }
+  const bool bad = active && o1 < o0;
+  const u64 bad_mask = __ballot(bad);
+  if (bad_mask && lane == (int)__builtin_ctzll(bad_mask)) atomicMin(&acc[SA_BAD_ROW], i);
+  const bool ok_wave = i0 < n && !bad_mask && s1 >= s0;
+  if (ok_wave && !chars && s1 > s0 && lane == 0) atomicAdd(&acc[SA_NULL_CHARS], 1ull);
+  const bool usable = ok_wave && (chars || s1 == s0);
+  // stage the wave's span: 16-byte aligned loads covering [chars + s0, chars + s1)
+  const uintptr_t b0 = usable ? ((uintptr_t)(chars + s0) & ~(uintptr_t)15) : 0;
+  const u64 span_bytes = usable && s1 > s0 ? (u64)(((uintptr_t)(chars + s1) + 15) & ~(uintptr_t)15) - (u64)b0 : 0;
+  const bool staged = usable && span_bytes <= (u64)SH_STAGE;
+  if (staged) {
+    const uint4* src = reinterpret_cast<const uint4*>(b0);
+    uint4* dst = reinterpret_cast<uint4*>(&stage[w][0]);
+    for (u32 k = (u32)lane; k < (u32)(span_bytes >> 4); k += 64) dst[k] = src[k];
+  }
+  if (vals && i0 < n) {
+    const u64 vs = hmj::wave_sum_u64(active ? vals[i] : 0ull);
+    if (lane == 0) atomicAdd(&acc[SA_ACC + hmj::ACC_SUM_P], vs);
+  }
+  __syncthreads();
+  if (!usable || !active) return;
+  const u64 len = o1 - o0;
+  u64 h;
+  if (staged) {
+    h = hash_bytes(LdsLd{&stage[w][0]}, (u64)((uintptr_t)(chars + o0) - b0), len);
+  } else {
+    h = hash_bytes(GlobalLd{}, (u64)(uintptr_t)(chars + o0), len);
+  }
+  h = fold_bits(h, hash_bits);
+  if (rows) {
+    reinterpret_cast<ulonglong2*>(out)[i] = make_ulonglong2(h, i);
+  } else {
+    out[i] = h;
+  }
+}
+
+// Lexicographic comparison of two keys as std::string::operator< compares them (unsigned bytes, then length).
+__device__ __forceinline__ int key_cmp(const unsigned char* ca, const u64* oa, u64 ra, const unsigned char* cb, const u64* ob, u64 rb) {
+  const u64 pa = oa[ra], la = oa[ra + 1] - pa, pb = ob[rb], lb = ob[rb + 1] - pb;
+  const u64 m = la < lb ? la : lb;
+  KeyReader<GlobalLd> A(GlobalLd{}, (u64)(uintptr_t)(ca + pa), m), B(GlobalLd{}, (u64)(uintptr_t)(cb + pb), m);
+  while (A.left) {
+    const u64 x = A.left >= 8 ? A.word() : A.tail();
+    const u64 y = B.left >= 8 ? B.word() : B.tail();
+    if (x != y) {
+      const u32 sh = (u32)__builtin_ctzll(x ^ y) & ~7u;
+      return ((x >> sh) & 0xFF) < ((y >> sh) & 0xFF) ? -1 : 1;
+    }
+  }
+  return la < lb ? -1 : la > lb ? 1 : 0;
+}
+__device__ __forceinline__ bool key_eq(const unsigned char* ca, const u64* oa, u64 ra, const unsigned char* cb, const u64* ob, u64 rb) {
+  if (oa[ra + 1] - oa[ra] != ob[rb + 1] - ob[rb]) return false;
+  return key_cmp(ca, oa, ra, cb, ob, rb) == 0;
+}
+
+struct StrSide {
+  const unsigned char* chars;
+  const u64* offsets;
+  const u64* vals;
+};
+
+// Pass 1 of the verification.  MAT: one ballot word per wave (flags) and the survivors per workgroup (blk_cnt).
+// Count modes (!MAT): counts, sums and checksums of the survivors straight into acc.
+template <bool MAT>
+__global__ __launch_bounds__(SV_THREADS) void str_verify_kernel(const u64* __restrict__ hk, const u64* __restrict__ rr,
+                                                                const u64* __restrict__ sr, u64 np, StrSide R, StrSide S,
+                                                                u64* __restrict__ flags, u64* __restrict__ blk_cnt,
+                                                                u64* __restrict__ acc, int checksum) {
+  __shared__ u64 red[8];
+  if (threadIdx.x < 8) red[threadIdx.x] = 0;
+  __syncthreads();  // (wave 0 zeroes red[]; every wave's lane 0 adds to red[0] below)
+  const u64 j = (u64)blockIdx.x * SV_THREADS + threadIdx.x;
+  bool keep = false;
+  u64 r = 0, s = 0;
+  if (j < np) {
+    r = rr[j];
+    s = sr[j];
+    keep = key_eq(R.chars, R.offsets, r, S.chars, S.offsets, s);
+  }
+  if (MAT) {
+    const u64 m = __ballot(keep);
+    const int lane = threadIdx.x & 63;
+    if (lane == 0) {
+      flags[j >> 6] = m;
+      if (m) atomicAdd(&red[0], (u64)__builtin_popcountll(m));
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) blk_cnt[blockIdx.x] = red[0];
+  } else {
+    u64 v[6] = {0, 0, 0, 0, 0, 0};
+    if (keep) {
+      const u64 rv = R.vals[r], sv = S.vals[s];
+      v[hmj::ACC_N] = 1;
+      v[hmj::ACC_SUM_R] = rv;
+      v[hmj::ACC_SUM_S] = sv;
+      if (checksum) {
+        const u64 t = hmj::tmix(hk[j], rv, sv);
+        v[hmj::ACC_XOR] = t;
+        v[hmj::ACC_MIX] = t;
+      }
+    }
+    __syncthreads();
+    hmj::block_accumulate(red, acc + SA_ACC, v, 1u << hmj::ACC_XOR);
+  }
+}
+
+// Pass 2: the survivors of workgroup b go, in pair order, to rows [blk_off[b], ..) of the five result columns.
+__global__ __launch_bounds__(SV_THREADS) void str_compact_kernel(const u64* __restrict__ hk, const u64* __restrict__ rr,
+                                                                 const u64* __restrict__ sr, u64 np, StrSide R, StrSide S,
+                                                                 const u64* __restrict__ flags, const u64* __restrict__ blk_off,
+                                                                 u64* __restrict__ o_hash, u64* __restrict__ o_r, u64* __restrict__ o_s,
+                                                                 u64* __restrict__ o_rv, u64* __restrict__ o_sv, u64* __restrict__ acc,
+                                                                 int checksum) {
+  __shared__ u64 red[8];
+  if (threadIdx.x < 8) red[threadIdx.x] = 0;
+  const u64 j = (u64)blockIdx.x * SV_THREADS + threadIdx.x;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  u64 v[6] = {0, 0, 0, 0, 0, 0};
+  if (j < np) {
+    const u64 m = flags[j >> 6];
+    if ((m >> lane) & 1ull) {
+      u64 pos = blk_off[blockIdx.x] + hmj::popc_below(m);
+      const u64 f0 = ((u64)blockIdx.x * SV_THREADS) >> 6;
+      for (int k = 0; k < w; k++) pos += (u64)__builtin_popcountll(flags[f0 + (u64)k]);
+      const u64 h = hk[j], r = rr[j], s = sr[j];
+      const u64 rv = R.vals[r], sv = S.vals[s];
+      o_hash[pos] = h;
+      o_r[pos] = r;
+      o_s[pos] = s;
+      o_rv[pos] = rv;
+      o_sv[pos] = sv;
+      v[hmj::ACC_SUM_R] = rv;
+      v[hmj::ACC_SUM_S] = sv;
+      if (checksum) {
+        const u64 t = hmj::tmix(h, rv, sv);
+        v[hmj::ACC_XOR] = t;
+        v[hmj::ACC_MIX] = t;
+      }
+    }
+  }
+  __syncthreads();
+  hmj::block_accumulate(red, acc + SA_ACC, v, 1u << hmj::ACC_XOR);
+}
+
+// Collision search (ordered): row i whose hash equals row i-1's but whose build key differs is recorded.
+__global__ __launch_bounds__(SV_THREADS) void str_mismatch_kernel(const u64* __restrict__ hk, const u64* __restrict__ rr, u64 n,
+                                                                  StrSide R, u64* __restrict__ list, u64* __restrict__ acc) {
+  const u64 i = (u64)blockIdx.x * SV_THREADS + threadIdx.x + 1;
+  if (i >= n) return;
+  if (hk[i] != hk[i - 1]) return;
+  const u64 a = rr[i - 1], b = rr[i];
+  if (a == b || key_eq(R.chars, R.offsets, a, R.chars, R.offsets, b)) return;
+  const u64 k = atomicAdd(&acc[SA_LIST_N], 1ull);
+  if (k < kListCap) list[k] = i;
+  else atomicOr(&acc[SA_ERR], 2ull);
+}
+
+// One lane per recorded row i: its run [s, e) of equal hash (binary searches on the ascending hash column).  The lane whose
+// i is the FIRST mismatch of its run leads it (runs[2k], runs[2k + 1] = s, e); the others write an empty run.  A separate
+// launch from the sort, so that no leader test reads rows another workgroup is moving.
+__global__ __launch_bounds__(SV_THREADS) void str_run_leader_kernel(const u64* __restrict__ hk, const u64* __restrict__ rr, u64 n,
+                                                                    StrSide R, const u64* __restrict__ list, u64* __restrict__ runs,
+                                                                    u64* __restrict__ acc) {
+  const u64 cnt = acc[SA_LIST_N] < kListCap ? acc[SA_LIST_N] : kListCap;
+  for (u64 k = (u64)blockIdx.x * SV_THREADS + threadIdx.x; k < cnt; k += (u64)gridDim.x * SV_THREADS) {
+    const u64 i = list[k], h = hk[i];
+    u64 lo = 0, hi = i;  // first row with hash h
+    while (lo < hi) {
+      const u64 mid = (lo + hi) >> 1;
+      if (hk[mid] < h) lo = mid + 1;
+      else hi = mid;
+    }
+    const u64 s = lo;
+    lo = i + 1;
+    hi = n;  // first row past the run
+    while (lo < hi) {
+      const u64 mid = (lo + hi) >> 1;
+      if (hk[mid] <= h) lo = mid + 1;
+      else hi = mid;
+    }
+    const u64 e = lo;
+    runs[2 * k] = 0;
+    runs[2 * k + 1] = 0;
+    if (e - s > (u64)kRunCap) {
+      atomicOr(&acc[SA_ERR], 1ull);
+      continue;
+    }
+    bool first = true;
+    for (u64 t = s + 1; t < i && first; t++) {
+      const u64 a = rr[t - 1], b = rr[t];
+      if (a != b && !key_eq(R.chars, R.offsets, a, R.chars, R.offsets, b)) first = false;
+    }
+    if (first) {
+      runs[2 * k] = s;
+      runs[2 * k + 1] = e;
+    }
+  }
+}
+
+// One workgroup per led run: rows sorted stably by build key bytes (rank = rows with a smaller key + rows before it with
+// the same key), written back in place.  All rows of a run share the hash, so only r_row, s_row, rval, sval move.
+__global__ __launch_bounds__(SV_THREADS) void str_run_sort_kernel(const u64* __restrict__ runs, StrSide R, u64* __restrict__ o_r,
+                                                                  u64* __restrict__ o_s, u64* __restrict__ o_rv,
+                                                                  u64* __restrict__ o_sv, const u64* __restrict__ acc) {
+  __shared__ u64 col[4][kRunCap];
+  __shared__ u32 rank[kRunCap];
+  const u64 cnt = acc[SA_LIST_N] < kListCap ? acc[SA_LIST_N] : kListCap;
+  for (u64 k = blockIdx.x; k < cnt; k += gridDim.x) {
+    const u64 s = runs[2 * k], e = runs[2 * k + 1];
+    if (e <= s) continue;  // (uniform: not a leader)
+    const u32 L = (u32)(e - s);
+    for (u32 t = threadIdx.x; t < L; t += SV_THREADS) {
+      col[0][t] = o_r[s + t];
+      col[1][t] = o_s[s + t];
+      col[2][t] = o_rv[s + t];
+      col[3][t] = o_sv[s + t];
+    }
+    __syncthreads();
+    for (u32 t = threadIdx.x; t < L; t += SV_THREADS) {
+      const u64 me = col[0][t];
+      u32 rk = 0;
+      for (u32 o = 0; o < L; o++) {
+        const u64 other = col[0][o];
+        const int c = other == me ? 0 : key_cmp(R.chars, R.offsets, other, R.chars, R.offsets, me);
+        rk += (c < 0 || (c == 0 && o < t)) ? 1u : 0u;
+      }
+      rank[t] = rk;
+    }
+    __syncthreads();
+    for (u32 t = threadIdx.x; t < L; t += SV_THREADS) {
+      const u64 d = s + rank[t];
+      o_r[d] = col[0][t];
+      o_s[d] = col[1][t];
+      o_rv[d] = col[2][t];
+      o_sv[d] = col[3][t];
+    }
+    __syncthreads();
+  }
+}
+
+}  // namespace
+
+namespace {
+
+constexpr int kStrJoinMemoKind = 15;  // workload_signature kind of the inner {hash,row} join (u64 joins 0, sorts 1, kinds 3..9)
+constexpr u64 kNone = ~0ull;
+
+int check_str_rel(hmj_ctx* c, const hmj_str_rel* r, const char* name) {
+  char msg[128];
+  if (!r) {
+    std::snprintf(msg, sizeof(msg), "the %s relation is NULL", name);
+    return fail(c, HMJ_E_ARG, msg);
+  }
+  if (r->n > 0xFFFFFFFFull) {
+    std::snprintf(msg, sizeof(msg), "too many rows in the %s relation (at most 2^32-1)", name);
+    return fail(c, HMJ_E_ARG, msg);
+  }
+  if (r->n > 0 && (!r->offsets || !r->vals)) {
+    std::snprintf(msg, sizeof(msg), "%s relation: offsets / vals is NULL", name);
+    return fail(c, HMJ_E_ARG, msg);
+  }
+  return HMJ_OK;
+}
+
+// acc: three blocks of SA_N words -- [0] build side's hashing, [1] probe side's hashing, [2] verification / collisions
+int acc_reset(hmj_ctx* c, u64* acc) {
+  HIP_TRY(hipMemsetAsync(acc, 0, 3 * SA_N * sizeof(u64), c->stream));
+  HIP_TRY(hipMemsetAsync(acc + SA_BAD_ROW, 0xFF, sizeof(u64), c->stream));
+  HIP_TRY(hipMemsetAsync(acc + SA_N + SA_BAD_ROW, 0xFF, sizeof(u64), c->stream));
+  return HMJ_OK;
+}
+
+int launch_hash(hmj_ctx* c, const void* chars, const u64* offsets, u64 n, u32 bits, u64* out, bool rows, const u64* vals, u64* acc) {
+  if (!n) return HMJ_OK;
+  const u64 grid = (n + SH_THREADS - 1) / SH_THREADS;
+  hipLaunchKernelGGL(str_hash_kernel, dim3((u32)grid), dim3(SH_THREADS), 0, c->stream, (const unsigned char*)chars, offsets, n, bits,
+                     out, rows ? 1 : 0, vals, acc);
+  HIP_TRY(hipGetLastError());
+  return HMJ_OK;
+}
+
+// the hash kernel's verdict on one relation's offsets (h: its acc block, read back)
+int hash_errors(hmj_ctx* c, const u64* h, const char* name) {
+  char msg[160];
+  if (h[SA_BAD_ROW] != kNone) {
+    std::snprintf(msg, sizeof(msg), "%s relation: offsets decrease at row %llu (offsets[%llu] < offsets[%llu])", name,
+                  (unsigned long long)h[SA_BAD_ROW], (unsigned long long)h[SA_BAD_ROW] + 1, (unsigned long long)h[SA_BAD_ROW]);
+    return fail(c, HMJ_E_ARG, msg);
+  }
+  if (h[SA_NULL_CHARS]) {
+    std::snprintf(msg, sizeof(msg), "%s relation: chars is NULL but keys have bytes", name);
+    return fail(c, HMJ_E_ARG, msg);
+  }
+  return HMJ_OK;
+}
+
+int read_back(hmj_ctx* c, const void* dev, void* host, size_t bytes) {
+  HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return HMJ_OK;
+}
+
+int record(hmj_ctx* c, int k) {
+  if (!c->profiling) return HMJ_OK;
+  if (!c->str_ev[k]) HIP_TRY(hipEventCreate(&c->str_ev[k]));
+  HIP_TRY(hipEventRecord(c->str_ev[k], c->stream));
+  return HMJ_OK;
+}
+float elapsed(hmj_ctx* c, int a, int b) {
+  float ms = 0.f;
+  if (c->str_ev[a] && c->str_ev[b] && hipEventElapsedTime(&ms, c->str_ev[a], c->str_ev[b]) != hipSuccess) {
+    (void)hipGetLastError();
+    ms = 0.f;
+  }
+  return ms;
+}
+
+#define RC_TRY(expr)                   \
+  do {                                 \
+    const int _rc = (expr);            \
+    if (_rc != HMJ_OK) return _rc;     \
+  } while (0)
+
+int join_str(hmj_ctx* c, const hmj_str_rel* R, const hmj_str_rel* S, uint32_t flags, hmj_str_join_opts* opts, hmj_str_result* out) {
+  const u64 nb = R->n, np = S->n;
+  const u32 bits = opts->hash_bits;
+  if (flags & HMJ_ORDERED) flags |= HMJ_MATERIALIZE;
+  const bool mat = flags & HMJ_MATERIALIZE, ordered = flags & HMJ_ORDERED, checksum = flags & HMJ_CHECKSUM;
+  c->prep.valid = false;  // like any other call, a string join discards a prepared build side
+  RC_TRY(ensure_dev(c, c->str_acc, 3 * SA_N * sizeof(u64)));
+  RC_TRY(ensure_dev(c, c->str_rows_r, 16 * (nb ? nb : 1)));
+  RC_TRY(ensure_dev(c, c->str_rows_s, 16 * (np ? np : 1)));
+  u64* acc = (u64*)c->str_acc.p;
+  u64 h[3 * SA_N];
+  // 1. {hash, row} rows of both relations (+ the probe payloads' sum)
+  RC_TRY(record(c, 0));
+  RC_TRY(acc_reset(c, acc));
+  RC_TRY(launch_hash(c, R->chars, (const u64*)R->offsets, nb, bits, (u64*)c->str_rows_r.p, true, nullptr, acc));
+  RC_TRY(launch_hash(c, S->chars, (const u64*)S->offsets, np, bits, (u64*)c->str_rows_s.p, true, (flags & HMJ_SUM_PROBE) ? (const u64*)S->vals : nullptr,
+                     acc + SA_N));
+  RC_TRY(record(c, 1));
+  RC_TRY(read_back(c, acc, h, sizeof(h)));
+  RC_TRY(hash_errors(c, h, "build"));
+  RC_TRY(hash_errors(c, h + SA_N, "probe"));
+  if (flags & HMJ_SUM_PROBE) out->sum_probe_all = h[SA_N + SA_ACC + hmj::ACC_SUM_P];
+  if (nb == 0 || np == 0) {  // (nothing to join: no plan either)
+    std::memset(&c->plan, 0, sizeof(c->plan));
+    c->plan.struct_size = sizeof(c->plan);
+    std::memset(&c->timing, 0, sizeof(c->timing));
+    for (int k = 2; k < 5; k++) RC_TRY(record(c, k));
+    return HMJ_OK;
+  }
+  // 2. the u64 join of the {hash, row} rows: pairs of equal hash as (hash, r_row, s_row), ordered by them if asked
+  hmj_result inner;
+  spans_reset(c);
+  const int st = span_begin(c, K_TOTAL, -1);
+  c->memo_kind = kStrJoinMemoKind;
+  int rc = join_device(c, c->str_rows_r.p, nb, c->str_rows_s.p, np, HMJ_MATERIALIZE | (flags & HMJ_ORDERED), &inner, false);
+  c->memo_kind = 0;
+  span_end(c, st);
+  if (c->profiling) {
+    (void)hipStreamSynchronize(c->stream);
+    spans_collect(c);
+  }
+  if (rc != HMJ_OK) return rc;
+  RC_TRY(record(c, 2));
+  const u64 n_pairs = inner.n_matches;
+  opts->n_hash_pairs = n_pairs;
+  // 3. key verification, payload gather, stable compaction (or the count modes' reduction)
+  const StrSide RS{(const unsigned char*)R->chars, (const u64*)R->offsets, (const u64*)R->vals},
+      SS{(const unsigned char*)S->chars, (const u64*)S->offsets, (const u64*)S->vals};
+  const u64 *ik = (const u64*)inner.key, *ir = (const u64*)inner.rval, *is = (const u64*)inner.sval;
+  const u64 nblk = (n_pairs + SV_THREADS - 1) / SV_THREADS;
+  if (nblk > 0xFFFFFFFFull) return fail(c, HMJ_E_UNSUPPORTED, "string join: more than 2^40 pairs of equal hash");
+  u64* acc_v = acc + 2 * SA_N;
+  u64 n_out = 0;
+  if (n_pairs && mat) {
+    RC_TRY(ensure_dev(c, c->str_flags, nblk * (SV_THREADS / 64) * sizeof(u64)));
+    RC_TRY(ensure_dev(c, c->str_blk, nblk * sizeof(u64)));
+    RC_TRY(ensure_dev(c, c->str_blk_off, (nblk + 1) * sizeof(u64)));
+    DevBuf* cols[5] = {&c->str_hash, &c->str_rrow, &c->str_srow, &c->str_rval, &c->str_sval};
+    for (DevBuf* b : cols) RC_TRY(ensure_dev(c, *b, n_pairs * sizeof(u64)));
+    hipLaunchKernelGGL(str_verify_kernel<true>, dim3((u32)nblk), dim3(SV_THREADS), 0, c->stream, ik, ir, is,
+                       n_pairs, RS, SS, (u64*)c->str_flags.p, (u64*)c->str_blk.p, acc_v, 0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hmj::launch_scan_u64((const u64*)c->str_blk.p, (u64*)c->str_blk_off.p, (u32)nblk, c->stream));
+    hipLaunchKernelGGL(str_compact_kernel, dim3((u32)nblk), dim3(SV_THREADS), 0, c->stream, ik, ir, is, n_pairs,
+                       RS, SS, (const u64*)c->str_flags.p, (const u64*)c->str_blk_off.p, (u64*)c->str_hash.p, (u64*)c->str_rrow.p,
+                       (u64*)c->str_srow.p, (u64*)c->str_rval.p, (u64*)c->str_sval.p, acc_v, checksum ? 1 : 0);
+    HIP_TRY(hipGetLastError());
+    RC_TRY(read_back(c, (const u64*)c->str_blk_off.p + nblk, &n_out, sizeof(u64)));
+  } else if (n_pairs) {
+    hipLaunchKernelGGL(str_verify_kernel<false>, dim3((u32)nblk), dim3(SV_THREADS), 0, c->stream, ik, ir, is,
+                       n_pairs, RS, SS, nullptr, nullptr, acc_v, checksum ? 1 : 0);
+    HIP_TRY(hipGetLastError());
+  }
+  RC_TRY(record(c, 3));
+  // 4. ordered: runs of equal hash with different build keys, sorted by key bytes
+  if (ordered && n_out > 1) {
+    const u64 cap = n_out < kListCap ? n_out : kListCap;
+    RC_TRY(ensure_dev(c, c->str_list, cap * sizeof(u64)));
+    RC_TRY(ensure_dev(c, c->str_runs, 2 * cap * sizeof(u64)));
+    const u64 g = (n_out - 1 + SV_THREADS - 1) / SV_THREADS;
+    hipLaunchKernelGGL(str_mismatch_kernel, dim3((u32)g), dim3(SV_THREADS), 0, c->stream, (const u64*)c->str_hash.p,
+                       (const u64*)c->str_rrow.p, n_out, RS, (u64*)c->str_list.p, acc_v);
+    HIP_TRY(hipGetLastError());
+    const u64 gl = (cap + SV_THREADS - 1) / SV_THREADS;
+    hipLaunchKernelGGL(str_run_leader_kernel, dim3((u32)(gl < 1024 ? gl : 1024)), dim3(SV_THREADS), 0, c->stream,
+                       (const u64*)c->str_hash.p, (const u64*)c->str_rrow.p, n_out, RS, (const u64*)c->str_list.p,
+                       (u64*)c->str_runs.p, acc_v);
+    HIP_TRY(hipGetLastError());
+    const u64 gs = cap < (u64)(4 * c->num_cus) ? cap : (u64)(4 * c->num_cus);
+    hipLaunchKernelGGL(str_run_sort_kernel, dim3((u32)gs), dim3(SV_THREADS), 0, c->stream, (const u64*)c->str_runs.p, RS,
+                       (u64*)c->str_rrow.p, (u64*)c->str_srow.p, (u64*)c->str_rval.p, (u64*)c->str_sval.p, (const u64*)acc_v);
+    HIP_TRY(hipGetLastError());
+  }
+  RC_TRY(record(c, 4));
+  RC_TRY(read_back(c, acc_v, h, SA_N * sizeof(u64)));
+  if (h[SA_ERR] & 1) return fail(c, HMJ_E_UNSUPPORTED, "string join: a run of equal hash with several distinct keys holds more than 1024 rows");
+  if (h[SA_ERR] & 2) return fail(c, HMJ_E_UNSUPPORTED, "string join: more than 2^22 adjacent rows of equal hash with different keys");
+  const u64* a = h + SA_ACC;
+  out->n_matches = mat ? n_out : a[hmj::ACC_N];
+  out->sum_r = a[hmj::ACC_SUM_R];
+  out->sum_s = a[hmj::ACC_SUM_S];
+  if (checksum) {
+    out->xor_fold = a[hmj::ACC_XOR];
+    out->mix_sum = a[hmj::ACC_MIX];
+  }
+  if (mat) {
+    out->hash = (const uint64_t*)c->str_hash.p;
+    out->r_row = (const uint64_t*)c->str_rrow.p;
+    out->s_row = (const uint64_t*)c->str_srow.p;
+    out->rval = (const uint64_t*)c->str_rval.p;
+    out->sval = (const uint64_t*)c->str_sval.p;
+  }
+  opts->n_collisions = n_pairs - out->n_matches;
+  return HMJ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hmj_hash_str_device(hmj_ctx* c, const void* chars, const uint64_t* offsets, uint64_t n, uint32_t hash_bits, uint64_t* hash_out_dev) {
+  if (!c) return HMJ_E_ARG;
+  if (n > 0xFFFFFFFFull) return fail(c, HMJ_E_ARG, "too many rows (at most 2^32-1)");
+  if (hash_bits > 63) return fail(c, HMJ_E_ARG, "hash_bits > 63");
+  if (n > 0 && (!offsets || !hash_out_dev)) return fail(c, HMJ_E_ARG, "offsets / hash_out_dev is NULL");
+  if (n == 0) return HMJ_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  RC_TRY(ensure_dev(c, c->str_acc, 3 * SA_N * sizeof(u64)));
+  u64* acc = (u64*)c->str_acc.p;
+  RC_TRY(acc_reset(c, acc));
+  RC_TRY(launch_hash(c, chars, (const u64*)offsets, n, hash_bits, (u64*)hash_out_dev, false, nullptr, acc));
+  u64 h[SA_N];
+  RC_TRY(read_back(c, acc, h, sizeof(h)));
+  return hash_errors(c, h, "the");
+}
+
+int hmj_join_str_device(hmj_ctx* c, const hmj_str_rel* build, const hmj_str_rel* probe, uint32_t flags, hmj_str_join_opts* opts,
+                        hmj_str_result* out) {
+  if (!c) return HMJ_E_ARG;
+  if (!opts || !out) return fail(c, HMJ_E_ARG, "opts / out is NULL");
+  if (opts->struct_size < offsetof(hmj_str_join_opts, hash_bits) + sizeof(opts->hash_bits))
+    return fail(c, HMJ_E_ARG, "hmj_str_join_opts.struct_size too small");
+  if (opts->hash_bits > 63) return fail(c, HMJ_E_ARG, "hash_bits > 63");
+  if (flags & HMJ_FIRST_WINS) return fail(c, HMJ_E_ARG, "HMJ_FIRST_WINS is not defined for string joins");
+  RC_TRY(check_str_rel(c, build, "build"));
+  RC_TRY(check_str_rel(c, probe, "probe"));
+  std::memset(out, 0, sizeof(*out));
+  HIP_TRY(hipSetDevice(c->device));
+  // the out fields of opts go to a full-size copy first; the caller gets the prefix its struct_size holds
+  hmj_str_join_opts o;
+  std::memset(&o, 0, sizeof(o));
+  std::memcpy(&o, opts, opts->struct_size < sizeof(o) ? opts->struct_size : sizeof(o));
+  const int rc = join_str(c, build, probe, flags, &o, out);
+  if (rc != HMJ_OK) return rc;
+  if (c->profiling) {
+    (void)hipStreamSynchronize(c->stream);
+    o.ms_hash = elapsed(c, 0, 1);
+    o.ms_join = elapsed(c, 1, 2);
+    o.ms_verify = elapsed(c, 2, 3);
+    o.ms_order = elapsed(c, 3, 4);
+  }
+  const uint32_t room = opts->struct_size < sizeof(o) ? opts->struct_size : (uint32_t)sizeof(o);
+  o.struct_size = opts->struct_size;
+  std::memcpy(opts, &o, room);
+  return HMJ_OK;
+}
+
+}  // extern "C"

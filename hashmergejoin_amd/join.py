@@ -197,6 +197,67 @@ class Executor:
             out[:, c] = tmp.cpu().numpy().view(np.uint64)
         return out
 
+    # ---- string keys (hmj_hash_str_device / hmj_join_str_device) ------------------------------------
+    def _str_rel(self, rel):
+        """(chars uint8, offsets int64 [n + 1], vals int64 [n]) device tensors -> StrRel (chars may be None or empty when
+        every key is empty)."""
+        chars, offsets, vals = rel
+        _check_col(offsets, "offsets")
+        _check_col(vals, "vals")
+        n = vals.shape[0]
+        if offsets.shape[0] != n + 1:
+            raise ValueError("offsets must hold n + 1 entries")
+        r = _lib.StrRel()
+        r.chars = _chars_ptr(chars)
+        r.offsets = offsets.data_ptr() if n else None
+        r.vals = vals.data_ptr() if n else None
+        r.n = n
+        return r
+
+    def hash_str_device(self, chars, offsets, hash_bits=0):
+        """std::hash<std::string> of every key (libstdc++'s _Hash_bytes), computed on the device: int64 tensor [n]
+        (read as uint64).  hash_bits 1..63 keeps the top bits only (h >> (64 - hash_bits))."""
+        torch = self._torch
+        _check_col(offsets, "offsets")
+        if offsets.shape[0] < 1:
+            raise ValueError("offsets must hold n + 1 entries")
+        self._sync_stream()
+        n = offsets.shape[0] - 1
+        out = torch.empty(n, dtype=torch.int64, device=offsets.device)
+        self._check(self.L.hmj_hash_str_device(self.h, _chars_ptr(chars), C.c_void_p(offsets.data_ptr()), max(n, 0),
+                                               int(hash_bits), C.c_void_p(out.data_ptr()) if n > 0 else None))
+        return out
+
+    def join_str_device(self, build, probe, flags=0, hash_bits=0):
+        """Inner join of two string-keyed device relations (hmj_join_str_device).  build / probe: (chars uint8, offsets
+        int64 [n + 1], vals int64 [n]) device tensors -- the Arrow large_string layout plus payloads (`pack_strings`).
+        Returns (StrResult, {"n_hash_pairs", "n_collisions", "ms_hash", "ms_join", "ms_verify", "ms_order"}); read the
+        rows with `str_rows_to_numpy`."""
+        self._sync_stream()
+        rb, rp = self._str_rel(build), self._str_rel(probe)
+        opts = _lib.StrJoinOpts()
+        opts.struct_size = C.sizeof(_lib.StrJoinOpts)
+        opts.hash_bits = int(hash_bits)
+        res = _lib.StrResult()
+        self._check(self.L.hmj_join_str_device(self.h, C.byref(rb), C.byref(rp), flags, C.byref(opts), C.byref(res)))
+        info = {"n_hash_pairs": int(opts.n_hash_pairs), "n_collisions": int(opts.n_collisions)}
+        for k in ("ms_hash", "ms_join", "ms_verify", "ms_order"):
+            info[k] = float(getattr(opts, k))
+        return res, info
+
+    def str_rows_to_numpy(self, res):
+        """Copy a string join's device result out as an [n,5] uint64 array of (hash, r_row, s_row, rval, sval)."""
+        n = int(res.n_matches)
+        out = np.empty((n, 5), np.uint64)
+        if n == 0 or not res.hash:
+            return out[:0]
+        torch = self._torch
+        tmp = torch.empty(n, dtype=torch.int64, device="cuda:%d" % self.device)
+        for c, ptr in enumerate((res.hash, res.r_row, res.s_row, res.rval, res.sval)):
+            _memcpy_d2d(torch, tmp, ptr, n * 8)
+            out[:, c] = tmp.cpu().numpy().view(np.uint64)
+        return out
+
     def prepare_build(self, build, n_probe_hint):
         """Partition the build side now; the next matching plain-count join_device skips that work."""
         self._sync_stream()
@@ -376,6 +437,36 @@ class Executor:
         t = self._alloc(n)
         self._check(self.L.hmj_gen_uniform_domain_u64_device(self.h, C.c_void_p(t.data_ptr()), n, start, domain, seed, zseed))
         return t
+
+
+def _check_col(t, name):
+    """A column the string entries read on the device: contiguous, 1-D, 64-bit, on the GPU."""
+    if not t.is_cuda or not t.is_contiguous() or t.element_size() != 8 or t.dim() != 1:
+        raise ValueError("%s must be a contiguous 1-D 64-bit device tensor" % name)
+
+
+def _chars_ptr(chars):
+    if chars is None or chars.numel() == 0:
+        return None
+    if not chars.is_cuda or not chars.is_contiguous() or chars.element_size() != 1:
+        raise ValueError("chars must be a contiguous 1-byte device tensor")
+    return C.c_void_p(chars.data_ptr())
+
+
+def pack_strings(keys, device=None):
+    """Keys (str, encoded as UTF-8, or bytes) -> (chars uint8 [total bytes], offsets int64 [n + 1]): the Arrow
+    large_string layout hmj_join_str_device reads.  device=None leaves both tensors on the CPU."""
+    import torch
+
+    enc = [k.encode("utf-8") if isinstance(k, str) else bytes(k) for k in keys]
+    lens = np.fromiter((len(b) for b in enc), dtype=np.int64, count=len(enc))
+    offsets = np.zeros(len(enc) + 1, np.int64)
+    np.cumsum(lens, out=offsets[1:])
+    chars = np.frombuffer(b"".join(enc), dtype=np.uint8).copy()
+    c, o = torch.from_numpy(chars), torch.from_numpy(offsets)
+    if device is not None:
+        c, o = c.to(device), o.to(device)
+    return c, o
 
 
 def _memcpy_d2d(torch, dst_tensor, src_ptr, nbytes):

@@ -424,6 +424,70 @@ void hmj_rows_free(hmj_rows* rows);
  * reference frees its _r_sorted/_s_sorted vectors in clear(), hashjoin.h:192-195.)                     */
 uint64_t hmj_host_pool_trim(uint64_t keep_bytes);
 uint64_t hmj_host_pool_bytes(void);
+
+/* ---- string keys on the device ------------------------------------------------------------------ */
+/* Replaces HashMergeJoin<KeyValVec::iterator, KeyValVec::iterator> (hashjoin.h:29 KeyValVec = pair<std::string,
+ * uint64_t>, driven as hashjoin_bench.cc:109-143 drives it) for relations whose keys are variable-length byte strings
+ * held on the device.  Relation layout: Arrow large_string / large_binary -- n + 1 64-bit offsets into one byte buffer --
+ * plus a payload column.  Hashing, the join, key verification, payload gather and ordering all run on the GPU; no pass
+ * on the host touches keys or rows.  (The C++ drop-in, hashmergejoin_hip.hpp, hashes on the host and is unchanged.)    */
+typedef struct {
+  const void* chars;        /* device: key bytes of all rows; may be NULL when every key is empty                  */
+  const uint64_t* offsets;  /* device: n + 1 non-decreasing byte offsets; row i = chars[offsets[i], offsets[i+1])  */
+                            /* offsets[0] need not be 0 (Arrow slices); chars need not be aligned                   */
+  const uint64_t* vals;     /* device: n payloads (the reference's RValue / SValue)                                 */
+  uint64_t n;               /* rows, <= 2^32 - 1                                                                    */
+} hmj_str_rel;
+
+/* std::hash<std::string> of every row (libstdc++'s _Hash_bytes, seed 0xc70f6907; other standard libraries hash
+ * differently), on the device.  hash_bits 0 = all 64 bits; 1..63 = h >> (64 - hash_bits) (see hmj_str_join_opts).
+ * hash_out_dev: n uint64 (device).  HMJ_E_ARG: NULL ctx, NULL offsets / hash_out_dev with n > 0, more than 2^32-1 rows,
+ * hash_bits > 63, decreasing offsets (hmj_last_error names the first offending row), key bytes with chars == NULL.      */
+int hmj_hash_str_device(hmj_ctx* ctx, const void* chars, const uint64_t* offsets, uint64_t n, uint32_t hash_bits,
+                        uint64_t* hash_out_dev);
+
+typedef struct {
+  uint32_t struct_size;   /* in: sizeof of the caller's header (size-versioned like hmj_join_opts)                  */
+  uint32_t hash_bits;     /* in: 0 = 64; fewer bits make hash collisions between different keys common --            */
+                          /* exists so callers and tests can exercise collision handling                             */
+  uint64_t n_hash_pairs;  /* out: pairs of equal hash the {hash,row} join produced                                   */
+  uint64_t n_collisions;  /* out: of those, pairs whose keys differ (dropped)                                         */
+  float ms_hash, ms_join, ms_verify, ms_order; /* out, with hmj_set_profiling(ctx, 1): HIP-event phase times          */
+} hmj_str_join_opts;
+
+typedef struct {
+  uint64_t n_matches, sum_r, sum_s, xor_fold, mix_sum, sum_probe_all; /* as hmj_result; tmix over (hash, rval, sval) */
+  const uint64_t *hash, *r_row, *s_row, *rval, *sval; /* HMJ_MATERIALIZE: device columns owned by the ctx, valid   */
+                                                      /* until the next call on it / hmj_release_result            */
+} hmj_str_result;
+
+/* The inner equi-join of two string-keyed relations.
+ * Match rule: a result row is a pair (build row, probe row) whose keys are equal byte for byte -- equal length and equal
+ * bytes; embedded NUL bytes and bytes >= 0x80 are ordinary bytes.  Duplicate keys on either side give the cross product.
+ * Row contents: r_row / s_row are row indices into the caller's relations (gather maps); rval = build->vals[r_row],
+ * sval = probe->vals[s_row]; hash is the key's hash (hash_bits applied).
+ * Flags: HMJ_MATERIALIZE, HMJ_ORDERED, HMJ_CHECKSUM and HMJ_SUM_PROBE mean what they mean for hmj_join_u64_device;
+ * HMJ_FIRST_WINS is HMJ_E_ARG.  Without HMJ_MATERIALIZE only the counters and sums are filled; verification still runs,
+ * so every count is exact.
+ * HMJ_ORDERED: rows ascending by (hash, key bytes compared as std::string::operator< compares them, r_row, s_row).  For
+ * keys unique within each relation this is exactly the reference operator's iteration order: ascending std::hash, ties
+ * broken on the key (radix_hash.h:86-109).
+ * How: every key is hashed into a {hash, row} row (str_hash_kernel; the wave's 64 keys staged in LDS), the two row sets
+ * are joined by the u64 join (HMJ_MATERIALIZE, + HMJ_ORDERED), every pair of equal hash has its keys compared and its
+ * payloads gathered (str_verify_kernel; survivors compacted stably), and -- ordered only -- runs of equal hash whose
+ * build keys differ are sorted by key bytes, each inside one workgroup.
+ * n == 0 on either side: an empty result and HMJ_OK.
+ * HMJ_E_ARG: NULL ctx / rel / opts / out; NULL offsets or vals with n > 0; opts->struct_size too small; more than
+ * 2^32-1 rows; hash_bits > 63; HMJ_FIRST_WINS; key bytes with chars == NULL; offsets that decrease (checked on the device
+ * by the hash kernel: hmj_last_error names the relation and the first offending row, and the ctx stays usable).
+ * HMJ_E_UNSUPPORTED wherever the inner ordered u64 join returns it, and for an ordered join with a run of equal hash that
+ * holds several distinct matched build keys and more than 1024 rows (or more than 2^22 such adjacent rows in all) --
+ * with 64-bit hashes that takes a genuine _Hash_bytes collision.
+ * hmj_last_plan / hmj_last_timing describe the inner {hash,row} join.  Its workload memo is keyed apart from plain u64
+ * joins (as the kinds' are), so string joins do not change what u64 joins learn.  Like any other call it discards a
+ * prepared build side.  Out of scope: join kinds, the exchange (multi-GPU) path and host-resident string relations.    */
+int hmj_join_str_device(hmj_ctx* ctx, const hmj_str_rel* build, const hmj_str_rel* probe, uint32_t flags,
+                        hmj_str_join_opts* opts, hmj_str_result* out);
 /* Host threads of the optional staged upload (pageable input -> pinned chunks -> PCIe), used only
  * with HMJ_UPLOAD=staged in the environment; by default each relation goes up in one copy straight
  * from the caller's memory (54 GB/s on the MI355X box).  The reference ctor's num_threads argument,
