@@ -103,6 +103,19 @@ class StrJoinOpts(C.Structure):
                 ("ms_order", C.c_float)]
 
 
+# hmj_str_kind_opts (hmj_join_kind_str_device): r_row / s_row of an outer join's unmatched row
+HMJ_STR_NO_ROW = 0xFFFFFFFFFFFFFFFF
+
+
+class StrKindOpts(C.Structure):
+    """hmj_str_kind_opts: side, kind, hash bits and fill values (in); the kind's counters, pairs of equal hash, pairs whose
+    keys differ and phase times (out)."""
+    _fields_ = [("struct_size", C.c_uint32), ("side", C.c_uint32), ("kind", C.c_uint32), ("hash_bits", C.c_uint32),
+                ("probe_fill", C.c_uint64), ("build_fill", C.c_uint64), ("counts", KindCounts), ("n_hash_pairs", C.c_uint64),
+                ("n_collisions", C.c_uint64), ("ms_hash", C.c_float), ("ms_join", C.c_float), ("ms_verify", C.c_float),
+                ("ms_emit", C.c_float), ("ms_order", C.c_float)]
+
+
 class StrResult(C.Structure):
     """hmj_str_result: counts and sums as JoinResult (tmix over (hash, rval, sval)); device columns with HMJ_MATERIALIZE."""
     _fields_ = [("n_matches", C.c_uint64), ("sum_r", C.c_uint64), ("sum_s", C.c_uint64),
@@ -258,6 +271,9 @@ def load_library():
     L.hmj_join_str_device.restype = i
     L.hmj_join_str_device.argtypes = [vp, C.POINTER(StrRel), C.POINTER(StrRel), C.c_uint32, C.POINTER(StrJoinOpts),
                                       C.POINTER(StrResult)]
+    L.hmj_join_kind_str_device.restype = i
+    L.hmj_join_kind_str_device.argtypes = [vp, C.POINTER(StrRel), C.POINTER(StrRel), C.c_uint32, C.POINTER(StrKindOpts),
+                                           C.POINTER(StrResult)]
     L.hmj_prepare_build_u64_device.restype = i
     L.hmj_prepare_build_u64_device.argtypes = [vp, vp, u, u]
     L.hmj_join_u64.restype = i

@@ -3208,7 +3208,8 @@ void hmj_destroy(hmj_ctx* c) {
                     &c->slab_a, &c->slab_br, &c->slab_bs, &c->cnt_a, &c->cnt_br, &c->cnt_bs, &c->lookback, &c->gtab, &c->piece_off,
                     &c->split_r, &c->split_s, &c->split_off, &c->cat_key, &c->cat_rval, &c->cat_sval, &c->msd_off,
                     &c->bmatched, &c->bsweep, &c->str_rows_r, &c->str_rows_s, &c->str_flags, &c->str_blk, &c->str_blk_off,
-                    &c->str_hash, &c->str_rrow, &c->str_srow, &c->str_rval, &c->str_sval, &c->str_list, &c->str_runs, &c->str_acc};
+                    &c->str_hash, &c->str_rrow, &c->str_srow, &c->str_rval, &c->str_sval, &c->str_list, &c->str_runs, &c->str_acc,
+                    &c->str_mark_r, &c->str_mark_s, &c->str_amb, &c->str_ord, &c->str_khash, &c->str_krrow, &c->str_ksrow, &c->str_krval, &c->str_ksval};
   for (DevBuf* b : devs) free_dev(*b);
   HostBuf* hosts[] = {&c->h_accum, &c->h_key, &c->h_rval, &c->h_sval};
   for (HostBuf* b : hosts) free_host(*b);

@@ -110,8 +110,11 @@ struct hmj_ctx {
       // string joins (strjoin.hip): {hash, row} rows of both relations, pass-1 ballots, per-workgroup survivors and their
       // offsets, the five result columns, the collision search's rows and runs, its counters
       str_rows_r, str_rows_s, str_flags, str_blk, str_blk_off, str_hash, str_rrow, str_srow, str_rval, str_sval, str_list,
-      str_runs, str_acc;
-  hipEvent_t str_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // string joins' phase boundaries (profiling)
+      str_runs, str_acc,
+      // string join kinds: one mark byte per row of each relation, the rows whose representative's key differed, the
+      // ordered form's (hash, index) rows and sorted copy, the five result columns in sorted order
+      str_mark_r, str_mark_s, str_amb, str_ord, str_khash, str_krrow, str_ksrow, str_krval, str_ksval;
+  hipEvent_t str_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // string joins' phase boundaries (profiling)
   int memo_kind = 0;  // workload-signature kind of plain inner joins run on behalf of another entry (string joins)
   HostBuf h_accum, h_key, h_rval, h_sval;
   int host_threads = 0;  // staging threads for pageable input (0 = default)

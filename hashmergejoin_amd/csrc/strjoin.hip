@@ -8,6 +8,12 @@
 //                        payloads, or only counted / summed in the count modes;
 //   4. collision order   ordered joins only: runs of equal hash whose build keys differ are sorted by key bytes in one
 //                        workgroup each (a run beyond kRunCap rows is HMJ_E_UNSUPPORTED).
+// The join kinds (hmj_join_kind_str_device) reuse 1, 3 and 4 and add (see join_str_kind below):
+//   str_rep_verify_kernel  one lane per (representative, row) pair of a first-wins {hash,row} join: equal keys mark the
+//                          row (one byte per row), different keys put it on the ambiguous list;
+//   str_sweep_*_kernel     one lane per row of a relation: the rows its mark selects, counted / summed, then written in
+//                          row order (stable) with their payload or the kind's fill;
+//   str_sort_rows_kernel / str_gather_kernel   ordered kinds: (hash, index) rows for the u64 sort, columns gathered.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -35,9 +41,11 @@ constexpr int SH_STAGE = 4096;  // LDS bytes a wave stages its 64 keys in; a lon
 constexpr int SV_THREADS = 256;
 constexpr int kRunCap = 1024;  // rows of one mixed run the collision sort holds (one workgroup)
 constexpr u64 kListCap = 1ull << 22;  // mismatching adjacent rows the collision search records
+constexpr u64 kNoRow = ~0ull;         // HMJ_STR_NO_ROW
 // str_acc slots (u64): [0] first row with decreasing offsets (~0 = none), [1] keys with bytes but chars == NULL,
-// [2] mismatch list length, [3] error bits (1 = a mixed run beyond kRunCap, 2 = list overflow), [8..15] ACC_* sums
-enum { SA_BAD_ROW = 0, SA_NULL_CHARS, SA_LIST_N, SA_ERR, SA_ACC = 8, SA_N = 16 };
+// [2] mismatch list length, [3] error bits (1 = a mixed run beyond kRunCap, 2 = list overflow), [4] ambiguous rows and
+// [5] pairs whose keys differ (join kinds), [8..15] ACC_* sums
+enum { SA_BAD_ROW = 0, SA_NULL_CHARS, SA_LIST_N, SA_ERR, SA_AMB_N, SA_DIFF, SA_ACC = 8, SA_N = 16 };
 
 __device__ __forceinline__ u64 shift_mix(u64 v) { return v ^ (v >> 47); }
 
@@ -186,13 +194,32 @@ struct StrSide {
   const u64* vals;
 };
 
+// The join kinds' result rows: a row's key is the build key when r_row is present, else the probe key (rr == NULL: no
+// r_row column, every row a probe row).
+struct KeyRef {
+  const unsigned char* chars;
+  const u64* offsets;
+  u64 row;
+};
+__device__ __forceinline__ KeyRef key_of(const StrSide& R, const StrSide& S, u64 r, u64 s) {
+  return r != kNoRow ? KeyRef{R.chars, R.offsets, r} : KeyRef{S.chars, S.offsets, s};
+}
+__device__ __forceinline__ KeyRef row_key(const StrSide& R, const StrSide& S, const u64* rr, const u64* sr, u64 i) {
+  return key_of(R, S, rr ? rr[i] : kNoRow, sr ? sr[i] : kNoRow);
+}
+__device__ __forceinline__ bool same_key(const KeyRef& a, const KeyRef& b) {
+  return (a.offsets == b.offsets && a.row == b.row) || key_eq(a.chars, a.offsets, a.row, b.chars, b.offsets, b.row);
+}
+
 // Pass 1 of the verification.  MAT: one ballot word per wave (flags) and the survivors per workgroup (blk_cnt).
-// Count modes (!MAT): counts, sums and checksums of the survivors straight into acc.
-template <bool MAT>
+// Count modes (!MAT): counts, sums and checksums of the survivors straight into acc.  MARK (outer join kinds): the
+// survivors' build and probe rows are marked (one byte per row; every writer stores 1).
+template <bool MAT, bool MARK = false>
 __global__ __launch_bounds__(SV_THREADS) void str_verify_kernel(const u64* __restrict__ hk, const u64* __restrict__ rr,
                                                                 const u64* __restrict__ sr, u64 np, StrSide R, StrSide S,
                                                                 u64* __restrict__ flags, u64* __restrict__ blk_cnt,
-                                                                u64* __restrict__ acc, int checksum) {
+                                                                u64* __restrict__ acc, int checksum,
+                                                                unsigned char* __restrict__ mark_r, unsigned char* __restrict__ mark_s) {
   __shared__ u64 red[8];
   if (threadIdx.x < 8) red[threadIdx.x] = 0;
   __syncthreads();  // (wave 0 zeroes red[]; every wave's lane 0 adds to red[0] below)
@@ -203,6 +230,10 @@ __global__ __launch_bounds__(SV_THREADS) void str_verify_kernel(const u64* __res
     r = rr[j];
     s = sr[j];
     keep = key_eq(R.chars, R.offsets, r, S.chars, S.offsets, s);
+    if (MARK && keep) {
+      mark_r[r] = 1;
+      mark_s[s] = 1;
+    }
   }
   if (MAT) {
     const u64 m = __ballot(keep);
@@ -269,14 +300,21 @@ __global__ __launch_bounds__(SV_THREADS) void str_compact_kernel(const u64* __re
   hmj::block_accumulate(red, acc + SA_ACC, v, 1u << hmj::ACC_XOR);
 }
 
-// Collision search (ordered): row i whose hash equals row i-1's but whose build key differs is recorded.
+// Collision search (ordered): row i whose hash equals row i-1's but whose build key differs is recorded.  MIXED (join
+// kinds): the rows' keys are row_key's (sr, S: the probe side).
+template <bool MIXED = false>
 __global__ __launch_bounds__(SV_THREADS) void str_mismatch_kernel(const u64* __restrict__ hk, const u64* __restrict__ rr, u64 n,
-                                                                  StrSide R, u64* __restrict__ list, u64* __restrict__ acc) {
+                                                                  StrSide R, u64* __restrict__ list, u64* __restrict__ acc,
+                                                                  const u64* __restrict__ sr, StrSide S) {
   const u64 i = (u64)blockIdx.x * SV_THREADS + threadIdx.x + 1;
   if (i >= n) return;
   if (hk[i] != hk[i - 1]) return;
-  const u64 a = rr[i - 1], b = rr[i];
-  if (a == b || key_eq(R.chars, R.offsets, a, R.chars, R.offsets, b)) return;
+  if constexpr (MIXED) {
+    if (same_key(row_key(R, S, rr, sr, i - 1), row_key(R, S, rr, sr, i))) return;
+  } else {
+    const u64 a = rr[i - 1], b = rr[i];
+    if (a == b || key_eq(R.chars, R.offsets, a, R.chars, R.offsets, b)) return;
+  }
   const u64 k = atomicAdd(&acc[SA_LIST_N], 1ull);
   if (k < kListCap) list[k] = i;
   else atomicOr(&acc[SA_ERR], 2ull);
@@ -284,10 +322,11 @@ __global__ __launch_bounds__(SV_THREADS) void str_mismatch_kernel(const u64* __r
 
 // One lane per recorded row i: its run [s, e) of equal hash (binary searches on the ascending hash column).  The lane whose
 // i is the FIRST mismatch of its run leads it (runs[2k], runs[2k + 1] = s, e); the others write an empty run.  A separate
-// launch from the sort, so that no leader test reads rows another workgroup is moving.
+// launch from the sort, so that no leader test reads rows another workgroup is moving.  MIXED as str_mismatch_kernel.
+template <bool MIXED = false>
 __global__ __launch_bounds__(SV_THREADS) void str_run_leader_kernel(const u64* __restrict__ hk, const u64* __restrict__ rr, u64 n,
                                                                     StrSide R, const u64* __restrict__ list, u64* __restrict__ runs,
-                                                                    u64* __restrict__ acc) {
+                                                                    u64* __restrict__ acc, const u64* __restrict__ sr, StrSide S) {
   const u64 cnt = acc[SA_LIST_N] < kListCap ? acc[SA_LIST_N] : kListCap;
   for (u64 k = (u64)blockIdx.x * SV_THREADS + threadIdx.x; k < cnt; k += (u64)gridDim.x * SV_THREADS) {
     const u64 i = list[k], h = hk[i];
@@ -314,8 +353,12 @@ __global__ __launch_bounds__(SV_THREADS) void str_run_leader_kernel(const u64* _
     }
     bool first = true;
     for (u64 t = s + 1; t < i && first; t++) {
-      const u64 a = rr[t - 1], b = rr[t];
-      if (a != b && !key_eq(R.chars, R.offsets, a, R.chars, R.offsets, b)) first = false;
+      if constexpr (MIXED) {
+        if (!same_key(row_key(R, S, rr, sr, t - 1), row_key(R, S, rr, sr, t))) first = false;
+      } else {
+        const u64 a = rr[t - 1], b = rr[t];
+        if (a != b && !key_eq(R.chars, R.offsets, a, R.chars, R.offsets, b)) first = false;
+      }
     }
     if (first) {
       runs[2 * k] = s;
@@ -326,9 +369,11 @@ __global__ __launch_bounds__(SV_THREADS) void str_run_leader_kernel(const u64* _
 
 // One workgroup per led run: rows sorted stably by build key bytes (rank = rows with a smaller key + rows before it with
 // the same key), written back in place.  All rows of a run share the hash, so only r_row, s_row, rval, sval move.
+// MIXED: by row_key (S: the probe side); a NULL column is absent (read as HMJ_STR_NO_ROW / 0, not written).
+template <bool MIXED = false>
 __global__ __launch_bounds__(SV_THREADS) void str_run_sort_kernel(const u64* __restrict__ runs, StrSide R, u64* __restrict__ o_r,
                                                                   u64* __restrict__ o_s, u64* __restrict__ o_rv,
-                                                                  u64* __restrict__ o_sv, const u64* __restrict__ acc) {
+                                                                  u64* __restrict__ o_sv, const u64* __restrict__ acc, StrSide S) {
   __shared__ u64 col[4][kRunCap];
   __shared__ u32 rank[kRunCap];
   const u64 cnt = acc[SA_LIST_N] < kListCap ? acc[SA_LIST_N] : kListCap;
@@ -337,32 +382,193 @@ __global__ __launch_bounds__(SV_THREADS) void str_run_sort_kernel(const u64* __r
     if (e <= s) continue;  // (uniform: not a leader)
     const u32 L = (u32)(e - s);
     for (u32 t = threadIdx.x; t < L; t += SV_THREADS) {
-      col[0][t] = o_r[s + t];
-      col[1][t] = o_s[s + t];
-      col[2][t] = o_rv[s + t];
-      col[3][t] = o_sv[s + t];
+      if constexpr (MIXED) {
+        col[0][t] = o_r ? o_r[s + t] : kNoRow;
+        col[1][t] = o_s ? o_s[s + t] : kNoRow;
+        col[2][t] = o_rv ? o_rv[s + t] : 0ull;
+        col[3][t] = o_sv ? o_sv[s + t] : 0ull;
+      } else {
+        col[0][t] = o_r[s + t];
+        col[1][t] = o_s[s + t];
+        col[2][t] = o_rv[s + t];
+        col[3][t] = o_sv[s + t];
+      }
     }
     __syncthreads();
     for (u32 t = threadIdx.x; t < L; t += SV_THREADS) {
-      const u64 me = col[0][t];
       u32 rk = 0;
-      for (u32 o = 0; o < L; o++) {
-        const u64 other = col[0][o];
-        const int c = other == me ? 0 : key_cmp(R.chars, R.offsets, other, R.chars, R.offsets, me);
-        rk += (c < 0 || (c == 0 && o < t)) ? 1u : 0u;
+      if constexpr (MIXED) {
+        const KeyRef me = key_of(R, S, col[0][t], col[1][t]);
+        for (u32 o = 0; o < L; o++) {
+          const KeyRef other = key_of(R, S, col[0][o], col[1][o]);
+          const int c = (other.offsets == me.offsets && other.row == me.row)
+                            ? 0
+                            : key_cmp(other.chars, other.offsets, other.row, me.chars, me.offsets, me.row);
+          rk += (c < 0 || (c == 0 && o < t)) ? 1u : 0u;
+        }
+      } else {
+        const u64 me = col[0][t];
+        for (u32 o = 0; o < L; o++) {
+          const u64 other = col[0][o];
+          const int c = other == me ? 0 : key_cmp(R.chars, R.offsets, other, R.chars, R.offsets, me);
+          rk += (c < 0 || (c == 0 && o < t)) ? 1u : 0u;
+        }
       }
       rank[t] = rk;
     }
     __syncthreads();
     for (u32 t = threadIdx.x; t < L; t += SV_THREADS) {
       const u64 d = s + rank[t];
-      o_r[d] = col[0][t];
-      o_s[d] = col[1][t];
-      o_rv[d] = col[2][t];
-      o_sv[d] = col[3][t];
+      if constexpr (MIXED) {
+        if (o_r) o_r[d] = col[0][t];
+        if (o_s) o_s[d] = col[1][t];
+        if (o_rv) o_rv[d] = col[2][t];
+        if (o_sv) o_sv[d] = col[3][t];
+      } else {
+        o_r[d] = col[0][t];
+        o_s[d] = col[1][t];
+        o_rv[d] = col[2][t];
+        o_sv[d] = col[3][t];
+      }
     }
     __syncthreads();
   }
+}
+
+// ---- join kinds --------------------------------------------------------------------------------------------------------
+// One lane per pair of a first-wins {hash,row} join: row krow[j] of the side asked about (K) against row orow[j] of the
+// other side (O), the one representative of its hash there.  Equal keys mark the K row (every writer stores 1).  Different
+// keys: the pair counts in acc[SA_DIFF] and, when amb != NULL, the K row goes on the ambiguous list as a {hash, row} row
+// (one counter add per wave) -- another O row of the same hash may still hold its key.
+__global__ __launch_bounds__(SV_THREADS) void str_rep_verify_kernel(const u64* __restrict__ hk, const u64* __restrict__ orow,
+                                                                    const u64* __restrict__ krow, u64 np, StrSide O, StrSide K,
+                                                                    unsigned char* __restrict__ mark, u64* __restrict__ amb,
+                                                                    u64* __restrict__ acc) {
+  const u64 j = (u64)blockIdx.x * SV_THREADS + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  bool diff = false;
+  u64 k = 0;
+  if (j < np) {
+    k = krow[j];
+    if (key_eq(O.chars, O.offsets, orow[j], K.chars, K.offsets, k)) mark[k] = 1;
+    else diff = true;
+  }
+  const u64 m = __ballot(diff);
+  if (!m) return;
+  u64 base = 0;
+  if (lane == 0) {
+    atomicAdd(&acc[SA_DIFF], (u64)__builtin_popcountll(m));
+    if (amb) base = atomicAdd(&acc[SA_AMB_N], (u64)__builtin_popcountll(m));
+  }
+  base = __shfl(base, 0, 64);
+  if (amb && diff) reinterpret_cast<ulonglong2*>(amb)[base + hmj::popc_below(m)] = make_ulonglong2(hk[j], k);
+}
+
+// A relation's rows as the kinds emit them: row i ({hash, i} in rows) is selected when (mark[i] != 0) == want.  probe: the
+// row goes out as (hash, NO_ROW, i, fill, vals[i]), else as (hash, i, NO_ROW, vals[i], fill); NULL columns are not written.
+struct Sweep {
+  const u64* rows;
+  const unsigned char* mark;
+  const u64* vals;
+  u64 n, fill;
+  u32 want, probe;
+};
+__device__ __forceinline__ void sweep_vals(const Sweep& W, u64 i, u64& rv, u64& sv) {
+  const u64 v = W.vals[i];
+  rv = W.probe ? W.fill : v;
+  sv = W.probe ? v : W.fill;
+}
+
+// Sweep pass 1.  MAT: selected rows per workgroup (blk_cnt).  Count modes: count, sums and checksums into acc.
+template <bool MAT>
+__global__ __launch_bounds__(SV_THREADS) void str_sweep_count_kernel(Sweep W, u64* __restrict__ blk_cnt, u64* __restrict__ acc,
+                                                                     int checksum) {
+  __shared__ u64 red[8];
+  if (threadIdx.x < 8) red[threadIdx.x] = 0;
+  __syncthreads();
+  const u64 i = (u64)blockIdx.x * SV_THREADS + threadIdx.x;
+  const bool sel = i < W.n && ((W.mark[i] != 0) == (W.want != 0));
+  if (MAT) {
+    const u64 m = __ballot(sel);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(&red[0], (u64)__builtin_popcountll(m));
+    __syncthreads();
+    if (threadIdx.x == 0) blk_cnt[blockIdx.x] = red[0];
+  } else {
+    u64 v[6] = {0, 0, 0, 0, 0, 0};
+    if (sel) {
+      const u64 h = W.rows[2 * i];
+      u64 rv, sv;
+      sweep_vals(W, i, rv, sv);
+      v[hmj::ACC_N] = 1;
+      v[hmj::ACC_SUM_R] = rv;
+      v[hmj::ACC_SUM_S] = sv;
+      if (checksum) {
+        const u64 t = hmj::tmix(h, rv, sv);
+        v[hmj::ACC_XOR] = t;
+        v[hmj::ACC_MIX] = t;
+      }
+    }
+    hmj::block_accumulate(red, acc + SA_ACC, v, 1u << hmj::ACC_XOR);
+  }
+}
+
+// Sweep pass 2: the selected rows of workgroup b go, in row order, to rows [blk_off[b], ..) of the result columns; count,
+// sums and checksums into acc.
+__global__ __launch_bounds__(SV_THREADS) void str_sweep_emit_kernel(Sweep W, const u64* __restrict__ blk_off, u64* __restrict__ o_hash,
+                                                                    u64* __restrict__ o_r, u64* __restrict__ o_s, u64* __restrict__ o_rv,
+                                                                    u64* __restrict__ o_sv, u64* __restrict__ acc, int checksum) {
+  __shared__ u64 red[8];
+  __shared__ u32 wcnt[SV_THREADS / 64];
+  if (threadIdx.x < 8) red[threadIdx.x] = 0;
+  const u64 i = (u64)blockIdx.x * SV_THREADS + threadIdx.x;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const bool sel = i < W.n && ((W.mark[i] != 0) == (W.want != 0));
+  const u64 m = __ballot(sel);
+  if (lane == 0) wcnt[w] = (u32)__builtin_popcountll(m);
+  __syncthreads();
+  u64 v[6] = {0, 0, 0, 0, 0, 0};
+  if (sel) {
+    u64 pos = blk_off[blockIdx.x] + hmj::popc_below(m);
+    for (int k = 0; k < w; k++) pos += wcnt[k];
+    const u64 h = W.rows[2 * i];
+    u64 rv, sv;
+    sweep_vals(W, i, rv, sv);
+    o_hash[pos] = h;
+    if (o_r) o_r[pos] = W.probe ? kNoRow : i;
+    if (o_s) o_s[pos] = W.probe ? i : kNoRow;
+    if (o_rv) o_rv[pos] = rv;
+    if (o_sv) o_sv[pos] = sv;
+    v[hmj::ACC_N] = 1;
+    v[hmj::ACC_SUM_R] = rv;
+    v[hmj::ACC_SUM_S] = sv;
+    if (checksum) {
+      const u64 t = hmj::tmix(h, rv, sv);
+      v[hmj::ACC_XOR] = t;
+      v[hmj::ACC_MIX] = t;
+    }
+  }
+  hmj::block_accumulate(red, acc + SA_ACC, v, 1u << hmj::ACC_XOR);
+}
+
+// Ordered kinds: (hash, index) rows for the stable u64 sort, then the five columns gathered in the sorted order.
+__global__ __launch_bounds__(SV_THREADS) void str_sort_rows_kernel(const u64* __restrict__ hk, u64 n, u64* __restrict__ rows) {
+  const u64 i = (u64)blockIdx.x * SV_THREADS + threadIdx.x;
+  if (i < n) reinterpret_cast<ulonglong2*>(rows)[i] = make_ulonglong2(hk[i], i);
+}
+__global__ __launch_bounds__(SV_THREADS) void str_gather_kernel(const u64* __restrict__ sorted, u64 n, const u64* __restrict__ i_r,
+                                                                const u64* __restrict__ i_s, const u64* __restrict__ i_rv,
+                                                                const u64* __restrict__ i_sv, u64* __restrict__ o_hash,
+                                                                u64* __restrict__ o_r, u64* __restrict__ o_s, u64* __restrict__ o_rv,
+                                                                u64* __restrict__ o_sv) {
+  const u64 j = (u64)blockIdx.x * SV_THREADS + threadIdx.x;
+  if (j >= n) return;
+  const ulonglong2 e = reinterpret_cast<const ulonglong2*>(sorted)[j];
+  const u64 p = e.y;
+  o_hash[j] = e.x;
+  if (o_r) o_r[j] = i_r[p];
+  if (o_s) o_s[j] = i_s[p];
+  if (o_rv) o_rv[j] = i_rv[p];
+  if (o_sv) o_sv[j] = i_sv[p];
 }
 
 }  // namespace
@@ -508,7 +714,7 @@ int join_str(hmj_ctx* c, const hmj_str_rel* R, const hmj_str_rel* S, uint32_t fl
     DevBuf* cols[5] = {&c->str_hash, &c->str_rrow, &c->str_srow, &c->str_rval, &c->str_sval};
     for (DevBuf* b : cols) RC_TRY(ensure_dev(c, *b, n_pairs * sizeof(u64)));
     hipLaunchKernelGGL(str_verify_kernel<true>, dim3((u32)nblk), dim3(SV_THREADS), 0, c->stream, ik, ir, is,
-                       n_pairs, RS, SS, (u64*)c->str_flags.p, (u64*)c->str_blk.p, acc_v, 0);
+                       n_pairs, RS, SS, (u64*)c->str_flags.p, (u64*)c->str_blk.p, acc_v, 0, nullptr, nullptr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hmj::launch_scan_u64((const u64*)c->str_blk.p, (u64*)c->str_blk_off.p, (u32)nblk, c->stream));
     hipLaunchKernelGGL(str_compact_kernel, dim3((u32)nblk), dim3(SV_THREADS), 0, c->stream, ik, ir, is, n_pairs,
@@ -518,7 +724,7 @@ int join_str(hmj_ctx* c, const hmj_str_rel* R, const hmj_str_rel* S, uint32_t fl
     RC_TRY(read_back(c, (const u64*)c->str_blk_off.p + nblk, &n_out, sizeof(u64)));
   } else if (n_pairs) {
     hipLaunchKernelGGL(str_verify_kernel<false>, dim3((u32)nblk), dim3(SV_THREADS), 0, c->stream, ik, ir, is,
-                       n_pairs, RS, SS, nullptr, nullptr, acc_v, checksum ? 1 : 0);
+                       n_pairs, RS, SS, nullptr, nullptr, acc_v, checksum ? 1 : 0, nullptr, nullptr);
     HIP_TRY(hipGetLastError());
   }
   RC_TRY(record(c, 3));
@@ -528,17 +734,18 @@ int join_str(hmj_ctx* c, const hmj_str_rel* R, const hmj_str_rel* S, uint32_t fl
     RC_TRY(ensure_dev(c, c->str_list, cap * sizeof(u64)));
     RC_TRY(ensure_dev(c, c->str_runs, 2 * cap * sizeof(u64)));
     const u64 g = (n_out - 1 + SV_THREADS - 1) / SV_THREADS;
-    hipLaunchKernelGGL(str_mismatch_kernel, dim3((u32)g), dim3(SV_THREADS), 0, c->stream, (const u64*)c->str_hash.p,
-                       (const u64*)c->str_rrow.p, n_out, RS, (u64*)c->str_list.p, acc_v);
+    hipLaunchKernelGGL(str_mismatch_kernel<false>, dim3((u32)g), dim3(SV_THREADS), 0, c->stream, (const u64*)c->str_hash.p,
+                       (const u64*)c->str_rrow.p, n_out, RS, (u64*)c->str_list.p, acc_v, nullptr, StrSide{});
     HIP_TRY(hipGetLastError());
     const u64 gl = (cap + SV_THREADS - 1) / SV_THREADS;
-    hipLaunchKernelGGL(str_run_leader_kernel, dim3((u32)(gl < 1024 ? gl : 1024)), dim3(SV_THREADS), 0, c->stream,
+    hipLaunchKernelGGL(str_run_leader_kernel<false>, dim3((u32)(gl < 1024 ? gl : 1024)), dim3(SV_THREADS), 0, c->stream,
                        (const u64*)c->str_hash.p, (const u64*)c->str_rrow.p, n_out, RS, (const u64*)c->str_list.p,
-                       (u64*)c->str_runs.p, acc_v);
+                       (u64*)c->str_runs.p, acc_v, nullptr, StrSide{});
     HIP_TRY(hipGetLastError());
     const u64 gs = cap < (u64)(4 * c->num_cus) ? cap : (u64)(4 * c->num_cus);
-    hipLaunchKernelGGL(str_run_sort_kernel, dim3((u32)gs), dim3(SV_THREADS), 0, c->stream, (const u64*)c->str_runs.p, RS,
-                       (u64*)c->str_rrow.p, (u64*)c->str_srow.p, (u64*)c->str_rval.p, (u64*)c->str_sval.p, (const u64*)acc_v);
+    hipLaunchKernelGGL(str_run_sort_kernel<false>, dim3((u32)gs), dim3(SV_THREADS), 0, c->stream, (const u64*)c->str_runs.p, RS,
+                       (u64*)c->str_rrow.p, (u64*)c->str_srow.p, (u64*)c->str_rval.p, (u64*)c->str_sval.p, (const u64*)acc_v,
+                       StrSide{});
     HIP_TRY(hipGetLastError());
   }
   RC_TRY(record(c, 4));
@@ -561,6 +768,270 @@ int join_str(hmj_ctx* c, const hmj_str_rel* R, const hmj_str_rel* S, uint32_t fl
     out->sval = (const uint64_t*)c->str_sval.p;
   }
   opts->n_collisions = n_pairs - out->n_matches;
+  return HMJ_OK;
+}
+
+// ---- join kinds (hmj_join_kind_str_device) -------------------------------------------------------------------------
+// workload_signature kinds of the {hash,row} joins the kinds run (u64 joins 0, sorts 1, u64 kinds 3..9, inner string join
+// 15): none of them teaches a join of another entry anything
+constexpr int kMemoProbeRep = 10;  // first-wins join, probe rows against build representatives (probe SEMI / ANTI)
+constexpr int kMemoBuildRep = 11;  // ... build rows against probe representatives (BUILD_SEMI / BUILD_ANTI)
+constexpr int kMemoAmbiguous = 12; // the ambiguous rows against every row of their hash on the other side
+constexpr int kMemoPairs = 13;     // the outer kinds' pair join
+constexpr int kKindAccBlocks = 5;  // acc: [0] / [1] hashing, [2] verification, [3] probe sweep, [4] build sweep
+
+int memo_join(hmj_ctx* c, const void* Rr, u64 nr, const void* Sr, u64 ns, uint32_t flags, int memo, hmj_result* out) {
+  spans_reset(c);
+  const int st = span_begin(c, K_TOTAL, -1);
+  c->memo_kind = memo;
+  const int rc = join_device(c, Rr, nr, Sr, ns, flags, out, false);
+  c->memo_kind = 0;
+  span_end(c, st);
+  if (c->profiling) {
+    (void)hipStreamSynchronize(c->stream);
+    spans_collect(c);
+  }
+  return rc;
+}
+
+u64 blocks_of(u64 n) { return (n + SV_THREADS - 1) / SV_THREADS; }
+
+int join_str_kind(hmj_ctx* c, const hmj_str_rel* R, const hmj_str_rel* S, uint32_t flags, hmj_str_kind_opts* o, hmj_str_result* out) {
+  const u64 nb = R->n, np = S->n;
+  const u32 bits = o->hash_bits, kind = o->kind;
+  if (flags & HMJ_ORDERED) flags |= HMJ_MATERIALIZE;
+  const bool mat = flags & HMJ_MATERIALIZE, ordered = flags & HMJ_ORDERED, checksum = flags & HMJ_CHECKSUM;
+  const bool bside = o->side == HMJ_KIND_BUILD_SIDE;
+  // semi / anti of either side (HMJ_JOIN_SEMI == HMJ_BUILD_SEMI, HMJ_JOIN_ANTI == HMJ_BUILD_ANTI), else an outer kind
+  const bool semi_anti = kind == HMJ_JOIN_SEMI || kind == HMJ_JOIN_ANTI;
+  const bool sweep_p = bside ? kind == HMJ_FULL_OUTER : true;
+  const bool sweep_b = bside;
+  c->prep.valid = false;  // like any other call, a string join discards a prepared build side
+  std::memset(&c->plan, 0, sizeof(c->plan));
+  c->plan.struct_size = sizeof(c->plan);
+  std::memset(&c->timing, 0, sizeof(c->timing));
+  RC_TRY(ensure_dev(c, c->str_acc, kKindAccBlocks * SA_N * sizeof(u64)));
+  RC_TRY(ensure_dev(c, c->str_rows_r, 16 * (nb ? nb : 1)));
+  RC_TRY(ensure_dev(c, c->str_rows_s, 16 * (np ? np : 1)));
+  RC_TRY(ensure_dev(c, c->str_mark_r, nb ? nb : 1));
+  RC_TRY(ensure_dev(c, c->str_mark_s, np ? np : 1));
+  u64* acc = (u64*)c->str_acc.p;
+  u64* acc_v = acc + 2 * SA_N;
+  u64 h[kKindAccBlocks * SA_N];
+  // 1. {hash, row} rows of both relations (+ the probe payloads' sum), marks cleared
+  RC_TRY(record(c, 0));
+  HIP_TRY(hipMemsetAsync(acc, 0, kKindAccBlocks * SA_N * sizeof(u64), c->stream));
+  HIP_TRY(hipMemsetAsync(acc + SA_BAD_ROW, 0xFF, sizeof(u64), c->stream));
+  HIP_TRY(hipMemsetAsync(acc + SA_N + SA_BAD_ROW, 0xFF, sizeof(u64), c->stream));
+  RC_TRY(launch_hash(c, R->chars, (const u64*)R->offsets, nb, bits, (u64*)c->str_rows_r.p, true, nullptr, acc));
+  RC_TRY(launch_hash(c, S->chars, (const u64*)S->offsets, np, bits, (u64*)c->str_rows_s.p, true,
+                     (flags & HMJ_SUM_PROBE) ? (const u64*)S->vals : nullptr, acc + SA_N));
+  if (nb) HIP_TRY(hipMemsetAsync(c->str_mark_r.p, 0, nb, c->stream));
+  if (np) HIP_TRY(hipMemsetAsync(c->str_mark_s.p, 0, np, c->stream));
+  RC_TRY(record(c, 1));
+  RC_TRY(read_back(c, acc, h, 2 * SA_N * sizeof(u64)));
+  RC_TRY(hash_errors(c, h, "build"));
+  RC_TRY(hash_errors(c, h + SA_N, "probe"));
+  if (flags & HMJ_SUM_PROBE) out->sum_probe_all = h[SA_N + SA_ACC + hmj::ACC_SUM_P];
+  const StrSide RS{(const unsigned char*)R->chars, (const u64*)R->offsets, (const u64*)R->vals},
+      SS{(const unsigned char*)S->chars, (const u64*)S->offsets, (const u64*)S->vals};
+  unsigned char *mark_r = (unsigned char*)c->str_mark_r.p, *mark_s = (unsigned char*)c->str_mark_s.p;
+  // 2. + 3. the {hash,row} join(s) and the key verification, which marks the rows that have a partner
+  u64 n_pairs = 0;
+  hmj_result inner;
+  std::memset(&inner, 0, sizeof(inner));
+  if (semi_anti) {
+    // every row of the side asked about (K) meets the FIRST row of its hash on the other side (O), in row order
+    const u64 nK = bside ? nb : np, nO = bside ? np : nb;
+    const void *rowsK = bside ? c->str_rows_r.p : c->str_rows_s.p, *rowsO = bside ? c->str_rows_s.p : c->str_rows_r.p;
+    const StrSide &KS = bside ? RS : SS, &OS = bside ? SS : RS;
+    unsigned char* mark = bside ? mark_r : mark_s;
+    if (nK && nO) {
+      hmj_result rep;
+      RC_TRY(memo_join(c, rowsO, nO, rowsK, nK, HMJ_MATERIALIZE | HMJ_FIRST_WINS, bside ? kMemoBuildRep : kMemoProbeRep, &rep));
+      RC_TRY(record(c, 2));
+      n_pairs = rep.n_matches;  // <= nK
+      if (n_pairs) {
+        RC_TRY(ensure_dev(c, c->str_amb, 16 * n_pairs));
+        hipLaunchKernelGGL(str_rep_verify_kernel, dim3((u32)blocks_of(n_pairs)), dim3(SV_THREADS), 0, c->stream, (const u64*)rep.key,
+                           (const u64*)rep.rval, (const u64*)rep.sval, n_pairs, OS, KS, mark, (u64*)c->str_amb.p, acc_v);
+        HIP_TRY(hipGetLastError());
+        RC_TRY(read_back(c, acc_v, h, SA_N * sizeof(u64)));
+        const u64 n_amb = h[SA_AMB_N];
+        if (n_amb) {  // (a real hash collision: a representative's key differs from the row's)
+          hmj_result all;
+          RC_TRY(memo_join(c, rowsO, nO, c->str_amb.p, n_amb, HMJ_MATERIALIZE, kMemoAmbiguous, &all));
+          n_pairs += all.n_matches;
+          if (all.n_matches) {
+            hipLaunchKernelGGL(str_rep_verify_kernel, dim3((u32)blocks_of(all.n_matches)), dim3(SV_THREADS), 0, c->stream,
+                               (const u64*)all.key, (const u64*)all.rval, (const u64*)all.sval, all.n_matches, OS, KS, mark,
+                               nullptr, acc_v);
+            HIP_TRY(hipGetLastError());
+          }
+        }
+      }
+    } else {
+      RC_TRY(record(c, 2));
+    }
+  } else if (nb && np) {
+    RC_TRY(memo_join(c, c->str_rows_r.p, nb, c->str_rows_s.p, np, HMJ_MATERIALIZE | (flags & HMJ_ORDERED), kMemoPairs, &inner));
+    RC_TRY(record(c, 2));
+    n_pairs = inner.n_matches;
+  } else {
+    RC_TRY(record(c, 2));
+  }
+  if (blocks_of(n_pairs) > 0xFFFFFFFFull) return fail(c, HMJ_E_UNSUPPORTED, "string join: more than 2^40 pairs of equal hash");
+  o->n_hash_pairs = n_pairs;
+  // result rows: the verified pairs (outer kinds), then the probe sweep's rows, then the build sweep's
+  const u64 nblk_v = semi_anti ? 0 : blocks_of(n_pairs);
+  const u64 nblk_p = sweep_p ? blocks_of(np) : 0, nblk_b = sweep_b ? blocks_of(nb) : 0;
+  const u64 nblk = nblk_v + nblk_p + nblk_b;
+  const u64 cap = (semi_anti ? 0 : n_pairs) + (sweep_p ? np : 0) + (sweep_b ? nb : 0);
+  DevBuf* cols[5] = {&c->str_hash, &c->str_rrow, &c->str_srow, &c->str_rval, &c->str_sval};
+  if (mat) {
+    RC_TRY(ensure_dev(c, c->str_flags, (nblk_v ? nblk_v : 1) * (SV_THREADS / 64) * sizeof(u64)));
+    RC_TRY(ensure_dev(c, c->str_blk, (nblk ? nblk : 1) * sizeof(u64)));
+    RC_TRY(ensure_dev(c, c->str_blk_off, (nblk + 1) * sizeof(u64)));
+    for (DevBuf* b : cols) RC_TRY(ensure_dev(c, *b, (cap ? cap : 1) * sizeof(u64)));
+  }
+  const u64 *ik = (const u64*)inner.key, *ir = (const u64*)inner.rval, *is = (const u64*)inner.sval;
+  if (nblk_v && mat) {
+    hipLaunchKernelGGL((str_verify_kernel<true, true>), dim3((u32)nblk_v), dim3(SV_THREADS), 0, c->stream, ik, ir, is, n_pairs, RS,
+                       SS, (u64*)c->str_flags.p, (u64*)c->str_blk.p, acc_v, 0, mark_r, mark_s);
+    HIP_TRY(hipGetLastError());
+  } else if (nblk_v) {
+    hipLaunchKernelGGL((str_verify_kernel<false, true>), dim3((u32)nblk_v), dim3(SV_THREADS), 0, c->stream, ik, ir, is, n_pairs, RS,
+                       SS, nullptr, nullptr, acc_v, checksum ? 1 : 0, mark_r, mark_s);
+    HIP_TRY(hipGetLastError());
+  }
+  RC_TRY(record(c, 3));
+  // 4. the sweeps: SEMI / BUILD_SEMI take the marked rows, every other kind the unmarked ones
+  const u32 want = kind == HMJ_JOIN_SEMI ? 1u : 0u;
+  const u64 pfill = !semi_anti && (!bside || kind == HMJ_FULL_OUTER) ? o->probe_fill : 0ull;
+  const u64 bfill = !semi_anti && bside ? o->build_fill : 0ull;
+  const Sweep WP{(const u64*)c->str_rows_s.p, mark_s, SS.vals, np, pfill, want, 1u};
+  const Sweep WB{(const u64*)c->str_rows_r.p, mark_r, RS.vals, nb, bfill, want, 0u};
+  u64* acc_p = acc + 3 * SA_N;
+  u64* acc_b = acc + 4 * SA_N;
+  u64 n_out = 0, n_in = 0;  // result rows; of those, verified pairs (materialising)
+  u64* oc[5] = {(u64*)c->str_hash.p, (u64*)c->str_rrow.p, (u64*)c->str_srow.p, (u64*)c->str_rval.p, (u64*)c->str_sval.p};
+  if (semi_anti && !bside) oc[1] = oc[3] = nullptr;  // (hash, s_row, sval)
+  if (semi_anti && bside) oc[2] = oc[4] = nullptr;   // (hash, r_row, rval)
+  if (mat) {
+    u64* blk = (u64*)c->str_blk.p;
+    const u64* blk_off = (const u64*)c->str_blk_off.p;
+    if (nblk_p)
+      hipLaunchKernelGGL(str_sweep_count_kernel<true>, dim3((u32)nblk_p), dim3(SV_THREADS), 0, c->stream, WP, blk + nblk_v, nullptr, 0);
+    if (nblk_b)
+      hipLaunchKernelGGL(str_sweep_count_kernel<true>, dim3((u32)nblk_b), dim3(SV_THREADS), 0, c->stream, WB, blk + nblk_v + nblk_p,
+                         nullptr, 0);
+    HIP_TRY(hipGetLastError());
+    if (nblk) HIP_TRY(hmj::launch_scan_u64(blk, (u64*)c->str_blk_off.p, (u32)nblk, c->stream));
+    if (nblk_v) {
+      hipLaunchKernelGGL(str_compact_kernel, dim3((u32)nblk_v), dim3(SV_THREADS), 0, c->stream, ik, ir, is, n_pairs, RS, SS,
+                         (const u64*)c->str_flags.p, blk_off, oc[0], oc[1], oc[2], oc[3], oc[4], acc_v, checksum ? 1 : 0);
+    }
+    if (nblk_p)
+      hipLaunchKernelGGL(str_sweep_emit_kernel, dim3((u32)nblk_p), dim3(SV_THREADS), 0, c->stream, WP, blk_off + nblk_v, oc[0], oc[1],
+                         oc[2], oc[3], oc[4], acc_p, checksum ? 1 : 0);
+    if (nblk_b)
+      hipLaunchKernelGGL(str_sweep_emit_kernel, dim3((u32)nblk_b), dim3(SV_THREADS), 0, c->stream, WB, blk_off + nblk_v + nblk_p,
+                         oc[0], oc[1], oc[2], oc[3], oc[4], acc_b, checksum ? 1 : 0);
+    HIP_TRY(hipGetLastError());
+    if (nblk) {
+      HIP_TRY(hipMemcpyAsync(&n_in, blk_off + nblk_v, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+      RC_TRY(read_back(c, blk_off + nblk, &n_out, sizeof(u64)));
+    }
+  } else {
+    if (nblk_p)
+      hipLaunchKernelGGL(str_sweep_count_kernel<false>, dim3((u32)nblk_p), dim3(SV_THREADS), 0, c->stream, WP, nullptr, acc_p,
+                         checksum ? 1 : 0);
+    if (nblk_b)
+      hipLaunchKernelGGL(str_sweep_count_kernel<false>, dim3((u32)nblk_b), dim3(SV_THREADS), 0, c->stream, WB, nullptr, acc_b,
+                         checksum ? 1 : 0);
+    HIP_TRY(hipGetLastError());
+  }
+  RC_TRY(record(c, 4));
+  // 5. ordered: a stable sort of (hash, index) rows, the columns gathered in that order, then runs of equal hash with
+  // several keys sorted by key bytes.  (Outer kinds without unmatched rows are already in (hash, r_row, s_row) order.)
+  if (ordered && n_out > 1) {
+    if (n_out > n_in) {
+      RC_TRY(ensure_dev(c, c->str_ord, 32 * n_out));
+      u64* ord = (u64*)c->str_ord.p;
+      hipLaunchKernelGGL(str_sort_rows_kernel, dim3((u32)blocks_of(n_out)), dim3(SV_THREADS), 0, c->stream, oc[0], n_out, ord);
+      HIP_TRY(hipGetLastError());
+      const hmj_plan_desc plan = c->plan;  // (the sort is not a join: hmj_last_plan / hmj_last_timing keep describing the last one)
+      const hmj_timing timing = c->timing;
+      const int rc = hmj_sort_u64_device(c, ord, n_out, ord + 2 * n_out);
+      c->plan = plan;
+      c->timing = timing;
+      if (rc != HMJ_OK) return rc;
+      DevBuf* kc[5] = {&c->str_khash, &c->str_krrow, &c->str_ksrow, &c->str_krval, &c->str_ksval};
+      u64* nc[5];
+      for (int k = 0; k < 5; k++) {
+        nc[k] = nullptr;
+        if (!oc[k]) continue;
+        RC_TRY(ensure_dev(c, *kc[k], n_out * sizeof(u64)));
+        nc[k] = (u64*)kc[k]->p;
+      }
+      hipLaunchKernelGGL(str_gather_kernel, dim3((u32)blocks_of(n_out)), dim3(SV_THREADS), 0, c->stream, (const u64*)(ord + 2 * n_out),
+                         n_out, oc[1], oc[2], oc[3], oc[4], nc[0], nc[1], nc[2], nc[3], nc[4]);
+      HIP_TRY(hipGetLastError());
+      for (int k = 0; k < 5; k++) oc[k] = nc[k];
+    }
+    const u64 lcap = n_out < kListCap ? n_out : kListCap;
+    RC_TRY(ensure_dev(c, c->str_list, lcap * sizeof(u64)));
+    RC_TRY(ensure_dev(c, c->str_runs, 2 * lcap * sizeof(u64)));
+    hipLaunchKernelGGL(str_mismatch_kernel<true>, dim3((u32)blocks_of(n_out - 1)), dim3(SV_THREADS), 0, c->stream, (const u64*)oc[0],
+                       (const u64*)oc[1], n_out, RS, (u64*)c->str_list.p, acc_v, (const u64*)oc[2], SS);
+    HIP_TRY(hipGetLastError());
+    const u64 gl = blocks_of(lcap);
+    hipLaunchKernelGGL(str_run_leader_kernel<true>, dim3((u32)(gl < 1024 ? gl : 1024)), dim3(SV_THREADS), 0, c->stream,
+                       (const u64*)oc[0], (const u64*)oc[1], n_out, RS, (const u64*)c->str_list.p, (u64*)c->str_runs.p, acc_v,
+                       (const u64*)oc[2], SS);
+    HIP_TRY(hipGetLastError());
+    const u64 gs = lcap < (u64)(4 * c->num_cus) ? lcap : (u64)(4 * c->num_cus);
+    hipLaunchKernelGGL(str_run_sort_kernel<true>, dim3((u32)gs), dim3(SV_THREADS), 0, c->stream, (const u64*)c->str_runs.p, RS, oc[1],
+                       oc[2], oc[3], oc[4], (const u64*)acc_v, SS);
+    HIP_TRY(hipGetLastError());
+  }
+  RC_TRY(record(c, 5));
+  RC_TRY(read_back(c, acc_v, h + 2 * SA_N, 3 * SA_N * sizeof(u64)));
+  const u64 *av = h + 2 * SA_N, *ap = h + 3 * SA_N, *ab = h + 4 * SA_N;
+  if (av[SA_ERR] & 1) return fail(c, HMJ_E_UNSUPPORTED, "string join: a run of equal hash with several distinct keys holds more than 1024 rows");
+  if (av[SA_ERR] & 2) return fail(c, HMJ_E_UNSUPPORTED, "string join: more than 2^22 adjacent rows of equal hash with different keys");
+  // the sweeps count their rows in their acc blocks; the verified pairs: the scan (materialising) or acc (count modes)
+  const u64 n_p = ap[SA_ACC + hmj::ACC_N], n_b = ab[SA_ACC + hmj::ACC_N];
+  if (!mat) n_in = av[SA_ACC + hmj::ACC_N];
+  out->n_matches = n_in + n_p + n_b;
+  out->sum_r = av[SA_ACC + hmj::ACC_SUM_R] + ap[SA_ACC + hmj::ACC_SUM_R] + ab[SA_ACC + hmj::ACC_SUM_R];
+  out->sum_s = av[SA_ACC + hmj::ACC_SUM_S] + ap[SA_ACC + hmj::ACC_SUM_S] + ab[SA_ACC + hmj::ACC_SUM_S];
+  if (checksum) {
+    out->xor_fold = av[SA_ACC + hmj::ACC_XOR] ^ ap[SA_ACC + hmj::ACC_XOR] ^ ab[SA_ACC + hmj::ACC_XOR];
+    out->mix_sum = av[SA_ACC + hmj::ACC_MIX] + ap[SA_ACC + hmj::ACC_MIX] + ab[SA_ACC + hmj::ACC_MIX];
+  }
+  if (mat) {
+    out->hash = (const uint64_t*)oc[0];
+    out->r_row = (const uint64_t*)oc[1];
+    out->s_row = (const uint64_t*)oc[2];
+    out->rval = (const uint64_t*)oc[3];
+    out->sval = (const uint64_t*)oc[4];
+  }
+  o->n_collisions = semi_anti ? av[SA_DIFF] : n_pairs - n_in;
+  // the counters the u64 entry of the kind fills
+  hmj_kind_counts& k = o->counts;
+  std::memset(&k, 0, sizeof(k));
+  if (!bside) {
+    k.n_probe_unmatched = kind == HMJ_JOIN_SEMI ? np - n_p : n_p;
+    k.n_probe_matched = np - k.n_probe_unmatched;
+  } else {
+    k.n_build_unmatched = kind == HMJ_BUILD_SEMI ? nb - n_b : n_b;
+    k.n_build_matched = nb - k.n_build_unmatched;
+    if (kind == HMJ_FULL_OUTER) {
+      k.n_probe_unmatched = n_p;
+      k.n_probe_matched = np - n_p;
+    }
+  }
   return HMJ_OK;
 }
 
@@ -608,6 +1079,58 @@ int hmj_join_str_device(hmj_ctx* c, const hmj_str_rel* build, const hmj_str_rel*
     o.ms_join = elapsed(c, 1, 2);
     o.ms_verify = elapsed(c, 2, 3);
     o.ms_order = elapsed(c, 3, 4);
+  }
+  const uint32_t room = opts->struct_size < sizeof(o) ? opts->struct_size : (uint32_t)sizeof(o);
+  o.struct_size = opts->struct_size;
+  std::memcpy(opts, &o, room);
+  return HMJ_OK;
+}
+
+int hmj_join_kind_str_device(hmj_ctx* c, const hmj_str_rel* build, const hmj_str_rel* probe, uint32_t flags, hmj_str_kind_opts* opts,
+                             hmj_str_result* out) {
+  if (!c) return HMJ_E_ARG;
+  if (!opts || !out) return fail(c, HMJ_E_ARG, "opts / out is NULL");
+  if (opts->struct_size < offsetof(hmj_str_kind_opts, build_fill) + sizeof(opts->build_fill))
+    return fail(c, HMJ_E_ARG, "hmj_str_kind_opts.struct_size too small");
+  if (opts->side > HMJ_KIND_BUILD_SIDE) return fail(c, HMJ_E_ARG, "unknown join side");
+  if (opts->side == HMJ_KIND_PROBE_SIDE ? opts->kind > HMJ_JOIN_PROBE_OUTER : (opts->kind < HMJ_BUILD_SEMI || opts->kind > HMJ_FULL_OUTER))
+    return fail(c, HMJ_E_ARG, "unknown join kind");
+  if (opts->hash_bits > 63) return fail(c, HMJ_E_ARG, "hash_bits > 63");
+  if (flags & HMJ_FIRST_WINS) return fail(c, HMJ_E_ARG, "HMJ_FIRST_WINS is not defined for string joins");
+  RC_TRY(check_str_rel(c, build, "build"));
+  RC_TRY(check_str_rel(c, probe, "probe"));
+  std::memset(out, 0, sizeof(*out));
+  HIP_TRY(hipSetDevice(c->device));
+  // the out fields of opts go to a full-size copy first; the caller gets the prefix its struct_size holds
+  hmj_str_kind_opts o;
+  std::memset(&o, 0, sizeof(o));
+  std::memcpy(&o, opts, opts->struct_size < sizeof(o) ? opts->struct_size : sizeof(o));
+  std::memset(&o.counts, 0, sizeof(o) - offsetof(hmj_str_kind_opts, counts));
+  if (o.side == HMJ_KIND_PROBE_SIDE && o.kind == HMJ_JOIN_INNER) {  // exactly the inner string join
+    hmj_str_join_opts jo;
+    std::memset(&jo, 0, sizeof(jo));
+    jo.struct_size = sizeof(jo);
+    jo.hash_bits = o.hash_bits;
+    RC_TRY(join_str(c, build, probe, flags, &jo, out));
+    o.n_hash_pairs = jo.n_hash_pairs;
+    o.n_collisions = jo.n_collisions;
+    if (c->profiling) {
+      (void)hipStreamSynchronize(c->stream);
+      o.ms_hash = elapsed(c, 0, 1);
+      o.ms_join = elapsed(c, 1, 2);
+      o.ms_verify = elapsed(c, 2, 3);
+      o.ms_order = elapsed(c, 3, 4);
+    }
+  } else {
+    RC_TRY(join_str_kind(c, build, probe, flags, &o, out));
+    if (c->profiling) {
+      (void)hipStreamSynchronize(c->stream);
+      o.ms_hash = elapsed(c, 0, 1);
+      o.ms_join = elapsed(c, 1, 2);
+      o.ms_verify = elapsed(c, 2, 3);
+      o.ms_emit = elapsed(c, 3, 4);
+      o.ms_order = elapsed(c, 4, 5);
+    }
   }
   const uint32_t room = opts->struct_size < sizeof(o) ? opts->struct_size : (uint32_t)sizeof(o);
   o.struct_size = opts->struct_size;

@@ -438,6 +438,47 @@ class Executor:
         self._check(self.L.hmj_gen_uniform_domain_u64_device(self.h, C.c_void_p(t.data_ptr()), n, start, domain, seed, zseed))
         return t
 
+    def join_kind_str_device(self, build, probe, side, kind, flags=0, hash_bits=0, probe_fill=0, build_fill=0):
+        """Semi / anti / outer joins of two string-keyed device relations (hmj_join_kind_str_device).  side / kind as for
+        hmj_exchange_kind_opts: HMJ_KIND_PROBE_SIDE with HMJ_JOIN_*, or HMJ_KIND_BUILD_SIDE with HMJ_BUILD_* / HMJ_FULL_OUTER;
+        build / probe as for `join_str_device`.  Returns (StrResult, {"n_probe_matched", "n_probe_unmatched",
+        "n_build_matched", "n_build_unmatched", "n_hash_pairs", "n_collisions", "ms_hash", "ms_join", "ms_verify",
+        "ms_emit", "ms_order"}); read the rows with `str_kind_rows_to_numpy`."""
+        self._sync_stream()
+        rb, rp = self._str_rel(build), self._str_rel(probe)
+        opts = _lib.StrKindOpts()
+        opts.struct_size = C.sizeof(_lib.StrKindOpts)
+        opts.side = int(side)
+        opts.kind = int(kind)
+        opts.hash_bits = int(hash_bits)
+        opts.probe_fill = int(probe_fill) & 0xFFFFFFFFFFFFFFFF
+        opts.build_fill = int(build_fill) & 0xFFFFFFFFFFFFFFFF
+        res = _lib.StrResult()
+        self._check(self.L.hmj_join_kind_str_device(self.h, C.byref(rb), C.byref(rp), flags, C.byref(opts), C.byref(res)))
+        info = opts.counts.as_dict()
+        info["n_hash_pairs"] = int(opts.n_hash_pairs)
+        info["n_collisions"] = int(opts.n_collisions)
+        for k in ("ms_hash", "ms_join", "ms_verify", "ms_emit", "ms_order"):
+            info[k] = float(getattr(opts, k))
+        return res, info
+
+    def str_kind_rows_to_numpy(self, res):
+        """Copy a string kind join's device result out as an [n,5] uint64 array of (hash, r_row, s_row, rval, sval); a
+        column the kind does not produce reads as HMJ_STR_NO_ROW (row columns) or 0 (value columns)."""
+        n = int(res.n_matches)
+        out = np.empty((n, 5), np.uint64)
+        if n == 0 or not res.hash:
+            return out[:0]
+        torch = self._torch
+        tmp = torch.empty(n, dtype=torch.int64, device="cuda:%d" % self.device)
+        for c, ptr in enumerate((res.hash, res.r_row, res.s_row, res.rval, res.sval)):
+            if not ptr:
+                out[:, c] = _lib.HMJ_STR_NO_ROW if c in (1, 2) else 0
+                continue
+            _memcpy_d2d(torch, tmp, ptr, n * 8)
+            out[:, c] = tmp.cpu().numpy().view(np.uint64)
+        return out
+
 
 def _check_col(t, name):
     """A column the string entries read on the device: contiguous, 1-D, 64-bit, on the GPU."""

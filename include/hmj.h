@@ -485,9 +485,55 @@ typedef struct {
  * with 64-bit hashes that takes a genuine _Hash_bytes collision.
  * hmj_last_plan / hmj_last_timing describe the inner {hash,row} join.  Its workload memo is keyed apart from plain u64
  * joins (as the kinds' are), so string joins do not change what u64 joins learn.  Like any other call it discards a
- * prepared build side.  Out of scope: join kinds, the exchange (multi-GPU) path and host-resident string relations.    */
+ * prepared build side.  Join kinds: hmj_join_kind_str_device below.  Out of scope: the exchange (multi-GPU) path and
+ * host-resident string relations.                                                                                       */
 int hmj_join_str_device(hmj_ctx* ctx, const hmj_str_rel* build, const hmj_str_rel* probe, uint32_t flags,
                         hmj_str_join_opts* opts, hmj_str_result* out);
+
+/* The join kinds of hmj_join_kind_u64_device / hmj_join_build_kind_u64_device on string keys.  opts->side and opts->kind
+ * select the kind as hmj_exchange_kind_opts does: HMJ_KIND_PROBE_SIDE with HMJ_JOIN_INNER / _SEMI / _ANTI / _PROBE_OUTER,
+ * or HMJ_KIND_BUILD_SIDE with HMJ_BUILD_SEMI / _ANTI / _OUTER / HMJ_FULL_OUTER.  Every kind means what it means for the
+ * u64 entries, with the string join's match rule (keys equal byte for byte) and its row contents (hash with hash_bits
+ * applied, row indices, payloads):
+ *   probe SEMI / ANTI            columns hash, s_row, sval (r_row and rval are NULL); each probe row at most once, and
+ *                                SEMI + ANTI partition the probe relation;
+ *   BUILD_SEMI / BUILD_ANTI      columns hash, r_row, rval (s_row and sval are NULL);
+ *   PROBE_OUTER / BUILD_OUTER /  the inner string join's rows, + (hash, HMJ_STR_NO_ROW, s_row, probe_fill, sval) per
+ *   FULL_OUTER                   unmatched probe row and / or (hash, r_row, HMJ_STR_NO_ROW, rval, build_fill) per
+ *                                unmatched build row, as the kind asks.
+ * n_matches = result rows; sum_r / sum_s and HMJ_CHECKSUM's tmix(hash, rval, sval) are taken over result rows, a missing
+ * value column counting as 0 and fills as written; HMJ_SUM_PROBE is unchanged.  opts->counts: the counters the u64 entry
+ * of the kind fills (probe counters for SEMI / ANTI / PROBE_OUTER, build counters for the build kinds, both for
+ * FULL_OUTER), zeros elsewhere.  Empty sides as for the u64 kinds (n_build == 0: ANTI returns every probe row).
+ * HMJ_ORDERED (implies HMJ_MATERIALIZE): rows ascending by (hash, key bytes as std::string::operator< orders them, r_row,
+ * s_row), HMJ_STR_NO_ROW last; (hash, key bytes, row) for the semi / anti kinds.
+ * HMJ_KIND_PROBE_SIDE + HMJ_JOIN_INNER is exactly hmj_join_str_device (rows, sums, order; counters 0).
+ * How (DESIGN.md "String keys on the device", join kinds): semi / anti never form the cross product.  The {hash,row} rows
+ * are joined first-wins, so every row of the side asked about meets ONE row of its hash on the other side; a verify pass
+ * marks the rows whose keys are equal (one byte per row) and lists the others, which -- only after a real hash collision
+ * -- are joined with every row of their hash and verified again.  The outer kinds run the inner string join's pair join
+ * and verification with the same marks.  One sweep per relation emits the rows its mark selects, stably in row order.
+ * Ordered results are sorted by hash (a stable u64 sort of (hash, index) rows) and runs of equal hash with several keys
+ * by key bytes, as the inner join sorts them.
+ * HMJ_E_ARG: NULL ctx / rel / opts / out, opts->struct_size too small, an unknown side or kind, HMJ_FIRST_WINS, and
+ * everything hmj_join_str_device rejects (decreasing offsets included; the ctx stays usable).  HMJ_E_UNSUPPORTED wherever
+ * the ordered string join returns it.  hmj_last_plan / hmj_last_timing describe the last internal u64 join; the kinds'
+ * workloads are keyed apart from u64 joins, u64 kind joins and the inner string join.                                  */
+#define HMJ_STR_NO_ROW UINT64_MAX /* r_row / s_row of an outer join's unmatched row: there is no partner             */
+typedef struct {
+  uint32_t struct_size;   /* in: sizeof(hmj_str_kind_opts) of the caller's header                                       */
+  uint32_t side;          /* in: HMJ_KIND_PROBE_SIDE / HMJ_KIND_BUILD_SIDE                                             */
+  uint32_t kind;          /* in: a kind of that side                                                                   */
+  uint32_t hash_bits;     /* in: as hmj_str_join_opts                                                                  */
+  uint64_t probe_fill;    /* in: rval of an unmatched probe row (PROBE_OUTER, FULL_OUTER)                              */
+  uint64_t build_fill;    /* in: sval of an unmatched build row (BUILD_OUTER, FULL_OUTER)                              */
+  hmj_kind_counts counts; /* out: the counters the u64 entry of the kind fills, zeros elsewhere                        */
+  uint64_t n_hash_pairs;  /* out: pairs of equal hash whose keys were compared                                         */
+  uint64_t n_collisions;  /* out: of those, pairs whose keys differ                                                    */
+  float ms_hash, ms_join, ms_verify, ms_emit, ms_order; /* out, with hmj_set_profiling(ctx, 1): HIP-event phase times  */
+} hmj_str_kind_opts;
+int hmj_join_kind_str_device(hmj_ctx* ctx, const hmj_str_rel* build, const hmj_str_rel* probe, uint32_t flags,
+                             hmj_str_kind_opts* opts, hmj_str_result* out);
 /* Host threads of the optional staged upload (pageable input -> pinned chunks -> PCIe), used only
  * with HMJ_UPLOAD=staged in the environment; by default each relation goes up in one copy straight
  * from the caller's memory (54 GB/s on the MI355X box).  The reference ctor's num_threads argument,
