@@ -3235,7 +3235,8 @@ int hmj_set_stream(hmj_ctx* c, void* hip_stream) {
 }
 
 int hmj_set_radix_bits(hmj_ctx* c, int total_bits) {
-  if (!c || total_bits > 27) return HMJ_E_ARG;
+  if (!c) return HMJ_E_ARG;
+  if (total_bits > 27) return fail(c, HMJ_E_ARG, "total_bits must be at most 27");
   c->force_bits = total_bits < 0 ? -1 : total_bits;
   return HMJ_OK;
 }
@@ -3291,7 +3292,8 @@ int hmj_autotune_radix_bits(hmj_ctx* c, uint64_t n_build, uint64_t n_probe, int 
 }
 
 int hmj_set_key_prefix_bits(hmj_ctx* c, int bits) {
-  if (!c || bits < -1 || bits > 48) return HMJ_E_ARG;
+  if (!c) return HMJ_E_ARG;
+  if (bits < -1 || bits > 48) return fail(c, HMJ_E_ARG, "key prefix bits must be in -1..48");
   c->prefix_bits = bits;
   return HMJ_OK;
 }
@@ -3697,6 +3699,7 @@ int hmj_partition_u64_device(hmj_ctx* c, const void* in_aos_dev, uint64_t n, int
   if (!offsets_dev) return fail(c, HMJ_E_ARG, "offsets_dev is NULL");
   HIP_TRY(hipSetDevice(c->device));
   spans_reset(c);
+  c->prep.valid = false;  // "any other call discards the prepared state" (hmj.h)
   if (n == 0) {
     HIP_TRY(hipMemsetAsync(offsets_dev, 0, ((size_t)(1u << bits) + 1) * 8, c->stream));
   } else if ((rc = radix_pass(c, in_aos_dev, out_aos_dev, (u32)n, shift, bits, -1,
@@ -3715,9 +3718,9 @@ int hmj_sort_u64_device(hmj_ctx* c, const void* in_aos_dev, uint64_t n, void* ou
   if ((rc = check_rel(c, out_aos_dev, n, "out_aos is NULL")) != HMJ_OK) return rc;
   HIP_TRY(hipSetDevice(c->device));
   spans_reset(c);
+  c->prep.valid = false;  // rbuf[0] is the sort's ping-pong buffer (an empty sort discards too, like every other call)
   if (n == 0) return HMJ_OK;
   memo_for(c, workload_signature(n, 0, 0, 1));  // (what earlier sorts of this size learnt: the chain's cool-down)
-  c->prep.valid = false;  // rbuf[0] is the sort's ping-pong buffer
   if ((rc = ensure_dev(c, c->rbuf[0], (size_t)n * 16)) != HMJ_OK) return rc;
   // Digits in which no key differs need no pass (a stable pass on a constant digit is a copy): integer ids below 2^32
   // sort in four passes instead of eight (dense keys, 2^26 rows: 5.58 -> 2.93 ms, 2^28: 21.4 -> 10.8 ms = 24.8 G keys/s,
@@ -3925,6 +3928,7 @@ int hmj_sort_rows_by_u64_host(hmj_ctx* c, void* rows_host, uint64_t n, uint32_t 
   if (n > 0xFFFFFFFFull || (n && !rows_host)) return fail(c, HMJ_E_ARG, "hmj_sort_rows_by_u64_host");
   HIP_TRY(hipSetDevice(c->device));
   spans_reset(c);
+  c->prep.valid = false;  // "any other call discards the prepared state" (hmj.h), whatever n
   if (n < 2) return HMJ_OK;
   int rc;
   const size_t bytes = (size_t)n * row_bytes;
@@ -3946,6 +3950,7 @@ int hmj_argsort_u64_host(hmj_ctx* c, const void* keys_host, uint64_t n, uint32_t
   if (stride_bytes < 8 || n > 0xFFFFFFFFull || (n && (!keys_host || !perm_out))) return fail(c, HMJ_E_ARG, "hmj_argsort_u64_host");
   HIP_TRY(hipSetDevice(c->device));
   spans_reset(c);
+  c->prep.valid = false;  // "any other call discards the prepared state" (hmj.h), whatever n
   if (n == 0) return HMJ_OK;
   int rc;
   if ((rc = ensure_dev(c, c->in_r, (size_t)n * 8)) != HMJ_OK) return rc;

@@ -1044,6 +1044,7 @@ int hmj_hash_str_device(hmj_ctx* c, const void* chars, const uint64_t* offsets, 
   if (n > 0xFFFFFFFFull) return fail(c, HMJ_E_ARG, "too many rows (at most 2^32-1)");
   if (hash_bits > 63) return fail(c, HMJ_E_ARG, "hash_bits > 63");
   if (n > 0 && (!offsets || !hash_out_dev)) return fail(c, HMJ_E_ARG, "offsets / hash_out_dev is NULL");
+  c->prep.valid = false;  // like any other call, hashing discards a prepared build side
   if (n == 0) return HMJ_OK;
   HIP_TRY(hipSetDevice(c->device));
   RC_TRY(ensure_dev(c, c->str_acc, 3 * SA_N * sizeof(u64)));

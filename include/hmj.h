@@ -395,6 +395,12 @@ int hmj_exchange_join_kind_u64_device(hmj_ctx* ctx, const void* build_shard_dev,
  * xGMI).  One-shot: the NEXT hmj_join_u64_device on this ctx whose build pointer, row count and plan
  * match (count modes and materialising joins of relations of similar size plan alike; a join that plans
  * differently simply partitions R again) skips re-partitioning R; any other call discards the prepared state.  The caller promises the build rows do not change in between.
+ * "Any other call" is every call that runs on the device or touches the workspace: the joins of every kind (u64, string,
+ * host-resident, exchange), hmj_sort_u64_device, hmj_sort_rows_by_u64_host, hmj_argsort_u64_host, hmj_partition_u64_device,
+ * hmj_hash_str_device (each of them also when given no rows), hmj_reserve and hmj_autotune_radix_bits.  Left out are the calls that read or write no workspace buffer: hmj_set_stream,
+ * hmj_set_radix_bits / hmj_set_key_prefix_bits (the join then plans other bits and partitions R again), hmj_set_profiling,
+ * hmj_forget_workloads, hmj_release_result (result columns only), the hmj_last_* / hmj_placement_info queries and the
+ * hmj_gen_* generators; a call refused with HMJ_E_ARG before it started may leave the prepared state in place as well.
  * n_probe_hint: the probe size the join will have (it selects the partitioning path).
  * Corresponds to the first radix_non_inplace_par call of the reference ctor (hashjoin.h:65).       */
 int hmj_prepare_build_u64_device(hmj_ctx* ctx, const void* build_aos_dev, uint64_t n_build,

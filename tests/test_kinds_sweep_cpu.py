@@ -46,13 +46,15 @@ def _keys(rng, dist, n, dom):
     return (rng.integers(0, 3, size=n, dtype=np.uint64) << np.uint64(61)) | rng.integers(0, 1 << 40, size=n, dtype=np.uint64)
 
 
-def draw_u64_case(rng):
+def draw_u64_case(rng, sizes=None):
     """(B, P, fills, tag): two [n, 2] uint64 relations, (probe_fill, build_fill) and tag = (nb, np, dist, dom, share, hot).
     The key domain is raised to at least 50 * ceil(nb * np / 2^22): `dups` then has at least ceil(nb np / 2^22) distinct
     keys and `dense` fifty times as many, so the cross product stays near 2^22 pairs whatever the sizes, and no case needs
     to be skipped.  The hot key is written after the probe keys were drawn from the build keys (a hot build key copied
-    into the probe side as well would square)."""
-    nb, npb = int(rng.choice(SIZES)), int(rng.choice(SIZES))
+    into the probe side as well would square).  `sizes`: the row counts to draw from (SIZES unless given; the random stream
+    of the default is the one the sweeps have always drawn)."""
+    sizes = SIZES if sizes is None else sizes
+    nb, npb = int(rng.choice(sizes)), int(rng.choice(sizes))
     dist = str(rng.choice(DISTS))
     dom = max(int(rng.choice([97, 5000, 1 << 20])), 50 * -(-nb * npb // (1 << 22)))
     share = float(rng.choice([0.0, 0.3, 0.6, 1.0]))
@@ -124,14 +126,17 @@ def ambiguous_runs(rows, bk, pk):
     return largest, mixed
 
 
-def draw_str_case(rng):
+STR_KEYS = (60, 7000)  # distinct keys of a drawn string case: log-uniform between the two
+
+
+def draw_str_case(rng, sizes=STR_KEYS):
     """A dict: bk / bv / pk / pv (key bytes and 64-bit payloads of the build and the probe side), shift_b / base_b /
     shift_p / base_p for test_join_str_gpu.rel, hash_bits, mixed_run (an ordered outer join of the case sorts a run of equal
     hash with keys of both relations) and redraws.  Distinct keys from length classes: 1..8 bytes, 56..72 bytes (64 such
     keys span about the 4096 bytes a wave stages), the empty key in half the draws (keys are distinct, so `all empty` is one
     key with its copies), up to three keys of 4097..20000 bytes, proper prefixes of other keys and keys that differ from
-    another in the last byte only; each key 1..4 times per side, a third of the keys on one side only."""
-    n_keys = int(math.exp(rng.uniform(math.log(60), math.log(7000))))
+    another in the last byte only; each key 1..4 times per side, a third of the keys on one side only.  `sizes`: (fewest, most) distinct keys."""
+    n_keys = int(math.exp(rng.uniform(math.log(sizes[0]), math.log(sizes[1]))))
     p_short = float(rng.choice([0.1, 0.5, 0.85]))  # the rest from the 56..72 class
     keys = set()
     if rng.random() < 0.5:
