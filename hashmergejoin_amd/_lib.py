@@ -126,6 +126,40 @@ class StrResult(C.Structure):
         return {k: int(getattr(self, k)) for k in ("n_matches", "sum_r", "sum_s", "xor_fold", "mix_sum")}
 
 
+# hmj_join_cols_device: multi-column fixed-width keys
+HMJ_MAX_KEY_COLS = 8
+HMJ_COLS_PACKED, HMJ_COLS_HASHED = 1, 2
+
+
+class KeyCol(C.Structure):
+    """hmj_key_col: one key column on the device -- n values of `width` bytes (1, 2, 4 or 8), aligned to `width`."""
+    _fields_ = [("data", C.c_void_p), ("width", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ColsRel(C.Structure):
+    """hmj_cols_rel: a relation keyed by a tuple of fixed-width columns (struct of arrays) + optional payloads."""
+    _fields_ = [("cols", C.POINTER(KeyCol)), ("n_cols", C.c_uint32), ("reserved", C.c_uint32), ("vals", C.c_void_p),
+                ("n", C.c_uint64)]
+
+
+class ColsJoinOpts(C.Structure):
+    """hmj_cols_join_opts: hash bits and the forced hashed form (in); the form taken, pairs of equal key64, dropped
+    collisions and phase times (out)."""
+    _fields_ = [("struct_size", C.c_uint32), ("hash_bits", C.c_uint32), ("force_hashed", C.c_uint32), ("form", C.c_uint32),
+                ("n_key_pairs", C.c_uint64), ("n_collisions", C.c_uint64), ("ms_key", C.c_float), ("ms_join", C.c_float),
+                ("ms_verify", C.c_float), ("ms_order", C.c_float)]
+
+
+class ColsResult(C.Structure):
+    """hmj_cols_result: counts and sums as JoinResult (tmix over (key64, rval, sval)); device columns with HMJ_MATERIALIZE."""
+    _fields_ = [("n_matches", C.c_uint64), ("sum_r", C.c_uint64), ("sum_s", C.c_uint64),
+                ("xor_fold", C.c_uint64), ("mix_sum", C.c_uint64), ("sum_probe_all", C.c_uint64),
+                ("key64", C.c_void_p), ("r_row", C.c_void_p), ("s_row", C.c_void_p), ("rval", C.c_void_p), ("sval", C.c_void_p)]
+
+    def checks(self):
+        return {k: int(getattr(self, k)) for k in ("n_matches", "sum_r", "sum_s", "xor_fold", "mix_sum")}
+
+
 class Timing(C.Structure):
     _fields_ = [("ms_total", C.c_float), ("ms_h2d", C.c_float), ("ms_d2h", C.c_float),
                 ("ms_partition_build", C.c_float), ("ms_partition_probe", C.c_float),
@@ -274,6 +308,9 @@ def load_library():
     L.hmj_join_kind_str_device.restype = i
     L.hmj_join_kind_str_device.argtypes = [vp, C.POINTER(StrRel), C.POINTER(StrRel), C.c_uint32, C.POINTER(StrKindOpts),
                                            C.POINTER(StrResult)]
+    L.hmj_join_cols_device.restype = i
+    L.hmj_join_cols_device.argtypes = [vp, C.POINTER(ColsRel), C.POINTER(ColsRel), C.c_uint32, C.POINTER(ColsJoinOpts),
+                                       C.POINTER(ColsResult)]
     L.hmj_prepare_build_u64_device.restype = i
     L.hmj_prepare_build_u64_device.argtypes = [vp, vp, u, u]
     L.hmj_join_u64.restype = i

@@ -3209,7 +3209,9 @@ void hmj_destroy(hmj_ctx* c) {
                     &c->split_r, &c->split_s, &c->split_off, &c->cat_key, &c->cat_rval, &c->cat_sval, &c->msd_off,
                     &c->bmatched, &c->bsweep, &c->str_rows_r, &c->str_rows_s, &c->str_flags, &c->str_blk, &c->str_blk_off,
                     &c->str_hash, &c->str_rrow, &c->str_srow, &c->str_rval, &c->str_sval, &c->str_list, &c->str_runs, &c->str_acc,
-                    &c->str_mark_r, &c->str_mark_s, &c->str_amb, &c->str_ord, &c->str_khash, &c->str_krrow, &c->str_ksrow, &c->str_krval, &c->str_ksval};
+                    &c->str_mark_r, &c->str_mark_s, &c->str_amb, &c->str_ord, &c->str_khash, &c->str_krrow, &c->str_ksrow, &c->str_krval, &c->str_ksval,
+                    &c->col_rows_r, &c->col_rows_s, &c->col_flags, &c->col_blk, &c->col_blk_off, &c->col_key, &c->col_rrow, &c->col_srow,
+                    &c->col_rval, &c->col_sval, &c->col_list, &c->col_runs, &c->col_acc};
   for (DevBuf* b : devs) free_dev(*b);
   HostBuf* hosts[] = {&c->h_accum, &c->h_key, &c->h_rval, &c->h_sval};
   for (HostBuf* b : hosts) free_host(*b);
@@ -3219,6 +3221,8 @@ void hmj_destroy(hmj_ctx* c) {
   for (auto& e : c->place_ev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : c->str_ev)
+    if (e) (void)hipEventDestroy(e);
+  for (auto& e : c->col_ev)
     if (e) (void)hipEventDestroy(e);
   for (auto& st : c->up_streams) (void)hipStreamDestroy(st);
   for (auto& e : c->copy_ev) (void)hipEventDestroy(e);
@@ -3683,6 +3687,8 @@ void hmj_release_result(hmj_ctx* c) {
   free_dev(c->ord_sval);
   DevBuf* str_cols[5] = {&c->str_hash, &c->str_rrow, &c->str_srow, &c->str_rval, &c->str_sval};
   for (DevBuf* b : str_cols) free_dev(*b);
+  DevBuf* col_cols[5] = {&c->col_key, &c->col_rrow, &c->col_srow, &c->col_rval, &c->col_sval};
+  for (DevBuf* b : col_cols) free_dev(*b);
   free_host(c->h_key);
   free_host(c->h_rval);
   free_host(c->h_sval);

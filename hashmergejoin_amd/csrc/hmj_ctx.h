@@ -113,9 +113,15 @@ struct hmj_ctx {
       str_runs, str_acc,
       // string join kinds: one mark byte per row of each relation, the rows whose representative's key differed, the
       // ordered form's (hash, index) rows and sorted copy, the five result columns in sorted order
-      str_mark_r, str_mark_s, str_amb, str_ord, str_khash, str_krrow, str_ksrow, str_krval, str_ksval;
+      str_mark_r, str_mark_s, str_amb, str_ord, str_khash, str_krrow, str_ksrow, str_krval, str_ksval,
+      // multi-column joins (coljoin.hip): {key64, row} rows of both relations, pass-1 ballots, per-workgroup survivors and
+      // their offsets, the result columns (the packed form fills rval / sval only), the collision search's rows and runs,
+      // its counters
+      col_rows_r, col_rows_s, col_flags, col_blk, col_blk_off, col_key, col_rrow, col_srow, col_rval, col_sval, col_list,
+      col_runs, col_acc;
   hipEvent_t str_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // string joins' phase boundaries (profiling)
-  int memo_kind = 0;  // workload-signature kind of plain inner joins run on behalf of another entry (string joins)
+  hipEvent_t col_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // multi-column joins' phase boundaries (profiling)
+  int memo_kind = 0;  // workload-signature kind of plain inner joins run on behalf of another entry (string, multi-column joins)
   HostBuf h_accum, h_key, h_rval, h_sval;
   int host_threads = 0;  // staging threads for pageable input (0 = default)
   std::vector<hipStream_t> up_streams;

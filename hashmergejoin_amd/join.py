@@ -258,6 +258,67 @@ class Executor:
             out[:, c] = tmp.cpu().numpy().view(np.uint64)
         return out
 
+    # ---- multi-column fixed-width keys (hmj_join_cols_device) ------------------------------------------
+    def _cols_rel(self, cols, vals):
+        """Key columns (1-D contiguous device tensors of one length, any dtype) + payloads (int64 [n] or None) -> (ColsRel,
+        the KeyCol array it points to: keep it alive for the call).  Widths, alignment and column counts are checked by
+        the library."""
+        cols = list(cols)
+        for k, t in enumerate(cols):
+            if not t.is_cuda or not t.is_contiguous() or t.dim() != 1:
+                raise ValueError("key column %d must be a contiguous 1-D device tensor" % k)
+        n = cols[0].shape[0] if cols else (vals.shape[0] if vals is not None else 0)
+        if any(t.shape[0] != n for t in cols):
+            raise ValueError("key columns must have one length")
+        if vals is not None:
+            _check_col(vals, "vals")
+            if vals.shape[0] != n:
+                raise ValueError("vals must hold one payload per row")
+        arr = (_lib.KeyCol * max(len(cols), 1))()
+        for k, t in enumerate(cols):
+            arr[k].data = t.data_ptr() if n else None
+            arr[k].width = t.element_size()
+        r = _lib.ColsRel()
+        r.cols = arr
+        r.n_cols = len(cols)
+        r.vals = vals.data_ptr() if (vals is not None and n) else None
+        r.n = n
+        return r, arr
+
+    def join_cols_device(self, build_cols, build_vals, probe_cols, probe_vals, flags=0, hash_bits=0, force_hashed=False):
+        """Inner join of two device relations on a key of several fixed-width columns (hmj_join_cols_device).  *_cols:
+        lists of 1-D contiguous device tensors of any dtype whose element_size() is 1, 2, 4 or 8 (compared bit for bit);
+        *_vals: an int64 tensor [n], or None (the payload of row i is i).  Returns (ColsResult, {"form", "n_key_pairs",
+        "n_collisions", "ms_key", "ms_join", "ms_verify", "ms_order"}); read the rows with `cols_rows_to_numpy`,
+        reproduce key64 with `cols_key64`."""
+        self._sync_stream()
+        rb, keep_b = self._cols_rel(build_cols, build_vals)
+        rp, keep_p = self._cols_rel(probe_cols, probe_vals)
+        opts = _lib.ColsJoinOpts()
+        opts.struct_size = C.sizeof(_lib.ColsJoinOpts)
+        opts.hash_bits = int(hash_bits)
+        opts.force_hashed = 1 if force_hashed else 0
+        res = _lib.ColsResult()
+        self._check(self.L.hmj_join_cols_device(self.h, C.byref(rb), C.byref(rp), flags, C.byref(opts), C.byref(res)))
+        del keep_b, keep_p
+        info = {"form": int(opts.form), "n_key_pairs": int(opts.n_key_pairs), "n_collisions": int(opts.n_collisions)}
+        for k in ("ms_key", "ms_join", "ms_verify", "ms_order"):
+            info[k] = float(getattr(opts, k))
+        return res, info
+
+    def cols_rows_to_numpy(self, res):
+        """Copy a multi-column join's device result out as an [n,5] uint64 array of (key64, r_row, s_row, rval, sval)."""
+        n = int(res.n_matches)
+        out = np.empty((n, 5), np.uint64)
+        if n == 0 or not res.key64:
+            return out[:0]
+        torch = self._torch
+        tmp = torch.empty(n, dtype=torch.int64, device="cuda:%d" % self.device)
+        for c, ptr in enumerate((res.key64, res.r_row, res.s_row, res.rval, res.sval)):
+            _memcpy_d2d(torch, tmp, ptr, n * 8)
+            out[:, c] = tmp.cpu().numpy().view(np.uint64)
+        return out
+
     def prepare_build(self, build, n_probe_hint):
         """Partition the build side now; the next matching plain-count join_device skips that work."""
         self._sync_stream()
@@ -508,6 +569,44 @@ def pack_strings(keys, device=None):
     if device is not None:
         c, o = c.to(device), o.to(device)
     return c, o
+
+
+def _mix64(x):
+    x = x ^ (x >> np.uint64(30))
+    x = x * np.uint64(0xBF58476D1CE4E5B9)
+    x = x ^ (x >> np.uint64(27))
+    x = x * np.uint64(0x94D049BB133111EB)
+    return x ^ (x >> np.uint64(31))
+
+
+def cols_key64(columns, widths, hash_bits=0, force_hashed=False):
+    """The 64-bit join key hmj_join_cols_device gives every row (include/hmj.h), restated on the host: uint64 array [n].
+    columns: one numpy array per key column (any dtype of widths[c] bytes, or integers that fit it); widths: bytes per
+    column (1, 2, 4 or 8).  Packed form (widths sum to <= 8, not force_hashed): the columns concatenated, column 0 most
+    significant.  Hashed form: h = k; h = mix64(h + v_c + 0x9E3779B97F4A7C15) per column; hash_bits 1..63 keeps the top bits."""
+    widths = [int(w) for w in widths]
+    if len(columns) != len(widths) or not 1 <= len(widths) <= _lib.HMJ_MAX_KEY_COLS:
+        raise ValueError("1..%d columns, one width each" % _lib.HMJ_MAX_KEY_COLS)
+    if any(w not in (1, 2, 4, 8) for w in widths):
+        raise ValueError("widths must be 1, 2, 4 or 8")
+    if not 0 <= int(hash_bits) <= 63:
+        raise ValueError("hash_bits must be in 0..63")
+    vs = []
+    for col, w in zip(columns, widths):
+        a = np.ascontiguousarray(col)
+        if a.dtype.itemsize == w and a.dtype.kind != "u":
+            a = a.view("u%d" % w)  # signed integers and floats: their bytes
+        vs.append(a.astype(np.uint64) & np.uint64((1 << (8 * w)) - 1))
+    n = len(vs[0])
+    if sum(widths) <= 8 and not force_hashed:
+        key = np.zeros(n, np.uint64)
+        for v, w in zip(vs, widths):
+            key = v if w == 8 else ((key << np.uint64(8 * w)) | v)
+        return key
+    h = np.full(n, len(widths), np.uint64)
+    for v in vs:
+        h = _mix64(h + v + np.uint64(0x9E3779B97F4A7C15))
+    return h >> np.uint64(64 - int(hash_bits)) if hash_bits else h
 
 
 def _memcpy_d2d(torch, dst_tensor, src_ptr, nbytes):

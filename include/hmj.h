@@ -396,7 +396,7 @@ int hmj_exchange_join_kind_u64_device(hmj_ctx* ctx, const void* build_shard_dev,
  * match (count modes and materialising joins of relations of similar size plan alike; a join that plans
  * differently simply partitions R again) skips re-partitioning R; any other call discards the prepared state.  The caller promises the build rows do not change in between.
  * "Any other call" is every call that runs on the device or touches the workspace: the joins of every kind (u64, string,
- * host-resident, exchange), hmj_sort_u64_device, hmj_sort_rows_by_u64_host, hmj_argsort_u64_host, hmj_partition_u64_device,
+ * multi-column -- hmj_join_cols_device --, host-resident, exchange), hmj_sort_u64_device, hmj_sort_rows_by_u64_host, hmj_argsort_u64_host, hmj_partition_u64_device,
  * hmj_hash_str_device (each of them also when given no rows), hmj_reserve and hmj_autotune_radix_bits.  Left out are the calls that read or write no workspace buffer: hmj_set_stream,
  * hmj_set_radix_bits / hmj_set_key_prefix_bits (the join then plans other bits and partitions R again), hmj_set_profiling,
  * hmj_forget_workloads, hmj_release_result (result columns only), the hmj_last_* / hmj_placement_info queries and the
@@ -540,6 +540,83 @@ typedef struct {
 } hmj_str_kind_opts;
 int hmj_join_kind_str_device(hmj_ctx* ctx, const hmj_str_rel* build, const hmj_str_rel* probe, uint32_t flags,
                              hmj_str_kind_opts* opts, hmj_str_result* out);
+
+/* ---- multi-column fixed-width keys on the device --------------------------------------------------- */
+/* The inner equi-join of two relations whose key is a tuple of k fixed-width columns (ON a.x = b.x AND a.y = b.y ...),
+ * held on the device as the caller holds them: struct of arrays, one device pointer per column, plus an optional payload
+ * column.  Nothing in the reference corresponds: its operator is a template over ONE Key with std::hash<Key>
+ * (hashjoin.h:33-56), so a caller of it would pack the tuple into a Key type of its own.  Key construction, the join,
+ * tuple verification, payload gather and ordering all run on the GPU; no pass on the host touches keys or rows.         */
+#define HMJ_MAX_KEY_COLS 8
+typedef struct {
+  const void* data;         /* device: n contiguous values of `width` bytes, aligned to `width`                        */
+  uint32_t width;           /* 1, 2, 4 or 8                                                                             */
+  uint32_t reserved;        /* 0                                                                                        */
+} hmj_key_col;
+typedef struct {
+  const hmj_key_col* cols;  /* HOST array of n_cols entries (read during the call only)                                 */
+  uint32_t n_cols;          /* 1 .. HMJ_MAX_KEY_COLS                                                                    */
+  uint32_t reserved;        /* 0                                                                                        */
+  const uint64_t* vals;     /* device: n payloads; NULL = the payload of row i is i                                     */
+  uint64_t n;               /* rows, <= 2^32 - 1                                                                        */
+} hmj_cols_rel;
+#define HMJ_COLS_PACKED 1u
+#define HMJ_COLS_HASHED 2u
+typedef struct {
+  uint32_t struct_size;     /* in: sizeof of the caller's header (size-versioned like hmj_str_join_opts)               */
+  uint32_t hash_bits;       /* in: hashed form only; 0 = 64, 1..63 = h >> (64 - hash_bits): fewer bits make collisions  */
+                            /* between different tuples common -- exists so callers and tests can exercise them        */
+  uint32_t force_hashed;    /* in: != 0: take the hashed form even when the key fits 8 bytes                            */
+  uint32_t form;            /* out: HMJ_COLS_PACKED / HMJ_COLS_HASHED (0 when a side was empty)                         */
+  uint64_t n_key_pairs;     /* out: pairs of equal 64-bit join key the {key64,row} join produced                       */
+  uint64_t n_collisions;    /* out: of those, pairs whose tuples differ (dropped; always 0 in the packed form)          */
+  float ms_key, ms_join, ms_verify, ms_order; /* out, with hmj_set_profiling(ctx, 1): HIP-event phase times             */
+} hmj_cols_join_opts;
+typedef struct {
+  uint64_t n_matches, sum_r, sum_s, xor_fold, mix_sum, sum_probe_all; /* as hmj_str_result; tmix over (key64, rval, sval) */
+  const uint64_t *key64, *r_row, *s_row, *rval, *sval; /* HMJ_MATERIALIZE: device columns owned by the ctx, valid  */
+                                                       /* until the next call on it / hmj_release_result            */
+} hmj_cols_result;
+/* Match rule: a result row is a pair (build row, probe row) whose k columns are all equal bit for bit.  Signed integers
+ * and floats are compared as their bytes: -0.0 != 0.0, and equal NaN patterns match.  Duplicate tuples on either side
+ * give the cross product.  Both relations must have the same n_cols and the same width per column.
+ * Row contents: r_row / s_row are row indices into the caller's relations (gather maps; the key columns themselves are
+ * not copied out); rval = build->vals[r_row], sval = probe->vals[s_row] (the row index itself where vals is NULL); key64
+ * is the 64-bit join key below.
+ * The 64-bit join key, with v_c = column c's value zero-extended to 64 bits and T = the sum of the widths:
+ *   packed (T <= 8 and not force_hashed)   key64 = v_0 || v_1 || ... || v_{k-1}: column 0 in the most significant
+ *                                          position of the T low bytes, the upper 8 - T bytes zero -- i.e.
+ *                                          key64 = 0; for c in 0..k-1: key64 = (key64 << (8 * width_c)) | v_c.
+ *                                          Equal key64 IS equal tuples: no hash, no verification, no collisions.
+ *   hashed                                 h = k; for c in 0..k-1: h = mix64(h + v_c + 0x9E3779B97F4A7C15) (wrapping
+ *                                          64-bit sums), with mix64(x): x ^= x >> 30; x *= 0xBF58476D1CE4E5B9;
+ *                                          x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31.  Then
+ *                                          key64 = hash_bits ? h >> (64 - hash_bits) : h.
+ * Flags: HMJ_MATERIALIZE, HMJ_ORDERED, HMJ_CHECKSUM and HMJ_SUM_PROBE mean what they mean for hmj_join_str_device;
+ * HMJ_FIRST_WINS is HMJ_E_ARG.  Without HMJ_MATERIALIZE only the counters and sums are filled; the hashed form still
+ * verifies, so every count is exact.
+ * HMJ_ORDERED (implies HMJ_MATERIALIZE): rows ascending by (key64, the tuple compared column by column as UNSIGNED
+ * integers, r_row, s_row).  In the packed form that is plainly ascending tuple order.  In the hashed form rows of one
+ * tuple are contiguous and the order is reproducible from the definition above.
+ * How: every row becomes a {key64, row} row (cols_key_kernel: one lane per row, coalesced loads per column, one 16-byte
+ * store), the two row sets are joined by the u64 join (HMJ_MATERIALIZE, + HMJ_ORDERED).  Packed: the join's columns are
+ * the result's key64 / r_row / s_row; one kernel gathers the payloads and takes the sums.  Hashed: every pair of equal
+ * key64 has its tuples compared column by column and its payloads gathered (cols_verify_kernel; survivors compacted
+ * stably), and -- ordered only -- runs of equal key64 whose build tuples differ are sorted by tuple, each inside one
+ * workgroup.
+ * n == 0 on either side: an empty result and HMJ_OK (sum_probe_all is still filled when asked).
+ * HMJ_E_ARG (hmj_last_error names what was wrong): NULL ctx / rel / opts / out; opts->struct_size too small; n_cols
+ * outside 1..HMJ_MAX_KEY_COLS; a NULL cols array; a width other than 1, 2, 4 or 8; a NULL or misaligned data with n > 0;
+ * non-zero reserved; different n_cols or widths on the two sides; more than 2^32-1 rows; hash_bits > 63; HMJ_FIRST_WINS.
+ * HMJ_E_UNSUPPORTED wherever the inner ordered u64 join returns it, and in the hashed form for an ordered join with a run
+ * of equal key64 that holds several distinct matched build tuples and more than 1024 rows (or more than 2^22 such
+ * adjacent rows in all) -- with 64 hash bits that takes a genuine collision of the hash above.  The ctx stays usable.
+ * hmj_last_plan / hmj_last_timing describe the inner {key64,row} join.  Its workload memo is keyed apart from every
+ * other entry's, so multi-column joins do not change what u64 or string joins learn.  Like any other call it discards a
+ * prepared build side.  Out of scope: the join kinds, the exchange (multi-GPU) path, host-resident columns, validity
+ * bitmaps, returning the key columns, signed / collated ordering.                                                      */
+int hmj_join_cols_device(hmj_ctx* ctx, const hmj_cols_rel* build, const hmj_cols_rel* probe, uint32_t flags,
+                         hmj_cols_join_opts* opts, hmj_cols_result* out);
 /* Host threads of the optional staged upload (pageable input -> pinned chunks -> PCIe), used only
  * with HMJ_UPLOAD=staged in the environment; by default each relation goes up in one copy straight
  * from the caller's memory (54 GB/s on the MI355X box).  The reference ctor's num_threads argument,

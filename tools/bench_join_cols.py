@@ -1,0 +1,115 @@
+#!/usr/bin/env python3
+"""Time the multi-column key join on the device (hmj_join_cols_device) against its floor.  One JSON line.
+
+  Shapes: [4,4] (two int32 columns: the packed form) and [8,4,2] (the hashed form), 2^24 x 2^24 and 2^26 x 2^26 rows, unique
+  tuples on the build side, the probe side a permutation of them; count mode and HMJ_ORDERED.  Per shape, size and mode:
+
+  ms           median of --reps device-timed joins (HIP events around the call) after --warmup, profiling off
+  floor_ms     hmj_join_u64_device with the same flags, in the same process and timed the same way, on pre-built {key64,row}
+               rows -- the rows the key kernel writes (cols_key64 on the host).  What the column handling adds is ms - floor_ms.
+  phases_ms    median hmj_cols_join_opts ms_key / ms_join / ms_verify / ms_order (profiling on, separate joins)
+  key_kernel   both relations' key kernels: ms_key, their algorithmic bytes -- T + 16 per row (T = the widths' sum read, one
+               {key64,row} row written) -- and the share of the 8 TB/s HBM peak that is.  ms_key spans two launches and, with
+               HMJ_SUM_PROBE off, nothing else.
+
+    python tools/bench_join_cols.py [--reps 20] [--warmup 3] [--log2 24 26]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+HBM_TBPS = 8.0
+SHAPES = (("4_4", [4, 4]), ("8_4_2", [8, 4, 2]))
+
+
+def timed(torch, fn, reps, warmup):
+    out = None
+    for _ in range(warmup):
+        out = fn()
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return statistics.median(ms), out
+
+
+def make_columns(n, widths, seed):
+    """n distinct tuples over `widths` (numpy, unsigned) and a permutation of them for the probe side."""
+    rng = np.random.default_rng(seed)
+    ids = rng.permutation(n).astype(np.uint64)
+    cols = []
+    if widths == [4, 4]:  # (tenant, id): the id alone is distinct
+        cols = [(ids >> np.uint64(12)).astype(np.uint32) * np.uint32(2654435761), ids.astype(np.uint32)]
+    else:  # (id scattered over 64 bits, day, flag)
+        cols = [ids * np.uint64(0x9E3779B97F4A7C15), (ids % np.uint64(36500)).astype(np.uint32), (ids & np.uint64(0xFFFF)).astype(np.uint16)]
+    perm = rng.permutation(n)
+    return cols, [c[perm] for c in cols]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--log2", type=int, nargs="+", default=[24, 26])
+    args = ap.parse_args()
+    import torch
+
+    import hashmergejoin_amd as H
+
+    assert torch.cuda.is_available(), "bench_join_cols needs a GPU"
+    ex = H.Executor(0)
+    out = {"tool": "bench_join_cols", "reps": args.reps, "warmup": args.warmup, "hbm_peak_TBps": HBM_TBPS}
+
+    def dev(a):
+        return torch.from_numpy(np.ascontiguousarray(a).view("i%d" % a.dtype.itemsize)).cuda()
+
+    for lg in args.log2:
+        n = 1 << lg
+        for name, widths in SHAPES:
+            bc, pc = make_columns(n, widths, lg)
+            rows = np.arange(n, dtype=np.uint64)
+            Bu = dev(np.stack([H.cols_key64(bc, widths), rows], 1))
+            Pu = dev(np.stack([H.cols_key64(pc, widths), rows], 1))
+            B, P = [dev(c) for c in bc], [dev(c) for c in pc]
+            del bc, pc
+            for mode, flags in (("count", 0), ("ordered", H.HMJ_ORDERED)):
+                ex.set_profiling(False)
+                ms, (res, info) = timed(torch, lambda: ex.join_cols_device(B, None, P, None, flags), args.reps, args.warmup)
+                path = ex.last_plan()["path"]
+                floor, u = timed(torch, lambda: ex.join_device(Bu, Pu, flags), args.reps, args.warmup)
+                floor_path = ex.last_plan()["path"]
+                assert int(res.n_matches) == n == int(u.n_matches) and (int(res.sum_r), int(res.sum_s)) == (int(u.sum_r), int(u.sum_s))
+                ex.set_profiling(True)
+                ph = {k: [] for k in ("ms_key", "ms_join", "ms_verify", "ms_order")}
+                for _ in range(max(5, args.reps // 2)):
+                    _, inf = ex.join_cols_device(B, None, P, None, flags)
+                    for k in ph:
+                        ph[k].append(inf[k])
+                ex.set_profiling(False)
+                med = {k: statistics.median(v) for k, v in ph.items()}
+                byts = 2 * n * (sum(widths) + 16)
+                out["%s_2^%d_%s" % (name, lg, mode)] = {
+                    "form": "packed" if info["form"] == H.HMJ_COLS_PACKED else "hashed", "ms": round(ms, 4), "floor_ms": round(floor, 4),
+                    "added_ms": round(ms - floor, 4), "phases_ms": {k: round(v, 4) for k, v in med.items()},
+                    "key_kernel": {"ms": round(med["ms_key"], 4), "bytes": byts, "TBps": round(byts / med["ms_key"] / 1e9, 3),
+                                   "share_of_hbm_peak": round(byts / med["ms_key"] / 1e9 / HBM_TBPS, 3)},
+                    "n_matches": int(res.n_matches), "n_collisions": info["n_collisions"], "path": path, "floor_path": floor_path}
+            del B, P, Bu, Pu
+            ex.release_result()
+            torch.cuda.empty_cache()
+    ex.close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
