@@ -150,6 +150,19 @@ class ColsJoinOpts(C.Structure):
                 ("ms_verify", C.c_float), ("ms_order", C.c_float)]
 
 
+# hmj_cols_kind_opts (hmj_join_kind_cols_device): r_row / s_row of an outer join's unmatched row
+HMJ_COLS_NO_ROW = 0xFFFFFFFFFFFFFFFF
+
+
+class ColsKindOpts(C.Structure):
+    """hmj_cols_kind_opts: side, kind, hash bits, the forced hashed form and fill values (in); the form taken, the kind's
+    counters, pairs of equal key64, pairs whose tuples differ and phase times (out)."""
+    _fields_ = [("struct_size", C.c_uint32), ("side", C.c_uint32), ("kind", C.c_uint32), ("hash_bits", C.c_uint32),
+                ("force_hashed", C.c_uint32), ("form", C.c_uint32), ("probe_fill", C.c_uint64), ("build_fill", C.c_uint64),
+                ("counts", KindCounts), ("n_key_pairs", C.c_uint64), ("n_collisions", C.c_uint64), ("ms_key", C.c_float),
+                ("ms_join", C.c_float), ("ms_verify", C.c_float), ("ms_emit", C.c_float), ("ms_order", C.c_float)]
+
+
 class ColsResult(C.Structure):
     """hmj_cols_result: counts and sums as JoinResult (tmix over (key64, rval, sval)); device columns with HMJ_MATERIALIZE."""
     _fields_ = [("n_matches", C.c_uint64), ("sum_r", C.c_uint64), ("sum_s", C.c_uint64),
@@ -311,6 +324,9 @@ def load_library():
     L.hmj_join_cols_device.restype = i
     L.hmj_join_cols_device.argtypes = [vp, C.POINTER(ColsRel), C.POINTER(ColsRel), C.c_uint32, C.POINTER(ColsJoinOpts),
                                        C.POINTER(ColsResult)]
+    L.hmj_join_kind_cols_device.restype = i
+    L.hmj_join_kind_cols_device.argtypes = [vp, C.POINTER(ColsRel), C.POINTER(ColsRel), C.c_uint32, C.POINTER(ColsKindOpts),
+                                            C.POINTER(ColsResult)]
     L.hmj_prepare_build_u64_device.restype = i
     L.hmj_prepare_build_u64_device.argtypes = [vp, vp, u, u]
     L.hmj_join_u64.restype = i

@@ -78,7 +78,7 @@ static int ilog2_u64(uint64_t v) { return v ? 63 - __builtin_clzll(v) : 0; }
 uint64_t workload_signature(uint64_t n_build, uint64_t n_probe, uint32_t flags, int kind) {
   const uint32_t mode = ((flags & HMJ_ORDERED) ? 4u : 0u) | ((flags & (HMJ_MATERIALIZE | HMJ_ORDERED)) ? 2u : 0u) |
                         ((flags & HMJ_FIRST_WINS) ? 1u : 0u);
-  return ((uint64_t)(kind & 15) << 20) | ((uint64_t)mode << 16) | ((uint64_t)ilog2_u64(n_build) << 8) | (uint64_t)ilog2_u64(n_probe);
+  return ((uint64_t)(kind & 31) << 20) | ((uint64_t)mode << 16) | ((uint64_t)ilog2_u64(n_build) << 8) | (uint64_t)ilog2_u64(n_probe);
 }
 WorkloadMemo* memo_for(hmj_ctx* c, uint64_t sig) {
   auto it = c->memos.find(sig);
@@ -3211,7 +3211,8 @@ void hmj_destroy(hmj_ctx* c) {
                     &c->str_hash, &c->str_rrow, &c->str_srow, &c->str_rval, &c->str_sval, &c->str_list, &c->str_runs, &c->str_acc,
                     &c->str_mark_r, &c->str_mark_s, &c->str_amb, &c->str_ord, &c->str_khash, &c->str_krrow, &c->str_ksrow, &c->str_krval, &c->str_ksval,
                     &c->col_rows_r, &c->col_rows_s, &c->col_flags, &c->col_blk, &c->col_blk_off, &c->col_key, &c->col_rrow, &c->col_srow,
-                    &c->col_rval, &c->col_sval, &c->col_list, &c->col_runs, &c->col_acc};
+                    &c->col_rval, &c->col_sval, &c->col_list, &c->col_runs, &c->col_acc, &c->col_mark_r, &c->col_mark_s, &c->col_amb,
+                    &c->col_ord, &c->col_kkey, &c->col_krrow, &c->col_ksrow, &c->col_krval, &c->col_ksval};
   for (DevBuf* b : devs) free_dev(*b);
   HostBuf* hosts[] = {&c->h_accum, &c->h_key, &c->h_rval, &c->h_sval};
   for (HostBuf* b : hosts) free_host(*b);
@@ -3687,7 +3688,8 @@ void hmj_release_result(hmj_ctx* c) {
   free_dev(c->ord_sval);
   DevBuf* str_cols[5] = {&c->str_hash, &c->str_rrow, &c->str_srow, &c->str_rval, &c->str_sval};
   for (DevBuf* b : str_cols) free_dev(*b);
-  DevBuf* col_cols[5] = {&c->col_key, &c->col_rrow, &c->col_srow, &c->col_rval, &c->col_sval};
+  DevBuf* col_cols[11] = {&c->col_key,  &c->col_rrow,  &c->col_srow,  &c->col_rval,  &c->col_sval, &c->col_ord,
+                          &c->col_kkey, &c->col_krrow, &c->col_ksrow, &c->col_krval, &c->col_ksval};
   for (DevBuf* b : col_cols) free_dev(*b);
   free_host(c->h_key);
   free_host(c->h_rval);

@@ -118,10 +118,13 @@ struct hmj_ctx {
       // their offsets, the result columns (the packed form fills rval / sval only), the collision search's rows and runs,
       // its counters
       col_rows_r, col_rows_s, col_flags, col_blk, col_blk_off, col_key, col_rrow, col_srow, col_rval, col_sval, col_list,
-      col_runs, col_acc;
+      col_runs, col_acc,
+      // multi-column join kinds: one mark byte per row of each relation, the rows whose representative's tuple differed,
+      // the ordered form's (key64, index) rows and sorted copy, the five result columns in sorted order
+      col_mark_r, col_mark_s, col_amb, col_ord, col_kkey, col_krrow, col_ksrow, col_krval, col_ksval;
   hipEvent_t str_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // string joins' phase boundaries (profiling)
-  hipEvent_t col_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // multi-column joins' phase boundaries (profiling)
-  int memo_kind = 0;  // workload-signature kind of plain inner joins run on behalf of another entry (string, multi-column joins)
+  hipEvent_t col_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // multi-column joins' phase boundaries (profiling)
+  int memo_kind = 0;  // workload-signature kind of plain inner joins run on behalf of another entry (string, multi-column joins and their kinds)
   HostBuf h_accum, h_key, h_rval, h_sval;
   int host_threads = 0;  // staging threads for pageable input (0 = default)
   std::vector<hipStream_t> up_streams;

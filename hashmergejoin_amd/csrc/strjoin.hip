@@ -575,7 +575,8 @@ __global__ __launch_bounds__(SV_THREADS) void str_gather_kernel(const u64* __res
 
 namespace {
 
-constexpr int kStrJoinMemoKind = 15;  // workload_signature kind of the inner {hash,row} join (u64 joins 0, sorts 1, kinds 3..9)
+constexpr int kStrJoinMemoKind = 15;  // workload_signature kind of the inner {hash,row} join (u64 joins 0, sorts 1, kinds 3..9,
+                                      // string kinds 10..13, inner multi-column join 14, multi-column kinds 16..19)
 constexpr u64 kNone = ~0ull;
 
 int check_str_rel(hmj_ctx* c, const hmj_str_rel* r, const char* name) {
@@ -772,8 +773,8 @@ int join_str(hmj_ctx* c, const hmj_str_rel* R, const hmj_str_rel* S, uint32_t fl
 }
 
 // ---- join kinds (hmj_join_kind_str_device) -------------------------------------------------------------------------
-// workload_signature kinds of the {hash,row} joins the kinds run (u64 joins 0, sorts 1, u64 kinds 3..9, inner string join
-// 15): none of them teaches a join of another entry anything
+// workload_signature kinds of the {hash,row} joins the kinds run (u64 joins 0, sorts 1, u64 kinds 3..9, inner multi-column
+// join 14, inner string join 15, multi-column kinds 16..19): none of them teaches a join of another entry anything
 constexpr int kMemoProbeRep = 10;  // first-wins join, probe rows against build representatives (probe SEMI / ANTI)
 constexpr int kMemoBuildRep = 11;  // ... build rows against probe representatives (BUILD_SEMI / BUILD_ANTI)
 constexpr int kMemoAmbiguous = 12; // the ambiguous rows against every row of their hash on the other side

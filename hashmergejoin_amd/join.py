@@ -319,6 +319,52 @@ class Executor:
             out[:, c] = tmp.cpu().numpy().view(np.uint64)
         return out
 
+    def join_kind_cols_device(self, build_cols, build_vals, probe_cols, probe_vals, side, kind, flags=0, hash_bits=0,
+                              force_hashed=False, probe_fill=0, build_fill=0):
+        """Semi / anti / outer joins of two device relations on a key of several fixed-width columns
+        (hmj_join_kind_cols_device).  side / kind as for `join_kind_str_device`: HMJ_KIND_PROBE_SIDE with HMJ_JOIN_*, or
+        HMJ_KIND_BUILD_SIDE with HMJ_BUILD_* / HMJ_FULL_OUTER; relations as for `join_cols_device`.  Returns (ColsResult,
+        {"n_probe_matched", "n_probe_unmatched", "n_build_matched", "n_build_unmatched", "form", "n_key_pairs",
+        "n_collisions", "ms_key", "ms_join", "ms_verify", "ms_emit", "ms_order"}); read the rows with
+        `cols_kind_rows_to_numpy`."""
+        self._sync_stream()
+        rb, keep_b = self._cols_rel(build_cols, build_vals)
+        rp, keep_p = self._cols_rel(probe_cols, probe_vals)
+        opts = _lib.ColsKindOpts()
+        opts.struct_size = C.sizeof(_lib.ColsKindOpts)
+        opts.side = int(side)
+        opts.kind = int(kind)
+        opts.hash_bits = int(hash_bits)
+        opts.force_hashed = 1 if force_hashed else 0
+        opts.probe_fill = int(probe_fill) & 0xFFFFFFFFFFFFFFFF
+        opts.build_fill = int(build_fill) & 0xFFFFFFFFFFFFFFFF
+        res = _lib.ColsResult()
+        self._check(self.L.hmj_join_kind_cols_device(self.h, C.byref(rb), C.byref(rp), flags, C.byref(opts), C.byref(res)))
+        del keep_b, keep_p
+        info = opts.counts.as_dict()
+        info.update({"form": int(opts.form), "n_key_pairs": int(opts.n_key_pairs), "n_collisions": int(opts.n_collisions)})
+        for k in ("ms_key", "ms_join", "ms_verify", "ms_emit", "ms_order"):
+            info[k] = float(getattr(opts, k))
+        return res, info
+
+    def cols_kind_rows_to_numpy(self, res):
+        """Copy a multi-column kind join's device result out as an [n,5] uint64 array of (key64, r_row, s_row, rval, sval);
+        a column the kind does not produce (r_row / rval of probe SEMI / ANTI, s_row / sval of BUILD_SEMI / BUILD_ANTI)
+        reads as 0."""
+        n = int(res.n_matches)
+        out = np.empty((n, 5), np.uint64)
+        if n == 0 or not res.key64:
+            return out[:0]
+        torch = self._torch
+        tmp = torch.empty(n, dtype=torch.int64, device="cuda:%d" % self.device)
+        for c, ptr in enumerate((res.key64, res.r_row, res.s_row, res.rval, res.sval)):
+            if not ptr:
+                out[:, c] = 0
+                continue
+            _memcpy_d2d(torch, tmp, ptr, n * 8)
+            out[:, c] = tmp.cpu().numpy().view(np.uint64)
+        return out
+
     def prepare_build(self, build, n_probe_hint):
         """Partition the build side now; the next matching plain-count join_device skips that work."""
         self._sync_stream()

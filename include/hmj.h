@@ -396,7 +396,7 @@ int hmj_exchange_join_kind_u64_device(hmj_ctx* ctx, const void* build_shard_dev,
  * match (count modes and materialising joins of relations of similar size plan alike; a join that plans
  * differently simply partitions R again) skips re-partitioning R; any other call discards the prepared state.  The caller promises the build rows do not change in between.
  * "Any other call" is every call that runs on the device or touches the workspace: the joins of every kind (u64, string,
- * multi-column -- hmj_join_cols_device --, host-resident, exchange), hmj_sort_u64_device, hmj_sort_rows_by_u64_host, hmj_argsort_u64_host, hmj_partition_u64_device,
+ * multi-column -- hmj_join_cols_device, hmj_join_kind_cols_device --, host-resident, exchange), hmj_sort_u64_device, hmj_sort_rows_by_u64_host, hmj_argsort_u64_host, hmj_partition_u64_device,
  * hmj_hash_str_device (each of them also when given no rows), hmj_reserve and hmj_autotune_radix_bits.  Left out are the calls that read or write no workspace buffer: hmj_set_stream,
  * hmj_set_radix_bits / hmj_set_key_prefix_bits (the join then plans other bits and partitions R again), hmj_set_profiling,
  * hmj_forget_workloads, hmj_release_result (result columns only), the hmj_last_* / hmj_placement_info queries and the
@@ -613,10 +613,64 @@ typedef struct {
  * adjacent rows in all) -- with 64 hash bits that takes a genuine collision of the hash above.  The ctx stays usable.
  * hmj_last_plan / hmj_last_timing describe the inner {key64,row} join.  Its workload memo is keyed apart from every
  * other entry's, so multi-column joins do not change what u64 or string joins learn.  Like any other call it discards a
- * prepared build side.  Out of scope: the join kinds, the exchange (multi-GPU) path, host-resident columns, validity
- * bitmaps, returning the key columns, signed / collated ordering.                                                      */
+ * prepared build side.  Join kinds: hmj_join_kind_cols_device below.  Out of scope: the exchange (multi-GPU) path,
+ * host-resident columns, validity bitmaps, returning the key columns, signed / collated ordering.                      */
 int hmj_join_cols_device(hmj_ctx* ctx, const hmj_cols_rel* build, const hmj_cols_rel* probe, uint32_t flags,
                          hmj_cols_join_opts* opts, hmj_cols_result* out);
+
+/* The join kinds of hmj_join_kind_u64_device / hmj_join_build_kind_u64_device on multi-column keys.  opts->side and
+ * opts->kind select the kind as hmj_str_kind_opts does: HMJ_KIND_PROBE_SIDE with HMJ_JOIN_INNER / _SEMI / _ANTI /
+ * _PROBE_OUTER, or HMJ_KIND_BUILD_SIDE with HMJ_BUILD_SEMI / _ANTI / _OUTER / HMJ_FULL_OUTER.  Every kind means what it
+ * means for the u64 entries, with the multi-column join's match rule (all k columns equal bit for bit), its key64
+ * (packed or hashed, hash_bits applied) and its row contents (row indices, payloads; vals == NULL: the payload of row i
+ * is i, for emitted unmatched rows too):
+ *   probe SEMI / ANTI            columns key64, s_row, sval (r_row and rval are NULL); each probe row at most once, and
+ *                                SEMI + ANTI partition the probe relation;
+ *   BUILD_SEMI / BUILD_ANTI      columns key64, r_row, rval (s_row and sval are NULL);
+ *   PROBE_OUTER / BUILD_OUTER /  the inner multi-column join's rows, + (key64, HMJ_COLS_NO_ROW, s_row, probe_fill, sval)
+ *   FULL_OUTER                   per unmatched probe row and / or (key64, r_row, HMJ_COLS_NO_ROW, rval, build_fill) per
+ *                                unmatched build row, as the kind asks.  key64 of an unmatched row is its own tuple's.
+ * n_matches = result rows; sum_r / sum_s and HMJ_CHECKSUM's tmix(key64, rval, sval) are taken over result rows, a missing
+ * value column counting as 0 and fills as written; HMJ_SUM_PROBE is unchanged.  opts->counts: the counters the u64 entry
+ * of the kind fills (probe counters for SEMI / ANTI / PROBE_OUTER, build counters for the build kinds, both for
+ * FULL_OUTER), zeros elsewhere.  opts->form is always filled, empty sides included.
+ * Empty sides as for the u64 kinds: n_build == 0: ANTI, PROBE_OUTER and FULL_OUTER return every probe row; n_probe == 0:
+ * BUILD_ANTI, BUILD_OUTER and FULL_OUTER return every build row (key64 filled); both empty: an empty result and HMJ_OK.
+ * HMJ_ORDERED (implies HMJ_MATERIALIZE): rows ascending by (key64, the tuple compared column by column as UNSIGNED
+ * integers, r_row, s_row), HMJ_COLS_NO_ROW last; (key64, tuple, row) for the semi / anti kinds.  In the packed form that
+ * is plainly ascending tuple order.
+ * HMJ_KIND_PROBE_SIDE + HMJ_JOIN_INNER is exactly hmj_join_cols_device (rows, sums, order, n_key_pairs, n_collisions;
+ * counters 0).
+ * How (DESIGN.md "Multi-column keys on the device", join kinds): semi / anti never form the cross product.  The
+ * {key64,row} rows are joined first-wins, so every row of the side asked about meets ONE row of its key64 on the other
+ * side; a verify pass marks the rows whose tuples are equal (one byte per row; packed: every pair, without loading a
+ * column) and lists the others, which -- only after a collision of the hash -- are joined with every row of their key64
+ * and verified again.  The outer kinds run the inner join's pair join with the same marks (hashed: set by the verification;
+ * packed: by the payload gather).  One sweep per relation emits the rows its mark selects, stably in row order.  Ordered
+ * results are sorted by key64 (a stable u64 sort of (key64, index) rows) and -- hashed only -- runs of equal key64 with
+ * several tuples by tuple, as the inner join sorts them.
+ * HMJ_E_ARG: NULL ctx / rel / opts / out, opts->struct_size smaller than through build_fill, an unknown side or a kind
+ * not of that side, HMJ_FIRST_WINS, and everything hmj_join_cols_device rejects.  HMJ_E_UNSUPPORTED wherever the ordered
+ * inner multi-column join returns it (the same 1024-row and 2^22 limits, over result rows).  The ctx stays usable.
+ * hmj_last_plan / hmj_last_timing describe the last internal u64 join; the kinds' workloads are keyed apart from every
+ * other entry's.  Like any other call it discards a prepared build side.  Out of scope: as hmj_join_cols_device.        */
+#define HMJ_COLS_NO_ROW UINT64_MAX /* r_row / s_row of an outer join's unmatched row: there is no partner            */
+typedef struct {
+  uint32_t struct_size;   /* in: sizeof(hmj_cols_kind_opts) of the caller's header                                     */
+  uint32_t side;          /* in: HMJ_KIND_PROBE_SIDE / HMJ_KIND_BUILD_SIDE                                             */
+  uint32_t kind;          /* in: a kind of that side                                                                   */
+  uint32_t hash_bits;     /* in: as hmj_cols_join_opts                                                                 */
+  uint32_t force_hashed;  /* in: as hmj_cols_join_opts                                                                 */
+  uint32_t form;          /* out: HMJ_COLS_PACKED / HMJ_COLS_HASHED -- always filled, empty sides included             */
+  uint64_t probe_fill;    /* in: rval of an unmatched probe row (PROBE_OUTER, FULL_OUTER)                              */
+  uint64_t build_fill;    /* in: sval of an unmatched build row (BUILD_OUTER, FULL_OUTER)                              */
+  hmj_kind_counts counts; /* out: the counters the u64 entry of the kind fills, zeros elsewhere                        */
+  uint64_t n_key_pairs;   /* out: pairs of equal key64 that were compared (packed: formed)                             */
+  uint64_t n_collisions;  /* out: of those, pairs whose tuples differ (packed: 0)                                       */
+  float ms_key, ms_join, ms_verify, ms_emit, ms_order; /* out, with hmj_set_profiling(ctx, 1): HIP-event phase times   */
+} hmj_cols_kind_opts;
+int hmj_join_kind_cols_device(hmj_ctx* ctx, const hmj_cols_rel* build, const hmj_cols_rel* probe, uint32_t flags,
+                              hmj_cols_kind_opts* opts, hmj_cols_result* out);
 /* Host threads of the optional staged upload (pageable input -> pinned chunks -> PCIe), used only
  * with HMJ_UPLOAD=staged in the environment; by default each relation goes up in one copy straight
  * from the caller's memory (54 GB/s on the MI355X box).  The reference ctor's num_threads argument,

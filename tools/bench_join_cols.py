@@ -12,7 +12,11 @@
                {key64,row} row written) -- and the share of the 8 TB/s HBM peak that is.  ms_key spans two launches and, with
                HMJ_SUM_PROBE off, nothing else.
 
-    python tools/bench_join_cols.py [--reps 20] [--warmup 3] [--log2 24 26]
+  --kinds: the join kinds (hmj_join_kind_cols_device) instead.  Same shapes and sizes, but every second probe tuple is one the
+  build side does not hold; probe SEMI, probe ANTI and FULL_OUTER in count mode, each beside the inner count join
+  (hmj_join_cols_device) of the same relations in the same process, timed the same way: ms, inner_ms, ms / inner_ms.
+
+    python tools/bench_join_cols.py [--reps 20] [--warmup 3] [--log2 24 26] [--kinds]
 """
 import argparse
 import json
@@ -43,17 +47,47 @@ def timed(torch, fn, reps, warmup):
     return statistics.median(ms), out
 
 
-def make_columns(n, widths, seed):
-    """n distinct tuples over `widths` (numpy, unsigned) and a permutation of them for the probe side."""
+def columns_of(ids, widths):
+    if widths == [4, 4]:  # (tenant, id): the id alone is distinct
+        return [(ids >> np.uint64(12)).astype(np.uint32) * np.uint32(2654435761), ids.astype(np.uint32)]
+    # (id scattered over 64 bits, day, flag)
+    return [ids * np.uint64(0x9E3779B97F4A7C15), (ids % np.uint64(36500)).astype(np.uint32), (ids & np.uint64(0xFFFF)).astype(np.uint16)]
+
+
+def make_columns(n, widths, seed, miss_half=False):
+    """n distinct tuples over `widths` (numpy, unsigned) and a permutation of them for the probe side.  miss_half: every
+    second probe tuple is built from an id the build side does not hold (id + n)."""
     rng = np.random.default_rng(seed)
     ids = rng.permutation(n).astype(np.uint64)
-    cols = []
-    if widths == [4, 4]:  # (tenant, id): the id alone is distinct
-        cols = [(ids >> np.uint64(12)).astype(np.uint32) * np.uint32(2654435761), ids.astype(np.uint32)]
-    else:  # (id scattered over 64 bits, day, flag)
-        cols = [ids * np.uint64(0x9E3779B97F4A7C15), (ids % np.uint64(36500)).astype(np.uint32), (ids & np.uint64(0xFFFF)).astype(np.uint16)]
-    perm = rng.permutation(n)
-    return cols, [c[perm] for c in cols]
+    probe_ids = ids[rng.permutation(n)]
+    if miss_half:
+        probe_ids[::2] += np.uint64(n)
+    return columns_of(ids, widths), columns_of(probe_ids, widths)
+
+
+def bench_kinds(torch, H, ex, args, dev, out):
+    kinds = (("semi", H.HMJ_KIND_PROBE_SIDE, H.HMJ_JOIN_SEMI), ("anti", H.HMJ_KIND_PROBE_SIDE, H.HMJ_JOIN_ANTI),
+             ("full_outer", H.HMJ_KIND_BUILD_SIDE, H.HMJ_FULL_OUTER))
+    for lg in args.log2:
+        n = 1 << lg
+        for name, widths in SHAPES:
+            bc, pc = make_columns(n, widths, lg, miss_half=True)
+            B, P = [dev(c) for c in bc], [dev(c) for c in pc]
+            del bc, pc
+            ex.set_profiling(False)
+            inner_ms, (res, info) = timed(torch, lambda: ex.join_cols_device(B, None, P, None, 0), args.reps, args.warmup)
+            assert int(res.n_matches) == n // 2
+            row = {"form": "packed" if info["form"] == H.HMJ_COLS_PACKED else "hashed", "inner_ms": round(inner_ms, 4)}
+            for kname, side, kind in kinds:
+                ms, (res, inf) = timed(torch, lambda: ex.join_kind_cols_device(B, None, P, None, side, kind, 0), args.reps, args.warmup)
+                assert int(res.n_matches) == (n // 2 if kind != H.HMJ_FULL_OUTER else n + n // 2) and inf["n_collisions"] == 0
+                assert (inf["n_probe_matched"], inf["n_probe_unmatched"]) == (n // 2, n // 2)
+                row[kname] = {"ms": round(ms, 4), "vs_inner": round(ms / inner_ms, 3), "n_key_pairs": inf["n_key_pairs"],
+                              "path": ex.last_plan()["path"]}
+            out["kinds_%s_2^%d_count" % (name, lg)] = row
+            del B, P
+            ex.release_result()
+            torch.cuda.empty_cache()
 
 
 def main():
@@ -61,6 +95,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--log2", type=int, nargs="+", default=[24, 26])
+    ap.add_argument("--kinds", action="store_true", help="time probe SEMI / ANTI / FULL_OUTER beside the inner count join")
     args = ap.parse_args()
     import torch
 
@@ -72,6 +107,12 @@ def main():
 
     def dev(a):
         return torch.from_numpy(np.ascontiguousarray(a).view("i%d" % a.dtype.itemsize)).cuda()
+
+    if args.kinds:
+        bench_kinds(torch, H, ex, args, dev, out)
+        ex.close()
+        print(json.dumps(out))
+        return
 
     for lg in args.log2:
         n = 1 << lg
