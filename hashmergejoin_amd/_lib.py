@@ -142,6 +142,12 @@ class ColsRel(C.Structure):
                 ("n", C.c_uint64)]
 
 
+class Validity(C.Structure):
+    """hmj_validity: one key column's Arrow validity bitmap on the device (LSB first; NULL bits: no NULL in the column) and
+    the slice offset of row 0 in it, in bits."""
+    _fields_ = [("bits", C.c_void_p), ("bit_offset", C.c_uint64)]
+
+
 class ColsJoinOpts(C.Structure):
     """hmj_cols_join_opts: hash bits and the forced hashed form (in); the form taken, pairs of equal key64, dropped
     collisions and phase times (out)."""
@@ -155,12 +161,15 @@ HMJ_COLS_NO_ROW = 0xFFFFFFFFFFFFFFFF
 
 
 class ColsKindOpts(C.Structure):
-    """hmj_cols_kind_opts: side, kind, hash bits, the forced hashed form and fill values (in); the form taken, the kind's
-    counters, pairs of equal key64, pairs whose tuples differ and phase times (out)."""
+    """hmj_cols_kind_opts: side, kind, hash bits, the forced hashed form, fill values and the validity bitmaps per side
+    (in); the form taken, the kind's counters, pairs of equal key64, pairs whose tuples differ, phase times and the
+    NULL-key rows per side (out)."""
     _fields_ = [("struct_size", C.c_uint32), ("side", C.c_uint32), ("kind", C.c_uint32), ("hash_bits", C.c_uint32),
                 ("force_hashed", C.c_uint32), ("form", C.c_uint32), ("probe_fill", C.c_uint64), ("build_fill", C.c_uint64),
                 ("counts", KindCounts), ("n_key_pairs", C.c_uint64), ("n_collisions", C.c_uint64), ("ms_key", C.c_float),
-                ("ms_join", C.c_float), ("ms_verify", C.c_float), ("ms_emit", C.c_float), ("ms_order", C.c_float)]
+                ("ms_join", C.c_float), ("ms_verify", C.c_float), ("ms_emit", C.c_float), ("ms_order", C.c_float),
+                ("build_validity", C.POINTER(Validity)), ("probe_validity", C.POINTER(Validity)), ("n_build_null", C.c_uint64),
+                ("n_probe_null", C.c_uint64)]
 
 
 class ColsResult(C.Structure):

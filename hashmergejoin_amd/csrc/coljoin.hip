@@ -22,6 +22,11 @@
 //                         selects emitted stably in row order behind the pairs (one scan over all per-workgroup counts);
 //   order                 (key64, index) rows through the stable u64 sort, one gather, and -- HASHED only -- the collision
 //                         sort's MIXED variants (a row's tuple is its build row's, or its probe row's where there is none).
+// NULL keys (validity bitmaps, calls that pass one only): cols_valid_count_kernel counts the rows whose key columns are all
+// valid per workgroup, one scan places them, and cols_key_valid_kernel writes two arrays per relation: the dense rows the
+// sweeps walk by row index (a NULL-key row: key64 0, row HMJ_COLS_NO_ROW) and the compacted rows of the valid rows, which are
+// all the u64 joins see -- so a NULL-key row is never paired and never marked.  Ordered kinds: the sweeps emit the NULL-key
+// rows into a tail behind the rows that are sorted (DESIGN.md "NULL keys (validity bitmaps)").
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -163,6 +168,92 @@ __global__ __launch_bounds__(CJ_THREADS) void cols_key_kernel(ColSide A, u64 n, 
       for (int k = 0; k < CJ_WAVES; k++) t += red[k];
       if (t) atomicAdd(&acc[CA_SUM_P], t);
     }
+  }
+}
+
+// ---- NULL keys (validity bitmaps) ------------------------------------------------------------------------------------------
+// One relation's Arrow validity bitmaps, passed by value like ColSide: bits[c] == NULL: column c holds no NULL.  Row i is
+// valid in column c iff bit off[c] + i (least-significant bit first) is set; a row is a NULL-key row when any column's is not.
+struct ColValid {
+  const unsigned char* bits[kMaxCols];
+  u64 off[kMaxCols];
+  u32 k;
+};
+__device__ __forceinline__ bool row_valid(const ColValid& V, u64 i) {
+  bool ok = true;
+#pragma unroll
+  for (int c = 0; c < kMaxCols; c++) {
+    if (c < (int)V.k && V.bits[c]) {  // (uniform)
+      const u64 b = V.off[c] + i;
+      ok = ok && ((V.bits[c][b >> 3] >> (b & 7)) & 1u);
+    }
+  }
+  return ok;
+}
+
+// Pass 1 over the bitmaps alone: one lane per row (eight lanes share a byte, a wave reads 8-9 consecutive bytes per
+// column); the valid rows of workgroup b go to blk_cnt[b].
+__global__ __launch_bounds__(CJ_THREADS) void cols_valid_count_kernel(ColValid V, u64 n, u64* __restrict__ blk_cnt) {
+  __shared__ u32 wcnt[CJ_WAVES];
+  const u64 i = (u64)blockIdx.x * CJ_THREADS + threadIdx.x;
+  const bool ok = i < n && row_valid(V, i);
+  const u64 m = __ballot(ok);
+  if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = (u32)__builtin_popcountll(m);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    u64 t = 0;
+    for (int k = 0; k < CJ_WAVES; k++) t += wcnt[k];
+    blk_cnt[blockIdx.x] = t;
+  }
+}
+
+// Pass 2, cols_key_kernel for a relation with bitmaps: one lane per row, one workgroup per 256 rows (blk_off is indexed by
+// workgroup).  dense (NULL: not wanted): row i gets {key64, i}, a NULL-key row {0, HMJ_COLS_NO_ROW} -- what the sweeps walk
+// by row index.  comp: the valid rows' {key64, i}, workgroup b's at blk_off[b] in row order (the wave's ballot places a lane
+// inside its wave, the per-wave counts in LDS the wave inside its workgroup); cap: rows comp holds.  The values under a
+// NULL slot may be loaded; the key made of them is dropped.  sum_probe as cols_key_kernel (every row, NULL-key rows too).
+template <bool HASHED>
+__global__ __launch_bounds__(CJ_THREADS) void cols_key_valid_kernel(ColSide A, ColValid V, u64 n, u32 hash_bits, u64* __restrict__ dense,
+                                                                    u64* __restrict__ comp, u64 cap, const u64* __restrict__ blk_off,
+                                                                    int sum_probe, u64* __restrict__ acc) {
+  __shared__ u64 red[CJ_WAVES];
+  __shared__ u32 wcnt[CJ_WAVES];
+  const u64 i = (u64)blockIdx.x * CJ_THREADS + threadIdx.x;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  bool ok = false;
+  u64 key = 0, sum = 0;
+  if (i < n) {
+    ok = row_valid(V, i);
+    u64 h = HASHED ? (u64)A.k : 0ull;
+#pragma unroll
+    for (int c = 0; c < kMaxCols; c++) {
+      if (c < (int)A.k) {
+        const u64 v = col_load(A.p[c], A.w[c], i);
+        if (HASHED) h = hmj::mix64(h + v + kGolden);
+        else h = A.w[c] == 8 ? v : ((h << (8u * A.w[c])) | v);
+      }
+    }
+    if (HASHED) h = fold_bits(h, hash_bits);
+    key = ok ? h : 0ull;
+    if (dense) reinterpret_cast<ulonglong2*>(dense)[i] = make_ulonglong2(key, ok ? i : kNoRow);
+    if (sum_probe) sum = payload(A, i);
+  }
+  const u64 m = __ballot(ok);
+  if (lane == 0) wcnt[w] = (u32)__builtin_popcountll(m);
+  if (sum_probe) {  // (uniform)
+    sum = hmj::wave_sum_u64(sum);
+    if (lane == 0) red[w] = sum;
+  }
+  __syncthreads();
+  if (ok) {
+    u64 pos = blk_off[blockIdx.x] + hmj::popc_below(m);
+    for (int k = 0; k < w; k++) pos += wcnt[k];
+    if (pos < cap) reinterpret_cast<ulonglong2*>(comp)[pos] = make_ulonglong2(key, i);
+  }
+  if (sum_probe && threadIdx.x == 0) {
+    u64 t = 0;
+    for (int k = 0; k < CJ_WAVES; k++) t += red[k];
+    if (t) atomicAdd(&acc[CA_SUM_P], t);
   }
 }
 
@@ -473,14 +564,20 @@ __global__ __launch_bounds__(CJ_THREADS) void cols_rep_verify_kernel(const u64* 
 
 // A relation's rows as the kinds emit them: row i ({key64, i} in rows) is selected when (mark[i] != 0) == want.  probe: the
 // row goes out as (key64, NO_ROW, i, fill, payload), else as (key64, i, NO_ROW, payload, fill); NULL columns are not
-// written.  vals == NULL: the payload of row i is i.
+// written.  vals == NULL: the payload of row i is i.  nulls (ordered results of a relation with validity bitmaps, whose
+// NULL-key rows carry HMJ_COLS_NO_ROW in rows): 0 = every selected row, 1 = only those with a key, 2 = only the NULL-key rows.
 struct ColSweep {
   const u64* rows;
   const unsigned char* mark;
   const u64* vals;
   u64 n, fill;
-  u32 want, probe;
+  u32 want, probe, nulls;
 };
+__device__ __forceinline__ bool sweep_sel(const ColSweep& W, u64 i) {
+  if (i >= W.n || (W.mark[i] != 0) != (W.want != 0)) return false;
+  if (W.nulls == 0) return true;  // (uniform)
+  return (W.rows[2 * i + 1] == kNoRow) == (W.nulls == 2);
+}
 __device__ __forceinline__ void sweep_vals(const ColSweep& W, u64 i, u64& rv, u64& sv) {
   const u64 v = W.vals ? W.vals[i] : i;
   rv = W.probe ? W.fill : v;
@@ -495,7 +592,7 @@ __global__ __launch_bounds__(CJ_THREADS) void cols_sweep_count_kernel(ColSweep W
   if (threadIdx.x < 8) red[threadIdx.x] = 0;
   __syncthreads();
   const u64 i = (u64)blockIdx.x * CJ_THREADS + threadIdx.x;
-  const bool sel = i < W.n && ((W.mark[i] != 0) == (W.want != 0));
+  const bool sel = sweep_sel(W, i);
   if (MAT) {
     const u64 m = __ballot(sel);
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(&red[0], (u64)__builtin_popcountll(m));
@@ -530,7 +627,7 @@ __global__ __launch_bounds__(CJ_THREADS) void cols_sweep_emit_kernel(ColSweep W,
   if (threadIdx.x < 8) red[threadIdx.x] = 0;
   const u64 i = (u64)blockIdx.x * CJ_THREADS + threadIdx.x;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const bool sel = i < W.n && ((W.mark[i] != 0) == (W.want != 0));
+  const bool sel = sweep_sel(W, i);
   const u64 m = __ballot(sel);
   if (lane == 0) wcnt[w] = (u32)__builtin_popcountll(m);
   __syncthreads();
@@ -639,6 +736,8 @@ ColSide side_of(const hmj_cols_rel* r) {
   return A;
 }
 
+u64 blocks_of(u64 n) { return (n + CJ_THREADS - 1) / CJ_THREADS; }
+
 int launch_key(hmj_ctx* c, const ColSide& A, u64 n, bool hashed, u32 bits, u64* out, bool sum_probe, u64* acc) {
   if (!n) return HMJ_OK;
   const u64 need = (n + CJ_THREADS - 1) / CJ_THREADS, most = (u64)c->num_cus * 16;
@@ -657,6 +756,74 @@ int read_back(hmj_ctx* c, const void* dev, void* host, size_t bytes) {
   return HMJ_OK;
 }
 
+// ---- NULL keys: calls with validity bitmaps ---------------------------------------------------------------------------
+// The bitmaps of one relation as the kernels take them.  *any: at least one column has one (else the call is today's).
+int valid_of(hmj_ctx* c, const hmj_validity* v, const hmj_cols_rel* r, const char* name, ColValid* V, bool* any) {
+  std::memset(V, 0, sizeof(*V));
+  V->k = r->n_cols;
+  *any = false;
+  if (!v) return HMJ_OK;
+  for (u32 k = 0; k < r->n_cols; k++) {
+    if (!v[k].bits) continue;
+    if (v[k].bit_offset > UINT64_MAX - r->n) {
+      char msg[128];
+      std::snprintf(msg, sizeof(msg), "%s relation: column %u: validity bit_offset + n overflows 64 bits", name, k);
+      return fail(c, HMJ_E_ARG, msg);
+    }
+    V->bits[k] = (const unsigned char*)v[k].bits;
+    V->off[k] = v[k].bit_offset;
+    *any = true;
+  }
+  return HMJ_OK;
+}
+
+// The {key64,row} rows of one relation in a call with bitmaps.  dense: the relation's row-indexed rows (NULL: not wanted);
+// *rows / *n_valid: what the u64 joins take.  A relation with a bitmap: its valid rows counted per workgroup (vblk: nblk
+// counts, then nblk + 1 offsets), the total read back, the valid rows compacted into cmp.  A relation without one goes
+// through cols_key_kernel as always, and its dense rows are its join rows.
+int launch_key_valid(hmj_ctx* c, const ColSide& A, const ColValid& V, bool has, u64 n, bool hashed, u32 bits, u64* dense, u64* plain,
+                     DevBuf& cmp, u64* vblk, bool sum_probe, u64* acc, const void** rows, u64* n_valid) {
+  *rows = plain;
+  *n_valid = n;
+  if (!has || !n) return launch_key(c, A, n, hashed, bits, plain, sum_probe, acc);
+  const u64 nblk = blocks_of(n);
+  if (nblk > 0xFFFFFFFFull) return fail(c, HMJ_E_ARG, "multi-column join: too many rows");
+  u64 *cnt = vblk, *off = vblk + nblk;
+  hipLaunchKernelGGL(cols_valid_count_kernel, dim3((u32)nblk), dim3(CJ_THREADS), 0, c->stream, V, n, cnt);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hmj::launch_scan_u64(cnt, off, (u32)nblk, c->stream));
+  u64 nv = 0;
+  RC_TRY(read_back(c, off + nblk, &nv, sizeof(u64)));
+  if (nv > n) return fail(c, HMJ_E_HIP, "multi-column join: more valid rows counted than the relation holds");
+  RC_TRY(ensure_dev(c, cmp, 16 * (nv ? nv : 1)));
+  if (hashed)
+    hipLaunchKernelGGL(cols_key_valid_kernel<true>, dim3((u32)nblk), dim3(CJ_THREADS), 0, c->stream, A, V, n, bits, dense, (u64*)cmp.p, nv,
+                       (const u64*)off, sum_probe ? 1 : 0, acc);
+  else
+    hipLaunchKernelGGL(cols_key_valid_kernel<false>, dim3((u32)nblk), dim3(CJ_THREADS), 0, c->stream, A, V, n, bits, dense, (u64*)cmp.p, nv,
+                       (const u64*)off, sum_probe ? 1 : 0, acc);
+  HIP_TRY(hipGetLastError());
+  *rows = cmp.p;
+  *n_valid = nv;
+  return HMJ_OK;
+}
+
+// Both relations' {key64,row} rows in a call with bitmaps (the block counts of both sides share col_vblk).
+int launch_keys_valid(hmj_ctx* c, const ColSide& RS, const ColSide& SS, const ColValid* VB, const ColValid* VP, u64 nb, u64 np,
+                      bool hashed, u32 bits, bool dense, bool sum_probe, u64* acc, const void** rows_r, u64* nvb, const void** rows_s,
+                      u64* nvp) {
+  const u64 kb = VB ? blocks_of(nb) : 0, kp = VP ? blocks_of(np) : 0;
+  RC_TRY(ensure_dev(c, c->col_vblk, (2 * (kb + kp) + 2) * sizeof(u64)));
+  u64* vblk = (u64*)c->col_vblk.p;
+  const ColValid none{};
+  u64 *plain_r = (u64*)c->col_rows_r.p, *plain_s = (u64*)c->col_rows_s.p;
+  RC_TRY(launch_key_valid(c, RS, VB ? *VB : none, VB != nullptr, nb, hashed, bits, dense ? plain_r : nullptr, plain_r, c->col_cmp_r, vblk,
+                          false, acc, rows_r, nvb));
+  RC_TRY(launch_key_valid(c, SS, VP ? *VP : none, VP != nullptr, np, hashed, bits, dense ? plain_s : nullptr, plain_s, c->col_cmp_s,
+                          vblk + 2 * kb + 1, sum_probe, acc, rows_s, nvp));
+  return HMJ_OK;
+}
+
 int record(hmj_ctx* c, int k) {
   if (!c->profiling) return HMJ_OK;
   if (!c->col_ev[k]) HIP_TRY(hipEventCreate(&c->col_ev[k]));
@@ -672,7 +839,11 @@ float elapsed(hmj_ctx* c, int a, int b) {
   return ms;
 }
 
-int join_cols(hmj_ctx* c, const hmj_cols_rel* R, const hmj_cols_rel* S, uint32_t flags, hmj_cols_join_opts* opts, hmj_cols_result* out) {
+// VB / VP: the relations' validity bitmaps, NULL where a relation has none (both NULL: the call without NULL keys, all
+// hmj_join_cols_device makes -- hmj_cols_join_opts carries no bitmaps; the INNER kind of hmj_join_kind_cols_device passes
+// its own).  n_null (with bitmaps): the NULL-key rows of the build and the probe side.
+int join_cols(hmj_ctx* c, const hmj_cols_rel* R, const hmj_cols_rel* S, uint32_t flags, hmj_cols_join_opts* opts, hmj_cols_result* out,
+              const ColValid* VB = nullptr, const ColValid* VP = nullptr, u64* n_null = nullptr) {
   const u64 nb = R->n, np = S->n;
   u32 total = 0;
   for (u32 k = 0; k < R->n_cols; k++) total += R->cols[k].width;
@@ -690,10 +861,21 @@ int join_cols(hmj_ctx* c, const hmj_cols_rel* R, const hmj_cols_rel* S, uint32_t
   // 1. {key64, row} rows of both relations (+ the probe payloads' sum)
   RC_TRY(record(c, 0));
   HIP_TRY(hipMemsetAsync(acc, 0, CA_N * sizeof(u64), c->stream));
-  RC_TRY(launch_key(c, RS, nb, hashed, bits, (u64*)c->col_rows_r.p, false, acc));
-  RC_TRY(launch_key(c, SS, np, hashed, bits, (u64*)c->col_rows_s.p, flags & HMJ_SUM_PROBE, acc));
+  const void *rows_r = c->col_rows_r.p, *rows_s = c->col_rows_s.p;  // the rows the u64 join takes
+  u64 nvb = nb, nvp = np;                                           // ... and how many: the rows that have a key
+  if (!VB && !VP) {
+    RC_TRY(launch_key(c, RS, nb, hashed, bits, (u64*)c->col_rows_r.p, false, acc));
+    RC_TRY(launch_key(c, SS, np, hashed, bits, (u64*)c->col_rows_s.p, flags & HMJ_SUM_PROBE, acc));
+  } else {  // NULL keys: only the rows that have a key are joined (the inner join walks no relation by row: no dense rows)
+    RC_TRY(launch_keys_valid(c, RS, SS, VB, VP, nb, np, hashed, bits, false, flags & HMJ_SUM_PROBE, acc, &rows_r, &nvb, &rows_s, &nvp));
+    if (n_null) {
+      n_null[0] = nb - nvb;
+      n_null[1] = np - nvp;
+    }
+    if (nb && np) opts->form = hashed ? HMJ_COLS_HASHED : HMJ_COLS_PACKED;
+  }
   RC_TRY(record(c, 1));
-  if (nb == 0 || np == 0) {  // (nothing to join: no plan either)
+  if (nvb == 0 || nvp == 0) {  // (nothing to join: no plan either)
     std::memset(&c->plan, 0, sizeof(c->plan));
     c->plan.struct_size = sizeof(c->plan);
     std::memset(&c->timing, 0, sizeof(c->timing));
@@ -710,7 +892,7 @@ int join_cols(hmj_ctx* c, const hmj_cols_rel* R, const hmj_cols_rel* S, uint32_t
   spans_reset(c);
   const int st = span_begin(c, K_TOTAL, -1);
   c->memo_kind = kColsJoinMemoKind;
-  const int rc = join_device(c, c->col_rows_r.p, nb, c->col_rows_s.p, np, HMJ_MATERIALIZE | (flags & HMJ_ORDERED), &inner, false);
+  const int rc = join_device(c, rows_r, nvb, rows_s, nvp, HMJ_MATERIALIZE | (flags & HMJ_ORDERED), &inner, false);
   c->memo_kind = 0;
   span_end(c, st);
   if (c->profiling) {
@@ -838,9 +1020,8 @@ int memo_join(hmj_ctx* c, const void* Rr, u64 nr, const void* Sr, u64 ns, uint32
   return rc;
 }
 
-u64 blocks_of(u64 n) { return (n + CJ_THREADS - 1) / CJ_THREADS; }
-
-int join_cols_kind(hmj_ctx* c, const hmj_cols_rel* R, const hmj_cols_rel* S, uint32_t flags, hmj_cols_kind_opts* o, hmj_cols_result* out) {
+int join_cols_kind(hmj_ctx* c, const hmj_cols_rel* R, const hmj_cols_rel* S, uint32_t flags, hmj_cols_kind_opts* o, hmj_cols_result* out,
+                   const ColValid* VB, const ColValid* VP) {
   const u64 nb = R->n, np = S->n;
   const u32 kind = o->kind;
   u32 total = 0;
@@ -871,8 +1052,17 @@ int join_cols_kind(hmj_ctx* c, const hmj_cols_rel* R, const hmj_cols_rel* S, uin
   // 1. {key64, row} rows of both relations (+ the probe payloads' sum), marks cleared
   RC_TRY(record(c, 0));
   HIP_TRY(hipMemsetAsync(acc, 0, kKindAccBlocks * CA_N * sizeof(u64), c->stream));
-  RC_TRY(launch_key(c, RS, nb, hashed, bits, (u64*)c->col_rows_r.p, false, acc));
-  RC_TRY(launch_key(c, SS, np, hashed, bits, (u64*)c->col_rows_s.p, flags & HMJ_SUM_PROBE, acc));
+  // (NULL keys: the dense rows stay indexed by row for the sweeps; the u64 joins take only the rows that have a key)
+  const void *rows_r = c->col_rows_r.p, *rows_s = c->col_rows_s.p;
+  u64 nvb = nb, nvp = np;
+  if (!VB && !VP) {
+    RC_TRY(launch_key(c, RS, nb, hashed, bits, (u64*)c->col_rows_r.p, false, acc));
+    RC_TRY(launch_key(c, SS, np, hashed, bits, (u64*)c->col_rows_s.p, flags & HMJ_SUM_PROBE, acc));
+  } else {
+    RC_TRY(launch_keys_valid(c, RS, SS, VB, VP, nb, np, hashed, bits, true, flags & HMJ_SUM_PROBE, acc, &rows_r, &nvb, &rows_s, &nvp));
+    o->n_build_null = nb - nvb;
+    o->n_probe_null = np - nvp;
+  }
   if (nb) HIP_TRY(hipMemsetAsync(mark_r, 0, nb, c->stream));
   if (np) HIP_TRY(hipMemsetAsync(mark_s, 0, np, c->stream));
   RC_TRY(record(c, 1));
@@ -883,8 +1073,8 @@ int join_cols_kind(hmj_ctx* c, const hmj_cols_rel* R, const hmj_cols_rel* S, uin
   std::memset(&inner, 0, sizeof(inner));
   if (semi_anti) {
     // every row of the side asked about (K) meets the FIRST row of its key64 on the other side (O), in row order
-    const u64 nK = bside ? nb : np, nO = bside ? np : nb;
-    const void *rowsK = bside ? c->col_rows_r.p : c->col_rows_s.p, *rowsO = bside ? c->col_rows_s.p : c->col_rows_r.p;
+    const u64 nK = bside ? nvb : nvp, nO = bside ? nvp : nvb;
+    const void *rowsK = bside ? rows_r : rows_s, *rowsO = bside ? rows_s : rows_r;
     const ColSide &KS = bside ? RS : SS, &OS = bside ? SS : RS;
     unsigned char* mark = bside ? mark_r : mark_s;
     if (nK && nO) {
@@ -921,8 +1111,8 @@ int join_cols_kind(hmj_ctx* c, const hmj_cols_rel* R, const hmj_cols_rel* S, uin
     } else {
       RC_TRY(record(c, 2));
     }
-  } else if (nb && np) {
-    RC_TRY(memo_join(c, c->col_rows_r.p, nb, c->col_rows_s.p, np, HMJ_MATERIALIZE | (flags & HMJ_ORDERED), kMemoPairs, &inner));
+  } else if (nvb && nvp) {
+    RC_TRY(memo_join(c, rows_r, nvb, rows_s, nvp, HMJ_MATERIALIZE | (flags & HMJ_ORDERED), kMemoPairs, &inner));
     RC_TRY(record(c, 2));
     n_pairs = inner.n_matches;
   } else {
@@ -933,7 +1123,15 @@ int join_cols_kind(hmj_ctx* c, const hmj_cols_rel* R, const hmj_cols_rel* S, uin
   // result rows: the pairs (outer kinds), then the probe sweep's rows, then the build sweep's
   const u64 nblk_v = semi_anti ? 0 : blocks_of(n_pairs);
   const u64 nblk_p = sweep_p ? blocks_of(np) : 0, nblk_b = sweep_b ? blocks_of(nb) : 0;
-  const u64 nblk = nblk_v + nblk_p + nblk_b;
+  // ordered, NULL keys: the sweeps above take the rows that have a key, and a second launch per relation puts its NULL-key
+  // rows (never marked: only the kinds that take unmarked rows emit them) into a tail behind everything that is sorted --
+  // the build side's in r_row order, then the probe side's in s_row order
+  const u32 want = kind == HMJ_JOIN_SEMI ? 1u : 0u;
+  const bool split_b = ordered && VB, split_p = ordered && VP;
+  const u64 nblk_tb = split_b && sweep_b && !want && nvb < nb ? blocks_of(nb) : 0;
+  const u64 nblk_tp = split_p && sweep_p && !want && nvp < np ? blocks_of(np) : 0;
+  const u64 nblk_m = nblk_v + nblk_p + nblk_b;  // workgroups of the rows that have a key
+  const u64 nblk = nblk_m + nblk_tb + nblk_tp;
   if (nblk > 0xFFFFFFFFull) return fail(c, HMJ_E_UNSUPPORTED, "multi-column join: more than 2^40 pairs of equal key64");
   const u64 cap = (semi_anti ? 0 : n_pairs) + (sweep_p ? np : 0) + (sweep_b ? nb : 0);
   DevBuf* cols[5] = {&c->col_key, &c->col_rrow, &c->col_srow, &c->col_rval, &c->col_sval};
@@ -968,18 +1166,24 @@ int join_cols_kind(hmj_ctx* c, const hmj_cols_rel* R, const hmj_cols_rel* S, uin
   }
   RC_TRY(record(c, 3));
   // 4. the sweeps: SEMI / BUILD_SEMI take the marked rows, every other kind the unmarked ones
-  const u32 want = kind == HMJ_JOIN_SEMI ? 1u : 0u;
   const u64 pfill = !semi_anti && (!bside || kind == HMJ_FULL_OUTER) ? o->probe_fill : 0ull;
   const u64 bfill = !semi_anti && bside ? o->build_fill : 0ull;
-  const ColSweep WP{(const u64*)c->col_rows_s.p, mark_s, SS.vals, np, pfill, want, 1u};
-  const ColSweep WB{(const u64*)c->col_rows_r.p, mark_r, RS.vals, nb, bfill, want, 0u};
-  u64 n_out = 0, n_in = 0;  // result rows; of those, pairs (materialising)
+  const ColSweep WP{(const u64*)c->col_rows_s.p, mark_s, SS.vals, np, pfill, want, 1u, split_p ? 1u : 0u};
+  const ColSweep WB{(const u64*)c->col_rows_r.p, mark_r, RS.vals, nb, bfill, want, 0u, split_b ? 1u : 0u};
+  ColSweep TP = WP, TB = WB;  // the tails' sweeps
+  TP.nulls = TB.nulls = 2u;
+  u64 n_out = 0, n_in = 0, n_main = 0;  // result rows; of those, pairs (materialising); rows in front of the NULL-key tail
   if (mat) {
     const u64* blk_off = (const u64*)c->col_blk_off.p;
     if (nblk_p)
       hipLaunchKernelGGL(cols_sweep_count_kernel<true>, dim3((u32)nblk_p), dim3(CJ_THREADS), 0, c->stream, WP, blk + nblk_v, nullptr, 0);
     if (nblk_b)
       hipLaunchKernelGGL(cols_sweep_count_kernel<true>, dim3((u32)nblk_b), dim3(CJ_THREADS), 0, c->stream, WB, blk + nblk_v + nblk_p,
+                         nullptr, 0);
+    if (nblk_tb)
+      hipLaunchKernelGGL(cols_sweep_count_kernel<true>, dim3((u32)nblk_tb), dim3(CJ_THREADS), 0, c->stream, TB, blk + nblk_m, nullptr, 0);
+    if (nblk_tp)
+      hipLaunchKernelGGL(cols_sweep_count_kernel<true>, dim3((u32)nblk_tp), dim3(CJ_THREADS), 0, c->stream, TP, blk + nblk_m + nblk_tb,
                          nullptr, 0);
     HIP_TRY(hipGetLastError());
     if (nblk) HIP_TRY(hmj::launch_scan_u64(blk, (u64*)c->col_blk_off.p, (u32)nblk, c->stream));
@@ -992,10 +1196,18 @@ int join_cols_kind(hmj_ctx* c, const hmj_cols_rel* R, const hmj_cols_rel* S, uin
     if (nblk_b)
       hipLaunchKernelGGL(cols_sweep_emit_kernel, dim3((u32)nblk_b), dim3(CJ_THREADS), 0, c->stream, WB, blk_off + nblk_v + nblk_p,
                          oc[0], oc[1], oc[2], oc[3], oc[4], acc_b, checksum ? 1 : 0);
+    if (nblk_tb)
+      hipLaunchKernelGGL(cols_sweep_emit_kernel, dim3((u32)nblk_tb), dim3(CJ_THREADS), 0, c->stream, TB, blk_off + nblk_m, oc[0], oc[1],
+                         oc[2], oc[3], oc[4], acc_b, checksum ? 1 : 0);
+    if (nblk_tp)
+      hipLaunchKernelGGL(cols_sweep_emit_kernel, dim3((u32)nblk_tp), dim3(CJ_THREADS), 0, c->stream, TP, blk_off + nblk_m + nblk_tb,
+                         oc[0], oc[1], oc[2], oc[3], oc[4], acc_p, checksum ? 1 : 0);
     HIP_TRY(hipGetLastError());
     if (nblk) {
       HIP_TRY(hipMemcpyAsync(&n_in, blk_off + nblk_v, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipMemcpyAsync(&n_main, blk_off + nblk_m, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
       RC_TRY(read_back(c, blk_off + nblk, &n_out, sizeof(u64)));
+      if (n_main > n_out || n_out > cap) return fail(c, HMJ_E_HIP, "multi-column join: the sweeps' offsets exceed the result's capacity");
     }
   } else {
     if (nblk_p)
@@ -1010,15 +1222,16 @@ int join_cols_kind(hmj_ctx* c, const hmj_cols_rel* R, const hmj_cols_rel* S, uin
   // 5. ordered: a stable sort of (key64, index) rows, the columns gathered in that order; hashed: then runs of equal key64
   // with several tuples sorted by tuple.  (Outer kinds without unmatched rows are already in (key64, r_row, s_row) order;
   // packed: equal key64 is equal tuples, so there is no collision to search for.)
-  if (ordered && n_out > 1) {
-    if (n_out > n_in) {
-      RC_TRY(ensure_dev(c, c->col_ord, 32 * n_out));
+  // NULL keys: only the n_main rows in front of the tail are sorted; the tail is already in its order and is copied behind.
+  if (ordered && n_main > 1) {
+    if (n_main > n_in) {
+      RC_TRY(ensure_dev(c, c->col_ord, 32 * n_main));
       u64* ord = (u64*)c->col_ord.p;
-      hipLaunchKernelGGL(cols_sort_rows_kernel, dim3((u32)blocks_of(n_out)), dim3(CJ_THREADS), 0, c->stream, oc[0], n_out, ord);
+      hipLaunchKernelGGL(cols_sort_rows_kernel, dim3((u32)blocks_of(n_main)), dim3(CJ_THREADS), 0, c->stream, oc[0], n_main, ord);
       HIP_TRY(hipGetLastError());
       const hmj_plan_desc plan = c->plan;  // (the sort is not a join: hmj_last_plan / hmj_last_timing keep describing the last one)
       const hmj_timing timing = c->timing;
-      const int rc = hmj_sort_u64_device(c, ord, n_out, ord + 2 * n_out);
+      const int rc = hmj_sort_u64_device(c, ord, n_main, ord + 2 * n_main);
       c->plan = plan;
       c->timing = timing;
       if (rc != HMJ_OK) return rc;
@@ -1030,21 +1243,25 @@ int join_cols_kind(hmj_ctx* c, const hmj_cols_rel* R, const hmj_cols_rel* S, uin
         RC_TRY(ensure_dev(c, *kc[k], n_out * sizeof(u64)));
         nc[k] = (u64*)kc[k]->p;
       }
-      hipLaunchKernelGGL(cols_order_gather_kernel, dim3((u32)blocks_of(n_out)), dim3(CJ_THREADS), 0, c->stream,
-                         (const u64*)(ord + 2 * n_out), n_out, oc[1], oc[2], oc[3], oc[4], nc[0], nc[1], nc[2], nc[3], nc[4]);
+      hipLaunchKernelGGL(cols_order_gather_kernel, dim3((u32)blocks_of(n_main)), dim3(CJ_THREADS), 0, c->stream,
+                         (const u64*)(ord + 2 * n_main), n_main, oc[1], oc[2], oc[3], oc[4], nc[0], nc[1], nc[2], nc[3], nc[4]);
       HIP_TRY(hipGetLastError());
-      for (int k = 0; k < 5; k++) oc[k] = nc[k];
+      for (int k = 0; k < 5; k++) {
+        if (nc[k] && n_out > n_main)
+          HIP_TRY(hipMemcpyAsync(nc[k] + n_main, oc[k] + n_main, (n_out - n_main) * sizeof(u64), hipMemcpyDeviceToDevice, c->stream));
+        oc[k] = nc[k];
+      }
     }
     if (hashed) {
-      const u64 lcap = n_out < kListCap ? n_out : kListCap;
+      const u64 lcap = n_main < kListCap ? n_main : kListCap;
       RC_TRY(ensure_dev(c, c->col_list, lcap * sizeof(u64)));
       RC_TRY(ensure_dev(c, c->col_runs, 2 * lcap * sizeof(u64)));
-      hipLaunchKernelGGL(cols_mismatch_kernel<true>, dim3((u32)blocks_of(n_out - 1)), dim3(CJ_THREADS), 0, c->stream, (const u64*)oc[0],
-                         (const u64*)oc[1], n_out, RS, (u64*)c->col_list.p, acc, (const u64*)oc[2], SS);
+      hipLaunchKernelGGL(cols_mismatch_kernel<true>, dim3((u32)blocks_of(n_main - 1)), dim3(CJ_THREADS), 0, c->stream, (const u64*)oc[0],
+                         (const u64*)oc[1], n_main, RS, (u64*)c->col_list.p, acc, (const u64*)oc[2], SS);
       HIP_TRY(hipGetLastError());
       const u64 gl = blocks_of(lcap);
       hipLaunchKernelGGL(cols_run_leader_kernel<true>, dim3((u32)(gl < 1024 ? gl : 1024)), dim3(CJ_THREADS), 0, c->stream,
-                         (const u64*)oc[0], (const u64*)oc[1], n_out, RS, (const u64*)c->col_list.p, (u64*)c->col_runs.p, acc,
+                         (const u64*)oc[0], (const u64*)oc[1], n_main, RS, (const u64*)c->col_list.p, (u64*)c->col_runs.p, acc,
                          (const u64*)oc[2], SS);
       HIP_TRY(hipGetLastError());
       const u64 gs = lcap < (u64)(4 * c->num_cus) ? lcap : (u64)(4 * c->num_cus);
@@ -1114,6 +1331,29 @@ int check_cols_args(hmj_ctx* c, const hmj_cols_rel* build, const hmj_cols_rel* p
   return HMJ_OK;
 }
 
+// The validity arrays of a hmj_cols_kind_opts whose struct_size covers them, as the kernels take them; *pb / *pp stay NULL
+// for a relation without a bitmap.
+int opts_validity(hmj_ctx* c, const hmj_cols_kind_opts* opts, const hmj_cols_rel* build, const hmj_cols_rel* probe, ColValid* VB, ColValid* VP,
+                  const ColValid** pb, const ColValid** pp) {
+  *pb = *pp = nullptr;
+  if (opts->struct_size < offsetof(hmj_cols_kind_opts, probe_validity) + sizeof(opts->probe_validity)) return HMJ_OK;
+  bool any_b = false, any_p = false;
+  RC_TRY(valid_of(c, opts->build_validity, build, "build", VB, &any_b));
+  RC_TRY(valid_of(c, opts->probe_validity, probe, "probe", VP, &any_p));
+  if (any_b) *pb = VB;
+  if (any_p) *pp = VP;
+  return HMJ_OK;
+}
+// The out fields of a full-size copy o of the caller's opts are cleared from `first_out` on; the in fields that lie behind
+// them (the validity arrays) are the caller's again, as far as its struct_size holds them.
+void clear_out_fields(hmj_cols_kind_opts* o, const hmj_cols_kind_opts* opts, size_t first_out) {
+  using T = hmj_cols_kind_opts;
+  std::memset((char*)o + first_out, 0, sizeof(T) - first_out);
+  const size_t lo = offsetof(T, build_validity), hi = offsetof(T, n_build_null);
+  const size_t have = opts->struct_size < hi ? opts->struct_size : hi;
+  if (have > lo) std::memcpy((char*)o + lo, (const char*)opts + lo, have - lo);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1157,6 +1397,9 @@ int hmj_join_kind_cols_device(hmj_ctx* c, const hmj_cols_rel* build, const hmj_c
   if (opts->side == HMJ_KIND_PROBE_SIDE ? opts->kind > HMJ_JOIN_PROBE_OUTER : (opts->kind < HMJ_BUILD_SEMI || opts->kind > HMJ_FULL_OUTER))
     return fail(c, HMJ_E_ARG, "unknown join kind");
   RC_TRY(check_cols_args(c, build, probe, flags, opts->hash_bits));
+  ColValid VB, VP;
+  const ColValid *vb, *vp;
+  RC_TRY(opts_validity(c, opts, build, probe, &VB, &VP, &vb, &vp));
   std::memset(out, 0, sizeof(*out));
   HIP_TRY(hipSetDevice(c->device));
   // the out fields of opts go to a full-size copy first; the caller gets the prefix its struct_size holds
@@ -1164,14 +1407,17 @@ int hmj_join_kind_cols_device(hmj_ctx* c, const hmj_cols_rel* build, const hmj_c
   std::memset(&o, 0, sizeof(o));
   std::memcpy(&o, opts, opts->struct_size < sizeof(o) ? opts->struct_size : sizeof(o));
   o.form = 0;
-  std::memset(&o.counts, 0, sizeof(o) - offsetof(hmj_cols_kind_opts, counts));
+  clear_out_fields(&o, opts, offsetof(hmj_cols_kind_opts, counts));
   if (o.side == HMJ_KIND_PROBE_SIDE && o.kind == HMJ_JOIN_INNER) {  // exactly the inner multi-column join
     hmj_cols_join_opts jo;
     std::memset(&jo, 0, sizeof(jo));
     jo.struct_size = sizeof(jo);
     jo.hash_bits = o.hash_bits;
     jo.force_hashed = o.force_hashed;
-    RC_TRY(join_cols(c, build, probe, flags, &jo, out));
+    u64 n_null[2] = {0, 0};
+    RC_TRY(join_cols(c, build, probe, flags, &jo, out, vb, vp, n_null));
+    o.n_build_null = n_null[0];
+    o.n_probe_null = n_null[1];
     u32 total = 0;  // (the inner entry leaves form 0 when a side is empty; here it is always filled)
     for (u32 k = 0; k < build->n_cols; k++) total += build->cols[k].width;
     o.form = total > 8 || o.force_hashed ? HMJ_COLS_HASHED : HMJ_COLS_PACKED;
@@ -1185,7 +1431,7 @@ int hmj_join_kind_cols_device(hmj_ctx* c, const hmj_cols_rel* build, const hmj_c
       o.ms_order = elapsed(c, 3, 4);
     }
   } else {
-    RC_TRY(join_cols_kind(c, build, probe, flags, &o, out));
+    RC_TRY(join_cols_kind(c, build, probe, flags, &o, out, vb, vp));
     if (c->profiling) {
       (void)hipStreamSynchronize(c->stream);
       o.ms_key = elapsed(c, 0, 1);

@@ -285,12 +285,52 @@ class Executor:
         r.n = n
         return r, arr
 
-    def join_cols_device(self, build_cols, build_vals, probe_cols, probe_vals, flags=0, hash_bits=0, force_hashed=False):
+    def _validity(self, valid, rel, name):
+        """A relation's validity bitmaps -> the Validity array hmj_cols_*_opts point to (None: no bitmap on this side) and
+        what keeps it and its tensors alive for the call.  valid: None, or one entry per key column: None, a uint8 device
+        tensor (an Arrow bitmap, LSB first), or (tensor, bit_offset)."""
+        if valid is None:
+            return None, None
+        valid = list(valid)
+        if len(valid) != rel.n_cols:
+            raise ValueError("%s: one entry per key column" % name)
+        n = int(rel.n)
+        arr = (_lib.Validity * max(len(valid), 1))()
+        keep = [arr]
+        for k, v in enumerate(valid):
+            if v is None:
+                continue
+            t, off = v if isinstance(v, tuple) else (v, 0)
+            off = int(off)
+            if not t.is_cuda or not t.is_contiguous() or t.dim() != 1 or t.element_size() != 1:
+                raise ValueError("%s[%d] must be a contiguous 1-D uint8 device tensor" % (name, k))
+            if off < 0:
+                raise ValueError("%s[%d]: bit_offset must not be negative" % (name, k))
+            if off + n < (1 << 64) and t.shape[0] * 8 < off + n:  # (an overflowing offset is the library's to reject)
+                raise ValueError("%s[%d] holds fewer than bit_offset + n bits" % (name, k))
+            # (n == 0: the pointer is still passed; nothing reads it)
+            arr[k].bits = t.data_ptr() if t.shape[0] else None
+            arr[k].bit_offset = off & 0xFFFFFFFFFFFFFFFF
+            keep.append(t)
+        return arr, keep
+
+    def join_cols_device(self, build_cols, build_vals, probe_cols, probe_vals, flags=0, hash_bits=0, force_hashed=False,
+                         build_valid=None, probe_valid=None):
         """Inner join of two device relations on a key of several fixed-width columns (hmj_join_cols_device).  *_cols:
         lists of 1-D contiguous device tensors of any dtype whose element_size() is 1, 2, 4 or 8 (compared bit for bit);
-        *_vals: an int64 tensor [n], or None (the payload of row i is i).  Returns (ColsResult, {"form", "n_key_pairs",
-        "n_collisions", "ms_key", "ms_join", "ms_verify", "ms_order"}); read the rows with `cols_rows_to_numpy`,
-        reproduce key64 with `cols_key64`."""
+        *_vals: an int64 tensor [n], or None (the payload of row i is i).  *_valid: None, or a list with one entry per key
+        column -- None, a uint8 device tensor holding the column's Arrow validity bitmap (`pack_validity`), or (tensor,
+        bit_offset); a row with a NULL in any key column matches nothing.  hmj_cols_join_opts carries no bitmaps, so a call
+        with *_valid runs the INNER kind of hmj_join_kind_cols_device, which is the same join (its "form" is filled for
+        empty sides too).  Returns (ColsResult, {"form", "n_key_pairs", "n_collisions", "n_build_null", "n_probe_null",
+        "ms_key", "ms_join", "ms_verify", "ms_order"}); read the rows with `cols_rows_to_numpy`, reproduce key64 with
+        `cols_key64`."""
+        if build_valid is not None or probe_valid is not None:
+            res, info = self.join_kind_cols_device(build_cols, build_vals, probe_cols, probe_vals, _lib.HMJ_KIND_PROBE_SIDE,
+                                                   _lib.HMJ_JOIN_INNER, flags, hash_bits, force_hashed, build_valid=build_valid,
+                                                   probe_valid=probe_valid)
+            keys = ("form", "n_key_pairs", "n_collisions", "n_build_null", "n_probe_null", "ms_key", "ms_join", "ms_verify", "ms_order")
+            return res, {k: info[k] for k in keys}
         self._sync_stream()
         rb, keep_b = self._cols_rel(build_cols, build_vals)
         rp, keep_p = self._cols_rel(probe_cols, probe_vals)
@@ -301,7 +341,8 @@ class Executor:
         res = _lib.ColsResult()
         self._check(self.L.hmj_join_cols_device(self.h, C.byref(rb), C.byref(rp), flags, C.byref(opts), C.byref(res)))
         del keep_b, keep_p
-        info = {"form": int(opts.form), "n_key_pairs": int(opts.n_key_pairs), "n_collisions": int(opts.n_collisions)}
+        info = {"form": int(opts.form), "n_key_pairs": int(opts.n_key_pairs), "n_collisions": int(opts.n_collisions),
+                "n_build_null": 0, "n_probe_null": 0}
         for k in ("ms_key", "ms_join", "ms_verify", "ms_order"):
             info[k] = float(getattr(opts, k))
         return res, info
@@ -320,13 +361,14 @@ class Executor:
         return out
 
     def join_kind_cols_device(self, build_cols, build_vals, probe_cols, probe_vals, side, kind, flags=0, hash_bits=0,
-                              force_hashed=False, probe_fill=0, build_fill=0):
+                              force_hashed=False, probe_fill=0, build_fill=0, build_valid=None, probe_valid=None):
         """Semi / anti / outer joins of two device relations on a key of several fixed-width columns
         (hmj_join_kind_cols_device).  side / kind as for `join_kind_str_device`: HMJ_KIND_PROBE_SIDE with HMJ_JOIN_*, or
-        HMJ_KIND_BUILD_SIDE with HMJ_BUILD_* / HMJ_FULL_OUTER; relations as for `join_cols_device`.  Returns (ColsResult,
+        HMJ_KIND_BUILD_SIDE with HMJ_BUILD_* / HMJ_FULL_OUTER; relations and *_valid as for `join_cols_device` (a NULL-key
+        row has no partner: ANTI and the outer kinds of its side emit it with key64 0).  Returns (ColsResult,
         {"n_probe_matched", "n_probe_unmatched", "n_build_matched", "n_build_unmatched", "form", "n_key_pairs",
-        "n_collisions", "ms_key", "ms_join", "ms_verify", "ms_emit", "ms_order"}); read the rows with
-        `cols_kind_rows_to_numpy`."""
+        "n_collisions", "n_build_null", "n_probe_null", "ms_key", "ms_join", "ms_verify", "ms_emit", "ms_order"}); read
+        the rows with `cols_kind_rows_to_numpy`."""
         self._sync_stream()
         rb, keep_b = self._cols_rel(build_cols, build_vals)
         rp, keep_p = self._cols_rel(probe_cols, probe_vals)
@@ -338,11 +380,18 @@ class Executor:
         opts.force_hashed = 1 if force_hashed else 0
         opts.probe_fill = int(probe_fill) & 0xFFFFFFFFFFFFFFFF
         opts.build_fill = int(build_fill) & 0xFFFFFFFFFFFFFFFF
+        vb, keep_vb = self._validity(build_valid, rb, "build_valid")
+        vp, keep_vp = self._validity(probe_valid, rp, "probe_valid")
+        if vb is not None:
+            opts.build_validity = vb
+        if vp is not None:
+            opts.probe_validity = vp
         res = _lib.ColsResult()
         self._check(self.L.hmj_join_kind_cols_device(self.h, C.byref(rb), C.byref(rp), flags, C.byref(opts), C.byref(res)))
-        del keep_b, keep_p
+        del keep_b, keep_p, keep_vb, keep_vp
         info = opts.counts.as_dict()
-        info.update({"form": int(opts.form), "n_key_pairs": int(opts.n_key_pairs), "n_collisions": int(opts.n_collisions)})
+        info.update({"form": int(opts.form), "n_key_pairs": int(opts.n_key_pairs), "n_collisions": int(opts.n_collisions),
+                     "n_build_null": int(opts.n_build_null), "n_probe_null": int(opts.n_probe_null)})
         for k in ("ms_key", "ms_join", "ms_verify", "ms_emit", "ms_order"):
             info[k] = float(getattr(opts, k))
         return res, info
@@ -615,6 +664,22 @@ def pack_strings(keys, device=None):
     if device is not None:
         c, o = c.to(device), o.to(device)
     return c, o
+
+
+def pack_validity(mask, bit_offset=0, device=None):
+    """A bool array (True = valid) -> the Arrow validity bitmap of a column slice that starts `bit_offset` bits into it:
+    a uint8 tensor of ceil((bit_offset + n) / 8) bytes, least-significant bit first, row i at bit bit_offset + i.  The
+    bits in front of bit_offset are set on purpose -- a reader that ignores the offset sees valid rows where it should
+    not --; the padding behind the last row is 0.  device=None leaves the tensor on the CPU."""
+    import torch
+
+    mask = np.asarray(mask, bool).ravel()
+    bit_offset = int(bit_offset)
+    if bit_offset < 0:
+        raise ValueError("bit_offset must not be negative")
+    bits = np.concatenate([np.ones(bit_offset, bool), mask])
+    t = torch.from_numpy(np.packbits(bits, bitorder="little"))
+    return t if device is None else t.to(device)
 
 
 def _mix64(x):

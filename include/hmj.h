@@ -563,6 +563,12 @@ typedef struct {
 #define HMJ_COLS_PACKED 1u
 #define HMJ_COLS_HASHED 2u
 typedef struct {
+  const void* bits;     /* device: Arrow validity bitmap, least-significant bit first: row i is valid iff
+                           (bits[(bit_offset + i) >> 3] >> ((bit_offset + i) & 7)) & 1.  NULL: no NULL in this column.
+                           Byte-aligned only; never written                                                  */
+  uint64_t bit_offset;  /* Arrow slice offset, any value with bit_offset + n not overflowing                */
+} hmj_validity;
+typedef struct {
   uint32_t struct_size;     /* in: sizeof of the caller's header (size-versioned like hmj_str_join_opts)               */
   uint32_t hash_bits;       /* in: hashed form only; 0 = 64, 1..63 = h >> (64 - hash_bits): fewer bits make collisions  */
                             /* between different tuples common -- exists so callers and tests can exercise them        */
@@ -614,7 +620,11 @@ typedef struct {
  * hmj_last_plan / hmj_last_timing describe the inner {key64,row} join.  Its workload memo is keyed apart from every
  * other entry's, so multi-column joins do not change what u64 or string joins learn.  Like any other call it discards a
  * prepared build side.  Join kinds: hmj_join_kind_cols_device below.  Out of scope: the exchange (multi-GPU) path,
- * host-resident columns, validity bitmaps, returning the key columns, signed / collated ordering.                      */
+ * host-resident columns, returning the key columns, signed / collated ordering.
+ * NULL keys (Arrow validity bitmaps, hmj_validity above): hmj_cols_join_opts keeps its layout and carries none, so this
+ * entry joins columns without NULLs.  The inner join of nullable key columns is hmj_join_kind_cols_device below with
+ * HMJ_KIND_PROBE_SIDE + HMJ_JOIN_INNER, whose opts carry one hmj_validity per key column and side: the same rows, sums,
+ * order, n_key_pairs and n_collisions over the rows that have a key.                                                     */
 int hmj_join_cols_device(hmj_ctx* ctx, const hmj_cols_rel* build, const hmj_cols_rel* probe, uint32_t flags,
                          hmj_cols_join_opts* opts, hmj_cols_result* out);
 
@@ -653,7 +663,39 @@ int hmj_join_cols_device(hmj_ctx* ctx, const hmj_cols_rel* build, const hmj_cols
  * not of that side, HMJ_FIRST_WINS, and everything hmj_join_cols_device rejects.  HMJ_E_UNSUPPORTED wherever the ordered
  * inner multi-column join returns it (the same 1024-row and 2^22 limits, over result rows).  The ctx stays usable.
  * hmj_last_plan / hmj_last_timing describe the last internal u64 join; the kinds' workloads are keyed apart from every
- * other entry's.  Like any other call it discards a prepared build side.  Out of scope: as hmj_join_cols_device.        */
+ * other entry's.  Like any other call it discards a prepared build side.  Out of scope: as hmj_join_cols_device.
+ * NULL keys (Arrow validity bitmaps): opts->build_validity / probe_validity give one hmj_validity per key column of that
+ * side (a NULL array, entries with bits == NULL and bitmaps on one side only are all valid; a call without any bitmap
+ * launches exactly the kernels of a call that cannot pass one).  The fields are read and written only when struct_size
+ * covers them: a caller built against the header without them gets that header's behaviour bit for bit.  A row is a
+ * NULL-key row when at least one of its key columns is NULL in that row.  SQL's three-valued equality: a NULL-key row
+ * matches nothing -- no row of the other side and no other NULL-key row --, so it has no partner, and every kind follows
+ * with NOT EXISTS semantics (not NOT IN):
+ *   kind          NULL-key probe row                                      NULL-key build row
+ *   INNER         not in the result                                       not in the result
+ *   probe SEMI    not emitted                                             -
+ *   probe ANTI    emitted                                                 -
+ *   PROBE_OUTER   unmatched: (0, NO_ROW, s_row, probe_fill, sval)         not in the result
+ *   BUILD_SEMI    -                                                       not emitted
+ *   BUILD_ANTI    -                                                       emitted
+ *   BUILD_OUTER   not in the result                                       unmatched: (0, r_row, NO_ROW, rval, build_fill)
+ *   FULL_OUTER    emitted as unmatched                                    emitted as unmatched
+ * key64 of a NULL-key row is 0 wherever such a row is emitted; the sums and HMJ_CHECKSUM use that 0.  The bytes under a
+ * NULL slot are undefined and nothing in the result depends on them.  counts: n_*_unmatched includes the NULL-key rows of
+ * that side, so SEMI + ANTI still partition the relation; n_build_null / n_probe_null are filled by every kind and are 0
+ * without bitmaps.  n_key_pairs / n_collisions: NULL-key rows are never paired and count in neither.  HMJ_SUM_PROBE sums
+ * every probe row's payload, NULL-key rows included.
+ * HMJ_ORDERED: NULL-key rows come after every non-NULL row, among themselves ascending by (r_row, s_row) with
+ * HMJ_COLS_NO_ROW last -- in a FULL_OUTER result the build side's NULL-key rows by r_row, then the probe side's by s_row --;
+ * non-NULL rows keep the order above exactly.  NULL-key rows never enter the sort or the collision sort (the sweeps emit
+ * them into a tail segment of their own), so the 1024-row and 2^22 limits count non-NULL rows only.
+ * A side whose rows are all NULL-key behaves as an empty side for matching; its rows are still emitted by the kinds that
+ * emit unmatched rows of that side.  opts->form is filled as always.  HMJ_E_ARG also: bit_offset + n overflows 64 bits.
+ * How: a pass over the bitmaps alone counts the valid rows per workgroup (cols_valid_count_kernel), one scan places the
+ * workgroups, and cols_key_valid_kernel writes the {key64,row} rows of the valid rows only, compacted stably in row order;
+ * the u64 joins take those.  Row indices in the result stay the caller's.
+ * Out of scope for NULL keys: NULL-equals-NULL matching (IS NOT DISTINCT FROM), validity of the payload column, string
+ * keys' validity (hmj_join_str_device), the exchange path, bitmaps in hmj_cols_join_opts (use the INNER kind here).        */
 #define HMJ_COLS_NO_ROW UINT64_MAX /* r_row / s_row of an outer join's unmatched row: there is no partner            */
 typedef struct {
   uint32_t struct_size;   /* in: sizeof(hmj_cols_kind_opts) of the caller's header                                     */
@@ -668,6 +710,10 @@ typedef struct {
   uint64_t n_key_pairs;   /* out: pairs of equal key64 that were compared (packed: formed)                             */
   uint64_t n_collisions;  /* out: of those, pairs whose tuples differ (packed: 0)                                       */
   float ms_key, ms_join, ms_verify, ms_emit, ms_order; /* out, with hmj_set_profiling(ctx, 1): HIP-event phase times   */
+  /* NULL keys (above).  Read / written only when struct_size covers them; a shorter struct is a call without bitmaps */
+  const hmj_validity* build_validity; /* in: HOST array of n_cols entries (read during the call only), or NULL */
+  const hmj_validity* probe_validity; /* in: likewise                                                          */
+  uint64_t n_build_null, n_probe_null; /* out: NULL-key rows per side (0 without bitmaps); every kind, INNER included */
 } hmj_cols_kind_opts;
 int hmj_join_kind_cols_device(hmj_ctx* ctx, const hmj_cols_rel* build, const hmj_cols_rel* probe, uint32_t flags,
                               hmj_cols_kind_opts* opts, hmj_cols_result* out);

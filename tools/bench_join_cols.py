@@ -16,7 +16,13 @@
   build side does not hold; probe SEMI, probe ANTI and FULL_OUTER in count mode, each beside the inner count join
   (hmj_join_cols_device) of the same relations in the same process, timed the same way: ms, inner_ms, ms / inner_ms.
 
-    python tools/bench_join_cols.py [--reps 20] [--warmup 3] [--log2 24 26] [--kinds]
+  --nulls FRAC: NULL keys (validity bitmaps) instead.  Same shapes and sizes, the --kinds relations.  In one process and on
+  the same rows the inner count join -- with --kinds also probe SEMI, probe ANTI and FULL_OUTER in count mode -- is timed
+  three ways: plain_ms (no bitmap: the call as it was), all_valid_ms (a bitmap of ones on column 1 of both sides: what the
+  feature itself costs -- a pass over the bitmaps, a scan, a read-back and the compacted {key64,row} rows) and nulls_ms (FRAC
+  of the rows of each side NULL in column 1).
+
+    python tools/bench_join_cols.py [--reps 20] [--warmup 3] [--log2 24 26] [--kinds] [--nulls FRAC]
 """
 import argparse
 import json
@@ -90,12 +96,58 @@ def bench_kinds(torch, H, ex, args, dev, out):
             torch.cuda.empty_cache()
 
 
+def bench_nulls(torch, H, ex, args, dev, out):
+    calls = [("inner", None, None)]
+    if args.kinds:
+        calls += [("semi", H.HMJ_KIND_PROBE_SIDE, H.HMJ_JOIN_SEMI), ("anti", H.HMJ_KIND_PROBE_SIDE, H.HMJ_JOIN_ANTI),
+                  ("full_outer", H.HMJ_KIND_BUILD_SIDE, H.HMJ_FULL_OUTER)]
+    out["nulls_frac"] = args.nulls
+    for lg in args.log2:
+        n = 1 << lg
+        for name, widths in SHAPES:
+            bc, pc = make_columns(n, widths, lg, miss_half=True)
+            B, P = [dev(c) for c in bc], [dev(c) for c in pc]
+            del bc, pc
+            rng = np.random.default_rng(lg + 1)
+            k = len(widths)
+            on_col1 = lambda t: [None, t] + [None] * (k - 2)
+            ones = H.pack_validity(np.ones(n, bool), 0, "cuda")
+            mb, mp = rng.random(n) >= args.nulls, rng.random(n) >= args.nulls
+            variants = (("plain_ms", None, None), ("all_valid_ms", on_col1(ones), on_col1(ones)),
+                        ("nulls_ms", on_col1(H.pack_validity(mb, 0, "cuda")), on_col1(H.pack_validity(mp, 0, "cuda"))))
+            ex.set_profiling(False)
+            for cname, side, kind in calls:
+                row = {}
+                for vname, vb, vp in variants:
+                    if kind is None:
+                        fn = lambda: ex.join_cols_device(B, None, P, None, 0, build_valid=vb, probe_valid=vp)
+                    else:
+                        fn = lambda: ex.join_kind_cols_device(B, None, P, None, side, kind, 0, build_valid=vb, probe_valid=vp)
+                    ms, (res, inf) = timed(torch, fn, args.reps, args.warmup)
+                    row[vname] = round(ms, 4)
+                    if vname != "nulls_ms":
+                        assert (inf["n_build_null"], inf["n_probe_null"]) == (0, 0)
+                        row["n_matches"] = int(res.n_matches)
+                    else:
+                        assert (inf["n_build_null"], inf["n_probe_null"]) == (int((~mb).sum()), int((~mp).sum()))
+                        row["n_matches_nulls"] = int(res.n_matches)
+                    row["form"] = "packed" if inf["form"] == H.HMJ_COLS_PACKED else "hashed"
+                row["all_valid_vs_plain"] = round(row["all_valid_ms"] / row["plain_ms"], 3)
+                row["nulls_vs_plain"] = round(row["nulls_ms"] / row["plain_ms"], 3)
+                out["nulls_%s_%s_2^%d_count" % (cname, name, lg)] = row
+            del B, P, ones, variants
+            ex.release_result()
+            torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--log2", type=int, nargs="+", default=[24, 26])
     ap.add_argument("--kinds", action="store_true", help="time probe SEMI / ANTI / FULL_OUTER beside the inner count join")
+    ap.add_argument("--nulls", type=float, default=None, metavar="FRAC",
+                    help="time the plain call, the call with all-valid bitmaps and the call with FRAC of the rows NULL-keyed")
     args = ap.parse_args()
     import torch
 
@@ -108,6 +160,11 @@ def main():
     def dev(a):
         return torch.from_numpy(np.ascontiguousarray(a).view("i%d" % a.dtype.itemsize)).cuda()
 
+    if args.nulls is not None:
+        bench_nulls(torch, H, ex, args, dev, out)
+        ex.close()
+        print(json.dumps(out))
+        return
     if args.kinds:
         bench_kinds(torch, H, ex, args, dev, out)
         ex.close()
