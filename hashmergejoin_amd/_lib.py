@@ -107,13 +107,20 @@ class StrJoinOpts(C.Structure):
 HMJ_STR_NO_ROW = 0xFFFFFFFFFFFFFFFF
 
 
+class Validity(C.Structure):
+    """hmj_validity: one key column's Arrow validity bitmap on the device (LSB first; NULL bits: no NULL in the column) and
+    the slice offset of row 0 in it, in bits."""
+    _fields_ = [("bits", C.c_void_p), ("bit_offset", C.c_uint64)]
+
+
 class StrKindOpts(C.Structure):
-    """hmj_str_kind_opts: side, kind, hash bits and fill values (in); the kind's counters, pairs of equal hash, pairs whose
-    keys differ and phase times (out)."""
+    """hmj_str_kind_opts: side, kind, hash bits, fill values and the key column's validity bitmap per side (in); the kind's
+    counters, pairs of equal hash, pairs whose keys differ, phase times and the NULL-key rows per side (out)."""
     _fields_ = [("struct_size", C.c_uint32), ("side", C.c_uint32), ("kind", C.c_uint32), ("hash_bits", C.c_uint32),
                 ("probe_fill", C.c_uint64), ("build_fill", C.c_uint64), ("counts", KindCounts), ("n_hash_pairs", C.c_uint64),
                 ("n_collisions", C.c_uint64), ("ms_hash", C.c_float), ("ms_join", C.c_float), ("ms_verify", C.c_float),
-                ("ms_emit", C.c_float), ("ms_order", C.c_float)]
+                ("ms_emit", C.c_float), ("ms_order", C.c_float), ("build_validity", Validity), ("probe_validity", Validity),
+                ("n_build_null", C.c_uint64), ("n_probe_null", C.c_uint64)]
 
 
 class StrResult(C.Structure):
@@ -140,12 +147,6 @@ class ColsRel(C.Structure):
     """hmj_cols_rel: a relation keyed by a tuple of fixed-width columns (struct of arrays) + optional payloads."""
     _fields_ = [("cols", C.POINTER(KeyCol)), ("n_cols", C.c_uint32), ("reserved", C.c_uint32), ("vals", C.c_void_p),
                 ("n", C.c_uint64)]
-
-
-class Validity(C.Structure):
-    """hmj_validity: one key column's Arrow validity bitmap on the device (LSB first; NULL bits: no NULL in the column) and
-    the slice offset of row 0 in it, in bits."""
-    _fields_ = [("bits", C.c_void_p), ("bit_offset", C.c_uint64)]
 
 
 class ColsJoinOpts(C.Structure):

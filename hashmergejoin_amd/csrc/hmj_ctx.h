@@ -124,7 +124,9 @@ struct hmj_ctx {
       col_mark_r, col_mark_s, col_amb, col_ord, col_kkey, col_krrow, col_ksrow, col_krval, col_ksval,
       // multi-column joins with validity bitmaps only: the {key64, row} rows of the non-NULL rows of each relation
       // (compacted, in row order), the valid rows per workgroup of both relations and their offsets
-      col_cmp_r, col_cmp_s, col_vblk;
+      col_cmp_r, col_cmp_s, col_vblk,
+      // string joins with validity bitmaps only: likewise ({hash, row} rows of the non-NULL rows, counts and offsets)
+      str_cmp_r, str_cmp_s, str_vblk;
   hipEvent_t str_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // string joins' phase boundaries (profiling)
   hipEvent_t col_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // multi-column joins' phase boundaries (profiling)
   int memo_kind = 0;  // workload-signature kind of plain inner joins run on behalf of another entry (string, multi-column joins and their kinds)

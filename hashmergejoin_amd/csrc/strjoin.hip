@@ -14,6 +14,11 @@
 //   str_sweep_*_kernel     one lane per row of a relation: the rows its mark selects, counted / summed, then written in
 //                          row order (stable) with their payload or the kind's fill;
 //   str_sort_rows_kernel / str_gather_kernel   ordered kinds: (hash, index) rows for the u64 sort, columns gathered.
+// NULL keys (validity bitmaps, calls that pass one only): str_valid_count_kernel counts the rows that have a key per
+// workgroup, one scan places them, and str_hash_valid_kernel writes two arrays per relation: the dense rows the sweeps walk
+// by row index (a NULL-key row: hash 0, row HMJ_STR_NO_ROW) and the compacted rows of the valid rows, which are all the u64
+// joins see.  Row indices stay the caller's, so verification, marks and gathers are unchanged; ordered results emit the
+// NULL-key rows into a tail behind the rows that are sorted (DESIGN.md "NULL keys on string keys").
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -31,6 +36,11 @@ namespace {
   do {                                                          \
     hipError_t _e = (expr);                                     \
     if (_e != hipSuccess) return fail(c, HMJ_E_HIP, #expr, _e); \
+  } while (0)
+#define RC_TRY(expr)                   \
+  do {                                 \
+    const int _rc = (expr);            \
+    if (_rc != HMJ_OK) return _rc;     \
   } while (0)
 
 constexpr u64 kMul = 0xc6a4a7935bd1e995ull;
@@ -165,6 +175,105 @@ __global__ __launch_bounds__(SH_THREADS) void str_hash_kernel(const unsigned cha
     reinterpret_cast<ulonglong2*>(out)[i] = make_ulonglong2(h, i);
   } else {
     out[i] = h;
+  }
+}
+
+// ---- NULL keys (validity bitmaps) ------------------------------------------------------------------------------------------
+// One relation's Arrow validity bitmap (coljoin.hip's ColValid for the one key column a string relation has): row i has a
+// key iff bit off + i (least-significant bit first) is set.  Only calls that pass a bitmap reach the two kernels below.
+struct StrValid {
+  const unsigned char* bits;
+  u64 off;
+};
+__device__ __forceinline__ bool row_valid(const StrValid& V, u64 i) {
+  const u64 b = V.off + i;
+  return (V.bits[b >> 3] >> (b & 7)) & 1u;
+}
+
+// Pass 1 over the bitmap alone: one lane per row (eight lanes share a byte, a wave reads 8-9 consecutive bytes); the valid
+// rows of workgroup b -- the 256 rows str_hash_valid_kernel's workgroup b hashes -- go to blk_cnt[b].
+__global__ __launch_bounds__(SH_THREADS) void str_valid_count_kernel(StrValid V, u64 n, u64* __restrict__ blk_cnt) {
+  __shared__ u32 wcnt[SH_WAVES];
+  const u64 i = (u64)blockIdx.x * SH_THREADS + threadIdx.x;
+  const bool ok = i < n && row_valid(V, i);
+  const u64 m = __ballot(ok);
+  if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = (u32)__builtin_popcountll(m);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    u64 t = 0;
+    for (int k = 0; k < SH_WAVES; k++) t += wcnt[k];
+    blk_cnt[blockIdx.x] = t;
+  }
+}
+
+// Pass 2, str_hash_kernel for a relation with a bitmap: the same wave spans, staging and offset checks (a NULL slot's
+// offsets must not decrease either, and its bytes are staged with the span; a NULL lane hashes nothing).  dense (NULL: not
+// wanted): row i gets {hash, i}, a NULL-key row {0, HMJ_STR_NO_ROW} -- what the sweeps walk by row index.  comp: the valid
+// rows' {hash, i}, workgroup b's at blk_off[b] in row order (the wave's ballot places a lane inside its wave, the per-wave
+// counts in LDS the wave inside its workgroup); cap: rows comp holds.  No lane leaves before the second barrier: a lane
+// that is inactive, NULL or in a wave whose offsets are unusable only takes no part in the ballot's count.  Such a wave
+// reports its row as str_hash_kernel does and compacts nothing, so the rows behind it land in front of their places --
+// inside comp, and in a call that fails.
+__global__ __launch_bounds__(SH_THREADS) void str_hash_valid_kernel(const unsigned char* __restrict__ chars, const u64* __restrict__ offsets,
+                                                                    u64 n, u32 hash_bits, StrValid V, u64* __restrict__ dense,
+                                                                    u64* __restrict__ comp, u64 cap, const u64* __restrict__ blk_off,
+                                                                    const u64* __restrict__ vals, u64* __restrict__ acc) {
+  __shared__ u64 stage[SH_WAVES][SH_STAGE / 8 + 2];
+  __shared__ u32 wcnt[SH_WAVES];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const u64 i0 = ((u64)blockIdx.x * SH_WAVES + (u64)w) * 64ull;
+  const u64 i = i0 + (u64)lane;
+  const bool active = i < n;
+  const u64 iend = i0 + 64 < n ? i0 + 64 : n;
+  u64 o0 = 0, o1 = 0, s0 = 0, s1 = 0;
+  if (i0 < n) {
+    const u64 a = offsets[active ? i : n];
+    const u64 e = offsets[iend];
+    const u64 nxt = __shfl_down(a, 1, 64);
+    o0 = a;
+    o1 = lane == 63 ? e : nxt;
+    if (i + 1 == iend) o1 = e;
+    s0 = __shfl(a, 0, 64);
+    s1 = e;
+  }
+  const bool bad = active && o1 < o0;
+  const u64 bad_mask = __ballot(bad);
+  if (bad_mask && lane == (int)__builtin_ctzll(bad_mask)) atomicMin(&acc[SA_BAD_ROW], i);
+  const bool ok_wave = i0 < n && !bad_mask && s1 >= s0;
+  if (ok_wave && !chars && s1 > s0 && lane == 0) atomicAdd(&acc[SA_NULL_CHARS], 1ull);
+  const bool usable = ok_wave && (chars || s1 == s0);
+  const uintptr_t b0 = usable ? ((uintptr_t)(chars + s0) & ~(uintptr_t)15) : 0;
+  const u64 span_bytes = usable && s1 > s0 ? (u64)(((uintptr_t)(chars + s1) + 15) & ~(uintptr_t)15) - (u64)b0 : 0;
+  const bool staged = usable && span_bytes <= (u64)SH_STAGE;
+  if (staged) {
+    const uint4* src = reinterpret_cast<const uint4*>(b0);
+    uint4* dst = reinterpret_cast<uint4*>(&stage[w][0]);
+    for (u32 k = (u32)lane; k < (u32)(span_bytes >> 4); k += 64) dst[k] = src[k];
+  }
+  if (vals && i0 < n) {  // (every row's payload, NULL-key rows included)
+    const u64 vs = hmj::wave_sum_u64(active ? vals[i] : 0ull);
+    if (lane == 0) atomicAdd(&acc[SA_ACC + hmj::ACC_SUM_P], vs);
+  }
+  const bool ok = usable && active && row_valid(V, active ? i : 0);
+  __syncthreads();
+  u64 h = 0;
+  if (ok) {
+    const u64 len = o1 - o0;
+    if (staged) {
+      h = hash_bytes(LdsLd{&stage[w][0]}, (u64)((uintptr_t)(chars + o0) - b0), len);
+    } else {
+      h = hash_bytes(GlobalLd{}, (u64)(uintptr_t)(chars + o0), len);
+    }
+    h = fold_bits(h, hash_bits);
+  }
+  if (dense && active) reinterpret_cast<ulonglong2*>(dense)[i] = make_ulonglong2(h, ok ? i : kNoRow);
+  const u64 m = __ballot(ok);
+  if (lane == 0) wcnt[w] = (u32)__builtin_popcountll(m);
+  __syncthreads();
+  if (ok) {
+    u64 pos = blk_off[blockIdx.x] + hmj::popc_below(m);
+    for (int k = 0; k < w; k++) pos += wcnt[k];
+    if (pos < cap) reinterpret_cast<ulonglong2*>(comp)[pos] = make_ulonglong2(h, i);
   }
 }
 
@@ -466,13 +575,20 @@ __global__ __launch_bounds__(SV_THREADS) void str_rep_verify_kernel(const u64* _
 
 // A relation's rows as the kinds emit them: row i ({hash, i} in rows) is selected when (mark[i] != 0) == want.  probe: the
 // row goes out as (hash, NO_ROW, i, fill, vals[i]), else as (hash, i, NO_ROW, vals[i], fill); NULL columns are not written.
+// nulls (ordered results of a relation with a validity bitmap, whose NULL-key rows carry HMJ_STR_NO_ROW in rows): 0 = every
+// selected row, 1 = only those with a key, 2 = only the NULL-key rows.
 struct Sweep {
   const u64* rows;
   const unsigned char* mark;
   const u64* vals;
   u64 n, fill;
-  u32 want, probe;
+  u32 want, probe, nulls;
 };
+__device__ __forceinline__ bool sweep_sel(const Sweep& W, u64 i) {
+  if (i >= W.n || (W.mark[i] != 0) != (W.want != 0)) return false;
+  if (W.nulls == 0) return true;  // (uniform)
+  return (W.rows[2 * i + 1] == kNoRow) == (W.nulls == 2);
+}
 __device__ __forceinline__ void sweep_vals(const Sweep& W, u64 i, u64& rv, u64& sv) {
   const u64 v = W.vals[i];
   rv = W.probe ? W.fill : v;
@@ -487,7 +603,7 @@ __global__ __launch_bounds__(SV_THREADS) void str_sweep_count_kernel(Sweep W, u6
   if (threadIdx.x < 8) red[threadIdx.x] = 0;
   __syncthreads();
   const u64 i = (u64)blockIdx.x * SV_THREADS + threadIdx.x;
-  const bool sel = i < W.n && ((W.mark[i] != 0) == (W.want != 0));
+  const bool sel = sweep_sel(W, i);
   if (MAT) {
     const u64 m = __ballot(sel);
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(&red[0], (u64)__builtin_popcountll(m));
@@ -522,7 +638,7 @@ __global__ __launch_bounds__(SV_THREADS) void str_sweep_emit_kernel(Sweep W, con
   if (threadIdx.x < 8) red[threadIdx.x] = 0;
   const u64 i = (u64)blockIdx.x * SV_THREADS + threadIdx.x;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const bool sel = i < W.n && ((W.mark[i] != 0) == (W.want != 0));
+  const bool sel = sweep_sel(W, i);
   const u64 m = __ballot(sel);
   if (lane == 0) wcnt[w] = (u32)__builtin_popcountll(m);
   __syncthreads();
@@ -613,6 +729,45 @@ int launch_hash(hmj_ctx* c, const void* chars, const u64* offsets, u64 n, u32 bi
   return HMJ_OK;
 }
 
+// NULL keys: the {hash,row} rows of both relations in a call with bitmaps (VB / VP: NULL where a relation has none; such a
+// relation goes through str_hash_kernel as always, and its dense rows are its join rows).  A relation with a bitmap: its
+// valid rows counted per workgroup and scanned (str_vblk: nblk counts, then nblk + 1 offsets, the build side's first), then
+// hashed into cmp (room for every row: no read-back between the passes) and, if `dense`, into the row-indexed str_rows_*.
+// rows[2] / tot[2]: what the u64 joins take, and where on the device the number of those rows stands (NULL: every row).
+int launch_hashes_valid(hmj_ctx* c, const hmj_str_rel* R, const hmj_str_rel* S, const StrValid* VB, const StrValid* VP, u32 bits, bool dense,
+                        bool sum_probe, u64* acc, const void** rows, const u64** tot) {
+  const hmj_str_rel* rel[2] = {R, S};
+  const StrValid* V[2] = {VB, VP};
+  DevBuf* plain[2] = {&c->str_rows_r, &c->str_rows_s};
+  DevBuf* cmp[2] = {&c->str_cmp_r, &c->str_cmp_s};
+  u64 nblk[2];
+  for (int k = 0; k < 2; k++) nblk[k] = V[k] && rel[k]->n ? (rel[k]->n + SH_THREADS - 1) / SH_THREADS : 0;
+  RC_TRY(ensure_dev(c, c->str_vblk, (2 * (nblk[0] + nblk[1]) + 2) * sizeof(u64)));
+  u64* vblk = (u64*)c->str_vblk.p;
+  for (int k = 0; k < 2; k++) {
+    const u64 n = rel[k]->n;
+    const u64* vals = k == 1 && sum_probe ? (const u64*)rel[k]->vals : nullptr;
+    rows[k] = plain[k]->p;
+    tot[k] = nullptr;
+    if (!nblk[k]) {
+      RC_TRY(launch_hash(c, rel[k]->chars, (const u64*)rel[k]->offsets, n, bits, (u64*)plain[k]->p, true, vals, acc + k * SA_N));
+      continue;
+    }
+    u64 *cnt = vblk + (k ? 2 * nblk[0] + 1 : 0), *off = cnt + nblk[k];
+    RC_TRY(ensure_dev(c, *cmp[k], 16 * n));
+    hipLaunchKernelGGL(str_valid_count_kernel, dim3((u32)nblk[k]), dim3(SH_THREADS), 0, c->stream, *V[k], n, cnt);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hmj::launch_scan_u64(cnt, off, (u32)nblk[k], c->stream));
+    hipLaunchKernelGGL(str_hash_valid_kernel, dim3((u32)nblk[k]), dim3(SH_THREADS), 0, c->stream, (const unsigned char*)rel[k]->chars,
+                       (const u64*)rel[k]->offsets, n, bits, *V[k], dense ? (u64*)plain[k]->p : nullptr, (u64*)cmp[k]->p, n,
+                       (const u64*)off, vals, acc + k * SA_N);
+    HIP_TRY(hipGetLastError());
+    rows[k] = cmp[k]->p;
+    tot[k] = off + nblk[k];
+  }
+  return HMJ_OK;
+}
+
 // the hash kernel's verdict on one relation's offsets (h: its acc block, read back)
 int hash_errors(hmj_ctx* c, const u64* h, const char* name) {
   char msg[160];
@@ -649,14 +804,12 @@ float elapsed(hmj_ctx* c, int a, int b) {
   return ms;
 }
 
-#define RC_TRY(expr)                   \
-  do {                                 \
-    const int _rc = (expr);            \
-    if (_rc != HMJ_OK) return _rc;     \
-  } while (0)
-
-int join_str(hmj_ctx* c, const hmj_str_rel* R, const hmj_str_rel* S, uint32_t flags, hmj_str_join_opts* opts, hmj_str_result* out) {
-  const u64 nb = R->n, np = S->n;
+// VB / VP: the relations' validity bitmaps, NULL where a relation has none (both NULL: the call without NULL keys, all
+// hmj_join_str_device makes -- hmj_str_join_opts carries no bitmap; the INNER kind of hmj_join_kind_str_device passes its
+// own).  n_null (with bitmaps): the NULL-key rows of the build and the probe side.
+int join_str(hmj_ctx* c, const hmj_str_rel* R, const hmj_str_rel* S, uint32_t flags, hmj_str_join_opts* opts, hmj_str_result* out,
+             const StrValid* VB = nullptr, const StrValid* VP = nullptr, u64* n_null = nullptr) {
+  u64 nb = R->n, np = S->n;
   const u32 bits = opts->hash_bits;
   if (flags & HMJ_ORDERED) flags |= HMJ_MATERIALIZE;
   const bool mat = flags & HMJ_MATERIALIZE, ordered = flags & HMJ_ORDERED, checksum = flags & HMJ_CHECKSUM;
@@ -669,13 +822,30 @@ int join_str(hmj_ctx* c, const hmj_str_rel* R, const hmj_str_rel* S, uint32_t fl
   // 1. {hash, row} rows of both relations (+ the probe payloads' sum)
   RC_TRY(record(c, 0));
   RC_TRY(acc_reset(c, acc));
-  RC_TRY(launch_hash(c, R->chars, (const u64*)R->offsets, nb, bits, (u64*)c->str_rows_r.p, true, nullptr, acc));
-  RC_TRY(launch_hash(c, S->chars, (const u64*)S->offsets, np, bits, (u64*)c->str_rows_s.p, true, (flags & HMJ_SUM_PROBE) ? (const u64*)S->vals : nullptr,
-                     acc + SA_N));
-  RC_TRY(record(c, 1));
+  const void* rows[2] = {c->str_rows_r.p, c->str_rows_s.p};  // the rows the u64 join takes
+  u64 nv[2] = {nb, np};                                       // ... and how many: the rows that have a key
+  if (!VB && !VP) {
+    RC_TRY(launch_hash(c, R->chars, (const u64*)R->offsets, nb, bits, (u64*)c->str_rows_r.p, true, nullptr, acc));
+    RC_TRY(launch_hash(c, S->chars, (const u64*)S->offsets, np, bits, (u64*)c->str_rows_s.p, true, (flags & HMJ_SUM_PROBE) ? (const u64*)S->vals : nullptr,
+                       acc + SA_N));
+    RC_TRY(record(c, 1));
+  } else {  // NULL keys: only the rows that have a key are joined (the inner join walks no relation by row: no dense rows)
+    const u64* tot[2];
+    RC_TRY(launch_hashes_valid(c, R, S, VB, VP, bits, false, flags & HMJ_SUM_PROBE, acc, rows, tot));
+    RC_TRY(record(c, 1));
+    for (int k = 0; k < 2; k++)
+      if (tot[k]) HIP_TRY(hipMemcpyAsync(&nv[k], tot[k], sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  }
   RC_TRY(read_back(c, acc, h, sizeof(h)));
   RC_TRY(hash_errors(c, h, "build"));
   RC_TRY(hash_errors(c, h + SA_N, "probe"));
+  if (nv[0] > nb || nv[1] > np) return fail(c, HMJ_E_HIP, "string join: more valid rows counted than the relation holds");
+  if (n_null) {
+    n_null[0] = nb - nv[0];
+    n_null[1] = np - nv[1];
+  }
+  nb = nv[0];  // from here on: the rows that have a key (every row in a call without bitmaps)
+  np = nv[1];
   if (flags & HMJ_SUM_PROBE) out->sum_probe_all = h[SA_N + SA_ACC + hmj::ACC_SUM_P];
   if (nb == 0 || np == 0) {  // (nothing to join: no plan either)
     std::memset(&c->plan, 0, sizeof(c->plan));
@@ -689,7 +859,7 @@ int join_str(hmj_ctx* c, const hmj_str_rel* R, const hmj_str_rel* S, uint32_t fl
   spans_reset(c);
   const int st = span_begin(c, K_TOTAL, -1);
   c->memo_kind = kStrJoinMemoKind;
-  int rc = join_device(c, c->str_rows_r.p, nb, c->str_rows_s.p, np, HMJ_MATERIALIZE | (flags & HMJ_ORDERED), &inner, false);
+  int rc = join_device(c, rows[0], nb, rows[1], np, HMJ_MATERIALIZE | (flags & HMJ_ORDERED), &inner, false);
   c->memo_kind = 0;
   span_end(c, st);
   if (c->profiling) {
@@ -797,7 +967,9 @@ int memo_join(hmj_ctx* c, const void* Rr, u64 nr, const void* Sr, u64 ns, uint32
 
 u64 blocks_of(u64 n) { return (n + SV_THREADS - 1) / SV_THREADS; }
 
-int join_str_kind(hmj_ctx* c, const hmj_str_rel* R, const hmj_str_rel* S, uint32_t flags, hmj_str_kind_opts* o, hmj_str_result* out) {
+// VB / VP: as join_str; o->n_build_null / n_probe_null are filled in a call with bitmaps.
+int join_str_kind(hmj_ctx* c, const hmj_str_rel* R, const hmj_str_rel* S, uint32_t flags, hmj_str_kind_opts* o, hmj_str_result* out,
+                  const StrValid* VB = nullptr, const StrValid* VP = nullptr) {
   const u64 nb = R->n, np = S->n;
   const u32 bits = o->hash_bits, kind = o->kind;
   if (flags & HMJ_ORDERED) flags |= HMJ_MATERIALIZE;
@@ -824,15 +996,31 @@ int join_str_kind(hmj_ctx* c, const hmj_str_rel* R, const hmj_str_rel* S, uint32
   HIP_TRY(hipMemsetAsync(acc, 0, kKindAccBlocks * SA_N * sizeof(u64), c->stream));
   HIP_TRY(hipMemsetAsync(acc + SA_BAD_ROW, 0xFF, sizeof(u64), c->stream));
   HIP_TRY(hipMemsetAsync(acc + SA_N + SA_BAD_ROW, 0xFF, sizeof(u64), c->stream));
-  RC_TRY(launch_hash(c, R->chars, (const u64*)R->offsets, nb, bits, (u64*)c->str_rows_r.p, true, nullptr, acc));
-  RC_TRY(launch_hash(c, S->chars, (const u64*)S->offsets, np, bits, (u64*)c->str_rows_s.p, true,
-                     (flags & HMJ_SUM_PROBE) ? (const u64*)S->vals : nullptr, acc + SA_N));
+  // (NULL keys: the dense rows stay indexed by row for the sweeps; the u64 joins take only the rows that have a key)
+  const void* rows[2] = {c->str_rows_r.p, c->str_rows_s.p};
+  u64 nv[2] = {nb, np};
+  if (!VB && !VP) {
+    RC_TRY(launch_hash(c, R->chars, (const u64*)R->offsets, nb, bits, (u64*)c->str_rows_r.p, true, nullptr, acc));
+    RC_TRY(launch_hash(c, S->chars, (const u64*)S->offsets, np, bits, (u64*)c->str_rows_s.p, true,
+                       (flags & HMJ_SUM_PROBE) ? (const u64*)S->vals : nullptr, acc + SA_N));
+  } else {
+    const u64* tot[2];
+    RC_TRY(launch_hashes_valid(c, R, S, VB, VP, bits, true, flags & HMJ_SUM_PROBE, acc, rows, tot));
+    for (int k = 0; k < 2; k++)
+      if (tot[k]) HIP_TRY(hipMemcpyAsync(&nv[k], tot[k], sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  }
   if (nb) HIP_TRY(hipMemsetAsync(c->str_mark_r.p, 0, nb, c->stream));
   if (np) HIP_TRY(hipMemsetAsync(c->str_mark_s.p, 0, np, c->stream));
   RC_TRY(record(c, 1));
   RC_TRY(read_back(c, acc, h, 2 * SA_N * sizeof(u64)));
   RC_TRY(hash_errors(c, h, "build"));
   RC_TRY(hash_errors(c, h + SA_N, "probe"));
+  const u64 nvb = nv[0], nvp = nv[1];  // the rows that have a key
+  if (nvb > nb || nvp > np) return fail(c, HMJ_E_HIP, "string join: more valid rows counted than the relation holds");
+  if (VB || VP) {
+    o->n_build_null = nb - nvb;
+    o->n_probe_null = np - nvp;
+  }
   if (flags & HMJ_SUM_PROBE) out->sum_probe_all = h[SA_N + SA_ACC + hmj::ACC_SUM_P];
   const StrSide RS{(const unsigned char*)R->chars, (const u64*)R->offsets, (const u64*)R->vals},
       SS{(const unsigned char*)S->chars, (const u64*)S->offsets, (const u64*)S->vals};
@@ -843,8 +1031,8 @@ int join_str_kind(hmj_ctx* c, const hmj_str_rel* R, const hmj_str_rel* S, uint32
   std::memset(&inner, 0, sizeof(inner));
   if (semi_anti) {
     // every row of the side asked about (K) meets the FIRST row of its hash on the other side (O), in row order
-    const u64 nK = bside ? nb : np, nO = bside ? np : nb;
-    const void *rowsK = bside ? c->str_rows_r.p : c->str_rows_s.p, *rowsO = bside ? c->str_rows_s.p : c->str_rows_r.p;
+    const u64 nK = bside ? nvb : nvp, nO = bside ? nvp : nvb;
+    const void *rowsK = bside ? rows[0] : rows[1], *rowsO = bside ? rows[1] : rows[0];
     const StrSide &KS = bside ? RS : SS, &OS = bside ? SS : RS;
     unsigned char* mark = bside ? mark_r : mark_s;
     if (nK && nO) {
@@ -874,8 +1062,8 @@ int join_str_kind(hmj_ctx* c, const hmj_str_rel* R, const hmj_str_rel* S, uint32
     } else {
       RC_TRY(record(c, 2));
     }
-  } else if (nb && np) {
-    RC_TRY(memo_join(c, c->str_rows_r.p, nb, c->str_rows_s.p, np, HMJ_MATERIALIZE | (flags & HMJ_ORDERED), kMemoPairs, &inner));
+  } else if (nvb && nvp) {
+    RC_TRY(memo_join(c, rows[0], nvb, rows[1], nvp, HMJ_MATERIALIZE | (flags & HMJ_ORDERED), kMemoPairs, &inner));
     RC_TRY(record(c, 2));
     n_pairs = inner.n_matches;
   } else {
@@ -886,7 +1074,16 @@ int join_str_kind(hmj_ctx* c, const hmj_str_rel* R, const hmj_str_rel* S, uint32
   // result rows: the verified pairs (outer kinds), then the probe sweep's rows, then the build sweep's
   const u64 nblk_v = semi_anti ? 0 : blocks_of(n_pairs);
   const u64 nblk_p = sweep_p ? blocks_of(np) : 0, nblk_b = sweep_b ? blocks_of(nb) : 0;
-  const u64 nblk = nblk_v + nblk_p + nblk_b;
+  // ordered, NULL keys: the sweeps above take the rows that have a key, and a second launch per relation puts its NULL-key
+  // rows (never marked: only the kinds that take unmarked rows emit them) into a tail behind everything that is sorted --
+  // the build side's in r_row order, then the probe side's in s_row order
+  const u32 want = kind == HMJ_JOIN_SEMI ? 1u : 0u;
+  const bool split_b = ordered && VB, split_p = ordered && VP;
+  const u64 nblk_tb = split_b && sweep_b && !want && nvb < nb ? blocks_of(nb) : 0;
+  const u64 nblk_tp = split_p && sweep_p && !want && nvp < np ? blocks_of(np) : 0;
+  const u64 nblk_m = nblk_v + nblk_p + nblk_b;  // workgroups of the rows that have a key
+  const u64 nblk = nblk_m + nblk_tb + nblk_tp;
+  if (nblk > 0xFFFFFFFFull) return fail(c, HMJ_E_UNSUPPORTED, "string join: more than 2^40 pairs of equal hash");
   const u64 cap = (semi_anti ? 0 : n_pairs) + (sweep_p ? np : 0) + (sweep_b ? nb : 0);
   DevBuf* cols[5] = {&c->str_hash, &c->str_rrow, &c->str_srow, &c->str_rval, &c->str_sval};
   if (mat) {
@@ -907,14 +1104,15 @@ int join_str_kind(hmj_ctx* c, const hmj_str_rel* R, const hmj_str_rel* S, uint32
   }
   RC_TRY(record(c, 3));
   // 4. the sweeps: SEMI / BUILD_SEMI take the marked rows, every other kind the unmarked ones
-  const u32 want = kind == HMJ_JOIN_SEMI ? 1u : 0u;
   const u64 pfill = !semi_anti && (!bside || kind == HMJ_FULL_OUTER) ? o->probe_fill : 0ull;
   const u64 bfill = !semi_anti && bside ? o->build_fill : 0ull;
-  const Sweep WP{(const u64*)c->str_rows_s.p, mark_s, SS.vals, np, pfill, want, 1u};
-  const Sweep WB{(const u64*)c->str_rows_r.p, mark_r, RS.vals, nb, bfill, want, 0u};
+  const Sweep WP{(const u64*)c->str_rows_s.p, mark_s, SS.vals, np, pfill, want, 1u, split_p ? 1u : 0u};
+  const Sweep WB{(const u64*)c->str_rows_r.p, mark_r, RS.vals, nb, bfill, want, 0u, split_b ? 1u : 0u};
+  Sweep TP = WP, TB = WB;  // the tails' sweeps
+  TP.nulls = TB.nulls = 2u;
   u64* acc_p = acc + 3 * SA_N;
   u64* acc_b = acc + 4 * SA_N;
-  u64 n_out = 0, n_in = 0;  // result rows; of those, verified pairs (materialising)
+  u64 n_out = 0, n_in = 0, n_main = 0;  // result rows; of those, verified pairs (materialising); rows in front of the NULL-key tail
   u64* oc[5] = {(u64*)c->str_hash.p, (u64*)c->str_rrow.p, (u64*)c->str_srow.p, (u64*)c->str_rval.p, (u64*)c->str_sval.p};
   if (semi_anti && !bside) oc[1] = oc[3] = nullptr;  // (hash, s_row, sval)
   if (semi_anti && bside) oc[2] = oc[4] = nullptr;   // (hash, r_row, rval)
@@ -925,6 +1123,11 @@ int join_str_kind(hmj_ctx* c, const hmj_str_rel* R, const hmj_str_rel* S, uint32
       hipLaunchKernelGGL(str_sweep_count_kernel<true>, dim3((u32)nblk_p), dim3(SV_THREADS), 0, c->stream, WP, blk + nblk_v, nullptr, 0);
     if (nblk_b)
       hipLaunchKernelGGL(str_sweep_count_kernel<true>, dim3((u32)nblk_b), dim3(SV_THREADS), 0, c->stream, WB, blk + nblk_v + nblk_p,
+                         nullptr, 0);
+    if (nblk_tb)
+      hipLaunchKernelGGL(str_sweep_count_kernel<true>, dim3((u32)nblk_tb), dim3(SV_THREADS), 0, c->stream, TB, blk + nblk_m, nullptr, 0);
+    if (nblk_tp)
+      hipLaunchKernelGGL(str_sweep_count_kernel<true>, dim3((u32)nblk_tp), dim3(SV_THREADS), 0, c->stream, TP, blk + nblk_m + nblk_tb,
                          nullptr, 0);
     HIP_TRY(hipGetLastError());
     if (nblk) HIP_TRY(hmj::launch_scan_u64(blk, (u64*)c->str_blk_off.p, (u32)nblk, c->stream));
@@ -938,10 +1141,19 @@ int join_str_kind(hmj_ctx* c, const hmj_str_rel* R, const hmj_str_rel* S, uint32
     if (nblk_b)
       hipLaunchKernelGGL(str_sweep_emit_kernel, dim3((u32)nblk_b), dim3(SV_THREADS), 0, c->stream, WB, blk_off + nblk_v + nblk_p,
                          oc[0], oc[1], oc[2], oc[3], oc[4], acc_b, checksum ? 1 : 0);
+    if (nblk_tb)
+      hipLaunchKernelGGL(str_sweep_emit_kernel, dim3((u32)nblk_tb), dim3(SV_THREADS), 0, c->stream, TB, blk_off + nblk_m, oc[0], oc[1],
+                         oc[2], oc[3], oc[4], acc_b, checksum ? 1 : 0);
+    if (nblk_tp)
+      hipLaunchKernelGGL(str_sweep_emit_kernel, dim3((u32)nblk_tp), dim3(SV_THREADS), 0, c->stream, TP, blk_off + nblk_m + nblk_tb,
+                         oc[0], oc[1], oc[2], oc[3], oc[4], acc_p, checksum ? 1 : 0);
     HIP_TRY(hipGetLastError());
     if (nblk) {
       HIP_TRY(hipMemcpyAsync(&n_in, blk_off + nblk_v, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+      if (nblk > nblk_m) HIP_TRY(hipMemcpyAsync(&n_main, blk_off + nblk_m, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
       RC_TRY(read_back(c, blk_off + nblk, &n_out, sizeof(u64)));
+      if (nblk == nblk_m) n_main = n_out;  // (no tail)
+      if (n_main > n_out || n_out > cap) return fail(c, HMJ_E_HIP, "string join: the sweeps' offsets exceed the result's capacity");
     }
   } else {
     if (nblk_p)
@@ -955,15 +1167,16 @@ int join_str_kind(hmj_ctx* c, const hmj_str_rel* R, const hmj_str_rel* S, uint32
   RC_TRY(record(c, 4));
   // 5. ordered: a stable sort of (hash, index) rows, the columns gathered in that order, then runs of equal hash with
   // several keys sorted by key bytes.  (Outer kinds without unmatched rows are already in (hash, r_row, s_row) order.)
-  if (ordered && n_out > 1) {
-    if (n_out > n_in) {
-      RC_TRY(ensure_dev(c, c->str_ord, 32 * n_out));
+  // NULL keys: only the n_main rows in front of the tail are sorted; the tail is already in its order and is copied behind.
+  if (ordered && n_main > 1) {
+    if (n_main > n_in) {
+      RC_TRY(ensure_dev(c, c->str_ord, 32 * n_main));
       u64* ord = (u64*)c->str_ord.p;
-      hipLaunchKernelGGL(str_sort_rows_kernel, dim3((u32)blocks_of(n_out)), dim3(SV_THREADS), 0, c->stream, oc[0], n_out, ord);
+      hipLaunchKernelGGL(str_sort_rows_kernel, dim3((u32)blocks_of(n_main)), dim3(SV_THREADS), 0, c->stream, oc[0], n_main, ord);
       HIP_TRY(hipGetLastError());
       const hmj_plan_desc plan = c->plan;  // (the sort is not a join: hmj_last_plan / hmj_last_timing keep describing the last one)
       const hmj_timing timing = c->timing;
-      const int rc = hmj_sort_u64_device(c, ord, n_out, ord + 2 * n_out);
+      const int rc = hmj_sort_u64_device(c, ord, n_main, ord + 2 * n_main);
       c->plan = plan;
       c->timing = timing;
       if (rc != HMJ_OK) return rc;
@@ -975,20 +1188,24 @@ int join_str_kind(hmj_ctx* c, const hmj_str_rel* R, const hmj_str_rel* S, uint32
         RC_TRY(ensure_dev(c, *kc[k], n_out * sizeof(u64)));
         nc[k] = (u64*)kc[k]->p;
       }
-      hipLaunchKernelGGL(str_gather_kernel, dim3((u32)blocks_of(n_out)), dim3(SV_THREADS), 0, c->stream, (const u64*)(ord + 2 * n_out),
-                         n_out, oc[1], oc[2], oc[3], oc[4], nc[0], nc[1], nc[2], nc[3], nc[4]);
+      hipLaunchKernelGGL(str_gather_kernel, dim3((u32)blocks_of(n_main)), dim3(SV_THREADS), 0, c->stream, (const u64*)(ord + 2 * n_main),
+                         n_main, oc[1], oc[2], oc[3], oc[4], nc[0], nc[1], nc[2], nc[3], nc[4]);
       HIP_TRY(hipGetLastError());
-      for (int k = 0; k < 5; k++) oc[k] = nc[k];
+      for (int k = 0; k < 5; k++) {
+        if (nc[k] && n_out > n_main)
+          HIP_TRY(hipMemcpyAsync(nc[k] + n_main, oc[k] + n_main, (n_out - n_main) * sizeof(u64), hipMemcpyDeviceToDevice, c->stream));
+        oc[k] = nc[k];
+      }
     }
-    const u64 lcap = n_out < kListCap ? n_out : kListCap;
+    const u64 lcap = n_main < kListCap ? n_main : kListCap;
     RC_TRY(ensure_dev(c, c->str_list, lcap * sizeof(u64)));
     RC_TRY(ensure_dev(c, c->str_runs, 2 * lcap * sizeof(u64)));
-    hipLaunchKernelGGL(str_mismatch_kernel<true>, dim3((u32)blocks_of(n_out - 1)), dim3(SV_THREADS), 0, c->stream, (const u64*)oc[0],
-                       (const u64*)oc[1], n_out, RS, (u64*)c->str_list.p, acc_v, (const u64*)oc[2], SS);
+    hipLaunchKernelGGL(str_mismatch_kernel<true>, dim3((u32)blocks_of(n_main - 1)), dim3(SV_THREADS), 0, c->stream, (const u64*)oc[0],
+                       (const u64*)oc[1], n_main, RS, (u64*)c->str_list.p, acc_v, (const u64*)oc[2], SS);
     HIP_TRY(hipGetLastError());
     const u64 gl = blocks_of(lcap);
     hipLaunchKernelGGL(str_run_leader_kernel<true>, dim3((u32)(gl < 1024 ? gl : 1024)), dim3(SV_THREADS), 0, c->stream,
-                       (const u64*)oc[0], (const u64*)oc[1], n_out, RS, (const u64*)c->str_list.p, (u64*)c->str_runs.p, acc_v,
+                       (const u64*)oc[0], (const u64*)oc[1], n_main, RS, (const u64*)c->str_list.p, (u64*)c->str_runs.p, acc_v,
                        (const u64*)oc[2], SS);
     HIP_TRY(hipGetLastError());
     const u64 gs = lcap < (u64)(4 * c->num_cus) ? lcap : (u64)(4 * c->num_cus);
@@ -1034,6 +1251,39 @@ int join_str_kind(hmj_ctx* c, const hmj_str_rel* R, const hmj_str_rel* S, uint32
     }
   }
   return HMJ_OK;
+}
+
+// The validity bitmaps of a hmj_str_kind_opts whose struct_size covers them, as the kernels take them; *pb / *pp stay NULL
+// for a relation without a bitmap (bits == NULL).
+int opts_validity(hmj_ctx* c, const hmj_str_kind_opts* opts, const hmj_str_rel* build, const hmj_str_rel* probe, StrValid* VB, StrValid* VP,
+                  const StrValid** pb, const StrValid** pp) {
+  *pb = *pp = nullptr;
+  if (opts->struct_size < offsetof(hmj_str_kind_opts, probe_validity) + sizeof(opts->probe_validity)) return HMJ_OK;
+  const hmj_validity* v[2] = {&opts->build_validity, &opts->probe_validity};
+  const hmj_str_rel* rel[2] = {build, probe};
+  StrValid* V[2] = {VB, VP};
+  const StrValid** pv[2] = {pb, pp};
+  for (int k = 0; k < 2; k++) {
+    if (!v[k]->bits) continue;
+    if (v[k]->bit_offset > UINT64_MAX - rel[k]->n) {
+      char msg[128];
+      std::snprintf(msg, sizeof(msg), "%s relation: validity bit_offset + n overflows 64 bits", k ? "probe" : "build");
+      return fail(c, HMJ_E_ARG, msg);
+    }
+    V[k]->bits = (const unsigned char*)v[k]->bits;
+    V[k]->off = v[k]->bit_offset;
+    *pv[k] = V[k];
+  }
+  return HMJ_OK;
+}
+// The out fields of a full-size copy o of the caller's opts are cleared from `counts` on; the in fields that lie behind them
+// (the validity bitmaps) are the caller's again, as far as its struct_size holds them.
+void clear_out_fields(hmj_str_kind_opts* o, const hmj_str_kind_opts* opts) {
+  using T = hmj_str_kind_opts;
+  std::memset(&o->counts, 0, sizeof(T) - offsetof(T, counts));
+  const size_t lo = offsetof(T, build_validity), hi = offsetof(T, n_build_null);
+  const size_t have = opts->struct_size < hi ? opts->struct_size : hi;
+  if (have > lo) std::memcpy((char*)o + lo, (const char*)opts + lo, have - lo);
 }
 
 }  // namespace
@@ -1101,19 +1351,25 @@ int hmj_join_kind_str_device(hmj_ctx* c, const hmj_str_rel* build, const hmj_str
   if (flags & HMJ_FIRST_WINS) return fail(c, HMJ_E_ARG, "HMJ_FIRST_WINS is not defined for string joins");
   RC_TRY(check_str_rel(c, build, "build"));
   RC_TRY(check_str_rel(c, probe, "probe"));
+  StrValid VB, VP;
+  const StrValid *vb, *vp;
+  RC_TRY(opts_validity(c, opts, build, probe, &VB, &VP, &vb, &vp));
   std::memset(out, 0, sizeof(*out));
   HIP_TRY(hipSetDevice(c->device));
   // the out fields of opts go to a full-size copy first; the caller gets the prefix its struct_size holds
   hmj_str_kind_opts o;
   std::memset(&o, 0, sizeof(o));
   std::memcpy(&o, opts, opts->struct_size < sizeof(o) ? opts->struct_size : sizeof(o));
-  std::memset(&o.counts, 0, sizeof(o) - offsetof(hmj_str_kind_opts, counts));
+  clear_out_fields(&o, opts);
   if (o.side == HMJ_KIND_PROBE_SIDE && o.kind == HMJ_JOIN_INNER) {  // exactly the inner string join
     hmj_str_join_opts jo;
     std::memset(&jo, 0, sizeof(jo));
     jo.struct_size = sizeof(jo);
     jo.hash_bits = o.hash_bits;
-    RC_TRY(join_str(c, build, probe, flags, &jo, out));
+    u64 n_null[2] = {0, 0};
+    RC_TRY(join_str(c, build, probe, flags, &jo, out, vb, vp, n_null));
+    o.n_build_null = n_null[0];
+    o.n_probe_null = n_null[1];
     o.n_hash_pairs = jo.n_hash_pairs;
     o.n_collisions = jo.n_collisions;
     if (c->profiling) {
@@ -1124,7 +1380,7 @@ int hmj_join_kind_str_device(hmj_ctx* c, const hmj_str_rel* build, const hmj_str
       o.ms_order = elapsed(c, 3, 4);
     }
   } else {
-    RC_TRY(join_str_kind(c, build, probe, flags, &o, out));
+    RC_TRY(join_str_kind(c, build, probe, flags, &o, out, vb, vp));
     if (c->profiling) {
       (void)hipStreamSynchronize(c->stream);
       o.ms_hash = elapsed(c, 0, 1);

@@ -228,11 +228,38 @@ class Executor:
                                                int(hash_bits), C.c_void_p(out.data_ptr()) if n > 0 else None))
         return out
 
-    def join_str_device(self, build, probe, flags=0, hash_bits=0):
+    def _str_validity(self, valid, n, name, dst):
+        """A string relation's validity bitmap -> the Validity `dst` embedded in hmj_str_kind_opts; returns what must stay
+        alive for the call.  valid: None (no bitmap on this side), a uint8 device tensor (an Arrow bitmap, LSB first), or
+        (tensor, bit_offset)."""
+        if valid is None:
+            return None
+        t, off = valid if isinstance(valid, tuple) else (valid, 0)
+        off = int(off)
+        if not t.is_cuda or not t.is_contiguous() or t.dim() != 1 or t.element_size() != 1:
+            raise ValueError("%s must be a contiguous 1-D uint8 device tensor" % name)
+        if off < 0:
+            raise ValueError("%s: bit_offset must not be negative" % name)
+        if t.shape[0] and off + n < (1 << 64) and t.shape[0] * 8 < off + n:  # (an overflowing offset is the library's to reject)
+            raise ValueError("%s holds fewer than bit_offset + n bits" % name)
+        # (an empty tensor: bits == NULL, no NULL on this side; n == 0: the pointer is still passed, nothing reads it)
+        dst.bits = t.data_ptr() if t.shape[0] else None
+        dst.bit_offset = off & 0xFFFFFFFFFFFFFFFF
+        return t
+
+    def join_str_device(self, build, probe, flags=0, hash_bits=0, build_valid=None, probe_valid=None):
         """Inner join of two string-keyed device relations (hmj_join_str_device).  build / probe: (chars uint8, offsets
         int64 [n + 1], vals int64 [n]) device tensors -- the Arrow large_string layout plus payloads (`pack_strings`).
-        Returns (StrResult, {"n_hash_pairs", "n_collisions", "ms_hash", "ms_join", "ms_verify", "ms_order"}); read the
-        rows with `str_rows_to_numpy`."""
+        *_valid: None, a uint8 device tensor holding the key column's Arrow validity bitmap (`pack_validity`), or (tensor,
+        bit_offset); a row whose key is NULL matches nothing, and a valid empty string is not NULL.  hmj_str_join_opts
+        carries no bitmap, so a call with *_valid runs the INNER kind of hmj_join_kind_str_device, which is the same join.
+        Returns (StrResult, {"n_hash_pairs", "n_collisions", "n_build_null", "n_probe_null", "ms_hash", "ms_join",
+        "ms_verify", "ms_order"}); read the rows with `str_rows_to_numpy`."""
+        if build_valid is not None or probe_valid is not None:
+            res, info = self.join_kind_str_device(build, probe, _lib.HMJ_KIND_PROBE_SIDE, _lib.HMJ_JOIN_INNER, flags, hash_bits,
+                                                  build_valid=build_valid, probe_valid=probe_valid)
+            keys = ("n_hash_pairs", "n_collisions", "n_build_null", "n_probe_null", "ms_hash", "ms_join", "ms_verify", "ms_order")
+            return res, {k: info[k] for k in keys}
         self._sync_stream()
         rb, rp = self._str_rel(build), self._str_rel(probe)
         opts = _lib.StrJoinOpts()
@@ -240,7 +267,7 @@ class Executor:
         opts.hash_bits = int(hash_bits)
         res = _lib.StrResult()
         self._check(self.L.hmj_join_str_device(self.h, C.byref(rb), C.byref(rp), flags, C.byref(opts), C.byref(res)))
-        info = {"n_hash_pairs": int(opts.n_hash_pairs), "n_collisions": int(opts.n_collisions)}
+        info = {"n_hash_pairs": int(opts.n_hash_pairs), "n_collisions": int(opts.n_collisions), "n_build_null": 0, "n_probe_null": 0}
         for k in ("ms_hash", "ms_join", "ms_verify", "ms_order"):
             info[k] = float(getattr(opts, k))
         return res, info
@@ -594,12 +621,14 @@ class Executor:
         self._check(self.L.hmj_gen_uniform_domain_u64_device(self.h, C.c_void_p(t.data_ptr()), n, start, domain, seed, zseed))
         return t
 
-    def join_kind_str_device(self, build, probe, side, kind, flags=0, hash_bits=0, probe_fill=0, build_fill=0):
+    def join_kind_str_device(self, build, probe, side, kind, flags=0, hash_bits=0, probe_fill=0, build_fill=0, build_valid=None,
+                             probe_valid=None):
         """Semi / anti / outer joins of two string-keyed device relations (hmj_join_kind_str_device).  side / kind as for
         hmj_exchange_kind_opts: HMJ_KIND_PROBE_SIDE with HMJ_JOIN_*, or HMJ_KIND_BUILD_SIDE with HMJ_BUILD_* / HMJ_FULL_OUTER;
-        build / probe as for `join_str_device`.  Returns (StrResult, {"n_probe_matched", "n_probe_unmatched",
-        "n_build_matched", "n_build_unmatched", "n_hash_pairs", "n_collisions", "ms_hash", "ms_join", "ms_verify",
-        "ms_emit", "ms_order"}); read the rows with `str_kind_rows_to_numpy`."""
+        build / probe and *_valid as for `join_str_device` (a NULL-key row has no partner: ANTI and the outer kinds of its
+        side emit it with hash 0).  Returns (StrResult, {"n_probe_matched", "n_probe_unmatched", "n_build_matched",
+        "n_build_unmatched", "n_hash_pairs", "n_collisions", "n_build_null", "n_probe_null", "ms_hash", "ms_join",
+        "ms_verify", "ms_emit", "ms_order"}); read the rows with `str_kind_rows_to_numpy`."""
         self._sync_stream()
         rb, rp = self._str_rel(build), self._str_rel(probe)
         opts = _lib.StrKindOpts()
@@ -609,11 +638,16 @@ class Executor:
         opts.hash_bits = int(hash_bits)
         opts.probe_fill = int(probe_fill) & 0xFFFFFFFFFFFFFFFF
         opts.build_fill = int(build_fill) & 0xFFFFFFFFFFFFFFFF
+        keep = (self._str_validity(build_valid, int(rb.n), "build_valid", opts.build_validity),
+                self._str_validity(probe_valid, int(rp.n), "probe_valid", opts.probe_validity))
         res = _lib.StrResult()
         self._check(self.L.hmj_join_kind_str_device(self.h, C.byref(rb), C.byref(rp), flags, C.byref(opts), C.byref(res)))
+        del keep
         info = opts.counts.as_dict()
         info["n_hash_pairs"] = int(opts.n_hash_pairs)
         info["n_collisions"] = int(opts.n_collisions)
+        info["n_build_null"] = int(opts.n_build_null)
+        info["n_probe_null"] = int(opts.n_probe_null)
         for k in ("ms_hash", "ms_join", "ms_verify", "ms_emit", "ms_order"):
             info[k] = float(getattr(opts, k))
         return res, info

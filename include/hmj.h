@@ -491,8 +491,9 @@ typedef struct {
  * with 64-bit hashes that takes a genuine _Hash_bytes collision.
  * hmj_last_plan / hmj_last_timing describe the inner {hash,row} join.  Its workload memo is keyed apart from plain u64
  * joins (as the kinds' are), so string joins do not change what u64 joins learn.  Like any other call it discards a
- * prepared build side.  Join kinds: hmj_join_kind_str_device below.  Out of scope: the exchange (multi-GPU) path and
- * host-resident string relations.                                                                                       */
+ * prepared build side.  Join kinds: hmj_join_kind_str_device below.  NULL keys: hmj_str_join_opts carries no validity
+ * bitmap, so this entry joins keys without NULLs; the inner join of nullable keys is the INNER kind of
+ * hmj_join_kind_str_device.  Out of scope: the exchange (multi-GPU) path and host-resident string relations.            */
 int hmj_join_str_device(hmj_ctx* ctx, const hmj_str_rel* build, const hmj_str_rel* probe, uint32_t flags,
                         hmj_str_join_opts* opts, hmj_str_result* out);
 
@@ -524,8 +525,54 @@ int hmj_join_str_device(hmj_ctx* ctx, const hmj_str_rel* build, const hmj_str_re
  * HMJ_E_ARG: NULL ctx / rel / opts / out, opts->struct_size too small, an unknown side or kind, HMJ_FIRST_WINS, and
  * everything hmj_join_str_device rejects (decreasing offsets included; the ctx stays usable).  HMJ_E_UNSUPPORTED wherever
  * the ordered string join returns it.  hmj_last_plan / hmj_last_timing describe the last internal u64 join; the kinds'
- * workloads are keyed apart from u64 joins, u64 kind joins and the inner string join.                                  */
+ * workloads are keyed apart from u64 joins, u64 kind joins and the inner string join.
+ * NULL keys (Arrow validity bitmaps, hmj_validity below): opts->build_validity / probe_validity give the key column's
+ * bitmap of that side, embedded by value (bits == NULL: no NULL on that side; a bitmap on one side only is valid; a call
+ * whose two bits are NULL launches exactly the kernels of a call that cannot pass one).  The fields are read and written
+ * only when struct_size covers them: a caller built against the header without them -- struct_size up to the offset of
+ * build_validity -- gets that header's behaviour bit for bit, whatever bytes lie behind.  hmj_str_join_opts keeps its
+ * layout and carries no bitmap: the inner join of nullable string keys is this entry with HMJ_KIND_PROBE_SIDE +
+ * HMJ_JOIN_INNER (the same rows, sums, order, n_hash_pairs and n_collisions over the rows that have a key).  SQL's
+ * three-valued equality: a NULL-key row matches nothing -- no row of the other side and no other NULL-key row --, so it
+ * has no partner, and every kind follows with NOT EXISTS semantics (not NOT IN):
+ *   kind          NULL-key probe row                                      NULL-key build row
+ *   INNER         not in the result                                       not in the result
+ *   probe SEMI    not emitted                                             -
+ *   probe ANTI    emitted                                                 -
+ *   PROBE_OUTER   unmatched: (0, NO_ROW, s_row, probe_fill, sval)         not in the result
+ *   BUILD_SEMI    -                                                       not emitted
+ *   BUILD_ANTI    -                                                       emitted
+ *   BUILD_OUTER   not in the result                                       unmatched: (0, r_row, NO_ROW, rval, build_fill)
+ *   FULL_OUTER    emitted as unmatched                                    emitted as unmatched
+ * hash of a NULL-key row is 0 wherever such a row is emitted; the sums and HMJ_CHECKSUM use that 0.  A valid empty string
+ * is a key like any other: it matches other valid empty strings and no NULL slot, even one of length zero.  The bytes and
+ * the length under a NULL slot are undefined and nothing in the result depends on them -- but the offsets of a NULL slot
+ * must still be non-decreasing (Arrow requires it, and the hash kernel stages a wave's whole byte span): a decrease
+ * anywhere stays HMJ_E_ARG naming the row, and the ctx stays usable.  chars == NULL stays legal when every slot, valid or
+ * NULL, has length 0.  counts: n_*_unmatched includes the NULL-key rows of that side, so SEMI + ANTI still partition the
+ * relation; n_build_null / n_probe_null are filled by every kind and are 0 without bitmaps.  n_hash_pairs /
+ * n_collisions: NULL-key rows are never paired and count in neither.  HMJ_SUM_PROBE sums every probe row's payload,
+ * NULL-key rows included.
+ * HMJ_ORDERED: NULL-key rows come after every non-NULL row, among themselves ascending by (r_row, s_row) with
+ * HMJ_STR_NO_ROW last -- in a FULL_OUTER result the build side's NULL-key rows by r_row, then the probe side's by s_row --;
+ * non-NULL rows keep the order above exactly.  NULL-key rows never enter the hash sort or the collision-run sort (the
+ * sweeps emit them into a tail segment of their own), so the 1024-row and 2^22 limits count non-NULL rows only.
+ * A side whose rows are all NULL-key behaves as an empty side for matching; its rows are still emitted by the kinds that
+ * emit unmatched rows of that side.  HMJ_E_ARG also: bit_offset + n overflows 64 bits.
+ * How: a pass over the bitmap alone counts the valid rows per 256-row workgroup (str_valid_count_kernel), one scan places
+ * the workgroups, and str_hash_valid_kernel -- str_hash_kernel with the wave's LDS staging and its unstaged path -- writes
+ * the {hash, row} rows of the valid rows only, compacted stably in row order (the u64 joins take those), and for the kinds
+ * a dense row-indexed array with {0, HMJ_STR_NO_ROW} for a NULL-key row, which the sweeps walk.  Row indices in the result
+ * stay the caller's.
+ * Out of scope for NULL keys: NULL-equals-NULL matching (IS NOT DISTINCT FROM), validity of the payload column,
+ * 32-bit-offset Arrow `string` columns, the exchange path, bitmaps on hmj_join_str_device itself (use the INNER kind).  */
 #define HMJ_STR_NO_ROW UINT64_MAX /* r_row / s_row of an outer join's unmatched row: there is no partner             */
+typedef struct {
+  const void* bits;     /* device: Arrow validity bitmap, least-significant bit first: row i is valid iff
+                           (bits[(bit_offset + i) >> 3] >> ((bit_offset + i) & 7)) & 1.  NULL: no NULL in this column.
+                           Byte-aligned only; never written                                                  */
+  uint64_t bit_offset;  /* Arrow slice offset, any value with bit_offset + n not overflowing                */
+} hmj_validity;
 typedef struct {
   uint32_t struct_size;   /* in: sizeof(hmj_str_kind_opts) of the caller's header                                       */
   uint32_t side;          /* in: HMJ_KIND_PROBE_SIDE / HMJ_KIND_BUILD_SIDE                                             */
@@ -537,6 +584,10 @@ typedef struct {
   uint64_t n_hash_pairs;  /* out: pairs of equal hash whose keys were compared                                         */
   uint64_t n_collisions;  /* out: of those, pairs whose keys differ                                                    */
   float ms_hash, ms_join, ms_verify, ms_emit, ms_order; /* out, with hmj_set_profiling(ctx, 1): HIP-event phase times  */
+  /* NULL keys (above).  Read / written only when struct_size covers them; a shorter struct is a call without bitmaps */
+  hmj_validity build_validity;   /* in: the build key column's bitmap; bits == NULL: no NULL on this side */
+  hmj_validity probe_validity;   /* in: likewise                                                          */
+  uint64_t n_build_null, n_probe_null; /* out: NULL-key rows per side (0 without bitmaps); every kind, INNER included */
 } hmj_str_kind_opts;
 int hmj_join_kind_str_device(hmj_ctx* ctx, const hmj_str_rel* build, const hmj_str_rel* probe, uint32_t flags,
                              hmj_str_kind_opts* opts, hmj_str_result* out);
@@ -562,12 +613,6 @@ typedef struct {
 } hmj_cols_rel;
 #define HMJ_COLS_PACKED 1u
 #define HMJ_COLS_HASHED 2u
-typedef struct {
-  const void* bits;     /* device: Arrow validity bitmap, least-significant bit first: row i is valid iff
-                           (bits[(bit_offset + i) >> 3] >> ((bit_offset + i) & 7)) & 1.  NULL: no NULL in this column.
-                           Byte-aligned only; never written                                                  */
-  uint64_t bit_offset;  /* Arrow slice offset, any value with bit_offset + n not overflowing                */
-} hmj_validity;
 typedef struct {
   uint32_t struct_size;     /* in: sizeof of the caller's header (size-versioned like hmj_str_join_opts)               */
   uint32_t hash_bits;       /* in: hashed form only; 0 = 64, 1..63 = h >> (64 - hash_bits): fewer bits make collisions  */
@@ -621,7 +666,7 @@ typedef struct {
  * other entry's, so multi-column joins do not change what u64 or string joins learn.  Like any other call it discards a
  * prepared build side.  Join kinds: hmj_join_kind_cols_device below.  Out of scope: the exchange (multi-GPU) path,
  * host-resident columns, returning the key columns, signed / collated ordering.
- * NULL keys (Arrow validity bitmaps, hmj_validity above): hmj_cols_join_opts keeps its layout and carries none, so this
+ * NULL keys (Arrow validity bitmaps, hmj_validity above, in the string section): hmj_cols_join_opts keeps its layout and carries none, so this
  * entry joins columns without NULLs.  The inner join of nullable key columns is hmj_join_kind_cols_device below with
  * HMJ_KIND_PROBE_SIDE + HMJ_JOIN_INNER, whose opts carry one hmj_validity per key column and side: the same rows, sums,
  * order, n_key_pairs and n_collisions over the rows that have a key.                                                     */
@@ -694,8 +739,9 @@ int hmj_join_cols_device(hmj_ctx* ctx, const hmj_cols_rel* build, const hmj_cols
  * How: a pass over the bitmaps alone counts the valid rows per workgroup (cols_valid_count_kernel), one scan places the
  * workgroups, and cols_key_valid_kernel writes the {key64,row} rows of the valid rows only, compacted stably in row order;
  * the u64 joins take those.  Row indices in the result stay the caller's.
- * Out of scope for NULL keys: NULL-equals-NULL matching (IS NOT DISTINCT FROM), validity of the payload column, string
- * keys' validity (hmj_join_str_device), the exchange path, bitmaps in hmj_cols_join_opts (use the INNER kind here).        */
+ * Out of scope for NULL keys: NULL-equals-NULL matching (IS NOT DISTINCT FROM), validity of the payload column, the
+ * exchange path, bitmaps in hmj_cols_join_opts (use the INNER kind here).  String keys' validity is not part of this entry:
+ * hmj_join_kind_str_device takes it, with these semantics.                                                              */
 #define HMJ_COLS_NO_ROW UINT64_MAX /* r_row / s_row of an outer join's unmatched row: there is no partner            */
 typedef struct {
   uint32_t struct_size;   /* in: sizeof(hmj_cols_kind_opts) of the caller's header                                     */
