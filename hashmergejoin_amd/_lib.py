@@ -183,6 +183,28 @@ class ColsResult(C.Structure):
         return {k: int(getattr(self, k)) for k in ("n_matches", "sum_r", "sum_s", "xor_fold", "mix_sum")}
 
 
+# hmj_take_cols_device: fixed-width columns taken through a row map (a join's r_row / s_row)
+HMJ_TAKE_NO_ROW = 0xFFFFFFFFFFFFFFFF
+HMJ_MAX_TAKE_COLS = 64
+
+
+class TakeSrc(C.Structure):
+    """hmj_take_src: one source column on the device -- n_src values of `width` bytes (1, 2, 4, 8 or 16), aligned to `width`,
+    and its validity bitmap (bits NULL: no NULL in the column)."""
+    _fields_ = [("data", C.c_void_p), ("width", C.c_uint32), ("reserved", C.c_uint32), ("validity", Validity)]
+
+
+class TakeDst(C.Structure):
+    """hmj_take_dst: one caller-owned output column -- n_out values, an optional bitmap of ceil(n_out / 64) 64-bit words (in);
+    its NULL slots (out)."""
+    _fields_ = [("data", C.c_void_p), ("validity", C.c_void_p), ("null_count", C.c_uint64)]
+
+
+class TakeOpts(C.Structure):
+    """hmj_take_opts: the map entries equal to HMJ_TAKE_NO_ROW and the kernel time (out)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("n_no_row", C.c_uint64), ("ms_take", C.c_float)]
+
+
 class Timing(C.Structure):
     _fields_ = [("ms_total", C.c_float), ("ms_h2d", C.c_float), ("ms_d2h", C.c_float),
                 ("ms_partition_build", C.c_float), ("ms_partition_probe", C.c_float),
@@ -337,6 +359,8 @@ def load_library():
     L.hmj_join_kind_cols_device.restype = i
     L.hmj_join_kind_cols_device.argtypes = [vp, C.POINTER(ColsRel), C.POINTER(ColsRel), C.c_uint32, C.POINTER(ColsKindOpts),
                                             C.POINTER(ColsResult)]
+    L.hmj_take_cols_device.restype = i
+    L.hmj_take_cols_device.argtypes = [vp, C.POINTER(TakeSrc), C.c_uint32, u, vp, u, C.POINTER(TakeDst), C.POINTER(TakeOpts)]
     L.hmj_prepare_build_u64_device.restype = i
     L.hmj_prepare_build_u64_device.argtypes = [vp, vp, u, u]
     L.hmj_join_u64.restype = i

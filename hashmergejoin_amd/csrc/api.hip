@@ -3213,7 +3213,7 @@ void hmj_destroy(hmj_ctx* c) {
                     &c->col_rows_r, &c->col_rows_s, &c->col_flags, &c->col_blk, &c->col_blk_off, &c->col_key, &c->col_rrow, &c->col_srow,
                     &c->col_rval, &c->col_sval, &c->col_list, &c->col_runs, &c->col_acc, &c->col_mark_r, &c->col_mark_s, &c->col_amb,
                     &c->col_ord, &c->col_kkey, &c->col_krrow, &c->col_ksrow, &c->col_krval, &c->col_ksval, &c->col_cmp_r,
-                    &c->col_cmp_s, &c->col_vblk, &c->str_cmp_r, &c->str_cmp_s, &c->str_vblk};
+                    &c->col_cmp_s, &c->col_vblk, &c->str_cmp_r, &c->str_cmp_s, &c->str_vblk, &c->take_acc};
   for (DevBuf* b : devs) free_dev(*b);
   HostBuf* hosts[] = {&c->h_accum, &c->h_key, &c->h_rval, &c->h_sval};
   for (HostBuf* b : hosts) free_host(*b);
@@ -3225,6 +3225,8 @@ void hmj_destroy(hmj_ctx* c) {
   for (auto& e : c->str_ev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : c->col_ev)
+    if (e) (void)hipEventDestroy(e);
+  for (auto& e : c->take_ev)
     if (e) (void)hipEventDestroy(e);
   for (auto& st : c->up_streams) (void)hipStreamDestroy(st);
   for (auto& e : c->copy_ev) (void)hipEventDestroy(e);

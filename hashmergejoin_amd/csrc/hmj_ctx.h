@@ -126,9 +126,12 @@ struct hmj_ctx {
       // (compacted, in row order), the valid rows per workgroup of both relations and their offsets
       col_cmp_r, col_cmp_s, col_vblk,
       // string joins with validity bitmaps only: likewise ({hash, row} rows of the non-NULL rows, counts and offsets)
-      str_cmp_r, str_cmp_s, str_vblk;
+      str_cmp_r, str_cmp_s, str_vblk,
+      // hmj_take_cols_device (take.hip): its counters -- the only workspace the call owns
+      take_acc;
   hipEvent_t str_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // string joins' phase boundaries (profiling)
   hipEvent_t col_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // multi-column joins' phase boundaries (profiling)
+  hipEvent_t take_ev[2] = {nullptr, nullptr};  // hmj_take_cols_device: around its launches (profiling)
   int memo_kind = 0;  // workload-signature kind of plain inner joins run on behalf of another entry (string, multi-column joins and their kinds)
   HostBuf h_accum, h_key, h_rval, h_sval;
   int host_threads = 0;  // staging threads for pageable input (0 = default)

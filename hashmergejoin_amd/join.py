@@ -441,6 +441,78 @@ class Executor:
             out[:, c] = tmp.cpu().numpy().view(np.uint64)
         return out
 
+    # ---- columns through a row map (hmj_take_cols_device) ------------------------------------------------
+    def take_cols_device(self, cols, row_map, valid=None, n_out=None, want_validity=True):
+        """Take fixed-width columns of one relation through a row map (hmj_take_cols_device): output row i is source row
+        row_map[i], or NULL where row_map[i] is HMJ_TAKE_NO_ROW or the source slot is NULL (the bytes of a NULL slot are 0).
+        cols: 1-D contiguous device tensors of one length whose element_size() is 1, 2, 4 or 8, or a contiguous [n,2]
+        int64 tensor for a 16-byte column.  valid: None, or one entry per column as `join_cols_device` takes them: None, a
+        uint8 bitmap tensor, or (tensor, bit_offset).  row_map: a contiguous 1-D int64 device tensor, or (device_pointer, n)
+        -- a result's r_row / s_row with its n_matches; the result stays as it is.  n_out: rows to take (default: the whole
+        map).  want_validity: True, False, or one bool per column.  The outputs are new tensors on the executor's device.
+        Returns (tensors of the sources' dtypes and shapes, int64 tensors of ceil(n_out / 64) bitmap words -- None for a
+        column without one, None instead of the list with want_validity=False --, {"null_count": [...], "n_no_row",
+        "ms_take"}); `unpack_validity` reads the words."""
+        torch = self._torch
+        self._sync_stream()
+        cols = list(cols)
+        if isinstance(row_map, tuple):
+            map_ptr, map_n = int(row_map[0] or 0), int(row_map[1])
+        else:
+            if not row_map.is_cuda or not row_map.is_contiguous() or row_map.dim() != 1 or row_map.dtype != torch.int64:
+                raise ValueError("row_map must be a contiguous 1-D int64 device tensor")
+            map_ptr, map_n = (row_map.data_ptr() if row_map.shape[0] else 0), row_map.shape[0]
+        n_out = map_n if n_out is None else int(n_out)
+        if not 0 <= n_out <= map_n:
+            raise ValueError("n_out must be in 0..len(row_map)")
+        widths = []
+        for k, t in enumerate(cols):
+            wide = t.dim() == 2 and t.shape[1] == 2 and t.element_size() == 8
+            if not t.is_cuda or not t.is_contiguous() or not (t.dim() == 1 or wide):
+                raise ValueError("column %d must be a contiguous device tensor, 1-D or [n,2] of 8-byte values" % k)
+            widths.append(16 if wide else t.element_size())
+        n_src = cols[0].shape[0] if cols else 0
+        if any(t.shape[0] != n_src for t in cols):
+            raise ValueError("columns must have one length")
+        if valid is not None and len(list(valid)) != len(cols):
+            raise ValueError("valid: one entry per column")
+        wants = [bool(want_validity)] * len(cols) if isinstance(want_validity, (bool, int)) else [bool(w) for w in want_validity]
+        if len(wants) != len(cols):
+            raise ValueError("want_validity: one entry per column")
+        dev = "cuda:%d" % self.device
+        src = (_lib.TakeSrc * max(len(cols), 1))()
+        dst = (_lib.TakeDst * max(len(cols), 1))()
+        outs, words, keep = [], [], []
+        for k, t in enumerate(cols):
+            src[k].data = t.data_ptr() if n_src else None
+            src[k].width = widths[k]
+            v = None if valid is None else list(valid)[k]
+            if v is not None:
+                b, off = v if isinstance(v, tuple) else (v, 0)
+                off = int(off)
+                if not b.is_cuda or not b.is_contiguous() or b.dim() != 1 or b.element_size() != 1:
+                    raise ValueError("valid[%d] must be a contiguous 1-D uint8 device tensor" % k)
+                if off < 0:
+                    raise ValueError("valid[%d]: bit_offset must not be negative" % k)
+                if off + n_src < (1 << 64) and b.shape[0] * 8 < off + n_src:  # (an overflowing offset is the library's to reject)
+                    raise ValueError("valid[%d] holds fewer than bit_offset + n bits" % k)
+                src[k].validity.bits = b.data_ptr() if b.shape[0] else None
+                src[k].validity.bit_offset = off & 0xFFFFFFFFFFFFFFFF
+                keep.append(b)
+            o = torch.empty((n_out,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev)
+            w = torch.empty((n_out + 63) // 64, dtype=torch.int64, device=dev) if wants[k] else None
+            dst[k].data = o.data_ptr() if n_out else None
+            dst[k].validity = w.data_ptr() if (w is not None and n_out) else None
+            outs.append(o)
+            words.append(w)
+        opts = _lib.TakeOpts()
+        opts.struct_size = C.sizeof(_lib.TakeOpts)
+        self._check(self.L.hmj_take_cols_device(self.h, src, len(cols), n_src, C.c_void_p(map_ptr or None), n_out, dst, C.byref(opts)))
+        del keep
+        info = {"null_count": [int(dst[k].null_count) for k in range(len(cols))], "n_no_row": int(opts.n_no_row),
+                "ms_take": float(opts.ms_take)}
+        return outs, (words if any(wants) or not cols else None), info
+
     def prepare_build(self, build, n_probe_hint):
         """Partition the build side now; the next matching plain-count join_device skips that work."""
         self._sync_stream()
@@ -714,6 +786,18 @@ def pack_validity(mask, bit_offset=0, device=None):
     bits = np.concatenate([np.ones(bit_offset, bool), mask])
     t = torch.from_numpy(np.packbits(bits, bitorder="little"))
     return t if device is None else t.to(device)
+
+
+def unpack_validity(words, n):
+    """The first n rows of an Arrow validity bitmap held as 64-bit words (what `Executor.take_cols_device` returns; a torch
+    tensor or a numpy array of int64 / uint64) -> a bool array, True = valid: row i is bit i & 63 of word i >> 6."""
+    if hasattr(words, "cpu"):
+        words = words.cpu().numpy()
+    raw = np.ascontiguousarray(words).view(np.uint8)
+    n = int(n)
+    if n < 0 or raw.size * 8 < n:
+        raise ValueError("the words hold fewer than n bits")
+    return np.unpackbits(raw, bitorder="little")[:n].astype(bool)
 
 
 def _mix64(x):

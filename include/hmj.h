@@ -399,8 +399,8 @@ int hmj_exchange_join_kind_u64_device(hmj_ctx* ctx, const void* build_shard_dev,
  * multi-column -- hmj_join_cols_device, hmj_join_kind_cols_device --, host-resident, exchange), hmj_sort_u64_device, hmj_sort_rows_by_u64_host, hmj_argsort_u64_host, hmj_partition_u64_device,
  * hmj_hash_str_device (each of them also when given no rows), hmj_reserve and hmj_autotune_radix_bits.  Left out are the calls that read or write no workspace buffer: hmj_set_stream,
  * hmj_set_radix_bits / hmj_set_key_prefix_bits (the join then plans other bits and partitions R again), hmj_set_profiling,
- * hmj_forget_workloads, hmj_release_result (result columns only), the hmj_last_* / hmj_placement_info queries and the
- * hmj_gen_* generators; a call refused with HMJ_E_ARG before it started may leave the prepared state in place as well.
+ * hmj_forget_workloads, hmj_release_result (result columns only), the hmj_last_* / hmj_placement_info queries, the
+ * hmj_gen_* generators and hmj_take_cols_device (its only workspace is a counter buffer of its own); a call refused with HMJ_E_ARG before it started may leave the prepared state in place as well.
  * n_probe_hint: the probe size the join will have (it selects the partitioning path).
  * Corresponds to the first radix_non_inplace_par call of the reference ctor (hashjoin.h:65).       */
 int hmj_prepare_build_u64_device(hmj_ctx* ctx, const void* build_aos_dev, uint64_t n_build,
@@ -665,7 +665,8 @@ typedef struct {
  * hmj_last_plan / hmj_last_timing describe the inner {key64,row} join.  Its workload memo is keyed apart from every
  * other entry's, so multi-column joins do not change what u64 or string joins learn.  Like any other call it discards a
  * prepared build side.  Join kinds: hmj_join_kind_cols_device below.  Out of scope: the exchange (multi-GPU) path,
- * host-resident columns, returning the key columns, signed / collated ordering.
+ * host-resident columns, signed / collated ordering.  The key columns (and any other fixed-width column of either
+ * relation) come back through the maps: hmj_take_cols_device below, with r_row / s_row as its row_map.
  * NULL keys (Arrow validity bitmaps, hmj_validity above, in the string section): hmj_cols_join_opts keeps its layout and carries none, so this
  * entry joins columns without NULLs.  The inner join of nullable key columns is hmj_join_kind_cols_device below with
  * HMJ_KIND_PROBE_SIDE + HMJ_JOIN_INNER, whose opts carry one hmj_validity per key column and side: the same rows, sums,
@@ -708,7 +709,8 @@ int hmj_join_cols_device(hmj_ctx* ctx, const hmj_cols_rel* build, const hmj_cols
  * not of that side, HMJ_FIRST_WINS, and everything hmj_join_cols_device rejects.  HMJ_E_UNSUPPORTED wherever the ordered
  * inner multi-column join returns it (the same 1024-row and 2^22 limits, over result rows).  The ctx stays usable.
  * hmj_last_plan / hmj_last_timing describe the last internal u64 join; the kinds' workloads are keyed apart from every
- * other entry's.  Like any other call it discards a prepared build side.  Out of scope: as hmj_join_cols_device.
+ * other entry's.  Like any other call it discards a prepared build side.  Out of scope: as hmj_join_cols_device; the
+ * columns of an outer kind's rows, NULL where HMJ_COLS_NO_ROW stands, come from hmj_take_cols_device below.
  * NULL keys (Arrow validity bitmaps): opts->build_validity / probe_validity give one hmj_validity per key column of that
  * side (a NULL array, entries with bits == NULL and bitmaps on one side only are all valid; a call without any bitmap
  * launches exactly the kernels of a call that cannot pass one).  The fields are read and written only when struct_size
@@ -763,6 +765,67 @@ typedef struct {
 } hmj_cols_kind_opts;
 int hmj_join_kind_cols_device(hmj_ctx* ctx, const hmj_cols_rel* build, const hmj_cols_rel* probe, uint32_t flags,
                               hmj_cols_kind_opts* opts, hmj_cols_result* out);
+
+/* ---- taking fixed-width columns through a row map (Arrow validity out) --------------------------------- */
+/* The joins above return gather maps (r_row / s_row), not columns.  This entry turns a map back into Arrow columns: up to
+ * HMJ_MAX_TAKE_COLS fixed-width columns of ONE relation (n_src rows each; keys, payloads, anything of 1, 2, 4, 8 or 16
+ * bytes per value) are taken through row_map (n_out entries) into caller-owned output columns, each with an optional
+ * validity bitmap and always with its null count.  src and dst are HOST arrays of n_cols entries (read during the call
+ * only; dst[c].null_count is written); everything they point to is on the device.
+ * Output slot i of column c is NULL when row_map[i] == HMJ_TAKE_NO_ROW (an outer join's missing partner), or when source
+ * row row_map[i] is NULL in column c (src[c].validity, an Arrow bitmap at any bit_offset; bits == NULL: the column has no
+ * NULL).  Otherwise it is valid and its value is the source value bit for bit.  The value bytes of a NULL output slot are
+ * written as 0, whatever lies under the source's NULL slot: the output is a function of the inputs alone.
+ * dst[c].validity != NULL: ceil(n_out / 64) 64-bit words are written, an Arrow bitmap at bit offset 0 (row i = bit i & 63
+ * of word i >> 6, least-significant bit first, which is Arrow's byte order on a little-endian host); the padding bits
+ * behind row n_out - 1 are written as 0.  dst[c].null_count is filled with or without a bitmap.  A map without
+ * HMJ_TAKE_NO_ROW over sources without bitmaps gives all-ones bitmaps (padding 0) and null_count 0.  opts->n_no_row: the
+ * map entries equal to HMJ_TAKE_NO_ROW.
+ * row_map may be a column the ctx owns -- the last result's r_row / s_row of hmj_join_cols_device,
+ * hmj_join_kind_cols_device, hmj_join_str_device or hmj_join_kind_str_device -- or any device array of the caller's.  The
+ * call neither releases nor overwrites the last result and does not discard a prepared build side; its only workspace is
+ * a small counter buffer of its own.  hmj_last_plan, hmj_last_timing and the workload memos stay as they were.  It returns
+ * with the work complete on the ctx stream, like the joins; the counts come back to the host.
+ * A map entry >= n_src that is not HMJ_TAKE_NO_ROW is HMJ_E_ARG, and hmj_last_error says how many there were.  The kernel
+ * compares before it loads, so such an index is never dereferenced (its lane writes a NULL slot); the outputs are
+ * unspecified after the error and the ctx stays usable.
+ * HMJ_E_ARG also (hmj_last_error names what was wrong): NULL ctx / src / dst / opts; a NULL row_map with n_out > 0;
+ * opts->struct_size smaller than through `reserved`; non-zero reserved (opts or a column); n_cols outside
+ * 1..HMJ_MAX_TAKE_COLS; a width other than 1, 2, 4, 8 or 16; NULL or misaligned data (source when n_src > 0, destination
+ * when n_out > 0; a 16-byte column is aligned to 16); a row_map or dst validity pointer not aligned to 8 bytes; bit_offset +
+ * n_src overflowing 64 bits; n_out or n_src above 2^32-1; a destination range (data or bitmap) that overlaps the row map or
+ * any source column or source bitmap of the call (a host check on address ranges).
+ * n_out == 0 returns HMJ_OK and writes nothing on the device.  n_src == 0 is legal when every entry is HMJ_TAKE_NO_ROW
+ * (source pointers may then be NULL).
+ * How (DESIGN.md "Taking columns through a join's row maps"): cols_take_kernel, one lane per output row in 256-thread
+ * workgroups, up to 8 columns per launch (the host loops over chunks of 8).  The map entry is loaded once per row and tested
+ * once for all columns; all of a row's gathers are issued before its first store.  A wave covers 64 consecutive rows that
+ * start at a multiple of 64, so its ballot of "valid" is one bitmap word, stored by one lane: no atomics and no
+ * read-modify-write on the bitmap.  The counts are ballot popcounts, one atomic per workgroup and counter.
+ * Out of scope: variable-width (string) columns, host-resident columns, bit-packed boolean value columns, the exchange
+ * path.                                                                                                              */
+#define HMJ_TAKE_NO_ROW UINT64_MAX   /* == HMJ_COLS_NO_ROW == HMJ_STR_NO_ROW */
+#define HMJ_MAX_TAKE_COLS 64
+typedef struct {
+  const void* data;       /* device: n_src values of `width` bytes, aligned to `width`          */
+  uint32_t width;         /* 1, 2, 4, 8 or 16                                                    */
+  uint32_t reserved;      /* 0                                                                   */
+  hmj_validity validity;  /* source bitmap, any bit_offset; bits == NULL: the column has no NULL */
+} hmj_take_src;
+typedef struct {
+  void* data;             /* device, caller-owned: n_out * width bytes, aligned to width         */
+  uint64_t* validity;     /* device, caller-owned, or NULL: ceil(n_out / 64) 64-bit words; Arrow
+                             bitmap at bit offset 0, row i = bit i, padding bits written as 0    */
+  uint64_t null_count;    /* out: NULL slots of this output column (filled with or without bitmap) */
+} hmj_take_dst;
+typedef struct {
+  uint32_t struct_size;   /* size-versioned like the other opts                                  */
+  uint32_t reserved;
+  uint64_t n_no_row;      /* out: map entries equal to HMJ_TAKE_NO_ROW                           */
+  float ms_take;          /* out, with hmj_set_profiling                                         */
+} hmj_take_opts;
+int hmj_take_cols_device(hmj_ctx* ctx, const hmj_take_src* src, uint32_t n_cols, uint64_t n_src,
+                         const uint64_t* row_map, uint64_t n_out, hmj_take_dst* dst, hmj_take_opts* opts);
 /* Host threads of the optional staged upload (pageable input -> pinned chunks -> PCIe), used only
  * with HMJ_UPLOAD=staged in the environment; by default each relation goes up in one copy straight
  * from the caller's memory (54 GB/s on the MI355X box).  The reference ctor's num_threads argument,
