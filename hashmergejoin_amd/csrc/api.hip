@@ -3207,24 +3207,19 @@ void hmj_destroy(hmj_ctx* c) {
                     &c->offs64, &c->irregular, &c->ord_key, &c->ord_rval, &c->ord_sval, &c->matched, &c->vparts,
                     &c->slab_a, &c->slab_br, &c->slab_bs, &c->cnt_a, &c->cnt_br, &c->cnt_bs, &c->lookback, &c->gtab, &c->piece_off,
                     &c->split_r, &c->split_s, &c->split_off, &c->cat_key, &c->cat_rval, &c->cat_sval, &c->msd_off,
-                    &c->bmatched, &c->bsweep, &c->str_rows_r, &c->str_rows_s, &c->str_flags, &c->str_blk, &c->str_blk_off,
-                    &c->str_hash, &c->str_rrow, &c->str_srow, &c->str_rval, &c->str_sval, &c->str_list, &c->str_runs, &c->str_acc,
-                    &c->str_mark_r, &c->str_mark_s, &c->str_amb, &c->str_ord, &c->str_khash, &c->str_krrow, &c->str_ksrow, &c->str_krval, &c->str_ksval,
-                    &c->col_rows_r, &c->col_rows_s, &c->col_flags, &c->col_blk, &c->col_blk_off, &c->col_key, &c->col_rrow, &c->col_srow,
-                    &c->col_rval, &c->col_sval, &c->col_list, &c->col_runs, &c->col_acc, &c->col_mark_r, &c->col_mark_s, &c->col_amb,
-                    &c->col_ord, &c->col_kkey, &c->col_krrow, &c->col_ksrow, &c->col_krval, &c->col_ksval, &c->col_cmp_r,
-                    &c->col_cmp_s, &c->col_vblk, &c->str_cmp_r, &c->str_cmp_s, &c->str_vblk, &c->take_acc};
+                    &c->bmatched, &c->bsweep, &c->take_acc};
   for (DevBuf* b : devs) free_dev(*b);
+  for (KeyJoinWs* ws : {&c->str_ws, &c->col_ws}) {
+    ws->each_buf(free_dev);
+    for (auto& e : ws->ev)
+      if (e) (void)hipEventDestroy(e);
+  }
   HostBuf* hosts[] = {&c->h_accum, &c->h_key, &c->h_rval, &c->h_sval};
   for (HostBuf* b : hosts) free_host(*b);
   for (auto& e : c->events)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : c->up_events) (void)hipEventDestroy(e);
   for (auto& e : c->place_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : c->str_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : c->col_ev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : c->take_ev)
     if (e) (void)hipEventDestroy(e);
@@ -3689,11 +3684,8 @@ void hmj_release_result(hmj_ctx* c) {
   free_dev(c->ord_key);
   free_dev(c->ord_rval);
   free_dev(c->ord_sval);
-  DevBuf* str_cols[5] = {&c->str_hash, &c->str_rrow, &c->str_srow, &c->str_rval, &c->str_sval};
-  for (DevBuf* b : str_cols) free_dev(*b);
-  DevBuf* col_cols[11] = {&c->col_key,  &c->col_rrow,  &c->col_srow,  &c->col_rval,  &c->col_sval, &c->col_ord,
-                          &c->col_kkey, &c->col_krrow, &c->col_ksrow, &c->col_krval, &c->col_ksval};
-  for (DevBuf* b : col_cols) free_dev(*b);
+  c->str_ws.each_result_buf(free_dev);
+  c->col_ws.each_result_buf(free_dev);
   free_host(c->h_key);
   free_host(c->h_rval);
   free_host(c->h_sval);

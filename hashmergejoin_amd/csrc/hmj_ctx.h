@@ -25,6 +25,30 @@ struct HostBuf {
   bool pinned = true;  // false: pageable memory on transparent huge pages (the result columns)
 };
 
+// Workspace of one of the two joins on {key64, row} rows (hmj_keyjoin.h; key64: the string join's hash, the multi-column
+// join's packed tuple or hash).
+struct KeyJoinWs {
+  DevBuf rows_r, rows_s,           // {key64, row} rows of both relations
+      flags, blk, blk_off,         // pass-1 ballots, per-workgroup survivors and their offsets
+      list, runs, acc,             // the collision search's rows and runs, the counters
+      mark_r, mark_s, amb,         // join kinds: one mark byte per row of each relation, the rows whose representative's key differed
+      cmp_r, cmp_s, vblk,          // validity bitmaps only: the compacted {key64, row} rows of the rows that have a key, the valid
+                                   // rows per workgroup of both relations and their offsets
+      key, rrow, srow, rval, sval, // the five result columns (the multi-column join's packed form fills rval / sval only)
+      ord, kkey, krrow, ksrow, krval, ksval;  // ordered kinds: (key64, index) rows and their sorted copy, the result columns in sorted order
+  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // phase boundaries (profiling)
+  // the buffers a result lives in (hmj_release_result frees them), and every buffer
+  template <class F>
+  void each_result_buf(F f) {
+    for (DevBuf* b : {&key, &rrow, &srow, &rval, &sval, &ord, &kkey, &krrow, &ksrow, &krval, &ksval}) f(*b);
+  }
+  template <class F>
+  void each_buf(F f) {
+    for (DevBuf* b : {&rows_r, &rows_s, &flags, &blk, &blk_off, &list, &runs, &acc, &mark_r, &mark_s, &amb, &cmp_r, &cmp_s, &vblk}) f(*b);
+    each_result_buf(f);
+  }
+};
+
 enum Kind {
   K_TOTAL = 0, K_H2D, K_D2H, K_HIST, K_SCAN, K_SCATTER, K_OFFSETS, K_PROBE_COUNT, K_OUT_SCAN,
   K_PROBE_WRITE, K_ORDER, K_NKINDS
@@ -107,30 +131,11 @@ struct hmj_ctx {
       split_r, split_s, split_off, cat_key, cat_rval, cat_sval,  // joins by key ranges: both relations cut, the appended result columns
       msd_off,  // the rank forms' build-side sort: partition offsets of its one MSD pass
       bmatched, bsweep,  // build-side kinds: one bit per build row slot; the sweep's row counts ([0] all, [1 + p] partition p)
-      // string joins (strjoin.hip): {hash, row} rows of both relations, pass-1 ballots, per-workgroup survivors and their
-      // offsets, the five result columns, the collision search's rows and runs, its counters
-      str_rows_r, str_rows_s, str_flags, str_blk, str_blk_off, str_hash, str_rrow, str_srow, str_rval, str_sval, str_list,
-      str_runs, str_acc,
-      // string join kinds: one mark byte per row of each relation, the rows whose representative's key differed, the
-      // ordered form's (hash, index) rows and sorted copy, the five result columns in sorted order
-      str_mark_r, str_mark_s, str_amb, str_ord, str_khash, str_krrow, str_ksrow, str_krval, str_ksval,
-      // multi-column joins (coljoin.hip): {key64, row} rows of both relations, pass-1 ballots, per-workgroup survivors and
-      // their offsets, the result columns (the packed form fills rval / sval only), the collision search's rows and runs,
-      // its counters
-      col_rows_r, col_rows_s, col_flags, col_blk, col_blk_off, col_key, col_rrow, col_srow, col_rval, col_sval, col_list,
-      col_runs, col_acc,
-      // multi-column join kinds: one mark byte per row of each relation, the rows whose representative's tuple differed,
-      // the ordered form's (key64, index) rows and sorted copy, the five result columns in sorted order
-      col_mark_r, col_mark_s, col_amb, col_ord, col_kkey, col_krrow, col_ksrow, col_krval, col_ksval,
-      // multi-column joins with validity bitmaps only: the {key64, row} rows of the non-NULL rows of each relation
-      // (compacted, in row order), the valid rows per workgroup of both relations and their offsets
-      col_cmp_r, col_cmp_s, col_vblk,
-      // string joins with validity bitmaps only: likewise ({hash, row} rows of the non-NULL rows, counts and offsets)
-      str_cmp_r, str_cmp_s, str_vblk,
       // hmj_take_cols_device (take.hip): its counters -- the only workspace the call owns
       take_acc;
-  hipEvent_t str_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // string joins' phase boundaries (profiling)
-  hipEvent_t col_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // multi-column joins' phase boundaries (profiling)
+  // string joins (strjoin.hip) and multi-column joins (coljoin.hip): one workspace each, so that neither call reuses or
+  // regrows the other's buffers
+  hmj_host::KeyJoinWs str_ws, col_ws;
   hipEvent_t take_ev[2] = {nullptr, nullptr};  // hmj_take_cols_device: around its launches (profiling)
   int memo_kind = 0;  // workload-signature kind of plain inner joins run on behalf of another entry (string, multi-column joins and their kinds)
   HostBuf h_accum, h_key, h_rval, h_sval;

@@ -480,7 +480,7 @@ typedef struct {
  * broken on the key (radix_hash.h:86-109).
  * How: every key is hashed into a {hash, row} row (str_hash_kernel; the wave's 64 keys staged in LDS), the two row sets
  * are joined by the u64 join (HMJ_MATERIALIZE, + HMJ_ORDERED), every pair of equal hash has its keys compared and its
- * payloads gathered (str_verify_kernel; survivors compacted stably), and -- ordered only -- runs of equal hash whose
+ * payloads gathered (verify_kernel; survivors compacted stably), and -- ordered only -- runs of equal hash whose
  * build keys differ are sorted by key bytes, each inside one workgroup.
  * n == 0 on either side: an empty result and HMJ_OK.
  * HMJ_E_ARG: NULL ctx / rel / opts / out; NULL offsets or vals with n > 0; opts->struct_size too small; more than
@@ -559,7 +559,7 @@ int hmj_join_str_device(hmj_ctx* ctx, const hmj_str_rel* build, const hmj_str_re
  * sweeps emit them into a tail segment of their own), so the 1024-row and 2^22 limits count non-NULL rows only.
  * A side whose rows are all NULL-key behaves as an empty side for matching; its rows are still emitted by the kinds that
  * emit unmatched rows of that side.  HMJ_E_ARG also: bit_offset + n overflows 64 bits.
- * How: a pass over the bitmap alone counts the valid rows per 256-row workgroup (str_valid_count_kernel), one scan places
+ * How: a pass over the bitmap alone counts the valid rows per 256-row workgroup (valid_count_kernel), one scan places
  * the workgroups, and str_hash_valid_kernel -- str_hash_kernel with the wave's LDS staging and its unstaged path -- writes
  * the {hash, row} rows of the valid rows only, compacted stably in row order (the u64 joins take those), and for the kinds
  * a dense row-indexed array with {0, HMJ_STR_NO_ROW} for a NULL-key row, which the sweeps walk.  Row indices in the result
@@ -652,7 +652,7 @@ typedef struct {
  * How: every row becomes a {key64, row} row (cols_key_kernel: one lane per row, coalesced loads per column, one 16-byte
  * store), the two row sets are joined by the u64 join (HMJ_MATERIALIZE, + HMJ_ORDERED).  Packed: the join's columns are
  * the result's key64 / r_row / s_row; one kernel gathers the payloads and takes the sums.  Hashed: every pair of equal
- * key64 has its tuples compared column by column and its payloads gathered (cols_verify_kernel; survivors compacted
+ * key64 has its tuples compared column by column and its payloads gathered (verify_kernel; survivors compacted
  * stably), and -- ordered only -- runs of equal key64 whose build tuples differ are sorted by tuple, each inside one
  * workgroup.
  * n == 0 on either side: an empty result and HMJ_OK (sum_probe_all is still filled when asked).
@@ -738,7 +738,7 @@ int hmj_join_cols_device(hmj_ctx* ctx, const hmj_cols_rel* build, const hmj_cols
  * them into a tail segment of their own), so the 1024-row and 2^22 limits count non-NULL rows only.
  * A side whose rows are all NULL-key behaves as an empty side for matching; its rows are still emitted by the kinds that
  * emit unmatched rows of that side.  opts->form is filled as always.  HMJ_E_ARG also: bit_offset + n overflows 64 bits.
- * How: a pass over the bitmaps alone counts the valid rows per workgroup (cols_valid_count_kernel), one scan places the
+ * How: a pass over the bitmaps alone counts the valid rows per workgroup (valid_count_kernel), one scan places the
  * workgroups, and cols_key_valid_kernel writes the {key64,row} rows of the valid rows only, compacted stably in row order;
  * the u64 joins take those.  Row indices in the result stay the caller's.
  * Out of scope for NULL keys: NULL-equals-NULL matching (IS NOT DISTINCT FROM), validity of the payload column, the
