@@ -67,12 +67,6 @@ void add_timing(hmj_timing* acc, const hmj_timing& t) {
   acc->n_probe_items += t.n_probe_items;
 }
 
-#define HIP_TRY(expr)                                                   \
-  do {                                                                  \
-    hipError_t _e = (expr);                                             \
-    if (_e != hipSuccess) return fail(c, HMJ_E_HIP, #expr, _e);         \
-  } while (0)
-
 // ---- what the context has learnt, per workload ------------------------------------------------------------------
 static int ilog2_u64(uint64_t v) { return v ? 63 - __builtin_clzll(v) : 0; }
 uint64_t workload_signature(uint64_t n_build, uint64_t n_probe, uint32_t flags, int kind) {
@@ -450,9 +444,8 @@ int radix_pass(hmj_ctx* c, const void* src, void* dst, u32 n, int shift, int bit
   const int variant = c->scatter_variant;
   const int tile = hmj::radix_tile_rows(bits, variant);
   hmj::radix_pass_geometry(n, tile, &nblk, &rpb);
-  int rc;
-  if ((rc = ensure_dev(c, c->hist, (size_t)(1u << bits) * nblk * sizeof(u32))) != HMJ_OK) return rc;
-  if ((rc = ensure_dev(c, c->totals, (size_t)hmj::RP_MAXD * sizeof(u32))) != HMJ_OK) return rc;
+  RC_TRY(ensure_dev(c, c->hist, (size_t)(1u << bits) * nblk * sizeof(u32)));
+  RC_TRY(ensure_dev(c, c->totals, (size_t)hmj::RP_MAXD * sizeof(u32)));
   int s = span_begin(c, K_HIST, rel);
   HIP_TRY(hmj::launch_radix_hist(src, n, tile, shift, bits, (u32*)c->hist.p, nblk, rpb, c->stream));
   span_end(c, s);
@@ -476,12 +469,11 @@ int partition_relation(hmj_ctx* c, const void* in, u32 n, DevBuf buf[2], int top
                        const int pass_bits[4], int rel, const void** result, bool try_in_place = false) {
   *result = in;
   if (passes == 0 || n == 0) return HMJ_OK;
-  int rc;
   if (try_in_place) {
     int bits = 0;
     for (int i = 0; i < passes; i++) bits += pass_bits[i];
-    if ((rc = ensure_dev(c, c->offs64, 8 * sizeof(u64))) != HMJ_OK) return rc;
-    if ((rc = ensure_host(c, c->h_accum, 8 * sizeof(u64))) != HMJ_OK) return rc;
+    RC_TRY(ensure_dev(c, c->offs64, 8 * sizeof(u64)));
+    RC_TRY(ensure_host(c, c->h_accum, 8 * sizeof(u64)));
     u32* flag = (u32*)((u64*)c->offs64.p + 7);
     u32* hflag = (u32*)((u64*)c->h_accum.p + 7);
     HIP_TRY(hipMemsetAsync(flag, 0, 4, c->stream));
@@ -495,13 +487,13 @@ int partition_relation(hmj_ctx* c, const void* in, u32 n, DevBuf buf[2], int top
       return HMJ_OK;  // *result == in
     }
   }
-  if ((rc = ensure_dev(c, buf[0], (size_t)n * 16)) != HMJ_OK) return rc;
-  if (passes > 1 && (rc = ensure_dev(c, buf[1], (size_t)n * 16)) != HMJ_OK) return rc;
+  RC_TRY(ensure_dev(c, buf[0], (size_t)n * 16));
+  if (passes > 1) RC_TRY(ensure_dev(c, buf[1], (size_t)n * 16));
   const void* src = in;
   int shift = top;  // lowest of the partition bits
   for (int i = 0; i < passes; i++) {
     void* dst = buf[i & 1].p;
-    if ((rc = radix_pass(c, src, dst, n, shift, pass_bits[i], rel, nullptr, i)) != HMJ_OK) return rc;
+    RC_TRY(radix_pass(c, src, dst, n, shift, pass_bits[i], rel, nullptr, i));
     shift += pass_bits[i];
     src = dst;
   }
@@ -583,6 +575,139 @@ constexpr int kRetryNoSlabProbe = 1004;  // internal: the probe-side slab partit
 constexpr int kRetryMoreBits = 1005;  // internal: a partition did not fit the ordered expansion but would with one more radix bit -> re-plan
 constexpr int kRetryNoPrefix = 1000;  // internal: ordered join must be re-planned without the sampled prefix
 
+// ---- steps the plans share, each written once ---------------------------------------------------------------------------
+// The accumulators of the join in progress read back: c->accum -> c->h_accum, one stream sync.  *h = the host copy (the
+// ACC_* slots); a caller looks at its ACC_ERR bits before it takes the sums (result_sums).
+static int read_accum(hmj_ctx* c, u64** h) {
+  u64* hh = (u64*)c->h_accum.p;
+  HIP_TRY(hipMemcpyAsync(hh, c->accum.p, 8 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  *h = hh;
+  return HMJ_OK;
+}
+// the six sums of an hmj_result from the accumulators' host copy
+static void result_sums(hmj_result* out, const u64* h) {
+  out->n_matches = h[hmj::ACC_N];
+  out->sum_r = h[hmj::ACC_SUM_R];
+  out->sum_s = h[hmj::ACC_SUM_S];
+  out->xor_fold = h[hmj::ACC_XOR];
+  out->mix_sum = h[hmj::ACC_MIX];
+  out->sum_probe_all = h[hmj::ACC_SUM_P];
+}
+
+// The result columns handed to the caller: three dense device columns of `bytes` bytes each (a join kind without an rval /
+// sval column passes nullptr there, and the result's pointer stays null), as they are or -- to_host -- copied into the
+// context's host columns under a K_D2H span.  sync_always: the stream is synchronised on both legs (the sites whose last
+// kernels nobody has waited for); otherwise only behind the copies.  A small join's latency is mostly these syncs, so every
+// site says which it needs.
+static int deliver_columns(hmj_ctx* c, hmj_result* out, bool to_host, const void* key, const void* rval, const void* sval,
+                           size_t bytes, bool sync_always) {
+  if (to_host) {
+    RC_TRY(ensure_host(c, c->h_key, bytes, false));
+    if (rval) RC_TRY(ensure_host(c, c->h_rval, bytes, false));
+    if (sval) RC_TRY(ensure_host(c, c->h_sval, bytes, false));
+    const int s = span_begin(c, K_D2H, -1);
+    HIP_TRY(hipMemcpyAsync(c->h_key.p, key, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (rval) HIP_TRY(hipMemcpyAsync(c->h_rval.p, rval, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (sval) HIP_TRY(hipMemcpyAsync(c->h_sval.p, sval, bytes, hipMemcpyDeviceToHost, c->stream));
+    span_end(c, s);
+  }
+  if (to_host || sync_always) HIP_TRY(hipStreamSynchronize(c->stream));
+  out->key = (const uint64_t*)(to_host ? c->h_key.p : key);
+  out->rval = rval ? (const uint64_t*)(to_host ? c->h_rval.p : rval) : nullptr;
+  out->sval = sval ? (const uint64_t*)(to_host ? c->h_sval.p : sval) : nullptr;
+  return HMJ_OK;
+}
+
+// ProbeArgs of the offset layout: both relations partitioned exactly, partition p = rows [off[p], off[p + 1]) of Rp / Sp.
+static hmj::ProbeArgs offset_probe_args(hmj_ctx* c, const void* Rp, const void* Sp, u32 P, u32 Q) {
+  hmj::ProbeArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.R = Rp;
+  a.r_off = (const u32*)c->r_off.p;
+  a.S = Sp;
+  a.s_off = (const u32*)c->s_off.p;
+  a.P = P;
+  a.Q = Q;
+  a.accum = (u64*)c->accum.p;
+  return a;
+}
+// ProbeArgs of the slab layouts.  The probe side lies in the pieces of s_slab / s_cnt, s_cap rows each (pass-B slabs, or --
+// with the caller's s_wa / s_ppi on top -- the worker-private slabs of pass A).  The build side lies in the build slabs
+// (build_slabs: their geometry; c->slab_br / c->cnt_br) or was partitioned exactly (build_slabs == nullptr: Rp and c->r_off).
+static hmj::ProbeArgs slab_probe_args(hmj_ctx* c, const hmj::SlabGeom* build_slabs, const void* Rp, const DevBuf& s_slab,
+                                      const DevBuf& s_cnt, u32 s_cap, u32 P, u32 Q) {
+  hmj::ProbeArgs a;
+  std::memset(&a, 0, sizeof(a));
+  if (build_slabs) {
+    a.R = c->slab_br.p;
+    a.r_cnt = (const u32*)c->cnt_br.p;
+    a.r_cap = build_slabs->CB;
+    a.r_cnt_n = c->cnt_br.cap / 4;
+    a.r_rows = c->slab_br.cap / 16;
+  } else {
+    a.R = Rp;
+    a.r_off = (const u32*)c->r_off.p;
+  }
+  a.S = s_slab.p;
+  a.s_cnt = (const u32*)s_cnt.p;
+  a.s_cap = s_cap;
+  a.s_cnt_n = s_cnt.cap / 4;
+  a.s_rows = s_slab.cap / 16;
+  a.P = P;
+  a.Q = Q;
+  a.accum = (u64*)c->accum.p;
+  return a;
+}
+
+// Slab pass A of one relation: its rows into the worker-private slabs c->slab_a / c->cnt_a (allocated by the caller) by the
+// `bits`-bit digit at `low`.  arriving: the probe rows are still arriving over the links (exchange.hip) -- pass-A workers own
+// contiguous input ranges, so the workers whose rows are complete start after each round's event.
+static int slab_pass_a(hmj_ctx* c, const void* in, u32 n, int rel, int low, int bits, const hmj::SlabGeom& g, bool arriving) {
+  u64* acc = (u64*)c->accum.p;
+  const u64 a_rows = c->slab_a.cap / 16, a_cnt = c->cnt_a.cap / 4;  // what is allocated: the launchers check it
+  const int sp = span_begin(c, K_SCATTER, rel, 0);
+  if (arriving) {
+    u32 w_done = 0;
+    for (size_t i = 0; i < c->arrive_ev.size(); i++) {
+      RC_TRY(wait_arrival(c, c->arrive_ev[i]));
+      const bool last = i + 1 == c->arrive_ev.size();
+      const u32 w_end = last ? g.WA : (u32)std::min<u64>(g.WA, c->arrive_rows[i] / g.rpw);
+      if (w_end > w_done) {
+        HIP_TRY(hmj::launch_slab_a(in, n, low, bits, g, c->slab_a.p, a_rows, (u32*)c->cnt_a.p, a_cnt, acc, c->stream, w_done, w_end));
+        w_done = w_end;
+      }
+    }
+  } else {
+    HIP_TRY(hmj::launch_slab_a(in, n, low, bits, g, c->slab_a.p, a_rows, (u32*)c->cnt_a.p, a_cnt, acc, c->stream));
+  }
+  span_end(c, sp);
+  c->timing.bytes_scatter += 32ull * n;
+  return HMJ_OK;
+}
+// Both slab passes of one relation: pass A (above), then pass B out of c->slab_a into the slab / count pair `sb` / `cb`
+// (allocated by the caller) by the bb-bit digit above pass A's.
+static int slab_passes(hmj_ctx* c, const void* in, u32 n, int rel, int low, int ba, int bb, const hmj::SlabGeom& g, DevBuf& sb,
+                       DevBuf& cb, bool arriving) {
+  RC_TRY(slab_pass_a(c, in, n, rel, low, ba, g, arriving));
+  const int sp = span_begin(c, K_SCATTER, rel, 1);
+  HIP_TRY(hmj::launch_slab_b(c->slab_a.p, (const u32*)c->cnt_a.p, ba, low + ba, bb, g, sb.p, sb.cap / 16, (u32*)cb.p, cb.cap / 4,
+                             (u64*)c->accum.p, c->stream));
+  span_end(c, sp);
+  c->timing.bytes_scatter += 32ull * n;
+  return HMJ_OK;
+}
+
+// The `matched` bitmap (first-wins joins, join kinds): one bit per probe row -- or probe row SLOT of a slab layout --
+// allocated and cleared.
+static int clear_matched(hmj_ctx* c, size_t slots, u32** matched) {
+  const size_t bytes = (slots / 32 + 1) * 4;
+  RC_TRY(ensure_dev(c, c->matched, bytes));
+  *matched = (u32*)c->matched.p;
+  HIP_TRY(hipMemsetAsync(c->matched.p, 0, bytes, c->stream));
+  return HMJ_OK;
+}
+
 // The ordered epilogue.  order_kernel sorts every partition's rows from the unsorted columns (c->out_*) into
 // c->ord_*; a segment too large for its in-LDS paths (hundreds of thousands of rows of a few keys) is only
 // copied and flagged, and the whole result is then sorted by (key, rval, sval) with three stable LSD sorts
@@ -591,11 +716,10 @@ constexpr int kRetryNoPrefix = 1000;  // internal: ordered join must be re-plann
 // finishes the order.  On return *rk/*rr/*rs are the ordered columns.
 int order_rows(hmj_ctx* c, const u32* vstart, const u32* in_base32, const u64* in_base64, u32 P, u32 Q, int low,
                u64 n, bool by_key_only, bool many_per_key, const u64** rk, const u64** rr, const u64** rs, int* retry_code) {
-  int rc;
   const size_t bytes = (size_t)n * 8;
-  if ((rc = ensure_dev(c, c->ord_key, bytes)) != HMJ_OK) return rc;
-  if ((rc = ensure_dev(c, c->ord_rval, bytes)) != HMJ_OK) return rc;
-  if ((rc = ensure_dev(c, c->ord_sval, bytes)) != HMJ_OK) return rc;
+  RC_TRY(ensure_dev(c, c->ord_key, bytes));
+  RC_TRY(ensure_dev(c, c->ord_rval, bytes));
+  RC_TRY(ensure_dev(c, c->ord_sval, bytes));
   const bool can_sort = n <= 0xFFFFFFFFull;  // row indices of the global sorts are 32-bit
   if (by_key_only && !can_sort) {
     *retry_code = kRetryNoWinOrdered;
@@ -619,8 +743,8 @@ int order_rows(hmj_ctx* c, const u32* vstart, const u32* in_base32, const u64* i
   if (!deferred && !by_key_only) return HMJ_OK;
   c->timing.path |= (deferred ? HMJ_PATH_ORDER_DEFERRED : 0u) | (by_key_only ? HMJ_PATH_ORDER_BY_KEY : 0u);
   c->prep.valid = false;  // the partition buffers become the sort's ping-pong pair
-  if ((rc = ensure_dev(c, c->rbuf[0], (size_t)n * 16)) != HMJ_OK) return rc;
-  if ((rc = ensure_dev(c, c->rbuf[1], (size_t)n * 16)) != HMJ_OK) return rc;
+  RC_TRY(ensure_dev(c, c->rbuf[0], (size_t)n * 16));
+  RC_TRY(ensure_dev(c, c->rbuf[1], (size_t)n * 16));
   sp = span_begin(c, K_ORDER, -1);
   const u64* cols[3] = {*rs, *rr, *rk};  // least significant sort key first
   int cur = 0;  // rbuf[cur] holds the {column value, row} pairs
@@ -633,7 +757,7 @@ int order_rows(hmj_ctx* c, const u32* vstart, const u32* in_base32, const u64* i
     // payloads of a few thousand keys: half of the 24 passes and more are copies; as in hmj_sort_u64_device)
     u32 digits = 0xFFu;
     if (n >= (1u << 22)) {
-      if ((rc = ensure_dev(c, c->offs64, 8 * sizeof(u64))) != HMJ_OK) return rc;
+      RC_TRY(ensure_dev(c, c->offs64, 8 * sizeof(u64)));
       const u64 init[3] = {0, ~0ull, 0};
       HIP_TRY(hipMemcpyAsync(c->offs64.p, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
       HIP_TRY(hmj::launch_key_exact(c->rbuf[cur].p, (u32)n, nullptr, 0u, 0, (u64*)c->offs64.p, c->num_cus, c->stream, true));
@@ -644,7 +768,7 @@ int order_rows(hmj_ctx* c, const u32* vstart, const u32* in_base32, const u64* i
     }
     for (int d = 0; d < 8; d++) {
       if (!(digits & (1u << d))) continue;
-      if ((rc = radix_pass(c, c->rbuf[cur].p, c->rbuf[cur ^ 1].p, (u32)n, 8 * d, 8, -1, nullptr)) != HMJ_OK) return rc;
+      RC_TRY(radix_pass(c, c->rbuf[cur].p, c->rbuf[cur ^ 1].p, (u32)n, 8 * d, 8, -1, nullptr));
       cur ^= 1;
     }
   }
@@ -664,14 +788,13 @@ int order_rows(hmj_ctx* c, const u32* vstart, const u32* in_base32, const u64* i
 int unique_key_write(hmj_ctx* c, hmj::ProbeArgs& wa, bool slab, u32 nb, u32 np, int low, bool extra,
                          int verify_prefix, u64 pfx_ref, bool ordered, bool to_host, bool fk_wide_plan, double density,
                          hmj_result* out) {
-  int rc;
   const u32 P = wa.P;
   const size_t cap_bytes = ((size_t)np + 8) * 8;  // at most one row per probe row
-  if ((rc = ensure_dev(c, c->part_count, (size_t)P * 8)) != HMJ_OK) return rc;
-  if ((rc = ensure_dev(c, c->part_out_off, ((size_t)P + 1) * 8)) != HMJ_OK) return rc;
-  if ((rc = ensure_dev(c, c->out_key, cap_bytes)) != HMJ_OK) return rc;
-  if ((rc = ensure_dev(c, c->out_rval, cap_bytes)) != HMJ_OK) return rc;
-  if ((rc = ensure_dev(c, c->out_sval, cap_bytes)) != HMJ_OK) return rc;
+  RC_TRY(ensure_dev(c, c->part_count, (size_t)P * 8));
+  RC_TRY(ensure_dev(c, c->part_out_off, ((size_t)P + 1) * 8));
+  RC_TRY(ensure_dev(c, c->out_key, cap_bytes));
+  RC_TRY(ensure_dev(c, c->out_rval, cap_bytes));
+  RC_TRY(ensure_dev(c, c->out_sval, cap_bytes));
   wa.part_count = (u64*)c->part_count.p;
   wa.out_key = (u64*)c->out_key.p;
   wa.out_rval = (u64*)c->out_rval.p;
@@ -684,7 +807,7 @@ int unique_key_write(hmj_ctx* c, hmj::ProbeArgs& wa, bool slab, u32 nb, u32 np, 
   const u64* in_base64 = nullptr;
   const u32* in_base32 = nullptr;
   if (slab) {  // first output slot of partition p = number of probe rows in partitions < p
-    if ((rc = ensure_dev(c, c->offs64, ((size_t)P * 2 + 2) * 8)) != HMJ_OK) return rc;
+    RC_TRY(ensure_dev(c, c->offs64, ((size_t)P * 2 + 2) * 8));
     u64* npv = (u64*)c->offs64.p;
     u64* base = npv + P;
     HIP_TRY(hmj::launch_slab_np(wa.s_cnt, P, npv, c->stream));
@@ -694,26 +817,7 @@ int unique_key_write(hmj_ctx* c, hmj::ProbeArgs& wa, bool slab, u32 nb, u32 np, 
   } else {
     in_base32 = wa.s_off;
   }
-  u64* h = (u64*)c->h_accum.p;
-  // the result delivered from three dense device columns
-  auto deliver = [&](const u64* rk, const u64* rr, const u64* rs) -> int {
-    const size_t bytes = (size_t)out->n_matches * 8;
-    if (to_host) {
-      if ((rc = ensure_host(c, c->h_key, bytes, false)) != HMJ_OK) return rc;
-      if ((rc = ensure_host(c, c->h_rval, bytes, false)) != HMJ_OK) return rc;
-      if ((rc = ensure_host(c, c->h_sval, bytes, false)) != HMJ_OK) return rc;
-      const int s2 = span_begin(c, K_D2H, -1);
-      HIP_TRY(hipMemcpyAsync(c->h_key.p, rk, bytes, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipMemcpyAsync(c->h_rval.p, rr, bytes, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipMemcpyAsync(c->h_sval.p, rs, bytes, hipMemcpyDeviceToHost, c->stream));
-      span_end(c, s2);
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    out->key = to_host ? (const uint64_t*)c->h_key.p : (const uint64_t*)rk;
-    out->rval = to_host ? (const uint64_t*)c->h_rval.p : (const uint64_t*)rr;
-    out->sval = to_host ? (const uint64_t*)c->h_sval.p : (const uint64_t*)rs;
-    return HMJ_OK;
-  };
+  u64* h;
   // ---- ordered joins: probe, sort and write in one pass (probe_write_sorted_kernel) when the keys allow it
   if (ordered && c->wm->sorted_cooldown > 0) c->wm->sorted_cooldown--;
   // two forms of the kernel: unique probe keys (a match bitmap), and repeating probe keys (a foreign-key join:
@@ -739,7 +843,7 @@ int unique_key_write(hmj_ctx* c, hmj::ProbeArgs& wa, bool slab, u32 nb, u32 np, 
       half = !no_half && f >= 2.0 && hi_np <= 3072.0 && hi_nb <= 2048.0;
       shape = half ? 1 : (fk_wide_plan && hi_nb <= 2560.0) ? 2 : 0;
     }
-    if ((rc = ensure_dev(c, c->lookback, ((size_t)P + 1) * 8)) != HMJ_OK) return rc;
+    RC_TRY(ensure_dev(c, c->lookback, ((size_t)P + 1) * 8));
     HIP_TRY(hipMemsetAsync(c->lookback.p, 0, ((size_t)P + 1) * 8, c->stream));
     // long runs (from 24 probe rows per build row on): the kernel's instantiation that buckets the output slots by (build
     // rank, payload position) and ranks inside those buckets instead of inside whole runs (HMJ_FK_PAYLOAD_BUCKETS=0: never)
@@ -747,20 +851,14 @@ int unique_key_write(hmj_ctx* c, hmj::ProbeArgs& wa, bool slab, u32 nb, u32 np, 
     int sp = span_begin(c, K_PROBE_WRITE, -1);
     HIP_TRY(hmj::launch_probe_write_sorted(wa, slab, fk, shape, (u64*)c->lookback.p, c->wm->sorted_chained, low, c->num_cus, c->stream));
     span_end(c, sp);
-    HIP_TRY(hipMemcpyAsync(h, c->accum.p, 8 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    RC_TRY(read_accum(c, &h));
     if (h[hmj::ACC_ERR] & hmj::ERR_SLAB) {
       c->wm->slab_cooldown = 8;
       return kRetryNoSlab;
     }
     if (h[hmj::ACC_ERR] & hmj::ERR_PREFIX) return kRetryNoPrefix;
     if (!(h[hmj::ACC_ERR] & hmj::ERR_SORTED)) {
-      out->n_matches = h[hmj::ACC_N];
-      out->sum_r = h[hmj::ACC_SUM_R];
-      out->sum_s = h[hmj::ACC_SUM_S];
-      out->xor_fold = h[hmj::ACC_XOR];
-      out->mix_sum = h[hmj::ACC_MIX];
-      out->sum_probe_all = h[hmj::ACC_SUM_P];
+      result_sums(out, h);
       c->timing.bytes_probe_write = 16ull * ((u64)nb + np) + 24ull * out->n_matches;
       c->timing.path |= HMJ_PATH_UNIQ_WRITE | HMJ_PATH_SORTED_WRITE | (fk ? HMJ_PATH_SORTED_FK : 0u) | (half ? HMJ_PATH_SORTED_FK_HALF : 0u) |
                         (shape == 2 ? HMJ_PATH_SORTED_FK_WIDE : 0u);
@@ -774,11 +872,10 @@ int unique_key_write(hmj_ctx* c, hmj::ProbeArgs& wa, bool slab, u32 nb, u32 np, 
         // unmatched probe rows left gaps at the end of every partition's slots: the ordered epilogue closes them
         HIP_TRY(hmj::launch_scan_u64((const u64*)c->part_count.p, (u64*)c->part_out_off.p, P, c->stream));
         int retry = 0;
-        if ((rc = order_rows(c, nullptr, in_base32, in_base64, P, 1, low, out->n_matches, false, out->n_matches > 2ull * nb,
-                             &rk, &rr, &rs, &retry)) != HMJ_OK)
-          return rc;
+        RC_TRY(order_rows(c, nullptr, in_base32, in_base64, P, 1, low, out->n_matches, false, out->n_matches > 2ull * nb,
+                          &rk, &rr, &rs, &retry));
       }
-      return deliver(rk, rr, rs);
+      return deliver_columns(c, out, to_host, rk, rr, rs, (size_t)out->n_matches * 8, true);
     }
     // the partitions stay valid: repeating probe keys -> the foreign-key form; anything else (duplicate build keys,
     // clustered keys, a hot key, an oversized partition) -> the two-step form, and do not ask again for a while
@@ -818,8 +915,7 @@ int unique_key_write(hmj_ctx* c, hmj::ProbeArgs& wa, bool slab, u32 nb, u32 np, 
   sp = span_begin(c, K_OUT_SCAN, -1);
   HIP_TRY(hmj::launch_scan_u64((const u64*)c->part_count.p, (u64*)c->part_out_off.p, P, c->stream));
   span_end(c, sp);
-  HIP_TRY(hipMemcpyAsync(h, c->accum.p, 8 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  RC_TRY(read_accum(c, &h));
   if (h[hmj::ACC_ERR] & hmj::ERR_SLAB) {
     c->wm->slab_cooldown = 8;
     return kRetryNoSlab;
@@ -829,12 +925,7 @@ int unique_key_write(hmj_ctx* c, hmj::ProbeArgs& wa, bool slab, u32 nb, u32 np, 
     c->wm->uniq_cooldown = 8;
     return kRetryNoFastWrite;
   }
-  out->n_matches = h[hmj::ACC_N];
-  out->sum_r = h[hmj::ACC_SUM_R];
-  out->sum_s = h[hmj::ACC_SUM_S];
-  out->xor_fold = h[hmj::ACC_XOR];
-  out->mix_sum = h[hmj::ACC_MIX];
-  out->sum_probe_all = h[hmj::ACC_SUM_P];
+  result_sums(out, h);
   c->timing.bytes_probe_write = 16ull * ((u64)nb + np) + 24ull * out->n_matches;
   c->timing.path |= HMJ_PATH_UNIQ_WRITE;
   if (out->n_matches == 0) return HMJ_OK;
@@ -844,18 +935,16 @@ int unique_key_write(hmj_ctx* c, hmj::ProbeArgs& wa, bool slab, u32 nb, u32 np, 
   const u64 *rk = wa.out_key, *rr = wa.out_rval, *rs = wa.out_sval;
   if (!dense_out && ordered) {
     int retry = 0;
-    if ((rc = order_rows(c, nullptr, in_base32, in_base64, P, 1, low, out->n_matches, false, out->n_matches > 2ull * nb,
-                         &rk, &rr, &rs, &retry)) !=
-        HMJ_OK)
-      return rc;
+    RC_TRY(order_rows(c, nullptr, in_base32, in_base64, P, 1, low, out->n_matches, false, out->n_matches > 2ull * nb,
+                      &rk, &rr, &rs, &retry));
   } else if (!dense_out) {
     // an unordered result only has to lose the gaps unmatched probe rows left: every partition's rows move to the
     // partition's dense offset as they are.  (Until round 3 this went through the ordered epilogue, which also sorts:
     // a foreign-key join with fan-out 16 and a fifth of its probe rows unmatched took 16.4 ms instead of 2.)
     const size_t bytes = (size_t)out->n_matches * 8;
-    if ((rc = ensure_dev(c, c->ord_key, bytes)) != HMJ_OK) return rc;
-    if ((rc = ensure_dev(c, c->ord_rval, bytes)) != HMJ_OK) return rc;
-    if ((rc = ensure_dev(c, c->ord_sval, bytes)) != HMJ_OK) return rc;
+    RC_TRY(ensure_dev(c, c->ord_key, bytes));
+    RC_TRY(ensure_dev(c, c->ord_rval, bytes));
+    RC_TRY(ensure_dev(c, c->ord_sval, bytes));
     const int sp2 = span_begin(c, K_ORDER, -1);
     HIP_TRY(hmj::launch_compact((const u64*)c->part_out_off.p, in_base32, in_base64, P, rk, rr, rs, (u64*)c->ord_key.p,
                                 (u64*)c->ord_rval.p, (u64*)c->ord_sval.p, c->num_cus * 8, c->stream));
@@ -864,7 +953,7 @@ int unique_key_write(hmj_ctx* c, hmj::ProbeArgs& wa, bool slab, u32 nb, u32 np, 
     rr = (const u64*)c->ord_rval.p;
     rs = (const u64*)c->ord_sval.p;
   }
-  return deliver(rk, rr, rs);
+  return deliver_columns(c, out, to_host, rk, rr, rs, (size_t)out->n_matches * 8, true);
 }
 
 // ---- one attempt of the partitioned join = plan_join (key sample, radix bits, partition window, which kernels are on
@@ -888,7 +977,6 @@ struct JoinPlan {
 static int plan_join(hmj_ctx* c, const void* R, uint64_t n_build, const void* S, uint64_t n_probe, uint32_t flags,
                      bool allow_auto_prefix, bool allow_slab, bool allow_fast_write, bool allow_win_ordered, bool prefix_unsafe,
                      bool allow_slab_probe, JoinPlan* plan_out) {
-  int rc;
   const bool materialize = flags & HMJ_MATERIALIZE;
   const u32 nb = (u32)n_build, np = (u32)n_probe;
   const u32 np_plan = c->prepare_only ? (u32)c->probe_hint : np;  // probe size the plan is made for
@@ -904,8 +992,8 @@ static int plan_join(hmj_ctx* c, const void* R, uint64_t n_build, const void* S,
   bool prefix_exact = false;  // smp[0] / [4] / [5] come from a pass over ALL keys (the retry after a prefix violation)
   const bool have_sample = c->prefix_bits < 0 && allow_auto_prefix && B > 0 && (u64)nb + np > 0;
   if (have_sample) {
-    if ((rc = ensure_dev(c, c->offs64, 8 * sizeof(u64))) != HMJ_OK) return rc;
-    if ((rc = ensure_host(c, c->h_accum, 8 * sizeof(u64))) != HMJ_OK) return rc;
+    RC_TRY(ensure_dev(c, c->offs64, 8 * sizeof(u64)));
+    RC_TRY(ensure_host(c, c->h_accum, 8 * sizeof(u64)));
     HIP_TRY(hmj::launch_key_sample(R, nb, c->sample_build_only ? nullptr : S, c->sample_build_only ? 0u : np,
                                    (u64*)c->offs64.p, c->stream));
     HIP_TRY(hipMemcpyAsync(c->h_accum.p, c->offs64.p, 8 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
@@ -922,7 +1010,7 @@ static int plan_join(hmj_ctx* c, const void* R, uint64_t n_build, const void* S,
       //  now, or will have once its events fire: this IS the retry.  Its keys must be in the exact prefix, or an
       //  ordered join whose probe keys lie outside the build keys' prefix would fail a second time)
       for (hipEvent_t ev : c->arrive_ev)
-        if ((rc = wait_arrival(c, ev)) != HMJ_OK) return rc;
+        RC_TRY(wait_arrival(c, ev));
       const bool probe_readable = !c->sample_build_only || !c->arrive_ev.empty();
       u64* ex3 = (u64*)c->offs64.p;
       const u64 init[3] = {0, ~0ull, 0};
@@ -1187,7 +1275,6 @@ static int plan_join(hmj_ctx* c, const void* R, uint64_t n_build, const void* S,
   p.fast_write = fast_write;
   p.np_plan = np_plan;
   for (int i = 0; i < 4; i++) c->plan.pass_bits[i] = p.pass_bits[i];
-  (void)rc;
   return HMJ_OK;
 }
 
@@ -1202,7 +1289,6 @@ constexpr uint32_t kKindBuild = 3;
 // at the end of p's output, so the ordered epilogue sorts them with p's other rows.
 static int execute_kind_probe(hmj_ctx* c, hmj::ProbeArgs a, u32 nb, u32 np, uint32_t flags, hmj_result* out, bool to_host,
                               const u32* v_start, u32 P, u32 Q, u32 Pi, bool split, int low, bool win_ordered) {
-  int rc;
   const bool materialize = flags & HMJ_MATERIALIZE, first = flags & HMJ_FIRST_WINS;
   const int kind = (int)c->join_kind;
   const int bkind = kind > (int)kKindBuild ? kind - (int)kKindBuild : 0;  // HMJ_BUILD_*, 0 = a probe-side kind
@@ -1210,18 +1296,16 @@ static int execute_kind_probe(hmj_ctx* c, hmj::ProbeArgs a, u32 nb, u32 np, uint
   const u64 n_items = split ? Pi : (u64)P * Q;
   a.extra = (flags & (HMJ_CHECKSUM | HMJ_SUM_PROBE)) ? 1u : 0u;
   const size_t matched_bytes = ((size_t)np / 32 + 1) * 4;
-  if ((rc = ensure_dev(c, c->matched, matched_bytes)) != HMJ_OK) return rc;
-  a.matched = (u32*)c->matched.p;
-  HIP_TRY(hipMemsetAsync(c->matched.p, 0, matched_bytes, c->stream));
+  RC_TRY(clear_matched(c, np, &a.matched));
   u32* bmark = nullptr;
   u64* sweep_n = nullptr;
   hmj::ProbeArgs sw = a;  // the sweep's operands: a's, with the build bitmap as `matched`
   const u64 b_fill = b_semi_anti ? 0 : c->build_fill;  // sval of a swept row
   if (bkind) {
     const size_t bmark_bytes = ((size_t)nb / 32 + 1) * 4;
-    if ((rc = ensure_dev(c, c->bmatched, bmark_bytes)) != HMJ_OK) return rc;
-    if ((rc = ensure_dev(c, c->bsweep, ((size_t)P + 1) * 8)) != HMJ_OK) return rc;
-    if ((rc = ensure_host(c, c->h_accum, 9 * sizeof(u64))) != HMJ_OK) return rc;
+    RC_TRY(ensure_dev(c, c->bmatched, bmark_bytes));
+    RC_TRY(ensure_dev(c, c->bsweep, ((size_t)P + 1) * 8));
+    RC_TRY(ensure_host(c, c->h_accum, 9 * sizeof(u64)));
     bmark = (u32*)c->bmatched.p;
     sweep_n = (u64*)c->bsweep.p;
     HIP_TRY(hipMemsetAsync(bmark, 0, bmark_bytes, c->stream));  // (every attempt: a retry partitions anew)
@@ -1249,12 +1333,8 @@ static int execute_kind_probe(hmj_ctx* c, hmj::ProbeArgs a, u32 nb, u32 np, uint
   if (bkind) HIP_TRY(hipMemcpyAsync(h + 8, sweep_n, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (h[hmj::ACC_ERR] & hmj::ERR_PREFIX) return kRetryNoPrefix;
-  out->n_matches = h[hmj::ACC_N];
-  out->sum_r = h[hmj::ACC_SUM_R];
-  out->sum_s = h[hmj::ACC_SUM_S];
-  out->xor_fold = h[hmj::ACC_XOR];
-  out->mix_sum = h[hmj::ACC_MIX];
-  out->sum_probe_all = (flags & HMJ_SUM_PROBE) ? h[hmj::ACC_SUM_P] : 0;
+  result_sums(out, h);
+  if (!(flags & HMJ_SUM_PROBE)) out->sum_probe_all = 0;
   c->kind_unmatched = h[hmj::ACC_PAD];  // rows emitted with the fill: the unmatched probe rows (ANTI, OUTER)
   c->kind_build_swept = bkind ? h[8] : 0;
   if (!materialize || out->n_matches == 0) return HMJ_OK;
@@ -1263,9 +1343,9 @@ static int execute_kind_probe(hmj_ctx* c, hmj::ProbeArgs a, u32 nb, u32 np, uint
   const bool rval_col = kind == HMJ_JOIN_PROBE_OUTER || bkind || (flags & HMJ_ORDERED);
   const bool sval_col = !b_semi_anti || (flags & HMJ_ORDERED);
   const size_t bytes = (size_t)out->n_matches * 8;
-  if ((rc = ensure_dev(c, c->out_key, bytes)) != HMJ_OK) return rc;
-  if (rval_col && (rc = ensure_dev(c, c->out_rval, bytes)) != HMJ_OK) return rc;
-  if (sval_col && (rc = ensure_dev(c, c->out_sval, bytes)) != HMJ_OK) return rc;
+  RC_TRY(ensure_dev(c, c->out_key, bytes));
+  if (rval_col) RC_TRY(ensure_dev(c, c->out_rval, bytes));
+  if (sval_col) RC_TRY(ensure_dev(c, c->out_sval, bytes));
   a.out_key = (u64*)c->out_key.p;
   a.out_rval = rval_col ? (u64*)c->out_rval.p : nullptr;
   a.out_sval = sval_col ? (u64*)c->out_sval.p : nullptr;
@@ -1287,531 +1367,401 @@ static int execute_kind_probe(hmj_ctx* c, hmj::ProbeArgs a, u32 nb, u32 np, uint
   const u64 *rk = a.out_key, *rr = a.out_rval, *rs = a.out_sval;
   if (flags & HMJ_ORDERED) {
     int retry = 0;
-    if ((rc = order_rows(c, v_start, nullptr, nullptr, P, Q, low, out->n_matches, win_ordered, out->n_matches > 2ull * nb, &rk,
-                         &rr, &rs, &retry)) != HMJ_OK)
-      return rc;
+    RC_TRY(order_rows(c, v_start, nullptr, nullptr, P, Q, low, out->n_matches, win_ordered, out->n_matches > 2ull * nb, &rk,
+                      &rr, &rs, &retry));
     if (retry) return retry;
   }
   if (kind != HMJ_JOIN_PROBE_OUTER && !bkind) rr = nullptr;
   if (b_semi_anti) rs = nullptr;
-  if (to_host) {
-    if ((rc = ensure_host(c, c->h_key, bytes, false)) != HMJ_OK) return rc;
-    if (rr && (rc = ensure_host(c, c->h_rval, bytes, false)) != HMJ_OK) return rc;
-    if (rs && (rc = ensure_host(c, c->h_sval, bytes, false)) != HMJ_OK) return rc;
-    s = span_begin(c, K_D2H, -1);
-    HIP_TRY(hipMemcpyAsync(c->h_key.p, rk, bytes, hipMemcpyDeviceToHost, c->stream));
-    if (rr) HIP_TRY(hipMemcpyAsync(c->h_rval.p, rr, bytes, hipMemcpyDeviceToHost, c->stream));
-    if (rs) HIP_TRY(hipMemcpyAsync(c->h_sval.p, rs, bytes, hipMemcpyDeviceToHost, c->stream));
-    span_end(c, s);
-  }
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  out->key = to_host ? (const uint64_t*)c->h_key.p : (const uint64_t*)rk;
-  out->rval = rr ? (to_host ? (const uint64_t*)c->h_rval.p : (const uint64_t*)rr) : nullptr;
-  out->sval = rs ? (to_host ? (const uint64_t*)c->h_sval.p : (const uint64_t*)rs) : nullptr;
-  return HMJ_OK;
+  return deliver_columns(c, out, to_host, rk, rr, rs, bytes, true);
 }
 
-static int execute_join(hmj_ctx* c, const void* R, uint64_t n_build, const void* S, uint64_t n_probe, uint32_t flags,
-                        hmj_result* out, bool to_host, const JoinPlan& p) {
-  int rc;
-  const bool materialize = flags & HMJ_MATERIALIZE, first = flags & HMJ_FIRST_WINS;
-  const bool extra = flags & (HMJ_CHECKSUM | HMJ_SUM_PROBE);
-  const u32 nb = (u32)n_build, np = (u32)n_probe, np_plan = p.np_plan;
-  const bool allow_slab = p.allow_slab, allow_slab_probe = p.allow_slab_probe;
-  const int B = p.B, passes = p.passes, prefix = p.prefix, low = p.low;
+// One call of the join as the plan functions see it: the relations, the mode flags, where the result goes.
+struct JoinCall {
+  const void *R, *S;
+  u32 nb, np;
+  uint32_t flags;
+  hmj_result* out;
+  bool to_host;
+  bool materialize() const { return flags & HMJ_MATERIALIZE; }
+  bool first() const { return flags & HMJ_FIRST_WINS; }
+  bool extra() const { return flags & (HMJ_CHECKSUM | HMJ_SUM_PROBE); }
+  bool ordered() const { return (flags & HMJ_ORDERED) != 0; }
+};
+
+// execute_join tries the plans below in order.  A plan whose conditions do not hold says so with this code and has touched
+// nothing (run_slab_join: nothing but c->plan.refused); any other code -- HMJ_OK, an error, a kRetry* -- ends the attempt.
+constexpr int kPlanNotTaken = 1006;
+
+// ---- histogram-free slab path (plain count joins of large, evenly distributed relations; the unique-key write on top):
+// both relations through slab passes A and B, the probe kernels read the pass-B slabs.  Also the slab form of
+// hmj_prepare_build (build side only) and the join that reuses such a build side.
+static int run_slab_join(hmj_ctx* c, const JoinCall& j, const JoinPlan& p) {
+  const bool materialize = j.materialize(), first = j.first(), extra = j.extra();
+  const u32 nb = j.nb, np = j.np, np_plan = p.np_plan, P = p.P;
   const int* pass_bits = p.pass_bits;
-  const bool fk_wide_plan = p.fk_wide_plan, asc_r = p.asc_r, asc_s = p.asc_s, win_ordered = p.win_ordered, hot_hint = p.hot_hint;
-  const bool verify_pfx = p.verify_pfx, probe_fits = p.probe_fits, fast_write = p.fast_write;
-  const double dense_scale = p.dense_scale;
-  const u32 P = p.P, Q = p.Q;
-  const u64 items = p.items, pfx_ref = p.pfx_ref;
-  if ((rc = ensure_dev(c, c->r_off, ((size_t)P + 1) * 4)) != HMJ_OK) return rc;
-  if ((rc = ensure_dev(c, c->s_off, ((size_t)P + 1) * 4)) != HMJ_OK) return rc;
-  if ((rc = ensure_dev(c, c->accum, 8 * sizeof(u64))) != HMJ_OK) return rc;
-  if ((rc = ensure_host(c, c->h_accum, 8 * sizeof(u64))) != HMJ_OK) return rc;
-  if (materialize) {
-    if ((rc = ensure_dev(c, c->part_count, (size_t)items * 8)) != HMJ_OK) return rc;
-    if ((rc = ensure_dev(c, c->part_out_off, ((size_t)items + 1) * 8)) != HMJ_OK) return rc;
-  }
-  HIP_TRY(hipMemsetAsync(c->accum.p, 0, 8 * sizeof(u64), c->stream));
-  const void *Rp, *Sp;
-  // ---- histogram-free slab path (plain count joins of large, evenly distributed relations)
   hmj::SlabGeom gr, gs;
-  if (allow_slab && c->slab_mode && c->wm->slab_cooldown == 0 && !c->prepare_only && !(c->timing.path & HMJ_PATH_SLAB) &&
-      !((!materialize || fast_write) && Q == 1 && probe_fits && passes == 2 && pass_bits[0] <= hmj::SLAB_MAX_BITS &&
-        pass_bits[1] <= hmj::SLAB_MAX_BITS && dense_scale <= 2.5))
+  if (p.allow_slab && c->slab_mode && c->wm->slab_cooldown == 0 && !c->prepare_only && !(c->timing.path & HMJ_PATH_SLAB) &&
+      !((!materialize || p.fast_write) && p.Q == 1 && p.probe_fits && p.passes == 2 && pass_bits[0] <= hmj::SLAB_MAX_BITS &&
+        pass_bits[1] <= hmj::SLAB_MAX_BITS && p.dense_scale <= 2.5))
     c->plan.refused |= HMJ_REFUSED_SLAB_SHAPE;
-  if (allow_slab && c->slab_mode && c->wm->slab_cooldown == 0 && (!materialize || fast_write) && Q == 1 &&
-      probe_fits &&
-      passes == 2 && pass_bits[0] <= hmj::SLAB_MAX_BITS && pass_bits[1] <= hmj::SLAB_MAX_BITS &&
-      slab_sizes_ok(c, nb, np_plan, materialize || np_plan < nb) &&
-      dense_scale <= 2.5 &&  // (beyond: slabs of several times the relation's size; the exact path needs none)
-      hmj::slab_geometry(nb, pass_bits[0], pass_bits[1], &gr, 0, 1.0, dense_scale) &&
-      hmj::slab_geometry(np_plan, pass_bits[0], pass_bits[1], &gs, 0,
-                         (nb && np_plan > nb) ? (double)np_plan / (double)nb : 1.0, dense_scale)) {
-    // (a foreign-key probe side repeats every key np / nb times: the rows of a slab piece then vary sqrt(np / nb) times
-    //  more, and the slabs are sized for that.  Until round 3 only the wide ordered plan passed the fan-out; count joins
-    //  such as 2^22 x 2^26 overflowed a slab at their first attempt, started over with probe-side slabs only (2.2 ms
-    //  against 1.4 ms) and tried again every ninth join.)
-    const bool reuse = c->prep.valid && c->prep.slab && c->prep.ptr == R && c->prep.n == nb &&
-                       c->prep.low == low && c->prep.B == B;
-    c->prep.valid = false;  // one-shot; slab_br is about to be (re)written unless reused
-    c->timing.path |= HMJ_PATH_SLAB | (reuse ? HMJ_PATH_PREPARED : 0u);
-    c->timing.n_probe_items = P;
-    const int ba = pass_bits[0], bb = pass_bits[1];
-    const u64 rows_a = gr.rows_a > gs.rows_a ? gr.rows_a : gs.rows_a;
-    const u32 wa = gr.WA > gs.WA ? gr.WA : gs.WA;
-    if ((rc = ensure_dev(c, c->slab_a, rows_a * 16)) != HMJ_OK) return rc;
-    if ((rc = ensure_dev(c, c->cnt_a, ((size_t)wa << ba) * 4)) != HMJ_OK) return rc;
-    if ((rc = ensure_dev(c, c->slab_br, gr.rows_b * 16)) != HMJ_OK) return rc;
-    if ((rc = ensure_dev(c, c->slab_bs, gs.rows_b * 16)) != HMJ_OK) return rc;
-    if ((rc = ensure_dev(c, c->cnt_br, (size_t)P * gr.KB * 4)) != HMJ_OK) return rc;
-    if ((rc = ensure_dev(c, c->cnt_bs, (size_t)P * gs.KB * 4)) != HMJ_OK) return rc;
-    u64* acc = (u64*)c->accum.p;
-    struct { const void* in; u32 n; const hmj::SlabGeom* g; DevBuf* sb; DevBuf* cb; int rel; } side[2] = {
-        {R, nb, &gr, &c->slab_br, &c->cnt_br, 0}, {S, np, &gs, &c->slab_bs, &c->cnt_bs, 1}};
-    const u64 a_rows = c->slab_a.cap / 16, a_cnt = c->cnt_a.cap / 4;  // what is allocated: the launchers check it
-    for (auto& sd : side) {
-      if (sd.rel == 0 && reuse) continue;            // build side already in slab_br / cnt_br
-      if (sd.rel == 1 && c->prepare_only) continue;  // hmj_prepare_build: build side only
-      int sp = span_begin(c, K_SCATTER, sd.rel);
-      if (sd.rel == 1 && !c->arrive_ev.empty()) {
-        // the probe rows are still arriving over the links (exchange.hip): pass-A workers own contiguous input
-        // ranges, so the workers whose rows are complete start after each round's event
-        u32 w_done = 0;
-        for (size_t i = 0; i < c->arrive_ev.size(); i++) {
-          if ((rc = wait_arrival(c, c->arrive_ev[i])) != HMJ_OK) return rc;
-          const bool last = i + 1 == c->arrive_ev.size();
-          const u32 w_end = last ? sd.g->WA : (u32)std::min<u64>(sd.g->WA, c->arrive_rows[i] / sd.g->rpw);
-          if (w_end > w_done) {
-            HIP_TRY(hmj::launch_slab_a(sd.in, sd.n, low, ba, *sd.g, c->slab_a.p, a_rows, (u32*)c->cnt_a.p, a_cnt, acc, c->stream, w_done, w_end));
-            w_done = w_end;
-          }
-        }
-      } else {
-        HIP_TRY(hmj::launch_slab_a(sd.in, sd.n, low, ba, *sd.g, c->slab_a.p, a_rows, (u32*)c->cnt_a.p, a_cnt, acc, c->stream));
-      }
-      span_end(c, sp);
-      sp = span_begin(c, K_SCATTER, sd.rel, 1);
-      HIP_TRY(hmj::launch_slab_b(c->slab_a.p, (const u32*)c->cnt_a.p, ba, low + ba, bb, *sd.g, sd.sb->p, sd.sb->cap / 16,
-                                 (u32*)sd.cb->p, sd.cb->cap / 4, acc, c->stream));
-      span_end(c, sp);
-      c->timing.bytes_scatter += 2 * 32ull * sd.n;
-    }
-    u64* hh = (u64*)c->h_accum.p;
-    if (c->prepare_only) {
-      HIP_TRY(hipMemcpyAsync(hh, c->accum.p, 8 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      if (hh[hmj::ACC_ERR] & hmj::ERR_SLAB) {
-        c->wm->slab_cooldown = 8;
-        return kRetryNoSlab;
-      }
-      c->prep.valid = true;
-      c->prep.slab = true;
-      c->prep.ptr = R;
-      c->prep.n = nb;
-      c->prep.low = low;
-      c->prep.B = B;
-      return HMJ_OK;
-    }
-    if (fast_write) {
-      hmj::ProbeArgs wa;
-      std::memset(&wa, 0, sizeof(wa));
-      wa.R = c->slab_br.p;
-      wa.S = c->slab_bs.p;
-      wa.r_cnt = (const u32*)c->cnt_br.p;
-      wa.s_cnt = (const u32*)c->cnt_bs.p;
-      wa.r_cap = gr.CB;
-      wa.s_cap = gs.CB;
-      wa.r_cnt_n = c->cnt_br.cap / 4;
-      wa.s_cnt_n = c->cnt_bs.cap / 4;
-      wa.r_rows = c->slab_br.cap / 16;
-      wa.s_rows = c->slab_bs.cap / 16;
-      wa.P = P;
-      wa.Q = 1;
-      wa.accum = acc;
-      return unique_key_write(c, wa, true, nb, np, low, extra, verify_pfx ? prefix : 0, pfx_ref,
-                                  (flags & HMJ_ORDERED) != 0, to_host, fk_wide_plan, dense_scale, out);
-    }
-    hmj::ProbeArgs sa;
-    std::memset(&sa, 0, sizeof(sa));
-    sa.R = c->slab_br.p;
-    sa.S = c->slab_bs.p;
-    sa.r_cnt = (const u32*)c->cnt_br.p;
-    sa.s_cnt = (const u32*)c->cnt_bs.p;
-    sa.r_cap = gr.CB;
-    sa.s_cap = gs.CB;
-    sa.r_cnt_n = c->cnt_br.cap / 4;
-    sa.s_cnt_n = c->cnt_bs.cap / 4;
-    sa.r_rows = c->slab_br.cap / 16;
-    sa.s_rows = c->slab_bs.cap / 16;
-    sa.P = P;
-    sa.Q = 1;
-    sa.accum = acc;
-#ifdef HMJ_DEV
-    sa.debug = c->dev_ablate;
-#endif
-    int sp = span_begin(c, K_PROBE_COUNT, -1);
-    if (first || extra) {
-      sa.extra = (extra ? 1u : 0u) | (first ? 2u : 0u);
-      HIP_TRY(hmj::launch_probe_count_ext(sa, nullptr, nullptr, true, c->num_cus, c->stream));
-    } else {
-      HIP_TRY(hmj::launch_probe_count_slab(sa, c->num_cus, c->stream));
-    }
-    span_end(c, sp);
-    c->timing.bytes_probe_count = 16ull * ((u64)nb + np);
-    HIP_TRY(hipMemcpyAsync(hh, c->accum.p, 8 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (hh[hmj::ACC_ERR] & hmj::ERR_SLAB) {  // skewed digits: remember, and take the exact path
+  if (!(p.allow_slab && c->slab_mode && c->wm->slab_cooldown == 0 && (!materialize || p.fast_write) && p.Q == 1 &&
+        p.probe_fits &&
+        p.passes == 2 && pass_bits[0] <= hmj::SLAB_MAX_BITS && pass_bits[1] <= hmj::SLAB_MAX_BITS &&
+        slab_sizes_ok(c, nb, np_plan, materialize || np_plan < nb) &&
+        p.dense_scale <= 2.5 &&  // (beyond: slabs of several times the relation's size; the exact path needs none)
+        hmj::slab_geometry(nb, pass_bits[0], pass_bits[1], &gr, 0, 1.0, p.dense_scale) &&
+        hmj::slab_geometry(np_plan, pass_bits[0], pass_bits[1], &gs, 0,
+                           (nb && np_plan > nb) ? (double)np_plan / (double)nb : 1.0, p.dense_scale)))
+    return kPlanNotTaken;
+  // (a foreign-key probe side repeats every key np / nb times: the rows of a slab piece then vary sqrt(np / nb) times
+  //  more, and the slabs are sized for that.  Until round 3 only the wide ordered plan passed the fan-out; count joins
+  //  such as 2^22 x 2^26 overflowed a slab at their first attempt, started over with probe-side slabs only (2.2 ms
+  //  against 1.4 ms) and tried again every ninth join.)
+  const bool reuse = c->prep.valid && c->prep.slab && c->prep.ptr == j.R && c->prep.n == nb &&
+                     c->prep.low == p.low && c->prep.B == p.B;
+  c->prep.valid = false;  // one-shot; slab_br is about to be (re)written unless reused
+  c->timing.path |= HMJ_PATH_SLAB | (reuse ? HMJ_PATH_PREPARED : 0u);
+  c->timing.n_probe_items = P;
+  const int ba = pass_bits[0], bb = pass_bits[1];
+  const u64 rows_a = gr.rows_a > gs.rows_a ? gr.rows_a : gs.rows_a;
+  const u32 wa = gr.WA > gs.WA ? gr.WA : gs.WA;
+  RC_TRY(ensure_dev(c, c->slab_a, rows_a * 16));
+  RC_TRY(ensure_dev(c, c->cnt_a, ((size_t)wa << ba) * 4));
+  RC_TRY(ensure_dev(c, c->slab_br, gr.rows_b * 16));
+  RC_TRY(ensure_dev(c, c->slab_bs, gs.rows_b * 16));
+  RC_TRY(ensure_dev(c, c->cnt_br, (size_t)P * gr.KB * 4));
+  RC_TRY(ensure_dev(c, c->cnt_bs, (size_t)P * gs.KB * 4));
+  // (a reused build side is already in slab_br / cnt_br; hmj_prepare_build partitions the build side only)
+  if (!reuse) RC_TRY(slab_passes(c, j.R, nb, 0, p.low, ba, bb, gr, c->slab_br, c->cnt_br, false));
+  if (!c->prepare_only) RC_TRY(slab_passes(c, j.S, np, 1, p.low, ba, bb, gs, c->slab_bs, c->cnt_bs, !c->arrive_ev.empty()));
+  u64* hh;
+  if (c->prepare_only) {
+    RC_TRY(read_accum(c, &hh));
+    if (hh[hmj::ACC_ERR] & hmj::ERR_SLAB) {
       c->wm->slab_cooldown = 8;
       return kRetryNoSlab;
     }
-    out->n_matches = hh[hmj::ACC_N];
-    out->sum_r = hh[hmj::ACC_SUM_R];
-    out->sum_s = hh[hmj::ACC_SUM_S];
-    out->xor_fold = hh[hmj::ACC_XOR];
-    out->mix_sum = hh[hmj::ACC_MIX];
-    out->sum_probe_all = hh[hmj::ACC_SUM_P];
+    c->prep.valid = true;
+    c->prep.slab = true;
+    c->prep.ptr = j.R;
+    c->prep.n = nb;
+    c->prep.low = p.low;
+    c->prep.B = p.B;
     return HMJ_OK;
   }
+  hmj::ProbeArgs sa = slab_probe_args(c, &gr, nullptr, c->slab_bs, c->cnt_bs, gs.CB, P, 1);
+  if (p.fast_write)
+    return unique_key_write(c, sa, true, nb, np, p.low, extra, p.verify_pfx ? p.prefix : 0, p.pfx_ref, j.ordered(), j.to_host,
+                            p.fk_wide_plan, p.dense_scale, j.out);
+#ifdef HMJ_DEV
+  sa.debug = c->dev_ablate;
+#endif
+  int sp = span_begin(c, K_PROBE_COUNT, -1);
+  if (first || extra) {
+    sa.extra = (extra ? 1u : 0u) | (first ? 2u : 0u);
+    HIP_TRY(hmj::launch_probe_count_ext(sa, nullptr, nullptr, true, c->num_cus, c->stream));
+  } else {
+    HIP_TRY(hmj::launch_probe_count_slab(sa, c->num_cus, c->stream));
+  }
+  span_end(c, sp);
+  c->timing.bytes_probe_count = 16ull * ((u64)nb + np);
+  RC_TRY(read_accum(c, &hh));
+  if (hh[hmj::ACC_ERR] & hmj::ERR_SLAB) {  // skewed digits: remember, and take the exact path
+    c->wm->slab_cooldown = 8;
+    return kRetryNoSlab;
+  }
+  result_sums(j.out, hh);
+  return HMJ_OK;
+}
 
-  const bool reuse_exact = c->prep.valid && !c->prep.slab && c->prep.ptr == R && c->prep.n == nb &&
-                           c->prep.low == low && c->prep.B == B;
+// ---- the exact build side: the build rows through histogram / scan / scatter passes (or where a prepared build side left
+// them) and their partition offsets in c->r_off.  *Rp = the partitioned rows.  Under hmj_prepare_build (c->prepare_only) this
+// is all there is: the prepared state is recorded and the caller returns.
+static int partition_build_exact(hmj_ctx* c, const JoinCall& j, const JoinPlan& p, const void** Rp) {
+  const bool reuse_exact = c->prep.valid && !c->prep.slab && c->prep.ptr == j.R && c->prep.n == j.nb &&
+                           c->prep.low == p.low && c->prep.B == p.B;
   c->prep.valid = false;  // one-shot; rbuf / r_off are about to be (re)written unless reused
   c->timing.path |= HMJ_PATH_EXACT | (reuse_exact ? HMJ_PATH_PREPARED : 0u);
-  int s;
   if (reuse_exact) {
-    Rp = c->prep.Rp;
+    *Rp = c->prep.Rp;
   } else {
-    if ((rc = partition_relation(c, R, nb, c->rbuf, low, passes, pass_bits, 0, &Rp, asc_r)) != HMJ_OK) return rc;
-    s = span_begin(c, K_OFFSETS, -1);
-    HIP_TRY(hmj::launch_part_offsets(Rp, nb, low, B, (u32*)c->r_off.p, c->stream));
+    RC_TRY(partition_relation(c, j.R, j.nb, c->rbuf, p.low, p.passes, p.pass_bits, 0, Rp, p.asc_r));
+    const int s = span_begin(c, K_OFFSETS, -1);
+    HIP_TRY(hmj::launch_part_offsets(*Rp, j.nb, p.low, p.B, (u32*)c->r_off.p, c->stream));
     span_end(c, s);
   }
   if (c->prepare_only) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->prep.valid = true;
     c->prep.slab = false;
-    c->prep.ptr = R;
-    c->prep.Rp = Rp;
-    c->prep.n = nb;
-    c->prep.low = low;
-    c->prep.B = B;
-    return HMJ_OK;
+    c->prep.ptr = j.R;
+    c->prep.Rp = *Rp;
+    c->prep.n = j.nb;
+    c->prep.low = p.low;
+    c->prep.B = p.B;
   }
-  for (hipEvent_t ev : c->arrive_ev)
-    if ((rc = wait_arrival(c, ev)) != HMJ_OK) return rc;  // probe rows still on the links
-  // ---- probe-heavy count joins (BASELINE configs[4]: 2^24 build rows, 2^30 probe rows): the build side is
-  // small and was partitioned exactly above; the probe side -- almost all of the bytes -- takes the
-  // histogram-free slab partitioning (32 instead of 48 B per row and pass) and the generic kernel reads a
-  // partition's KB slab pieces as its KB probe slices.  Skewed probe keys overflow a slab: exact path.
-  {
-    hmj::SlabGeom gp;
-    // 2^bits_a * KB >= 512 pass-B workers (HMJ_SLAB_PROBE_KB: any piece count, for the bounds regression tests)
-    const u32 kb = c->slab_probe_kb ? c->slab_probe_kb : (pass_bits[0] < 7 ? (512u >> pass_bits[0]) : 4u);
-    if (allow_slab_probe && c->slab_mode && c->wm->slab_probe_cooldown == 0 && !materialize && !probe_fits && Q == 1 && passes == 2 &&
-        pass_bits[0] <= hmj::SLAB_MAX_BITS && pass_bits[1] <= hmj::SLAB_MAX_BITS && np >= c->slab_min_rows && (u64)np >= 4ull * nb &&
-        hmj::slab_geometry(np, pass_bits[0], pass_bits[1], &gp, kb, (double)np / (double)(nb ? nb : 1))) {  // (a foreign-key
-      // probe side repeats every key np / nb times: the slabs are sized for that spread)
-      const int ba = pass_bits[0], bb = pass_bits[1];
-      if ((rc = ensure_dev(c, c->slab_a, gp.rows_a * 16)) != HMJ_OK) return rc;
-      if ((rc = ensure_dev(c, c->cnt_a, ((size_t)gp.WA << ba) * 4)) != HMJ_OK) return rc;
-      if ((rc = ensure_dev(c, c->slab_bs, gp.rows_b * 16)) != HMJ_OK) return rc;
-      if ((rc = ensure_dev(c, c->cnt_bs, (size_t)P * kb * 4)) != HMJ_OK) return rc;
-      u64* acc = (u64*)c->accum.p;
-      int sp = span_begin(c, K_SCATTER, 1, 0);
-      HIP_TRY(hmj::launch_slab_a(S, np, low, ba, gp, c->slab_a.p, c->slab_a.cap / 16, (u32*)c->cnt_a.p, c->cnt_a.cap / 4, acc, c->stream));
-      span_end(c, sp);
-      sp = span_begin(c, K_SCATTER, 1, 1);
-      HIP_TRY(hmj::launch_slab_b(c->slab_a.p, (const u32*)c->cnt_a.p, ba, low + ba, bb, gp, c->slab_bs.p, c->slab_bs.cap / 16,
-                                 (u32*)c->cnt_bs.p, c->cnt_bs.cap / 4, acc, c->stream));
-      span_end(c, sp);
-      c->timing.bytes_scatter += 2 * 32ull * np;
-      c->timing.path |= HMJ_PATH_SLAB_PROBE;
-      hmj::ProbeArgs a;
-      std::memset(&a, 0, sizeof(a));
-      a.R = Rp;
-      a.r_off = (const u32*)c->r_off.p;
-      a.S = c->slab_bs.p;
-      a.s_cnt = (const u32*)c->cnt_bs.p;
-      a.s_cap = gp.CB;
-      a.s_cnt_n = c->cnt_bs.cap / 4;
-      a.s_rows = c->slab_bs.cap / 16;
-      a.P = P;
-      a.Q = kb;
-      a.accum = acc;
-      c->timing.n_probe_items = P * kb;
-      if (first) {  // one bit per probe row SLOT of the slab layout
-        const size_t mb = ((size_t)gp.rows_b / 32 + 1) * 4;
-        if ((rc = ensure_dev(c, c->matched, mb)) != HMJ_OK) return rc;
-        a.matched = (u32*)c->matched.p;
-        HIP_TRY(hipMemsetAsync(c->matched.p, 0, mb, c->stream));
-      }
-      sp = span_begin(c, K_PROBE_COUNT, -1);
-      HIP_TRY(hmj::launch_probe(a, 0, first, extra, hmj::probe_default_grid(c->num_cus), c->stream));
-      span_end(c, sp);
-      c->timing.bytes_probe_count = 16ull * ((u64)nb + np);
-      u64* hh = (u64*)c->h_accum.p;
-      HIP_TRY(hipMemcpyAsync(hh, c->accum.p, 8 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      if (hh[hmj::ACC_ERR] & hmj::ERR_SLAB) {  // a probe slab overflowed (skewed probe keys)
-        c->wm->slab_probe_cooldown = 8;
-        return kRetryNoSlabProbe;
-      }
-      out->n_matches = hh[hmj::ACC_N];
-      out->sum_r = hh[hmj::ACC_SUM_R];
-      out->sum_s = hh[hmj::ACC_SUM_S];
-      out->xor_fold = hh[hmj::ACC_XOR];
-      out->mix_sum = hh[hmj::ACC_MIX];
-      out->sum_probe_all = hh[hmj::ACC_SUM_P];
-      return HMJ_OK;
-    }
-  }
-  // ---- count joins of a mid-size build side (2^18 ... 2^20 rows: ONE radix pass, too big for the global table of
-  // gtable.hip) with a probe side several times larger -- a dimension table under a fact table.  The exact path costs the
-  // probe side 16 (histogram) + 32 (scatter) + 16 (probe) bytes per row.  Here its one pass is the histogram-free slab
-  // pass A (32 B), and the generic kernel reads a partition straight out of the pass's worker-private slabs: partition p =
-  // the WA pieces [p][0 .. WA), an item = (partition, a run of pieces), a wave per piece.  48 instead of 64 B per row.
-  if (allow_slab_probe && c->slab_mode && c->one_pass_slab && c->wm->slab_probe_cooldown == 0 && !(flags & HMJ_ORDERED) &&
-      (!materialize || c->wm->one_pass_write_cooldown == 0) && passes == 1 &&
-      B >= 5 && B <= hmj::SLAB_MAX_BITS && np >= (1u << 22) && (u64)np >= 8ull * nb && nb > 0) {
-    hmj::SlabGeom g1;
-    if (hmj::slab_geometry_one_pass(np, B, dense_scale * (double)nb / (double)P, 512, &g1)) {
-      if ((rc = ensure_dev(c, c->slab_a, g1.rows_a * 16)) != HMJ_OK) return rc;
-      if ((rc = ensure_dev(c, c->cnt_a, ((size_t)g1.WA << B) * 4)) != HMJ_OK) return rc;
-      u64* acc = (u64*)c->accum.p;
-      int sp = span_begin(c, K_SCATTER, 1, 0);
-      HIP_TRY(hmj::launch_slab_a(S, np, low, B, g1, c->slab_a.p, c->slab_a.cap / 16, (u32*)c->cnt_a.p, c->cnt_a.cap / 4, acc, c->stream));
-      span_end(c, sp);
-      c->timing.bytes_scatter += 32ull * np;
-      c->timing.path |= HMJ_PATH_SLAB_PROBE | HMJ_PATH_SLAB_ONE_PASS;
-      // items: about eight per CU; an item walks ppi of its partition's WA pieces
-      u32 qi = 2048u / P;
-      if (qi < 1) qi = 1;
-      if (qi > g1.WA / 16) qi = g1.WA / 16;  // (a wave per piece, 16 waves per workgroup: an item of fewer pieces idles some)
-      if (qi < 1) qi = 1;
-      const u32 ppi = (g1.WA + qi - 1) / qi;
-      qi = (g1.WA + ppi - 1) / ppi;
-      hmj::ProbeArgs a;
-      std::memset(&a, 0, sizeof(a));
-      a.R = Rp;
-      a.r_off = (const u32*)c->r_off.p;
-      a.S = c->slab_a.p;
-      a.s_cnt = (const u32*)c->cnt_a.p;
-      a.s_cap = g1.CA;
-      a.s_wa = g1.WA;
-      a.s_ppi = ppi;
-      a.s_cnt_n = c->cnt_a.cap / 4;
-      a.s_rows = c->slab_a.cap / 16;
-      a.P = P;
-      a.Q = qi;
-      a.accum = acc;
-      c->timing.n_probe_items = P * qi;
-      if (first) {  // one bit per probe row SLOT of the slab buffer (used where a build partition needs several tables)
-        const size_t mb = ((size_t)g1.rows_a / 32 + 1) * 4;
-        if ((rc = ensure_dev(c, c->matched, mb)) != HMJ_OK) return rc;
-        a.matched = (u32*)c->matched.p;
-        HIP_TRY(hipMemsetAsync(c->matched.p, 0, mb, c->stream));
-      }
-      if (materialize) {
-        // unordered rows: counted AND written in the same walk, behind one output cursor (probe_kernel<3>); the columns hold
-        // one row per probe row -- more (duplicate build keys: a probe row expands) raises ERR_FASTPATH, and the
-        // count / scan / write passes run instead
-        const size_t bytes = (size_t)np * 8;
-        if ((rc = ensure_dev(c, c->out_key, bytes)) != HMJ_OK) return rc;
-        if ((rc = ensure_dev(c, c->out_rval, bytes)) != HMJ_OK) return rc;
-        if ((rc = ensure_dev(c, c->out_sval, bytes)) != HMJ_OK) return rc;
-        a.out_key = (u64*)c->out_key.p;
-        a.out_rval = (u64*)c->out_rval.p;
-        a.out_sval = (u64*)c->out_sval.p;
-        a.out_cap = np;
-      }
-      sp = span_begin(c, materialize ? K_PROBE_WRITE : K_PROBE_COUNT, -1);
-      HIP_TRY(hmj::launch_probe(a, materialize ? 3 : 0, first, extra, hmj::probe_default_grid(c->num_cus) * 2, c->stream));
-      span_end(c, sp);
-      if (materialize)
-        c->timing.bytes_probe_write = 16ull * ((u64)nb + np);
-      else
-        c->timing.bytes_probe_count = 16ull * ((u64)nb + np);
-      u64* hh = (u64*)c->h_accum.p;
-      HIP_TRY(hipMemcpyAsync(hh, c->accum.p, 8 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      if (hh[hmj::ACC_ERR] & hmj::ERR_SLAB) {  // a slab overflowed (skewed probe keys): the exact path, and not again for a while
-        c->wm->slab_probe_cooldown = 8;
-        return kRetryNoSlabProbe;
-      }
-      if (hh[hmj::ACC_ERR] & hmj::ERR_FASTPATH) {  // more result rows than probe rows: the general materialising passes
-        c->wm->one_pass_write_cooldown = 8;
-        return kRetryNoSlabProbe;
-      }
-      out->n_matches = hh[hmj::ACC_N];
-      out->sum_r = hh[hmj::ACC_SUM_R];
-      out->sum_s = hh[hmj::ACC_SUM_S];
-      out->xor_fold = hh[hmj::ACC_XOR];
-      out->mix_sum = hh[hmj::ACC_MIX];
-      out->sum_probe_all = hh[hmj::ACC_SUM_P];
-      if (materialize && out->n_matches) {
-        c->timing.bytes_probe_write += 24ull * out->n_matches;
-        const size_t bytes = (size_t)out->n_matches * 8;
-        if (to_host) {
-          if ((rc = ensure_host(c, c->h_key, bytes, false)) != HMJ_OK) return rc;
-          if ((rc = ensure_host(c, c->h_rval, bytes, false)) != HMJ_OK) return rc;
-          if ((rc = ensure_host(c, c->h_sval, bytes, false)) != HMJ_OK) return rc;
-          const int s2 = span_begin(c, K_D2H, -1);
-          HIP_TRY(hipMemcpyAsync(c->h_key.p, c->out_key.p, bytes, hipMemcpyDeviceToHost, c->stream));
-          HIP_TRY(hipMemcpyAsync(c->h_rval.p, c->out_rval.p, bytes, hipMemcpyDeviceToHost, c->stream));
-          HIP_TRY(hipMemcpyAsync(c->h_sval.p, c->out_sval.p, bytes, hipMemcpyDeviceToHost, c->stream));
-          span_end(c, s2);
-          HIP_TRY(hipStreamSynchronize(c->stream));
-        }
-        out->key = (const uint64_t*)(to_host ? c->h_key.p : c->out_key.p);
-        out->rval = (const uint64_t*)(to_host ? c->h_rval.p : c->out_rval.p);
-        out->sval = (const uint64_t*)(to_host ? c->h_sval.p : c->out_sval.p);
-      }
-      return HMJ_OK;
-    }
-  }
-  if ((rc = partition_relation(c, S, np, c->sbuf, low, passes, pass_bits, 1, &Sp, asc_s)) != HMJ_OK) return rc;
-  s = span_begin(c, K_OFFSETS, -1);
-  HIP_TRY(hmj::launch_part_offsets(Sp, np, low, B, (u32*)c->s_off.p, c->stream));
-  span_end(c, s);
+  return HMJ_OK;
+}
 
-  // Skewed probe side (a hot foreign key): partitions with far more probe rows than the rest are cut into
-  // virtual partitions so that no single workgroup is left with millions of rows (probe.hip,
-  // split_*_kernel).  Pi = number of (virtual) partitions the probe kernels iterate over.
-  u32 Pi = P;
-  const u32 *v_start = nullptr, *vr_beg = nullptr, *vr_end = nullptr, *vs_beg = nullptr, *vs_end = nullptr;
+// ---- probe-heavy count joins (BASELINE configs[4]: 2^24 build rows, 2^30 probe rows): the build side is
+// small and was partitioned exactly (Rp); the probe side -- almost all of the bytes -- takes the
+// histogram-free slab partitioning (32 instead of 48 B per row and pass) and the generic kernel reads a
+// partition's KB slab pieces as its KB probe slices.  Skewed probe keys overflow a slab: exact path.
+static int run_probe_slab_join(hmj_ctx* c, const JoinCall& j, const JoinPlan& p, const void* Rp) {
+  const bool materialize = j.materialize(), first = j.first(), extra = j.extra();
+  const u32 nb = j.nb, np = j.np, P = p.P;
+  const int* pass_bits = p.pass_bits;
+  hmj::SlabGeom gp;
+  // 2^bits_a * KB >= 512 pass-B workers (HMJ_SLAB_PROBE_KB: any piece count, for the bounds regression tests)
+  const u32 kb = c->slab_probe_kb ? c->slab_probe_kb : (pass_bits[0] < 7 ? (512u >> pass_bits[0]) : 4u);
+  if (!(p.allow_slab_probe && c->slab_mode && c->wm->slab_probe_cooldown == 0 && !materialize && !p.probe_fits && p.Q == 1 && p.passes == 2 &&
+        pass_bits[0] <= hmj::SLAB_MAX_BITS && pass_bits[1] <= hmj::SLAB_MAX_BITS && np >= c->slab_min_rows && (u64)np >= 4ull * nb &&
+        hmj::slab_geometry(np, pass_bits[0], pass_bits[1], &gp, kb, (double)np / (double)(nb ? nb : 1))))  // (a foreign-key
+    // probe side repeats every key np / nb times: the slabs are sized for that spread)
+    return kPlanNotTaken;
+  const int ba = pass_bits[0], bb = pass_bits[1];
+  RC_TRY(ensure_dev(c, c->slab_a, gp.rows_a * 16));
+  RC_TRY(ensure_dev(c, c->cnt_a, ((size_t)gp.WA << ba) * 4));
+  RC_TRY(ensure_dev(c, c->slab_bs, gp.rows_b * 16));
+  RC_TRY(ensure_dev(c, c->cnt_bs, (size_t)P * kb * 4));
+  RC_TRY(slab_passes(c, j.S, np, 1, p.low, ba, bb, gp, c->slab_bs, c->cnt_bs, false));  // (the probe rows have all arrived)
+  c->timing.path |= HMJ_PATH_SLAB_PROBE;
+  hmj::ProbeArgs a = slab_probe_args(c, nullptr, Rp, c->slab_bs, c->cnt_bs, gp.CB, P, kb);
+  c->timing.n_probe_items = P * kb;
+  if (first) RC_TRY(clear_matched(c, gp.rows_b, &a.matched));  // one bit per probe row SLOT of the slab layout
+  const int sp = span_begin(c, K_PROBE_COUNT, -1);
+  HIP_TRY(hmj::launch_probe(a, 0, first, extra, hmj::probe_default_grid(c->num_cus), c->stream));
+  span_end(c, sp);
+  c->timing.bytes_probe_count = 16ull * ((u64)nb + np);
+  u64* hh;
+  RC_TRY(read_accum(c, &hh));
+  if (hh[hmj::ACC_ERR] & hmj::ERR_SLAB) {  // a probe slab overflowed (skewed probe keys)
+    c->wm->slab_probe_cooldown = 8;
+    return kRetryNoSlabProbe;
+  }
+  result_sums(j.out, hh);
+  return HMJ_OK;
+}
+
+// ---- count joins of a mid-size build side (2^18 ... 2^20 rows: ONE radix pass, too big for the global table of
+// gtable.hip) with a probe side several times larger -- a dimension table under a fact table.  The exact path costs the
+// probe side 16 (histogram) + 32 (scatter) + 16 (probe) bytes per row.  Here its one pass is the histogram-free slab
+// pass A (32 B), and the generic kernel reads a partition straight out of the pass's worker-private slabs: partition p =
+// the WA pieces [p][0 .. WA), an item = (partition, a run of pieces), a wave per piece.  48 instead of 64 B per row.
+// Unordered materialising joins write their rows in the same walk (duplicate build keys: kRetryNoSlabProbe).
+static int run_one_pass_slab_join(hmj_ctx* c, const JoinCall& j, const JoinPlan& p, const void* Rp) {
+  const bool materialize = j.materialize(), first = j.first(), extra = j.extra();
+  const u32 nb = j.nb, np = j.np, P = p.P;
+  const int B = p.B;
+  hmj::SlabGeom g1;
+  if (!(p.allow_slab_probe && c->slab_mode && c->one_pass_slab && c->wm->slab_probe_cooldown == 0 && !(j.flags & HMJ_ORDERED) &&
+        (!materialize || c->wm->one_pass_write_cooldown == 0) && p.passes == 1 &&
+        B >= 5 && B <= hmj::SLAB_MAX_BITS && np >= (1u << 22) && (u64)np >= 8ull * nb && nb > 0))
+    return kPlanNotTaken;
+  if (!hmj::slab_geometry_one_pass(np, B, p.dense_scale * (double)nb / (double)P, 512, &g1)) return kPlanNotTaken;
+  RC_TRY(ensure_dev(c, c->slab_a, g1.rows_a * 16));
+  RC_TRY(ensure_dev(c, c->cnt_a, ((size_t)g1.WA << B) * 4));
+  RC_TRY(slab_pass_a(c, j.S, np, 1, p.low, B, g1, false));
+  c->timing.path |= HMJ_PATH_SLAB_PROBE | HMJ_PATH_SLAB_ONE_PASS;
+  // items: about eight per CU; an item walks ppi of its partition's WA pieces
+  u32 qi = 2048u / P;
+  if (qi < 1) qi = 1;
+  if (qi > g1.WA / 16) qi = g1.WA / 16;  // (a wave per piece, 16 waves per workgroup: an item of fewer pieces idles some)
+  if (qi < 1) qi = 1;
+  const u32 ppi = (g1.WA + qi - 1) / qi;
+  qi = (g1.WA + ppi - 1) / ppi;
+  hmj::ProbeArgs a = slab_probe_args(c, nullptr, Rp, c->slab_a, c->cnt_a, g1.CA, P, qi);
+  a.s_wa = g1.WA;
+  a.s_ppi = ppi;
+  c->timing.n_probe_items = P * qi;
+  // one bit per probe row SLOT of the slab buffer (used where a build partition needs several tables)
+  if (first) RC_TRY(clear_matched(c, g1.rows_a, &a.matched));
+  if (materialize) {
+    // unordered rows: counted AND written in the same walk, behind one output cursor (probe_kernel<3>); the columns hold
+    // one row per probe row -- more (duplicate build keys: a probe row expands) raises ERR_FASTPATH, and the
+    // count / scan / write passes run instead
+    const size_t bytes = (size_t)np * 8;
+    RC_TRY(ensure_dev(c, c->out_key, bytes));
+    RC_TRY(ensure_dev(c, c->out_rval, bytes));
+    RC_TRY(ensure_dev(c, c->out_sval, bytes));
+    a.out_key = (u64*)c->out_key.p;
+    a.out_rval = (u64*)c->out_rval.p;
+    a.out_sval = (u64*)c->out_sval.p;
+    a.out_cap = np;
+  }
+  const int sp = span_begin(c, materialize ? K_PROBE_WRITE : K_PROBE_COUNT, -1);
+  HIP_TRY(hmj::launch_probe(a, materialize ? 3 : 0, first, extra, hmj::probe_default_grid(c->num_cus) * 2, c->stream));
+  span_end(c, sp);
+  if (materialize)
+    c->timing.bytes_probe_write = 16ull * ((u64)nb + np);
+  else
+    c->timing.bytes_probe_count = 16ull * ((u64)nb + np);
+  u64* hh;
+  RC_TRY(read_accum(c, &hh));
+  if (hh[hmj::ACC_ERR] & hmj::ERR_SLAB) {  // a slab overflowed (skewed probe keys): the exact path, and not again for a while
+    c->wm->slab_probe_cooldown = 8;
+    return kRetryNoSlabProbe;
+  }
+  if (hh[hmj::ACC_ERR] & hmj::ERR_FASTPATH) {  // more result rows than probe rows: the general materialising passes
+    c->wm->one_pass_write_cooldown = 8;
+    return kRetryNoSlabProbe;
+  }
+  result_sums(j.out, hh);
+  if (materialize && j.out->n_matches) {
+    c->timing.bytes_probe_write += 24ull * j.out->n_matches;
+    RC_TRY(deliver_columns(c, j.out, j.to_host, c->out_key.p, c->out_rval.p, c->out_sval.p, (size_t)j.out->n_matches * 8, false));
+  }
+  return HMJ_OK;
+}
+
+// Skewed probe side (a hot foreign key): partitions with far more probe rows than the rest are cut into
+// virtual partitions so that no single workgroup is left with millions of rows (probe.hip,
+// split_*_kernel).  Pi = number of (virtual) partitions the probe kernels iterate over (P: nothing was cut, the five
+// tables are null); v_start[p] = partition p's first virtual partition, the other four the row ranges of each.
+struct VirtualParts {
+  u32 Pi;
+  const u32 *v_start, *r_beg, *r_end, *s_beg, *s_end;
+};
+static int split_partitions(hmj_ctx* c, const JoinCall& j, const JoinPlan& p, VirtualParts* v) {
+  const bool materialize = j.materialize(), first = j.first(), extra = j.extra();
+  const u32 np = j.np, P = p.P;
+  *v = VirtualParts{P, nullptr, nullptr, nullptr, nullptr, nullptr};
   // (not with HMJ_SUM_PROBE: a probe row would be added once per build slice)
-  const bool enumerating = (materialize || extra) && !first && !(flags & HMJ_SUM_PROBE);
+  const bool enumerating = (materialize || extra) && !first && !(j.flags & HMJ_SUM_PROBE);
   // the step costs one 4-byte read-back: taken from 1024 partitions on (joins of a few ms), and from 16 on when
   // the key sample saw a repeated key (a hot key can mean one partition with most of the rows)
-  if (Q == 1 && (P >= 1024 || (hot_hint && P >= 16)) && np > 0 && c->split_mode) {
-    // average partition fits the pipelines: cut everything above them into 4096-row slices.  Otherwise (big
-    // probe partitions by plan) a slice is 1/2048 of the probe side -- enough slices to fill the chip even when
-    // one partition holds most of the rows -- and only partitions of more than four slices are cut.
-    u32 slice = probe_fits ? 4096u : np / 2048u;
-    if (!probe_fits && slice < 16384u) slice = 16384u;
-    const u32 thr = probe_fits ? (fk_wide_plan ? 6144u : 5120u) : 4u * slice;  // (the one-pass ordered write's partition capacity)
-    // modes that enumerate every pair (materialise, checksums) and are not first-wins also cut partitions with
-    // thousands of copies of a key on the build side: the cross product of a hot key is then written by many
-    // workgroups (each build slice meets every probe slice of the partition)
-    const u32 build_slice = 4096u;
-    // virtual partitions: at most P + np / slice from probe slices; build slices multiply a partition's count,
-    // bounded by giving the table room for 8x that (a larger total makes the split be ignored)
-    // (join kinds: never -- a probe row must meet its key's build rows in ONE work item, or its hit / miss status is wrong)
-    const bool build_slices = enumerating && !c->join_kind;
-    u32 build_thr = build_slices ? 6144u : 0u;
-    u32 cap_v = (P + np / slice + 1) * (build_slices ? 8u : 1u);
-    if (build_slices && cap_v < (1u << 18)) cap_v = 1u << 18;  // room for the 256-row slices of build-heavy partitions
-    u32* hnv = (u32*)c->h_accum.p;
-    u32 *d_vstart = nullptr, *d_rb = nullptr, *d_re = nullptr, *d_sb = nullptr, *d_se = nullptr;
-    // The count step reports how many virtual partitions the split needs.  If the table is too small it is
-    // grown (up to 2^24 entries) and the split repeated; a split that would still not fit falls back to
-    // probe-only slices (bounded by P + np / slice) instead of being dropped -- one workgroup enumerating a
-    // whole hot cross product is a cliff of minutes.
-    for (int attempt = 0; attempt < 4; attempt++) {
-      if ((rc = ensure_dev(c, c->vparts, ((size_t)cap_v * 4 + P + 3) * 4)) != HMJ_OK) return rc;
-      u32* vp = (u32*)c->vparts.p;
-      d_vstart = vp;
-      u32* d_nv = vp + P + 1;
-      d_rb = vp + P + 2;
-      d_re = d_rb + cap_v;
-      d_sb = d_re + cap_v;
-      d_se = d_sb + cap_v;
-      HIP_TRY(hmj::launch_split_parts((const u32*)c->r_off.p, (const u32*)c->s_off.p, P, thr, slice, build_thr, build_slice,
-                                      cap_v, d_vstart, d_rb, d_re, d_sb, d_se, d_nv, c->stream));
-      HIP_TRY(hipMemcpyAsync(hnv, d_nv, 4, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      if (*hnv <= cap_v) break;
-      c->timing.n_split_retries++;
-      if (attempt < 2 && cap_v < (1u << 24)) {
-        u64 want = (u64)cap_v * 8;  // per-partition counts are clamped at cap_v + 1: the total is a lower bound
-        cap_v = want > (1ull << 24) ? (1u << 24) : (u32)want;
-      } else {
-        build_thr = 0;  // probe slices only
-        cap_v = P + np / slice + 1;
-      }
-    }
-    if (*hnv > P && *hnv <= cap_v) {
-      Pi = *hnv;
-      v_start = d_vstart;
-      vr_beg = d_rb;
-      vr_end = d_re;
-      vs_beg = d_sb;
-      vs_end = d_se;
-      if (materialize) {
-        if ((rc = ensure_dev(c, c->part_count, (size_t)Pi * 8)) != HMJ_OK) return rc;
-        if ((rc = ensure_dev(c, c->part_out_off, ((size_t)Pi + 1) * 8)) != HMJ_OK) return rc;
-      }
+  if (!(p.Q == 1 && (P >= 1024 || (p.hot_hint && P >= 16)) && np > 0 && c->split_mode)) return HMJ_OK;
+  // average partition fits the pipelines: cut everything above them into 4096-row slices.  Otherwise (big
+  // probe partitions by plan) a slice is 1/2048 of the probe side -- enough slices to fill the chip even when
+  // one partition holds most of the rows -- and only partitions of more than four slices are cut.
+  u32 slice = p.probe_fits ? 4096u : np / 2048u;
+  if (!p.probe_fits && slice < 16384u) slice = 16384u;
+  const u32 thr = p.probe_fits ? (p.fk_wide_plan ? 6144u : 5120u) : 4u * slice;  // (the one-pass ordered write's partition capacity)
+  // modes that enumerate every pair (materialise, checksums) and are not first-wins also cut partitions with
+  // thousands of copies of a key on the build side: the cross product of a hot key is then written by many
+  // workgroups (each build slice meets every probe slice of the partition)
+  const u32 build_slice = 4096u;
+  // virtual partitions: at most P + np / slice from probe slices; build slices multiply a partition's count,
+  // bounded by giving the table room for 8x that (a larger total makes the split be ignored)
+  // (join kinds: never -- a probe row must meet its key's build rows in ONE work item, or its hit / miss status is wrong)
+  const bool build_slices = enumerating && !c->join_kind;
+  u32 build_thr = build_slices ? 6144u : 0u;
+  u32 cap_v = (P + np / slice + 1) * (build_slices ? 8u : 1u);
+  if (build_slices && cap_v < (1u << 18)) cap_v = 1u << 18;  // room for the 256-row slices of build-heavy partitions
+  u32* hnv = (u32*)c->h_accum.p;
+  u32 *d_vstart = nullptr, *d_rb = nullptr, *d_re = nullptr, *d_sb = nullptr, *d_se = nullptr;
+  // The count step reports how many virtual partitions the split needs.  If the table is too small it is
+  // grown (up to 2^24 entries) and the split repeated; a split that would still not fit falls back to
+  // probe-only slices (bounded by P + np / slice) instead of being dropped -- one workgroup enumerating a
+  // whole hot cross product is a cliff of minutes.
+  for (int attempt = 0; attempt < 4; attempt++) {
+    RC_TRY(ensure_dev(c, c->vparts, ((size_t)cap_v * 4 + P + 3) * 4));
+    u32* vp = (u32*)c->vparts.p;
+    d_vstart = vp;
+    u32* d_nv = vp + P + 1;
+    d_rb = vp + P + 2;
+    d_re = d_rb + cap_v;
+    d_sb = d_re + cap_v;
+    d_se = d_sb + cap_v;
+    HIP_TRY(hmj::launch_split_parts((const u32*)c->r_off.p, (const u32*)c->s_off.p, P, thr, slice, build_thr, build_slice,
+                                    cap_v, d_vstart, d_rb, d_re, d_sb, d_se, d_nv, c->stream));
+    HIP_TRY(hipMemcpyAsync(hnv, d_nv, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (*hnv <= cap_v) break;
+    c->timing.n_split_retries++;
+    if (attempt < 2 && cap_v < (1u << 24)) {
+      u64 want = (u64)cap_v * 8;  // per-partition counts are clamped at cap_v + 1: the total is a lower bound
+      cap_v = want > (1ull << 24) ? (1u << 24) : (u32)want;
+    } else {
+      build_thr = 0;  // probe slices only
+      cap_v = P + np / slice + 1;
     }
   }
-  const bool split = Pi != P;
-  if (split) c->timing.path |= HMJ_PATH_SPLIT;
-  c->timing.n_probe_items = split ? Pi : (u32)items;
+  if (*hnv > P && *hnv <= cap_v) {
+    *v = VirtualParts{*hnv, d_vstart, d_rb, d_re, d_sb, d_se};
+    if (materialize) {
+      RC_TRY(ensure_dev(c, c->part_count, (size_t)v->Pi * 8));
+      RC_TRY(ensure_dev(c, c->part_out_off, ((size_t)v->Pi + 1) * 8));
+    }
+  }
+  return HMJ_OK;
+}
 
-  if (fast_write && !split) {  // (with split partitions a partition's rows are not in one piece: general passes)
-    hmj::ProbeArgs wa;
-    std::memset(&wa, 0, sizeof(wa));
-    wa.R = Rp;
-    wa.r_off = (const u32*)c->r_off.p;
-    wa.S = Sp;
-    wa.s_off = (const u32*)c->s_off.p;
-    wa.P = P;
-    wa.Q = 1;
-    wa.accum = (u64*)c->accum.p;
-    rc = unique_key_write(c, wa, false, nb, np, low, extra, verify_pfx ? prefix : 0, pfx_ref,
-                                  (flags & HMJ_ORDERED) != 0, to_host, fk_wide_plan, dense_scale, out);
-    if (rc != kRetryNoFastWrite) return rc;
-    // duplicate build keys: the partitions stay valid, carry on with the count / scan / write passes
-    HIP_TRY(hipMemsetAsync(c->accum.p, 0, 8 * sizeof(u64), c->stream));
+// Ordered, and the unique-key forms were not taken (duplicate build keys): while the partitions are key ranges and fit
+// the kernel, the result is written IN ORDER partition by partition (probe_expand_ordered_kernel: both sides sorted in
+// LDS, every build row against its key's run of probe rows) instead of written in probe order and sorted afterwards --
+// 8 x 8 rows per key, 1.3 * 10^8 result rows: write 1.9 + order 16.1 ms -> one kernel.  `a`: the counted partitions with
+// their output columns and offsets.  *expanded = the result rows are written; otherwise the write pass (+ order_rows) runs.
+static int try_ordered_expansion(hmj_ctx* c, const JoinCall& j, const JoinPlan& p, const hmj::ProbeArgs& a, bool split,
+                                 bool* expanded) {
+  const u32 nb = j.nb, np = j.np;
+  const hmj_result* out = j.out;
+  u64* h = (u64*)c->h_accum.p;
+  *expanded = false;
+  // (An unordered result takes it too -- rows in order are rows: 1.15 against 1.9 ms for the general write pass, whose
+  //  workgroups re-probe their partition; there the partitions need not be key ranges.)
+  if (c->wm->expand_cooldown > 0) {
+    c->wm->expand_cooldown--;
+    return HMJ_OK;
   }
-  hmj::ProbeArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.R = Rp;
-  a.r_off = split ? vr_beg : (const u32*)c->r_off.p;
-  a.r_end = vr_end;
-  a.S = Sp;
-  a.s_off = split ? vs_beg : (const u32*)c->s_off.p;
-  a.s_end = vs_end;
-  a.P = Pi;
-  a.Q = Q;
-  a.accum = (u64*)c->accum.p;
-  if (verify_pfx) {
-    a.pfx_shift = (u32)(64 - prefix);
-    a.pfx_val = pfx_ref >> (64 - prefix);
+  //  Only where the result is several times the input: the kernel runs one workgroup per CU through a dozen barriers per
+  //  partition -- at about one result row per input row the general write pass is as fast: 2^28 x 2^28, every 4th build key
+  //  doubled: 6.4 against 6.9 ms.)
+  if (!(c->expand_mode && ((j.flags & HMJ_ORDERED) ? !p.win_ordered : out->n_matches >= 2 * ((u64)nb + np)) && !split && p.Q == 1 &&
+        !j.first() && p.P >= 2))
+    return HMJ_OK;
+  const int s = span_begin(c, K_PROBE_WRITE, -1);
+  HIP_TRY(hmj::launch_probe_expand_ordered(a, p.low, c->num_cus, c->stream));
+  span_end(c, s);
+  HIP_TRY(hipMemcpyAsync(&h[hmj::ACC_ERR], (u64*)c->accum.p + hmj::ACC_ERR, 16, hipMemcpyDeviceToHost, c->stream));  // (+ ACC_PAD)
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (h[hmj::ACC_ERR] & hmj::ERR_FASTPATH) {  // a partition beyond the kernel's capacity: write + sort, as before ...
+    // ... unless ONE more radix bit would make every partition fit (the biggest is under twice the capacity: keys with
+    // many copies make partition sizes vary like copies x keys, not a hot key) and sorting the result rows would cost more
+    // than partitioning again (0.12 ns per result row against ~0.06 per input row): the join starts over with B + 1
+    if (c->expand_allow_rebits && (j.flags & HMJ_ORDERED) && c->force_bits < 0 && h[hmj::ACC_PAD] <= 7800 && p.B + 1 <= 18 &&
+        2 * out->n_matches >= (u64)nb + np) {
+      c->expand_rebits = p.B + 1;
+      return kRetryMoreBits;
+    }
+    c->wm->expand_cooldown = 8;
+    HIP_TRY(hipMemsetAsync((u64*)c->accum.p + hmj::ACC_ERR, 0, sizeof(u64), c->stream));
+    std::vector<Span> keep;
+    for (const Span& s2 : c->spans)
+      if (s2.kind != K_PROBE_WRITE) keep.push_back(s2);
+    c->spans.swap(keep);
+  } else {
+    *expanded = true;
+    c->timing.path |= HMJ_PATH_ORDERED_EXPANSION;
+    c->timing.bytes_probe_write = 16ull * ((u64)nb + np) + 24ull * out->n_matches;
   }
-#ifdef HMJ_DEV
-  a.debug = c->dev_ablate;
-#endif
-  a.part_count = (u64*)c->part_count.p;
-  a.part_out_off = (const u64*)c->part_out_off.p;
-  const int grid = hmj::probe_default_grid(c->num_cus);
-  const size_t matched_bytes = ((size_t)np / 32 + 1) * 4;
-  if (first) {  // bitmap of probe rows already paired (used when a build partition needs chunks)
-    if ((rc = ensure_dev(c, c->matched, matched_bytes)) != HMJ_OK) return rc;
-    a.matched = (u32*)c->matched.p;
-    HIP_TRY(hipMemsetAsync(c->matched.p, 0, matched_bytes, c->stream));
-  }
+  return HMJ_OK;
+}
 
-  if (c->join_kind) return execute_kind_probe(c, a, nb, np, flags, out, to_host, v_start, P, Q, Pi, split, low, win_ordered);
-  s = span_begin(c, K_PROBE_COUNT, -1);
-  if (!first && !extra && Q == 1 && Pi >= 2) {
+// The count pass over (virtual) partitions in the offset layout: the pipelined kernels where the mode has one, the generic
+// kernel over the partitions they set aside -- or over everything.
+static int count_partitions(hmj_ctx* c, const JoinCall& j, const JoinPlan& p, const hmj::ProbeArgs& a) {
+  const bool materialize = j.materialize(), first = j.first(), extra = j.extra();
+  const u32 Pi = a.P;
+  const int s = span_begin(c, K_PROBE_COUNT, -1);
+  if (!first && !extra && p.Q == 1 && Pi >= 2) {
     // pipelined count kernel (with per-partition counts when materialising), then the generic
     // kernel over the partitions it set aside
-    if ((rc = ensure_dev(c, c->irregular, ((size_t)Pi + 1) * 4)) != HMJ_OK) return rc;
+    RC_TRY(ensure_dev(c, c->irregular, ((size_t)Pi + 1) * 4));
     u32* n_irr = (u32*)c->irregular.p;
     u32* irr = n_irr + 1;
     HIP_TRY(hipMemsetAsync(n_irr, 0, 4, c->stream));
-    const bool big = ((u64)nb >> B) > 2300;  // average build partition beyond the 2560-row pipeline
+    const bool big = ((u64)j.nb >> p.B) > 2300;  // average build partition beyond the 2560-row pipeline
     HIP_TRY(hmj::launch_probe_count_fast(a, irr, n_irr, big, materialize, c->num_cus, c->stream));
     hmj::ProbeArgs a2 = a;
     a2.item_list = irr;
     a2.n_item_list = n_irr;
     HIP_TRY(hmj::launch_probe(a2, materialize ? 1 : 0, false, false, c->num_cus, c->stream));
-  } else if (!materialize && Q == 1 && Pi >= 2) {
+  } else if (!materialize && p.Q == 1 && Pi >= 2) {
     // count mode with checksums / first-wins: the pipelined kernel's extended variant, then the generic
     // kernel (same flags) over the partitions it set aside
-    if ((rc = ensure_dev(c, c->irregular, ((size_t)Pi + 1) * 4)) != HMJ_OK) return rc;
+    RC_TRY(ensure_dev(c, c->irregular, ((size_t)Pi + 1) * 4));
     u32* n_irr = (u32*)c->irregular.p;
     u32* irr = n_irr + 1;
     HIP_TRY(hipMemsetAsync(n_irr, 0, 4, c->stream));
@@ -1823,119 +1773,132 @@ static int execute_join(hmj_ctx* c, const void* R, uint64_t n_build, const void*
     a2.n_item_list = n_irr;
     HIP_TRY(hmj::launch_probe(a2, 0, first, extra, c->num_cus, c->stream));
   } else {
-    HIP_TRY(hmj::launch_probe(a, materialize ? 1 : 0, first, extra, grid, c->stream));
+    HIP_TRY(hmj::launch_probe(a, materialize ? 1 : 0, first, extra, hmj::probe_default_grid(c->num_cus), c->stream));
   }
   span_end(c, s);
-  c->timing.bytes_probe_count = 16ull * ((u64)nb + np);
+  c->timing.bytes_probe_count = 16ull * ((u64)j.nb + j.np);
+  return HMJ_OK;
+}
+
+// ---- the general plan: both relations partitioned exactly (the build side already is: Rp), oversized partitions cut
+// (split_partitions), then the unique-key write where it is on offer, or count -> scan -> write (ordered: the ordered
+// expansion, or the write pass and the order_rows epilogue).  Join kinds branch off to execute_kind_probe.
+static int run_partitioned_join(hmj_ctx* c, const JoinCall& j, const JoinPlan& p, const void* Rp) {
+  const bool materialize = j.materialize(), first = j.first(), extra = j.extra();
+  const u32 nb = j.nb, np = j.np, P = p.P, Q = p.Q;
+  hmj_result* out = j.out;
+  const void* Sp;
+  RC_TRY(partition_relation(c, j.S, np, c->sbuf, p.low, p.passes, p.pass_bits, 1, &Sp, p.asc_s));
+  int s = span_begin(c, K_OFFSETS, -1);
+  HIP_TRY(hmj::launch_part_offsets(Sp, np, p.low, p.B, (u32*)c->s_off.p, c->stream));
+  span_end(c, s);
+
+  VirtualParts v;
+  RC_TRY(split_partitions(c, j, p, &v));
+  const u32 Pi = v.Pi;
+  const bool split = Pi != P;
+  if (split) c->timing.path |= HMJ_PATH_SPLIT;
+  c->timing.n_probe_items = split ? Pi : (u32)p.items;
+
+  if (p.fast_write && !split) {  // (with split partitions a partition's rows are not in one piece: general passes)
+    hmj::ProbeArgs wa = offset_probe_args(c, Rp, Sp, P, 1);
+    const int rc = unique_key_write(c, wa, false, nb, np, p.low, extra, p.verify_pfx ? p.prefix : 0, p.pfx_ref, j.ordered(),
+                                    j.to_host, p.fk_wide_plan, p.dense_scale, out);
+    if (rc != kRetryNoFastWrite) return rc;
+    // duplicate build keys: the partitions stay valid, carry on with the count / scan / write passes
+    HIP_TRY(hipMemsetAsync(c->accum.p, 0, 8 * sizeof(u64), c->stream));
+  }
+  hmj::ProbeArgs a = offset_probe_args(c, Rp, Sp, Pi, Q);
+  if (split) {
+    a.r_off = v.r_beg;
+    a.s_off = v.s_beg;
+  }
+  a.r_end = v.r_end;
+  a.s_end = v.s_end;
+  if (p.verify_pfx) {
+    a.pfx_shift = (u32)(64 - p.prefix);
+    a.pfx_val = p.pfx_ref >> (64 - p.prefix);
+  }
+#ifdef HMJ_DEV
+  a.debug = c->dev_ablate;
+#endif
+  a.part_count = (u64*)c->part_count.p;
+  a.part_out_off = (const u64*)c->part_out_off.p;
+  const size_t matched_bytes = ((size_t)np / 32 + 1) * 4;
+  if (first) RC_TRY(clear_matched(c, np, &a.matched));  // bitmap of probe rows already paired (used when a build partition needs chunks)
+
+  if (c->join_kind) return execute_kind_probe(c, a, nb, np, j.flags, out, j.to_host, v.v_start, P, Q, Pi, split, p.low, p.win_ordered);
+  RC_TRY(count_partitions(c, j, p, a));
   if (materialize) {
     s = span_begin(c, K_OUT_SCAN, -1);
     HIP_TRY(hmj::launch_scan_u64((const u64*)c->part_count.p, (u64*)c->part_out_off.p,
-                                 split ? Pi : (u32)items, c->stream));
+                                 split ? Pi : (u32)p.items, c->stream));
     span_end(c, s);
   }
-  u64* h = (u64*)c->h_accum.p;
-  HIP_TRY(hipMemcpyAsync(h, c->accum.p, 8 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  u64* h;
+  RC_TRY(read_accum(c, &h));
   if (h[hmj::ACC_ERR] & hmj::ERR_PREFIX) return kRetryNoPrefix;
-  out->n_matches = h[hmj::ACC_N];
-  out->sum_r = h[hmj::ACC_SUM_R];
-  out->sum_s = h[hmj::ACC_SUM_S];
-  out->xor_fold = h[hmj::ACC_XOR];
-  out->mix_sum = h[hmj::ACC_MIX];
-  out->sum_probe_all = h[hmj::ACC_SUM_P];
+  result_sums(out, h);
+  if (!materialize || !out->n_matches) return HMJ_OK;
 
-  if (materialize && out->n_matches) {
-    const size_t bytes = (size_t)out->n_matches * 8;
-    if ((rc = ensure_dev(c, c->out_key, bytes)) != HMJ_OK) return rc;
-    if ((rc = ensure_dev(c, c->out_rval, bytes)) != HMJ_OK) return rc;
-    if ((rc = ensure_dev(c, c->out_sval, bytes)) != HMJ_OK) return rc;
-    a.out_key = (u64*)c->out_key.p;
-    a.out_rval = (u64*)c->out_rval.p;
-    a.out_sval = (u64*)c->out_sval.p;
-    // Ordered, and the unique-key forms were not taken (duplicate build keys): while the partitions are key ranges and fit
-    // the kernel, the result is written IN ORDER partition by partition (probe_expand_ordered_kernel: both sides sorted in
-    // LDS, every build row against its key's run of probe rows) instead of written in probe order and sorted afterwards --
-    // 8 x 8 rows per key, 1.3 * 10^8 result rows: write 1.9 + order 16.1 ms -> one kernel.
-    bool expanded = false;
-    // (An unordered result takes it too -- rows in order are rows: 1.15 against 1.9 ms for the general write pass, whose
-    //  workgroups re-probe their partition; there the partitions need not be key ranges.)
-    if (c->wm->expand_cooldown > 0) c->wm->expand_cooldown--;
-    //  Only where the result is several times the input: the kernel runs one workgroup per CU through a dozen barriers per
-    //  partition -- at about one result row per input row the general write pass is as fast: 2^28 x 2^28, every 4th build key
-    //  doubled: 6.4 against 6.9 ms.)
-    else if (c->expand_mode && ((flags & HMJ_ORDERED) ? !win_ordered : out->n_matches >= 2 * ((u64)nb + np)) && !split && Q == 1 &&
-             !first && P >= 2) {
-      s = span_begin(c, K_PROBE_WRITE, -1);
-      HIP_TRY(hmj::launch_probe_expand_ordered(a, low, c->num_cus, c->stream));
-      span_end(c, s);
-      HIP_TRY(hipMemcpyAsync(&h[hmj::ACC_ERR], (u64*)c->accum.p + hmj::ACC_ERR, 16, hipMemcpyDeviceToHost, c->stream));  // (+ ACC_PAD)
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      if (h[hmj::ACC_ERR] & hmj::ERR_FASTPATH) {  // a partition beyond the kernel's capacity: write + sort, as before ...
-        // ... unless ONE more radix bit would make every partition fit (the biggest is under twice the capacity: keys with
-        // many copies make partition sizes vary like copies x keys, not a hot key) and sorting the result rows would cost more
-        // than partitioning again (0.12 ns per result row against ~0.06 per input row): the join starts over with B + 1
-        if (c->expand_allow_rebits && (flags & HMJ_ORDERED) && c->force_bits < 0 && h[hmj::ACC_PAD] <= 7800 && B + 1 <= 18 &&
-            2 * out->n_matches >= (u64)nb + np) {
-          c->expand_rebits = B + 1;
-          return kRetryMoreBits;
-        }
-        c->wm->expand_cooldown = 8;
-        HIP_TRY(hipMemsetAsync((u64*)c->accum.p + hmj::ACC_ERR, 0, sizeof(u64), c->stream));
-        std::vector<Span> keep;
-        for (const Span& s2 : c->spans)
-          if (s2.kind != K_PROBE_WRITE) keep.push_back(s2);
-        c->spans.swap(keep);
-      } else {
-        expanded = true;
-        c->timing.path |= HMJ_PATH_ORDERED_EXPANSION;
-        c->timing.bytes_probe_write = 16ull * ((u64)nb + np) + 24ull * out->n_matches;
-      }
-    }
-    if (!expanded) {
+  const size_t bytes = (size_t)out->n_matches * 8;
+  RC_TRY(ensure_dev(c, c->out_key, bytes));
+  RC_TRY(ensure_dev(c, c->out_rval, bytes));
+  RC_TRY(ensure_dev(c, c->out_sval, bytes));
+  a.out_key = (u64*)c->out_key.p;
+  a.out_rval = (u64*)c->out_rval.p;
+  a.out_sval = (u64*)c->out_sval.p;
+  bool expanded = false;
+  RC_TRY(try_ordered_expansion(c, j, p, a, split, &expanded));
+  const u64 *rk = a.out_key, *rr = a.out_rval, *rs = a.out_sval;
+  if (!expanded) {
     if (first) HIP_TRY(hipMemsetAsync(c->matched.p, 0, matched_bytes, c->stream));
     s = span_begin(c, K_PROBE_WRITE, -1);
-    HIP_TRY(hmj::launch_probe(a, 2, first, false, grid, c->stream));
+    HIP_TRY(hmj::launch_probe(a, 2, first, false, hmj::probe_default_grid(c->num_cus), c->stream));
     span_end(c, s);
     c->timing.bytes_probe_write = 16ull * ((u64)nb + np) + 24ull * out->n_matches;
-    }
-    if ((flags & HMJ_ORDERED) && !expanded) {  // out of place: unsorted columns -> sorted columns (order_rows)
-      const u64 *rk = nullptr, *rr = nullptr, *rs = nullptr;
+    if (j.flags & HMJ_ORDERED) {  // out of place: unsorted columns -> sorted columns (order_rows)
       int retry = 0;
-      if ((rc = order_rows(c, v_start, nullptr, nullptr, P, Q, low, out->n_matches, win_ordered,
-                           out->n_matches > 2ull * nb, &rk, &rr, &rs, &retry)) != HMJ_OK)
-        return rc;
+      RC_TRY(order_rows(c, v.v_start, nullptr, nullptr, P, Q, p.low, out->n_matches, p.win_ordered,
+                        out->n_matches > 2ull * nb, &rk, &rr, &rs, &retry));
       if (retry) return retry;
-      a.out_key = const_cast<u64*>(rk);
-      a.out_rval = const_cast<u64*>(rr);
-      a.out_sval = const_cast<u64*>(rs);
     }
-    if (to_host) {
-      if ((rc = ensure_host(c, c->h_key, bytes, false)) != HMJ_OK) return rc;
-      if ((rc = ensure_host(c, c->h_rval, bytes, false)) != HMJ_OK) return rc;
-      if ((rc = ensure_host(c, c->h_sval, bytes, false)) != HMJ_OK) return rc;
-      s = span_begin(c, K_D2H, -1);
-      HIP_TRY(hipMemcpyAsync(c->h_key.p, a.out_key, bytes, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipMemcpyAsync(c->h_rval.p, a.out_rval, bytes, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipMemcpyAsync(c->h_sval.p, a.out_sval, bytes, hipMemcpyDeviceToHost, c->stream));
-      span_end(c, s);
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    out->key = to_host ? (const uint64_t*)c->h_key.p : (const uint64_t*)a.out_key;
-    out->rval = to_host ? (const uint64_t*)c->h_rval.p : (const uint64_t*)a.out_rval;
-    out->sval = to_host ? (const uint64_t*)c->h_sval.p : (const uint64_t*)a.out_sval;
   }
-  return HMJ_OK;
+  return deliver_columns(c, out, j.to_host, rk, rr, rs, bytes, true);
+}
+
+// One attempt, executed: the allocations every plan needs, then the plans in the order they are tried.
+static int execute_join(hmj_ctx* c, const JoinCall& j, const JoinPlan& p) {
+  RC_TRY(ensure_dev(c, c->r_off, ((size_t)p.P + 1) * 4));
+  RC_TRY(ensure_dev(c, c->s_off, ((size_t)p.P + 1) * 4));
+  RC_TRY(ensure_dev(c, c->accum, 8 * sizeof(u64)));
+  RC_TRY(ensure_host(c, c->h_accum, 8 * sizeof(u64)));
+  if (j.materialize()) {
+    RC_TRY(ensure_dev(c, c->part_count, (size_t)p.items * 8));
+    RC_TRY(ensure_dev(c, c->part_out_off, ((size_t)p.items + 1) * 8));
+  }
+  HIP_TRY(hipMemsetAsync(c->accum.p, 0, 8 * sizeof(u64), c->stream));
+  int rc = run_slab_join(c, j, p);  // both relations in slabs
+  if (rc != kPlanNotTaken) return rc;
+  const void* Rp;
+  RC_TRY(partition_build_exact(c, j, p, &Rp));
+  if (c->prepare_only) return HMJ_OK;  // hmj_prepare_build: the prepared state is recorded
+  for (hipEvent_t ev : c->arrive_ev) RC_TRY(wait_arrival(c, ev));  // probe rows still on the links
+  rc = run_probe_slab_join(c, j, p, Rp);  // exact build side, probe side in pass-B slabs
+  if (rc != kPlanNotTaken) return rc;
+  rc = run_one_pass_slab_join(c, j, p, Rp);  // exact build side of one pass, probe side in pass-A slabs
+  if (rc != kPlanNotTaken) return rc;
+  return run_partitioned_join(c, j, p, Rp);
 }
 
 int join_device_impl(hmj_ctx* c, const void* R, uint64_t n_build, const void* S, uint64_t n_probe,
                      uint32_t flags, hmj_result* out, bool to_host, bool allow_auto_prefix,
                      bool allow_slab, bool allow_fast_write, bool allow_win_ordered, bool prefix_unsafe,
                      bool allow_slab_probe) {
-  int rc;
   if (!out) return fail(c, HMJ_E_ARG, "out is NULL");
   std::memset(out, 0, sizeof(*out));
-  if ((rc = check_rel(c, R, n_build, "build_aos is NULL")) != HMJ_OK) return rc;
-  if ((rc = check_rel(c, S, n_probe, "probe_aos is NULL")) != HMJ_OK) return rc;
+  RC_TRY(check_rel(c, R, n_build, "build_aos is NULL"));
+  RC_TRY(check_rel(c, S, n_probe, "probe_aos is NULL"));
   if (flags & HMJ_ORDERED) flags |= HMJ_MATERIALIZE;
   // a build side partitioned ahead by hmj_prepare_build pins the partitioning path of the join that uses it (a
   // slab cool-down that ran out in between must not make the join partition the build side a second time)
@@ -1946,10 +1909,10 @@ int join_device_impl(hmj_ctx* c, const void* R, uint64_t n_build, const void* S,
   if (c->wm->slab_probe_cooldown > 0 && allow_slab_probe) c->wm->slab_probe_cooldown--;
   if (c->wm->one_pass_write_cooldown > 0 && materialize && allow_slab_probe) c->wm->one_pass_write_cooldown--;
   JoinPlan p;
-  if ((rc = plan_join(c, R, n_build, S, n_probe, flags, allow_auto_prefix, allow_slab, allow_fast_write, allow_win_ordered,
-                      prefix_unsafe, allow_slab_probe, &p)) != HMJ_OK)
-    return rc;
-  return execute_join(c, R, n_build, S, n_probe, flags, out, to_host, p);
+  RC_TRY(plan_join(c, R, n_build, S, n_probe, flags, allow_auto_prefix, allow_slab, allow_fast_write, allow_win_ordered,
+                   prefix_unsafe, allow_slab_probe, &p));
+  const JoinCall j{R, S, (u32)n_build, (u32)n_probe, flags, out, to_host};
+  return execute_join(c, j, p);
 }
 
 // Small build side, count modes: one global hash table, the probe side streamed once (gtable.hip).  *done = the join
@@ -1987,10 +1950,9 @@ int try_global_table(hmj_ctx* c, const void* R, uint64_t n_build, const void* S,
     c->plan.refused |= HMJ_REFUSED_GTABLE_COOLING;
     return HMJ_OK;
   }
-  int rc;
   if (!out) return fail(c, HMJ_E_ARG, "out is NULL");
-  if ((rc = check_rel(c, R, n_build, "build_aos is NULL")) != HMJ_OK) return rc;
-  if ((rc = check_rel(c, S, n_probe, "probe_aos is NULL")) != HMJ_OK) return rc;
+  RC_TRY(check_rel(c, R, n_build, "build_aos is NULL"));
+  RC_TRY(check_rel(c, S, n_probe, "probe_aos is NULL"));
   int log_cap = 10;
   // slots: 16 per build row while the table stays within 2^18 slots (4 MiB, an XCD's L2), never fewer than 4
   while (((u64)1 << log_cap) < (u64)c->gtable_slots_per_row * n_build) log_cap++;
@@ -2002,9 +1964,9 @@ int try_global_table(hmj_ctx* c, const void* R, uint64_t n_build, const void* S,
   //  accumulators; 2^10 x 2^26 rows 0.36 -> 0.24 ms, 2^11: 0.41 -> 0.30, 2^12: 0.42 -> 0.57 and not taken)
   const bool lds_table = !materialize && c->ltable_mode && n_probe >= (1u << 16) &&
                          n_build <= (uint64_t)((flags & (HMJ_CHECKSUM | HMJ_SUM_PROBE)) ? hmj::ltable_max_rows() / 4 : hmj::ltable_max_rows() / 2);
-  if (!lds_table && (rc = ensure_dev(c, c->gtab, tab_bytes)) != HMJ_OK) return rc;
-  if ((rc = ensure_dev(c, c->accum, 8 * sizeof(u64))) != HMJ_OK) return rc;
-  if ((rc = ensure_host(c, c->h_accum, 8 * sizeof(u64))) != HMJ_OK) return rc;
+  if (!lds_table) RC_TRY(ensure_dev(c, c->gtab, tab_bytes));
+  RC_TRY(ensure_dev(c, c->accum, 8 * sizeof(u64)));
+  RC_TRY(ensure_host(c, c->h_accum, 8 * sizeof(u64)));
   const bool first = flags & HMJ_FIRST_WINS, extra = flags & (HMJ_CHECKSUM | HMJ_SUM_PROBE);
   HIP_TRY(hipMemsetAsync(c->accum.p, 0, 8 * sizeof(u64), c->stream));
   int sp = span_begin(c, K_PROBE_COUNT, -1);
@@ -2033,9 +1995,9 @@ int try_global_table(hmj_ctx* c, const void* R, uint64_t n_build, const void* S,
   if (lds_table) {
   } else if (materialize) {
     const size_t bytes = (size_t)(n_probe ? n_probe : 1) * 8;  // (at most one result row per probe row)
-    if ((rc = ensure_dev(c, c->out_key, bytes)) != HMJ_OK) return rc;
-    if ((rc = ensure_dev(c, c->out_rval, bytes)) != HMJ_OK) return rc;
-    if ((rc = ensure_dev(c, c->out_sval, bytes)) != HMJ_OK) return rc;
+    RC_TRY(ensure_dev(c, c->out_key, bytes));
+    RC_TRY(ensure_dev(c, c->out_rval, bytes));
+    RC_TRY(ensure_dev(c, c->out_sval, bytes));
     span_end(c, sp);
     sp = span_begin(c, K_PROBE_WRITE, -1);
     HIP_TRY(hmj::launch_gtable_write(S, (u32)n_probe, c->gtab.p, log_cap, R, (u64*)c->accum.p, (u64*)c->out_key.p,
@@ -2047,8 +2009,7 @@ int try_global_table(hmj_ctx* c, const void* R, uint64_t n_build, const void* S,
   }
   span_end(c, sp);
   u64* hh = (u64*)c->h_accum.p;
-  HIP_TRY(hipMemcpyAsync(hh, c->accum.p, 8 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  RC_TRY(read_accum(c, &hh));
   const bool dup_write = materialize && !first && hh[hmj::ACC_PAD] != 0;  // duplicate build keys: a probe row may expand to several rows
   if (dup_write && !(hh[hmj::ACC_ERR] & hmj::ERR_GTABLE)) c->wm->gtable_write_cooldown = 8;
   if ((hh[hmj::ACC_ERR] & hmj::ERR_GTABLE) || dup_write) {
@@ -2063,12 +2024,7 @@ int try_global_table(hmj_ctx* c, const void* R, uint64_t n_build, const void* S,
     return HMJ_OK;
   }
   std::memset(out, 0, sizeof(*out));
-  out->n_matches = hh[hmj::ACC_N];
-  out->sum_r = hh[hmj::ACC_SUM_R];
-  out->sum_s = hh[hmj::ACC_SUM_S];
-  out->xor_fold = hh[hmj::ACC_XOR];
-  out->mix_sum = hh[hmj::ACC_MIX];
-  out->sum_probe_all = hh[hmj::ACC_SUM_P];
+  result_sums(out, hh);
   c->timing.path |= HMJ_PATH_GLOBAL_TABLE | (lds_table ? HMJ_PATH_LDS_TABLE : 0u);
   c->timing.radix_bits = 0;
   c->timing.radix_passes = 0;
@@ -2078,23 +2034,8 @@ int try_global_table(hmj_ctx* c, const void* R, uint64_t n_build, const void* S,
   else
     c->timing.bytes_probe_count = 16ull * (n_build + n_probe);
   c->prep.valid = false;
-  if (materialize && out->n_matches) {
-    const size_t bytes = (size_t)out->n_matches * 8;
-    if (to_host) {
-      if ((rc = ensure_host(c, c->h_key, bytes, false)) != HMJ_OK) return rc;
-      if ((rc = ensure_host(c, c->h_rval, bytes, false)) != HMJ_OK) return rc;
-      if ((rc = ensure_host(c, c->h_sval, bytes, false)) != HMJ_OK) return rc;
-      const int s2 = span_begin(c, K_D2H, -1);
-      HIP_TRY(hipMemcpyAsync(c->h_key.p, c->out_key.p, bytes, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipMemcpyAsync(c->h_rval.p, c->out_rval.p, bytes, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipMemcpyAsync(c->h_sval.p, c->out_sval.p, bytes, hipMemcpyDeviceToHost, c->stream));
-      span_end(c, s2);
-      HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    out->key = (const uint64_t*)(to_host ? c->h_key.p : c->out_key.p);
-    out->rval = (const uint64_t*)(to_host ? c->h_rval.p : c->out_rval.p);
-    out->sval = (const uint64_t*)(to_host ? c->h_sval.p : c->out_sval.p);
-  }
+  if (materialize && out->n_matches)
+    RC_TRY(deliver_columns(c, out, to_host, c->out_key.p, c->out_rval.p, c->out_sval.p, (size_t)out->n_matches * 8, false));
   if (c->trace) std::fprintf(stderr, "[hmj] join nb=%llu np=%llu flags=%#x: global table of 2^%d slots\n",
                              (unsigned long long)n_build, (unsigned long long)n_probe, flags, log_cap);
   *done = true;
@@ -2120,9 +2061,8 @@ static int slab_chain(hmj_ctx* c, const void* dense_in, u32 n, const ChainDigit*
                       u32* pc_cap, int* pc_which) {
   *ok_out = false;
   *pc_n = 0;
-  int rc;
-  if ((rc = ensure_dev(c, c->accum, 8 * sizeof(u64))) != HMJ_OK) return rc;
-  if ((rc = ensure_host(c, c->h_accum, 8 * sizeof(u64))) != HMJ_OK) return rc;
+  RC_TRY(ensure_dev(c, c->accum, 8 * sizeof(u64)));
+  RC_TRY(ensure_host(c, c->h_accum, 8 * sizeof(u64)));
   DevBuf* sl[2] = {&c->slab_a, &c->slab_bs};
   DevBuf* cn[2] = {&c->cnt_a, &c->cnt_bs};
   u64* acc = (u64*)c->accum.p;
@@ -2144,8 +2084,8 @@ static int slab_chain(hmj_ctx* c, const void* dense_in, u32 n, const ChainDigit*
       if (!hmj::slab_geometry_one_pass(n, bits, 1e18, 512, &g, dens)) {
         ok = false;
       } else {
-        if ((rc = ensure_dev(c, *sl[0], g.rows_a * 16)) != HMJ_OK) return rc;
-        if ((rc = ensure_dev(c, *cn[0], ((size_t)g.WA << bits) * 4)) != HMJ_OK) return rc;
+        RC_TRY(ensure_dev(c, *sl[0], g.rows_a * 16));
+        RC_TRY(ensure_dev(c, *cn[0], ((size_t)g.WA << bits) * 4));
         HIP_TRY(hmj::launch_slab_a(dense_in, n, shift, bits, g, sl[0]->p, sl[0]->cap / 16, (u32*)cn[0]->p, cn[0]->cap / 4, acc, c->stream));
         W = g.WA;
         C = g.CA;
@@ -2166,8 +2106,8 @@ static int slab_chain(hmj_ctx* c, const void* dense_in, u32 n, const ChainDigit*
       } else {
         DevBuf& so = *sl[i & 1];
         DevBuf& co = *cn[i & 1];
-        if ((rc = ensure_dev(c, so, pieces * g.CB * 16)) != HMJ_OK) return rc;
-        if ((rc = ensure_dev(c, co, pieces * 4)) != HMJ_OK) return rc;
+        RC_TRY(ensure_dev(c, so, pieces * g.CB * 16));
+        RC_TRY(ensure_dev(c, co, pieces * 4));
         HIP_TRY(hmj::launch_slab_b(sl[(i - 1) & 1]->p, (const u32*)cn[(i - 1) & 1]->p, bprev, shift, bits, g, so.p, so.cap / 16,
                                    (u32*)co.p, co.cap / 4, acc, c->stream));
         W = Wn;
@@ -2190,8 +2130,7 @@ static int slab_chain(hmj_ctx* c, const void* dense_in, u32 n, const ChainDigit*
     }
   }
   if (ok) {
-    HIP_TRY(hipMemcpyAsync(hh, c->accum.p, 8 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    RC_TRY(read_accum(c, &hh));
     if (hh[hmj::ACC_ERR] & hmj::ERR_SLAB) ok = false;
   }
   if (ok) {
@@ -2351,20 +2290,19 @@ int try_small_build_ordered(hmj_ctx* c, const void* R, uint64_t n_build, const v
     c->plan.refused |= HMJ_REFUSED_RANK_SORT_COOLING;
     return HMJ_OK;
   }
-  int rc;
   if (!out) return fail(c, HMJ_E_ARG, "out is NULL");
-  if ((rc = check_rel(c, R, n_build, "build_aos is NULL")) != HMJ_OK) return rc;
-  if ((rc = check_rel(c, S, n_probe, "probe_aos is NULL")) != HMJ_OK) return rc;
+  RC_TRY(check_rel(c, R, n_build, "build_aos is NULL"));
+  RC_TRY(check_rel(c, S, n_probe, "probe_aos is NULL"));
   const u32 nb = (u32)n_build, np = (u32)n_probe;
   const bool extra = flags & (HMJ_CHECKSUM | HMJ_SUM_PROBE);
   c->prep.valid = false;  // rbuf is the build side's sort buffer
-  if ((rc = ensure_dev(c, c->rbuf[0], (size_t)nb * 16)) != HMJ_OK) return rc;
-  if ((rc = ensure_dev(c, c->rbuf[1], (size_t)nb * 16)) != HMJ_OK) return rc;
-  if ((rc = ensure_dev(c, c->sbuf[0], (size_t)np * 16)) != HMJ_OK) return rc;
-  if ((rc = ensure_dev(c, c->sbuf[1], (size_t)np * 16)) != HMJ_OK) return rc;
-  if ((rc = ensure_dev(c, c->accum, 8 * sizeof(u64))) != HMJ_OK) return rc;
-  if ((rc = ensure_dev(c, c->offs64, 8 * sizeof(u64))) != HMJ_OK) return rc;
-  if ((rc = ensure_host(c, c->h_accum, 8 * sizeof(u64))) != HMJ_OK) return rc;
+  RC_TRY(ensure_dev(c, c->rbuf[0], (size_t)nb * 16));
+  RC_TRY(ensure_dev(c, c->rbuf[1], (size_t)nb * 16));
+  RC_TRY(ensure_dev(c, c->sbuf[0], (size_t)np * 16));
+  RC_TRY(ensure_dev(c, c->sbuf[1], (size_t)np * 16));
+  RC_TRY(ensure_dev(c, c->accum, 8 * sizeof(u64)));
+  RC_TRY(ensure_dev(c, c->offs64, 8 * sizeof(u64)));
+  RC_TRY(ensure_host(c, c->h_accum, 8 * sizeof(u64)));
   u64* hh = (u64*)c->h_accum.p;
   auto give_up = [&](const char* why) {
     c->wm->gtable_sort_cooldown = 8;
@@ -2436,11 +2374,11 @@ int try_small_build_ordered(hmj_ctx* c, const void* R, uint64_t n_build, const v
     while (level < 2 && mean + 8.0 * std::sqrt(mean) + 24.0 > (double)hmj::rank_sort_max_run(level)) level++;
     if (mean + 8.0 * std::sqrt(mean) + 24.0 <= (double)hmj::rank_sort_max_run(level)) {
       const u32 P = 1u << h;
-      if ((rc = ensure_dev(c, c->msd_off, ((size_t)P + 1) * 8)) != HMJ_OK) return rc;
+      RC_TRY(ensure_dev(c, c->msd_off, ((size_t)P + 1) * 8));
       HIP_TRY(hipMemsetAsync(c->accum.p, 0, 8 * sizeof(u64), c->stream));
       const void* parted = R;
       if (h > 0) {
-        if ((rc = radix_pass(c, R, c->rbuf[0].p, nb, hb + 1 - h, h, 0, (u64*)c->msd_off.p, 0)) != HMJ_OK) return rc;
+        RC_TRY(radix_pass(c, R, c->rbuf[0].p, nb, hb + 1 - h, h, 0, (u64*)c->msd_off.p, 0));
         parted = c->rbuf[0].p;
       } else {
         const u64 off01[2] = {0, nb};
@@ -2465,7 +2403,7 @@ int try_small_build_ordered(hmj_ctx* c, const void* R, uint64_t n_build, const v
     for (int d = 0; d < 8; d++) {
       if (!(digits & (1u << d))) continue;
       void* dst = c->rbuf[k & 1].p;
-      if ((rc = radix_pass(c, sortedR, dst, nb, 8 * d, 8, 0, nullptr, k ? 1 : 0)) != HMJ_OK) return rc;
+      RC_TRY(radix_pass(c, sortedR, dst, nb, 8 * d, 8, 0, nullptr, k ? 1 : 0));
       sortedR = dst;
       k++;
     }
@@ -2475,7 +2413,7 @@ int try_small_build_ordered(hmj_ctx* c, const void* R, uint64_t n_build, const v
   while (((u64)1 << log_cap) < (u64)c->gtable_slots_per_row * nb) log_cap++;
   while (log_cap > c->gtable_max_log_cap && ((u64)1 << (log_cap - 1)) >= (nb > c->gtable_max_rows ? 2 : 4) * (u64)nb) log_cap--;
   const size_t tab_bytes = (size_t)16 << log_cap;
-  if ((rc = ensure_dev(c, c->gtab, tab_bytes)) != HMJ_OK) return rc;
+  RC_TRY(ensure_dev(c, c->gtab, tab_bytes));
   HIP_TRY(hipMemsetAsync(c->accum.p, 0, 8 * sizeof(u64), c->stream));
   HIP_TRY(hipMemsetAsync(c->gtab.p, 0xFF, tab_bytes, c->stream));
   int sp = span_begin(c, K_PROBE_COUNT, -1);
@@ -2540,8 +2478,7 @@ int try_small_build_ordered(hmj_ctx* c, const void* R, uint64_t n_build, const v
                   "launch_rank_sort_write");
       span_end(c, s2);
       if (r2 != HMJ_OK) return r2;
-      HIP_TRY(hipMemcpyAsync(hh, c->accum.p, 8 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
+      RC_TRY(read_accum(c, &hh));
       if (hh[hmj::ACC_ERR] & hmj::ERR_GTABLE) return 2;
       if (hh[hmj::ACC_PAD] != 0) return 3;
       if (hh[hmj::ACC_ERR] & (hmj::ERR_SLAB | hmj::ERR_FASTPATH)) {
@@ -2585,8 +2522,7 @@ int try_small_build_ordered(hmj_ctx* c, const void* R, uint64_t n_build, const v
     if (!runs_done && run_tb <= 0) {  // (cut runs: the emit below writes ranks, not partition numbers -- on to the composites)
       HIP_TRY(hmj::launch_gtable_emit_ranks(S, np, c->gtab.p, log_cap, (u64*)c->accum.p, c->sbuf[0].p, extra, c->num_cus, c->gtable_wg_per_cu, c->stream));
       span_end(c, sp);
-      HIP_TRY(hipMemcpyAsync(hh, c->accum.p, 8 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
+      RC_TRY(read_accum(c, &hh));
       if (hh[hmj::ACC_ERR] & hmj::ERR_GTABLE) return give_up("the table gave up");
       if (hh[hmj::ACC_PAD] != 0) return give_up("duplicate build keys");
       n = hh[hmj::ACC_N];
@@ -2629,8 +2565,7 @@ int try_small_build_ordered(hmj_ctx* c, const void* R, uint64_t n_build, const v
   HIP_TRY(hmj::launch_gtable_emit(S, np, c->gtab.p, log_cap, svmin, range_bits, (u64*)c->accum.p, c->sbuf[0].p, extra, wide,
                                   c->num_cus, c->gtable_wg_per_cu, c->stream));
   span_end(c, sp);
-  HIP_TRY(hipMemcpyAsync(hh, c->accum.p, 8 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  RC_TRY(read_accum(c, &hh));
   if (hh[hmj::ACC_ERR] & hmj::ERR_GTABLE) return give_up("the table gave up");
   if (hh[hmj::ACC_PAD] != 0) return give_up("duplicate build keys");
   n = hh[hmj::ACC_N];
@@ -2672,7 +2607,7 @@ int try_small_build_ordered(hmj_ctx* c, const void* R, uint64_t n_build, const v
       shift += dg[i].bits;
     }
     bool ok = false;
-    if ((rc = slab_chain(c, c->sbuf[0].p, (u32)n, dg, passes, 1, &ok, &pc_n, &pc_cap, &pc_which)) != HMJ_OK) return rc;
+    RC_TRY(slab_chain(c, c->sbuf[0].p, (u32)n, dg, passes, 1, &ok, &pc_n, &pc_cap, &pc_which));
     if (ok) {
       n_passes = passes;
       c->timing.path |= HMJ_PATH_SLAB;
@@ -2684,27 +2619,27 @@ int try_small_build_ordered(hmj_ctx* c, const void* R, uint64_t n_build, const v
   if (pc_n) {
     // (sorted: the pieces of the chain's last pass)
   } else if (!wide) {
-    if ((rc = lsd(rank_bits + range_bits)) != HMJ_OK) return rc;
+    RC_TRY(lsd(rank_bits + range_bits));
   } else {
-    if ((rc = lsd(range_bits)) != HMJ_OK) return rc;  // {payload, rank} by payload
+    RC_TRY(lsd(range_bits));  // {payload, rank} by payload
     if (n) {
       HIP_TRY(hmj::launch_gtable_swap(sorted, c->sbuf[which ^ 1].p, n, c->num_cus, c->stream));  // -> {rank, payload}
       sorted = c->sbuf[which ^ 1].p;
       which ^= 1;
     }
-    if ((rc = lsd(rank_bits)) != HMJ_OK) return rc;  // stably by rank
+    RC_TRY(lsd(rank_bits));  // stably by rank
   }
   // ---- 6. composites -> result rows
   if (n) {
     const size_t bytes = (size_t)n * 8;
-    if ((rc = ensure_dev(c, c->out_key, bytes)) != HMJ_OK) return rc;
-    if ((rc = ensure_dev(c, c->out_rval, bytes)) != HMJ_OK) return rc;
-    if ((rc = ensure_dev(c, c->out_sval, bytes)) != HMJ_OK) return rc;
+    RC_TRY(ensure_dev(c, c->out_key, bytes));
+    RC_TRY(ensure_dev(c, c->out_rval, bytes));
+    RC_TRY(ensure_dev(c, c->out_sval, bytes));
     sp = span_begin(c, K_PROBE_WRITE, -1);
     if (pc_n) {
       DevBuf& so = pc_which ? c->slab_bs : c->slab_a;
       DevBuf& co = pc_which ? c->cnt_bs : c->cnt_a;
-      if ((rc = ensure_dev(c, c->piece_off, (size_t)pc_n * 8)) != HMJ_OK) return rc;
+      RC_TRY(ensure_dev(c, c->piece_off, (size_t)pc_n * 8));
       HIP_TRY(hmj::launch_piece_offsets((const u32*)co.p, pc_n, (u64*)c->piece_off.p, c->stream));
       HIP_TRY(hmj::launch_gtable_expand_pieces(so.p, (const u32*)co.p, (const u64*)c->piece_off.p, pc_n, pc_cap, sortedR, svmin, range_bits,
                                                (u64*)c->out_key.p, (u64*)c->out_rval.p, (u64*)c->out_sval.p, (u64*)c->accum.p, extra,
@@ -2714,17 +2649,12 @@ int try_small_build_ordered(hmj_ctx* c, const void* R, uint64_t n_build, const v
                                         (u64*)c->out_sval.p, (u64*)c->accum.p, extra, wide, c->num_cus, c->stream));
     }
     span_end(c, sp);
-    HIP_TRY(hipMemcpyAsync(hh, c->accum.p, 8 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    RC_TRY(read_accum(c, &hh));
   }
   }  // (!runs_done)
   std::memset(out, 0, sizeof(*out));
-  out->n_matches = n;
-  out->sum_r = hh[hmj::ACC_SUM_R];
-  out->sum_s = hh[hmj::ACC_SUM_S];
-  out->xor_fold = hh[hmj::ACC_XOR];
-  out->mix_sum = hh[hmj::ACC_MIX];
-  out->sum_probe_all = hh[hmj::ACC_SUM_P];
+  result_sums(out, hh);
+  out->n_matches = n;  // (the rows the emit counted)
   c->timing.path |= HMJ_PATH_GLOBAL_TABLE | HMJ_PATH_ORDER_BY_RANK_SORT;
   if (!runs_done) {
     c->timing.radix_bits = rank_bits + range_bits;
@@ -2732,23 +2662,7 @@ int try_small_build_ordered(hmj_ctx* c, const void* R, uint64_t n_build, const v
   }
   c->timing.n_probe_items = 1;
   c->timing.bytes_probe_write = 16ull * (n_build + n_probe) + 24ull * n;
-  if (n) {
-    const size_t bytes = (size_t)n * 8;
-    if (to_host) {
-      if ((rc = ensure_host(c, c->h_key, bytes, false)) != HMJ_OK) return rc;
-      if ((rc = ensure_host(c, c->h_rval, bytes, false)) != HMJ_OK) return rc;
-      if ((rc = ensure_host(c, c->h_sval, bytes, false)) != HMJ_OK) return rc;
-      const int s2 = span_begin(c, K_D2H, -1);
-      HIP_TRY(hipMemcpyAsync(c->h_key.p, c->out_key.p, bytes, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipMemcpyAsync(c->h_rval.p, c->out_rval.p, bytes, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipMemcpyAsync(c->h_sval.p, c->out_sval.p, bytes, hipMemcpyDeviceToHost, c->stream));
-      span_end(c, s2);
-      HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    out->key = (const uint64_t*)(to_host ? c->h_key.p : c->out_key.p);
-    out->rval = (const uint64_t*)(to_host ? c->h_rval.p : c->out_rval.p);
-    out->sval = (const uint64_t*)(to_host ? c->h_sval.p : c->out_sval.p);
-  }
+  if (n) RC_TRY(deliver_columns(c, out, to_host, c->out_key.p, c->out_rval.p, c->out_sval.p, (size_t)n * 8, false));
   if (c->trace) std::fprintf(stderr, "[hmj] join nb=%u np=%u flags=%#x: ordered by a sort on (rank, payload): %d + %d bits\n", nb, np, flags,
                              rank_bits, range_bits);
   *done = true;
@@ -2796,11 +2710,11 @@ static int join_by_key_ranges(hmj_ctx* c, const void* R, uint64_t n_build, const
   *done = false;
   int rc;
   if (!out) return fail(c, HMJ_E_ARG, "out is NULL");
-  if ((rc = check_rel(c, R, n_build, "build_aos is NULL")) != HMJ_OK) return rc;
-  if ((rc = check_rel(c, S, n_probe, "probe_aos is NULL")) != HMJ_OK) return rc;
+  RC_TRY(check_rel(c, R, n_build, "build_aos is NULL"));
+  RC_TRY(check_rel(c, S, n_probe, "probe_aos is NULL"));
   const u32 nb = (u32)n_build, np = (u32)n_probe;
-  if ((rc = ensure_dev(c, c->offs64, 8 * sizeof(u64))) != HMJ_OK) return rc;
-  if ((rc = ensure_host(c, c->h_accum, 8 * sizeof(u64))) != HMJ_OK) return rc;
+  RC_TRY(ensure_dev(c, c->offs64, 8 * sizeof(u64)));
+  RC_TRY(ensure_host(c, c->h_accum, 8 * sizeof(u64)));
   u64* hh = (u64*)c->h_accum.p;
   // ---- 1. the bits in which keys differ, over both relations
   {
@@ -2817,13 +2731,13 @@ static int join_by_key_ranges(hmj_ctx* c, const void* R, uint64_t n_build, const
   const int shift = hb + 1 - h;
   const u32 D = 1u << h;
   // ---- 2. both relations cut into their 2^h key ranges (stable, dense, + range starts)
-  if ((rc = ensure_dev(c, c->split_r, (size_t)nb * 16 + 16)) != HMJ_OK) return rc;
-  if ((rc = ensure_dev(c, c->split_s, (size_t)np * 16 + 16)) != HMJ_OK) return rc;
-  if ((rc = ensure_dev(c, c->split_off, 2 * ((size_t)D + 1) * 8)) != HMJ_OK) return rc;
+  RC_TRY(ensure_dev(c, c->split_r, (size_t)nb * 16 + 16));
+  RC_TRY(ensure_dev(c, c->split_s, (size_t)np * 16 + 16));
+  RC_TRY(ensure_dev(c, c->split_off, 2 * ((size_t)D + 1) * 8));
   std::vector<u64> off(2 * ((size_t)D + 1));
   u64* od = (u64*)c->split_off.p;
-  if ((rc = radix_pass(c, R, c->split_r.p, nb, shift, h, 0, od, 0)) != HMJ_OK) return rc;
-  if ((rc = radix_pass(c, S, c->split_s.p, np, shift, h, 1, od + D + 1, 0)) != HMJ_OK) return rc;
+  RC_TRY(radix_pass(c, R, c->split_r.p, nb, shift, h, 0, od, 0));
+  RC_TRY(radix_pass(c, S, c->split_s.p, np, shift, h, 1, od + D + 1, 0));
   HIP_TRY(hipMemcpyAsync(off.data(), od, off.size() * 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   // ---- 3. range after range: a join of its own, its rows appended
@@ -2863,9 +2777,9 @@ static int join_by_key_ranges(hmj_ctx* c, const void* R, uint64_t n_build, const
     if (sub.n_matches) {
       if (rows_done == 0 && d + 1 < D) {  // (first range: room for the whole result at this range's rate, so that growing is rare)
         const double est = (double)sub.n_matches * (double)np / (double)ns * 1.05 + 4096.0;
-        if ((rc = grow(est > (double)sub.n_matches ? (u64)est : sub.n_matches)) != HMJ_OK) return rc;
+        RC_TRY(grow(est > (double)sub.n_matches ? (u64)est : sub.n_matches));
       }
-      if ((rc = grow(rows_done + sub.n_matches)) != HMJ_OK) return rc;
+      RC_TRY(grow(rows_done + sub.n_matches));
       const size_t bytes = (size_t)sub.n_matches * 8;
       HIP_TRY(hipMemcpyAsync((u64*)c->cat_key.p + rows_done, sub.key, bytes, hipMemcpyDeviceToDevice, c->stream));
       HIP_TRY(hipMemcpyAsync((u64*)c->cat_rval.p + rows_done, sub.rval, bytes, hipMemcpyDeviceToDevice, c->stream));
@@ -3374,7 +3288,7 @@ int hmj_reserve(hmj_ctx* c, uint64_t n_build, uint64_t n_probe, uint64_t max_mat
     explicit InReserve(hmj_ctx* c_) : c(c_) { c->in_reserve = true; }
     ~InReserve() { c->in_reserve = false; }
   } in_reserve(c);
-  int B, passes, pass_bits[4], rc;
+  int B, passes, pass_bits[4];
   plan_bits(n_build, c->force_bits, &B, &passes, pass_bits);
   const size_t P = (size_t)1 << B;
   const size_t items = P < 4096 ? 4096 : P;
@@ -3388,39 +3302,39 @@ int hmj_reserve(hmj_ctx* c, uint64_t n_build, uint64_t n_probe, uint64_t max_mat
                          hmj::slab_geometry((u32)n_build, pass_bits[0], pass_bits[1], &gr) &&
                          hmj::slab_geometry((u32)n_probe, pass_bits[0], pass_bits[1], &gs);
   if (passes >= 1 && !slab_plan) {
-    if ((rc = ensure_dev(c, c->rbuf[0], n_build * 16)) != HMJ_OK) return rc;
-    if ((rc = ensure_dev(c, c->sbuf[0], n_probe * 16)) != HMJ_OK) return rc;
+    RC_TRY(ensure_dev(c, c->rbuf[0], n_build * 16));
+    RC_TRY(ensure_dev(c, c->sbuf[0], n_probe * 16));
   }
   if (passes >= 2 && !slab_plan) {
-    if ((rc = ensure_dev(c, c->rbuf[1], n_build * 16)) != HMJ_OK) return rc;
-    if ((rc = ensure_dev(c, c->sbuf[1], n_probe * 16)) != HMJ_OK) return rc;
+    RC_TRY(ensure_dev(c, c->rbuf[1], n_build * 16));
+    RC_TRY(ensure_dev(c, c->sbuf[1], n_probe * 16));
   }
   if (slab_plan) {
     const u64 rows_a = gr.rows_a > gs.rows_a ? gr.rows_a : gs.rows_a;
     const u32 wa = gr.WA > gs.WA ? gr.WA : gs.WA;
-    if ((rc = ensure_dev(c, c->slab_a, rows_a * 16)) != HMJ_OK) return rc;
-    if ((rc = ensure_dev(c, c->cnt_a, ((size_t)wa << pass_bits[0]) * 4)) != HMJ_OK) return rc;
-    if ((rc = ensure_dev(c, c->slab_br, gr.rows_b * 16)) != HMJ_OK) return rc;
-    if ((rc = ensure_dev(c, c->slab_bs, gs.rows_b * 16)) != HMJ_OK) return rc;
-    if ((rc = ensure_dev(c, c->cnt_br, P * gr.KB * 4)) != HMJ_OK) return rc;
-    if ((rc = ensure_dev(c, c->cnt_bs, P * gs.KB * 4)) != HMJ_OK) return rc;
+    RC_TRY(ensure_dev(c, c->slab_a, rows_a * 16));
+    RC_TRY(ensure_dev(c, c->cnt_a, ((size_t)wa << pass_bits[0]) * 4));
+    RC_TRY(ensure_dev(c, c->slab_br, gr.rows_b * 16));
+    RC_TRY(ensure_dev(c, c->slab_bs, gs.rows_b * 16));
+    RC_TRY(ensure_dev(c, c->cnt_br, P * gr.KB * 4));
+    RC_TRY(ensure_dev(c, c->cnt_bs, P * gs.KB * 4));
   }
-  if ((rc = ensure_dev(c, c->hist, (size_t)hmj::RP_MAXD * hmj::RP_MAX_BLOCKS * 4)) != HMJ_OK) return rc;
-  if ((rc = ensure_dev(c, c->totals, (size_t)hmj::RP_MAXD * 4)) != HMJ_OK) return rc;
-  if ((rc = ensure_dev(c, c->r_off, (P + 1) * 4)) != HMJ_OK) return rc;
-  if ((rc = ensure_dev(c, c->s_off, (P + 1) * 4)) != HMJ_OK) return rc;
-  if ((rc = ensure_dev(c, c->accum, 64)) != HMJ_OK) return rc;
-  if ((rc = ensure_host(c, c->h_accum, 64)) != HMJ_OK) return rc;
+  RC_TRY(ensure_dev(c, c->hist, (size_t)hmj::RP_MAXD * hmj::RP_MAX_BLOCKS * 4));
+  RC_TRY(ensure_dev(c, c->totals, (size_t)hmj::RP_MAXD * 4));
+  RC_TRY(ensure_dev(c, c->r_off, (P + 1) * 4));
+  RC_TRY(ensure_dev(c, c->s_off, (P + 1) * 4));
+  RC_TRY(ensure_dev(c, c->accum, 64));
+  RC_TRY(ensure_host(c, c->h_accum, 64));
   if (flags & (HMJ_MATERIALIZE | HMJ_ORDERED)) {
-    if ((rc = ensure_dev(c, c->part_count, items * 8)) != HMJ_OK) return rc;
-    if ((rc = ensure_dev(c, c->part_out_off, (items + 1) * 8)) != HMJ_OK) return rc;
-    if ((rc = ensure_dev(c, c->out_key, max_matches * 8)) != HMJ_OK) return rc;
-    if ((rc = ensure_dev(c, c->out_rval, max_matches * 8)) != HMJ_OK) return rc;
-    if ((rc = ensure_dev(c, c->out_sval, max_matches * 8)) != HMJ_OK) return rc;
+    RC_TRY(ensure_dev(c, c->part_count, items * 8));
+    RC_TRY(ensure_dev(c, c->part_out_off, (items + 1) * 8));
+    RC_TRY(ensure_dev(c, c->out_key, max_matches * 8));
+    RC_TRY(ensure_dev(c, c->out_rval, max_matches * 8));
+    RC_TRY(ensure_dev(c, c->out_sval, max_matches * 8));
     if (flags & HMJ_ORDERED) {
-      if ((rc = ensure_dev(c, c->ord_key, max_matches * 8)) != HMJ_OK) return rc;
-      if ((rc = ensure_dev(c, c->ord_rval, max_matches * 8)) != HMJ_OK) return rc;
-      if ((rc = ensure_dev(c, c->ord_sval, max_matches * 8)) != HMJ_OK) return rc;
+      RC_TRY(ensure_dev(c, c->ord_key, max_matches * 8));
+      RC_TRY(ensure_dev(c, c->ord_rval, max_matches * 8));
+      RC_TRY(ensure_dev(c, c->ord_sval, max_matches * 8));
     }
   }
   return HMJ_OK;
@@ -3546,16 +3460,16 @@ static int join_host_impl(hmj_ctx* c, const void* build_aos_host, uint64_t n_bui
   HIP_TRY(hipSetDevice(c->device));
   spans_reset(c);
   int rc;
-  if ((rc = ensure_dev(c, c->in_r, n_build * 16 + 16)) != HMJ_OK) return rc;
-  if ((rc = ensure_dev(c, c->in_s, n_probe * 16 + 16)) != HMJ_OK) return rc;
+  RC_TRY(ensure_dev(c, c->in_r, n_build * 16 + 16));
+  RC_TRY(ensure_dev(c, c->in_s, n_probe * 16 + 16));
   const auto t0 = std::chrono::steady_clock::now();
   // small inputs, the staged multi-thread upload, or no pipeline wanted (HMJ_HOST_PIPELINE=0): the serial form
   constexpr uint64_t kPipeMinRows = 1ull << 22;
   const int kChunks = 8;
   const bool pipeline = c->host_pipeline && !c->staged_upload && n_build >= kPipeMinRows && n_probe >= kPipeMinRows;
   if (!pipeline) {
-    if ((rc = upload_host(c, c->in_r.p, build_aos_host, n_build * 16)) != HMJ_OK) return rc;
-    if ((rc = upload_host(c, c->in_s.p, probe_aos_host, n_probe * 16)) != HMJ_OK) return rc;
+    RC_TRY(upload_host(c, c->in_r.p, build_aos_host, n_build * 16));
+    RC_TRY(upload_host(c, c->in_s.p, probe_aos_host, n_probe * 16));
     HIP_TRY(hipStreamSynchronize(c->stream));
     const float ms_h2d = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     int st = span_begin(c, K_TOTAL, -1);
@@ -3696,18 +3610,16 @@ int hmj_partition_u64_device(hmj_ctx* c, const void* in_aos_dev, uint64_t n, int
   if (!c) return HMJ_E_ARG;
   if (bits < 1 || bits > hmj::RP_MAX_BITS || shift < 0 || shift + bits > 64)
     return fail(c, HMJ_E_ARG, "bits must be in 1..9 and shift+bits <= 64");
-  int rc;
-  if ((rc = check_rel(c, in_aos_dev, n, "in_aos is NULL")) != HMJ_OK) return rc;
-  if ((rc = check_rel(c, out_aos_dev, n, "out_aos is NULL")) != HMJ_OK) return rc;
+  RC_TRY(check_rel(c, in_aos_dev, n, "in_aos is NULL"));
+  RC_TRY(check_rel(c, out_aos_dev, n, "out_aos is NULL"));
   if (!offsets_dev) return fail(c, HMJ_E_ARG, "offsets_dev is NULL");
   HIP_TRY(hipSetDevice(c->device));
   spans_reset(c);
   c->prep.valid = false;  // "any other call discards the prepared state" (hmj.h)
   if (n == 0) {
     HIP_TRY(hipMemsetAsync(offsets_dev, 0, ((size_t)(1u << bits) + 1) * 8, c->stream));
-  } else if ((rc = radix_pass(c, in_aos_dev, out_aos_dev, (u32)n, shift, bits, -1,
-                              (u64*)offsets_dev)) != HMJ_OK) {
-    return rc;
+  } else {
+    RC_TRY(radix_pass(c, in_aos_dev, out_aos_dev, (u32)n, shift, bits, -1, (u64*)offsets_dev));
   }
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (c->profiling) spans_collect(c);
@@ -3716,15 +3628,14 @@ int hmj_partition_u64_device(hmj_ctx* c, const void* in_aos_dev, uint64_t n, int
 
 int hmj_sort_u64_device(hmj_ctx* c, const void* in_aos_dev, uint64_t n, void* out_aos_dev) {
   if (!c) return HMJ_E_ARG;
-  int rc;
-  if ((rc = check_rel(c, in_aos_dev, n, "in_aos is NULL")) != HMJ_OK) return rc;
-  if ((rc = check_rel(c, out_aos_dev, n, "out_aos is NULL")) != HMJ_OK) return rc;
+  RC_TRY(check_rel(c, in_aos_dev, n, "in_aos is NULL"));
+  RC_TRY(check_rel(c, out_aos_dev, n, "out_aos is NULL"));
   HIP_TRY(hipSetDevice(c->device));
   spans_reset(c);
   c->prep.valid = false;  // rbuf[0] is the sort's ping-pong buffer (an empty sort discards too, like every other call)
   if (n == 0) return HMJ_OK;
   memo_for(c, workload_signature(n, 0, 0, 1));  // (what earlier sorts of this size learnt: the chain's cool-down)
-  if ((rc = ensure_dev(c, c->rbuf[0], (size_t)n * 16)) != HMJ_OK) return rc;
+  RC_TRY(ensure_dev(c, c->rbuf[0], (size_t)n * 16));
   // Digits in which no key differs need no pass (a stable pass on a constant digit is a copy): integer ids below 2^32
   // sort in four passes instead of eight (dense keys, 2^26 rows: 5.58 -> 2.93 ms, 2^28: 21.4 -> 10.8 ms = 24.8 G keys/s,
   // tools/exp_cliffs_sort.py; from 2^22 rows on -- below, the two host round trips cost more than the passes saved).  A sample of the keys
@@ -3734,8 +3645,8 @@ int hmj_sort_u64_device(hmj_ctx* c, const void* in_aos_dev, uint64_t n, void* ou
   u64 diff = ~0ull, kmin = 0, kmax = ~0ull;  // the bits in which keys differ; exact (with the extremes) when != ~0
   u64 sdiff = ~0ull;                          // the bits in which the SAMPLED keys differ
   if (n >= (1u << 22)) {
-    if ((rc = ensure_dev(c, c->offs64, 8 * sizeof(u64))) != HMJ_OK) return rc;
-    if ((rc = ensure_host(c, c->h_accum, 8 * sizeof(u64))) != HMJ_OK) return rc;
+    RC_TRY(ensure_dev(c, c->offs64, 8 * sizeof(u64)));
+    RC_TRY(ensure_host(c, c->h_accum, 8 * sizeof(u64)));
     u64* h = (u64*)c->h_accum.p;
     HIP_TRY(hmj::launch_key_sample(in_aos_dev, (u32)n, nullptr, 0u, (u64*)c->offs64.p, c->stream));
     HIP_TRY(hipMemcpyAsync(h, c->offs64.p, 8 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
@@ -3805,14 +3716,14 @@ int hmj_sort_u64_device(hmj_ctx* c, const void* in_aos_dev, uint64_t n, void* ou
     if (TB >= 2 && ba <= hmj::SLAB_MAX_BITS && mean + 8.0 * std::sqrt(mean) + 24.0 <= (double)hmj::rank_sort_max_run(level) &&
         hmj::slab_geometry((u32)n, ba, bb, &g, 0, 1.0, dens)) {
       const u32 P = 1u << TB;
-      if ((rc = ensure_dev(c, c->accum, 8 * sizeof(u64))) != HMJ_OK) return rc;
-      if ((rc = ensure_host(c, c->h_accum, 8 * sizeof(u64))) != HMJ_OK) return rc;
-      if ((rc = ensure_dev(c, c->slab_a, g.rows_a * 16)) != HMJ_OK) return rc;
-      if ((rc = ensure_dev(c, c->cnt_a, ((size_t)g.WA << ba) * 4)) != HMJ_OK) return rc;
-      if ((rc = ensure_dev(c, c->slab_bs, g.rows_b * 16)) != HMJ_OK) return rc;
-      if ((rc = ensure_dev(c, c->cnt_bs, (size_t)P * g.KB * 4)) != HMJ_OK) return rc;
-      if ((rc = ensure_dev(c, c->part_out_off, ((size_t)P + 1) * 8)) != HMJ_OK) return rc;
-      if ((rc = ensure_dev(c, c->part_count, ((size_t)P / 1024 + 1) * 8)) != HMJ_OK) return rc;
+      RC_TRY(ensure_dev(c, c->accum, 8 * sizeof(u64)));
+      RC_TRY(ensure_host(c, c->h_accum, 8 * sizeof(u64)));
+      RC_TRY(ensure_dev(c, c->slab_a, g.rows_a * 16));
+      RC_TRY(ensure_dev(c, c->cnt_a, ((size_t)g.WA << ba) * 4));
+      RC_TRY(ensure_dev(c, c->slab_bs, g.rows_b * 16));
+      RC_TRY(ensure_dev(c, c->cnt_bs, (size_t)P * g.KB * 4));
+      RC_TRY(ensure_dev(c, c->part_out_off, ((size_t)P + 1) * 8));
+      RC_TRY(ensure_dev(c, c->part_count, ((size_t)P / 1024 + 1) * 8));
       u64* acc = (u64*)c->accum.p;
       u64* hh = (u64*)c->h_accum.p;
       HIP_TRY(hipMemsetAsync(c->accum.p, 0, 8 * sizeof(u64), c->stream));
@@ -3828,8 +3739,7 @@ int hmj_sort_u64_device(hmj_ctx* c, const void* in_aos_dev, uint64_t n, void* ou
       HIP_TRY(hmj::launch_sort_runs_write(c->slab_bs.p, (const u32*)c->cnt_bs.p, g.CB, P, (const u64*)c->part_out_off.p, out_aos_dev, acc, level,
                                           c->num_cus, c->stream));
       span_end(c, sp);
-      HIP_TRY(hipMemcpyAsync(hh, c->accum.p, 8 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
+      RC_TRY(read_accum(c, &hh));
       if (hh[hmj::ACC_ERR] & (hmj::ERR_SLAB | hmj::ERR_FASTPATH)) {
         c->wm->sort_msd_cooldown = 8;
         HIP_TRY(hipMemsetAsync((u64*)c->accum.p + hmj::ACC_ERR, 0, sizeof(u64), c->stream));
@@ -3874,11 +3784,11 @@ int hmj_sort_u64_device(hmj_ctx* c, const void* in_aos_dev, uint64_t n, void* ou
     bool ok = false;
     u32 pc_n = 0, pc_cap = 0;
     int pc_which = 0;
-    if ((rc = hmj_host::slab_chain(c, in_aos_dev, (u32)n, dg, nd, -1, &ok, &pc_n, &pc_cap, &pc_which)) != HMJ_OK) return rc;
+    RC_TRY(hmj_host::slab_chain(c, in_aos_dev, (u32)n, dg, nd, -1, &ok, &pc_n, &pc_cap, &pc_which));
     if (ok) {
       DevBuf& so = pc_which ? c->slab_bs : c->slab_a;
       DevBuf& co = pc_which ? c->cnt_bs : c->cnt_a;
-      if ((rc = ensure_dev(c, c->piece_off, (size_t)pc_n * 8)) != HMJ_OK) return rc;
+      RC_TRY(ensure_dev(c, c->piece_off, (size_t)pc_n * 8));
       HIP_TRY(hmj::launch_piece_offsets((const u32*)co.p, pc_n, (u64*)c->piece_off.p, c->stream));
       const int sp = span_begin(c, K_SCATTER, -1, nd);
       HIP_TRY(hmj::launch_pieces_compact(so.p, (const u32*)co.p, (const u64*)c->piece_off.p, pc_n, pc_cap, out_aos_dev, c->num_cus, c->stream));
@@ -3902,7 +3812,7 @@ int hmj_sort_u64_device(hmj_ctx* c, const void* in_aos_dev, uint64_t n, void* ou
     for (int d = 0; d < 8; d++) {  // LSD: bits [8 d, 8 d + 8)
       if (!(digits & (1u << d))) continue;
       void* dst = ((left & 1) == (end_in_out ? 1 : 0)) ? out_aos_dev : tmp;
-      if ((rc = radix_pass(c, src, dst, (u32)n, 8 * d, 8, -1, nullptr)) != HMJ_OK) return rc;
+      RC_TRY(radix_pass(c, src, dst, (u32)n, 8 * d, 8, -1, nullptr));
       src = dst;
       left--;
     }
@@ -3915,12 +3825,11 @@ int hmj_sort_u64_device(hmj_ctx* c, const void* in_aos_dev, uint64_t n, void* ou
 
 // {key, index} pairs in rbuf[0] -> sorted by key (stable), back in rbuf[0]: eight 8-bit LSD passes
 static int sort_pairs_in_rbuf(hmj_ctx* c, u64 n) {
-  int rc;
   c->prep.valid = false;
-  if ((rc = ensure_dev(c, c->rbuf[0], (size_t)n * 16)) != HMJ_OK) return rc;
-  if ((rc = ensure_dev(c, c->rbuf[1], (size_t)n * 16)) != HMJ_OK) return rc;
+  RC_TRY(ensure_dev(c, c->rbuf[0], (size_t)n * 16));
+  RC_TRY(ensure_dev(c, c->rbuf[1], (size_t)n * 16));
   for (int pass = 0; pass < 8; pass++)
-    if ((rc = radix_pass(c, c->rbuf[pass & 1].p, c->rbuf[(pass & 1) ^ 1].p, (u32)n, 8 * pass, 8, -1, nullptr)) != HMJ_OK) return rc;
+    RC_TRY(radix_pass(c, c->rbuf[pass & 1].p, c->rbuf[(pass & 1) ^ 1].p, (u32)n, 8 * pass, 8, -1, nullptr));
   return HMJ_OK;
 }
 
@@ -3933,15 +3842,14 @@ int hmj_sort_rows_by_u64_host(hmj_ctx* c, void* rows_host, uint64_t n, uint32_t 
   spans_reset(c);
   c->prep.valid = false;  // "any other call discards the prepared state" (hmj.h), whatever n
   if (n < 2) return HMJ_OK;
-  int rc;
   const size_t bytes = (size_t)n * row_bytes;
   const u32 words = row_bytes / 8;
-  if ((rc = ensure_dev(c, c->in_r, bytes)) != HMJ_OK) return rc;
-  if ((rc = ensure_dev(c, c->in_s, bytes)) != HMJ_OK) return rc;
-  if ((rc = ensure_dev(c, c->rbuf[0], (size_t)n * 16)) != HMJ_OK) return rc;
+  RC_TRY(ensure_dev(c, c->in_r, bytes));
+  RC_TRY(ensure_dev(c, c->in_s, bytes));
+  RC_TRY(ensure_dev(c, c->rbuf[0], (size_t)n * 16));
   HIP_TRY(hipMemcpyAsync(c->in_r.p, rows_host, bytes, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hmj::launch_rows_key_idx(c->in_r.p, n, words, key_offset / 8, c->rbuf[0].p, c->stream));
-  if ((rc = sort_pairs_in_rbuf(c, n)) != HMJ_OK) return rc;
+  RC_TRY(sort_pairs_in_rbuf(c, n));
   HIP_TRY(hmj::launch_rows_gather(c->in_r.p, c->rbuf[0].p, n, words, c->in_s.p, c->stream));
   HIP_TRY(hipMemcpyAsync(rows_host, c->in_s.p, bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -3955,12 +3863,11 @@ int hmj_argsort_u64_host(hmj_ctx* c, const void* keys_host, uint64_t n, uint32_t
   spans_reset(c);
   c->prep.valid = false;  // "any other call discards the prepared state" (hmj.h), whatever n
   if (n == 0) return HMJ_OK;
-  int rc;
-  if ((rc = ensure_dev(c, c->in_r, (size_t)n * 8)) != HMJ_OK) return rc;
-  if ((rc = ensure_dev(c, c->rbuf[0], (size_t)n * 16)) != HMJ_OK) return rc;
+  RC_TRY(ensure_dev(c, c->in_r, (size_t)n * 8));
+  RC_TRY(ensure_dev(c, c->rbuf[0], (size_t)n * 16));
   HIP_TRY(hipMemcpy2DAsync(c->in_r.p, 8, keys_host, stride_bytes, 8, n, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hmj::launch_key_idx((const u64*)c->in_r.p, n, c->rbuf[0].p, c->stream));
-  if ((rc = sort_pairs_in_rbuf(c, n)) != HMJ_OK) return rc;
+  RC_TRY(sort_pairs_in_rbuf(c, n));
   HIP_TRY(hmj::launch_pairs_val_u32(c->rbuf[0].p, n, (u32*)c->in_r.p, c->stream));
   HIP_TRY(hipMemcpyAsync(perm_out, c->in_r.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));

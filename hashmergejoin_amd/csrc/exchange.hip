@@ -143,12 +143,6 @@ struct hmj_comm {
 
 namespace {
 
-#define HIP_TRY(expr)                                           \
-  do {                                                          \
-    hipError_t _e = (expr);                                     \
-    if (_e != hipSuccess) return fail(c, HMJ_E_HIP, #expr, _e); \
-  } while (0)
-
 int rccl_fail(hmj_ctx* c, const char* what, ncclResult_t r) {
   RcclApi* a = rccl_api();
   std::string m = std::string(what) + ": " + (a && a->GetErrorString ? a->GetErrorString(r) : "RCCL error");
@@ -379,9 +373,8 @@ int transport_allgather(hmj_ctx* c, const u64* send, u64* recv, int count) {
   }
   if (m->has_cb) return transport_cb_status(c, m->cb.allgather_u64(m->cb.user, send, recv, count), "transport: allgather_u64");
   RcclApi* a = rccl_api();
-  int rc;
   const size_t bytes = (size_t)count * 8;
-  if ((rc = ensure_dev(c, m->gather_dev, bytes * (m->n_ranks + 1))) != HMJ_OK) return rc;
+  RC_TRY(ensure_dev(c, m->gather_dev, bytes * (m->n_ranks + 1)));
   char* d = static_cast<char*>(m->gather_dev.p);
   HIP_TRY(hipMemcpyAsync(d, send, bytes, hipMemcpyHostToDevice, m->stream));
   {
@@ -474,9 +467,8 @@ int owner_split(hmj_ctx* c, const void* in, u32 n, const hmj::OwnerFn& own, void
   }
   u32 nblk, rpb;
   hmj::radix_pass_geometry(n, hmj::RP_TILE, &nblk, &rpb);
-  int rc;
-  if ((rc = ensure_dev(c, c->hist, (size_t)(1u << bits) * nblk * sizeof(u32))) != HMJ_OK) return rc;
-  if ((rc = ensure_dev(c, c->totals, (size_t)hmj::RP_MAXD * sizeof(u32))) != HMJ_OK) return rc;
+  RC_TRY(ensure_dev(c, c->hist, (size_t)(1u << bits) * nblk * sizeof(u32)));
+  RC_TRY(ensure_dev(c, c->totals, (size_t)hmj::RP_MAXD * sizeof(u32)));
   HIP_TRY(hmj::launch_radix_hist(in, n, hmj::RP_TILE, 0, bits, (u32*)c->hist.p, nblk, rpb, c->stream, &own));
   HIP_TRY(hmj::launch_radix_rowscan((u32*)c->hist.p, nblk, bits, (u32*)c->totals.p, c->stream));
   HIP_TRY(hmj::launch_owner_scatter(in, out, n, bits, own, (const u32*)c->hist.p, (const u32*)c->totals.p, nblk, rpb,
@@ -662,7 +654,7 @@ int exchange_relation(hmj_ctx* c, const void* parted, const u64* counts_matrix, 
       sb[g] = sr[(size_t)r * G + g] * 16;
       rb[g] = rr[(size_t)r * G + g] * 16;
     }
-    if ((rc = transport_round(c, (int)r, sp.data(), sb.data(), rp.data(), rb.data())) != HMJ_OK) return rc;
+    RC_TRY(transport_round(c, (int)r, sp.data(), sb.data(), rp.data(), rb.data()));
     if (ev_after_round) {
       const hipError_t e = hipEventRecord(ev_after_round[r], m->stream);
       if (e != hipSuccess && *soft_err == HMJ_OK) *soft_err = fail(c, HMJ_E_HIP, "hipEventRecord", e);
@@ -971,7 +963,7 @@ int final_reduction(hmj_ctx* c, int mine, const JoinKind& kind, const hmj_result
   for (int g = 0; g < G; g++)
     if (all[W * (size_t)g + 11] != w[11]) return fail(c, HMJ_E_ARG, "the ranks passed different join kinds (side, kind)");
   for (int g = 0; g < G; g++) st[g] = all[W * (size_t)g];
-  if ((rc = settle(c, mine, st)) != HMJ_OK) return rc;
+  RC_TRY(settle(c, mine, st));
   if (global_out) {
     std::memset(global_out, 0, sizeof(*global_out));
     for (int g = 0; g < G; g++) {
@@ -1085,7 +1077,7 @@ int exchange_digit_path(hmj_ctx* c, const void* R, u64 nb, const void* S, u64 np
       st[g] = all[(size_t)g * (D + 1)];
       std::memcpy(&counts[(size_t)g * D], &all[(size_t)g * (D + 1) + 1], (size_t)D * 8);
     }
-    if ((rc = settle(c, *err, st)) != HMJ_OK) return rc;
+    RC_TRY(settle(c, *err, st));
     // rows every rank will own: the 2^32-1 limit of one local join is checked for ALL ranks by ALL ranks
     for (int g = 0; g < G; g++)
       for (int s = 0; s < G; s++)
@@ -1104,7 +1096,7 @@ int exchange_digit_path(hmj_ctx* c, const void* R, u64 nb, const void* S, u64 np
     const bool grows = any_rank_grows(m, 2 + rel, need);
     int mine = ensure_dev(c, recv, (size_t)need[me] * 16 + 16);
     if (grows) {
-      if ((rc = status_round(c, mine)) != HMJ_OK) return rc;
+      RC_TRY(status_round(c, mine));
       note_peaks(m, 2 + rel, need);
     } else if (mine != HMJ_OK) {
       return mine;  // cannot happen: the buffer is at least as large as in an earlier step
@@ -1126,7 +1118,7 @@ int exchange_digit_path(hmj_ctx* c, const void* R, u64 nb, const void* S, u64 np
         sb[g] = sr[(size_t)r * G + g] * 16;
         rb[g] = rr[(size_t)r * G + g] * 16;
       }
-      if ((rc = transport_round(c, (int)(rel * NR + r), sp.data(), sb.data(), rp.data(), rb.data())) != HMJ_OK) return rc;
+      RC_TRY(transport_round(c, (int)(rel * NR + r), sp.data(), sb.data(), rp.data(), rb.data()));
       if (rel == 1) note(hipEventRecord(m->round_ev[r], m->stream), "hipEventRecord");
     }
     if (rel == 0) {
@@ -1265,10 +1257,10 @@ int exchange_owner_path(hmj_ctx* c, const void* build_shard_dev, u64 n_build, co
   }
   m->info.ms_split = ms_since(t_split);
   cnt[0] = *err == HMJ_OK ? 0ull : (u64)(int64_t)*err;
-  if ((rc = transport_allgather(c, cnt.data(), allcnt.data(), 2 * G + 1)) != HMJ_OK) return rc;
+  RC_TRY(transport_allgather(c, cnt.data(), allcnt.data(), 2 * G + 1));
   std::vector<u64> st((size_t)G);
   for (int g = 0; g < G; g++) st[g] = allcnt[(size_t)g * (2 * G + 1)];
-  if ((rc = settle(c, *err, st)) != HMJ_OK) return rc;
+  RC_TRY(settle(c, *err, st));
   std::vector<u64> MR((size_t)G * G), MS((size_t)G * G);  // [src][dst]
   for (int s = 0; s < G; s++)
     for (int d = 0; d < G; d++) {
@@ -1313,7 +1305,7 @@ int exchange_owner_path(hmj_ctx* c, const void* build_shard_dev, u64 n_build, co
     if (mine == HMJ_OK) mine = ensure_dev(c, m->recv_s, (size_t)ns * 16 + 16);
     if (mine == HMJ_OK) mine = ensure_round_events(c, rounds_s);
     if (grows) {
-      if ((rc = status_round(c, mine)) != HMJ_OK) return rc;
+      RC_TRY(status_round(c, mine));
       note_peaks(m, 2, need_r);
       note_peaks(m, 3, need_s);
     } else if (mine != HMJ_OK) {
@@ -1328,12 +1320,11 @@ int exchange_owner_path(hmj_ctx* c, const void* build_shard_dev, u64 n_build, co
     if (e2 != hipSuccess && *err == HMJ_OK) *err = fail(c, HMJ_E_HIP, what, e2);
   };
   note(hipEventRecord(m->ev_t0, m->stream), "hipEventRecord");
-  if ((rc = exchange_relation(c, parted_r, MR.data(), rounds_r, 0, m->recv_r.p, nullptr, nullptr, err)) != HMJ_OK) return rc;
+  RC_TRY(exchange_relation(c, parted_r, MR.data(), rounds_r, 0, m->recv_r.p, nullptr, nullptr, err));
   note(hipEventRecord(m->ev_build, m->stream), "hipEventRecord");
   note(hipEventRecord(m->ev_t1, m->stream), "hipEventRecord");
   std::vector<u64> round_end(rounds_s);
-  if ((rc = exchange_relation(c, parted_s, MS.data(), rounds_s, 1, m->recv_s.p, m->round_ev.data(), round_end.data(), err)) != HMJ_OK)
-    return rc;
+  RC_TRY(exchange_relation(c, parted_s, MS.data(), rounds_s, 1, m->recv_s.p, m->round_ev.data(), round_end.data(), err));
   note(hipEventRecord(m->ev_t2, m->stream), "hipEventRecord");
 
   // ---- local join: build side as soon as it is complete, probe side as its rounds arrive

@@ -264,8 +264,23 @@ struct hmj_ctx {
 };
 
 
+// The hmj_host helpers every host translation unit shares, and the two macros that propagate their errors.  Both macros
+// return from the enclosing function, which must have the context in scope as `c`:
+//   HIP_TRY(expr): a HIP call; on failure fail(c, HMJ_E_HIP, "<the expression's text>", error)
+//   RC_TRY(expr):  a call that returns an HMJ_* code; anything but HMJ_OK is passed on as it is (the internal retry
+//                  codes included -- a caller that inspects the code does not use the macro)
 namespace hmj_host {
 int fail(hmj_ctx* c, int code, const char* what, hipError_t e = hipSuccess);
+#define HIP_TRY(expr)                                                        \
+  do {                                                                       \
+    hipError_t _e = (expr);                                                  \
+    if (_e != hipSuccess) return ::hmj_host::fail(c, HMJ_E_HIP, #expr, _e); \
+  } while (0)
+#define RC_TRY(expr)               \
+  do {                             \
+    const int _rc = (expr);        \
+    if (_rc != HMJ_OK) return _rc; \
+  } while (0)
 // the per-phase times and byte counts of one (sub-)join, added to a call's totals (exchange rounds, key ranges); api.hip
 void add_timing(hmj_timing* acc, const hmj_timing& t);
 int ensure_dev(hmj_ctx* c, DevBuf& b, size_t bytes);

@@ -30,17 +30,6 @@ using hmj::u32;
 using hmj::u64;
 using namespace hmj_host;
 
-#define HIP_TRY(expr)                                           \
-  do {                                                          \
-    hipError_t _e = (expr);                                     \
-    if (_e != hipSuccess) return fail(c, HMJ_E_HIP, #expr, _e); \
-  } while (0)
-#define RC_TRY(expr)               \
-  do {                             \
-    const int _rc = (expr);        \
-    if (_rc != HMJ_OK) return _rc; \
-  } while (0)
-
 constexpr int KJ_THREADS = 256;
 constexpr int KJ_WAVES = KJ_THREADS / 64;
 constexpr int kRunCap = 1024;         // rows of one mixed run the collision sort holds (one workgroup)

@@ -27,18 +27,6 @@ using namespace hmj_host;
 
 namespace {
 
-#define HIP_TRY(expr)                                           \
-  do {                                                          \
-    hipError_t _e = (expr);                                     \
-    if (_e != hipSuccess) return fail(c, HMJ_E_HIP, #expr, _e); \
-  } while (0)
-
-#define RC_TRY(expr)               \
-  do {                             \
-    const int _rc = (expr);        \
-    if (_rc != HMJ_OK) return _rc; \
-  } while (0)
-
 constexpr int TK_THREADS = 256;
 constexpr int TK_WAVES = TK_THREADS / 64;
 constexpr int kTakeChunk = 8;  // columns per launch

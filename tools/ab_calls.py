@@ -1,0 +1,233 @@
+#!/usr/bin/env python3
+"""Parent against change, call by call: a fixed list of calls -- one or two per plan of the u64 join driver, shapes from the
+tests -- against the library HMJ_LIB names, one JSON record per call: return code, hmj_last_error, every field of
+hmj_last_timing that is not a time, hmj_last_plan, the six sums, and (materialising calls) which result columns are null
+and hashes of the rows -- of the row set, and for ordered calls of the row sequence (an unordered result's sequence is
+whatever order the workgroups reached the output cursor in: it differs from run to run of ONE library).  Every call is
+issued three times in a row on its context (cool-downs).  Two libraries built from a host-only refactor must write
+identical files:
+
+    HMJ_LIB=<parent .so> python tools/ab_calls.py parent.jsonl
+    HMJ_LIB=<change .so> python tools/ab_calls.py change.jsonl   # a process each
+    cmp parent.jsonl change.jsonl
+"""
+import ctypes as C
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+import hashmergejoin_amd as H
+from hashmergejoin_amd import _lib
+from hashmergejoin_amd.join import _memcpy_d2d
+
+M, O, F, CK, SP = H.HMJ_MATERIALIZE, H.HMJ_ORDERED, H.HMJ_FIRST_WINS, H.HMJ_CHECKSUM, H.HMJ_SUM_PROBE
+TIMING = ("path", "radix_bits", "radix_passes", "key_prefix_bits", "key_window_low", "n_probe_items", "n_split_retries",
+          "bytes_scatter", "bytes_hist", "bytes_probe_count", "bytes_probe_write")
+SUMS = ("n_matches", "sum_r", "sum_s", "xor_fold", "mix_sum", "sum_probe_all")
+out_f = open(sys.argv[1], "w") if len(sys.argv) > 1 else sys.stdout
+n_records = 0
+
+
+def executor(**env):
+    """An executor created under HMJ_* settings (read once at hmj_create)."""
+    os.environ.update({k: str(v) for k, v in env.items()})
+    try:
+        return H.Executor(0)
+    finally:
+        for k in env:
+            del os.environ[k]
+
+
+def to_dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a, np.uint64).reshape(-1, 2).view(np.int64).copy()).cuda()
+
+
+def to_np(t):
+    return t.cpu().numpy().view(np.uint64)
+
+
+def zipf_thresholds(domain, theta=0.9):
+    w = 1.0 / np.arange(1, domain + 1, dtype=np.float64) ** theta
+    cdf = np.cumsum(w) / w.sum()
+    thr = np.empty(domain, np.uint64)
+    big = cdf >= 1.0 - 2.0 ** -53
+    thr[~big] = (cdf[~big] * 2.0 ** 64).astype(np.uint64)
+    thr[big] = np.uint64(0xFFFFFFFFFFFFFFFF)
+    thr[-1] = np.uint64(0xFFFFFFFFFFFFFFFF)
+    return torch.from_numpy(thr.view(np.int64).copy()).cuda()
+
+
+def column(ex, ptr, n, host):
+    if host:
+        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint64)), shape=(n,)).copy()
+    tmp = torch.empty(n, dtype=torch.int64, device="cuda:0")
+    _memcpy_d2d(torch, tmp, ptr, n * 8)
+    return tmp.cpu().numpy().view(np.uint64)
+
+
+def rows_digest(ex, res, host, ordered):
+    """Null columns, a hash of the row set and (ordered) one of the row sequence (uint64 arithmetic wraps)."""
+    n = int(res.n_matches)
+    ptrs = (res.key, res.rval, res.sval)
+    d = {"null_cols": [not p for p in ptrs]}
+    if n == 0 or not res.key:
+        return d
+    with np.errstate(over="ignore"):
+        h = np.zeros(n, np.uint64)
+        for p, mul in zip(ptrs, (0x9E3779B97F4A7C15, 0xC2B2AE3D27D4EB4F, 0x165667B19E3779F9)):
+            if p:
+                h = (h ^ column(ex, p, n, host)) * np.uint64(mul)
+                h ^= h >> np.uint64(29)
+        d["rows_set"] = [int(h.sum(dtype=np.uint64)), int((h * h).sum(dtype=np.uint64))]
+        if ordered:
+            d["rows_seq"] = int((h * (np.arange(n, dtype=np.uint64) * np.uint64(2) + np.uint64(1))).sum(dtype=np.uint64))
+    return d
+
+
+def record(name, ex, fn, host=False, ordered=False, repeat=3):
+    """fn() -> JoinResult or (JoinResult, counters); an HmjError is part of the record."""
+    global n_records
+    for i in range(repeat):
+        rec = {"call": name, "i": i}
+        try:
+            got = fn()
+            res, extra = got if isinstance(got, tuple) else (got, None)
+            rec["rc"] = 0
+            rec.update({k: int(getattr(res, k)) for k in SUMS})
+            if extra is not None:
+                rec["counts"] = extra
+            rec.update(rows_digest(ex, res, host, ordered))
+        except H.HmjError as e:
+            rec["rc"] = e.code
+        rec["last_error"] = ex.L.hmj_last_error(ex.h).decode()
+        t = ex.last_timing()
+        rec["timing"] = {k: int(t[k]) for k in TIMING}
+        rec["plan"] = ex.last_plan()
+        out_f.write(json.dumps(rec, sort_keys=True) + "\n")
+        out_f.flush()
+        n_records += 1
+
+
+def joins(name, ex, R, S, flag_list, **kw):
+    for fl in flag_list:
+        record("%s flags=%#x" % (name, fl), ex, lambda: ex.join_device(R, S, fl), ordered=bool(fl & O), **kw)
+
+
+def host_join(name, ex, R, S, flags=M):
+    Rh, Sh = (R if isinstance(R, np.ndarray) else to_np(R)), (S if isinstance(S, np.ndarray) else to_np(S))
+    record("%s host flags=%#x" % (name, flags), ex, lambda: ex.join_host(Rh, Sh, flags), host=True, ordered=bool(flags & O))
+
+
+rng = np.random.default_rng(7)
+ex = executor(HMJ_SLAB_MIN_LOG2=22)           # (the slab plans from 2^22 rows on, as in the tests)
+exp = executor(HMJ_SLAB_MIN_LOG2=22, HMJ_GTABLE=0)  # ... and small joins on the partitioned plans
+
+# ---- full slab path: count modes, the unique-key write on top (unordered and ordered, with and without unmatched rows)
+nb = (1 << 22) + 1000
+R, S, Sm = ex.gen_build(nb), ex.gen_probe(nb, nb), ex.gen_probe(nb + 4321, nb, miss_mod=3)
+joins("slab", ex, R, S, (0, CK, F | CK | SP, M | CK, O | CK))
+joins("slab miss", ex, R, Sm, (CK, M | CK, O | CK))
+host_join("slab", ex, R, Sm)
+# ... and a build side prepared ahead, reused
+record("slab prepared", ex, lambda: (ex.prepare_build(R, nb), ex.join_device(R, S, 0))[1])
+# ---- exact path, a hot foreign key: split partitions
+Sz = ex.gen_from_cdf(1 << 23, zipf_thresholds(nb, theta=1.1))
+joins("split", ex, R, Sz, (0, F | CK | SP, M | CK, O | CK))
+host_join("split", ex, R, Sz)
+del S, Sm, Sz
+# ---- probe-side slabs: a Zipf build side under a uniform probe side; a skewed probe side overflows and retries
+nb, npb, dom = 1 << 22, (1 << 24) + 777, 1 << 22
+thr = zipf_thresholds(dom)
+Rz, Su = ex.gen_from_cdf(nb, thr), ex.gen_uniform_domain(npb, dom)
+joins("slab_probe", ex, Rz, Su, (0, F | SP, CK))
+del Rz, Su
+Rb, Sk = ex.gen_build(nb), ex.gen_from_cdf(npb, thr, zseed=0x5EED)
+joins("slab_probe skewed", ex, Rb, Sk, (0, CK))
+del R, Rb, Sk, thr
+ex.release_result()
+# ---- one-pass slab walk: count, materialising, its duplicate-key fallback, a hot key
+nb, npb = 300000, (1 << 22) + 777
+B = to_np(ex.gen_build(nb)).copy()
+P = to_np(ex.gen_uniform_domain(npb, nb)).copy()
+Bd, Pd = to_dev(B), to_dev(P)
+joins("one_pass", ex, Bd, Pd, (0, CK | SP, F | CK, M | CK, M | F | CK | SP, O | CK))
+host_join("one_pass", ex, B, P)
+B2 = B.copy()
+B2[1::2, 0] = B2[0::2, 0]
+P2 = P.copy()
+P2[:, 0] = B2[0::2, 0][rng.integers(0, nb // 2, npb)]
+joins("one_pass dup keys", ex, to_dev(B2), to_dev(P2), (M | CK, CK))
+P3 = P.copy()
+P3[::2, 0] = B[12345, 0]
+joins("one_pass hot key", ex, Bd, to_dev(P3), (CK,))
+del Bd, Pd, B2, P2, P3
+ex.release_result()
+# ---- global table (L2 and LDS forms), its give-up on duplicate build keys
+Rg, Sg = ex.gen_build(1 << 14), ex.gen_uniform_domain(1 << 22, 1 << 14)
+joins("gtable", ex, Rg, Sg, (0, CK, M | CK))
+host_join("gtable", ex, Rg, Sg)
+joins("ltable", ex, ex.gen_build(1000), ex.gen_uniform_domain(1 << 20, 1000), (0, CK))
+Bg = to_np(Rg).copy()
+Bg[1::2, 0] = Bg[0::2, 0]
+joins("gtable dup keys", ex, to_dev(Bg), Sg, (M | CK, CK))
+# ---- ordered, small build side: rank runs, rank sort
+joins("rank", ex, Rg, Sg, (O | CK,))
+host_join("rank", ex, Rg, Sg, O)
+joins("rank 2^10", ex, ex.gen_build(1 << 10), ex.gen_uniform_domain(1 << 22, 1 << 10), (O | CK,))
+exr = executor(HMJ_RANK_RUNS=0)
+joins("rank sort", exr, exr.gen_build(1 << 10), exr.gen_uniform_domain(1 << 22, 1 << 10), (O | CK,))
+exr.close()
+del Rg, Sg
+ex.release_result()
+# ---- partitioned plans of small joins: unique-key write, general passes, ordered expansion and its give-up
+nb, npb, keys_n = 200000, 300000, 30000
+pool = rng.integers(0, 1 << 62, keys_n + keys_n // 4, dtype=np.uint64)
+B = np.stack([pool[rng.integers(0, keys_n, nb)], rng.permutation(nb).astype(np.uint64)], 1)
+P = np.stack([pool[rng.integers(keys_n // 8, len(pool), npb)], rng.permutation(npb).astype(np.uint64) + np.uint64(1 << 40)], 1)
+Bd, Pd = to_dev(B), to_dev(P)
+joins("dup keys", exp, Bd, Pd, (0, CK, M | CK, O | CK | SP, O | F | CK))
+host_join("dup keys", exp, B, P)
+host_join("dup keys", exp, B, P, O)
+B[:9000, 0] = pool[5]
+P[:3, 0] = pool[5]
+joins("dup keys hot", exp, to_dev(B), Pd, (O | CK,))
+nk = 1 << 15  # 16 copies of every key on both sides: the expansion asks for one more radix bit
+pool = rng.integers(0, 1 << 62, nk, dtype=np.uint64)
+B = np.stack([np.repeat(pool, 16)[rng.permutation(nk * 16)], rng.permutation(nk * 16).astype(np.uint64)], 1)
+P = np.stack([np.repeat(pool, 16)[rng.permutation(nk * 16)], rng.permutation(nk * 16).astype(np.uint64) + np.uint64(7)], 1)
+joins("16 x 16", exp, to_dev(B), to_dev(P), (O | CK,))
+R1, S1 = exp.gen_build((1 << 20) + 77), exp.gen_probe((1 << 21) + 5, (1 << 20) + 77, miss_mod=3)
+joins("unique keys", exp, R1, S1, (0, CK, M | CK, O | CK, O | F | CK))
+host_join("unique keys", exp, R1, S1)
+record("exact prepared", exp, lambda: (exp.prepare_build(R1, (1 << 21) + 5), exp.join_device(R1, S1, 0))[1])
+# ---- each join kind once
+for kind in (H.HMJ_JOIN_SEMI, H.HMJ_JOIN_ANTI, H.HMJ_JOIN_PROBE_OUTER):
+    for fl in (CK, M | CK, O | CK):
+        record("kind %d flags=%#x" % (kind, fl), exp, lambda: exp.join_kind_device(R1, S1, kind, fl, outer_fill=77),
+               ordered=bool(fl & O))
+for kind in (H.HMJ_BUILD_SEMI, H.HMJ_BUILD_ANTI, H.HMJ_BUILD_OUTER, H.HMJ_FULL_OUTER):
+    for fl in (CK, M | CK, O | CK):
+        record("build kind %d flags=%#x" % (kind, fl), exp,
+               lambda: exp.join_build_kind_device(R1, S1, kind, fl, build_fill=55, probe_fill=77), ordered=bool(fl & O))
+exp.release_result()
+# ---- ordered joins cut into key ranges
+exk = executor(HMJ_KEY_RANGES_FORCE=2)
+joins("key ranges", exk, exk.gen_build(50000), exk.gen_uniform_domain(400001, 50000), (O | CK | SP,))
+joins("key ranges miss", exk, exk.gen_build(50000), exk.gen_probe(300000, 50000, miss_mod=3), (O,))
+exk.close()
+# ---- argument errors (their messages are part of the contract)
+def raw_join(build_ptr, n_build):
+    res = H.JoinResult()
+    ex._check(ex.L.hmj_join_u64_device(ex.h, build_ptr, n_build, C.c_void_p(R1.data_ptr()), 4, 0, C.byref(res)))
+    return res
+
+
+record("misaligned build", ex, lambda: raw_join(C.c_void_p(R1.data_ptr() + 8), 4), repeat=1)
+record("null build", ex, lambda: raw_join(None, 4), repeat=1)
+record("too many rows", ex, lambda: raw_join(C.c_void_p(R1.data_ptr()), 1 << 33), repeat=1)
+ex.close()
+exp.close()
+print("ab_calls: %d records from %s" % (n_records, _lib.lib_path()), file=sys.stderr)
