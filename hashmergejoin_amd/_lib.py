@@ -205,6 +205,26 @@ class TakeOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("n_no_row", C.c_uint64), ("ms_take", C.c_float)]
 
 
+# hmj_take_str_device: one Arrow large_string / large_binary column taken through a row map
+class TakeStrSrc(C.Structure):
+    """hmj_take_str_src: the source column on the device -- chars (any alignment; NULL when chars_bytes is 0), the size of
+    the chars buffer, n_src + 1 offsets (offsets[0] need not be 0) and its validity bitmap (bits NULL: no NULL)."""
+    _fields_ = [("chars", C.c_void_p), ("chars_bytes", C.c_uint64), ("offsets", C.c_void_p), ("validity", Validity)]
+
+
+class TakeStrDst(C.Structure):
+    """hmj_take_str_dst: the caller-owned output column -- n_out + 1 offsets, chars aligned to 16 (NULL: a sizing call) with
+    their capacity, an optional bitmap of ceil(n_out / 64) 64-bit words (in); its NULL slots and offsets[n_out] (out)."""
+    _fields_ = [("offsets", C.c_void_p), ("chars", C.c_void_p), ("chars_capacity", C.c_uint64), ("validity", C.c_void_p),
+                ("null_count", C.c_uint64), ("total_bytes", C.c_uint64)]
+
+
+class TakeStrOpts(C.Structure):
+    """hmj_take_str_opts: the map entries equal to HMJ_TAKE_NO_ROW and the times of the two phases (out)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("n_no_row", C.c_uint64), ("ms_offsets", C.c_float),
+                ("ms_chars", C.c_float)]
+
+
 class Timing(C.Structure):
     _fields_ = [("ms_total", C.c_float), ("ms_h2d", C.c_float), ("ms_d2h", C.c_float),
                 ("ms_partition_build", C.c_float), ("ms_partition_probe", C.c_float),
@@ -361,6 +381,8 @@ def load_library():
                                             C.POINTER(ColsResult)]
     L.hmj_take_cols_device.restype = i
     L.hmj_take_cols_device.argtypes = [vp, C.POINTER(TakeSrc), C.c_uint32, u, vp, u, C.POINTER(TakeDst), C.POINTER(TakeOpts)]
+    L.hmj_take_str_device.restype = i
+    L.hmj_take_str_device.argtypes = [vp, C.POINTER(TakeStrSrc), u, vp, u, C.POINTER(TakeStrDst), C.POINTER(TakeStrOpts)]
     L.hmj_prepare_build_u64_device.restype = i
     L.hmj_prepare_build_u64_device.argtypes = [vp, vp, u, u]
     L.hmj_join_u64.restype = i

@@ -132,11 +132,15 @@ struct hmj_ctx {
       msd_off,  // the rank forms' build-side sort: partition offsets of its one MSD pass
       bmatched, bsweep,  // build-side kinds: one bit per build row slot; the sweep's row counts ([0] all, [1 + p] partition p)
       // hmj_take_cols_device (take.hip): its counters -- the only workspace the call owns
-      take_acc;
+      take_acc,
+      // hmj_take_str_device (takestr.hip): its counters, and the bytes per workgroup of 256 output rows followed by their
+      // exclusive scan -- the only workspace the call owns
+      takestr_acc, takestr_blk;
   // string joins (strjoin.hip) and multi-column joins (coljoin.hip): one workspace each, so that neither call reuses or
   // regrows the other's buffers
   hmj_host::KeyJoinWs str_ws, col_ws;
   hipEvent_t take_ev[2] = {nullptr, nullptr};  // hmj_take_cols_device: around its launches (profiling)
+  hipEvent_t takestr_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // hmj_take_str_device: around its offsets and its bytes phase
   int memo_kind = 0;  // workload-signature kind of plain inner joins run on behalf of another entry (string, multi-column joins and their kinds)
   HostBuf h_accum, h_key, h_rval, h_sval;
   int host_threads = 0;  // staging threads for pageable input (0 = default)
@@ -281,6 +285,12 @@ int fail(hmj_ctx* c, int code, const char* what, hipError_t e = hipSuccess);
     const int _rc = (expr);        \
     if (_rc != HMJ_OK) return _rc; \
   } while (0)
+// address ranges, for the host checks of the entries that write caller-owned columns (take.hip, takestr.hip)
+struct Range {
+  uintptr_t lo, hi;  // [lo, hi); empty when lo == hi
+};
+inline Range range_of(const void* p, uint64_t bytes) { return Range{(uintptr_t)p, (uintptr_t)p + (uintptr_t)(p ? bytes : 0)}; }
+inline bool overlap(const Range& a, const Range& b) { return a.lo < a.hi && b.lo < b.hi && a.lo < b.hi && b.lo < a.hi; }
 // the per-phase times and byte counts of one (sub-)join, added to a call's totals (exchange rounds, key ranges); api.hip
 void add_timing(hmj_timing* acc, const hmj_timing& t);
 int ensure_dev(hmj_ctx* c, DevBuf& b, size_t bytes);

@@ -142,12 +142,6 @@ __global__ __launch_bounds__(TK_THREADS) void cols_take_kernel(TakeCols T, const
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
-struct Range {
-  uintptr_t lo, hi;  // [lo, hi); empty when lo == hi
-};
-Range range_of(const void* p, u64 bytes) { return Range{(uintptr_t)p, (uintptr_t)p + (uintptr_t)(p ? bytes : 0)}; }
-bool overlap(const Range& a, const Range& b) { return a.lo < a.hi && b.lo < b.hi && a.lo < b.hi && b.lo < a.hi; }
-
 int check_take_args(hmj_ctx* c, const hmj_take_src* src, u32 n_cols, u64 n_src, const u64* row_map, u64 n_out, const hmj_take_dst* dst,
                     const hmj_take_opts* opts) {
   char msg[192];

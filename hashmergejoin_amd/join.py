@@ -513,6 +513,67 @@ class Executor:
                 "ms_take": float(opts.ms_take)}
         return outs, (words if any(wants) or not cols else None), info
 
+    # ---- a string column through a row map (hmj_take_str_device) -----------------------------------------
+    def take_str_device(self, chars, offsets, row_map, valid=None, n_out=None, want_validity=True, capacity=None):
+        """Take one Arrow large_string / large_binary column through a row map (hmj_take_str_device): output row i is
+        source row row_map[i], or NULL -- with length 0 -- where row_map[i] is HMJ_TAKE_NO_ROW or the source slot is NULL; a
+        valid empty string stays valid.  chars: a contiguous 1-byte device tensor of any alignment (None or empty when every
+        row is empty), offsets: a contiguous int64 device tensor of n_src + 1 entries (offsets[0] need not be 0); no taken
+        row may end behind len(chars).  valid: None, a uint8 bitmap tensor, or (tensor, bit_offset).  row_map and n_out as
+        `take_cols_device` takes them, the (device_pointer, n) form of a result's r_row / s_row included; the result stays as
+        it is.  capacity=None: a sizing call, an allocation of exactly total_bytes, then the full call; a capacity (an upper
+        bound of the output bytes): one call, and HMJ_E_ARG when it is too small.
+        Returns (chars_out uint8 [total_bytes], offsets_out int64 [n_out + 1], int64 tensor of ceil(n_out / 64) bitmap words
+        or None with want_validity=False, {"null_count", "n_no_row", "total_bytes", "ms_offsets", "ms_chars"}); the times
+        are those of the last call made.  `unpack_strings` and `unpack_validity` read the outputs."""
+        torch = self._torch
+        self._sync_stream()
+        if isinstance(row_map, tuple):
+            map_ptr, map_n = int(row_map[0] or 0), int(row_map[1])
+        else:
+            if not row_map.is_cuda or not row_map.is_contiguous() or row_map.dim() != 1 or row_map.dtype != torch.int64:
+                raise ValueError("row_map must be a contiguous 1-D int64 device tensor")
+            map_ptr, map_n = (row_map.data_ptr() if row_map.shape[0] else 0), row_map.shape[0]
+        n_out = map_n if n_out is None else int(n_out)
+        if not 0 <= n_out <= map_n:
+            raise ValueError("n_out must be in 0..len(row_map)")
+        _check_col(offsets, "offsets")
+        if offsets.shape[0] < 1:
+            raise ValueError("offsets must hold n + 1 entries")
+        n_src = offsets.shape[0] - 1
+        src = _lib.TakeStrSrc()
+        cp = _chars_ptr(chars)
+        src.chars = cp.value if cp is not None else None
+        src.chars_bytes = chars.numel() if cp is not None else 0
+        src.offsets = offsets.data_ptr()
+        keep = self._str_validity(valid, n_src, "valid", src.validity)
+        dev = "cuda:%d" % self.device
+        off_out = torch.zeros(n_out + 1, dtype=torch.int64, device=dev)  # (n_out == 0 writes nothing: offsets[0] = 0 is ours)
+        words = torch.empty((n_out + 63) // 64, dtype=torch.int64, device=dev) if want_validity else None
+        dst = _lib.TakeStrDst()
+        dst.offsets = off_out.data_ptr()
+        dst.validity = words.data_ptr() if (words is not None and n_out) else None
+        opts = _lib.TakeStrOpts()
+        opts.struct_size = C.sizeof(_lib.TakeStrOpts)
+
+        def call():
+            self._check(self.L.hmj_take_str_device(self.h, C.byref(src), n_src, C.c_void_p(map_ptr or None), n_out, C.byref(dst),
+                                                   C.byref(opts)))
+
+        if capacity is None:
+            call()  # the sizing call
+            capacity = int(dst.total_bytes)
+        capacity = int(capacity)
+        chars_out = torch.empty(max(capacity, 1), dtype=torch.uint8, device=dev)  # (never a NULL pointer: that is the sizing call)
+        dst.chars = chars_out.data_ptr()
+        dst.chars_capacity = capacity
+        call()
+        del keep
+        total = int(dst.total_bytes)
+        info = {"null_count": int(dst.null_count), "n_no_row": int(opts.n_no_row), "total_bytes": total,
+                "ms_offsets": float(opts.ms_offsets), "ms_chars": float(opts.ms_chars)}
+        return chars_out[:total], off_out, words, info
+
     def prepare_build(self, build, n_probe_hint):
         """Partition the build side now; the next matching plain-count join_device skips that work."""
         self._sync_stream()
@@ -770,6 +831,23 @@ def pack_strings(keys, device=None):
     if device is not None:
         c, o = c.to(device), o.to(device)
     return c, o
+
+
+def unpack_strings(chars, offsets, valid=None):
+    """The inverse of `pack_strings`: (chars uint8, offsets int64 [n + 1]; torch tensors or numpy arrays) -> a list of n
+    `bytes`.  valid: None, or n bools (True = valid; `unpack_validity` makes them from bitmap words): a NULL slot reads as
+    None."""
+    if hasattr(chars, "cpu"):
+        chars = chars.cpu().numpy()
+    if hasattr(offsets, "cpu"):
+        offsets = offsets.cpu().numpy()
+    raw = np.ascontiguousarray(chars).view(np.uint8).tobytes() if chars is not None else b""
+    off = np.asarray(offsets).astype(np.int64).tolist()
+    if len(off) < 1:
+        raise ValueError("offsets must hold n + 1 entries")
+    if valid is not None and len(valid) != len(off) - 1:
+        raise ValueError("valid: one entry per row")
+    return [None if (valid is not None and not valid[i]) else raw[off[i]:off[i + 1]] for i in range(len(off) - 1)]
 
 
 def pack_validity(mask, bit_offset=0, device=None):

@@ -400,7 +400,7 @@ int hmj_exchange_join_kind_u64_device(hmj_ctx* ctx, const void* build_shard_dev,
  * hmj_hash_str_device (each of them also when given no rows), hmj_reserve and hmj_autotune_radix_bits.  Left out are the calls that read or write no workspace buffer: hmj_set_stream,
  * hmj_set_radix_bits / hmj_set_key_prefix_bits (the join then plans other bits and partitions R again), hmj_set_profiling,
  * hmj_forget_workloads, hmj_release_result (result columns only), the hmj_last_* / hmj_placement_info queries, the
- * hmj_gen_* generators and hmj_take_cols_device (its only workspace is a counter buffer of its own); a call refused with HMJ_E_ARG before it started may leave the prepared state in place as well.
+ * hmj_gen_* generators, hmj_take_cols_device and hmj_take_str_device (their only workspace is small buffers of their own); a call refused with HMJ_E_ARG before it started may leave the prepared state in place as well.
  * n_probe_hint: the probe size the join will have (it selects the partitioning path).
  * Corresponds to the first radix_non_inplace_par call of the reference ctor (hashjoin.h:65).       */
 int hmj_prepare_build_u64_device(hmj_ctx* ctx, const void* build_aos_dev, uint64_t n_build,
@@ -802,8 +802,8 @@ int hmj_join_kind_cols_device(hmj_ctx* ctx, const hmj_cols_rel* build, const hmj
  * once for all columns; all of a row's gathers are issued before its first store.  A wave covers 64 consecutive rows that
  * start at a multiple of 64, so its ballot of "valid" is one bitmap word, stored by one lane: no atomics and no
  * read-modify-write on the bitmap.  The counts are ballot popcounts, one atomic per workgroup and counter.
- * Out of scope: variable-width (string) columns, host-resident columns, bit-packed boolean value columns, the exchange
- * path.                                                                                                              */
+ * Out of scope: host-resident columns, bit-packed boolean value columns, the exchange path.  Variable-width (string)
+ * columns go through hmj_take_str_device below.                                                                      */
 #define HMJ_TAKE_NO_ROW UINT64_MAX   /* == HMJ_COLS_NO_ROW == HMJ_STR_NO_ROW */
 #define HMJ_MAX_TAKE_COLS 64
 typedef struct {
@@ -826,6 +826,69 @@ typedef struct {
 } hmj_take_opts;
 int hmj_take_cols_device(hmj_ctx* ctx, const hmj_take_src* src, uint32_t n_cols, uint64_t n_src,
                          const uint64_t* row_map, uint64_t n_out, hmj_take_dst* dst, hmj_take_opts* opts);
+
+/* ---- taking an Arrow string column through a row map --------------------------------------------------- */
+/* The sibling of hmj_take_cols_device for ONE variable-width column per call: an Arrow large_string / large_binary column
+ * (n_src rows: n_src + 1 64-bit offsets into a chars buffer, an optional validity bitmap) is taken through row_map (n_out
+ * entries) into caller-owned offsets, chars and an optional validity bitmap, in the same contract style: what turns the
+ * r_row / s_row of the string joins back into their key strings, or takes any other string column of either relation.  src,
+ * dst and opts are host structs; everything they point to is on the device.
+ * NULL and empty slots.  Output slot i is NULL when row_map[i] == HMJ_TAKE_NO_ROW or source row row_map[i] is NULL
+ * (src->validity, any bit_offset; bits == NULL: no NULL).  A NULL slot has length 0, whatever bytes the source holds under
+ * its NULL slot; a valid empty string is valid with length 0.  The offsets of a source slot that is NULL or never taken are
+ * not consulted: they may hold anything.  Source offsets[0] need not be 0, and src->chars needs no alignment.
+ * Sizing and full calls.  dst->chars == NULL is the sizing call: it writes dst->offsets (n_out + 1 final values,
+ * offsets[0] = 0), the bitmap (when dst->validity != NULL: ceil(n_out / 64) words as hmj_take_dst's, padding bits 0),
+ * dst->null_count, dst->total_bytes (= offsets[n_out]) and opts->n_no_row, and copies no bytes.  With dst->chars set the
+ * call does all of that and copies the bytes: a caller who knows an upper bound needs one call, otherwise two.  If
+ * chars_capacity < total_bytes the call returns HMJ_E_ARG with dst->total_bytes filled, and not one byte of chars is
+ * written.
+ * Outputs.  Offsets, bitmap words and counts are a function of the inputs alone.  Exactly the bytes chars[0, total_bytes)
+ * are written: no byte at or behind total_bytes changes, although the kernel stores 16 bytes at a time (the last, short
+ * piece is stored bytewise).
+ * Bad map entries and bad source offsets are HMJ_E_ARG, never a fault: a map entry >= n_src that is not HMJ_TAKE_NO_ROW,
+ * and a taken valid row with offsets[r + 1] < offsets[r] or offsets[r + 1] > chars_bytes; hmj_last_error gives the counts.
+ * All three are compared before any address is formed from them; such a lane contributes a NULL slot of length 0, and the
+ * bytes phase does not run.  The outputs are unspecified after the error and the ctx stays usable.
+ * HMJ_E_ARG also, found on the host before any launch (hmj_last_error names what was wrong): NULL ctx / src / dst / opts;
+ * opts->struct_size smaller than through `reserved`, non-zero reserved; a NULL row_map or NULL dst->offsets with n_out > 0;
+ * NULL source offsets with n_src > 0; NULL source chars with chars_bytes > 0; a row_map, source offsets, dst->offsets or
+ * dst->validity not aligned to 8 bytes, or dst->chars not aligned to 16; n_out or n_src above 2^32-1; bit_offset + n_src
+ * overflowing 64 bits; a destination range -- offsets, bitmap words, chars[0, chars_capacity) -- that overlaps the row map,
+ * the source offsets, the source bitmap, [chars, chars + chars_bytes) or another destination range of the call (address
+ * ranges; ranges that merely touch do not overlap).
+ * n_out == 0 is HMJ_OK with total_bytes = 0, and nothing on the device is written (not even offsets[0]).  Like
+ * hmj_take_cols_device the call keeps the last result, a prepared build side, hmj_last_plan, hmj_last_timing and the workload
+ * memos as they were -- its only workspace is a counter block and the per-workgroup byte totals with their scan --; row_map
+ * may be the ctx's own r_row / s_row; it returns with the work complete on the ctx stream.
+ * How (DESIGN.md "Taking string columns through a join's row maps").  Offsets phase: one lane per output row, one
+ * 256-thread workgroup per 256 consecutive rows; the map entry is tested once, offsets[r], offsets[r + 1] and the validity
+ * byte are gathered together, the row is checked; a wave's ballot of "valid" is one bitmap word, the counts are ballot
+ * popcounts; the workgroup's exclusive scan of the lengths goes to dst->offsets, the workgroup totals are scanned, and a
+ * streaming kernel adds every workgroup's base and writes offsets[n_out].  The host reads one counter block back: the only
+ * synchronisation before the bytes phase, and where a bad call stops.  Bytes phase, balanced by output bytes: a workgroup
+ * owns a tile of 4096 output bytes, finds the rows that intersect it by binary search in the final offsets and stages
+ * their output and source starts in LDS (up to 1024 rows per tile; beyond, lanes read them from global memory); a lane
+ * builds one aligned 16-byte piece from aligned 16-byte source granules that hold a byte of a taken row, shifted into
+ * place, and stores it once.  A row longer than a tile is covered by several tiles.
+ * opts->ms_offsets / ms_chars: HIP-event times of the two phases with hmj_set_profiling (ms_chars 0 for a sizing call). */
+typedef struct {
+  const void* chars;        /* device; may be NULL when chars_bytes == 0; need not be aligned        */
+  uint64_t chars_bytes;     /* size of the chars buffer: no taken row may end behind it               */
+  const uint64_t* offsets;  /* device: n_src + 1 offsets, Arrow large_string; offsets[0] need not be 0 */
+  hmj_validity validity;    /* source bitmap at any bit_offset; bits == NULL: no NULL                 */
+} hmj_take_str_src;
+typedef struct {
+  uint64_t* offsets;        /* device, caller-owned: n_out + 1 entries, offsets[0] = 0                */
+  void* chars;              /* device, caller-owned, aligned to 16; NULL: a sizing call               */
+  uint64_t chars_capacity;  /* bytes available behind chars                                           */
+  uint64_t* validity;       /* device or NULL: ceil(n_out / 64) words, as hmj_take_dst                */
+  uint64_t null_count;      /* out */
+  uint64_t total_bytes;     /* out: offsets[n_out], filled by sizing and full calls alike             */
+} hmj_take_str_dst;
+typedef struct { uint32_t struct_size, reserved; uint64_t n_no_row; float ms_offsets, ms_chars; } hmj_take_str_opts;
+int hmj_take_str_device(hmj_ctx* ctx, const hmj_take_str_src* src, uint64_t n_src, const uint64_t* row_map,
+                        uint64_t n_out, hmj_take_str_dst* dst, hmj_take_str_opts* opts);
 /* Host threads of the optional staged upload (pageable input -> pinned chunks -> PCIe), used only
  * with HMJ_UPLOAD=staged in the environment; by default each relation goes up in one copy straight
  * from the caller's memory (54 GB/s on the MI355X box).  The reference ctor's num_threads argument,
