@@ -183,6 +183,32 @@ class ColsResult(C.Structure):
         return {k: int(getattr(self, k)) for k in ("n_matches", "sum_r", "sum_s", "xor_fold", "mix_sum")}
 
 
+# hmj_join_mixed_device: key tuples of Arrow large_string and fixed-width columns
+HMJ_KEY_FIXED, HMJ_KEY_LARGE_STRING = 0, 1
+
+
+class MixedCol(C.Structure):
+    """hmj_mixed_col: one key column on the device -- FIXED: n values of `width` bytes; LARGE_STRING: a chars buffer (width
+    0) and n + 1 64-bit offsets -- and its validity bitmap (bits NULL: no NULL in the column)."""
+    _fields_ = [("type", C.c_uint32), ("width", C.c_uint32), ("data", C.c_void_p), ("offsets", C.c_void_p),
+                ("validity", Validity)]
+
+
+class MixedRel(C.Structure):
+    """hmj_mixed_rel: a relation keyed by a tuple of string and fixed-width columns + optional payloads."""
+    _fields_ = [("cols", C.POINTER(MixedCol)), ("n_cols", C.c_uint32), ("reserved", C.c_uint32), ("vals", C.c_void_p),
+                ("n", C.c_uint64)]
+
+
+class MixedOpts(C.Structure):
+    """hmj_mixed_opts: side, kind, hash bits and fill values (in); the kind's counters, pairs of equal key64, pairs whose
+    tuples differ, the NULL-key rows per side and phase times (out)."""
+    _fields_ = [("struct_size", C.c_uint32), ("side", C.c_uint32), ("kind", C.c_uint32), ("hash_bits", C.c_uint32),
+                ("probe_fill", C.c_uint64), ("build_fill", C.c_uint64), ("counts", KindCounts), ("n_key_pairs", C.c_uint64),
+                ("n_collisions", C.c_uint64), ("n_build_null", C.c_uint64), ("n_probe_null", C.c_uint64), ("ms_key", C.c_float),
+                ("ms_join", C.c_float), ("ms_verify", C.c_float), ("ms_emit", C.c_float), ("ms_order", C.c_float)]
+
+
 # hmj_take_cols_device: fixed-width columns taken through a row map (a join's r_row / s_row)
 HMJ_TAKE_NO_ROW = 0xFFFFFFFFFFFFFFFF
 HMJ_MAX_TAKE_COLS = 64
@@ -379,6 +405,9 @@ def load_library():
     L.hmj_join_kind_cols_device.restype = i
     L.hmj_join_kind_cols_device.argtypes = [vp, C.POINTER(ColsRel), C.POINTER(ColsRel), C.c_uint32, C.POINTER(ColsKindOpts),
                                             C.POINTER(ColsResult)]
+    L.hmj_join_mixed_device.restype = i
+    L.hmj_join_mixed_device.argtypes = [vp, C.POINTER(MixedRel), C.POINTER(MixedRel), C.c_uint32, C.POINTER(MixedOpts),
+                                        C.POINTER(ColsResult)]
     L.hmj_take_cols_device.restype = i
     L.hmj_take_cols_device.argtypes = [vp, C.POINTER(TakeSrc), C.c_uint32, u, vp, u, C.POINTER(TakeDst), C.POINTER(TakeOpts)]
     L.hmj_take_str_device.restype = i

@@ -3123,7 +3123,7 @@ void hmj_destroy(hmj_ctx* c) {
                     &c->split_r, &c->split_s, &c->split_off, &c->cat_key, &c->cat_rval, &c->cat_sval, &c->msd_off,
                     &c->bmatched, &c->bsweep, &c->take_acc, &c->takestr_acc, &c->takestr_blk};
   for (DevBuf* b : devs) free_dev(*b);
-  for (KeyJoinWs* ws : {&c->str_ws, &c->col_ws}) {
+  for (KeyJoinWs* ws : {&c->str_ws, &c->col_ws, &c->mix_ws}) {
     ws->each_buf(free_dev);
     for (auto& e : ws->ev)
       if (e) (void)hipEventDestroy(e);
@@ -3602,6 +3602,7 @@ void hmj_release_result(hmj_ctx* c) {
   free_dev(c->ord_sval);
   c->str_ws.each_result_buf(free_dev);
   c->col_ws.each_result_buf(free_dev);
+  c->mix_ws.each_result_buf(free_dev);
   free_host(c->h_key);
   free_host(c->h_rval);
   free_host(c->h_sval);

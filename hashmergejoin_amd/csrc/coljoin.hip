@@ -2,7 +2,9 @@
 // corresponds: its operator is a template over ONE Key with std::hash<Key> (hashjoin.h:33-56).  The structure is the
 // string join's (strjoin.hip) with the byte walks replaced by column loads; what the two share -- every kernel and launch
 // sequence named below without a cols_ prefix -- lives in hmj_keyjoin.h and is instantiated here on ColSide.  This file
-// holds the key kernels, the packed form's gather, the key policy (key_eq / key_cmp / payload on ColSide) and stages 1-3:
+// holds the key kernels, the packed form's gather and the key policy (key_eq / key_cmp / payload on ColSide); the launch
+// sequence of the stages below is hmj_tuplejoin.h's (tuple_join / tuple_join_kind), shared with the mixed-key join
+// (mixjoin.hip) and instantiated here on ColPolicy:
 //   1. cols_key_kernel    k columns (struct of arrays, one device pointer each) -> {key64, row} rows (16 bytes, what the
 //                         u64 join takes).  PACKED (widths sum to <= 8 bytes): key64 is the tuple itself, column 0 in the
 //                         most significant position, so equal key64 IS equal tuples and ascending key64 IS tuple order.
@@ -35,14 +37,12 @@
 #include <cstdio>
 #include <cstring>
 
-#include "hmj_keyjoin.h"
+#include "hmj_tuplejoin.h"
 
 namespace {
 
 constexpr int CJ_THREADS = KJ_THREADS;  // the key kernels' workgroup: valid_count_kernel counts the rows of one of cols_key_valid_kernel
 constexpr int CJ_WAVES = CJ_THREADS / 64;
-constexpr int kMaxCols = HMJ_MAX_KEY_COLS;
-constexpr u64 kGolden = 0x9E3779B97F4A7C15ull;
 
 // One relation's key columns and payloads, passed to the kernels by value.  Every loop over the columns is fully unrolled
 // with a `c < k` guard, so p[c] / w[c] are read from the kernel arguments at constant offsets.
@@ -53,21 +53,11 @@ struct ColSide {
   const u64* vals;  // NULL: the payload of row i is i
 };
 
-// column value of row i, zero-extended (w is uniform: a scalar branch)
-__device__ __forceinline__ u64 col_load(const void* p, u32 w, u64 i) {
-  switch (w) {
-    case 1: return (u64) reinterpret_cast<const unsigned char*>(p)[i];
-    case 2: return (u64) reinterpret_cast<const unsigned short*>(p)[i];
-    case 4: return (u64) reinterpret_cast<const u32*>(p)[i];
-    default: return reinterpret_cast<const u64*>(p)[i];
-  }
-}
 __device__ __forceinline__ u64 payload(const ColSide& A, u64 i) { return A.vals ? A.vals[i] : i; }
 
 // The key policy of the shared kernels (hmj_keyjoin.h).  Both sides have the same column count and widths, so where a lane
 // chooses its side at run time (the join kinds' mixed rows) the first lane's count and widths are every lane's: the choice
 // only selects the column pointers, and col_load's switch stays a scalar branch.
-__device__ __forceinline__ u32 uniform(u32 v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ bool key_eq(const ColSide& A, u64 a, const ColSide& B, u64 b) {
   bool eq = true;
   const int k = uniform(A.k);
@@ -126,26 +116,7 @@ __global__ __launch_bounds__(CJ_THREADS) void cols_key_kernel(ColSide A, u64 n, 
   }
 }
 
-// ---- NULL keys (validity bitmaps) ------------------------------------------------------------------------------------------
-// One relation's Arrow validity bitmaps, passed by value like ColSide: bits[c] == NULL: column c holds no NULL.  Row i is
-// valid in column c iff bit off[c] + i (least-significant bit first) is set; a row is a NULL-key row when any column's is not.
-struct ColValid {
-  const unsigned char* bits[kMaxCols];
-  u64 off[kMaxCols];
-  u32 k;
-};
-__device__ __forceinline__ bool row_valid(const ColValid& V, u64 i) {
-  bool ok = true;
-#pragma unroll
-  for (int c = 0; c < kMaxCols; c++) {
-    if (c < (int)V.k && V.bits[c]) {  // (uniform)
-      const u64 b = V.off[c] + i;
-      ok = ok && ((V.bits[c][b >> 3] >> (b & 7)) & 1u);
-    }
-  }
-  return ok;
-}
-
+// ---- NULL keys (validity bitmaps: ColValid / row_valid, hmj_tuplejoin.h) ------------------------------------------------
 // Pass 2, cols_key_kernel for a relation with bitmaps: one lane per row, one workgroup per 256 rows (blk_off is indexed by
 // workgroup).  dense (NULL: not wanted): row i gets {key64, i}, a NULL-key row {0, HMJ_COLS_NO_ROW} -- what the sweeps walk
 // by row index.  comp: the valid rows' {key64, i}, workgroup b's at blk_off[b] in row order (the wave's ballot places a lane
@@ -251,8 +222,6 @@ __global__ __launch_bounds__(CJ_THREADS) void cols_gather_kernel(const u64* __re
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
 constexpr KeyJoinNames kNames{"multi-column join", "key64", "tuples"};
-constexpr int kColsJoinMemoKind = 14;  // workload_signature kind of the inner {key64,row} join (u64 joins 0, sorts 1, kinds
-                                       // 3..9, string kinds 10..13, inner string join 15, multi-column kinds 16..19)
 
 int check_cols_rel(hmj_ctx* c, const hmj_cols_rel* r, const char* name) {
   char msg[160];
@@ -343,52 +312,61 @@ int valid_of(hmj_ctx* c, const hmj_validity* v, const hmj_cols_rel* r, const cha
   return HMJ_OK;
 }
 
-// The {key64,row} rows of one relation in a call with bitmaps.  dense: the relation's row-indexed rows (NULL: not wanted);
-// *rows / *n_valid: what the u64 joins take.  A relation with a bitmap: its valid rows counted per workgroup (vblk: nblk
-// counts, then nblk + 1 offsets), the total read back, the valid rows compacted into cmp.  A relation without one goes
-// through cols_key_kernel as always, and its dense rows are its join rows.
-int launch_key_valid(hmj_ctx* c, const ColSide& A, const ColValid& V, bool has, u64 n, bool hashed, u32 bits, u64* dense, u64* plain,
-                     DevBuf& cmp, u64* vblk, bool sum_probe, u64* acc, const void** rows, u64* n_valid) {
-  *rows = plain;
-  *n_valid = n;
-  if (!has || !n) return launch_key(c, A, n, hashed, bits, plain, sum_probe, acc);
-  const u64 nblk = blocks_of(n);
-  if (nblk > 0xFFFFFFFFull) return fail(c, HMJ_E_ARG, "multi-column join: too many rows");
-  u64 *cnt = vblk, *off = vblk + nblk;
-  hipLaunchKernelGGL(valid_count_kernel<ColValid>, dim3((u32)nblk), dim3(CJ_THREADS), 0, c->stream, V, n, cnt);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hmj::launch_scan_u64(cnt, off, (u32)nblk, c->stream));
-  u64 nv = 0;
-  RC_TRY(read_back(c, off + nblk, &nv, sizeof(u64)));
-  if (nv > n) return fail(c, HMJ_E_HIP, "multi-column join: more valid rows counted than the relation holds");
-  RC_TRY(ensure_dev(c, cmp, 16 * (nv ? nv : 1)));
-  if (hashed)
-    hipLaunchKernelGGL(cols_key_valid_kernel<true>, dim3((u32)nblk), dim3(CJ_THREADS), 0, c->stream, A, V, n, bits, dense, (u64*)cmp.p, nv,
-                       (const u64*)off, sum_probe ? 1 : 0, acc);
-  else
-    hipLaunchKernelGGL(cols_key_valid_kernel<false>, dim3((u32)nblk), dim3(CJ_THREADS), 0, c->stream, A, V, n, bits, dense, (u64*)cmp.p, nv,
-                       (const u64*)off, sum_probe ? 1 : 0, acc);
-  HIP_TRY(hipGetLastError());
-  *rows = cmp.p;
-  *n_valid = nv;
-  return HMJ_OK;
-}
+// The multi-column join's side of the driver (hmj_tuplejoin.h): its key kernels and the packed form's gather.
+struct ColPolicy {
+  using Side = ColSide;
+  static constexpr bool kCanPack = true;
+  static constexpr int kAccExtra = 0;
+  // workload_signature kinds of the {key64,row} joins (u64 joins 0, sorts 1, kinds 3..9, string kinds 10..13, inner string
+  // join 15, mixed-key joins 20..24): none of them teaches a join of another entry anything
+  static constexpr int kMemoInner = 14;      // the inner join
+  static constexpr int kMemoProbeRep = 16;   // first-wins join, probe rows against build representatives (probe SEMI / ANTI)
+  static constexpr int kMemoBuildRep = 17;   // ... build rows against probe representatives (BUILD_SEMI / BUILD_ANTI)
+  static constexpr int kMemoAmbiguous = 18;  // the ambiguous rows against every row of their key64 on the other side
+  static constexpr int kMemoPairs = 19;      // the outer kinds' pair join
+  static const KeyJoinNames& names() { return kNames; }
+  static KeyJoinWs& ws(hmj_ctx* c) { return c->col_ws; }
+  static int keys_begin(hmj_ctx*) { return HMJ_OK; }
+  static int keys_check(hmj_ctx*) { return HMJ_OK; }
+  static int key(hmj_ctx* c, const ColSide& A, int, u64 n, const TupleCall& call, u64* out, bool sum_probe, u64* acc) {
+    return launch_key(c, A, n, call.hashed, call.bits, out, sum_probe, acc);
+  }
+  static int key_valid(hmj_ctx* c, const ColSide& A, const ColValid& V, int, u64 n, const TupleCall& call, u64 nblk, u64* dense, u64* comp,
+                       u64 cap, const u64* off, bool sum_probe, u64* acc) {
+    if (call.hashed)
+      hipLaunchKernelGGL(cols_key_valid_kernel<true>, dim3((u32)nblk), dim3(CJ_THREADS), 0, c->stream, A, V, n, call.bits, dense, comp, cap,
+                         off, sum_probe ? 1 : 0, acc);
+    else
+      hipLaunchKernelGGL(cols_key_valid_kernel<false>, dim3((u32)nblk), dim3(CJ_THREADS), 0, c->stream, A, V, n, call.bits, dense, comp, cap,
+                         off, sum_probe ? 1 : 0, acc);
+    HIP_TRY(hipGetLastError());
+    return HMJ_OK;
+  }
+  // packed: every pair is a result row (o_rv / o_sv: the payload columns, materialising); mark: the outer kinds' PairMark
+  static int gather(hmj_ctx* c, bool mat, bool mark, u64 nblk, const u64* kk, const u64* rr, const u64* sr, u64 n_pairs, const ColSide& RS,
+                    const ColSide& SS, u64* o_rv, u64* o_sv, u64* acc, bool checksum, unsigned char* mark_r, unsigned char* mark_s, u64* o_key,
+                    u64* o_r, u64* o_s, u64* blk) {
+    const PairMark M{mark_r, mark_s, o_key, o_r, o_s, blk};
+    const dim3 G((u32)nblk), T(CJ_THREADS);
+    const int cs = checksum ? 1 : 0;
+    if (mat && mark)
+      hipLaunchKernelGGL((cols_gather_kernel<true, true>), G, T, 0, c->stream, kk, rr, sr, n_pairs, RS.vals, SS.vals, o_rv, o_sv, acc, cs, M);
+    else if (mark)
+      hipLaunchKernelGGL((cols_gather_kernel<false, true>), G, T, 0, c->stream, kk, rr, sr, n_pairs, RS.vals, SS.vals, nullptr, nullptr, acc,
+                         cs, M);
+    else if (mat)
+      hipLaunchKernelGGL(cols_gather_kernel<true>, G, T, 0, c->stream, kk, rr, sr, n_pairs, RS.vals, SS.vals, o_rv, o_sv, acc, cs, M);
+    else
+      hipLaunchKernelGGL(cols_gather_kernel<false>, G, T, 0, c->stream, kk, rr, sr, n_pairs, RS.vals, SS.vals, nullptr, nullptr, acc, cs, M);
+    HIP_TRY(hipGetLastError());
+    return HMJ_OK;
+  }
+};
 
-// Both relations' {key64,row} rows in a call with bitmaps (the block counts of both sides share vblk).
-int launch_keys_valid(hmj_ctx* c, const ColSide& RS, const ColSide& SS, const ColValid* VB, const ColValid* VP, u64 nb, u64 np,
-                      bool hashed, u32 bits, bool dense, bool sum_probe, u64* acc, const void** rows_r, u64* nvb, const void** rows_s,
-                      u64* nvp) {
-  KeyJoinWs& ws = c->col_ws;
-  const u64 kb = VB ? blocks_of(nb) : 0, kp = VP ? blocks_of(np) : 0;
-  RC_TRY(ensure_dev(c, ws.vblk, (2 * (kb + kp) + 2) * sizeof(u64)));
-  u64* vblk = (u64*)ws.vblk.p;
-  const ColValid none{};
-  u64 *plain_r = (u64*)ws.rows_r.p, *plain_s = (u64*)ws.rows_s.p;
-  RC_TRY(launch_key_valid(c, RS, VB ? *VB : none, VB != nullptr, nb, hashed, bits, dense ? plain_r : nullptr, plain_r, ws.cmp_r, vblk,
-                          false, acc, rows_r, nvb));
-  RC_TRY(launch_key_valid(c, SS, VP ? *VP : none, VP != nullptr, np, hashed, bits, dense ? plain_s : nullptr, plain_s, ws.cmp_s,
-                          vblk + 2 * kb + 1, sum_probe, acc, rows_s, nvp));
-  return HMJ_OK;
+bool cols_hashed(const hmj_cols_rel* R, uint32_t force_hashed) {
+  u32 total = 0;
+  for (u32 k = 0; k < R->n_cols; k++) total += R->cols[k].width;
+  return total > 8 || force_hashed;
 }
 
 // VB / VP: the relations' validity bitmaps, NULL where a relation has none (both NULL: the call without NULL keys, all
@@ -396,274 +374,36 @@ int launch_keys_valid(hmj_ctx* c, const ColSide& RS, const ColSide& SS, const Co
 // its own).  n_null (with bitmaps): the NULL-key rows of the build and the probe side.
 int join_cols(hmj_ctx* c, const hmj_cols_rel* R, const hmj_cols_rel* S, uint32_t flags, hmj_cols_join_opts* opts, hmj_cols_result* out,
               const ColValid* VB = nullptr, const ColValid* VP = nullptr, u64* n_null = nullptr) {
-  const u64 nb = R->n, np = S->n;
-  u32 total = 0;
-  for (u32 k = 0; k < R->n_cols; k++) total += R->cols[k].width;
-  const bool hashed = total > 8 || opts->force_hashed;
-  const u32 bits = hashed ? opts->hash_bits : 0;
-  if (flags & HMJ_ORDERED) flags |= HMJ_MATERIALIZE;
-  const bool mat = flags & HMJ_MATERIALIZE, ordered = flags & HMJ_ORDERED, checksum = flags & HMJ_CHECKSUM;
-  c->prep.valid = false;  // like any other call, a multi-column join discards a prepared build side
-  KeyJoinWs& ws = c->col_ws;
-  RC_TRY(ensure_dev(c, ws.acc, KA_N * sizeof(u64)));
-  RC_TRY(ensure_dev(c, ws.rows_r, 16 * (nb ? nb : 1)));
-  RC_TRY(ensure_dev(c, ws.rows_s, 16 * (np ? np : 1)));
-  u64* acc = (u64*)ws.acc.p;
-  u64 h[KA_N];
-  const ColSide RS = side_of(R), SS = side_of(S);
-  // 1. {key64, row} rows of both relations (+ the probe payloads' sum)
-  RC_TRY(record(c, ws.ev, 0));
-  HIP_TRY(hipMemsetAsync(acc, 0, KA_N * sizeof(u64), c->stream));
-  const void *rows_r = ws.rows_r.p, *rows_s = ws.rows_s.p;  // the rows the u64 join takes
-  u64 nvb = nb, nvp = np;                                           // ... and how many: the rows that have a key
-  if (!VB && !VP) {
-    RC_TRY(launch_key(c, RS, nb, hashed, bits, (u64*)ws.rows_r.p, false, acc));
-    RC_TRY(launch_key(c, SS, np, hashed, bits, (u64*)ws.rows_s.p, flags & HMJ_SUM_PROBE, acc));
-  } else {  // NULL keys: only the rows that have a key are joined (the inner join walks no relation by row: no dense rows)
-    RC_TRY(launch_keys_valid(c, RS, SS, VB, VP, nb, np, hashed, bits, false, flags & HMJ_SUM_PROBE, acc, &rows_r, &nvb, &rows_s, &nvp));
-    if (n_null) {
-      n_null[0] = nb - nvb;
-      n_null[1] = np - nvp;
-    }
-    if (nb && np) opts->form = hashed ? HMJ_COLS_HASHED : HMJ_COLS_PACKED;
+  TupleCall call;
+  call.hashed = cols_hashed(R, opts->force_hashed);
+  call.bits = call.hashed ? opts->hash_bits : 0;
+  if (R->n && S->n) opts->form = call.hashed ? HMJ_COLS_HASHED : HMJ_COLS_PACKED;
+  RC_TRY(tuple_join<ColPolicy>(c, side_of(R), R->n, side_of(S), S->n, flags, &call, out, VB, VP));
+  if (n_null && (VB || VP)) {
+    n_null[0] = call.n_build_null;
+    n_null[1] = call.n_probe_null;
   }
-  RC_TRY(record(c, ws.ev, 1));
-  if (nvb == 0 || nvp == 0) {  // (nothing to join: no plan either)
-    std::memset(&c->plan, 0, sizeof(c->plan));
-    c->plan.struct_size = sizeof(c->plan);
-    std::memset(&c->timing, 0, sizeof(c->timing));
-    for (int k = 2; k < 5; k++) RC_TRY(record(c, ws.ev, k));
-    if (flags & HMJ_SUM_PROBE) {
-      RC_TRY(read_back(c, acc, h, sizeof(h)));
-      out->sum_probe_all = h[KA_SUM_P];
-    }
-    return HMJ_OK;
-  }
-  opts->form = hashed ? HMJ_COLS_HASHED : HMJ_COLS_PACKED;
-  // 2. the u64 join of the {key64, row} rows: pairs of equal key64 as (key64, r_row, s_row), ordered by them if asked
-  hmj_result inner;
-  RC_TRY(memo_join(c, rows_r, nvb, rows_s, nvp, HMJ_MATERIALIZE | (flags & HMJ_ORDERED), kColsJoinMemoKind, &inner));
-  RC_TRY(record(c, ws.ev, 2));
-  const u64 n_pairs = inner.n_matches;
-  opts->n_key_pairs = n_pairs;
-  const u64 *ik = (const u64*)inner.key, *ir = (const u64*)inner.rval, *is = (const u64*)inner.sval;
-  const u64 nblk = blocks_of(n_pairs);
-  if (nblk > 0xFFFFFFFFull) return too_many_pairs(c, kNames);
-  u64 n_out = 0;
-  if (!hashed) {
-    // 3a. packed: every pair is a result row; payloads gathered, or only reduced
-    if (n_pairs && mat) {
-      RC_TRY(ensure_dev(c, ws.rval, n_pairs * sizeof(u64)));
-      RC_TRY(ensure_dev(c, ws.sval, n_pairs * sizeof(u64)));
-      hipLaunchKernelGGL(cols_gather_kernel<true>, dim3((u32)nblk), dim3(CJ_THREADS), 0, c->stream, ik, ir, is, n_pairs, RS.vals,
-                         SS.vals, (u64*)ws.rval.p, (u64*)ws.sval.p, acc, checksum ? 1 : 0, PairMark{});
-      HIP_TRY(hipGetLastError());
-    } else if (n_pairs) {
-      hipLaunchKernelGGL(cols_gather_kernel<false>, dim3((u32)nblk), dim3(CJ_THREADS), 0, c->stream, ik, ir, is, n_pairs, RS.vals,
-                         SS.vals, nullptr, nullptr, acc, checksum ? 1 : 0, PairMark{});
-      HIP_TRY(hipGetLastError());
-    }
-    n_out = n_pairs;
-    RC_TRY(record(c, ws.ev, 3));
-  } else {
-    // 3b. hashed: tuple verification, payload gather, stable compaction (or the count modes' reduction)
-    if (n_pairs && mat) {
-      RC_TRY(ensure_dev(c, ws.flags, nblk * CJ_WAVES * sizeof(u64)));
-      RC_TRY(ensure_dev(c, ws.blk, nblk * sizeof(u64)));
-      RC_TRY(ensure_dev(c, ws.blk_off, (nblk + 1) * sizeof(u64)));
-      DevBuf* cols[5] = {&ws.key, &ws.rrow, &ws.srow, &ws.rval, &ws.sval};
-      for (DevBuf* b : cols) RC_TRY(ensure_dev(c, *b, n_pairs * sizeof(u64)));
-      hipLaunchKernelGGL((verify_kernel<ColSide, true>), dim3((u32)nblk), dim3(CJ_THREADS), 0, c->stream, ik, ir, is, n_pairs, RS, SS,
-                         (u64*)ws.flags.p, (u64*)ws.blk.p, acc, 0, nullptr, nullptr);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hmj::launch_scan_u64((const u64*)ws.blk.p, (u64*)ws.blk_off.p, (u32)nblk, c->stream));
-      hipLaunchKernelGGL(compact_kernel<ColSide>, dim3((u32)nblk), dim3(CJ_THREADS), 0, c->stream, ik, ir, is, n_pairs, RS, SS,
-                         (const u64*)ws.flags.p, (const u64*)ws.blk_off.p, (u64*)ws.key.p, (u64*)ws.rrow.p,
-                         (u64*)ws.srow.p, (u64*)ws.rval.p, (u64*)ws.sval.p, acc, checksum ? 1 : 0);
-      HIP_TRY(hipGetLastError());
-      RC_TRY(read_back(c, (const u64*)ws.blk_off.p + nblk, &n_out, sizeof(u64)));
-    } else if (n_pairs) {
-      hipLaunchKernelGGL((verify_kernel<ColSide, false>), dim3((u32)nblk), dim3(CJ_THREADS), 0, c->stream, ik, ir, is, n_pairs, RS, SS,
-                         nullptr, nullptr, acc, checksum ? 1 : 0, nullptr, nullptr);
-      HIP_TRY(hipGetLastError());
-    }
-    RC_TRY(record(c, ws.ev, 3));
-    // 4. ordered: runs of equal key64 with different build tuples, sorted by the tuple
-    if (ordered && n_out > 1) {
-      u64* cols[5] = {(u64*)ws.key.p, (u64*)ws.rrow.p, (u64*)ws.srow.p, (u64*)ws.rval.p, (u64*)ws.sval.p};
-      RC_TRY(order_collisions<false>(c, ws, RS, ColSide{}, cols, n_out, acc));
-    }
-  }
-  RC_TRY(record(c, ws.ev, 4));
-  RC_TRY(read_back(c, acc, h, sizeof(h)));
-  RC_TRY(collision_errors(c, kNames, h[KA_ERR]));
-  const u64* a = h + KA_ACC;
-  out->n_matches = (hashed && mat) ? n_out : a[hmj::ACC_N];
-  out->sum_r = a[hmj::ACC_SUM_R];
-  out->sum_s = a[hmj::ACC_SUM_S];
-  if (checksum) {
-    out->xor_fold = a[hmj::ACC_XOR];
-    out->mix_sum = a[hmj::ACC_MIX];
-  }
-  if (flags & HMJ_SUM_PROBE) out->sum_probe_all = h[KA_SUM_P];
-  if (mat && !hashed) {
-    out->key64 = (const uint64_t*)ik;
-    out->r_row = (const uint64_t*)ir;
-    out->s_row = (const uint64_t*)is;
-    out->rval = (const uint64_t*)ws.rval.p;
-    out->sval = (const uint64_t*)ws.sval.p;
-  } else if (mat) {
-    out->key64 = (const uint64_t*)ws.key.p;
-    out->r_row = (const uint64_t*)ws.rrow.p;
-    out->s_row = (const uint64_t*)ws.srow.p;
-    out->rval = (const uint64_t*)ws.rval.p;
-    out->sval = (const uint64_t*)ws.sval.p;
-  }
-  opts->n_collisions = n_pairs - out->n_matches;
+  opts->n_key_pairs = call.n_key_pairs;
+  opts->n_collisions = call.n_collisions;
   return HMJ_OK;
 }
 
-// ---- join kinds (hmj_join_kind_cols_device) --------------------------------------------------------------------------
-// workload_signature kinds of the {key64,row} joins the kinds run: none of them teaches a join of another entry anything
-constexpr int kMemoProbeRep = 16;   // first-wins join, probe rows against build representatives (probe SEMI / ANTI)
-constexpr int kMemoBuildRep = 17;   // ... build rows against probe representatives (BUILD_SEMI / BUILD_ANTI)
-constexpr int kMemoAmbiguous = 18;  // the ambiguous rows against every row of their key64 on the other side
-constexpr int kMemoPairs = 19;      // the outer kinds' pair join
-constexpr int kKindAccBlocks = 3;   // acc: [0] keys, verification, collision search, [1] probe sweep, [2] build sweep
-
 int join_cols_kind(hmj_ctx* c, const hmj_cols_rel* R, const hmj_cols_rel* S, uint32_t flags, hmj_cols_kind_opts* o, hmj_cols_result* out,
                    const ColValid* VB, const ColValid* VP) {
-  const u64 nb = R->n, np = S->n;
-  const u32 kind = o->kind;
-  u32 total = 0;
-  for (u32 k = 0; k < R->n_cols; k++) total += R->cols[k].width;
-  const bool hashed = total > 8 || o->force_hashed;
-  const u32 bits = hashed ? o->hash_bits : 0;
-  if (flags & HMJ_ORDERED) flags |= HMJ_MATERIALIZE;
-  const bool mat = flags & HMJ_MATERIALIZE, checksum = flags & HMJ_CHECKSUM;
-  const bool bside = o->side == HMJ_KIND_BUILD_SIDE;
-  // semi / anti of either side (HMJ_JOIN_SEMI == HMJ_BUILD_SEMI, HMJ_JOIN_ANTI == HMJ_BUILD_ANTI), else an outer kind
-  const bool semi_anti = kind == HMJ_JOIN_SEMI || kind == HMJ_JOIN_ANTI;
-  c->prep.valid = false;  // like any other call, a multi-column join discards a prepared build side
-  KeyJoinWs& ws = c->col_ws;
-  std::memset(&c->plan, 0, sizeof(c->plan));
-  c->plan.struct_size = sizeof(c->plan);
-  std::memset(&c->timing, 0, sizeof(c->timing));
-  RC_TRY(ensure_dev(c, ws.acc, kKindAccBlocks * KA_N * sizeof(u64)));
-  RC_TRY(ensure_dev(c, ws.rows_r, 16 * (nb ? nb : 1)));
-  RC_TRY(ensure_dev(c, ws.rows_s, 16 * (np ? np : 1)));
-  RC_TRY(ensure_dev(c, ws.mark_r, nb ? nb : 1));
-  RC_TRY(ensure_dev(c, ws.mark_s, np ? np : 1));
-  u64* acc = (u64*)ws.acc.p;
-  u64 *acc_p = acc + KA_N, *acc_b = acc + 2 * KA_N;
-  u64 h[kKindAccBlocks * KA_N];
-  const ColSide RS = side_of(R), SS = side_of(S);
-  unsigned char *mark_r = (unsigned char*)ws.mark_r.p, *mark_s = (unsigned char*)ws.mark_s.p;
-  // 1. {key64, row} rows of both relations (+ the probe payloads' sum), marks cleared
-  RC_TRY(record(c, ws.ev, 0));
-  HIP_TRY(hipMemsetAsync(acc, 0, kKindAccBlocks * KA_N * sizeof(u64), c->stream));
-  // (NULL keys: the dense rows stay indexed by row for the sweeps; the u64 joins take only the rows that have a key)
-  const void *rows_r = ws.rows_r.p, *rows_s = ws.rows_s.p;
-  u64 nvb = nb, nvp = np;
-  if (!VB && !VP) {
-    RC_TRY(launch_key(c, RS, nb, hashed, bits, (u64*)ws.rows_r.p, false, acc));
-    RC_TRY(launch_key(c, SS, np, hashed, bits, (u64*)ws.rows_s.p, flags & HMJ_SUM_PROBE, acc));
-  } else {
-    RC_TRY(launch_keys_valid(c, RS, SS, VB, VP, nb, np, hashed, bits, true, flags & HMJ_SUM_PROBE, acc, &rows_r, &nvb, &rows_s, &nvp));
-    o->n_build_null = nb - nvb;
-    o->n_probe_null = np - nvp;
-  }
-  if (nb) HIP_TRY(hipMemsetAsync(mark_r, 0, nb, c->stream));
-  if (np) HIP_TRY(hipMemsetAsync(mark_s, 0, np, c->stream));
-  RC_TRY(record(c, ws.ev, 1));
-  o->form = hashed ? HMJ_COLS_HASHED : HMJ_COLS_PACKED;
-  // 2. + 3. the {key64,row} join(s) and the tuple verification, which marks the rows that have a partner
-  u64 n_pairs = 0;
-  hmj_result inner;
-  std::memset(&inner, 0, sizeof(inner));
-  if (semi_anti) {
-    // every row of the side asked about (K) meets the FIRST row of its key64 on the other side (O), in row order
-    const u64 nK = bside ? nvb : nvp, nO = bside ? nvp : nvb;
-    const void *rowsK = bside ? rows_r : rows_s, *rowsO = bside ? rows_s : rows_r;
-    const ColSide &KS = bside ? RS : SS, &OS = bside ? SS : RS;
-    unsigned char* mark = bside ? mark_r : mark_s;
-    if (nK && nO) {
-      hmj_result rep;
-      RC_TRY(memo_join(c, rowsO, nO, rowsK, nK, HMJ_MATERIALIZE | HMJ_FIRST_WINS, bside ? kMemoBuildRep : kMemoProbeRep, &rep));
-      RC_TRY(record(c, ws.ev, 2));
-      n_pairs = rep.n_matches;  // <= nK
-      if (n_pairs && !hashed) {
-        hipLaunchKernelGGL((rep_verify_kernel<ColSide, false>), dim3((u32)blocks_of(n_pairs)), dim3(CJ_THREADS), 0, c->stream,
-                           (const u64*)rep.key, (const u64*)rep.rval, (const u64*)rep.sval, n_pairs, OS, KS, mark, nullptr, acc);
-        HIP_TRY(hipGetLastError());
-      } else if (n_pairs) {
-        RC_TRY(ensure_dev(c, ws.amb, 16 * n_pairs));
-        hipLaunchKernelGGL((rep_verify_kernel<ColSide, true>), dim3((u32)blocks_of(n_pairs)), dim3(CJ_THREADS), 0, c->stream,
-                           (const u64*)rep.key, (const u64*)rep.rval, (const u64*)rep.sval, n_pairs, OS, KS, mark,
-                           (u64*)ws.amb.p, acc);
-        HIP_TRY(hipGetLastError());
-        RC_TRY(read_back(c, acc, h, KA_N * sizeof(u64)));
-        const u64 n_amb = h[KA_AMB_N];
-        if (n_amb) {  // (a collision: a representative's tuple differs from the row's)
-          hmj_result all;
-          RC_TRY(memo_join(c, rowsO, nO, ws.amb.p, n_amb, HMJ_MATERIALIZE, kMemoAmbiguous, &all));
-          n_pairs += all.n_matches;
-          if (blocks_of(all.n_matches) > 0xFFFFFFFFull) return too_many_pairs(c, kNames);
-          if (all.n_matches) {
-            hipLaunchKernelGGL((rep_verify_kernel<ColSide, true>), dim3((u32)blocks_of(all.n_matches)), dim3(CJ_THREADS), 0, c->stream,
-                               (const u64*)all.key, (const u64*)all.rval, (const u64*)all.sval, all.n_matches, OS, KS, mark, nullptr,
-                               acc);
-            HIP_TRY(hipGetLastError());
-          }
-        }
-      }
-    } else {
-      RC_TRY(record(c, ws.ev, 2));
-    }
-  } else if (nvb && nvp) {
-    RC_TRY(memo_join(c, rows_r, nvb, rows_s, nvp, HMJ_MATERIALIZE | (flags & HMJ_ORDERED), kMemoPairs, &inner));
-    RC_TRY(record(c, ws.ev, 2));
-    n_pairs = inner.n_matches;
-  } else {
-    RC_TRY(record(c, ws.ev, 2));
-  }
-  o->n_key_pairs = n_pairs;
-  KindRows k;
-  RC_TRY(kind_rows(c, ws, kNames, o->side, kind, flags, nb, np, nvb, nvp, VB != nullptr, VP != nullptr, n_pairs, &k));
-  const u64* pairs[3] = {(const u64*)inner.key, (const u64*)inner.rval, (const u64*)inner.sval};
-  u64* blk = (u64*)ws.blk.p;
-  if (k.nblk_v && !hashed) {  // packed: every pair is a result row and marks its two rows
-    const PairMark M{mark_r, mark_s, k.oc[0], k.oc[1], k.oc[2], blk};
-    if (mat)
-      hipLaunchKernelGGL((cols_gather_kernel<true, true>), dim3((u32)k.nblk_v), dim3(CJ_THREADS), 0, c->stream, pairs[0], pairs[1],
-                         pairs[2], n_pairs, RS.vals, SS.vals, k.oc[3], k.oc[4], acc, checksum ? 1 : 0, M);
-    else
-      hipLaunchKernelGGL((cols_gather_kernel<false, true>), dim3((u32)k.nblk_v), dim3(CJ_THREADS), 0, c->stream, pairs[0], pairs[1],
-                         pairs[2], n_pairs, RS.vals, SS.vals, nullptr, nullptr, acc, checksum ? 1 : 0, M);
-    HIP_TRY(hipGetLastError());
-  } else if (k.nblk_v) {  // hashed: the surviving pairs mark theirs
-    if (mat)
-      hipLaunchKernelGGL((verify_kernel<ColSide, true, true>), dim3((u32)k.nblk_v), dim3(CJ_THREADS), 0, c->stream, pairs[0], pairs[1],
-                         pairs[2], n_pairs, RS, SS, (u64*)ws.flags.p, blk, acc, 0, mark_r, mark_s);
-    else
-      hipLaunchKernelGGL((verify_kernel<ColSide, false, true>), dim3((u32)k.nblk_v), dim3(CJ_THREADS), 0, c->stream, pairs[0], pairs[1],
-                         pairs[2], n_pairs, RS, SS, nullptr, nullptr, acc, checksum ? 1 : 0, mark_r, mark_s);
-    HIP_TRY(hipGetLastError());
-  }
-  RC_TRY(record(c, ws.ev, 3));
-  // 4. the sweeps (hashed: the pairs' survivors compacted in front of them), 5. ordered: the sort by key64, then -- hashed
-  // only: packed, equal key64 is equal tuples, so there is no collision to search for -- runs of equal key64 with several
-  // tuples sorted by tuple
-  RC_TRY(kind_sweeps(c, ws, kNames, k, RS, SS, o->probe_fill, o->build_fill, hashed, pairs, acc, acc_p, acc_b));
-  RC_TRY(record(c, ws.ev, 4));
-  RC_TRY(kind_order(c, ws, k, RS, SS, hashed, acc));
-  RC_TRY(record(c, ws.ev, 5));
-  RC_TRY(read_back(c, acc, h, sizeof(h)));
-  RC_TRY(collision_errors(c, kNames, h[KA_ERR]));
-  kind_report(k, h + KA_ACC, h + KA_N + KA_ACC, h + 2 * KA_N + KA_ACC, out, &o->counts);
-  if (flags & HMJ_SUM_PROBE) out->sum_probe_all = h[KA_SUM_P];
-  if (mat) out->key64 = (const uint64_t*)k.oc[0];
-  o->n_collisions = semi_anti ? h[KA_DIFF] : n_pairs - k.n_in;
+  TupleCall call;
+  call.hashed = cols_hashed(R, o->force_hashed);
+  call.bits = call.hashed ? o->hash_bits : 0;
+  call.side = o->side;
+  call.kind = o->kind;
+  call.probe_fill = o->probe_fill;
+  call.build_fill = o->build_fill;
+  o->form = call.hashed ? HMJ_COLS_HASHED : HMJ_COLS_PACKED;
+  RC_TRY(tuple_join_kind<ColPolicy>(c, side_of(R), R->n, side_of(S), S->n, flags, &call, out, VB, VP));
+  o->n_build_null = call.n_build_null;
+  o->n_probe_null = call.n_probe_null;
+  o->n_key_pairs = call.n_key_pairs;
+  o->n_collisions = call.n_collisions;
+  o->counts = call.counts;
   return HMJ_OK;
 }
 

@@ -25,8 +25,8 @@ struct HostBuf {
   bool pinned = true;  // false: pageable memory on transparent huge pages (the result columns)
 };
 
-// Workspace of one of the two joins on {key64, row} rows (hmj_keyjoin.h; key64: the string join's hash, the multi-column
-// join's packed tuple or hash).
+// Workspace of one of the joins on {key64, row} rows (hmj_keyjoin.h; key64: the string join's hash, the multi-column
+// join's packed tuple or hash, the mixed-key join's hash).
 struct KeyJoinWs {
   DevBuf rows_r, rows_s,           // {key64, row} rows of both relations
       flags, blk, blk_off,         // pass-1 ballots, per-workgroup survivors and their offsets
@@ -136,9 +136,9 @@ struct hmj_ctx {
       // hmj_take_str_device (takestr.hip): its counters, and the bytes per workgroup of 256 output rows followed by their
       // exclusive scan -- the only workspace the call owns
       takestr_acc, takestr_blk;
-  // string joins (strjoin.hip) and multi-column joins (coljoin.hip): one workspace each, so that neither call reuses or
-  // regrows the other's buffers
-  hmj_host::KeyJoinWs str_ws, col_ws;
+  // string joins (strjoin.hip), multi-column joins (coljoin.hip) and mixed-key joins (mixjoin.hip): one workspace each, so
+  // that no call reuses or regrows another's buffers
+  hmj_host::KeyJoinWs str_ws, col_ws, mix_ws;
   hipEvent_t take_ev[2] = {nullptr, nullptr};  // hmj_take_cols_device: around its launches (profiling)
   hipEvent_t takestr_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // hmj_take_str_device: around its offsets and its bytes phase
   int memo_kind = 0;  // workload-signature kind of plain inner joins run on behalf of another entry (string, multi-column joins and their kinds)

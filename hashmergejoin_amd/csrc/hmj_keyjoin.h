@@ -1,7 +1,8 @@
-// What the string-key join (strjoin.hip) and the multi-column key join (coljoin.hip) share: both turn a relation into
+// What the string-key join (strjoin.hip), the multi-column key join (coljoin.hip) and the mixed-key join (mixjoin.hip)
+// share: all turn a relation into
 // {key64, row} rows (a hash of the key, or the packed tuple), run the u64 join on those rows and then work on pairs and
 // rows of equal key64.  Everything here is that second half, once, as templates over the relation-side struct of the
-// including file (StrSide, ColSide).  Internal header: its contents are local to the file that includes it.
+// including file (StrSide, ColSide, MixSide).  Internal header: its contents are local to the file that includes it.
 //
 // The key policy is the Side struct itself, with three overloads the including file keeps next to it:
 //   bool key_eq(const Side& A, u64 a, const Side& B, u64 b)    row a of A and row b of B hold the same key

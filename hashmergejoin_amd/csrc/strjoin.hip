@@ -10,7 +10,8 @@
 //                        workgroup each (a run beyond kRunCap rows is HMJ_E_UNSUPPORTED).
 // Steps 3 and 4 and everything the join kinds add to them -- rep_verify_kernel, the sweeps, the ordered kinds' sort and
 // gather -- are hmj_keyjoin.h's kernels and launch sequences, shared with the multi-column join and instantiated here on
-// StrSide; this file holds the hashing, the key policy (key_eq / key_cmp / payload on StrSide) and stages 1-3 of the calls.
+// StrSide; this file holds the hash kernels, the key policy (key_eq / key_cmp / payload on StrSide) and stages 1-3 of the
+// calls.  The byte reader, _Hash_bytes and the byte comparison are hmj_strkey.h's, shared with the mixed-key join (mixjoin.hip).
 // NULL keys (validity bitmaps, calls that pass one only): valid_count_kernel counts the rows that have a key per
 // workgroup, one scan places them, and str_hash_valid_kernel writes two arrays per relation: the dense rows the sweeps walk
 // by row index (a NULL-key row: hash 0, row HMJ_STR_NO_ROW) and the compacted rows of the valid rows, which are all the u64
@@ -22,77 +23,14 @@
 #include <cstring>
 
 #include "hmj_keyjoin.h"
+#include "hmj_strkey.h"
 
 namespace {
 
-constexpr u64 kMul = 0xc6a4a7935bd1e995ull;
-constexpr u64 kSeed = 0xc70f6907ull;
 constexpr int SH_THREADS = 256;
 constexpr int SH_WAVES = SH_THREADS / 64;
 constexpr int SH_STAGE = 4096;  // LDS bytes a wave stages its 64 keys in; a longer span: per-lane reads from global memory
 static_assert(SH_THREADS == KJ_THREADS, "valid_count_kernel counts the rows of one workgroup of str_hash_valid_kernel");
-
-__device__ __forceinline__ u64 shift_mix(u64 v) { return v ^ (v >> 47); }
-
-// Reads the key bytes at byte position `pos` as little-endian 64-bit words through aligned 8-byte loads (word q = bytes
-// [8q, 8q + 8) of the address space the loader LD sees).  A load never reaches beyond the 8-byte-aligned words that
-// hold key bytes, so no load crosses into a page the key does not touch.
-template <class LD>
-struct KeyReader {
-  LD ld;
-  u64 q;     // aligned word holding the next byte
-  u32 s;     // bit offset of the next byte in that word
-  u64 cur;   // word q (valid when it holds key bytes)
-  u64 left;  // key bytes not yet read
-  __device__ __forceinline__ KeyReader(LD l, u64 pos, u64 len) : ld(l), q(pos >> 3), s((u32)(pos & 7) * 8u), cur(0), left(len) {
-    if (len) cur = ld(q);
-  }
-  // the next 8 bytes (left >= 8)
-  __device__ __forceinline__ u64 word() {
-    u64 d;
-    left -= 8;
-    if (s == 0) {
-      d = cur;
-      q++;
-      if (left) cur = ld(q);
-    } else {
-      const u64 nx = ld(q + 1);
-      d = (cur >> s) | (nx << (64 - s));
-      cur = nx;
-      q++;
-    }
-    return d;
-  }
-  // the last 1..7 bytes (left < 8), zero-extended
-  __device__ __forceinline__ u64 tail() {
-    const u32 t = (u32)left;
-    u64 d = cur >> s;
-    if (s + 8u * t > 64u) d |= ld(q + 1) << (64 - s);
-    left = 0;
-    return d & ((1ull << (8u * t)) - 1ull);
-  }
-};
-struct GlobalLd {
-  __device__ __forceinline__ u64 operator()(u64 q) const { return *reinterpret_cast<const u64*>(q << 3); }
-};
-struct LdsLd {
-  const u64* w;
-  __device__ __forceinline__ u64 operator()(u64 q) const { return w[q]; }
-};
-
-// libstdc++ _Hash_bytes (64-bit size_t), i.e. std::hash<std::string>
-template <class LD>
-__device__ __forceinline__ u64 hash_bytes(LD ld, u64 pos, u64 len) {
-  KeyReader<LD> rd(ld, pos, len);
-  u64 h = kSeed ^ (len * kMul);
-  for (u64 k = len >> 3; k; k--) {
-    const u64 d = shift_mix(rd.word() * kMul) * kMul;
-    h = (h ^ d) * kMul;
-  }
-  if (len & 7) h = (h ^ rd.tail()) * kMul;
-  return shift_mix(shift_mix(h) * kMul);
-}
-
 
 // Per wave: 64 consecutive keys, bytes [offsets[i0], offsets[i0 + 64]).  Staged in LDS when the span's aligned 16-byte
 // blocks fit SH_STAGE, else read per lane from global memory.  rows: out = {hash, row} x n, else bare hashes.  vals != NULL: their sum goes to acc[KA_ACC + ACC_SUM_P].
@@ -242,20 +180,10 @@ struct StrSide {
   const u64* vals;
 };
 
-// Lexicographic comparison of two keys as std::string::operator< compares them (unsigned bytes, then length).
+// Lexicographic comparison of two keys as std::string::operator< compares them (bytes_cmp, hmj_strkey.h).
 __device__ __forceinline__ int key_cmp(const StrSide& A, u64 ra, const StrSide& B, u64 rb) {
   const u64 pa = A.offsets[ra], la = A.offsets[ra + 1] - pa, pb = B.offsets[rb], lb = B.offsets[rb + 1] - pb;
-  const u64 m = la < lb ? la : lb;
-  KeyReader<GlobalLd> X(GlobalLd{}, (u64)(uintptr_t)(A.chars + pa), m), Y(GlobalLd{}, (u64)(uintptr_t)(B.chars + pb), m);
-  while (X.left) {
-    const u64 x = X.left >= 8 ? X.word() : X.tail();
-    const u64 y = Y.left >= 8 ? Y.word() : Y.tail();
-    if (x != y) {
-      const u32 sh = (u32)__builtin_ctzll(x ^ y) & ~7u;
-      return ((x >> sh) & 0xFF) < ((y >> sh) & 0xFF) ? -1 : 1;
-    }
-  }
-  return la < lb ? -1 : la > lb ? 1 : 0;
+  return bytes_cmp(A.chars + pa, la, B.chars + pb, lb);
 }
 __device__ __forceinline__ bool key_eq(const StrSide& A, u64 ra, const StrSide& B, u64 rb) {
   if (A.offsets[ra + 1] - A.offsets[ra] != B.offsets[rb + 1] - B.offsets[rb]) return false;

@@ -441,6 +441,94 @@ class Executor:
             out[:, c] = tmp.cpu().numpy().view(np.uint64)
         return out
 
+    # ---- mixed keys: string and fixed-width columns in one tuple (hmj_join_mixed_device) ------------------
+    def _mixed_rel(self, cols, vals, valid, name):
+        """Key columns -- a 1-D contiguous device tensor (fixed-width) or a (chars uint8, offsets int64 [n + 1]) pair (an Arrow
+        large_string column; chars may be None or empty when every slot is empty) --, payloads (int64 [n] or None) and the
+        per-column validity list -> (MixedRel, what must stay alive for the call).  Types, widths, alignment and column
+        counts are checked by the library."""
+        cols = list(cols)
+        n = None
+        for k, col in enumerate(cols):
+            if isinstance(col, (tuple, list)):
+                _check_col(col[1], "%s column %d: offsets" % (name, k))
+                if col[1].shape[0] < 1:
+                    raise ValueError("%s column %d: offsets must hold n + 1 entries" % (name, k))
+                m = col[1].shape[0] - 1
+            else:
+                if not col.is_cuda or not col.is_contiguous() or col.dim() != 1:
+                    raise ValueError("%s column %d must be a contiguous 1-D device tensor" % (name, k))
+                m = col.shape[0]
+            if n is None:
+                n = m
+            if m != n:
+                raise ValueError("%s: key columns must have one length" % name)
+        if n is None:
+            n = vals.shape[0] if vals is not None else 0
+        if vals is not None:
+            _check_col(vals, "vals")
+            if vals.shape[0] != n:
+                raise ValueError("vals must hold one payload per row")
+        if valid is not None and len(list(valid)) != len(cols):
+            raise ValueError("%s_valid: one entry per key column" % name)
+        arr = (_lib.MixedCol * max(len(cols), 1))()
+        keep = [arr, cols]
+        for k, col in enumerate(cols):
+            if isinstance(col, (tuple, list)):
+                arr[k].type = _lib.HMJ_KEY_LARGE_STRING
+                arr[k].width = 0
+                arr[k].data = _chars_ptr(col[0])
+                arr[k].offsets = col[1].data_ptr()
+            else:
+                arr[k].type = _lib.HMJ_KEY_FIXED
+                arr[k].width = col.element_size()
+                arr[k].data = col.data_ptr() if n else None
+            if valid is not None and list(valid)[k] is not None:
+                keep.append(self._str_validity(list(valid)[k], n, "%s_valid[%d]" % (name, k), arr[k].validity))
+        r = _lib.MixedRel()
+        r.cols = arr
+        r.n_cols = len(cols)
+        r.vals = vals.data_ptr() if (vals is not None and n) else None
+        r.n = n
+        return r, keep
+
+    def join_mixed_device(self, build_cols, build_vals, probe_cols, probe_vals, side, kind, flags=0, hash_bits=0, probe_fill=0,
+                          build_fill=0, build_valid=None, probe_valid=None):
+        """Inner / semi / anti / outer joins of two device relations on a key tuple of string and fixed-width columns
+        (hmj_join_mixed_device).  *_cols: one entry per key column -- a 1-D contiguous device tensor whose element_size() is
+        1, 2, 4 or 8 (compared bit for bit), or a (chars uint8, offsets int64 [n + 1]) pair, the Arrow large_string layout
+        (`pack_strings`; compared byte for byte); *_vals: an int64 tensor [n], or None (the payload of row i is i).  side /
+        kind as for `join_kind_cols_device`, HMJ_KIND_PROBE_SIDE + HMJ_JOIN_INNER included.  *_valid: None, or a list with
+        one entry per key column -- None, a uint8 device tensor holding the column's Arrow validity bitmap
+        (`pack_validity`), or (tensor, bit_offset); a row with a NULL in any key column has no partner.  Returns (ColsResult,
+        {"n_probe_matched", "n_probe_unmatched", "n_build_matched", "n_build_unmatched", "n_key_pairs", "n_collisions",
+        "n_build_null", "n_probe_null", "ms_key", "ms_join", "ms_verify", "ms_emit", "ms_order"}); read the rows with
+        `mixed_rows_to_numpy`, reproduce key64 with `mixed_key64`."""
+        self._sync_stream()
+        rb, keep_b = self._mixed_rel(build_cols, build_vals, build_valid, "build")
+        rp, keep_p = self._mixed_rel(probe_cols, probe_vals, probe_valid, "probe")
+        opts = _lib.MixedOpts()
+        opts.struct_size = C.sizeof(_lib.MixedOpts)
+        opts.side = int(side)
+        opts.kind = int(kind)
+        opts.hash_bits = int(hash_bits)
+        opts.probe_fill = int(probe_fill) & 0xFFFFFFFFFFFFFFFF
+        opts.build_fill = int(build_fill) & 0xFFFFFFFFFFFFFFFF
+        res = _lib.ColsResult()
+        self._check(self.L.hmj_join_mixed_device(self.h, C.byref(rb), C.byref(rp), flags, C.byref(opts), C.byref(res)))
+        del keep_b, keep_p
+        info = opts.counts.as_dict()
+        info.update({"n_key_pairs": int(opts.n_key_pairs), "n_collisions": int(opts.n_collisions),
+                     "n_build_null": int(opts.n_build_null), "n_probe_null": int(opts.n_probe_null)})
+        for k in ("ms_key", "ms_join", "ms_verify", "ms_emit", "ms_order"):
+            info[k] = float(getattr(opts, k))
+        return res, info
+
+    def mixed_rows_to_numpy(self, res):
+        """Copy a mixed-key join's device result out as an [n,5] uint64 array of (key64, r_row, s_row, rval, sval); a column
+        the kind does not produce (r_row / rval of probe SEMI / ANTI, s_row / sval of BUILD_SEMI / BUILD_ANTI) reads as 0."""
+        return self.cols_kind_rows_to_numpy(res)
+
     # ---- columns through a row map (hmj_take_cols_device) ------------------------------------------------
     def take_cols_device(self, cols, row_map, valid=None, n_out=None, want_validity=True):
         """Take fixed-width columns of one relation through a row map (hmj_take_cols_device): output row i is source row
@@ -913,6 +1001,48 @@ def cols_key64(columns, widths, hash_bits=0, force_hashed=False):
     h = np.full(n, len(widths), np.uint64)
     for v in vs:
         h = _mix64(h + v + np.uint64(0x9E3779B97F4A7C15))
+    return h >> np.uint64(64 - int(hash_bits)) if hash_bits else h
+
+
+def _hash_bytes(b):
+    """libstdc++'s _Hash_bytes (64-bit size_t, seed 0xc70f6907): std::hash<std::string> of the bytes b."""
+    M, mask = 0xc6a4a7935bd1e995, 0xFFFFFFFFFFFFFFFF
+    n = len(b)
+    h = (0xc70f6907 ^ (n * M)) & mask
+    for k in range(0, n & ~7, 8):
+        d = (int.from_bytes(b[k:k + 8], "little") * M) & mask
+        d = ((d ^ (d >> 47)) * M) & mask
+        h = ((h ^ d) * M) & mask
+    if n & 7:
+        h = ((h ^ int.from_bytes(b[n & ~7:], "little")) * M) & mask
+    h = ((h ^ (h >> 47)) * M) & mask
+    return h ^ (h >> 47)
+
+
+def mixed_key64(columns, hash_bits=0):
+    """The 64-bit join key hmj_join_mixed_device gives every row (include/hmj.h), restated on the host: uint64 array [n].
+    columns: one entry per key column -- a numpy integer array (a fixed-width column: its values zero-extended from the
+    dtype's width) or a list of `bytes` (a string column: libstdc++'s _Hash_bytes of every slot, all 64 bits).
+    h = k; h = mix64(h + v_c + 0x9E3779B97F4A7C15) per column; hash_bits 1..63 keeps the top bits."""
+    if not 1 <= len(columns) <= _lib.HMJ_MAX_KEY_COLS:
+        raise ValueError("1..%d columns" % _lib.HMJ_MAX_KEY_COLS)
+    if not 0 <= int(hash_bits) <= 63:
+        raise ValueError("hash_bits must be in 0..63")
+    vs = []
+    for col in columns:
+        if isinstance(col, np.ndarray):
+            a = np.ascontiguousarray(col)
+            if a.dtype.itemsize not in (1, 2, 4, 8):
+                raise ValueError("a fixed-width column has 1, 2, 4 or 8 bytes per value")
+            vs.append(a.view("u%d" % a.dtype.itemsize).astype(np.uint64))
+        else:
+            vs.append(np.array([_hash_bytes(bytes(b)) for b in col], np.uint64))
+    if any(len(v) != len(vs[0]) for v in vs):
+        raise ValueError("columns must have one length")
+    h = np.full(len(vs[0]), len(vs), np.uint64)
+    with np.errstate(over="ignore"):
+        for v in vs:
+            h = _mix64(h + v + np.uint64(0x9E3779B97F4A7C15))
     return h >> np.uint64(64 - int(hash_bits)) if hash_bits else h
 
 

@@ -396,7 +396,7 @@ int hmj_exchange_join_kind_u64_device(hmj_ctx* ctx, const void* build_shard_dev,
  * match (count modes and materialising joins of relations of similar size plan alike; a join that plans
  * differently simply partitions R again) skips re-partitioning R; any other call discards the prepared state.  The caller promises the build rows do not change in between.
  * "Any other call" is every call that runs on the device or touches the workspace: the joins of every kind (u64, string,
- * multi-column -- hmj_join_cols_device, hmj_join_kind_cols_device --, host-resident, exchange), hmj_sort_u64_device, hmj_sort_rows_by_u64_host, hmj_argsort_u64_host, hmj_partition_u64_device,
+ * multi-column -- hmj_join_cols_device, hmj_join_kind_cols_device --, mixed-key -- hmj_join_mixed_device --, host-resident, exchange), hmj_sort_u64_device, hmj_sort_rows_by_u64_host, hmj_argsort_u64_host, hmj_partition_u64_device,
  * hmj_hash_str_device (each of them also when given no rows), hmj_reserve and hmj_autotune_radix_bits.  Left out are the calls that read or write no workspace buffer: hmj_set_stream,
  * hmj_set_radix_bits / hmj_set_key_prefix_bits (the join then plans other bits and partitions R again), hmj_set_profiling,
  * hmj_forget_workloads, hmj_release_result (result columns only), the hmj_last_* / hmj_placement_info queries, the
@@ -766,6 +766,75 @@ typedef struct {
 int hmj_join_kind_cols_device(hmj_ctx* ctx, const hmj_cols_rel* build, const hmj_cols_rel* probe, uint32_t flags,
                               hmj_cols_kind_opts* opts, hmj_cols_result* out);
 
+/* ---- mixed keys: string and fixed-width columns in one tuple ----------------------------------------- */
+/* The joins of hmj_join_kind_cols_device on a key tuple whose columns are Arrow large_string columns and fixed-width
+ * columns in any order (ON a.name = b.name AND a.day = b.day; two string columns; ...).  One entry for all eight (side,
+ * kind) pairs, HMJ_KIND_PROBE_SIDE + HMJ_JOIN_INNER included; the result struct is hmj_cols_result.  The key is always
+ * hashed: a caller whose columns are all fixed-width should prefer hmj_join_kind_cols_device, whose packed form needs no
+ * verification; fixed-only and string-only column sets are still legal here.  Nothing in the reference corresponds (one
+ * Key type per operator, hashjoin.h:33-56).
+ * Everything the header text of hmj_join_kind_cols_device says holds here word for word -- kinds and their columns, row
+ * contents (row indices, payloads; vals == NULL: the payload of row i is i), sums and checksums, counts, empty sides,
+ * flags (HMJ_FIRST_WINS is HMJ_E_ARG), the NULL-key table -- with these points changed:
+ * Match rule: every column equal.  A fixed column is equal bit for bit; a string column byte for byte -- equal length and
+ * equal bytes, NUL and bytes >= 0x80 being ordinary bytes.  Both relations need the same n_cols and, per column, the same
+ * type and width.
+ * key64: h = k; for c in 0..k-1: h = mix64(h + v_c + 0x9E3779B97F4A7C15) (hmj_join_cols_device's hashed form), with
+ *   v_c = the column's value zero-extended to 64 bits                         for a fixed column,
+ *   v_c = libstdc++'s _Hash_bytes of the slot's bytes, all 64 bits, seed 0xc70f6907 -- std::hash<std::string>, what
+ *         hmj_hash_str_device returns with hash_bits 0 --                      for a string column;
+ *   key64 = hash_bits ? h >> (64 - hash_bits) : h.  A string's length is inside _Hash_bytes, so ("ab","c") and ("a","bc")
+ *   differ before verification, and they differ after it.
+ * HMJ_ORDERED: rows ascending by (key64, the tuple column by column, r_row, s_row), HMJ_COLS_NO_ROW last: fixed columns
+ * compare as unsigned integers, string columns as std::string::operator< (unsigned bytes, then length).  NULL-key rows go
+ * into the tail exactly as in the column join.
+ * NULL keys: the bitmaps are part of the columns (hmj_mixed_col.validity; bits == NULL: no NULL in the column).  A row is
+ * a NULL-key row when any key column is NULL in it: the same eight-row table, key64 0, counters and n_build_null /
+ * n_probe_null.  A valid empty string is a key.  The bytes and the length under a NULL slot are undefined, but its
+ * offsets must still be non-decreasing.  A call without any bitmap launches neither valid_count_kernel nor its scan.
+ * HMJ_E_ARG (hmj_last_error names what was wrong): everything hmj_join_kind_cols_device rejects; an unknown type; width
+ * != 0 on a string column or offsets != NULL on a fixed one; NULL offsets with n > 0 (or offsets not aligned to 8 bytes);
+ * a type or width that differs between the sides (the message names the column); bit_offset + n overflowing 64 bits; key
+ * bytes under data == NULL; decreasing offsets.  The last two are found on the device by the key kernel, before anything
+ * reads a key byte through them: hmj_last_error names the relation, the lowest-numbered offending column and, for
+ * decreasing offsets, that column's first offending row.  The ctx stays usable.
+ * HMJ_E_UNSUPPORTED where the column join returns it, with the same 1024-row and 2^22 limits.
+ * The result lives until the next call on the ctx / hmj_release_result.  r_row / s_row are valid row maps for
+ * hmj_take_cols_device (fixed columns) and hmj_take_str_device (string columns).  hmj_last_plan / hmj_last_timing
+ * describe the last internal u64 join; the workloads are keyed apart from every other entry's (workload kinds 20..24), and
+ * the entry has a workspace of its own.  Like any other call it discards a prepared build side.
+ * How (DESIGN.md "Mixed keys (string and fixed-width columns)"): mix_key_kernel, one lane per row, walks the columns
+ * once -- a fixed column is one coalesced load per wave; for a string column the wave stages its 64 keys' byte span in
+ * LDS as the string join's hash kernel does -- and writes one {key64, row} row; the rest is the column join's sequence on
+ * a key policy that compares fixed columns first, then string lengths, then bytes.
+ * Out of scope: 32-bit-offset `string` columns, the exchange (multi-GPU) path, host-resident columns, NULL-equals-NULL
+ * matching (IS NOT DISTINCT FROM), collated or signed ordering, a packed form for mixed keys.                          */
+#define HMJ_KEY_FIXED 0u
+#define HMJ_KEY_LARGE_STRING 1u
+typedef struct {
+  uint32_t type;            /* HMJ_KEY_FIXED / HMJ_KEY_LARGE_STRING                                              */
+  uint32_t width;           /* FIXED: 1, 2, 4 or 8.  LARGE_STRING: 0                                             */
+  const void* data;         /* FIXED: n values aligned to width.  LARGE_STRING: the chars buffer (unaligned is   */
+                            /* fine; NULL is legal when every slot, valid or NULL, has length 0)                 */
+  const uint64_t* offsets;  /* LARGE_STRING: n + 1 non-decreasing offsets, offsets[0] need not be 0. FIXED: NULL */
+  hmj_validity validity;    /* bits == NULL: no NULL in this column                                              */
+} hmj_mixed_col;
+typedef struct {
+  const hmj_mixed_col* cols; /* HOST array of n_cols entries (read during the call only); what they point to: device */
+  uint32_t n_cols, reserved; /* 1 .. HMJ_MAX_KEY_COLS; 0                                                              */
+  const uint64_t* vals;      /* device: n payloads; NULL = the payload of row i is i                                  */
+  uint64_t n;                /* rows, <= 2^32 - 1                                                                     */
+} hmj_mixed_rel;
+typedef struct {
+  uint32_t struct_size, side, kind, hash_bits; /* in: sizeof of the caller's header (at least through build_fill); as hmj_cols_kind_opts */
+  uint64_t probe_fill, build_fill;             /* in: as hmj_cols_kind_opts                                                               */
+  hmj_kind_counts counts;                      /* out: as hmj_cols_kind_opts (zeros for INNER)                                            */
+  uint64_t n_key_pairs, n_collisions, n_build_null, n_probe_null; /* out: as hmj_cols_kind_opts                                           */
+  float ms_key, ms_join, ms_verify, ms_emit, ms_order; /* out, with hmj_set_profiling(ctx, 1) (INNER: ms_emit 0)                          */
+} hmj_mixed_opts;
+int hmj_join_mixed_device(hmj_ctx* ctx, const hmj_mixed_rel* build, const hmj_mixed_rel* probe, uint32_t flags,
+                          hmj_mixed_opts* opts, hmj_cols_result* out);
+
 /* ---- taking fixed-width columns through a row map (Arrow validity out) --------------------------------- */
 /* The joins above return gather maps (r_row / s_row), not columns.  This entry turns a map back into Arrow columns: up to
  * HMJ_MAX_TAKE_COLS fixed-width columns of ONE relation (n_src rows each; keys, payloads, anything of 1, 2, 4, 8 or 16
@@ -782,7 +851,8 @@ int hmj_join_kind_cols_device(hmj_ctx* ctx, const hmj_cols_rel* build, const hmj
  * HMJ_TAKE_NO_ROW over sources without bitmaps gives all-ones bitmaps (padding 0) and null_count 0.  opts->n_no_row: the
  * map entries equal to HMJ_TAKE_NO_ROW.
  * row_map may be a column the ctx owns -- the last result's r_row / s_row of hmj_join_cols_device,
- * hmj_join_kind_cols_device, hmj_join_str_device or hmj_join_kind_str_device -- or any device array of the caller's.  The
+ * hmj_join_kind_cols_device, hmj_join_mixed_device, hmj_join_str_device or hmj_join_kind_str_device -- or any device array
+ * of the caller's.  The
  * call neither releases nor overwrites the last result and does not discard a prepared build side; its only workspace is
  * a small counter buffer of its own.  hmj_last_plan, hmj_last_timing and the workload memos stay as they were.  It returns
  * with the work complete on the ctx stream, like the joins; the counts come back to the host.
@@ -831,7 +901,8 @@ int hmj_take_cols_device(hmj_ctx* ctx, const hmj_take_src* src, uint32_t n_cols,
 /* The sibling of hmj_take_cols_device for ONE variable-width column per call: an Arrow large_string / large_binary column
  * (n_src rows: n_src + 1 64-bit offsets into a chars buffer, an optional validity bitmap) is taken through row_map (n_out
  * entries) into caller-owned offsets, chars and an optional validity bitmap, in the same contract style: what turns the
- * r_row / s_row of the string joins back into their key strings, or takes any other string column of either relation.  src,
+ * r_row / s_row of the string joins (and the string key columns of hmj_join_mixed_device) back into their key strings,
+ * or takes any other string column of either relation.  src,
  * dst and opts are host structs; everything they point to is on the device.
  * NULL and empty slots.  Output slot i is NULL when row_map[i] == HMJ_TAKE_NO_ROW or source row row_map[i] is NULL
  * (src->validity, any bit_offset; bits == NULL: no NULL).  A NULL slot has length 0, whatever bytes the source holds under
