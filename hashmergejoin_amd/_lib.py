@@ -8,6 +8,7 @@ HMJ_ORDERED = 0x02
 HMJ_FIRST_WINS = 0x04
 HMJ_CHECKSUM = 0x08
 HMJ_SUM_PROBE = 0x10
+HMJ_NULL_EQUAL = 0x20  # NULL key slots match NULL slots of the same column (the column kinds and the mixed entry)
 HMJ_E_RCCL, HMJ_E_PEER, HMJ_E_TIMEOUT = -6, -7, -8
 # hmj_timing.path bits
 HMJ_PATH_SLAB, HMJ_PATH_EXACT, HMJ_PATH_UNIQ_WRITE, HMJ_PATH_SPLIT, HMJ_PATH_WINDOW = 0x1, 0x2, 0x4, 0x8, 0x10

@@ -31,6 +31,9 @@
 // sweeps walk by row index (a NULL-key row: key64 0, row HMJ_COLS_NO_ROW) and the compacted rows of the valid rows, which are
 // all the u64 joins see -- so a NULL-key row is never paired and never marked.  Ordered kinds: the sweeps emit the NULL-key
 // rows into a tail behind the rows that are sorted (DESIGN.md "NULL keys (validity bitmaps)").
+// NULL-equals-NULL matching (HMJ_NULL_EQUAL with a bitmap): none of that -- cols_key_ne_kernel gives every row a key (a NULL
+// slot hashes as 0, the row's NULL-column mask is mixed in last), and the sequence above runs in its hashed form on
+// ColNeSide / ColNePolicy, whose key_eq / key_cmp read the bitmaps (DESIGN.md "NULL-equals-NULL matching").
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -78,6 +81,49 @@ __device__ __forceinline__ int key_cmp(const ColSide& A, u64 a, const ColSide& B
     if (c < k && r == 0) {
       const u64 x = col_load(A.p[c], w, a), y = col_load(B.p[c], w, b);
       if (x != y) r = x < y ? -1 : 1;
+    }
+  }
+  return r;
+}
+
+// NULL-equals-NULL matching (HMJ_NULL_EQUAL, calls that pass a bitmap only): the relation with its validity bitmaps.  A
+// NULL slot is a value of its own that equals only the NULL slot of the same column and sorts behind every valid value;
+// what lies under it is never loaded.  Where a lane chooses its side at run time the bitmap pointers are the lane's own
+// (a per-lane branch); count and widths stay the first lane's.
+struct ColNeSide {
+  ColSide s;
+  ColValid v;
+};
+__device__ __forceinline__ u64 payload(const ColNeSide& A, u64 i) { return payload(A.s, i); }
+__device__ __forceinline__ bool key_eq(const ColNeSide& A, u64 a, const ColNeSide& B, u64 b) {
+  bool eq = true;
+  const int k = uniform(A.s.k);
+#pragma unroll
+  for (int c = 0; c < kMaxCols; c++) {
+    const u32 w = uniform(A.s.w[c]);
+    if (c < k && eq) {
+      const bool na = slot_null(A.v, c, a), nb = slot_null(B.v, c, b);
+      if (na || nb) eq = na && nb;
+      else eq = col_load(A.s.p[c], w, a) == col_load(B.s.p[c], w, b);
+    }
+  }
+  return eq;
+}
+// column by column, NULLS LAST in each: two NULL slots tie
+__device__ __forceinline__ int key_cmp(const ColNeSide& A, u64 a, const ColNeSide& B, u64 b) {
+  int r = 0;
+  const int k = uniform(A.s.k);
+#pragma unroll
+  for (int c = 0; c < kMaxCols; c++) {
+    const u32 w = uniform(A.s.w[c]);
+    if (c < k && r == 0) {
+      const bool na = slot_null(A.v, c, a), nb = slot_null(B.v, c, b);
+      if (na || nb) {
+        r = (int)na - (int)nb;
+      } else {
+        const u64 x = col_load(A.s.p[c], w, a), y = col_load(B.s.p[c], w, b);
+        if (x != y) r = x < y ? -1 : 1;
+      }
     }
   }
   return r;
@@ -164,6 +210,62 @@ __global__ __launch_bounds__(CJ_THREADS) void cols_key_valid_kernel(ColSide A, C
     u64 t = 0;
     for (int k = 0; k < CJ_WAVES; k++) t += red[k];
     if (t) atomicAdd(&acc[KA_SUM_P], t);
+  }
+}
+
+// ---- NULL-equals-NULL matching (HMJ_NULL_EQUAL) ----------------------------------------------------------------------------
+// cols_key_kernel for a call that matches NULL slots with NULL slots (always HASHED): every row gets a key, so there is
+// nothing to count, scan or compact -- one dense {key64, row} row per row, as without bitmaps.  Grid-stride by waves: a
+// wave keys the 64 consecutive rows from i0 (a multiple of 64, wave-uniform), and reads a column's 64 validity bits as one
+// or two aligned 8-byte words (wave_valid_word).  A NULL slot contributes v_c = 0 and is not loaded; the row's NULL columns
+// (m: bit c for column c) are mixed in behind the last column, so a row without NULLs has exactly cols_key_kernel's key64.
+// n_null: the relation's kNullWords words for the rows with m != 0 (count_null_rows: one atomic per workgroup).  sum_probe as
+// cols_key_kernel.
+__global__ __launch_bounds__(CJ_THREADS) void cols_key_ne_kernel(ColSide A, ColValid V, u64 n, u32 hash_bits, u64* __restrict__ out,
+                                                                 int sum_probe, u64* __restrict__ acc, u64* __restrict__ n_null) {
+  __shared__ u64 red[CJ_WAVES];
+  __shared__ u32 nred[CJ_WAVES];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  u64 sum = 0;
+  u32 nulls = 0;  // rows of this wave's steps with a NULL slot (the same in every lane)
+  for (u64 i0 = uniform64((u64)blockIdx.x * CJ_THREADS + (u64)(w * 64)); i0 < n; i0 += (u64)gridDim.x * CJ_THREADS) {
+    const u32 cnt = n - i0 < 64ull ? (u32)(n - i0) : 64u;
+    const u64 i = i0 + (u64)lane;
+    const bool active = (u32)lane < cnt;
+    u64 key = (u64)A.k, m = 0;
+#pragma unroll
+    for (int c = 0; c < kMaxCols; c++) {
+      if (c < (int)A.k) {
+        bool null = false;
+        if (V.bits[c]) null = !((wave_valid_word(V.bits[c], V.off[c], i0, cnt) >> lane) & 1ull);  // (uniform branch)
+        u64 v = 0;
+        if (active && !null) v = col_load(A.p[c], A.w[c], i);
+        if (null) m |= 1ull << c;
+        key = hmj::mix64(key + v + kGolden);
+      }
+    }
+    if (m) key = hmj::mix64(key + m + kGolden);
+    key = fold_bits(key, hash_bits);
+    if (active) {
+      reinterpret_cast<ulonglong2*>(out)[i] = make_ulonglong2(key, i);
+      if (sum_probe) sum += payload(A, i);
+    }
+    nulls += (u32)__builtin_popcountll(__ballot(active && m != 0));
+  }
+  if (sum_probe) sum = hmj::wave_sum_u64(sum);  // (uniform)
+  if (lane == 0) {
+    red[w] = sum;
+    nred[w] = nulls;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    u64 t = 0, tn = 0;
+    for (int k = 0; k < CJ_WAVES; k++) {
+      t += red[k];
+      tn += nred[k];
+    }
+    if (sum_probe && t) atomicAdd(&acc[KA_SUM_P], t);
+    count_null_rows(n_null, tn);
   }
 }
 
@@ -327,7 +429,7 @@ struct ColPolicy {
   static const KeyJoinNames& names() { return kNames; }
   static KeyJoinWs& ws(hmj_ctx* c) { return c->col_ws; }
   static int keys_begin(hmj_ctx*) { return HMJ_OK; }
-  static int keys_check(hmj_ctx*) { return HMJ_OK; }
+  static int keys_check(hmj_ctx*, TupleCall*) { return HMJ_OK; }
   static int key(hmj_ctx* c, const ColSide& A, int, u64 n, const TupleCall& call, u64* out, bool sum_probe, u64* acc) {
     return launch_key(c, A, n, call.hashed, call.bits, out, sum_probe, acc);
   }
@@ -363,6 +465,51 @@ struct ColPolicy {
   }
 };
 
+// HMJ_NULL_EQUAL with a bitmap on either side: the hashed form on ColNeSide.  The driver runs its no-bitmap path (every row
+// has a key; VB == VP == NULL in tuple_join / tuple_join_kind), so key_valid is never reached.  The {key64,row} joins are
+// the hashed column join's, under its memo kinds: what they learn about a relation's key64 distribution holds for both.
+struct ColNePolicy {
+  using Side = ColNeSide;
+  static constexpr bool kCanPack = false;
+  static constexpr int kAccExtra = 2 * kNullWords;  // the key kernels' counts of rows with a NULL slot: build, probe
+  static constexpr int kMemoInner = ColPolicy::kMemoInner, kMemoProbeRep = ColPolicy::kMemoProbeRep;
+  static constexpr int kMemoBuildRep = ColPolicy::kMemoBuildRep, kMemoAmbiguous = ColPolicy::kMemoAmbiguous;
+  static constexpr int kMemoPairs = ColPolicy::kMemoPairs;
+  static const KeyJoinNames& names() { return kNames; }
+  static KeyJoinWs& ws(hmj_ctx* c) { return c->col_ws; }
+  static int keys_begin(hmj_ctx* c) {
+    HIP_TRY(hipMemsetAsync(tuple_acc_extra<ColNePolicy>(c), 0, kAccExtra * sizeof(u64), c->stream));
+    return HMJ_OK;
+  }
+  static int keys_check(hmj_ctx* c, TupleCall* call) {
+    u64 nn[kAccExtra];
+    RC_TRY(read_back(c, tuple_acc_extra<ColNePolicy>(c), nn, sizeof(nn)));
+    call->n_build_null = null_rows_of(nn);
+    call->n_probe_null = null_rows_of(nn + kNullWords);
+    return HMJ_OK;
+  }
+  static int key(hmj_ctx* c, const ColNeSide& A, int rel, u64 n, const TupleCall& call, u64* out, bool sum_probe, u64* acc) {
+    if (!n) return HMJ_OK;
+    const u64 need = blocks_of(n), most = (u64)c->num_cus * 16;
+    hipLaunchKernelGGL(cols_key_ne_kernel, dim3((u32)(need < most ? need : most)), dim3(CJ_THREADS), 0, c->stream, A.s, A.v, n, call.bits, out,
+                       sum_probe ? 1 : 0, acc, tuple_acc_extra<ColNePolicy>(c) + rel * kNullWords);
+    HIP_TRY(hipGetLastError());
+    return HMJ_OK;
+  }
+  static int key_valid(hmj_ctx* c, const ColNeSide&, const ColValid&, int, u64, const TupleCall&, u64, u64*, u64*, u64, const u64*, bool, u64*) {
+    return fail(c, HMJ_E_HIP, "multi-column join: the NULL-equals-NULL form compacts no rows");
+  }
+};
+// V == NULL: the relation has no bitmap (no NULL slot)
+ColNeSide ne_side_of(const hmj_cols_rel* r, const ColValid* V) {
+  ColNeSide A;
+  std::memset(&A, 0, sizeof(A));
+  A.s = side_of(r);
+  if (V) A.v = *V;
+  A.v.k = r->n_cols;
+  return A;
+}
+
 bool cols_hashed(const hmj_cols_rel* R, uint32_t force_hashed) {
   u32 total = 0;
   for (u32 k = 0; k < R->n_cols; k++) total += R->cols[k].width;
@@ -371,14 +518,16 @@ bool cols_hashed(const hmj_cols_rel* R, uint32_t force_hashed) {
 
 // VB / VP: the relations' validity bitmaps, NULL where a relation has none (both NULL: the call without NULL keys, all
 // hmj_join_cols_device makes -- hmj_cols_join_opts carries no bitmaps; the INNER kind of hmj_join_kind_cols_device passes
-// its own).  n_null (with bitmaps): the NULL-key rows of the build and the probe side.
+// its own).  n_null (with bitmaps): the NULL-key rows of the build and the probe side.  null_equal (with a bitmap): NULL
+// slots match NULL slots -- the hashed form on ColNeSide, the bitmaps inside the sides.
 int join_cols(hmj_ctx* c, const hmj_cols_rel* R, const hmj_cols_rel* S, uint32_t flags, hmj_cols_join_opts* opts, hmj_cols_result* out,
-              const ColValid* VB = nullptr, const ColValid* VP = nullptr, u64* n_null = nullptr) {
+              const ColValid* VB = nullptr, const ColValid* VP = nullptr, u64* n_null = nullptr, bool null_equal = false) {
   TupleCall call;
-  call.hashed = cols_hashed(R, opts->force_hashed);
+  call.hashed = null_equal || cols_hashed(R, opts->force_hashed);
   call.bits = call.hashed ? opts->hash_bits : 0;
   if (R->n && S->n) opts->form = call.hashed ? HMJ_COLS_HASHED : HMJ_COLS_PACKED;
-  RC_TRY(tuple_join<ColPolicy>(c, side_of(R), R->n, side_of(S), S->n, flags, &call, out, VB, VP));
+  if (null_equal) RC_TRY(tuple_join<ColNePolicy>(c, ne_side_of(R, VB), R->n, ne_side_of(S, VP), S->n, flags, &call, out, nullptr, nullptr));
+  else RC_TRY(tuple_join<ColPolicy>(c, side_of(R), R->n, side_of(S), S->n, flags, &call, out, VB, VP));
   if (n_null && (VB || VP)) {
     n_null[0] = call.n_build_null;
     n_null[1] = call.n_probe_null;
@@ -389,16 +538,18 @@ int join_cols(hmj_ctx* c, const hmj_cols_rel* R, const hmj_cols_rel* S, uint32_t
 }
 
 int join_cols_kind(hmj_ctx* c, const hmj_cols_rel* R, const hmj_cols_rel* S, uint32_t flags, hmj_cols_kind_opts* o, hmj_cols_result* out,
-                   const ColValid* VB, const ColValid* VP) {
+                   const ColValid* VB, const ColValid* VP, bool null_equal) {
   TupleCall call;
-  call.hashed = cols_hashed(R, o->force_hashed);
+  call.hashed = null_equal || cols_hashed(R, o->force_hashed);
   call.bits = call.hashed ? o->hash_bits : 0;
   call.side = o->side;
   call.kind = o->kind;
   call.probe_fill = o->probe_fill;
   call.build_fill = o->build_fill;
   o->form = call.hashed ? HMJ_COLS_HASHED : HMJ_COLS_PACKED;
-  RC_TRY(tuple_join_kind<ColPolicy>(c, side_of(R), R->n, side_of(S), S->n, flags, &call, out, VB, VP));
+  if (null_equal)
+    RC_TRY(tuple_join_kind<ColNePolicy>(c, ne_side_of(R, VB), R->n, ne_side_of(S, VP), S->n, flags, &call, out, nullptr, nullptr));
+  else RC_TRY(tuple_join_kind<ColPolicy>(c, side_of(R), R->n, side_of(S), S->n, flags, &call, out, VB, VP));
   o->n_build_null = call.n_build_null;
   o->n_probe_null = call.n_probe_null;
   o->n_key_pairs = call.n_key_pairs;
@@ -494,6 +645,9 @@ int hmj_join_kind_cols_device(hmj_ctx* c, const hmj_cols_rel* build, const hmj_c
   ColValid VB, VP;
   const ColValid *vb, *vp;
   RC_TRY(opts_validity(c, opts, build, probe, &VB, &VP, &vb, &vp));
+  // NULL-equals-NULL matching needs a bitmap to differ from the call without the flag, which is what runs when there is none
+  const bool null_equal = (flags & HMJ_NULL_EQUAL) && (vb || vp);
+  flags &= ~HMJ_NULL_EQUAL;
   std::memset(out, 0, sizeof(*out));
   HIP_TRY(hipSetDevice(c->device));
   // the out fields of opts go to a full-size copy first; the caller gets the prefix its struct_size holds
@@ -509,12 +663,12 @@ int hmj_join_kind_cols_device(hmj_ctx* c, const hmj_cols_rel* build, const hmj_c
     jo.hash_bits = o.hash_bits;
     jo.force_hashed = o.force_hashed;
     u64 n_null[2] = {0, 0};
-    RC_TRY(join_cols(c, build, probe, flags, &jo, out, vb, vp, n_null));
+    RC_TRY(join_cols(c, build, probe, flags, &jo, out, vb, vp, n_null, null_equal));
     o.n_build_null = n_null[0];
     o.n_probe_null = n_null[1];
     u32 total = 0;  // (the inner entry leaves form 0 when a side is empty; here it is always filled)
     for (u32 k = 0; k < build->n_cols; k++) total += build->cols[k].width;
-    o.form = total > 8 || o.force_hashed ? HMJ_COLS_HASHED : HMJ_COLS_PACKED;
+    o.form = total > 8 || o.force_hashed || null_equal ? HMJ_COLS_HASHED : HMJ_COLS_PACKED;
     o.n_key_pairs = jo.n_key_pairs;
     o.n_collisions = jo.n_collisions;
     if (c->profiling) {
@@ -525,7 +679,7 @@ int hmj_join_kind_cols_device(hmj_ctx* c, const hmj_cols_rel* build, const hmj_c
       o.ms_order = elapsed(c->col_ws.ev, 3, 4);
     }
   } else {
-    RC_TRY(join_cols_kind(c, build, probe, flags, &o, out, vb, vp));
+    RC_TRY(join_cols_kind(c, build, probe, flags, &o, out, vb, vp, null_equal));
     if (c->profiling) {
       (void)hipStreamSynchronize(c->stream);
       o.ms_key = elapsed(c->col_ws.ev, 0, 1);

@@ -9,10 +9,13 @@
 //   P::names() / P::ws(c)      what error messages call the join; the workspace of the entry
 //   P::key(c, A, rel, n, call, out, sum_probe, acc)                          {key64,row} rows of a relation without bitmaps
 //   P::key_valid(c, A, V, rel, n, call, nblk, dense, comp, cap, off, sum_probe, acc)   ... of one with bitmaps (pass 2)
-//   P::keys_begin(c) / P::keys_check(c)   before the first key kernel / behind the last: where a key kernel that checks its
-//                                         input (string offsets) reports; both do nothing for fixed-width columns
+//   P::keys_begin(c) / P::keys_check(c, call)   before the first key kernel / behind the last: where a key kernel that checks
+//                                         its input (string offsets) reports, and where the NULL-equals-NULL key kernels'
+//                                         counts of rows with NULL slots reach call->n_*_null; the plain fixed-width
+//                                         policy does nothing in either
 //   P::gather(...)             kCanPack only: the packed form's payload gather
-// Also here: what both key kernels share -- col_load, the per-column validity bitmaps (ColValid / row_valid), kGolden.
+// Also here: what both key kernels share -- col_load, the per-column validity bitmaps (ColValid / row_valid, and for the
+// NULL-equals-NULL policies slot_null / wave_valid_word), kGolden.
 // Internal header: its contents are local to the file that includes it.
 #pragma once
 #include "hmj_keyjoin.h"
@@ -53,6 +56,44 @@ __device__ __forceinline__ bool row_valid(const ColValid& V, u64 i) {
     }
   }
   return ok;
+}
+
+// NULL-equals-NULL matching (HMJ_NULL_EQUAL): a NULL slot is a value of its own, so the bitmaps are read per column.
+// slot_null: row i is NULL in column c (one lane, any row: the comparisons of the shared kernels).
+__device__ __forceinline__ bool slot_null(const ColValid& V, int c, u64 i) {
+  const unsigned char* bits = V.bits[c];
+  if (!bits) return false;
+  const u64 b = V.off[c] + i;
+  return !((bits[b >> 3] >> (b & 7)) & 1u);
+}
+// The validity bits of rows [i0, i0 + cnt) of one column (1 <= cnt <= 64; row i0 + j at bit j; the bits from cnt on mean
+// nothing), for a wave that keys 64 consecutive rows: every argument is wave-uniform, so the one or two aligned 8-byte words
+// that hold the bits are loaded once per wave.  Only words that hold a wanted bit are read -- an aligned word that shares a
+// byte with the bitmap lies in the bitmap's pages, as bytes_cmp's words do (hmj_strkey.h).
+__device__ __forceinline__ u64 wave_valid_word(const unsigned char* bits, u64 off, u64 i0, u32 cnt) {
+  const u64 b0 = off + i0;
+  const uintptr_t at = (uintptr_t)bits + (uintptr_t)(b0 >> 3), base = at & ~(uintptr_t)7;
+  const u32 sh = (u32)((at - base) << 3) + (u32)(b0 & 7);  // 0..63: the first wanted bit inside the first word
+  const u64* wp = reinterpret_cast<const u64*>(base);
+  u64 word = wp[0] >> sh;
+  if (sh + cnt > 64u) word |= wp[1] << (64u - sh);  // (sh > 0 here)
+  return word;
+}
+__device__ __forceinline__ u64 uniform64(u64 v) {
+  return ((u64)uniform((u32)(v >> 32)) << 32) | (u64)uniform((u32)v);
+}
+// Where the NULL-equals-NULL key kernels count a relation's rows with a NULL slot: one atomic per workgroup, spread by
+// workgroup index over kNullSlots words that lie kNullStride words (one 128-byte line) apart -- one word takes about 88
+// atomics per microsecond, which 65536 workgroups of a 2^24-row relation would wait 0.7 ms for.  The host adds the slots up.
+constexpr int kNullSlots = 32, kNullStride = 16;
+constexpr int kNullWords = kNullSlots * kNullStride;
+__device__ __forceinline__ void count_null_rows(u64* __restrict__ slots, u64 t) {
+  if (t) atomicAdd(&slots[(blockIdx.x & (u32)(kNullSlots - 1)) * kNullStride], t);
+}
+inline u64 null_rows_of(const u64* slots) {
+  u64 t = 0;
+  for (int k = 0; k < kNullSlots; k++) t += slots[k * kNullStride];
+  return t;
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
@@ -150,7 +191,7 @@ int tuple_join(hmj_ctx* c, const typename P::Side& RS, u64 nb, const typename P:
     call->n_probe_null = np - nvp;
   }
   RC_TRY(record(c, ws.ev, 1));
-  RC_TRY(P::keys_check(c));
+  RC_TRY(P::keys_check(c, call));
   if (nvb == 0 || nvp == 0) {  // (nothing to join: no plan either)
     std::memset(&c->plan, 0, sizeof(c->plan));
     c->plan.struct_size = sizeof(c->plan);
@@ -289,7 +330,7 @@ int tuple_join_kind(hmj_ctx* c, const typename P::Side& RS, u64 nb, const typena
   if (nb) HIP_TRY(hipMemsetAsync(mark_r, 0, nb, c->stream));
   if (np) HIP_TRY(hipMemsetAsync(mark_s, 0, np, c->stream));
   RC_TRY(record(c, ws.ev, 1));
-  RC_TRY(P::keys_check(c));
+  RC_TRY(P::keys_check(c, o));
   // 2. + 3. the {key64,row} join(s) and the tuple verification, which marks the rows that have a partner
   u64 n_pairs = 0;
   hmj_result inner;

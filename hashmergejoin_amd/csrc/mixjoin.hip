@@ -12,11 +12,14 @@
 //                       hmj_keyjoin.h's kernels on MixSide.
 // The key policy (key_eq / key_cmp / payload on MixSide) compares fixed columns as coljoin.hip does and string columns
 // as strjoin.hip does (bytes_cmp: aligned 8-byte loads that never leave the words holding key bytes).
+// NULL-equals-NULL matching (HMJ_NULL_EQUAL with a bitmap): mix_key_kernel<false, true> keys every row, and the sequence
+// runs on MixNeSide / MixNePolicy, whose key_eq / key_cmp read the bitmaps before any value, length or byte.
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 
 #include "hmj_tuplejoin.h"
 #include "hmj_strkey.h"
@@ -86,8 +89,74 @@ __device__ __forceinline__ int key_cmp(const MixSide& A, u64 a, const MixSide& B
   return r;
 }
 
+// NULL-equals-NULL matching (HMJ_NULL_EQUAL, calls that pass a bitmap only): the relation with its validity bitmaps.  A
+// NULL slot is a value of its own that equals only the NULL slot of the same column -- not the valid empty string -- and
+// sorts behind every valid value; neither the value nor the offsets under it are read.  The bitmap pointers are the lane's
+// own where a lane chooses its side at run time; count, types and widths stay the first lane's.
+struct MixNeSide {
+  MixSide s;
+  ColValid v;
+};
+__device__ __forceinline__ u64 payload(const MixNeSide& A, u64 i) { return payload(A.s, i); }
+// key_eq: the validity of every column first, then MixSide's order over the columns valid on both sides
+__device__ __forceinline__ bool key_eq(const MixNeSide& A, u64 a, const MixNeSide& B, u64 b) {
+  bool eq = true;
+  const int k = uniform(A.s.k);
+  u32 nulls = 0;  // the columns NULL on both sides
+#pragma unroll
+  for (int c = 0; c < kMaxCols; c++) {
+    if (c < k && eq) {
+      const bool na = slot_null(A.v, c, a), nb = slot_null(B.v, c, b);
+      eq = na == nb;
+      if (na) nulls |= 1u << c;
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < kMaxCols; c++) {
+    const u32 w = uniform(A.s.w[c]);
+    if (c < k && w && eq && !((nulls >> c) & 1u)) eq = col_load(A.s.p[c], w, a) == col_load(B.s.p[c], w, b);
+  }
+#pragma unroll
+  for (int c = 0; c < kMaxCols; c++) {
+    const u32 w = uniform(A.s.w[c]);
+    if (c < k && !w && eq && !((nulls >> c) & 1u)) eq = A.s.off[c][a + 1] - A.s.off[c][a] == B.s.off[c][b + 1] - B.s.off[c][b];
+  }
+#pragma unroll
+  for (int c = 0; c < kMaxCols; c++) {
+    const u32 w = uniform(A.s.w[c]);
+    if (c < k && !w && eq && !((nulls >> c) & 1u)) {
+      const u64 pa = A.s.off[c][a], pb = B.s.off[c][b], len = A.s.off[c][a + 1] - pa;
+      eq = bytes_cmp((const unsigned char*)A.s.p[c] + pa, len, (const unsigned char*)B.s.p[c] + pb, len) == 0;
+    }
+  }
+  return eq;
+}
+// strictly column by column, NULLS LAST in each: two NULL slots tie
+__device__ __forceinline__ int key_cmp(const MixNeSide& A, u64 a, const MixNeSide& B, u64 b) {
+  int r = 0;
+  const int k = uniform(A.s.k);
+#pragma unroll
+  for (int c = 0; c < kMaxCols; c++) {
+    const u32 w = uniform(A.s.w[c]);
+    if (c < k && r == 0) {
+      const bool na = slot_null(A.v, c, a), nb = slot_null(B.v, c, b);
+      if (na || nb) {
+        r = (int)na - (int)nb;
+      } else if (w) {
+        const u64 x = col_load(A.s.p[c], w, a), y = col_load(B.s.p[c], w, b);
+        if (x != y) r = x < y ? -1 : 1;
+      } else {
+        const u64 pa = A.s.off[c][a], la = A.s.off[c][a + 1] - pa, pb = B.s.off[c][b], lb = B.s.off[c][b + 1] - pb;
+        r = bytes_cmp((const unsigned char*)A.s.p[c] + pa, la, (const unsigned char*)B.s.p[c] + pb, lb);
+      }
+    }
+  }
+  return r;
+}
+
 // What the key kernel reports per relation (err: 2 * kMaxCols words): [c] the first row of column c whose offsets decrease
 // (~0: none), [kMaxCols + c] the waves of column c that hold key bytes under chars == NULL.
+// NE: kNullWords more words behind them, from [kErrWords]: the rows with a NULL slot (count_null_rows).
 constexpr int kErrWords = 2 * kMaxCols;
 
 // One lane per row, workgroup b keys rows [256 b, 256 b + 256).  The columns are walked in a fully unrolled loop whose
@@ -101,7 +170,13 @@ constexpr int kErrWords = 2 * kMaxCols;
 // VALID == false: out[i] = {key64, i}.  VALID: cols_key_valid_kernel's outputs -- dense (NULL: not wanted): {key64, i}, a
 // NULL-key row {0, HMJ_COLS_NO_ROW}; comp: the valid rows' {key64, i}, workgroup b's at blk_off[b] in row order; cap: rows
 // comp holds.  A NULL-key lane hashes no bytes.  sum_probe: every row's payload (NULL-key rows too) into acc[KA_SUM_P].
-template <bool VALID>
+// NE (HMJ_NULL_EQUAL; with VALID == false, whose dense output it keeps): every row has a key.  A column's validity bits of
+// the wave's rows are one or two aligned 8-byte words, loaded once per wave (wave_valid_word; the branch on the column's
+// bitmap pointer depends on kernel arguments only).  A NULL slot contributes v_c = 0: a fixed value is not loaded, a
+// string's bytes are not hashed (the wave still stages its span and still checks the slot's offsets); the row's NULL
+// columns (m: bit c for column c) are mixed in behind the last column.  The rows with m != 0 are counted into the words
+// from err[kErrWords], one atomic per workgroup (count_null_rows).
+template <bool VALID, bool NE = false>
 __global__ __launch_bounds__(MK_THREADS) void mix_key_kernel(MixSide A, ColValid V, u64 n, u32 hash_bits, u64* __restrict__ out,
                                                              u64* __restrict__ comp, u64 cap, const u64* __restrict__ blk_off,
                                                              int sum_probe, u64* __restrict__ acc, u64* __restrict__ err) {
@@ -115,6 +190,8 @@ __global__ __launch_bounds__(MK_THREADS) void mix_key_kernel(MixSide A, ColValid
   const u64 iend = i0 + 64 < n ? i0 + 64 : n;
   bool ok = active;  // the row has a key
   if (VALID) ok = active && row_valid(V, active ? i : 0);
+  const u32 cnt = (u32)(iend > i0 ? iend - i0 : 0);  // rows of this wave
+  u64 m = 0;                                         // NE: the row's NULL columns
   bool wave_ok = true;  // every string column of this wave had usable offsets
   bool staged_before = false;
   u64 h = (u64)A.k;
@@ -122,8 +199,11 @@ __global__ __launch_bounds__(MK_THREADS) void mix_key_kernel(MixSide A, ColValid
   for (int c = 0; c < kMaxCols; c++) {
     if (c < (int)A.k) {  // (kernel arguments: uniform over the grid)
       u64 v = 0;
+      bool null = false;
+      if (NE && V.bits[c] && cnt) null = !((wave_valid_word(V.bits[c], V.off[c], uniform64(i0), uniform(cnt)) >> lane) & 1ull);
+      if (NE && null) m |= 1ull << c;
       if (A.w[c]) {
-        if (active) v = col_load(A.p[c], A.w[c], i);
+        if (active && !null) v = col_load(A.p[c], A.w[c], i);
       } else {
         const unsigned char* chars = (const unsigned char*)A.p[c];
         const u64* offsets = A.off[c];
@@ -157,7 +237,7 @@ __global__ __launch_bounds__(MK_THREADS) void mix_key_kernel(MixSide A, ColValid
         }
         __syncthreads();
         if (!usable) wave_ok = false;
-        if (usable && ok) {
+        if (usable && ok && !null) {
           const u64 len = o1 - o0;
           if (staged) v = hash_bytes(LdsLd{&stage[w][0]}, (u64)((uintptr_t)(chars + o0) - b0), len);
           else v = hash_bytes(GlobalLd{}, (u64)(uintptr_t)(chars + o0), len);
@@ -166,7 +246,12 @@ __global__ __launch_bounds__(MK_THREADS) void mix_key_kernel(MixSide A, ColValid
       h = hmj::mix64(h + v + kGolden);
     }
   }
+  if (NE && m) h = hmj::mix64(h + m + kGolden);
   h = fold_bits(h, hash_bits);
+  if (NE) {
+    const u64 with_null = __ballot(active && m != 0);
+    if (lane == 0) wcnt[w] = (u32)__builtin_popcountll(with_null);
+  }
   u64 sum = 0;
   if (sum_probe && active) sum = payload(A, i);
   if (sum_probe) {  // (uniform)
@@ -176,6 +261,11 @@ __global__ __launch_bounds__(MK_THREADS) void mix_key_kernel(MixSide A, ColValid
   if (!VALID) {
     if (active) reinterpret_cast<ulonglong2*>(out)[i] = make_ulonglong2(h, i);
     __syncthreads();
+    if (NE && threadIdx.x == 0) {
+      u64 t = 0;
+      for (int q = 0; q < MK_WAVES; q++) t += wcnt[q];
+      count_null_rows(err + kErrWords, t);
+    }
   } else {
     ok = ok && wave_ok;
     const u64 key = ok ? h : 0ull;
@@ -200,10 +290,16 @@ __global__ __launch_bounds__(MK_THREADS) void mix_key_kernel(MixSide A, ColValid
 constexpr KeyJoinNames kNames{"mixed-key join", "key64", "tuples"};
 constexpr u64 kNone = ~0ull;
 
-struct MixPolicy {
-  using Side = MixSide;
+// NE: the policy of HMJ_NULL_EQUAL calls that pass a bitmap -- MixNeSide, the NE key kernel, kNullWords more report words
+// per relation.  The driver runs its no-bitmap path (every row has a key), so key_valid is never reached.  The {key64,row} joins
+// keep the entry's memo kinds: what they learn about a relation's key64 distribution holds with and without the flag.
+template <bool NE>
+struct MixPolicyT {
+  using Side = typename std::conditional<NE, MixNeSide, MixSide>::type;
+  using Self = MixPolicyT<NE>;
   static constexpr bool kCanPack = false;     // the key is always hashed
-  static constexpr int kAccExtra = 2 * kErrWords;  // the key kernel's report: the build relation's, then the probe relation's
+  static constexpr int kRelWords = kErrWords + (NE ? kNullWords : 0);  // the key kernel's report on one relation
+  static constexpr int kAccExtra = 2 * kRelWords;             // the build relation's, then the probe relation's
   // workload_signature kinds of the {key64,row} joins (u64 joins 0, sorts 1, kinds 3..9, string joins 10..13 and 15,
   // multi-column joins 14 and 16..19): mixed joins teach no other entry anything
   static constexpr int kMemoInner = 20;      // the inner join
@@ -213,21 +309,25 @@ struct MixPolicy {
   static constexpr int kMemoPairs = 24;      // the outer kinds' pair join
   static const KeyJoinNames& names() { return kNames; }
   static KeyJoinWs& ws(hmj_ctx* c) { return c->mix_ws; }
-  static u64* err_of(hmj_ctx* c, int rel) { return tuple_acc_extra<MixPolicy>(c) + rel * kErrWords; }
+  static u64* err_of(hmj_ctx* c, int rel) { return tuple_acc_extra<Self>(c) + rel * kRelWords; }
   static int keys_begin(hmj_ctx* c) {
-    u64* e = tuple_acc_extra<MixPolicy>(c);
+    u64* e = tuple_acc_extra<Self>(c);
     HIP_TRY(hipMemsetAsync(e, 0, kAccExtra * sizeof(u64), c->stream));
     HIP_TRY(hipMemsetAsync(e, 0xFF, kMaxCols * sizeof(u64), c->stream));
-    HIP_TRY(hipMemsetAsync(e + kErrWords, 0xFF, kMaxCols * sizeof(u64), c->stream));
+    HIP_TRY(hipMemsetAsync(e + kRelWords, 0xFF, kMaxCols * sizeof(u64), c->stream));
     return HMJ_OK;
   }
   // The key kernels' verdict on both relations' string columns: the build relation first, the lowest-numbered column first.
-  static int keys_check(hmj_ctx* c) {
+  static int keys_check(hmj_ctx* c, TupleCall* call) {
     u64 e[kAccExtra];
-    RC_TRY(read_back(c, tuple_acc_extra<MixPolicy>(c), e, sizeof(e)));
+    RC_TRY(read_back(c, tuple_acc_extra<Self>(c), e, sizeof(e)));
+    if (NE) {
+      call->n_build_null = null_rows_of(e + kErrWords);
+      call->n_probe_null = null_rows_of(e + kRelWords + kErrWords);
+    }
     char msg[192];
     for (int rel = 0; rel < 2; rel++) {
-      const u64* r = e + rel * kErrWords;
+      const u64* r = e + rel * kRelWords;
       const char* name = rel ? "probe" : "build";
       for (int k = 0; k < kMaxCols; k++) {
         if (r[k] != kNone) {
@@ -243,21 +343,31 @@ struct MixPolicy {
     }
     return HMJ_OK;
   }
-  static int key(hmj_ctx* c, const MixSide& A, int rel, u64 n, const TupleCall& call, u64* out, bool sum_probe, u64* acc) {
+  static int key(hmj_ctx* c, const Side& A, int rel, u64 n, const TupleCall& call, u64* out, bool sum_probe, u64* acc) {
     if (!n) return HMJ_OK;
-    hipLaunchKernelGGL(mix_key_kernel<false>, dim3((u32)blocks_of(n)), dim3(MK_THREADS), 0, c->stream, A, ColValid{}, n, call.bits, out,
-                       nullptr, 0ull, nullptr, sum_probe ? 1 : 0, acc, err_of(c, rel));
+    if constexpr (NE)
+      hipLaunchKernelGGL((mix_key_kernel<false, true>), dim3((u32)blocks_of(n)), dim3(MK_THREADS), 0, c->stream, A.s, A.v, n, call.bits, out,
+                         nullptr, 0ull, nullptr, sum_probe ? 1 : 0, acc, err_of(c, rel));
+    else
+      hipLaunchKernelGGL(mix_key_kernel<false>, dim3((u32)blocks_of(n)), dim3(MK_THREADS), 0, c->stream, A, ColValid{}, n, call.bits, out,
+                         nullptr, 0ull, nullptr, sum_probe ? 1 : 0, acc, err_of(c, rel));
     HIP_TRY(hipGetLastError());
     return HMJ_OK;
   }
-  static int key_valid(hmj_ctx* c, const MixSide& A, const ColValid& V, int rel, u64 n, const TupleCall& call, u64 nblk, u64* dense, u64* comp,
+  static int key_valid(hmj_ctx* c, const Side& A, const ColValid& V, int rel, u64 n, const TupleCall& call, u64 nblk, u64* dense, u64* comp,
                        u64 cap, const u64* off, bool sum_probe, u64* acc) {
-    hipLaunchKernelGGL(mix_key_kernel<true>, dim3((u32)nblk), dim3(MK_THREADS), 0, c->stream, A, V, n, call.bits, dense, comp, cap, off,
-                       sum_probe ? 1 : 0, acc, err_of(c, rel));
-    HIP_TRY(hipGetLastError());
-    return HMJ_OK;
+    if constexpr (NE) {
+      return fail(c, HMJ_E_HIP, "mixed-key join: the NULL-equals-NULL form compacts no rows");
+    } else {
+      hipLaunchKernelGGL(mix_key_kernel<true>, dim3((u32)nblk), dim3(MK_THREADS), 0, c->stream, A, V, n, call.bits, dense, comp, cap, off,
+                         sum_probe ? 1 : 0, acc, err_of(c, rel));
+      HIP_TRY(hipGetLastError());
+      return HMJ_OK;
+    }
   }
 };
+using MixPolicy = MixPolicyT<false>;
+using MixNePolicy = MixPolicyT<true>;
 
 int check_mixed_rel(hmj_ctx* c, const hmj_mixed_rel* r, const char* name) {
   char msg[160];
@@ -387,8 +497,18 @@ int hmj_join_mixed_device(hmj_ctx* c, const hmj_mixed_rel* build, const hmj_mixe
   call.probe_fill = opts->probe_fill;
   call.build_fill = opts->build_fill;
   const bool inner = opts->side == HMJ_KIND_PROBE_SIDE && opts->kind == HMJ_JOIN_INNER;
-  if (inner) RC_TRY(tuple_join<MixPolicy>(c, RS, build->n, SS, probe->n, flags, &call, out, any_b ? &VB : nullptr, any_p ? &VP : nullptr));
-  else RC_TRY(tuple_join_kind<MixPolicy>(c, RS, build->n, SS, probe->n, flags, &call, out, any_b ? &VB : nullptr, any_p ? &VP : nullptr));
+  // NULL-equals-NULL matching needs a bitmap to differ from the call without the flag, which is what runs when there is none
+  const bool null_equal = (flags & HMJ_NULL_EQUAL) && (any_b || any_p);
+  flags &= ~HMJ_NULL_EQUAL;
+  if (null_equal) {
+    const MixNeSide RN{RS, VB}, SN{SS, VP};  // (a relation without a bitmap: its ColValid holds no pointer)
+    if (inner) RC_TRY(tuple_join<MixNePolicy>(c, RN, build->n, SN, probe->n, flags, &call, out, nullptr, nullptr));
+    else RC_TRY(tuple_join_kind<MixNePolicy>(c, RN, build->n, SN, probe->n, flags, &call, out, nullptr, nullptr));
+  } else if (inner) {
+    RC_TRY(tuple_join<MixPolicy>(c, RS, build->n, SS, probe->n, flags, &call, out, any_b ? &VB : nullptr, any_p ? &VP : nullptr));
+  } else {
+    RC_TRY(tuple_join_kind<MixPolicy>(c, RS, build->n, SS, probe->n, flags, &call, out, any_b ? &VB : nullptr, any_p ? &VP : nullptr));
+  }
   // the out fields go to a full-size copy first; the caller gets the prefix its struct_size holds
   hmj_mixed_opts o;
   std::memset(&o, 0, sizeof(o));

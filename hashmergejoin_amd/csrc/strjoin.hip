@@ -631,6 +631,8 @@ int hmj_join_kind_str_device(hmj_ctx* c, const hmj_str_rel* build, const hmj_str
     return fail(c, HMJ_E_ARG, "unknown join kind");
   if (opts->hash_bits > 63) return fail(c, HMJ_E_ARG, "hash_bits > 63");
   if (flags & HMJ_FIRST_WINS) return fail(c, HMJ_E_ARG, "HMJ_FIRST_WINS is not defined for string joins");
+  if (flags & HMJ_NULL_EQUAL)
+    return fail(c, HMJ_E_ARG, "HMJ_NULL_EQUAL is not taken by the string kinds: call hmj_join_mixed_device with one string column");
   RC_TRY(check_str_rel(c, build, "build"));
   RC_TRY(check_str_rel(c, probe, "probe"));
   StrValid VB, VP;

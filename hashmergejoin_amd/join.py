@@ -392,7 +392,9 @@ class Executor:
         """Semi / anti / outer joins of two device relations on a key of several fixed-width columns
         (hmj_join_kind_cols_device).  side / kind as for `join_kind_str_device`: HMJ_KIND_PROBE_SIDE with HMJ_JOIN_*, or
         HMJ_KIND_BUILD_SIDE with HMJ_BUILD_* / HMJ_FULL_OUTER; relations and *_valid as for `join_cols_device` (a NULL-key
-        row has no partner: ANTI and the outer kinds of its side emit it with key64 0).  Returns (ColsResult,
+        row has no partner: ANTI and the outer kinds of its side emit it with key64 0).  flags | HMJ_NULL_EQUAL with a bitmap
+        on either side: NULL slots match NULL slots of the same column, a row with NULL slots is an ordinary row of every
+        kind, the key is hashed and `cols_key64(..., valid=, null_equal=True)` reproduces it.  Returns (ColsResult,
         {"n_probe_matched", "n_probe_unmatched", "n_build_matched", "n_build_unmatched", "form", "n_key_pairs",
         "n_collisions", "n_build_null", "n_probe_null", "ms_key", "ms_join", "ms_verify", "ms_emit", "ms_order"}); read
         the rows with `cols_kind_rows_to_numpy`."""
@@ -500,7 +502,9 @@ class Executor:
         (`pack_strings`; compared byte for byte); *_vals: an int64 tensor [n], or None (the payload of row i is i).  side /
         kind as for `join_kind_cols_device`, HMJ_KIND_PROBE_SIDE + HMJ_JOIN_INNER included.  *_valid: None, or a list with
         one entry per key column -- None, a uint8 device tensor holding the column's Arrow validity bitmap
-        (`pack_validity`), or (tensor, bit_offset); a row with a NULL in any key column has no partner.  Returns (ColsResult,
+        (`pack_validity`), or (tensor, bit_offset); a row with a NULL in any key column has no partner -- unless flags holds
+        HMJ_NULL_EQUAL: then NULL slots match NULL slots of the same column (a NULL string is not the empty string) and
+        `mixed_key64(..., valid=, null_equal=True)` reproduces key64.  Returns (ColsResult,
         {"n_probe_matched", "n_probe_unmatched", "n_build_matched", "n_build_unmatched", "n_key_pairs", "n_collisions",
         "n_build_null", "n_probe_null", "ms_key", "ms_join", "ms_verify", "ms_emit", "ms_order"}); read the rows with
         `mixed_rows_to_numpy`, reproduce key64 with `mixed_key64`."""
@@ -974,11 +978,45 @@ def _mix64(x):
     return x ^ (x >> np.uint64(31))
 
 
-def cols_key64(columns, widths, hash_bits=0, force_hashed=False):
+def _null_masks(valid, k, n):
+    """`valid` of cols_key64 / mixed_key64 -> one bool array [n] per column, True = NULL."""
+    if valid is None:
+        return [np.zeros(n, bool) for _ in range(k)]
+    valid = list(valid)
+    if len(valid) != k:
+        raise ValueError("valid: one entry per key column")
+    out = []
+    for v in valid:
+        m = np.zeros(n, bool) if v is None else ~np.asarray(v, bool).ravel()
+        if len(m) != n:
+            raise ValueError("valid: one entry per row")
+        out.append(m)
+    return out
+
+
+def _null_equal_chain(vs, nulls, hash_bits):
+    """key64 under HMJ_NULL_EQUAL: the hash chain with v_c = 0 under a NULL slot, then -- rows with a NULL slot only -- one
+    more step over m = the sum of 2^c over the row's NULL columns."""
+    n = len(vs[0])
+    h = np.full(n, len(vs), np.uint64)
+    m = np.zeros(n, np.uint64)
+    with np.errstate(over="ignore"):
+        for c, (v, nl) in enumerate(zip(vs, nulls)):
+            h = _mix64(h + np.where(nl, np.uint64(0), v) + np.uint64(0x9E3779B97F4A7C15))
+            m = m | np.where(nl, np.uint64(1 << c), np.uint64(0))
+        h = np.where(m != 0, _mix64(h + m + np.uint64(0x9E3779B97F4A7C15)), h)
+    return h >> np.uint64(64 - int(hash_bits)) if hash_bits else h
+
+
+def cols_key64(columns, widths, hash_bits=0, force_hashed=False, valid=None, null_equal=False):
     """The 64-bit join key hmj_join_cols_device gives every row (include/hmj.h), restated on the host: uint64 array [n].
     columns: one numpy array per key column (any dtype of widths[c] bytes, or integers that fit it); widths: bytes per
     column (1, 2, 4 or 8).  Packed form (widths sum to <= 8, not force_hashed): the columns concatenated, column 0 most
-    significant.  Hashed form: h = k; h = mix64(h + v_c + 0x9E3779B97F4A7C15) per column; hash_bits 1..63 keeps the top bits."""
+    significant.  Hashed form: h = k; h = mix64(h + v_c + 0x9E3779B97F4A7C15) per column; hash_bits 1..63 keeps the top bits.
+    null_equal=True: the key of a HMJ_NULL_EQUAL call that passes a bitmap -- always the hashed form; valid: None, or one
+    entry per column, None or n bools (True = valid); a NULL slot has v_c = 0 whatever lies under it, and a row with NULL
+    slots takes one more step h = mix64(h + m + 0x9E3779B97F4A7C15), m = the sum of 2^c over its NULL columns.  Without
+    null_equal, valid is not read (a NULL-key row of a SQL-semantics call has key64 0 where it is emitted)."""
     widths = [int(w) for w in widths]
     if len(columns) != len(widths) or not 1 <= len(widths) <= _lib.HMJ_MAX_KEY_COLS:
         raise ValueError("1..%d columns, one width each" % _lib.HMJ_MAX_KEY_COLS)
@@ -993,6 +1031,8 @@ def cols_key64(columns, widths, hash_bits=0, force_hashed=False):
             a = a.view("u%d" % w)  # signed integers and floats: their bytes
         vs.append(a.astype(np.uint64) & np.uint64((1 << (8 * w)) - 1))
     n = len(vs[0])
+    if null_equal:
+        return _null_equal_chain(vs, _null_masks(valid, len(vs), n), hash_bits)
     if sum(widths) <= 8 and not force_hashed:
         key = np.zeros(n, np.uint64)
         for v, w in zip(vs, widths):
@@ -1019,11 +1059,13 @@ def _hash_bytes(b):
     return h ^ (h >> 47)
 
 
-def mixed_key64(columns, hash_bits=0):
+def mixed_key64(columns, hash_bits=0, valid=None, null_equal=False):
     """The 64-bit join key hmj_join_mixed_device gives every row (include/hmj.h), restated on the host: uint64 array [n].
     columns: one entry per key column -- a numpy integer array (a fixed-width column: its values zero-extended from the
     dtype's width) or a list of `bytes` (a string column: libstdc++'s _Hash_bytes of every slot, all 64 bits).
-    h = k; h = mix64(h + v_c + 0x9E3779B97F4A7C15) per column; hash_bits 1..63 keeps the top bits."""
+    h = k; h = mix64(h + v_c + 0x9E3779B97F4A7C15) per column; hash_bits 1..63 keeps the top bits.  valid / null_equal as
+    for `cols_key64`: under HMJ_NULL_EQUAL a NULL slot has v_c = 0 (a NULL string slot may hold None), and a row with NULL
+    slots takes the extra step over its NULL columns' mask."""
     if not 1 <= len(columns) <= _lib.HMJ_MAX_KEY_COLS:
         raise ValueError("1..%d columns" % _lib.HMJ_MAX_KEY_COLS)
     if not 0 <= int(hash_bits) <= 63:
@@ -1036,9 +1078,11 @@ def mixed_key64(columns, hash_bits=0):
                 raise ValueError("a fixed-width column has 1, 2, 4 or 8 bytes per value")
             vs.append(a.view("u%d" % a.dtype.itemsize).astype(np.uint64))
         else:
-            vs.append(np.array([_hash_bytes(bytes(b)) for b in col], np.uint64))
+            vs.append(np.array([0 if b is None else _hash_bytes(bytes(b)) for b in col], np.uint64))
     if any(len(v) != len(vs[0]) for v in vs):
         raise ValueError("columns must have one length")
+    if null_equal:
+        return _null_equal_chain(vs, _null_masks(valid, len(vs), len(vs[0])), hash_bits)
     h = np.full(len(vs[0]), len(vs), np.uint64)
     with np.errstate(over="ignore"):
         for v in vs:

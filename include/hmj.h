@@ -58,6 +58,9 @@ typedef struct hmj_ctx hmj_ctx;
 #define HMJ_CHECKSUM 0x08u    /* also fill xor_fold / mix_sum (parity checks)                     */
 #define HMJ_SUM_PROBE 0x10u   /* also fill sum_probe_all (the 'miss inserts 0' sum of             */
                               /* hashjoin_bench.cc:92-96 is sum_probe_all + sum_r w/ FIRST_WINS)  */
+#define HMJ_NULL_EQUAL 0x20u  /* NULL key slots compare equal to NULL slots of the same column     */
+                              /* (IS NOT DISTINCT FROM): hmj_join_kind_cols_device and            */
+                              /* hmj_join_mixed_device, see "NULL-equals-NULL matching" below     */
 
 typedef struct {
   uint64_t n_matches;
@@ -564,8 +567,10 @@ int hmj_join_str_device(hmj_ctx* ctx, const hmj_str_rel* build, const hmj_str_re
  * the {hash, row} rows of the valid rows only, compacted stably in row order (the u64 joins take those), and for the kinds
  * a dense row-indexed array with {0, HMJ_STR_NO_ROW} for a NULL-key row, which the sweeps walk.  Row indices in the result
  * stay the caller's.
- * Out of scope for NULL keys: NULL-equals-NULL matching (IS NOT DISTINCT FROM), validity of the payload column,
- * 32-bit-offset Arrow `string` columns, the exchange path, bitmaps on hmj_join_str_device itself (use the INNER kind).  */
+ * NULL-equals-NULL matching (HMJ_NULL_EQUAL, IS NOT DISTINCT FROM) is not taken here: the flag is HMJ_E_ARG, and the message
+ * points to hmj_join_mixed_device, which honours it and takes a single string column -- nobody gets SQL semantics silently.
+ * Out of scope for NULL keys: validity of the payload column, 32-bit-offset Arrow `string` columns, the exchange path,
+ * bitmaps on hmj_join_str_device itself (use the INNER kind).                                                           */
 #define HMJ_STR_NO_ROW UINT64_MAX /* r_row / s_row of an outer join's unmatched row: there is no partner             */
 typedef struct {
   const void* bits;     /* device: Arrow validity bitmap, least-significant bit first: row i is valid iff
@@ -741,9 +746,33 @@ int hmj_join_cols_device(hmj_ctx* ctx, const hmj_cols_rel* build, const hmj_cols
  * How: a pass over the bitmaps alone counts the valid rows per workgroup (valid_count_kernel), one scan places the
  * workgroups, and cols_key_valid_kernel writes the {key64,row} rows of the valid rows only, compacted stably in row order;
  * the u64 joins take those.  Row indices in the result stay the caller's.
- * Out of scope for NULL keys: NULL-equals-NULL matching (IS NOT DISTINCT FROM), validity of the payload column, the
- * exchange path, bitmaps in hmj_cols_join_opts (use the INNER kind here).  String keys' validity is not part of this entry:
- * hmj_join_kind_str_device takes it, with these semantics.                                                              */
+ * NULL-equals-NULL matching (flags | HMJ_NULL_EQUAL; IS NOT DISTINCT FROM, cuDF's null_equality::EQUAL, pandas' merge,
+ * Spark's <=>): the NULL-key table above is replaced by one rule.
+ *   Match rule: two rows match when, in every key column, both slots are NULL, or both are valid and equal (bit for bit,
+ *   as without the flag).  A NULL slot equals no value: (NULL, 5) does not equal (0, 5), and (NULL, x) does not equal
+ *   (x, NULL).  The bytes under a NULL slot stay undefined and nothing depends on them.
+ *   key64: 1. h = k.  2. for c in 0..k-1: h = mix64(h + v_c + 0x9E3779B97F4A7C15), with v_c = 0 for a NULL slot and the
+ *   hashed form's v_c otherwise.  3. m = the sum of 2^c over the row's NULL columns; if m != 0: h = mix64(h + m +
+ *   0x9E3779B97F4A7C15).  4. key64 = hash_bits ? h >> (64 - hash_bits) : h.  A row without NULLs has exactly the hashed
+ *   form's key64.
+ *   Form: with the flag and at least one bitmap actually passed on either side (an entry with bits != NULL), the call takes
+ *   the hashed form, opts->form says so and force_hashed changes nothing.  With the flag and no bitmap the call IS the call
+ *   without the flag: the packed form stays available and exactly the same kernels are launched.
+ *   Kinds: a row with NULL slots is an ordinary row for all eight (side, kind) pairs -- matched, marked, emitted and counted
+ *   in n_*_matched / n_*_unmatched like any other; emitted unmatched, its key64 is its own key64, not 0.  A relation whose
+ *   rows are all NULL is not an empty side: its rows match the other side's rows with the same NULL columns.
+ *   n_build_null / n_probe_null still report the rows with at least one NULL key column (informational; every kind).
+ *   n_key_pairs / n_collisions count these rows' pairs as they count any others.
+ *   HMJ_ORDERED: rows ascending by (key64, the tuple column by column, r_row, s_row), HMJ_COLS_NO_ROW last; in each column
+ *   a NULL slot sorts after every valid value (NULLS LAST) and two NULL slots tie.  There is no tail segment, and the
+ *   1024-row and 2^22 limits count all rows.
+ *   How: cols_key_ne_kernel, one lane per row, reads a column's 64 validity bits per wave as one or two aligned 8-byte
+ *   words, substitutes v_c = 0, mixes m in and writes one dense {key64, row} row per row -- no count pass, no scan, no
+ *   compaction; the rest is the hashed form's sequence on a key policy that compares validity before values.
+ *   Without the flag every call behaves and launches exactly as before.  hmj_join_cols_device (no bitmaps) ignores it.
+ * Out of scope for NULL keys: validity of the payload column, the exchange path, bitmaps in hmj_cols_join_opts (use the
+ * INNER kind here).  String keys' validity is not part of this entry: hmj_join_kind_str_device takes it under SQL
+ * semantics, hmj_join_mixed_device under either.                                                                        */
 #define HMJ_COLS_NO_ROW UINT64_MAX /* r_row / s_row of an outer join's unmatched row: there is no partner            */
 typedef struct {
   uint32_t struct_size;   /* in: sizeof(hmj_cols_kind_opts) of the caller's header                                     */
@@ -807,8 +836,16 @@ int hmj_join_kind_cols_device(hmj_ctx* ctx, const hmj_cols_rel* build, const hmj
  * once -- a fixed column is one coalesced load per wave; for a string column the wave stages its 64 keys' byte span in
  * LDS as the string join's hash kernel does -- and writes one {key64, row} row; the rest is the column join's sequence on
  * a key policy that compares fixed columns first, then string lengths, then bytes.
- * Out of scope: 32-bit-offset `string` columns, the exchange (multi-GPU) path, host-resident columns, NULL-equals-NULL
- * matching (IS NOT DISTINCT FROM), collated or signed ordering, a packed form for mixed keys.                          */
+ * NULL-equals-NULL matching (flags | HMJ_NULL_EQUAL): as written for hmj_join_kind_cols_device -- match rule, key64 (v_c =
+ * 0 for a NULL slot of either type, then the mask step), kinds, counters, NULLS LAST order without a tail -- with the
+ * bitmaps in hmj_mixed_col.validity; a call that passes the flag and no bitmap is the call without the flag.  A NULL
+ * string slot does not equal the valid empty string (whose v_c is _Hash_bytes of no bytes, not 0).  The bytes and the
+ * length under a NULL slot stay undefined and are neither hashed nor compared, but its offsets must still be
+ * non-decreasing; the decreasing-offsets and `data == NULL but keys have bytes` checks behave as without the flag.  A
+ * string-only column set is legal, so this is also the NULL-equals-NULL string join (hmj_join_kind_str_device refuses
+ * the flag).  mix_key_kernel's NULL-equals-NULL variant reads the validity words per wave and column as the column join's.
+ * Out of scope: 32-bit-offset `string` columns, the exchange (multi-GPU) path, host-resident columns, collated or signed
+ * ordering, a packed form for mixed keys.                                                                              */
 #define HMJ_KEY_FIXED 0u
 #define HMJ_KEY_LARGE_STRING 1u
 typedef struct {

@@ -22,7 +22,14 @@
   feature itself costs -- a pass over the bitmaps, a scan, a read-back and the compacted {key64,row} rows) and nulls_ms (FRAC
   of the rows of each side NULL in column 1).
 
-    python tools/bench_join_cols.py [--reps 20] [--warmup 3] [--log2 24 26] [--kinds] [--nulls FRAC]
+  --null-equal: NULL-equals-NULL matching (HMJ_NULL_EQUAL) instead.  Same shapes and sizes, the --kinds relations with 10 %
+  of the slots of one column NULL on each side -- column 0 of [4,4] and column 1 of [8,4,2]: the other columns keep the
+  tuples distinct, so NULL slots add matches (the same id NULL on both sides) without piling rows up on one tuple.  In one process and on the same rows the inner count join -- with --kinds also
+  probe SEMI, probe ANTI and FULL_OUTER in count mode -- runs once under SQL semantics (sql_ms: the call without the flag,
+  the yardstick) and once under the flag (null_equal_ms); ms_key and ms_verify of both from separate calls with profiling
+  on.  Under SQL semantics [4,4] keeps its packed form; under the flag every call with a bitmap is hashed.  No gate.
+
+    python tools/bench_join_cols.py [--reps 20] [--warmup 3] [--log2 24 26] [--kinds] [--nulls FRAC] [--null-equal]
 """
 import argparse
 import json
@@ -140,6 +147,44 @@ def bench_nulls(torch, H, ex, args, dev, out):
             torch.cuda.empty_cache()
 
 
+def bench_null_equal(torch, H, ex, args, dev, out, frac=0.1):
+    calls = [("inner", H.HMJ_KIND_PROBE_SIDE, H.HMJ_JOIN_INNER)]
+    if args.kinds:
+        calls += [("semi", H.HMJ_KIND_PROBE_SIDE, H.HMJ_JOIN_SEMI), ("anti", H.HMJ_KIND_PROBE_SIDE, H.HMJ_JOIN_ANTI),
+                  ("full_outer", H.HMJ_KIND_BUILD_SIDE, H.HMJ_FULL_OUTER)]
+    out["null_slots_frac"] = frac
+    for lg in args.log2:
+        n = 1 << lg
+        for name, widths in SHAPES:
+            bc, pc = make_columns(n, widths, lg, miss_half=True)
+            B, P = [dev(c) for c in bc], [dev(c) for c in pc]
+            del bc, pc
+            rng = np.random.default_rng(lg + 2)
+            mb, mp = rng.random(n) >= frac, rng.random(n) >= frac
+            col = 0 if len(widths) == 2 else 1
+            on_col = lambda m: [H.pack_validity(m, 0, "cuda") if c == col else None for c in range(len(widths))]
+            vb, vp = on_col(mb), on_col(mp)
+            for cname, side, kind in calls:
+                row = {}
+                for vname, flag in (("sql", 0), ("null_equal", H.HMJ_NULL_EQUAL)):
+                    fn = lambda: ex.join_kind_cols_device(B, None, P, None, side, kind, flag, build_valid=vb, probe_valid=vp)
+                    ex.set_profiling(False)
+                    ms, (res, inf) = timed(torch, fn, args.reps, args.warmup)
+                    assert (inf["n_build_null"], inf["n_probe_null"]) == (int((~mb).sum()), int((~mp).sum()))
+                    ex.set_profiling(True)
+                    ph = [fn()[1] for _ in range(max(5, args.reps // 2))]
+                    ex.set_profiling(False)
+                    row[vname + "_ms"] = round(ms, 4)
+                    row[vname] = {"form": "packed" if inf["form"] == H.HMJ_COLS_PACKED else "hashed", "n_matches": int(res.n_matches),
+                                  "ms_key": round(statistics.median(p["ms_key"] for p in ph), 4),
+                                  "ms_verify": round(statistics.median(p["ms_verify"] for p in ph), 4)}
+                row["null_equal_vs_sql"] = round(row["null_equal_ms"] / row["sql_ms"], 3)
+                out["null_equal_%s_%s_2^%d_count" % (cname, name, lg)] = row
+            del B, P, vb, vp
+            ex.release_result()
+            torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -148,6 +193,8 @@ def main():
     ap.add_argument("--kinds", action="store_true", help="time probe SEMI / ANTI / FULL_OUTER beside the inner count join")
     ap.add_argument("--nulls", type=float, default=None, metavar="FRAC",
                     help="time the plain call, the call with all-valid bitmaps and the call with FRAC of the rows NULL-keyed")
+    ap.add_argument("--null-equal", action="store_true",
+                    help="time each call under SQL semantics and under HMJ_NULL_EQUAL on the same rows with 10 %% NULL slots")
     args = ap.parse_args()
     import torch
 
@@ -160,6 +207,11 @@ def main():
     def dev(a):
         return torch.from_numpy(np.ascontiguousarray(a).view("i%d" % a.dtype.itemsize)).cuda()
 
+    if args.null_equal:
+        bench_null_equal(torch, H, ex, args, dev, out)
+        ex.close()
+        print(json.dumps(out))
+        return
     if args.nulls is not None:
         bench_nulls(torch, H, ex, args, dev, out)
         ex.close()

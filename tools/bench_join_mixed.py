@@ -19,7 +19,12 @@
   yardstick    ms_hash of the string join + ms_key of the column join in this same run: together they read what the mixed
                key kernel reads (the column join 8 bytes a row more: its id column) and write the rows twice
 
-    python tools/bench_join_mixed.py [--reps 20] [--warmup 3] [--sizes 2^24 10^6]
+  --null-equal: NULL-equals-NULL matching (HMJ_NULL_EQUAL) instead.  The same relations with 10 % of the int32 column's
+  slots NULL on each side (the strings keep the tuples distinct); per size and kind the call runs once under SQL semantics (sql_ms: the call without the flag, the
+  yardstick) and once under the flag (null_equal_ms) in this one process, with ms_key and ms_verify of both from separate
+  calls with profiling on.  No gate.
+
+    python tools/bench_join_mixed.py [--reps 20] [--warmup 3] [--sizes 2^24 10^6] [--null-equal]
 """
 import argparse
 import json
@@ -71,11 +76,44 @@ def relations(torch, H, size):
     return out
 
 
+def bench_null_equal(torch, H, ex, args, kinds, out, frac=0.1):
+    out["null_slots_frac"] = frac
+    for size in args.sizes:
+        (bc, bo, bday, bid), (pc, po, pday, pid) = relations(torch, H, size)
+        nb, np_ = bday.shape[0], pday.shape[0]
+        rng = np.random.default_rng(7)
+        mb, mp = rng.random(nb) >= frac, rng.random(np_) >= frac
+        vb, vp = [None, H.pack_validity(mb, 0, "cuda")], [None, H.pack_validity(mp, 0, "cuda")]
+        rec = {"n_build": nb, "n_probe": np_}
+        for name, side, kind, flags in kinds:
+            row = {}
+            for vname, flag in (("sql", 0), ("null_equal", H.HMJ_NULL_EQUAL)):
+                fn = lambda: ex.join_mixed_device([(bc, bo), bday], None, [(pc, po), pday], None, side, kind, flags | flag, build_valid=vb,
+                                                  probe_valid=vp)
+                ex.set_profiling(False)
+                ms, (res, inf) = timed(torch, fn, args.reps, args.warmup)
+                assert (inf["n_build_null"], inf["n_probe_null"]) == (int((~mb).sum()), int((~mp).sum()))
+                ex.set_profiling(True)
+                ph = [fn()[1] for _ in range(max(5, args.reps // 2))]
+                ex.set_profiling(False)
+                row[vname + "_ms"] = round(ms, 4)
+                row[vname] = {"n_matches": int(res.n_matches), "ms_key": round(statistics.median(p["ms_key"] for p in ph), 4),
+                              "ms_verify": round(statistics.median(p["ms_verify"] for p in ph), 4)}
+            row["null_equal_vs_sql"] = round(row["null_equal_ms"] / row["sql_ms"], 3)
+            rec[name] = row
+        out[size] = rec
+        del bc, bo, bday, bid, pc, po, pday, pid, vb, vp
+        ex.release_result()
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--sizes", nargs="+", default=["2^24", "10^6"], choices=["2^24", "10^6"])
+    ap.add_argument("--null-equal", action="store_true",
+                    help="time each call under SQL semantics and under HMJ_NULL_EQUAL on the same rows with 10 %% NULL int32 slots")
     args = ap.parse_args()
     import torch
 
@@ -86,6 +124,11 @@ def main():
     P, B = H.HMJ_KIND_PROBE_SIDE, H.HMJ_KIND_BUILD_SIDE
     kinds = (("inner_count", P, H.HMJ_JOIN_INNER, 0), ("inner_ordered", P, H.HMJ_JOIN_INNER, H.HMJ_ORDERED),
              ("semi", P, H.HMJ_JOIN_SEMI, 0), ("full_outer", B, H.HMJ_FULL_OUTER, 0))
+    if args.null_equal:
+        bench_null_equal(torch, H, ex, args, kinds, out)
+        ex.close()
+        print(json.dumps(out))
+        return
     for size in args.sizes:
         (bc, bo, bday, bid), (pc, po, pday, pid) = relations(torch, H, size)
         nb, np_ = bday.shape[0], pday.shape[0]
