@@ -210,6 +210,27 @@ class MixedOpts(C.Structure):
                 ("ms_join", C.c_float), ("ms_verify", C.c_float), ("ms_emit", C.c_float), ("ms_order", C.c_float)]
 
 
+# hmj_group_cols_device: rows grouped by multi-column keys; hmj_group_opts.want
+HMJ_GROUP_COUNT, HMJ_GROUP_SUM, HMJ_GROUP_MIN, HMJ_GROUP_MAX, HMJ_GROUP_ROW_MAP = 0x01, 0x02, 0x04, 0x08, 0x10
+
+
+class GroupOpts(C.Structure):
+    """hmj_group_opts: the columns wanted, hash bits, the forced hashed form and the key columns' validity bitmaps (in); the
+    form taken, the rows with a NULL key slot, the heads inside runs of equal key64 and phase times (out)."""
+    _fields_ = [("struct_size", C.c_uint32), ("want", C.c_uint32), ("hash_bits", C.c_uint32), ("force_hashed", C.c_uint32),
+                ("form", C.c_uint32), ("reserved", C.c_uint32), ("validity", C.POINTER(Validity)), ("n_null", C.c_uint64),
+                ("n_collisions", C.c_uint64), ("ms_key", C.c_float), ("ms_sort", C.c_float), ("ms_groups", C.c_float),
+                ("ms_agg", C.c_float)]
+
+
+class GroupResult(C.Structure):
+    """hmj_group_result: groups, rows and the largest group's rows; device columns with HMJ_MATERIALIZE (NULL when not
+    asked for)."""
+    _fields_ = [("n_groups", C.c_uint64), ("n_rows", C.c_uint64), ("max_count", C.c_uint64), ("key64", C.c_void_p),
+                ("first_row", C.c_void_p), ("count", C.c_void_p), ("sum", C.c_void_p), ("min", C.c_void_p), ("max", C.c_void_p),
+                ("group_of_row", C.c_void_p)]
+
+
 # hmj_take_cols_device: fixed-width columns taken through a row map (a join's r_row / s_row)
 HMJ_TAKE_NO_ROW = 0xFFFFFFFFFFFFFFFF
 HMJ_MAX_TAKE_COLS = 64
@@ -409,6 +430,8 @@ def load_library():
     L.hmj_join_mixed_device.restype = i
     L.hmj_join_mixed_device.argtypes = [vp, C.POINTER(MixedRel), C.POINTER(MixedRel), C.c_uint32, C.POINTER(MixedOpts),
                                         C.POINTER(ColsResult)]
+    L.hmj_group_cols_device.restype = i
+    L.hmj_group_cols_device.argtypes = [vp, C.POINTER(ColsRel), C.c_uint32, C.POINTER(GroupOpts), C.POINTER(GroupResult)]
     L.hmj_take_cols_device.restype = i
     L.hmj_take_cols_device.argtypes = [vp, C.POINTER(TakeSrc), C.c_uint32, u, vp, u, C.POINTER(TakeDst), C.POINTER(TakeOpts)]
     L.hmj_take_str_device.restype = i

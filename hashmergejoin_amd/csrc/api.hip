@@ -3128,6 +3128,9 @@ void hmj_destroy(hmj_ctx* c) {
     for (auto& e : ws->ev)
       if (e) (void)hipEventDestroy(e);
   }
+  c->grp_ws.each_buf(free_dev);
+  for (auto& e : c->grp_ws.ev)
+    if (e) (void)hipEventDestroy(e);
   HostBuf* hosts[] = {&c->h_accum, &c->h_key, &c->h_rval, &c->h_sval};
   for (HostBuf* b : hosts) free_host(*b);
   for (auto& e : c->events)
@@ -3603,6 +3606,7 @@ void hmj_release_result(hmj_ctx* c) {
   c->str_ws.each_result_buf(free_dev);
   c->col_ws.each_result_buf(free_dev);
   c->mix_ws.each_result_buf(free_dev);
+  c->grp_ws.each_result_buf(free_dev);
   free_host(c->h_key);
   free_host(c->h_rval);
   free_host(c->h_sval);

@@ -49,6 +49,25 @@ struct KeyJoinWs {
   }
 };
 
+// Workspace of hmj_group_cols_device (coljoin.hip, hmj_group.h): no other entry reuses or regrows its buffers.
+struct GroupWs {
+  DevBuf rows, sorted,        // {key64, row} rows as keyed, and sorted by key64 (hashed: runs with several tuples by tuple too)
+      flags, blk, blk_off,    // head ballots (one word per wave), heads per workgroup and their offsets
+      list, runs, acc,        // the collision search's rows and runs, the counters
+      start,                  // first sorted position of every group, and n behind the last
+      key, first, count, sum, min, max, gmap;  // the result columns
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // phase boundaries (profiling)
+  template <class F>
+  void each_result_buf(F f) {
+    for (DevBuf* b : {&key, &first, &count, &sum, &min, &max, &gmap}) f(*b);
+  }
+  template <class F>
+  void each_buf(F f) {
+    for (DevBuf* b : {&rows, &sorted, &flags, &blk, &blk_off, &list, &runs, &acc, &start}) f(*b);
+    each_result_buf(f);
+  }
+};
+
 enum Kind {
   K_TOTAL = 0, K_H2D, K_D2H, K_HIST, K_SCAN, K_SCATTER, K_OFFSETS, K_PROBE_COUNT, K_OUT_SCAN,
   K_PROBE_WRITE, K_ORDER, K_NKINDS
@@ -139,6 +158,7 @@ struct hmj_ctx {
   // string joins (strjoin.hip), multi-column joins (coljoin.hip) and mixed-key joins (mixjoin.hip): one workspace each, so
   // that no call reuses or regrows another's buffers
   hmj_host::KeyJoinWs str_ws, col_ws, mix_ws;
+  hmj_host::GroupWs grp_ws;  // hmj_group_cols_device
   hipEvent_t take_ev[2] = {nullptr, nullptr};  // hmj_take_cols_device: around its launches (profiling)
   hipEvent_t takestr_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // hmj_take_str_device: around its offsets and its bytes phase
   int memo_kind = 0;  // workload-signature kind of plain inner joins run on behalf of another entry (string, multi-column joins and their kinds)

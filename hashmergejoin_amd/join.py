@@ -443,6 +443,48 @@ class Executor:
             out[:, c] = tmp.cpu().numpy().view(np.uint64)
         return out
 
+    # ---- grouping rows by multi-column keys (hmj_group_cols_device) ----------------------------------------
+    def group_cols_device(self, cols, vals=None, valid=None, flags=0, want=_lib.HMJ_GROUP_COUNT, hash_bits=0, force_hashed=False):
+        """Group the rows of one device relation by a key of several fixed-width columns (hmj_group_cols_device): GROUP BY /
+        DISTINCT with NULLs of a column forming one group.  cols, vals and valid as `join_cols_device` takes one side's.
+        flags: 0 (counts only: n_groups, max_count), HMJ_MATERIALIZE (key64 and first_row, + what `want` asks for) or
+        HMJ_ORDERED (groups ascending by key64, then tuple, NULLS LAST).  want: HMJ_GROUP_* bits.  Returns (GroupResult,
+        {"form", "n_null", "n_collisions", "ms_key", "ms_sort", "ms_groups", "ms_agg"}); read the columns with
+        `group_rows_to_numpy`, reproduce them with `expected_groups`."""
+        self._sync_stream()
+        rel, keep = self._cols_rel(cols, vals)
+        opts = _lib.GroupOpts()
+        opts.struct_size = C.sizeof(_lib.GroupOpts)
+        opts.want = int(want)
+        opts.hash_bits = int(hash_bits)
+        opts.force_hashed = 1 if force_hashed else 0
+        v, keep_v = self._validity(valid, rel, "valid")
+        if v is not None:
+            opts.validity = v
+        res = _lib.GroupResult()
+        self._check(self.L.hmj_group_cols_device(self.h, C.byref(rel), flags, C.byref(opts), C.byref(res)))
+        del keep, keep_v
+        info = {"form": int(opts.form), "n_null": int(opts.n_null), "n_collisions": int(opts.n_collisions)}
+        for k in ("ms_key", "ms_sort", "ms_groups", "ms_agg"):
+            info[k] = float(getattr(opts, k))
+        return res, info
+
+    def group_rows_to_numpy(self, res):
+        """Copy a grouping's device result out: {"key64", "first_row", "count", "sum", "min", "max", "group_of_row"} -> a
+        uint64 array (n_groups entries; group_of_row: n_rows), or None for a column the call did not produce."""
+        torch = self._torch
+        out = {}
+        for name in ("key64", "first_row", "count", "sum", "min", "max", "group_of_row"):
+            ptr = getattr(res, name)
+            n = int(res.n_rows if name == "group_of_row" else res.n_groups)
+            if not ptr:
+                out[name] = None
+                continue
+            tmp = torch.empty(n, dtype=torch.int64, device="cuda:%d" % self.device)
+            _memcpy_d2d(torch, tmp, ptr, n * 8)
+            out[name] = tmp.cpu().numpy().view(np.uint64)
+        return out
+
     # ---- mixed keys: string and fixed-width columns in one tuple (hmj_join_mixed_device) ------------------
     def _mixed_rel(self, cols, vals, valid, name):
         """Key columns -- a 1-D contiguous device tensor (fixed-width) or a (chars uint8, offsets int64 [n + 1]) pair (an Arrow
@@ -1042,6 +1084,80 @@ def cols_key64(columns, widths, hash_bits=0, force_hashed=False, valid=None, nul
     for v in vs:
         h = _mix64(h + v + np.uint64(0x9E3779B97F4A7C15))
     return h >> np.uint64(64 - int(hash_bits)) if hash_bits else h
+
+
+def expected_groups(columns, widths, vals=None, valid=None, hash_bits=0, force_hashed=False, ordered=False):
+    """What hmj_group_cols_device returns (include/hmj.h), restated on the host in plain numpy.  columns / widths as
+    `cols_key64`; vals: n integers (taken mod 2^64) or None (the payload of row i is i); valid: None, or one entry per
+    column, None or n bools (True = valid) -- an entry that is not None is a bitmap passed, which makes the form hashed
+    even when every bit is set.  Two rows are one group when in every column both slots are NULL or both are valid and
+    equal; what lies under a NULL slot is not read.  Returns a dict: "form", "n_groups", "n_rows", "max_count", "n_null",
+    "n_collisions" (groups minus distinct key64), "max_mixed_run" (rows of the largest run of equal key64 that holds
+    several tuples: the call is HMJ_E_UNSUPPORTED beyond 1024), the uint64 group columns "key64", "first_row", "count",
+    "sum", "min", "max", and "group_of_row" [n].  ordered: groups ascending by (key64, the tuple column by column as
+    unsigned integers, NULLS LAST per column) as HMJ_ORDERED gives them; else ascending by first_row, the order in which
+    an unordered result is compared."""
+    widths = [int(w) for w in widths]
+    k = len(widths)
+    n = len(np.ascontiguousarray(columns[0])) if k else 0
+    bitmap = valid is not None and any(v is not None for v in valid)
+    nulls = _null_masks(valid, k, n)
+    hashed = bitmap or sum(widths) > 8 or bool(force_hashed)
+    if bitmap:
+        key64 = cols_key64(columns, widths, hash_bits, valid=valid, null_equal=True)
+    else:
+        key64 = cols_key64(columns, widths, hash_bits, force_hashed)
+    # the tuple as the order and the grouping rule see it: per column (is NULL, value or 0 under a NULL slot)
+    canon = np.zeros((n, 2 * k), np.uint64)
+    for c, (col, w) in enumerate(zip(columns, widths)):
+        a = np.ascontiguousarray(col)
+        if a.dtype.itemsize == w and a.dtype.kind != "u":
+            a = a.view("u%d" % w)
+        v = a.astype(np.uint64) & np.uint64((1 << (8 * w)) - 1)
+        canon[:, 2 * c] = nulls[c]
+        canon[:, 2 * c + 1] = np.where(nulls[c], np.uint64(0), v)
+    if vals is None:
+        pay = np.arange(n, dtype=np.uint64)
+    else:
+        pay = np.asarray(vals)
+        if pay.dtype.kind == "i":
+            pay = pay.astype(np.int64).view(np.uint64)
+        elif pay.dtype.kind == "u":
+            pay = pay.astype(np.uint64)
+        else:  # Python integers beyond int64
+            pay = np.array([int(x) & 0xFFFFFFFFFFFFFFFF for x in pay.ravel()], np.uint64)
+        if len(pay) != n:
+            raise ValueError("vals: one payload per row")
+    out = {"form": _lib.HMJ_COLS_HASHED if hashed else _lib.HMJ_COLS_PACKED, "n_rows": n,
+           "n_null": int(np.count_nonzero(np.any(np.stack(nulls), axis=0))) if k and n else 0}
+    empty = np.zeros(0, np.uint64)
+    if n == 0:
+        out.update({"n_groups": 0, "max_count": 0, "n_collisions": 0, "max_mixed_run": 0, "group_of_row": empty})
+        out.update({name: empty for name in ("key64", "first_row", "count", "sum", "min", "max")})
+        return out
+    # groups in tuple order (numpy.unique sorts rows lexicographically; return_index: the first, i.e. smallest, row)
+    _, first, inv, count = np.unique(canon, axis=0, return_index=True, return_inverse=True, return_counts=True)
+    inv = inv.reshape(-1)
+    gkey = key64[first]
+    order = np.lexsort((np.arange(len(first)), gkey)) if ordered else np.argsort(first, kind="stable")
+    rank = np.empty(len(first), np.int64)
+    rank[order] = np.arange(len(first))
+    group_of_row = rank[inv]
+    by_group = np.argsort(group_of_row, kind="stable")
+    starts = np.concatenate([[0], np.cumsum(count[order])[:-1]]).astype(np.int64)
+    sorted_pay = pay[by_group]
+    with np.errstate(over="ignore"):
+        gsum = np.add.reduceat(sorted_pay, starts)
+    ukey, kinv = np.unique(key64, return_inverse=True)
+    tuples_per_key = np.bincount(kinv.reshape(-1)[first], minlength=len(ukey))
+    rows_per_key = np.bincount(kinv.reshape(-1), minlength=len(ukey))
+    mixed = rows_per_key[tuples_per_key > 1]
+    out.update({"n_groups": len(first), "max_count": int(count.max()), "n_collisions": int(len(first) - len(ukey)),
+                "max_mixed_run": int(mixed.max()) if len(mixed) else 0,
+                "key64": gkey[order], "first_row": first[order].astype(np.uint64), "count": count[order].astype(np.uint64),
+                "sum": gsum.astype(np.uint64), "min": np.minimum.reduceat(sorted_pay, starts),
+                "max": np.maximum.reduceat(sorted_pay, starts), "group_of_row": group_of_row.astype(np.uint64)})
+    return out
 
 
 def _hash_bytes(b):

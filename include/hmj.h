@@ -872,6 +872,75 @@ typedef struct {
 int hmj_join_mixed_device(hmj_ctx* ctx, const hmj_mixed_rel* build, const hmj_mixed_rel* probe, uint32_t flags,
                           hmj_mixed_opts* opts, hmj_cols_result* out);
 
+/* ---- grouping rows by multi-column keys (GROUP BY / DISTINCT) ------------------------------------------ */
+/* The rows of ONE relation of hmj_join_cols_device's shape (k fixed-width key columns, struct of arrays, an optional
+ * payload column) are grouped by their key tuple on the device: SELECT DISTINCT a, b; COUNT(*) per foreign key, to size a
+ * join's result; GROUP BY a, b with COUNT / SUM / MIN / MAX of one unsigned 64-bit value column.  Nothing in the reference
+ * corresponds.  A new entry with structs of its own: no other struct, flag or path bit changes.
+ * Grouping rule: two rows are in one group when, in every key column, both slots are NULL, or both are valid and equal bit
+ * for bit -- HMJ_NULL_EQUAL's match rule, always on here (SQL's GROUP BY, pandas' dropna=False): the NULLs of a column form
+ * one group, (NULL, 5) and (0, 5) are different groups, and so are (NULL, x) and (x, NULL).  The bytes under a NULL slot are
+ * undefined and nothing depends on them.  Every row belongs to exactly one group.  A caller who wants pandas' default drops
+ * the groups whose first_row is NULL in a key column; a take of the key columns with validity tells which.
+ * HMJ_NULL_EQUAL in flags is accepted and ignored (it is implied).
+ * key64 and form are exactly hmj_join_kind_cols_device's under HMJ_NULL_EQUAL.  Packed: T <= 8, not force_hashed and no
+ * entry of opts->validity with bits != NULL; key64 is the tuple itself.  Otherwise hashed, with the NULL-column mask step
+ * (a row without NULLs has the plain hashed key64); hash_bits is applied last.  opts->form is always filled.
+ * Outputs.  Without HMJ_MATERIALIZE only n_groups, n_rows, max_count, opts->n_null, opts->n_collisions and opts->form are
+ * filled (COUNT(DISTINCT ...)); every column pointer is NULL.  With HMJ_MATERIALIZE key64 and first_row are always filled:
+ * first_row is the SMALLEST row index of the group, so the representative is deterministic, and a take of the key columns
+ * through first_row (hmj_take_cols_device) is the DISTINCT table.  The HMJ_GROUP_* bits of opts->want add count, sum / min /
+ * max and group_of_row; a column not asked for is NULL.  sum / min / max run over rel->vals, or over the row index where
+ * vals is NULL; sum wraps mod 2^64, min / max compare unsigned.  group_of_row[i] is the index of row i's group into the
+ * group columns.  The result is owned by the ctx and valid until the next call on it or hmj_release_result;
+ * hmj_take_cols_device keeps it.  Like any other call this one discards a prepared build side.
+ * Order of groups.  HMJ_ORDERED (implies HMJ_MATERIALIZE): ascending by (key64, the tuple column by column as UNSIGNED
+ * integers, NULLS LAST in each column) -- in the packed form plainly ascending tuple order, i.e. GROUP BY ... ORDER BY the
+ * keys.  Without it the order is unspecified; all group columns agree with each other and with group_of_row.
+ * n == 0: n_groups == 0 and HMJ_OK.
+ * HMJ_E_ARG (hmj_last_error names what was wrong): everything hmj_join_cols_device rejects for one relation (NULL ctx / rel
+ * / opts / out, n_cols, widths, NULL or misaligned data, non-zero reserved, more than 2^32-1 rows, hash_bits > 63);
+ * HMJ_FIRST_WINS, HMJ_CHECKSUM, HMJ_SUM_PROBE; unknown want bits; non-zero opts->reserved; struct_size smaller than through
+ * validity; a bit_offset + n that overflows 64 bits.
+ * HMJ_E_UNSUPPORTED, the hashed form's limit: a run of equal key64 that holds several distinct tuples and more than 1024
+ * rows, or more than 2^22 adjacent sorted rows of equal key64 with different tuples.  Unlike the joins, which meet it in
+ * ordered calls only, it applies to every call here: no group can be formed without resolving such a run.  With 64 hash bits
+ * that takes a genuine collision of the hash.  The ctx stays usable.
+ * How (DESIGN.md "Grouping rows by multi-column keys"): the join's key kernel writes {key64, row} rows, hmj_sort_u64_device
+ * sorts them stably (rows of one key64 ascending by row), the hashed form sorts runs of equal key64 with several tuples by
+ * (tuple, row) in one workgroup each, group_heads_kernel marks every position whose key differs from its predecessor's
+ * (a wave's ballot is 64 head bits; one scan places the workgroups; tuples are compared only in a call whose collision
+ * search found a mismatch), group_emit_kernel writes the group columns and the row map, and group_agg_kernel reduces the
+ * payloads by a segmented scan inside each wave, finishing a group that crosses the 512 positions a wave walks with one
+ * atomic per wave.  Everything runs on the ctx stream in a workspace of the entry's own; the host reads back the
+ * mismatch count, n_groups and one counter block.  hmj_last_plan / hmj_last_timing are left as they were.
+ * Out of scope: string and mixed keys, several value columns per call, signed and float aggregates, the exchange path. */
+#define HMJ_GROUP_COUNT   0x01u  /* out->count                                                                         */
+#define HMJ_GROUP_SUM     0x02u  /* out->sum: wrapping u64 sum of the payloads                                          */
+#define HMJ_GROUP_MIN     0x04u  /* out->min: unsigned                                                                  */
+#define HMJ_GROUP_MAX     0x08u  /* out->max: unsigned                                                                  */
+#define HMJ_GROUP_ROW_MAP 0x10u  /* out->group_of_row                                                                   */
+typedef struct {
+  uint32_t struct_size;          /* in: sizeof of the caller's header (size-versioned like hmj_cols_kind_opts)          */
+  uint32_t want;                 /* in: HMJ_GROUP_* bits; any other bit is HMJ_E_ARG                                     */
+  uint32_t hash_bits;            /* in: as hmj_cols_join_opts                                                           */
+  uint32_t force_hashed;         /* in: as hmj_cols_join_opts                                                           */
+  uint32_t form;                 /* out: HMJ_COLS_PACKED / HMJ_COLS_HASHED, always filled                               */
+  uint32_t reserved;             /* 0                                                                                   */
+  const hmj_validity* validity;  /* in: HOST array of n_cols entries (read during the call only), or NULL               */
+  uint64_t n_null;               /* out: rows with at least one NULL key slot                                           */
+  uint64_t n_collisions;         /* out: adjacent sorted rows of equal key64 whose tuples differ (packed: 0)            */
+  float ms_key, ms_sort, ms_groups, ms_agg; /* out, with hmj_set_profiling(ctx, 1): HIP-event phase times              */
+} hmj_group_opts;
+typedef struct {
+  uint64_t n_groups, n_rows;
+  uint64_t max_count;            /* rows of the largest group (0 when n == 0)                                           */
+  const uint64_t *key64, *first_row, *count, *sum, *min, *max; /* n_groups each; device, HMJ_MATERIALIZE               */
+  const uint64_t* group_of_row;  /* n_rows; device, HMJ_MATERIALIZE + HMJ_GROUP_ROW_MAP                                 */
+} hmj_group_result;
+int hmj_group_cols_device(hmj_ctx* ctx, const hmj_cols_rel* rel, uint32_t flags, hmj_group_opts* opts,
+                          hmj_group_result* out);
+
 /* ---- taking fixed-width columns through a row map (Arrow validity out) --------------------------------- */
 /* The joins above return gather maps (r_row / s_row), not columns.  This entry turns a map back into Arrow columns: up to
  * HMJ_MAX_TAKE_COLS fixed-width columns of ONE relation (n_src rows each; keys, payloads, anything of 1, 2, 4, 8 or 16
