@@ -470,12 +470,19 @@ float elapsed(const hipEvent_t* ev, int a, int b) {
   return ms;
 }
 
-// join_device on {key64,row} rows under a workload_signature kind of its own (memo), with its spans collected
+// join_device on {key64,row} rows under a workload_signature kind of its own (memo), with its spans collected.
+// hmj_set_key_prefix_bits describes the CALLER'S u64 relations; key64 is a hash or a packed tuple, about which the caller
+// promised nothing (a hint would place the partition window as if key64 shared those top bits: partitions would stop
+// being key ranges, and an ordered result is not sorted again).  So this join samples its own keys, and the hint is put
+// back for the caller's next u64 join on every way out.
 int memo_join(hmj_ctx* c, const void* Rr, u64 nr, const void* Sr, u64 ns, uint32_t flags, int memo, hmj_result* out) {
   spans_reset(c);
   const int st = span_begin(c, K_TOTAL, -1);
   c->memo_kind = memo;
+  const int hint = c->prefix_bits;
+  c->prefix_bits = -1;
   const int rc = join_device(c, Rr, nr, Sr, ns, flags, out, false);
+  c->prefix_bits = hint;
   c->memo_kind = 0;
   span_end(c, st);
   if (c->profiling) {

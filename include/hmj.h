@@ -217,8 +217,14 @@ int hmj_autotune_radix_bits(hmj_ctx* ctx, uint64_t n_build, uint64_t n_probe, in
  * below them, as the reference's recursion masks off consumed bits (radix_hash.h:219-220).
  * bits = -1 (the default): the executor samples both relations and skips the top bits all sampled
  * keys share (dense / small-integer keys would otherwise all fall into partition 0).
- * Any value is safe for the result; ordered output additionally verifies a sampled prefix on every
- * row and re-plans without it if a row disagrees.                                                */
+ * Any value is safe for the counts, the sums and the set of result rows (every window of key bits is a
+ * partition function).  The ORDER of HMJ_ORDERED output relies on partitions being key ranges: a sampled
+ * prefix is verified on every row, and the join re-plans without it if a row disagrees; a prefix given
+ * here is the caller's promise and is taken as it is.
+ * The hint describes the caller's u64 relations -- hmj_join_u64_device, the u64 kind entries, the host and
+ * exchange joins.  The string, multi-column and mixed-key entries join on a key64 of their own (a hash, or
+ * a packed tuple): their internal joins always sample that key64 and never read the hint, and they leave
+ * it in place for the caller's next u64 join.                                                    */
 int hmj_set_key_prefix_bits(hmj_ctx* ctx, int bits);
 /* The automatic plan for a build side of n_build rows: total bits and per-pass bits (LSD order).*/
 int hmj_plan(uint64_t n_build, int* total_bits, int* n_passes, int pass_bits[4]);

@@ -15,7 +15,8 @@ pytestmark = pytest.mark.gpu
 M64 = (1 << 64) - 1
 HMJ_E_ARG, HMJ_E_UNSUPPORTED = -1, -5
 COLUMNS = ("key64", "first_row", "count", "sum", "min", "max", "group_of_row")
-SIZES = [1, 2, 63, 64, 65, 255, 256, 257, 1023, 1025, 4097]
+# (511 .. 513 and 2047 .. 2049: the 512 positions one wave of group_agg_kernel walks, the 2048 of one of its workgroups)
+SIZES = [1, 2, 63, 64, 65, 255, 256, 257, 511, 512, 513, 1023, 1025, 2047, 2048, 2049, 4097]
 
 
 @pytest.fixture(scope="module")
@@ -105,13 +106,20 @@ def run_and_check(H, ex, cols, widths, vals=None, valid=None, ordered=False, tag
 def test_sizes_and_group_boundaries(H, ex, n):
     """Every size with one group, all rows distinct, groups of exactly 64 and 256 rows aligned to the sorted order (packed
     keys i // 64: the stable sort leaves row i at position i), and the same shifted by one row, so that every group
-    straddles a wave and every fourth a workgroup boundary.  Payloads near 2^63: the sums wrap."""
+    straddles a wave and every fourth a workgroup boundary; and the same with groups of 512 and 2048 rows, the positions one
+    wave and one workgroup of group_agg_kernel walk (kAggChunks * 64, KJ_WAVES waves): a group that ends exactly on a wave's
+    range is the only one its carry stores without an atomic, one that crosses it by a single row the smallest atomic finish.
+    Payloads near 2^63: the sums wrap."""
     rng = np.random.default_rng(n)
     i = np.arange(n, dtype=np.uint64)
     vals = (np.uint64(1 << 63) - np.uint64(5)) + rng.integers(0, 11, size=n).astype(np.uint64)
     zero = np.zeros(n, np.uint32)
     cases = {"one group": i * np.uint64(0), "distinct": i, "64 aligned": i // np.uint64(64), "256 aligned": i // np.uint64(256),
-             "64 shifted": (i + np.uint64(1)) // np.uint64(64), "256 shifted": (i + np.uint64(1)) // np.uint64(256)}
+             "64 shifted": (i + np.uint64(1)) // np.uint64(64), "256 shifted": (i + np.uint64(1)) // np.uint64(256),
+             # the aggregate kernel's own ranges: a group that ends exactly on a wave's 512 positions (the only one its
+             # carry stores without an atomic) or on a workgroup's 2048, and the same crossing the range by one row
+             "512 aligned": i // np.uint64(512), "512 shifted": (i + np.uint64(1)) // np.uint64(512),
+             "2048 aligned": i // np.uint64(2048), "2048 shifted": (i + np.uint64(1)) // np.uint64(2048)}
     for name, key in cases.items():
         cols = [zero, key.astype(np.uint32)]
         for ordered in (False, True):
