@@ -666,6 +666,8 @@ typedef struct {
  * key64 has its tuples compared column by column and its payloads gathered (verify_kernel; survivors compacted
  * stably), and -- ordered only -- runs of equal key64 whose build tuples differ are sorted by tuple, each inside one
  * workgroup.
+ * Every tuple is a legal key, the packed tuple of 8 bytes 0xFF (key64 == 2^64 - 1) included: the inner join's global
+ * table, whose empty slots hold that value, gives way to the partitioned path for such a build side.
  * n == 0 on either side: an empty result and HMJ_OK (sum_probe_all is still filled when asked).
  * HMJ_E_ARG (hmj_last_error names what was wrong): NULL ctx / rel / opts / out; opts->struct_size too small; n_cols
  * outside 1..HMJ_MAX_KEY_COLS; a NULL cols array; a width other than 1, 2, 4 or 8; a NULL or misaligned data with n > 0;
