@@ -10,7 +10,7 @@ from ._lib import (HMJ_BUILD_ANTI, HMJ_BUILD_OUTER, HMJ_BUILD_SEMI, HMJ_CHECKSUM
                    HMJ_PATH_KEY_RANGES, HMJ_PATH_PREPARED, HMJ_PATH_PRESORTED, HMJ_PATH_RANK_RUNS, HMJ_PATH_SORT_MSD, HMJ_PATH_SLAB, HMJ_PATH_SLAB_ONE_PASS, HMJ_PATH_SLAB_PROBE, HMJ_PATH_SORTED_FK, HMJ_PATH_SORTED_FK_HALF, HMJ_PATH_SORTED_FK_WIDE, HMJ_PATH_SORTED_WRITE, HMJ_PATH_SPLIT, HMJ_PATH_UNIQ_WRITE, HMJ_PATH_WINDOW,
                    HMJ_KEY_FIXED, HMJ_KEY_LARGE_STRING, HMJ_MAX_KEY_COLS, HMJ_MAX_TAKE_COLS, HMJ_NULL_EQUAL, HMJ_STR_NO_ROW, HMJ_SUM_PROBE, HMJ_TAKE_NO_ROW, BuildJoinOpts, ColsJoinOpts, ColsKindOpts, ColsRel, ColsResult, ExchangeKindOpts, GroupOpts, GroupResult, HmjError, JoinOpts, JoinResult, KeyCol, KindCounts, MixedCol, MixedOpts, MixedRel, StrJoinOpts, StrKindOpts, StrRel, StrResult, TakeDst, TakeOpts, TakeSrc, TakeStrDst, TakeStrOpts, TakeStrSrc, Timing, Validity,
                    lib_path, load_library)
-from .join import Executor, HashMergeJoin, cols_key64, expected_groups, mixed_key64, pack_strings, pack_validity, plan, unpack_strings, unpack_validity
+from .join import Executor, HashMergeJoin, cols_key64, expected_groups, expected_mixed_groups, mixed_key64, pack_strings, pack_validity, plan, unpack_strings, unpack_validity
 
 __all__ = ["Executor", "HashMergeJoin", "plan", "HmjError", "JoinResult", "Timing", "load_library",
            "lib_path", "HMJ_MATERIALIZE", "HMJ_ORDERED", "HMJ_FIRST_WINS", "HMJ_CHECKSUM",
@@ -25,4 +25,4 @@ __all__ = ["Executor", "HashMergeJoin", "plan", "HmjError", "JoinResult", "Timin
            "MixedCol", "MixedRel", "MixedOpts", "HMJ_KEY_FIXED", "HMJ_KEY_LARGE_STRING", "mixed_key64",
            "HMJ_NULL_EQUAL",
            "GroupOpts", "GroupResult", "HMJ_GROUP_COUNT", "HMJ_GROUP_SUM", "HMJ_GROUP_MIN", "HMJ_GROUP_MAX", "HMJ_GROUP_ROW_MAP",
-           "expected_groups"]
+           "expected_groups", "expected_mixed_groups"]

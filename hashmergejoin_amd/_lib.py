@@ -210,7 +210,7 @@ class MixedOpts(C.Structure):
                 ("ms_join", C.c_float), ("ms_verify", C.c_float), ("ms_emit", C.c_float), ("ms_order", C.c_float)]
 
 
-# hmj_group_cols_device: rows grouped by multi-column keys; hmj_group_opts.want
+# hmj_group_cols_device / hmj_group_mixed_device: rows grouped by multi-column / string and mixed keys; hmj_group_opts.want
 HMJ_GROUP_COUNT, HMJ_GROUP_SUM, HMJ_GROUP_MIN, HMJ_GROUP_MAX, HMJ_GROUP_ROW_MAP = 0x01, 0x02, 0x04, 0x08, 0x10
 
 
@@ -432,6 +432,8 @@ def load_library():
                                         C.POINTER(ColsResult)]
     L.hmj_group_cols_device.restype = i
     L.hmj_group_cols_device.argtypes = [vp, C.POINTER(ColsRel), C.c_uint32, C.POINTER(GroupOpts), C.POINTER(GroupResult)]
+    L.hmj_group_mixed_device.restype = i
+    L.hmj_group_mixed_device.argtypes = [vp, C.POINTER(MixedRel), C.c_uint32, C.POINTER(GroupOpts), C.POINTER(GroupResult)]
     L.hmj_take_cols_device.restype = i
     L.hmj_take_cols_device.argtypes = [vp, C.POINTER(TakeSrc), C.c_uint32, u, vp, u, C.POINTER(TakeDst), C.POINTER(TakeOpts)]
     L.hmj_take_str_device.restype = i

@@ -36,7 +36,7 @@
 // ColNeSide / ColNePolicy, whose key_eq / key_cmp read the bitmaps (DESIGN.md "NULL-equals-NULL matching").
 // Grouping (hmj_group_cols_device): one relation's {key64, row} rows from the key kernels above (cols_key_ne_kernel where a
 // bitmap is passed: NULLs of a column form one group), hmj_sort_u64_device, then hmj_group.h's kernels on ColSide /
-// ColNeSide -- collision sort, group heads, group columns, aggregates (group_rows below; DESIGN.md "Grouping rows by
+// ColNeSide -- collision sort, group heads, group columns, aggregates (group_rows, hmj_group.h; DESIGN.md "Grouping rows by
 // multi-column keys").
 #include <hip/hip_runtime.h>
 
@@ -604,124 +604,8 @@ void clear_out_fields(hmj_cols_kind_opts* o, const hmj_cols_kind_opts* opts, siz
   if (have > lo) std::memcpy((char*)o + lo, (const char*)opts + lo, have - lo);
 }
 
-// ---- grouping (hmj_group_cols_device; kernels: hmj_group.h) ---------------------------------------------------------------
+// ---- grouping (hmj_group_cols_device; kernels and the driver, group_rows: hmj_group.h) ------------------------------------
 constexpr KeyJoinNames kGroupNames{"multi-column grouping", "key64", "tuples"};
-
-// What hmj_group_cols_device does behind its argument checks.  A: the relation as the kernels of steps 3-6 take it (ColSide:
-// no bitmap; ColNeSide: with bitmaps, always hashed); key: launches the key kernel of that form into the rows it is given.
-// o: hash_bits / force_hashed / want in, n_null / n_collisions out.
-template <class Side, class KeyFn>
-int group_rows(hmj_ctx* c, const Side& A, u64 n, bool hashed, bool mat, KeyFn key, hmj_group_opts* o, hmj_group_result* out) {
-  GroupWs& ws = c->grp_ws;
-  const u32 want = mat ? o->want : 0u;
-  const u64 nblk = blocks_of(n);
-  RC_TRY(ensure_dev(c, ws.acc, GA_N * sizeof(u64)));
-  RC_TRY(ensure_dev(c, ws.rows, 16 * n));
-  RC_TRY(ensure_dev(c, ws.sorted, 16 * n));
-  RC_TRY(ensure_dev(c, ws.flags, nblk * KJ_WAVES * sizeof(u64)));
-  RC_TRY(ensure_dev(c, ws.blk, nblk * sizeof(u64)));
-  RC_TRY(ensure_dev(c, ws.blk_off, (nblk + 1) * sizeof(u64)));
-  u64* acc = (u64*)ws.acc.p;
-  ulonglong2* rows = (ulonglong2*)ws.sorted.p;
-  const dim3 G((u32)nblk), T(KJ_THREADS);
-  u64 h[GA_N];
-  // 1. {key64, row} rows
-  RC_TRY(record(c, ws.ev, 0));
-  HIP_TRY(hipMemsetAsync(acc, 0, GA_N * sizeof(u64), c->stream));
-  RC_TRY(key(c, (u64*)ws.rows.p, acc));
-  RC_TRY(record(c, ws.ev, 1));
-  // 2. the stable u64 sort: rows of one key64 contiguous and ascending by row
-  {
-    const hmj_plan_desc plan = c->plan;  // (the sort is not a join: hmj_last_plan / hmj_last_timing keep describing the last one)
-    const hmj_timing timing = c->timing;
-    const int rc = hmj_sort_u64_device(c, ws.rows.p, n, ws.sorted.p);
-    c->plan = plan;
-    c->timing = timing;
-    if (rc != HMJ_OK) return rc;
-  }
-  RC_TRY(record(c, ws.ev, 2));
-  // 3. hashed: runs of equal key64 that hold several tuples, sorted by (tuple, row)
-  bool mixed = false;  // some run of equal key64 holds several tuples
-  if (hashed && n > 1) {
-    const u64 cap = n < kListCap ? n : kListCap;
-    RC_TRY(ensure_dev(c, ws.list, cap * sizeof(u64)));
-    RC_TRY(ensure_dev(c, ws.runs, 2 * cap * sizeof(u64)));
-    hipLaunchKernelGGL(group_mismatch_kernel<Side>, dim3((u32)blocks_of(n - 1)), T, 0, c->stream, (const ulonglong2*)rows, n, A,
-                       (u64*)ws.list.p, acc);
-    HIP_TRY(hipGetLastError());
-    RC_TRY(read_back(c, acc, h, KA_N * sizeof(u64)));
-    RC_TRY(collision_errors(c, kGroupNames, h[KA_ERR]));
-    mixed = h[KA_LIST_N] != 0;
-    if (mixed) {
-      const u64 gl = blocks_of(h[KA_LIST_N]), gs = h[KA_LIST_N] < (u64)(4 * c->num_cus) ? h[KA_LIST_N] : (u64)(4 * c->num_cus);
-      hipLaunchKernelGGL(group_run_leader_kernel<Side>, dim3((u32)(gl < 1024 ? gl : 1024)), T, 0, c->stream, (const ulonglong2*)rows, n, A,
-                         (const u64*)ws.list.p, (u64*)ws.runs.p, acc);
-      HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(group_run_sort_kernel<Side>, dim3((u32)gs), T, 0, c->stream, (const u64*)ws.runs.p, A, rows, (const u64*)acc);
-      HIP_TRY(hipGetLastError());
-      RC_TRY(read_back(c, acc, h, KA_N * sizeof(u64)));
-      RC_TRY(collision_errors(c, kGroupNames, h[KA_ERR]));
-    }
-  }
-  // 4. heads: one ballot word per wave, heads per workgroup, one scan; n_groups comes back to size the group columns.  The
-  // tuples are compared only where the collision search found a mismatch: without one, equal key64 is equal tuples.
-  if (mixed) hipLaunchKernelGGL((group_heads_kernel<Side, true>), G, T, 0, c->stream, (const ulonglong2*)rows, n, A, (u64*)ws.flags.p,
-                                 (u64*)ws.blk.p, acc);
-  else hipLaunchKernelGGL((group_heads_kernel<Side, false>), G, T, 0, c->stream, (const ulonglong2*)rows, n, A, (u64*)ws.flags.p,
-                          (u64*)ws.blk.p, acc);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hmj::launch_scan_u64((const u64*)ws.blk.p, (u64*)ws.blk_off.p, (u32)nblk, c->stream));
-  u64 ng = 0;
-  RC_TRY(read_back(c, (const u64*)ws.blk_off.p + nblk, &ng, sizeof(u64)));
-  if (ng < 1 || ng > n) return fail(c, HMJ_E_HIP, "multi-column grouping: the heads' count is not in 1..n");
-  // 5. the group columns (count-only calls: start alone, for max_count)
-  RC_TRY(ensure_dev(c, ws.start, (ng + 1) * sizeof(u64)));
-  struct Col {
-    DevBuf* b;
-    bool on;
-    u64 rows;
-    u64* p;
-  } cols[7] = {{&ws.key, mat, ng, nullptr},
-               {&ws.first, mat, ng, nullptr},
-               {&ws.count, (want & HMJ_GROUP_COUNT) != 0, ng, nullptr},
-               {&ws.sum, (want & HMJ_GROUP_SUM) != 0, ng, nullptr},
-               {&ws.min, (want & HMJ_GROUP_MIN) != 0, ng, nullptr},
-               {&ws.max, (want & HMJ_GROUP_MAX) != 0, ng, nullptr},
-               {&ws.gmap, (want & HMJ_GROUP_ROW_MAP) != 0, n, nullptr}};
-  for (Col& k : cols) {
-    if (!k.on) continue;
-    RC_TRY(ensure_dev(c, *k.b, k.rows * sizeof(u64)));
-    k.p = (u64*)k.b->p;
-  }
-  hipLaunchKernelGGL(group_emit_kernel, G, T, 0, c->stream, (const ulonglong2*)rows, n, ng, (const u64*)ws.flags.p, (const u64*)ws.blk_off.p,
-                     cols[0].p, cols[1].p, (u64*)ws.start.p, cols[3].p, cols[4].p, cols[5].p, cols[6].p);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(group_count_kernel, dim3((u32)blocks_of(ng)), T, 0, c->stream, (const u64*)ws.start.p, ng, cols[2].p, acc);
-  HIP_TRY(hipGetLastError());
-  RC_TRY(record(c, ws.ev, 3));
-  // 6. sum / min / max of the payloads
-  if (want & (HMJ_GROUP_SUM | HMJ_GROUP_MIN | HMJ_GROUP_MAX)) {
-    const u64 waves = ((n + 63) / 64 + kAggChunks - 1) / kAggChunks;  // a wave walks kAggChunks chunks of 64 positions
-    hipLaunchKernelGGL(group_agg_kernel<Side>, dim3((u32)((waves + KJ_WAVES - 1) / KJ_WAVES)), T, 0, c->stream, (const ulonglong2*)rows, n, ng, A, (const u64*)ws.flags.p,
-                       (const u64*)ws.blk_off.p, cols[3].p, cols[4].p, cols[5].p);
-    HIP_TRY(hipGetLastError());
-  }
-  RC_TRY(record(c, ws.ev, 4));
-  RC_TRY(read_back(c, acc, h, sizeof(h)));
-  RC_TRY(collision_errors(c, kGroupNames, h[KA_ERR]));
-  o->n_null = null_rows_of(h + GA_NULL);
-  o->n_collisions = h[GA_COLL];
-  out->n_groups = ng;
-  out->max_count = h[GA_MAXC];
-  out->key64 = (const uint64_t*)cols[0].p;
-  out->first_row = (const uint64_t*)cols[1].p;
-  out->count = (const uint64_t*)cols[2].p;
-  out->sum = (const uint64_t*)cols[3].p;
-  out->min = (const uint64_t*)cols[4].p;
-  out->max = (const uint64_t*)cols[5].p;
-  out->group_of_row = (const uint64_t*)cols[6].p;
-  return HMJ_OK;
-}
 
 }  // namespace
 
@@ -861,11 +745,11 @@ int hmj_group_cols_device(hmj_ctx* c, const hmj_cols_rel* rel, uint32_t flags, h
         HIP_TRY(hipGetLastError());
         return (int)HMJ_OK;
       };
-      RC_TRY(group_rows(c, A, n, true, mat, key, &o, out));
+      RC_TRY(group_rows(c, kGroupNames, A, n, true, mat, key, GroupNoCheck{}, &o, out));
     } else {
       const ColSide A = side_of(rel);
       auto key = [&](hmj_ctx* c, u64* rows, u64* acc) { return launch_key(c, A, n, hashed, bits, rows, false, acc); };
-      RC_TRY(group_rows(c, A, n, hashed, mat, key, &o, out));
+      RC_TRY(group_rows(c, kGroupNames, A, n, hashed, mat, key, GroupNoCheck{}, &o, out));
     }
     if (c->profiling) {
       (void)hipStreamSynchronize(c->stream);

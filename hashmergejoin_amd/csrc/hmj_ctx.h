@@ -49,7 +49,8 @@ struct KeyJoinWs {
   }
 };
 
-// Workspace of hmj_group_cols_device (coljoin.hip, hmj_group.h): no other entry reuses or regrows its buffers.
+// Workspace of the group entries, hmj_group_cols_device (coljoin.hip) and hmj_group_mixed_device (mixjoin.hip), through
+// hmj_group.h's group_rows: no other entry reuses or regrows its buffers.
 struct GroupWs {
   DevBuf rows, sorted,        // {key64, row} rows as keyed, and sorted by key64 (hashed: runs with several tuples by tuple too)
       flags, blk, blk_off,    // head ballots (one word per wave), heads per workgroup and their offsets
@@ -158,7 +159,7 @@ struct hmj_ctx {
   // string joins (strjoin.hip), multi-column joins (coljoin.hip) and mixed-key joins (mixjoin.hip): one workspace each, so
   // that no call reuses or regrows another's buffers
   hmj_host::KeyJoinWs str_ws, col_ws, mix_ws;
-  hmj_host::GroupWs grp_ws;  // hmj_group_cols_device
+  hmj_host::GroupWs grp_ws;  // hmj_group_cols_device, hmj_group_mixed_device
   hipEvent_t take_ev[2] = {nullptr, nullptr};  // hmj_take_cols_device: around its launches (profiling)
   hipEvent_t takestr_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // hmj_take_str_device: around its offsets and its bytes phase
   int memo_kind = 0;  // workload-signature kind of plain inner joins run on behalf of another entry (string, multi-column joins and their kinds)

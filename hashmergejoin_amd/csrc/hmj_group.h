@@ -1,8 +1,8 @@
-// Grouping rows by key (hmj_group_cols_device, coljoin.hip): what follows the key kernel and the stable u64 sort of the
-// {key64, row} rows -- the collision sort on 16-byte rows, the group heads, the group columns and the aggregates -- as
-// templates over the relation-side struct of the including file, with hmj_keyjoin.h's key policy (key_eq / key_cmp /
-// payload overloads next to the Side), so that other key shapes can follow.  Internal header: its contents are local to the
-// file that includes it.
+// Grouping rows by key (hmj_group_cols_device, coljoin.hip; hmj_group_mixed_device, mixjoin.hip): what follows the key
+// kernel and the stable u64 sort of the {key64, row} rows -- the collision sort on 16-byte rows, the group heads, the group
+// columns and the aggregates -- as templates over the relation-side struct of the including file, with hmj_keyjoin.h's key
+// policy (key_eq / key_cmp / payload overloads next to the Side), and group_rows, the host sequence of both entries behind
+// their argument checks.  Internal header: its contents are local to the file that includes it.
 // Kernels (KJ_THREADS lanes per workgroup; `rows` are the sorted {key64, row} rows, n of them):
 //   group_mismatch_kernel / group_run_leader_kernel / group_run_sort_kernel   hashed keys: runs of equal key64 that hold
 //                          several keys are sorted by (key, row), each in one workgroup (hmj_keyjoin.h's collision order on
@@ -20,7 +20,8 @@
 namespace {
 
 // acc words of a group call behind hmj_keyjoin.h's KA_LIST_N / KA_ERR: heads that follow a row of equal key64, the largest
-// group's rows; from GA_NULL on the key kernel's kNullWords words (count_null_rows)
+// group's rows; from GA_NULL on the column key kernel's kNullWords words (count_null_rows); behind GA_N the words of
+// group_rows' Check, if any
 enum { GA_COLL = KA_ACC, GA_MAXC = KA_ACC + 1, GA_NULL = KA_N, GA_N = KA_N + kNullWords };
 
 // Row i of the sorted rows whose key64 equals row i-1's but whose key differs is recorded (mismatch_kernel's test).
@@ -317,6 +318,148 @@ __global__ __launch_bounds__(KJ_THREADS) void group_agg_kernel(const ulonglong2*
     heads += (u64)__builtin_popcountll(m);
   }
   if (have && lane == 0) group_put(true, heads - 1, ng, cs, clo, chi, sum, mn, mx);  // open on the right, always
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------
+// What a key kernel that checks its input adds to group_rows: kWords report words behind the call's GA_N accumulator words
+// (cleared with them), begin() to preset them before the key kernel, and check() on their host copy -- behind the key
+// kernel and the u64 sort, which reads key64 and row only, and in front of the first kernel that compares tuples.  A check
+// that fails ends the call; one that passes may fill o->n_null.  GroupNoCheck: fixed-width columns, whose key kernels
+// report nothing -- no word, no launch and no round trip is added.
+struct GroupNoCheck {
+  static constexpr int kWords = 0;
+  int begin(hmj_ctx*, u64*) const { return HMJ_OK; }
+  int check(hmj_ctx*, const u64*, hmj_group_opts*) const { return HMJ_OK; }
+};
+
+// What a group entry does behind its argument checks.  A: the relation as the kernels of steps 3-6 take it (a Side without
+// bitmaps, or its NULL-equals-NULL form with them, always hashed); key: launches the key kernel of that form into the rows
+// it is given (acc: the call's accumulator, the Check's words from acc + GA_N).
+// o: hash_bits / force_hashed / want in, n_null / n_collisions out.
+template <class Side, class KeyFn, class Check>
+int group_rows(hmj_ctx* c, const KeyJoinNames& nm, const Side& A, u64 n, bool hashed, bool mat, KeyFn key, const Check& chk, hmj_group_opts* o,
+               hmj_group_result* out) {
+  GroupWs& ws = c->grp_ws;
+  const u32 want = mat ? o->want : 0u;
+  const u64 nblk = blocks_of(n);
+  constexpr size_t acc_words = (size_t)GA_N + (size_t)Check::kWords;
+  RC_TRY(ensure_dev(c, ws.acc, acc_words * sizeof(u64)));
+  RC_TRY(ensure_dev(c, ws.rows, 16 * n));
+  RC_TRY(ensure_dev(c, ws.sorted, 16 * n));
+  RC_TRY(ensure_dev(c, ws.flags, nblk * KJ_WAVES * sizeof(u64)));
+  RC_TRY(ensure_dev(c, ws.blk, nblk * sizeof(u64)));
+  RC_TRY(ensure_dev(c, ws.blk_off, (nblk + 1) * sizeof(u64)));
+  u64* acc = (u64*)ws.acc.p;
+  ulonglong2* rows = (ulonglong2*)ws.sorted.p;
+  const dim3 G((u32)nblk), T(KJ_THREADS);
+  u64 h[GA_N];
+  // 1. {key64, row} rows
+  RC_TRY(record(c, ws.ev, 0));
+  HIP_TRY(hipMemsetAsync(acc, 0, acc_words * sizeof(u64), c->stream));
+  if constexpr (Check::kWords != 0) RC_TRY(chk.begin(c, acc + GA_N));
+  RC_TRY(key(c, (u64*)ws.rows.p, acc));
+  RC_TRY(record(c, ws.ev, 1));
+  // 2. the stable u64 sort: rows of one key64 contiguous and ascending by row
+  {
+    const hmj_plan_desc plan = c->plan;  // (the sort is not a join: hmj_last_plan / hmj_last_timing keep describing the last one)
+    const hmj_timing timing = c->timing;
+    const int rc = hmj_sort_u64_device(c, ws.rows.p, n, ws.sorted.p);
+    c->plan = plan;
+    c->timing = timing;
+    if (rc != HMJ_OK) return rc;
+  }
+  RC_TRY(record(c, ws.ev, 2));
+  // the key kernel's verdict on its input, before any kernel follows a row into the key columns
+  if constexpr (Check::kWords != 0) {
+    u64 e[Check::kWords];
+    RC_TRY(read_back(c, acc + GA_N, e, sizeof(e)));
+    RC_TRY(chk.check(c, e, o));
+  }
+  // 3. hashed: runs of equal key64 that hold several tuples, sorted by (tuple, row)
+  bool mixed = false;  // some run of equal key64 holds several tuples
+  if (hashed && n > 1) {
+    const u64 cap = n < kListCap ? n : kListCap;
+    RC_TRY(ensure_dev(c, ws.list, cap * sizeof(u64)));
+    RC_TRY(ensure_dev(c, ws.runs, 2 * cap * sizeof(u64)));
+    hipLaunchKernelGGL(group_mismatch_kernel<Side>, dim3((u32)blocks_of(n - 1)), T, 0, c->stream, (const ulonglong2*)rows, n, A,
+                       (u64*)ws.list.p, acc);
+    HIP_TRY(hipGetLastError());
+    RC_TRY(read_back(c, acc, h, KA_N * sizeof(u64)));
+    RC_TRY(collision_errors(c, nm, h[KA_ERR]));
+    mixed = h[KA_LIST_N] != 0;
+    if (mixed) {
+      const u64 gl = blocks_of(h[KA_LIST_N]), gs = h[KA_LIST_N] < (u64)(4 * c->num_cus) ? h[KA_LIST_N] : (u64)(4 * c->num_cus);
+      hipLaunchKernelGGL(group_run_leader_kernel<Side>, dim3((u32)(gl < 1024 ? gl : 1024)), T, 0, c->stream, (const ulonglong2*)rows, n, A,
+                         (const u64*)ws.list.p, (u64*)ws.runs.p, acc);
+      HIP_TRY(hipGetLastError());
+      hipLaunchKernelGGL(group_run_sort_kernel<Side>, dim3((u32)gs), T, 0, c->stream, (const u64*)ws.runs.p, A, rows, (const u64*)acc);
+      HIP_TRY(hipGetLastError());
+      RC_TRY(read_back(c, acc, h, KA_N * sizeof(u64)));
+      RC_TRY(collision_errors(c, nm, h[KA_ERR]));
+    }
+  }
+  // 4. heads: one ballot word per wave, heads per workgroup, one scan; n_groups comes back to size the group columns.  The
+  // tuples are compared only where the collision search found a mismatch: without one, equal key64 is equal tuples.
+  if (mixed) hipLaunchKernelGGL((group_heads_kernel<Side, true>), G, T, 0, c->stream, (const ulonglong2*)rows, n, A, (u64*)ws.flags.p,
+                                 (u64*)ws.blk.p, acc);
+  else hipLaunchKernelGGL((group_heads_kernel<Side, false>), G, T, 0, c->stream, (const ulonglong2*)rows, n, A, (u64*)ws.flags.p,
+                          (u64*)ws.blk.p, acc);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hmj::launch_scan_u64((const u64*)ws.blk.p, (u64*)ws.blk_off.p, (u32)nblk, c->stream));
+  u64 ng = 0;
+  RC_TRY(read_back(c, (const u64*)ws.blk_off.p + nblk, &ng, sizeof(u64)));
+  if (ng < 1 || ng > n) {
+    char msg[128];
+    std::snprintf(msg, sizeof(msg), "%s: the heads' count is not in 1..n", nm.join);
+    return fail(c, HMJ_E_HIP, msg);
+  }
+  // 5. the group columns (count-only calls: start alone, for max_count)
+  RC_TRY(ensure_dev(c, ws.start, (ng + 1) * sizeof(u64)));
+  struct Col {
+    DevBuf* b;
+    bool on;
+    u64 rows;
+    u64* p;
+  } cols[7] = {{&ws.key, mat, ng, nullptr},
+               {&ws.first, mat, ng, nullptr},
+               {&ws.count, (want & HMJ_GROUP_COUNT) != 0, ng, nullptr},
+               {&ws.sum, (want & HMJ_GROUP_SUM) != 0, ng, nullptr},
+               {&ws.min, (want & HMJ_GROUP_MIN) != 0, ng, nullptr},
+               {&ws.max, (want & HMJ_GROUP_MAX) != 0, ng, nullptr},
+               {&ws.gmap, (want & HMJ_GROUP_ROW_MAP) != 0, n, nullptr}};
+  for (Col& k : cols) {
+    if (!k.on) continue;
+    RC_TRY(ensure_dev(c, *k.b, k.rows * sizeof(u64)));
+    k.p = (u64*)k.b->p;
+  }
+  hipLaunchKernelGGL(group_emit_kernel, G, T, 0, c->stream, (const ulonglong2*)rows, n, ng, (const u64*)ws.flags.p, (const u64*)ws.blk_off.p,
+                     cols[0].p, cols[1].p, (u64*)ws.start.p, cols[3].p, cols[4].p, cols[5].p, cols[6].p);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(group_count_kernel, dim3((u32)blocks_of(ng)), T, 0, c->stream, (const u64*)ws.start.p, ng, cols[2].p, acc);
+  HIP_TRY(hipGetLastError());
+  RC_TRY(record(c, ws.ev, 3));
+  // 6. sum / min / max of the payloads
+  if (want & (HMJ_GROUP_SUM | HMJ_GROUP_MIN | HMJ_GROUP_MAX)) {
+    const u64 waves = ((n + 63) / 64 + kAggChunks - 1) / kAggChunks;  // a wave walks kAggChunks chunks of 64 positions
+    hipLaunchKernelGGL(group_agg_kernel<Side>, dim3((u32)((waves + KJ_WAVES - 1) / KJ_WAVES)), T, 0, c->stream, (const ulonglong2*)rows, n, ng, A, (const u64*)ws.flags.p,
+                       (const u64*)ws.blk_off.p, cols[3].p, cols[4].p, cols[5].p);
+    HIP_TRY(hipGetLastError());
+  }
+  RC_TRY(record(c, ws.ev, 4));
+  RC_TRY(read_back(c, acc, h, sizeof(h)));
+  RC_TRY(collision_errors(c, nm, h[KA_ERR]));
+  if constexpr (Check::kWords == 0) o->n_null = null_rows_of(h + GA_NULL);  // (else: the Check's words hold the count)
+  o->n_collisions = h[GA_COLL];
+  out->n_groups = ng;
+  out->max_count = h[GA_MAXC];
+  out->key64 = (const uint64_t*)cols[0].p;
+  out->first_row = (const uint64_t*)cols[1].p;
+  out->count = (const uint64_t*)cols[2].p;
+  out->sum = (const uint64_t*)cols[3].p;
+  out->min = (const uint64_t*)cols[4].p;
+  out->max = (const uint64_t*)cols[5].p;
+  out->group_of_row = (const uint64_t*)cols[6].p;
+  return HMJ_OK;
 }
 
 }  // namespace

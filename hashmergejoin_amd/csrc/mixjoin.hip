@@ -14,6 +14,9 @@
 // as strjoin.hip does (bytes_cmp: aligned 8-byte loads that never leave the words holding key bytes).
 // NULL-equals-NULL matching (HMJ_NULL_EQUAL with a bitmap): mix_key_kernel<false, true> keys every row, and the sequence
 // runs on MixNeSide / MixNePolicy, whose key_eq / key_cmp read the bitmaps before any value, length or byte.
+// Grouping (hmj_group_mixed_device): one relation's {key64, row} rows from mix_key_kernel<false, NE>, then hmj_group.h's
+// group_rows on MixSide (no bitmap) / MixNeSide (some column has one), with MixGroupCheck reading the key kernel's verdict on
+// the offsets back before any kernel compares tuples (DESIGN.md "Grouping rows by string and mixed keys").
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -22,6 +25,7 @@
 #include <type_traits>
 
 #include "hmj_tuplejoin.h"
+#include "hmj_group.h"
 #include "hmj_strkey.h"
 
 namespace {
@@ -457,6 +461,37 @@ MixSide side_of(const hmj_mixed_rel* r, ColValid* V, bool* any) {
   return A;
 }
 
+// ---- grouping (hmj_group_mixed_device; kernels and the driver, group_rows: hmj_group.h) ------------------------------------
+constexpr KeyJoinNames kGroupNames{"mixed-key grouping", "key64", "tuples"};
+
+// group_rows' Check for this key shape: the key kernel's report on the one relation, laid out as MixPolicyT lays out a
+// relation's (kErrWords offset-error words, preset as keys_begin presets them; NE: kNullWords behind them).  key_eq / key_cmp
+// follow a string column's offsets into its chars, so decreasing offsets must end the call before any of them runs.
+template <bool NE>
+struct MixGroupCheck {
+  static constexpr int kWords = kErrWords + (NE ? kNullWords : 0);
+  int begin(hmj_ctx* c, u64* e) const {  // (group_rows cleared the words)
+    HIP_TRY(hipMemsetAsync(e, 0xFF, kMaxCols * sizeof(u64), c->stream));
+    return HMJ_OK;
+  }
+  int check(hmj_ctx* c, const u64* e, hmj_group_opts* o) const {
+    char msg[192];
+    for (int k = 0; k < kMaxCols; k++) {  // the lowest-numbered column first, keys_check's wording
+      if (e[k] != kNone) {
+        std::snprintf(msg, sizeof(msg), "grouped relation: column %d: offsets decrease at row %llu (offsets[%llu] < offsets[%llu])", k,
+                      (unsigned long long)e[k], (unsigned long long)e[k] + 1, (unsigned long long)e[k]);
+        return fail(c, HMJ_E_ARG, msg);
+      }
+      if (e[kMaxCols + k]) {
+        std::snprintf(msg, sizeof(msg), "grouped relation: column %d: data is NULL but keys have bytes", k);
+        return fail(c, HMJ_E_ARG, msg);
+      }
+    }
+    if (NE) o->n_null = null_rows_of(e + kErrWords);
+    return HMJ_OK;
+  }
+};
+
 }  // namespace
 
 extern "C" {
@@ -530,6 +565,70 @@ int hmj_join_mixed_device(hmj_ctx* c, const hmj_mixed_rel* build, const hmj_mixe
     } else {
       o.ms_emit = elapsed(ev, 3, 4);
       o.ms_order = elapsed(ev, 4, 5);
+    }
+  }
+  const uint32_t room = opts->struct_size < sizeof(o) ? opts->struct_size : (uint32_t)sizeof(o);
+  o.struct_size = opts->struct_size;
+  std::memcpy(opts, &o, room);
+  return HMJ_OK;
+}
+
+int hmj_group_mixed_device(hmj_ctx* c, const hmj_mixed_rel* rel, uint32_t flags, hmj_group_opts* opts, hmj_group_result* out) {
+  if (!c) return HMJ_E_ARG;
+  if (!opts || !out) return fail(c, HMJ_E_ARG, "opts / out is NULL");
+  if (opts->struct_size < offsetof(hmj_group_opts, validity) + sizeof(opts->validity))
+    return fail(c, HMJ_E_ARG, "hmj_group_opts.struct_size too small");
+  if (opts->hash_bits > 63) return fail(c, HMJ_E_ARG, "hash_bits > 63");
+  if (flags & HMJ_FIRST_WINS) return fail(c, HMJ_E_ARG, "HMJ_FIRST_WINS is not defined for grouping");
+  if (flags & HMJ_CHECKSUM) return fail(c, HMJ_E_ARG, "HMJ_CHECKSUM is not defined for grouping");
+  if (flags & HMJ_SUM_PROBE) return fail(c, HMJ_E_ARG, "HMJ_SUM_PROBE is not defined for grouping");
+  const uint32_t all = HMJ_GROUP_COUNT | HMJ_GROUP_SUM | HMJ_GROUP_MIN | HMJ_GROUP_MAX | HMJ_GROUP_ROW_MAP;
+  if (opts->want & ~all) return fail(c, HMJ_E_ARG, "hmj_group_opts.want has unknown bits");
+  if (opts->reserved) return fail(c, HMJ_E_ARG, "hmj_group_opts.reserved must be 0");
+  if (opts->validity) return fail(c, HMJ_E_ARG, "hmj_group_opts.validity must be NULL for mixed keys: the bitmaps are in the columns");
+  RC_TRY(check_mixed_rel(c, rel, "grouped"));
+  ColValid V;
+  bool any = false;
+  const MixSide A = side_of(rel, &V, &any);
+  if (flags & HMJ_ORDERED) flags |= HMJ_MATERIALIZE;  // (HMJ_NULL_EQUAL: implied, ignored)
+  const bool mat = flags & HMJ_MATERIALIZE;
+  std::memset(out, 0, sizeof(*out));
+  HIP_TRY(hipSetDevice(c->device));
+  c->prep.valid = false;  // like any other call, this one discards a prepared build side
+  // the out fields of opts go to a full-size copy first; the caller gets the prefix its struct_size holds
+  hmj_group_opts o;
+  std::memset(&o, 0, sizeof(o));
+  std::memcpy(&o, opts, opts->struct_size < sizeof(o) ? opts->struct_size : sizeof(o));
+  o.n_null = o.n_collisions = 0;
+  o.ms_key = o.ms_sort = o.ms_groups = o.ms_agg = 0.f;
+  o.form = HMJ_COLS_HASHED;  // (force_hashed: ignored)
+  const u32 bits = o.hash_bits;
+  const u64 n = rel->n;
+  out->n_rows = n;
+  if (n) {
+    const dim3 G((u32)blocks_of(n)), T(MK_THREADS);
+    if (any) {
+      const MixNeSide N{A, V};
+      auto key = [&](hmj_ctx* c, u64* rows, u64* acc) {
+        hipLaunchKernelGGL((mix_key_kernel<false, true>), G, T, 0, c->stream, N.s, N.v, n, bits, rows, nullptr, 0ull, nullptr, 0, acc, acc + GA_N);
+        HIP_TRY(hipGetLastError());
+        return (int)HMJ_OK;
+      };
+      RC_TRY(group_rows(c, kGroupNames, N, n, true, mat, key, MixGroupCheck<true>{}, &o, out));
+    } else {
+      auto key = [&](hmj_ctx* c, u64* rows, u64* acc) {
+        hipLaunchKernelGGL(mix_key_kernel<false>, G, T, 0, c->stream, A, ColValid{}, n, bits, rows, nullptr, 0ull, nullptr, 0, acc, acc + GA_N);
+        HIP_TRY(hipGetLastError());
+        return (int)HMJ_OK;
+      };
+      RC_TRY(group_rows(c, kGroupNames, A, n, true, mat, key, MixGroupCheck<false>{}, &o, out));
+    }
+    if (c->profiling) {
+      (void)hipStreamSynchronize(c->stream);
+      o.ms_key = elapsed(c->grp_ws.ev, 0, 1);
+      o.ms_sort = elapsed(c->grp_ws.ev, 1, 2);
+      o.ms_groups = elapsed(c->grp_ws.ev, 2, 3);
+      o.ms_agg = elapsed(c->grp_ws.ev, 3, 4);
     }
   }
   const uint32_t room = opts->struct_size < sizeof(o) ? opts->struct_size : (uint32_t)sizeof(o);

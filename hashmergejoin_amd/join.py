@@ -575,6 +575,27 @@ class Executor:
         the kind does not produce (r_row / rval of probe SEMI / ANTI, s_row / sval of BUILD_SEMI / BUILD_ANTI) reads as 0."""
         return self.cols_kind_rows_to_numpy(res)
 
+    # ---- grouping rows by string and mixed keys (hmj_group_mixed_device) ----------------------------------
+    def group_mixed_device(self, cols, vals=None, valid=None, flags=0, want=_lib.HMJ_GROUP_COUNT, hash_bits=0):
+        """Group the rows of one device relation by a key tuple of string and fixed-width columns (hmj_group_mixed_device):
+        GROUP BY / DISTINCT with NULLs of a column forming one group, a NULL string not being the empty string.  cols, vals
+        and valid as `join_mixed_device` takes one side's; flags and want as for `group_cols_device`.  The key is always
+        hashed.  Returns (GroupResult, {"form", "n_null", "n_collisions", "ms_key", "ms_sort", "ms_groups", "ms_agg"}); read
+        the columns with `group_rows_to_numpy`, reproduce them with `expected_mixed_groups`."""
+        self._sync_stream()
+        rel, keep = self._mixed_rel(cols, vals, valid, "grouped")
+        opts = _lib.GroupOpts()
+        opts.struct_size = C.sizeof(_lib.GroupOpts)
+        opts.want = int(want)
+        opts.hash_bits = int(hash_bits)
+        res = _lib.GroupResult()
+        self._check(self.L.hmj_group_mixed_device(self.h, C.byref(rel), flags, C.byref(opts), C.byref(res)))
+        del keep
+        info = {"form": int(opts.form), "n_null": int(opts.n_null), "n_collisions": int(opts.n_collisions)}
+        for k in ("ms_key", "ms_sort", "ms_groups", "ms_agg"):
+            info[k] = float(getattr(opts, k))
+        return res, info
+
     # ---- columns through a row map (hmj_take_cols_device) ------------------------------------------------
     def take_cols_device(self, cols, row_map, valid=None, n_out=None, want_validity=True):
         """Take fixed-width columns of one relation through a row map (hmj_take_cols_device): output row i is source row
@@ -1116,18 +1137,29 @@ def expected_groups(columns, widths, vals=None, valid=None, hash_bits=0, force_h
         v = a.astype(np.uint64) & np.uint64((1 << (8 * w)) - 1)
         canon[:, 2 * c] = nulls[c]
         canon[:, 2 * c + 1] = np.where(nulls[c], np.uint64(0), v)
+    return _group_table(canon, key64, _group_payloads(vals, n), nulls, hashed, ordered)
+
+
+def _group_payloads(vals, n):
+    """`vals` of expected_groups / expected_mixed_groups -> the n payloads as uint64."""
     if vals is None:
-        pay = np.arange(n, dtype=np.uint64)
-    else:
-        pay = np.asarray(vals)
-        if pay.dtype.kind == "i":
-            pay = pay.astype(np.int64).view(np.uint64)
-        elif pay.dtype.kind == "u":
-            pay = pay.astype(np.uint64)
-        else:  # Python integers beyond int64
-            pay = np.array([int(x) & 0xFFFFFFFFFFFFFFFF for x in pay.ravel()], np.uint64)
-        if len(pay) != n:
-            raise ValueError("vals: one payload per row")
+        return np.arange(n, dtype=np.uint64)
+    pay = np.asarray(vals)
+    if pay.dtype.kind == "i":
+        pay = pay.astype(np.int64).view(np.uint64)
+    elif pay.dtype.kind == "u":
+        pay = pay.astype(np.uint64)
+    else:  # Python integers beyond int64
+        pay = np.array([int(x) & 0xFFFFFFFFFFFFFFFF for x in pay.ravel()], np.uint64)
+    if len(pay) != n:
+        raise ValueError("vals: one payload per row")
+    return pay
+
+
+def _group_table(canon, key64, pay, nulls, hashed, ordered):
+    """The result dict of expected_groups / expected_mixed_groups from the canonical tuples: canon [n, 2k] uint64, per
+    column (is NULL, a number that orders and equals as the column's values do, 0 under a NULL slot)."""
+    n, k = canon.shape[0], canon.shape[1] // 2
     out = {"form": _lib.HMJ_COLS_HASHED if hashed else _lib.HMJ_COLS_PACKED, "n_rows": n,
            "n_null": int(np.count_nonzero(np.any(np.stack(nulls), axis=0))) if k and n else 0}
     empty = np.zeros(0, np.uint64)
@@ -1204,6 +1236,33 @@ def mixed_key64(columns, hash_bits=0, valid=None, null_equal=False):
         for v in vs:
             h = _mix64(h + v + np.uint64(0x9E3779B97F4A7C15))
     return h >> np.uint64(64 - int(hash_bits)) if hash_bits else h
+
+
+def expected_mixed_groups(columns, vals=None, valid=None, hash_bits=0, ordered=False):
+    """What hmj_group_mixed_device returns (include/hmj.h), restated on the host.  columns as `mixed_key64` takes them: a
+    numpy integer array per fixed-width column, a list of `bytes` per string column (None is fine under a NULL slot);
+    vals / valid / ordered as for `expected_groups`.  The form is always hashed and key64 is `mixed_key64(columns,
+    hash_bits, valid, null_equal=True)`.  Two rows are one group when in every column both slots are NULL or both are
+    valid and equal (strings: length and bytes; a NULL string is not the empty string); what lies under a NULL slot is not
+    read.  Returns `expected_groups`' dict, "max_mixed_run" included.  ordered: ascending by (key64, the tuple column by
+    column, NULLS LAST per column): fixed columns as unsigned integers, strings as Python orders `bytes`, which is
+    std::string::operator<."""
+    k = len(columns)
+    n = len(columns[0]) if k else 0
+    nulls = _null_masks(valid, k, n)
+    key64 = mixed_key64(columns, hash_bits, valid, null_equal=True) if k else np.zeros(0, np.uint64)
+    canon = np.zeros((n, 2 * k), np.uint64)
+    for c, col in enumerate(columns):
+        if isinstance(col, np.ndarray):
+            a = np.ascontiguousarray(col)
+            v = a.view("u%d" % a.dtype.itemsize).astype(np.uint64)
+        else:  # a string's number: its rank among the column's distinct valid strings in bytes order
+            slots = [b"" if (nulls[c][i] or b is None) else bytes(b) for i, b in enumerate(col)]
+            rank = {b: r for r, b in enumerate(sorted(set(slots)))}
+            v = np.array([rank[b] for b in slots], np.uint64)
+        canon[:, 2 * c] = nulls[c]
+        canon[:, 2 * c + 1] = np.where(nulls[c], np.uint64(0), v)
+    return _group_table(canon, key64, _group_payloads(vals, n), nulls, True, ordered)
 
 
 def _memcpy_d2d(torch, dst_tensor, src_ptr, nbytes):

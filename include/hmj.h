@@ -922,7 +922,8 @@ int hmj_join_mixed_device(hmj_ctx* ctx, const hmj_mixed_rel* build, const hmj_mi
  * payloads by a segmented scan inside each wave, finishing a group that crosses the 512 positions a wave walks with one
  * atomic per wave.  Everything runs on the ctx stream in a workspace of the entry's own; the host reads back the
  * mismatch count, n_groups and one counter block.  hmj_last_plan / hmj_last_timing are left as they were.
- * Out of scope: string and mixed keys, several value columns per call, signed and float aggregates, the exchange path. */
+ * String and mixed keys: hmj_group_mixed_device below.
+ * Out of scope: several value columns per call, signed and float aggregates, the exchange path.                        */
 #define HMJ_GROUP_COUNT   0x01u  /* out->count                                                                         */
 #define HMJ_GROUP_SUM     0x02u  /* out->sum: wrapping u64 sum of the payloads                                          */
 #define HMJ_GROUP_MIN     0x04u  /* out->min: unsigned                                                                  */
@@ -948,6 +949,41 @@ typedef struct {
 } hmj_group_result;
 int hmj_group_cols_device(hmj_ctx* ctx, const hmj_cols_rel* rel, uint32_t flags, hmj_group_opts* opts,
                           hmj_group_result* out);
+
+/* ---- grouping rows by string and mixed keys ------------------------------------------------------------ */
+/* hmj_group_cols_device on ONE relation of hmj_join_mixed_device's shape: any mix of HMJ_KEY_FIXED and
+ * HMJ_KEY_LARGE_STRING key columns (strings only and fixed columns only included), validity in the columns, rel->vals the
+ * one value column: GROUP BY name; SELECT DISTINCT name, day; COUNT(*) per string foreign key.  hmj_group_opts and
+ * hmj_group_result are reused unchanged; no struct, flag or path bit is new.
+ * Everything the header text of hmj_group_cols_device says holds here -- outputs, want bits, first_row, aggregates, n == 0,
+ * the flags refused, HMJ_NULL_EQUAL accepted and ignored, result lifetime, hmj_last_plan / hmj_last_timing left as they
+ * were, a prepared build side discarded -- with these points changed:
+ * Grouping rule: in every column both slots NULL, or both valid and equal: a fixed column bit for bit, a string column in
+ * length and bytes (NUL and bytes >= 0x80 being ordinary bytes).  A NULL string is not the empty string.  Chars and fixed
+ * values under a NULL slot are never read; the offsets under a NULL slot must still be non-decreasing.
+ * key64 and form: always hashed -- opts->form is HMJ_COLS_HASHED, opts->force_hashed is ignored.  key64 is
+ * hmj_join_mixed_device's under HMJ_NULL_EQUAL: the plain mixed chain for a row without NULL slots, v_c = 0 for a NULL
+ * slot and the NULL-column mask step for a row with one, hash_bits last.  For a relation of fixed columns only that is
+ * hmj_group_cols_device's hashed key64, and every output equals that entry's with force_hashed.
+ * opts->validity must be NULL (the bitmaps are hmj_mixed_col.validity).
+ * HMJ_ORDERED: ascending by (key64, the tuple column by column, NULLS LAST in each column): fixed columns as unsigned
+ * integers, string columns as std::string::operator< (unsigned bytes, then length).
+ * HMJ_E_ARG (hmj_last_error names what was wrong): what hmj_group_cols_device rejects in opts and flags; non-NULL
+ * opts->validity; everything hmj_join_mixed_device rejects for one relation (the messages name the "grouped" relation);
+ * key bytes under data == NULL; decreasing offsets, the message naming the lowest-numbered offending column and its first
+ * offending row in hmj_join_mixed_device's wording.  The last two are found by the key kernel; the host reads its verdict
+ * back behind the sort of the {key64, row} rows and before any kernel follows an offset into chars.  The ctx stays usable.
+ * HMJ_E_UNSUPPORTED: hmj_group_cols_device's 1024-row and 2^22 limits, in every mode.
+ * The result lives in hmj_group_cols_device's workspace: either group call replaces the other's result;
+ * hmj_take_cols_device and hmj_take_str_device keep it, and a take of a string key column through first_row is the
+ * DISTINCT table.
+ * How (DESIGN.md "Grouping rows by string and mixed keys"): mix_key_kernel's dense forms write the rows, and the sequence
+ * of hmj_group_cols_device runs on the mixed join's key policies (MixSide; MixNeSide where a column has a bitmap).  One
+ * round trip more than the column entry: the key kernel's verdict.
+ * Out of scope: 32-bit-offset `string` columns, several value columns per call, signed and float aggregates, the exchange
+ * path, a sort-free path for few groups.                                                                               */
+int hmj_group_mixed_device(hmj_ctx* ctx, const hmj_mixed_rel* rel, uint32_t flags, hmj_group_opts* opts,
+                           hmj_group_result* out);
 
 /* ---- taking fixed-width columns through a row map (Arrow validity out) --------------------------------- */
 /* The joins above return gather maps (r_row / s_row), not columns.  This entry turns a map back into Arrow columns: up to
