@@ -482,10 +482,7 @@ struct ColNePolicy {
   static constexpr int kMemoPairs = ColPolicy::kMemoPairs;
   static const KeyJoinNames& names() { return kNames; }
   static KeyJoinWs& ws(hmj_ctx* c) { return c->col_ws; }
-  static int keys_begin(hmj_ctx* c) {
-    HIP_TRY(hipMemsetAsync(tuple_acc_extra<ColNePolicy>(c), 0, kAccExtra * sizeof(u64), c->stream));
-    return HMJ_OK;
-  }
+  static int keys_begin(hmj_ctx*) { return HMJ_OK; }  // (the driver cleared the counts)
   static int keys_check(hmj_ctx* c, TupleCall* call) {
     u64 nn[kAccExtra];
     RC_TRY(read_back(c, tuple_acc_extra<ColNePolicy>(c), nn, sizeof(nn)));

@@ -25,15 +25,16 @@ struct HostBuf {
   bool pinned = true;  // false: pageable memory on transparent huge pages (the result columns)
 };
 
-// Workspace of one of the joins on {key64, row} rows (hmj_keyjoin.h; key64: the string join's hash, the multi-column
-// join's packed tuple or hash, the mixed-key join's hash).
+// Workspace of one of the joins on {key64, row} rows, all three of them run by hmj_tuplejoin.h's driver on hmj_keyjoin.h's
+// kernels (key64: the string join's hash, the multi-column join's packed tuple or hash, the mixed-key join's hash).
 struct KeyJoinWs {
   DevBuf rows_r, rows_s,           // {key64, row} rows of both relations
       flags, blk, blk_off,         // pass-1 ballots, per-workgroup survivors and their offsets
-      list, runs, acc,             // the collision search's rows and runs, the counters
+      list, runs, acc,             // the collision search's rows and runs; the counters: the driver's three blocks (keys,
+                                   // verification and collisions / probe sweep / build sweep), then the policy's report words
       mark_r, mark_s, amb,         // join kinds: one mark byte per row of each relation, the rows whose representative's key differed
-      cmp_r, cmp_s, vblk,          // validity bitmaps only: the compacted {key64, row} rows of the rows that have a key, the valid
-                                   // rows per workgroup of both relations and their offsets
+      cmp_r, cmp_s, vblk,          // validity bitmaps only: the compacted {key64, row} rows of the rows that have a key (room for
+                                   // every row of the relation), the valid rows per workgroup of both relations and their offsets
       key, rrow, srow, rval, sval, // the five result columns (the multi-column join's packed form fills rval / sval only)
       ord, kkey, krrow, ksrow, krval, ksval;  // ordered kinds: (key64, index) rows and their sorted copy, the result columns in sorted order
   hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // phase boundaries (profiling)

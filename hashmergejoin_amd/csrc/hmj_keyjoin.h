@@ -38,10 +38,10 @@ constexpr u64 kListCap = 1ull << 22;  // mismatching adjacent rows the collision
 constexpr u64 kNoRow = ~0ull;
 static_assert(kNoRow == HMJ_STR_NO_ROW && kNoRow == HMJ_COLS_NO_ROW, "one marker for a row without a partner");
 
-// One accumulator block (u64 slots; a call owns several and says which one a stage adds to): [0] first row with decreasing
-// offsets (~0 = none) and [1] keys with bytes but chars == NULL (string hashing), [2] mismatch list length, [3] error bits
-// (1 = a mixed run beyond kRunCap, 2 = list overflow), [4] ambiguous rows and [5] pairs whose keys differ (join kinds),
-// [6] sum of the probe payloads (multi-column key kernels), [8..15] ACC_* sums
+// One accumulator block (u64 slots; a call owns several and says which one a stage adds to): [2] mismatch list length,
+// [3] error bits (1 = a mixed run beyond kRunCap, 2 = list overflow), [4] ambiguous rows and [5] pairs whose keys differ
+// (join kinds), [6] sum of the probe payloads (key kernels), [8..15] ACC_* sums.  [0] and [1] index the string hash kernels'
+// report words of one relation instead: first row with decreasing offsets (~0 = none), keys with bytes but chars == NULL
 enum { KA_BAD_ROW = 0, KA_NULL_CHARS, KA_LIST_N, KA_ERR, KA_AMB_N, KA_DIFF, KA_SUM_P, KA_ACC = 8, KA_N = 16 };
 
 // What a caller's error messages call itself, its key64 and its keys.
@@ -696,9 +696,8 @@ int kind_order(hmj_ctx* c, KeyJoinWs& ws, KindRows& k, const Side& R, const Side
 
 // What a kind call reports once its acc blocks are back on the host (av / ap / ab: the KA_ACC sums of the pairs, the probe
 // sweep and the build sweep): the result's count, sums and columns, and the counters the u64 entry of the kind fills.
-// Res: hmj_str_result / hmj_cols_result; its key64 column is set by the caller.
-template <class Res>
-void kind_report(KindRows& k, const u64* av, const u64* ap, const u64* ab, Res* out, hmj_kind_counts* counts) {
+// The result's key64 column is set by the caller.
+void kind_report(KindRows& k, const u64* av, const u64* ap, const u64* ab, hmj_cols_result* out, hmj_kind_counts* counts) {
   // the sweeps count their rows in their acc blocks; the pairs: the scan (materialising) or acc (count modes)
   const u64 n_p = ap[hmj::ACC_N], n_b = ab[hmj::ACC_N];
   if (!k.mat) k.n_in = av[hmj::ACC_N];

@@ -1,7 +1,8 @@
-// The driver of the joins whose key is a TUPLE of columns: the multi-column join of fixed-width columns (coljoin.hip) and
-// the mixed-key join of string and fixed-width columns (mixjoin.hip).  Both turn every row into a {key64, row} row, run the
-// u64 join on those rows and finish on hmj_keyjoin.h's kernels; tuple_join (the inner join) and tuple_join_kind (the join
-// kinds) are that sequence once, as templates over a policy P the including file defines:
+// The driver of the keyed joins: the string-key join (strjoin.hip, a tuple of one string column), the multi-column join of
+// fixed-width columns (coljoin.hip) and the mixed-key join of string and fixed-width columns (mixjoin.hip).  All three turn
+// every row into a {key64, row} row, run the u64 join on those rows and finish on hmj_keyjoin.h's kernels; tuple_join (the
+// inner join) and tuple_join_kind (the join kinds) are that sequence once, as templates over a policy P the including file
+// defines:
 //   P::Side                    the relation-side struct with its key_eq / key_cmp / payload overloads (hmj_keyjoin.h)
 //   P::kCanPack                the key may be the packed tuple itself (the call says so: TupleCall::hashed == false)
 //   P::kAccExtra               u64 words the key kernels own behind the call's accumulator blocks (tuple_acc_extra)
@@ -9,12 +10,15 @@
 //   P::names() / P::ws(c)      what error messages call the join; the workspace of the entry
 //   P::key(c, A, rel, n, call, out, sum_probe, acc)                          {key64,row} rows of a relation without bitmaps
 //   P::key_valid(c, A, V, rel, n, call, nblk, dense, comp, cap, off, sum_probe, acc)   ... of one with bitmaps (pass 2)
-//   P::keys_begin(c) / P::keys_check(c, call)   before the first key kernel / behind the last: where a key kernel that checks
-//                                         its input (string offsets) reports, and where the NULL-equals-NULL key kernels'
-//                                         counts of rows with NULL slots reach call->n_*_null; the plain fixed-width
-//                                         policy does nothing in either
+//   P::keys_begin(c) / P::keys_check(c, call)   before the first key kernel (the call's blocks and P's words are zero:
+//                                         presets the words that start elsewhere) / behind the last: where a key kernel
+//                                         that checks its input (string offsets) reports, and where the NULL-equals-NULL
+//                                         key kernels' counts of rows with NULL slots reach call->n_*_null; the plain
+//                                         fixed-width policy does nothing in either
 //   P::gather(...)             kCanPack only: the packed form's payload gather
-// Also here: what both key kernels share -- col_load, the per-column validity bitmaps (ColValid / row_valid, and for the
+// A relation with bitmaps is keyed in one sequence for every policy (launch_key_valid: count, scan, key_valid with room for
+// every row; keys_end reads the valid-row totals once, behind the key phase).
+// Also here: what the key kernels share -- col_load, the per-column validity bitmaps (ColValid / row_valid, and for the
 // NULL-equals-NULL policies slot_null / wave_valid_word), kGolden.
 // Internal header: its contents are local to the file that includes it.
 #pragma once
@@ -107,46 +111,47 @@ struct TupleCall {
   hmj_kind_counts counts{};
 };
 
-// the words P's key kernels own in the workspace's accumulator: behind the blocks every call clears
+// the words P's key kernels own in the workspace's accumulator: behind the call's blocks, cleared with them
 template <class P>
 u64* tuple_acc_extra(hmj_ctx* c) {
   return (u64*)P::ws(c).acc.p + kKindAccBlocks * KA_N;
 }
+template <class P>
+constexpr size_t tuple_acc_bytes() {
+  return (kKindAccBlocks * KA_N + P::kAccExtra) * sizeof(u64);
+}
 
 // The {key64,row} rows of one relation (rel: 0 build, 1 probe) in a call with bitmaps.  dense: the relation's row-indexed
-// rows (NULL: not wanted); *rows / *n_valid: what the u64 joins take.  A relation with a bitmap: its valid rows counted per
-// workgroup (vblk: nblk counts, then nblk + 1 offsets), the total read back, the valid rows compacted into cmp.  A relation
-// without one goes through P::key as always, and its dense rows are its join rows.
+// rows (NULL: not wanted); *rows: what the u64 joins take; *tot: where on the device the number of those rows stands (NULL:
+// every row).  A relation with a bitmap: its valid rows counted per workgroup (vblk: nblk counts, then nblk + 1 offsets) and
+// compacted into cmp, which has room for every row: nothing is read back between the passes (keys_end fetches the totals).
+// A relation without one goes through P::key as always, and its dense rows are its join rows.
 template <class P>
 int launch_key_valid(hmj_ctx* c, const typename P::Side& A, const ColValid& V, bool has, int rel, u64 n, const TupleCall& call, u64* dense,
-                     u64* plain, DevBuf& cmp, u64* vblk, bool sum_probe, u64* acc, const void** rows, u64* n_valid) {
+                     u64* plain, DevBuf& cmp, u64* vblk, bool sum_probe, u64* acc, const void** rows, const u64** tot) {
   *rows = plain;
-  *n_valid = n;
+  *tot = nullptr;
   if (!has || !n) return P::key(c, A, rel, n, call, plain, sum_probe, acc);
   const u64 nblk = blocks_of(n);
   char msg[96];
   std::snprintf(msg, sizeof(msg), "%s: too many rows", P::names().join);
   if (nblk > 0xFFFFFFFFull) return fail(c, HMJ_E_ARG, msg);
   u64 *cnt = vblk, *off = vblk + nblk;
+  RC_TRY(ensure_dev(c, cmp, 16 * n));
   hipLaunchKernelGGL(valid_count_kernel<ColValid>, dim3((u32)nblk), dim3(KJ_THREADS), 0, c->stream, V, n, cnt);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hmj::launch_scan_u64(cnt, off, (u32)nblk, c->stream));
-  u64 nv = 0;
-  RC_TRY(read_back(c, off + nblk, &nv, sizeof(u64)));
-  std::snprintf(msg, sizeof(msg), "%s: more valid rows counted than the relation holds", P::names().join);
-  if (nv > n) return fail(c, HMJ_E_HIP, msg);
-  RC_TRY(ensure_dev(c, cmp, 16 * (nv ? nv : 1)));
-  RC_TRY(P::key_valid(c, A, V, rel, n, call, nblk, dense, (u64*)cmp.p, nv, (const u64*)off, sum_probe, acc));
+  RC_TRY(P::key_valid(c, A, V, rel, n, call, nblk, dense, (u64*)cmp.p, n, (const u64*)off, sum_probe, acc));
   *rows = cmp.p;
-  *n_valid = nv;
+  *tot = off + nblk;
   return HMJ_OK;
 }
 
 // Both relations' {key64,row} rows in a call with bitmaps (the block counts of both sides share vblk).
 template <class P>
 int launch_keys_valid(hmj_ctx* c, const typename P::Side& RS, const typename P::Side& SS, const ColValid* VB, const ColValid* VP, u64 nb,
-                      u64 np, const TupleCall& call, bool dense, bool sum_probe, u64* acc, const void** rows_r, u64* nvb,
-                      const void** rows_s, u64* nvp) {
+                      u64 np, const TupleCall& call, bool dense, bool sum_probe, u64* acc, const void** rows_r, const u64** tot_b,
+                      const void** rows_s, const u64** tot_p) {
   KeyJoinWs& ws = P::ws(c);
   const u64 kb = VB ? blocks_of(nb) : 0, kp = VP ? blocks_of(np) : 0;
   RC_TRY(ensure_dev(c, ws.vblk, (2 * (kb + kp) + 2) * sizeof(u64)));
@@ -154,9 +159,28 @@ int launch_keys_valid(hmj_ctx* c, const typename P::Side& RS, const typename P::
   const ColValid none{};
   u64 *plain_r = (u64*)ws.rows_r.p, *plain_s = (u64*)ws.rows_s.p;
   RC_TRY(launch_key_valid<P>(c, RS, VB ? *VB : none, VB != nullptr, 0, nb, call, dense ? plain_r : nullptr, plain_r, ws.cmp_r, vblk,
-                             false, acc, rows_r, nvb));
+                             false, acc, rows_r, tot_b));
   RC_TRY(launch_key_valid<P>(c, SS, VP ? *VP : none, VP != nullptr, 1, np, call, dense ? plain_s : nullptr, plain_s, ws.cmp_s,
-                             vblk + 2 * kb + 1, sum_probe, acc, rows_s, nvp));
+                             vblk + 2 * kb + 1, sum_probe, acc, rows_s, tot_p));
+  return HMJ_OK;
+}
+
+// Behind the key phase: P's verdict on its input, then -- a call with bitmaps (tot_b / tot_p as launch_key_valid left
+// them) -- the rows of each relation that have a key, into *nvb / *nvp and call->n_*_null.  The totals' copies are queued
+// in front of keys_check, so a policy that reads its report words back fetches them in the same synchronisation.
+template <class P>
+int keys_end(hmj_ctx* c, TupleCall* call, bool bitmaps, const u64* tot_b, const u64* tot_p, u64 nb, u64 np, u64* nvb, u64* nvp) {
+  if (tot_b) HIP_TRY(hipMemcpyAsync(nvb, tot_b, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  if (tot_p) HIP_TRY(hipMemcpyAsync(nvp, tot_p, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  const int rc = P::keys_check(c, call);
+  if (tot_b || tot_p) HIP_TRY(hipStreamSynchronize(c->stream));  // (the totals are on the host whatever keys_check did)
+  RC_TRY(rc);
+  if (!bitmaps) return HMJ_OK;
+  char msg[96];
+  std::snprintf(msg, sizeof(msg), "%s: more valid rows counted than the relation holds", P::names().join);
+  if (*nvb > nb || *nvp > np) return fail(c, HMJ_E_HIP, msg);
+  call->n_build_null = nb - *nvb;
+  call->n_probe_null = np - *nvp;
   return HMJ_OK;
 }
 
@@ -171,27 +195,26 @@ int tuple_join(hmj_ctx* c, const typename P::Side& RS, u64 nb, const typename P:
   const bool mat = flags & HMJ_MATERIALIZE, ordered = flags & HMJ_ORDERED, checksum = flags & HMJ_CHECKSUM;
   c->prep.valid = false;  // like any other call, the join discards a prepared build side
   KeyJoinWs& ws = P::ws(c);
-  RC_TRY(ensure_dev(c, ws.acc, (kKindAccBlocks * KA_N + P::kAccExtra) * sizeof(u64)));
+  RC_TRY(ensure_dev(c, ws.acc, tuple_acc_bytes<P>()));
   RC_TRY(ensure_dev(c, ws.rows_r, 16 * (nb ? nb : 1)));
   RC_TRY(ensure_dev(c, ws.rows_s, 16 * (np ? np : 1)));
   u64* acc = (u64*)ws.acc.p;
   u64 h[KA_N];
   // 1. {key64, row} rows of both relations (+ the probe payloads' sum)
   RC_TRY(record(c, ws.ev, 0));
-  HIP_TRY(hipMemsetAsync(acc, 0, KA_N * sizeof(u64), c->stream));
+  HIP_TRY(hipMemsetAsync(acc, 0, tuple_acc_bytes<P>(), c->stream));
   RC_TRY(P::keys_begin(c));
   const void *rows_r = ws.rows_r.p, *rows_s = ws.rows_s.p;  // the rows the u64 join takes
   u64 nvb = nb, nvp = np;                                   // ... and how many: the rows that have a key
+  const u64 *tot_b = nullptr, *tot_p = nullptr;
   if (!VB && !VP) {
     RC_TRY(P::key(c, RS, 0, nb, *call, (u64*)ws.rows_r.p, false, acc));
     RC_TRY(P::key(c, SS, 1, np, *call, (u64*)ws.rows_s.p, flags & HMJ_SUM_PROBE, acc));
   } else {  // NULL keys: only the rows that have a key are joined (the inner join walks no relation by row: no dense rows)
-    RC_TRY(launch_keys_valid<P>(c, RS, SS, VB, VP, nb, np, *call, false, flags & HMJ_SUM_PROBE, acc, &rows_r, &nvb, &rows_s, &nvp));
-    call->n_build_null = nb - nvb;
-    call->n_probe_null = np - nvp;
+    RC_TRY(launch_keys_valid<P>(c, RS, SS, VB, VP, nb, np, *call, false, flags & HMJ_SUM_PROBE, acc, &rows_r, &tot_b, &rows_s, &tot_p));
   }
   RC_TRY(record(c, ws.ev, 1));
-  RC_TRY(P::keys_check(c, call));
+  RC_TRY(keys_end<P>(c, call, VB || VP, tot_b, tot_p, nb, np, &nvb, &nvp));
   if (nvb == 0 || nvp == 0) {  // (nothing to join: no plan either)
     std::memset(&c->plan, 0, sizeof(c->plan));
     c->plan.struct_size = sizeof(c->plan);
@@ -303,7 +326,7 @@ int tuple_join_kind(hmj_ctx* c, const typename P::Side& RS, u64 nb, const typena
   std::memset(&c->plan, 0, sizeof(c->plan));
   c->plan.struct_size = sizeof(c->plan);
   std::memset(&c->timing, 0, sizeof(c->timing));
-  RC_TRY(ensure_dev(c, ws.acc, (kKindAccBlocks * KA_N + P::kAccExtra) * sizeof(u64)));
+  RC_TRY(ensure_dev(c, ws.acc, tuple_acc_bytes<P>()));
   RC_TRY(ensure_dev(c, ws.rows_r, 16 * (nb ? nb : 1)));
   RC_TRY(ensure_dev(c, ws.rows_s, 16 * (np ? np : 1)));
   RC_TRY(ensure_dev(c, ws.mark_r, nb ? nb : 1));
@@ -314,23 +337,22 @@ int tuple_join_kind(hmj_ctx* c, const typename P::Side& RS, u64 nb, const typena
   unsigned char *mark_r = (unsigned char*)ws.mark_r.p, *mark_s = (unsigned char*)ws.mark_s.p;
   // 1. {key64, row} rows of both relations (+ the probe payloads' sum), marks cleared
   RC_TRY(record(c, ws.ev, 0));
-  HIP_TRY(hipMemsetAsync(acc, 0, kKindAccBlocks * KA_N * sizeof(u64), c->stream));
+  HIP_TRY(hipMemsetAsync(acc, 0, tuple_acc_bytes<P>(), c->stream));
   RC_TRY(P::keys_begin(c));
   // (NULL keys: the dense rows stay indexed by row for the sweeps; the u64 joins take only the rows that have a key)
   const void *rows_r = ws.rows_r.p, *rows_s = ws.rows_s.p;
   u64 nvb = nb, nvp = np;
+  const u64 *tot_b = nullptr, *tot_p = nullptr;
   if (!VB && !VP) {
     RC_TRY(P::key(c, RS, 0, nb, *o, (u64*)ws.rows_r.p, false, acc));
     RC_TRY(P::key(c, SS, 1, np, *o, (u64*)ws.rows_s.p, flags & HMJ_SUM_PROBE, acc));
   } else {
-    RC_TRY(launch_keys_valid<P>(c, RS, SS, VB, VP, nb, np, *o, true, flags & HMJ_SUM_PROBE, acc, &rows_r, &nvb, &rows_s, &nvp));
-    o->n_build_null = nb - nvb;
-    o->n_probe_null = np - nvp;
+    RC_TRY(launch_keys_valid<P>(c, RS, SS, VB, VP, nb, np, *o, true, flags & HMJ_SUM_PROBE, acc, &rows_r, &tot_b, &rows_s, &tot_p));
   }
   if (nb) HIP_TRY(hipMemsetAsync(mark_r, 0, nb, c->stream));
   if (np) HIP_TRY(hipMemsetAsync(mark_s, 0, np, c->stream));
   RC_TRY(record(c, ws.ev, 1));
-  RC_TRY(P::keys_check(c, o));
+  RC_TRY(keys_end<P>(c, o, VB || VP, tot_b, tot_p, nb, np, &nvb, &nvp));
   // 2. + 3. the {key64,row} join(s) and the tuple verification, which marks the rows that have a partner
   u64 n_pairs = 0;
   hmj_result inner;

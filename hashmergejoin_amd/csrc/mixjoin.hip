@@ -315,8 +315,7 @@ struct MixPolicyT {
   static KeyJoinWs& ws(hmj_ctx* c) { return c->mix_ws; }
   static u64* err_of(hmj_ctx* c, int rel) { return tuple_acc_extra<Self>(c) + rel * kRelWords; }
   static int keys_begin(hmj_ctx* c) {
-    u64* e = tuple_acc_extra<Self>(c);
-    HIP_TRY(hipMemsetAsync(e, 0, kAccExtra * sizeof(u64), c->stream));
+    u64* e = tuple_acc_extra<Self>(c);  // (the driver cleared the words)
     HIP_TRY(hipMemsetAsync(e, 0xFF, kMaxCols * sizeof(u64), c->stream));
     HIP_TRY(hipMemsetAsync(e + kRelWords, 0xFF, kMaxCols * sizeof(u64), c->stream));
     return HMJ_OK;

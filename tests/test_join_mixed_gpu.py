@@ -604,6 +604,31 @@ def test_argument_errors(H, ex):
     check(H, ex, B2, P2v, D2B, D2Pv, kinds=[(BUILD, FULL_OUTER)], tag=("after bad offsets, bitmaps",))
 
 
+@pytest.mark.parametrize("side,kind", [(PROBE, INNER), (BUILD, FULL_OUTER)])
+def test_bad_offsets_under_a_bitmap_then_the_right_ones(H, ex, side, kind):
+    """[str, u32], 600 rows a side, a bitmap on the probe relation's string column, its offsets decreasing at row 70: the
+    second wave of the first workgroup compacts nothing, so the two workgroups behind it compact in front of their places,
+    into an array that has room for every row.  Materialising, the call fails with HMJ_E_ARG naming relation, column and
+    row; the same call with the offsets put right, on the same context, is the brute force's."""
+    import torch
+
+    rng = random.Random(8070)
+    B, P = relations(rng, ["s", 4], 600, 600)
+    P.valid = draw_masks(np.random.default_rng(8070), P.n, 2, [0])
+    P.valid[0][70] = True
+    assert P.valid[0][256:].sum() > 64
+    DB, DP = dev(H, B), dev(H, P, bit_off=3)
+    chars, off = DP[0][0]
+    host = off.cpu().numpy().copy()
+    host[70] = host[71] + 3  # offsets[71] < offsets[70]
+    flags = H.HMJ_MATERIALIZE | H.HMJ_CHECKSUM | H.HMJ_SUM_PROBE
+    with pytest.raises(H.HmjError) as e:
+        ex.join_mixed_device(DB[0], DB[1], [(chars, torch.from_numpy(host).cuda()), DP[0][1]], DP[1], side, kind, flags, probe_fill=PFILL,
+                             build_fill=BFILL, probe_valid=DP[2])
+    assert e.value.code == HMJ_E_ARG and "probe relation: column 0: offsets decrease at row 70 " in str(e.value), str(e.value)
+    check(H, ex, B, P, DB, DP, kinds=[(side, kind)], modes=(flags,), tag=("offsets put right",))
+
+
 # ---- end to end: the key columns back through the row maps ---------------------------------------------------------------------
 def test_take_the_key_columns_back(H, ex):
     """Ordered FULL_OUTER on [str, i32] with NULLs; both key columns taken through r_row and s_row with hmj_take_str_device /

@@ -617,6 +617,34 @@ def test_errors_leave_the_ctx_usable(H, ex):
     good()
 
 
+@pytest.mark.parametrize("side,kind", [(PROBE, INNER), (BUILD, FULL_OUTER)])
+def test_bad_offsets_under_a_bitmap_then_the_right_ones(H, ex, side, kind):
+    """600 rows a side, a bitmap on the probe relation, its offsets decreasing at row 70: the second wave of the first
+    workgroup compacts nothing, so the two workgroups behind it compact in front of their places, into an array that has
+    room for every row.  Materialising, the call fails with HMJ_E_ARG naming the relation and the row; the same call with
+    the offsets put right, on the same context, is the brute force's."""
+    rng = random.Random(8070)
+    n = 600
+    bk, pk = drawn(rng, n, n)
+    bv, pv = payloads(rng, n), payloads(rng, n)
+    B, P = rel(H, bk, bv), rel(H, pk, pv)
+    mp = np.random.default_rng(8070).random(n) >= 0.3
+    mp[70] = True
+    assert mp[256:].sum() > 64
+    VP = dev_valid(H, mp, 3)
+    chars, offs, vals = P
+    bad = offs.clone()
+    bad[70] = bad[71] + 3  # offsets[71] < offsets[70]
+    flags = H.HMJ_MATERIALIZE | H.HMJ_CHECKSUM | H.HMJ_SUM_PROBE
+    with pytest.raises(H.HmjError) as e:
+        ex.join_kind_str_device(B, (chars, bad, vals), side, kind, flags, probe_fill=PFILL, build_fill=BFILL, probe_valid=VP)
+    assert e.value.code == HMJ_E_ARG, str(e.value)
+    assert "probe relation: offsets decrease at row 70 (offsets[71] < offsets[70])" in str(e.value), str(e.value)
+    bnull, pnull = np.zeros(n, bool), ~mp
+    expect = expect_all(bk, bv, pk, pv, bnull, pnull, kinds=[(side, kind)])
+    check(H, ex, B, P, None, VP, expect, pv, bnull, pnull, (flags,), tag=("offsets put right",))
+
+
 def test_inner_entry_routes_to_the_inner_kind(H, ex):
     rng = random.Random(8)
     nrng = np.random.default_rng(8)

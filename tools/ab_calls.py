@@ -10,6 +10,9 @@ identical files:
     HMJ_LIB=<parent .so> python tools/ab_calls.py parent.jsonl
     HMJ_LIB=<change .so> python tools/ab_calls.py change.jsonl   # a process each
     cmp parent.jsonl change.jsonl
+
+A second argument chooses the calls: `u64` (the u64 driver's plans), `keyed` (the string, column and mixed entries:
+keyed_section) or `all` (the default).
 """
 import ctypes as C
 import json
@@ -69,15 +72,19 @@ def column(ex, ptr, n, host):
 
 
 def rows_digest(ex, res, host, ordered):
-    """Null columns, a hash of the row set and (ordered) one of the row sequence (uint64 arithmetic wraps)."""
+    """Null columns, a hash of the row set and (ordered) one of the row sequence (uint64 arithmetic wraps).  A keyed join's
+    result has five columns: key64 (the string join's hash), r_row, s_row, rval, sval."""
     n = int(res.n_matches)
-    ptrs = (res.key, res.rval, res.sval)
+    if hasattr(res, "key"):
+        ptrs = (res.key, res.rval, res.sval)
+    else:
+        ptrs = (res.hash if hasattr(res, "hash") else res.key64, res.rval, res.sval, res.r_row, res.s_row)
     d = {"null_cols": [not p for p in ptrs]}
-    if n == 0 or not res.key:
+    if n == 0 or not ptrs[0]:
         return d
     with np.errstate(over="ignore"):
         h = np.zeros(n, np.uint64)
-        for p, mul in zip(ptrs, (0x9E3779B97F4A7C15, 0xC2B2AE3D27D4EB4F, 0x165667B19E3779F9)):
+        for p, mul in zip(ptrs, (0x9E3779B97F4A7C15, 0xC2B2AE3D27D4EB4F, 0x165667B19E3779F9, 0x27D4EB2F165667C5, 0x85EBCA77C2B2AE63)):
             if p:
                 h = (h ^ column(ex, p, n, host)) * np.uint64(mul)
                 h ^= h >> np.uint64(29)
@@ -87,8 +94,9 @@ def rows_digest(ex, res, host, ordered):
     return d
 
 
-def record(name, ex, fn, host=False, ordered=False, repeat=3):
-    """fn() -> JoinResult or (JoinResult, counters); an HmjError is part of the record."""
+def record(name, ex, fn, host=False, ordered=False, repeat=3, unstable_path=0):
+    """fn() -> JoinResult or (JoinResult, counters); an HmjError is part of the record.  unstable_path: HMJ_PATH_* bits left
+    out of the record (they differ between runs of ONE library)."""
     global n_records
     for i in range(repeat):
         rec = {"call": name, "i": i}
@@ -98,7 +106,7 @@ def record(name, ex, fn, host=False, ordered=False, repeat=3):
             rec["rc"] = 0
             rec.update({k: int(getattr(res, k)) for k in SUMS})
             if extra is not None:
-                rec["counts"] = extra
+                rec["counts"] = {k: v for k, v in extra.items() if not k.startswith("ms_")}
             rec.update(rows_digest(ex, res, host, ordered))
         except H.HmjError as e:
             rec["rc"] = e.code
@@ -106,6 +114,8 @@ def record(name, ex, fn, host=False, ordered=False, repeat=3):
         t = ex.last_timing()
         rec["timing"] = {k: int(t[k]) for k in TIMING}
         rec["plan"] = ex.last_plan()
+        rec["timing"]["path"] &= ~unstable_path
+        rec["plan"]["path"] &= ~unstable_path
         out_f.write(json.dumps(rec, sort_keys=True) + "\n")
         out_f.flush()
         n_records += 1
@@ -120,6 +130,89 @@ def host_join(name, ex, R, S, flags=M):
     Rh, Sh = (R if isinstance(R, np.ndarray) else to_np(R)), (S if isinstance(S, np.ndarray) else to_np(S))
     record("%s host flags=%#x" % (name, flags), ex, lambda: ex.join_host(Rh, Sh, flags), host=True, ordered=bool(flags & O))
 
+
+def keyed_section():
+    """The keyed joins, whose host sequence is hmj_tuplejoin.h's driver: the string entries in every mode for four kinds,
+    without bitmaps, with one on the probe side and with one on both; collisions (hash_bits = 4) through the collision sort
+    and the ambiguous re-join; the string entries' device-found argument errors and an empty side; the column and the
+    mixed entry with bitmaps on both sides.  Shapes from the tests: a few hundred to a few thousand rows, more than one
+    workgroup (256 rows) per relation.  HOT_KEY_HINT is left out under bitmaps (tests/test_keyjoin_plans_gpu.py, UNSTABLE)."""
+    import random
+
+    PROBE, BUILD = H.HMJ_KIND_PROBE_SIDE, H.HMJ_KIND_BUILD_SIDE
+    KINDS = (("inner", PROBE, H.HMJ_JOIN_INNER), ("probe semi", PROBE, H.HMJ_JOIN_SEMI), ("build anti", BUILD, H.HMJ_BUILD_ANTI),
+             ("full outer", BUILD, H.HMJ_FULL_OUTER))
+    MODES = (("count", CK | SP), ("mat", M | CK | SP), ("ordered", O | CK | SP))
+    HOT = H.HMJ_PATH_HOT_KEY_HINT
+    prng, nrng = random.Random(11), np.random.default_rng(11)
+    kx = H.Executor(0)
+    pool = sorted({b"k%06d" % prng.randrange(10 ** 6) + bytes(prng.getrandbits(8) for _ in range(prng.randrange(0, 24))) for _ in range(1500)})
+    prng.shuffle(pool)
+
+    def payloads(n):
+        return torch.from_numpy(nrng.integers(0, 1 << 62, n, dtype=np.int64)).cuda()
+
+    def str_rel(n, lo, hi):  # duplicates on both sides, misses on both sides
+        chars, offs = H.pack_strings([pool[prng.randrange(lo, hi)] for _ in range(n)], "cuda")
+        return chars, offs, payloads(n)
+
+    def bitmap(n, off):
+        return H.pack_validity(nrng.random(n) >= 0.2, off, "cuda"), off
+
+    def str_calls(tag, B, P, kinds, modes, bits=0):
+        nb, npr = B[2].shape[0], P[2].shape[0]
+        for vname, vb, vp in (("no bitmap", None, None), ("probe bitmap", None, bitmap(npr, 3)), ("both bitmaps", bitmap(nb, 5), bitmap(npr, 0))):
+            for kname, side, kind in kinds:
+                for mname, fl in modes:
+                    record("str %s %s %s %s" % (tag, kname, mname, vname), kx,
+                           lambda: kx.join_kind_str_device(B, P, side, kind, fl, hash_bits=bits, probe_fill=77, build_fill=55, build_valid=vb,
+                                                           probe_valid=vp),
+                           ordered=bool(fl & O), unstable_path=HOT if vb or vp else 0)
+
+    B, P = str_rel(1500, 0, 1000), str_rel(2100, 500, len(pool))
+    str_calls("", B, P, KINDS, MODES)
+    for mname, fl in MODES:  # the inner entry proper
+        record("str inner entry %s" % mname, kx, lambda: kx.join_str_device(B, P, fl), ordered=bool(fl & O))
+    # 16 hash values: runs of equal hash with several keys (the collision sort), representatives that hold another key
+    Bs, Ps = str_rel(300, 0, 200), str_rel(330, 100, 300)
+    str_calls("hash_bits=4", Bs, Ps, KINDS, MODES[2:], bits=4)
+    # what the hash kernels find: decreasing offsets (the first bad row is named), key bytes without a chars buffer; an empty side
+    bad = P[1].clone()
+    bad[701] = bad[700] - 1
+    for kname, side, kind in (KINDS[0], KINDS[3]):
+        record("str decreasing offsets %s" % kname, kx, lambda: kx.join_kind_str_device(B, (P[0], bad, P[2]), side, kind, M))
+        record("str chars NULL %s" % kname, kx, lambda: kx.join_kind_str_device((None, B[1], B[2]), P, side, kind, M))
+        record("str empty build %s" % kname, kx, lambda: kx.join_kind_str_device((B[0], B[1][:1], B[2][:0]), P, side, kind, O | CK | SP,
+                                                                                 probe_fill=77), ordered=True)
+    record("str bad offsets inner entry", kx, lambda: kx.join_str_device(B, (P[0], bad, P[2]), M))
+    # the column and the mixed entry with bitmaps on both sides (their valid rows are compacted into full-size arrays now)
+    nb, npr = 1500, 2100
+    days = [torch.from_numpy(nrng.integers(0, 40, n, dtype=np.int32)).cuda() for n in (nb, npr)]
+    ids = [torch.from_numpy(nrng.integers(0, 50, n, dtype=np.int64)).cuda() for n in (nb, npr)]
+    vals = [payloads(nb), payloads(npr)]
+    cv = [[bitmap(n, 1), bitmap(n, 6)] for n in (nb, npr)]
+    mv = [[bitmap(n, 2), None] for n in (nb, npr)]
+    for kname, side, kind in (KINDS[0], KINDS[3]):
+        for mname, fl in MODES:
+            record("cols %s %s both bitmaps" % (kname, mname), kx,
+                   lambda: kx.join_kind_cols_device([ids[0], days[0]], vals[0], [ids[1], days[1]], vals[1], side, kind, fl, force_hashed=True,
+                                                    probe_fill=77, build_fill=55, build_valid=cv[0], probe_valid=cv[1]),
+                   ordered=bool(fl & O), unstable_path=HOT)
+            record("mixed %s %s both bitmaps" % (kname, mname), kx,
+                   lambda: kx.join_mixed_device([B[:2], days[0]], vals[0], [P[:2], days[1]], vals[1], side, kind, fl, probe_fill=77,
+                                                build_fill=55, build_valid=mv[0], probe_valid=mv[1]),
+                   ordered=bool(fl & O), unstable_path=HOT)
+    record("mixed decreasing offsets under a bitmap", kx,
+           lambda: kx.join_mixed_device([B[:2], days[0]], vals[0], [(P[0], bad), days[1]], vals[1], BUILD, H.HMJ_FULL_OUTER, M,
+                                        build_valid=mv[0], probe_valid=mv[1]))
+    kx.close()
+
+
+SECTION = sys.argv[2] if len(sys.argv) > 2 else "all"  # all | u64 | keyed
+if SECTION == "keyed":
+    keyed_section()
+    print("ab_calls: %d records from %s" % (n_records, _lib.lib_path()), file=sys.stderr)
+    sys.exit(0)
 
 rng = np.random.default_rng(7)
 ex = executor(HMJ_SLAB_MIN_LOG2=22)           # (the slab plans from 2^22 rows on, as in the tests)
@@ -230,4 +323,6 @@ record("null build", ex, lambda: raw_join(None, 4), repeat=1)
 record("too many rows", ex, lambda: raw_join(C.c_void_p(R1.data_ptr()), 1 << 33), repeat=1)
 ex.close()
 exp.close()
+if SECTION == "all":
+    keyed_section()
 print("ab_calls: %d records from %s" % (n_records, _lib.lib_path()), file=sys.stderr)
