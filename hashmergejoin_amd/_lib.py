@@ -231,6 +231,32 @@ class GroupResult(C.Structure):
                 ("group_of_row", C.c_void_p)]
 
 
+# hmj_group_agg_device: typed value columns aggregated over the ctx's live grouping; hmj_agg_src.op and .type
+HMJ_AGG_COUNT, HMJ_AGG_SUM, HMJ_AGG_MIN, HMJ_AGG_MAX, HMJ_AGG_MEAN = 0, 1, 2, 3, 4
+HMJ_TYPE_I8, HMJ_TYPE_I16, HMJ_TYPE_I32, HMJ_TYPE_I64 = 0, 1, 2, 3
+HMJ_TYPE_U8, HMJ_TYPE_U16, HMJ_TYPE_U32, HMJ_TYPE_U64 = 4, 5, 6, 7
+HMJ_TYPE_F32, HMJ_TYPE_F64 = 8, 9
+HMJ_MAX_AGGS = 64
+
+
+class AggSrc(C.Structure):
+    """hmj_agg_src: one aggregate's source column on the device -- n_rows values of `type` (HMJ_TYPE_*), aligned to their
+    width (NULL allowed for HMJ_AGG_COUNT) --, the operation (HMJ_AGG_*) and the column's validity bitmap (bits NULL: no
+    NULL in the column)."""
+    _fields_ = [("data", C.c_void_p), ("type", C.c_uint32), ("op", C.c_uint32), ("validity", Validity)]
+
+
+class AggDst(C.Structure):
+    """hmj_agg_dst: one caller-owned output column -- n_groups values of the aggregate's output type, an optional bitmap of
+    ceil(n_groups / 64) 64-bit words (in); its NULL slots (out)."""
+    _fields_ = [("data", C.c_void_p), ("validity", C.c_void_p), ("null_count", C.c_uint64)]
+
+
+class GroupAggOpts(C.Structure):
+    """hmj_group_agg_opts: the live grouping's groups and the kernel time (out)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("n_groups", C.c_uint64), ("ms_agg", C.c_float)]
+
+
 # hmj_take_cols_device: fixed-width columns taken through a row map (a join's r_row / s_row)
 HMJ_TAKE_NO_ROW = 0xFFFFFFFFFFFFFFFF
 HMJ_MAX_TAKE_COLS = 64
@@ -434,6 +460,8 @@ def load_library():
     L.hmj_group_cols_device.argtypes = [vp, C.POINTER(ColsRel), C.c_uint32, C.POINTER(GroupOpts), C.POINTER(GroupResult)]
     L.hmj_group_mixed_device.restype = i
     L.hmj_group_mixed_device.argtypes = [vp, C.POINTER(MixedRel), C.c_uint32, C.POINTER(GroupOpts), C.POINTER(GroupResult)]
+    L.hmj_group_agg_device.restype = i
+    L.hmj_group_agg_device.argtypes = [vp, C.POINTER(AggSrc), C.c_uint32, u, C.POINTER(AggDst), C.POINTER(GroupAggOpts)]
     L.hmj_take_cols_device.restype = i
     L.hmj_take_cols_device.argtypes = [vp, C.POINTER(TakeSrc), C.c_uint32, u, vp, u, C.POINTER(TakeDst), C.POINTER(TakeOpts)]
     L.hmj_take_str_device.restype = i

@@ -3121,7 +3121,8 @@ void hmj_destroy(hmj_ctx* c) {
                     &c->offs64, &c->irregular, &c->ord_key, &c->ord_rval, &c->ord_sval, &c->matched, &c->vparts,
                     &c->slab_a, &c->slab_br, &c->slab_bs, &c->cnt_a, &c->cnt_br, &c->cnt_bs, &c->lookback, &c->gtab, &c->piece_off,
                     &c->split_r, &c->split_s, &c->split_off, &c->cat_key, &c->cat_rval, &c->cat_sval, &c->msd_off,
-                    &c->bmatched, &c->bsweep, &c->take_acc, &c->takestr_acc, &c->takestr_blk};
+                    &c->bmatched, &c->bsweep, &c->take_acc, &c->takestr_acc, &c->takestr_blk,
+                    &c->agg_acc, &c->agg_grp, &c->agg_part};
   for (DevBuf* b : devs) free_dev(*b);
   for (KeyJoinWs* ws : {&c->str_ws, &c->col_ws, &c->mix_ws}) {
     ws->each_buf(free_dev);
@@ -3141,6 +3142,8 @@ void hmj_destroy(hmj_ctx* c) {
   for (auto& e : c->take_ev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : c->takestr_ev)
+    if (e) (void)hipEventDestroy(e);
+  for (auto& e : c->agg_ev)
     if (e) (void)hipEventDestroy(e);
   for (auto& st : c->up_streams) (void)hipStreamDestroy(st);
   for (auto& e : c->copy_ev) (void)hipEventDestroy(e);
@@ -3607,6 +3610,7 @@ void hmj_release_result(hmj_ctx* c) {
   c->col_ws.each_result_buf(free_dev);
   c->mix_ws.each_result_buf(free_dev);
   c->grp_ws.each_result_buf(free_dev);
+  c->grp_ws.live = false;  // hmj_group_agg_device: the grouping is gone with its columns
   free_host(c->h_key);
   free_host(c->h_rval);
   free_host(c->h_sval);

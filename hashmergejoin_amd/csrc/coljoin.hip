@@ -702,6 +702,7 @@ int hmj_join_kind_cols_device(hmj_ctx* c, const hmj_cols_rel* build, const hmj_c
 
 int hmj_group_cols_device(hmj_ctx* c, const hmj_cols_rel* rel, uint32_t flags, hmj_group_opts* opts, hmj_group_result* out) {
   if (!c) return HMJ_E_ARG;
+  c->grp_ws.live = false;  // hmj_group_agg_device's binding ends here, whatever becomes of this call
   if (!opts || !out) return fail(c, HMJ_E_ARG, "opts / out is NULL");
   if (opts->struct_size < offsetof(hmj_group_opts, validity) + sizeof(opts->validity))
     return fail(c, HMJ_E_ARG, "hmj_group_opts.struct_size too small");
@@ -759,6 +760,9 @@ int hmj_group_cols_device(hmj_ctx* c, const hmj_cols_rel* rel, uint32_t flags, h
   const uint32_t room = opts->struct_size < sizeof(o) ? opts->struct_size : (uint32_t)sizeof(o);
   o.struct_size = opts->struct_size;
   std::memcpy(opts, &o, room);
+  c->grp_ws.live = mat;  // the live grouping of hmj_group_agg_device
+  c->grp_ws.live_rows = n;
+  c->grp_ws.live_groups = out->n_groups;
   return HMJ_OK;
 }
 

@@ -59,6 +59,11 @@ struct GroupWs {
       start,                  // first sorted position of every group, and n behind the last
       key, first, count, sum, min, max, gmap;  // the result columns
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // phase boundaries (profiling)
+  // The live grouping, what hmj_group_agg_device (groupagg.hip) aggregates over: set when a group call made with
+  // HMJ_MATERIALIZE returns HMJ_OK -- sorted, flags, blk_off and start then describe live_rows rows in live_groups groups --,
+  // cleared at the entry of either group call, by hmj_release_result and with the ctx.  Nothing else writes these buffers.
+  bool live = false;
+  uint64_t live_rows = 0, live_groups = 0;
   template <class F>
   void each_result_buf(F f) {
     for (DevBuf* b : {&key, &first, &count, &sum, &min, &max, &gmap}) f(*b);
@@ -156,13 +161,17 @@ struct hmj_ctx {
       take_acc,
       // hmj_take_str_device (takestr.hip): its counters, and the bytes per workgroup of 256 output rows followed by their
       // exclusive scan -- the only workspace the call owns
-      takestr_acc, takestr_blk;
+      takestr_acc, takestr_blk,
+      // hmj_group_agg_device (groupagg.hip): its NULL counters, the accumulator and valid-count slots per group of one
+      // launch chunk of aggregates, and the partial slots per wave of the walk -- the only workspace the call owns
+      agg_acc, agg_grp, agg_part;
   // string joins (strjoin.hip), multi-column joins (coljoin.hip) and mixed-key joins (mixjoin.hip): one workspace each, so
   // that no call reuses or regrows another's buffers
   hmj_host::KeyJoinWs str_ws, col_ws, mix_ws;
   hmj_host::GroupWs grp_ws;  // hmj_group_cols_device, hmj_group_mixed_device
   hipEvent_t take_ev[2] = {nullptr, nullptr};  // hmj_take_cols_device: around its launches (profiling)
   hipEvent_t takestr_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // hmj_take_str_device: around its offsets and its bytes phase
+  hipEvent_t agg_ev[2] = {nullptr, nullptr};  // hmj_group_agg_device: around its launches (profiling)
   int memo_kind = 0;  // workload-signature kind of plain inner joins run on behalf of another entry (string, multi-column joins and their kinds)
   HostBuf h_accum, h_key, h_rval, h_sval;
   int host_threads = 0;  // staging threads for pageable input (0 = default)

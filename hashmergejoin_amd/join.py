@@ -462,7 +462,10 @@ class Executor:
         if v is not None:
             opts.validity = v
         res = _lib.GroupResult()
+        self._group_rows = self._group_groups = 0  # (group_agg_device: the library drops its live grouping here)
         self._check(self.L.hmj_group_cols_device(self.h, C.byref(rel), flags, C.byref(opts), C.byref(res)))
+        if flags & (HMJ_MATERIALIZE | HMJ_ORDERED):
+            self._group_rows, self._group_groups = int(res.n_rows), int(res.n_groups)
         del keep, keep_v
         info = {"form": int(opts.form), "n_null": int(opts.n_null), "n_collisions": int(opts.n_collisions)}
         for k in ("ms_key", "ms_sort", "ms_groups", "ms_agg"):
@@ -589,12 +592,97 @@ class Executor:
         opts.want = int(want)
         opts.hash_bits = int(hash_bits)
         res = _lib.GroupResult()
+        self._group_rows = self._group_groups = 0  # (group_agg_device: the library drops its live grouping here)
         self._check(self.L.hmj_group_mixed_device(self.h, C.byref(rel), flags, C.byref(opts), C.byref(res)))
+        if flags & (HMJ_MATERIALIZE | HMJ_ORDERED):
+            self._group_rows, self._group_groups = int(res.n_rows), int(res.n_groups)
         del keep
         info = {"form": int(opts.form), "n_null": int(opts.n_null), "n_collisions": int(opts.n_collisions)}
         for k in ("ms_key", "ms_sort", "ms_groups", "ms_agg"):
             info[k] = float(getattr(opts, k))
         return res, info
+
+    # ---- typed columns aggregated over the live grouping (hmj_group_agg_device) ----------------------------
+    def _agg_type(self, t):
+        torch = self._torch
+        names = ("int8", "int16", "int32", "int64", "uint8", "uint16", "uint32", "uint64", "float32", "float64")
+        for code, name in enumerate(names):
+            if getattr(torch, name, None) is t.dtype:
+                return code
+        raise ValueError("no HMJ_TYPE_* for %s" % (t.dtype,))
+
+    def group_agg_device(self, aggs, want_validity=True, n_rows=None):
+        """Aggregate typed value columns over the executor's live grouping (hmj_group_agg_device): the last successful
+        `group_cols_device` / `group_mixed_device` call made with HMJ_MATERIALIZE or HMJ_ORDERED; slot g of every output is
+        group g of that call's columns.  aggs: a list of (op, column, valid[, bit_offset]) -- op an HMJ_AGG_* code; column a
+        contiguous 1-D device tensor of an integer or float dtype of 1 to 8 bytes (the HMJ_TYPE_* is inferred), or None
+        for HMJ_AGG_COUNT; valid None or a contiguous 1-D device tensor holding the column's Arrow bitmap (uint8 bytes as
+        `pack_validity` makes them, or 64-bit words), row i at bit bit_offset + i.  want_validity: True, False, or one bool
+        per aggregate.  n_rows: the grouped relation's rows (default: the first column's length, or the rows of the last
+        group call made through this executor).  The outputs are new tensors: COUNT uint64, SUM int64 / uint64 / float64,
+        MIN / MAX the source dtype, MEAN float64.  Returns ([(values, validity words or None, null_count), ...],
+        {"n_groups", "ms_agg"}); `unpack_validity` reads the words, `expected_group_aggs` reproduces everything."""
+        torch = self._torch
+        self._sync_stream()
+        aggs = [tuple(a) for a in aggs]
+        wants = [bool(want_validity)] * len(aggs) if isinstance(want_validity, (bool, int)) else [bool(w) for w in want_validity]
+        if len(wants) != len(aggs):
+            raise ValueError("want_validity: one entry per aggregate")
+        if n_rows is None:
+            lens = [a[1].shape[0] for a in aggs if a[1] is not None]
+            n_rows = lens[0] if lens else getattr(self, "_group_rows", 0)
+        n_rows = int(n_rows)
+        # the groups size the outputs: an HMJ_E_ARG call must still reach the library, so any count will do for it
+        n_groups = int(getattr(self, "_group_groups", 0))
+        dev = "cuda:%d" % self.device
+        src = (_lib.AggSrc * max(len(aggs), 1))()
+        dst = (_lib.AggDst * max(len(aggs), 1))()
+        outs, words, keep = [], [], []
+        f64, i64 = torch.float64, torch.int64
+        u64 = getattr(torch, "uint64", i64)
+        for k, a in enumerate(aggs):
+            op, t, v = int(a[0]), a[1], a[2] if len(a) > 2 else None
+            off = int(a[3]) if len(a) > 3 else 0
+            code = _lib.HMJ_TYPE_U64
+            if t is not None:
+                if not t.is_cuda or not t.is_contiguous() or t.dim() != 1:
+                    raise ValueError("aggregate %d: the column must be a contiguous 1-D device tensor" % k)
+                code = self._agg_type(t)
+                src[k].data = t.data_ptr() if t.shape[0] else None
+                keep.append(t)
+            src[k].type = code
+            src[k].op = op & 0xFFFFFFFF
+            if v is not None:
+                if not v.is_cuda or not v.is_contiguous() or v.dim() != 1:
+                    raise ValueError("aggregate %d: valid must be a contiguous 1-D device tensor" % k)
+                if off < 0:
+                    raise ValueError("aggregate %d: bit_offset must not be negative" % k)
+                src[k].validity.bits = v.data_ptr() if v.shape[0] else None
+                src[k].validity.bit_offset = off & 0xFFFFFFFFFFFFFFFF
+                keep.append(v)
+            if op == _lib.HMJ_AGG_COUNT:
+                dt = u64
+            elif op == _lib.HMJ_AGG_MEAN:
+                dt = f64
+            elif op == _lib.HMJ_AGG_SUM:
+                dt = f64 if code >= _lib.HMJ_TYPE_F32 else (i64 if code <= _lib.HMJ_TYPE_I64 else u64)
+            else:
+                dt = t.dtype if t is not None else u64
+            o = torch.empty(n_groups, dtype=dt, device=dev)
+            w = torch.empty((n_groups + 63) // 64, dtype=i64, device=dev) if wants[k] else None
+            dst[k].data = o.data_ptr() if n_groups else None
+            dst[k].validity = w.data_ptr() if (w is not None and n_groups) else None
+            outs.append(o)
+            words.append(w)
+        opts = _lib.GroupAggOpts()
+        opts.struct_size = C.sizeof(_lib.GroupAggOpts)
+        self._check(self.L.hmj_group_agg_device(self.h, src, len(aggs), n_rows, dst, C.byref(opts)))
+        del keep
+        if int(opts.n_groups) != n_groups:
+            raise RuntimeError("the live grouping has %d groups, the executor sized the outputs for %d: group through this "
+                               "executor's group_cols_device / group_mixed_device" % (int(opts.n_groups), n_groups))
+        info = {"n_groups": int(opts.n_groups), "ms_agg": float(opts.ms_agg)}
+        return [(outs[k], words[k], int(dst[k].null_count)) for k in range(len(aggs))], info
 
     # ---- columns through a row map (hmj_take_cols_device) ------------------------------------------------
     def take_cols_device(self, cols, row_map, valid=None, n_out=None, want_validity=True):
@@ -763,6 +851,7 @@ class Executor:
         return out
 
     def release_result(self):
+        self._group_rows = self._group_groups = 0
         self.L.hmj_release_result(self.h)
 
     # ---- multi-GPU exchange (hmj_comm_* / hmj_exchange_join_u64_device) -------------------------
@@ -1189,6 +1278,91 @@ def _group_table(canon, key64, pay, nulls, hashed, ordered):
                 "key64": gkey[order], "first_row": first[order].astype(np.uint64), "count": count[order].astype(np.uint64),
                 "sum": gsum.astype(np.uint64), "min": np.minimum.reduceat(sorted_pay, starts),
                 "max": np.maximum.reduceat(sorted_pay, starts), "group_of_row": group_of_row.astype(np.uint64)})
+    return out
+
+
+def _float_order_keys(a):
+    """Floats (float32 / float64) -> (unsigned keys whose integer order is IEEE order with -0.0 < +0.0, is-NaN mask)."""
+    bits = a.view("u%d" % a.dtype.itemsize)
+    top = bits.dtype.type(1 << (8 * a.dtype.itemsize - 1))
+    keys = np.where(bits & top, ~bits, bits | top)
+    return keys, (bits & ~top) > (bits.dtype.type(0x7F800000) if a.dtype.itemsize == 4 else bits.dtype.type(0x7FF0000000000000))
+
+
+def expected_group_aggs(group_of_row, n_groups, aggs):
+    """What hmj_group_agg_device returns (include/hmj.h), restated on the host from group_of_row alone -- no key logic.
+    group_of_row: n integers in 0..n_groups-1; aggs: a list of (op, values, valid): op an HMJ_AGG_* code, values a numpy
+    array of n integers or floats of the column's dtype (None for HMJ_AGG_COUNT), valid None or n bools (True = valid).
+    What lies under a NULL slot is not read.  Returns one dict per aggregate: "values" (n_groups entries of the output
+    dtype: COUNT uint64, SUM int64 / uint64 / float64, MIN / MAX the source dtype, MEAN float64; 0 in a NULL slot),
+    "valid" (n_groups bools), "null_count", "count" (the valid values per group, int64) and "abs_sum" (float64: the sum of
+    |x| over the group's valid values for float SUM and for MEAN, each x converted to double; None otherwise).  Float sums
+    are math.fsum per group, i.e. correctly rounded: the device's differ from them by at most gamma_k * abs_sum."""
+    import math
+
+    gmap = np.asarray(group_of_row).astype(np.int64).ravel()
+    n, ng = len(gmap), int(n_groups)
+    if n and (gmap.min() < 0 or gmap.max() >= ng):
+        raise ValueError("group_of_row: entries must be in 0..n_groups-1")
+    out = []
+    for op, vals, valid in [tuple(a)[:3] if len(tuple(a)) > 2 else tuple(a) + (None,) for a in aggs]:
+        op = int(op)
+        ok = np.ones(n, bool) if valid is None else np.asarray(valid, bool).ravel()
+        if len(ok) != n:
+            raise ValueError("valid: one entry per row")
+        count = np.bincount(gmap[ok], minlength=ng).astype(np.int64)
+        res = {"count": count, "abs_sum": None}
+        if op == _lib.HMJ_AGG_COUNT:
+            res.update({"values": count.astype(np.uint64), "valid": np.ones(ng, bool)})
+        else:
+            a = np.ascontiguousarray(vals).ravel()
+            if len(a) != n or a.dtype.kind not in "iuf" or a.dtype.itemsize > 8 or a.dtype == np.float16:
+                raise ValueError("values: n integers or floats of 1 to 8 bytes")
+            g, x = gmap[ok], a[ok]
+            is_float = a.dtype.kind == "f"
+            if op == _lib.HMJ_AGG_MEAN or (op == _lib.HMJ_AGG_SUM and is_float):
+                xd = x.astype(np.float64)
+                order = np.argsort(g, kind="stable")
+                ends = np.cumsum(count)
+                sums, abss = np.zeros(ng), np.zeros(ng)
+                with np.errstate(all="ignore"):
+                    for k in range(ng):
+                        seg = xd[order[ends[k] - count[k]:ends[k]]]
+                        try:
+                            sums[k] = math.fsum(seg)
+                        except (OverflowError, ValueError):  # an intermediate overflow, inf - inf: as IEEE addition has it
+                            sums[k] = float(np.sum(seg))
+                        abss[k] = float(np.sum(np.abs(seg)))
+                    v = sums / np.maximum(count, 1) if op == _lib.HMJ_AGG_MEAN else sums
+                res["abs_sum"] = abss
+            elif op == _lib.HMJ_AGG_SUM:
+                wide = x.astype(np.int64).view(np.uint64) if a.dtype.kind == "i" else x.astype(np.uint64)
+                acc = np.zeros(ng, np.uint64)
+                np.add.at(acc, g, wide)  # (wraps mod 2^64)
+                v = acc.view(np.int64) if a.dtype.kind == "i" else acc
+            elif op in (_lib.HMJ_AGG_MIN, _lib.HMJ_AGG_MAX):
+                low = op == _lib.HMJ_AGG_MIN
+                if is_float:
+                    keys, nan = _float_order_keys(x)
+                    ident = keys.dtype.type(np.iinfo(keys.dtype).max if low else 0)
+                    acc = np.full(ng, ident, keys.dtype)
+                    (np.minimum if low else np.maximum).at(acc, g[~nan], keys[~nan])
+                    numbers = np.bincount(g[~nan], minlength=ng) > 0
+                    top = keys.dtype.type(1 << (8 * a.dtype.itemsize - 1))
+                    v = np.where(acc & top, acc ^ top, ~acc).view(a.dtype).copy()
+                    v[~numbers] = np.nan  # (numpy's default NaN is the canonical quiet one)
+                else:
+                    info = np.iinfo(a.dtype)
+                    acc = np.full(ng, info.max if low else info.min, a.dtype)
+                    (np.minimum if low else np.maximum).at(acc, g, x)
+                    v = acc
+            else:
+                raise ValueError("unknown op %d" % op)
+            v = np.array(v)
+            v[count == 0] = 0
+            res.update({"values": v, "valid": count > 0})
+        res["null_count"] = int(ng - np.count_nonzero(res["valid"]))
+        out.append(res)
     return out
 
 

@@ -923,7 +923,8 @@ int hmj_join_mixed_device(hmj_ctx* ctx, const hmj_mixed_rel* build, const hmj_mi
  * atomic per wave.  Everything runs on the ctx stream in a workspace of the entry's own; the host reads back the
  * mismatch count, n_groups and one counter block.  hmj_last_plan / hmj_last_timing are left as they were.
  * String and mixed keys: hmj_group_mixed_device below.
- * Out of scope: several value columns per call, signed and float aggregates, the exchange path.                        */
+ * Several value columns per call, signed and float aggregates, NULL values: hmj_group_agg_device below, over this call's
+ * grouping.  Out of scope: the exchange path.                                                                          */
 #define HMJ_GROUP_COUNT   0x01u  /* out->count                                                                         */
 #define HMJ_GROUP_SUM     0x02u  /* out->sum: wrapping u64 sum of the payloads                                          */
 #define HMJ_GROUP_MIN     0x04u  /* out->min: unsigned                                                                  */
@@ -980,10 +981,107 @@ int hmj_group_cols_device(hmj_ctx* ctx, const hmj_cols_rel* rel, uint32_t flags,
  * How (DESIGN.md "Grouping rows by string and mixed keys"): mix_key_kernel's dense forms write the rows, and the sequence
  * of hmj_group_cols_device runs on the mixed join's key policies (MixSide; MixNeSide where a column has a bitmap).  One
  * round trip more than the column entry: the key kernel's verdict.
- * Out of scope: 32-bit-offset `string` columns, several value columns per call, signed and float aggregates, the exchange
- * path, a sort-free path for few groups.                                                                               */
+ * Several value columns per call, signed and float aggregates, NULL values: hmj_group_agg_device below, over this call's
+ * grouping.  Out of scope: 32-bit-offset `string` columns, the exchange path, a sort-free path for few groups.         */
 int hmj_group_mixed_device(hmj_ctx* ctx, const hmj_mixed_rel* rel, uint32_t flags, hmj_group_opts* opts,
                            hmj_group_result* out);
+
+/* ---- aggregating typed value columns over a grouping (SUM / MIN / MAX / MEAN / COUNT) ------------------ */
+/* What turns a grouping into a query result: up to HMJ_MAX_AGGS aggregates of typed, NULL-aware value columns are reduced
+ * over the groups of the ctx's LIVE GROUPING in one call -- SUM(price), AVG(qty), MIN(ts) over an int32, a float64 and an
+ * int64 column.  The counterpart of hmj_take_cols_device for the group entries.  Nothing in the reference corresponds.  A
+ * new entry with structs of its own: no other entry, struct, flag or path bit changes.
+ * src and dst are HOST arrays of n_aggs entries (read during the call only; dst[a].null_count is written); everything they
+ * point to is on the device and caller-owned.  One source column may appear in several entries (SUM and MIN of one column).
+ * Binding.  The live grouping is the last successful hmj_group_cols_device or hmj_group_mixed_device call made with
+ * HMJ_MATERIALIZE (HMJ_ORDERED implies it).  Output slot g of every aggregate belongs to group g of that call's group
+ * columns: the index of key64[g], first_row[g], count[g] and of group_of_row.  n_rows must equal that call's n_rows, and
+ * row i of every source column is row i of the grouped relation.  The binding begins when such a call returns HMJ_OK.  It
+ * ends at the entry of the next group call on the ctx -- whether that call succeeds or not, count-only calls included --, at
+ * hmj_release_result and at hmj_destroy.  No other entry touches the group workspace: joins, sorts, takes and earlier
+ * aggregate calls in between keep the binding.  Without a live grouping the call is HMJ_E_ARG ("no live grouping").
+ * The call has a workspace of its own and leaves the last result (the group columns included), a prepared build side,
+ * hmj_last_plan, hmj_last_timing and the workload memos as they were.  It returns with the work complete on the ctx stream;
+ * opts->n_groups is filled.
+ * Semantics; every output is a function of the inputs and the grouping alone.
+ * Validity: source slot i of aggregate a is NULL where bit bit_offset + i of src[a].validity.bits is 0 (an Arrow bitmap at
+ * any bit_offset; bits == NULL: the column has no NULL).  NULL values are skipped, and whatever lies under a NULL slot is
+ * never used.  HMJ_AGG_COUNT is the number of valid values of the group -- without a bitmap the group's size --, always a
+ * valid uint64; its data may be NULL and its type is ignored beyond being a known one.
+ * Empty groups: a group without a valid value gives a NULL output slot for SUM, MIN, MAX and MEAN, its value bytes written
+ * as 0.  dst[a].validity != NULL: ceil(n_groups / 64) 64-bit words are written exactly as hmj_take_dst's (group g = bit
+ * g & 63 of word g >> 6, padding bits 0).  dst[a].null_count is filled with or without a bitmap.
+ * SUM: signed integers are sign-extended and summed in int64, unsigned ones zero-extended and summed in uint64, both
+ * wrapping; F32 and F64 are summed in double (an F32 value converts exactly).  The output is int64 / uint64 / double.
+ * MIN / MAX: the output has the source type.  Integers compare in their own signedness; floats by IEEE order with
+ * -0.0 < +0.0; a NaN loses against any number, and a group whose valid values are all NaN gives the canonical quiet NaN
+ * (0x7ff8000000000000, 0x7fc00000).
+ * MEAN: double -- the double sum of the values, each converted to double, divided by the valid count (not the wrapped
+ * integer sum).
+ * Float sums are deterministic: the bits depend on the inputs and on the grouping only -- the same call gives the same bits
+ * whatever ran before it.  The order of the additions is fixed by the sorted positions of the group's rows (a segmented
+ * scan inside chunks of 64 positions, chunks in ascending order inside the 512 positions a wave walks, then the waves'
+ * partials in ascending order in a fixed shape); there is no floating-point atomic and no integer one either.  The sum is
+ * NOT the correctly rounded one: |sum - exact| <= gamma_k * sum|x| with gamma_k = k u / (1 - k u), u = 2^-53, k the valid
+ * count, as for any order of summation.
+ * n_rows == 0 (a live grouping of zero rows): HMJ_OK, n_groups 0, null_count 0, nothing is written on the device.
+ * HMJ_E_ARG, found by the host before any launch (hmj_last_error names what was wrong): NULL ctx / src / dst / opts;
+ * opts->struct_size smaller than through `reserved`; non-zero reserved; n_aggs outside 1..HMJ_MAX_AGGS; an unknown type or
+ * op; NULL data except for HMJ_AGG_COUNT, or data misaligned to the value's width, when n_rows > 0; NULL dst[a].data when
+ * there are groups; dst[a].data misaligned to the output's width; dst[a].validity not aligned to 8 bytes; bit_offset + n_rows
+ * overflowing 64 bits; no live grouping; n_rows differing from the live grouping's; a destination range (data or bitmap)
+ * that overlaps a source column, a source bitmap or another destination of the call (address ranges).  The ctx stays usable
+ * after any error.
+ * How (DESIGN.md "Aggregating typed columns over a grouping"): per launch chunk of up to 4 aggregates three kernels run
+ * over the grouping's sorted {key64,row} rows, head ballots and group starts.  agg_walk_kernel: group_agg_kernel's walk -- a
+ * wave covers 8 chunks of 64 sorted positions, the row index and the ballot word are loaded once for all aggregates, every
+ * gather of a position (values and validity bytes) is issued before the segmented __shfl_up scan; an aggregate that names
+ * the source column or bitmap of the one in front of it (SUM(x), MIN(x), MAX(x)) reuses its load -- with a 64-bit
+ * accumulator and a valid count per aggregate (integer sums as u64, float sums and means as double, MIN / MAX on an
+ * order-preserving u64 key); a group inside the wave's range is stored by its last lane, the at most two groups open at the
+ * range's ends go to the wave's left and right partial slots.  agg_combine_kernel: one wave per group that reaches a wave
+ * boundary reduces its partials, strided over the lanes in ascending wave order, then a fixed shuffle tree.
+ * agg_finish_kernel: one lane per group converts the accumulator (MEAN divides, MIN / MAX unmap, NULL slots become 0),
+ * stores the value, stores a wave's ballot as one bitmap word and counts NULLs by popcount, one atomic per workgroup; that
+ * counter block is the call's one read-back.
+ * Out of scope: variance / stddev, string MIN / MAX, COUNT(DISTINCT value), decimal128, the exchange path, host-resident
+ * columns.                                                                                                              */
+#define HMJ_AGG_COUNT 0u  /* valid (non-NULL) values of the group -> uint64, never NULL                                 */
+#define HMJ_AGG_SUM   1u  /* -> int64 (signed types), uint64 (unsigned types), double (F32 / F64)                        */
+#define HMJ_AGG_MIN   2u  /* -> the source type                                                                         */
+#define HMJ_AGG_MAX   3u  /* -> the source type                                                                         */
+#define HMJ_AGG_MEAN  4u  /* -> double                                                                                  */
+#define HMJ_TYPE_I8  0u
+#define HMJ_TYPE_I16 1u
+#define HMJ_TYPE_I32 2u
+#define HMJ_TYPE_I64 3u
+#define HMJ_TYPE_U8  4u
+#define HMJ_TYPE_U16 5u
+#define HMJ_TYPE_U32 6u
+#define HMJ_TYPE_U64 7u
+#define HMJ_TYPE_F32 8u
+#define HMJ_TYPE_F64 9u
+#define HMJ_MAX_AGGS 64
+typedef struct {
+  const void* data;       /* device: n_rows values of `type`, aligned to their width; may be NULL for HMJ_AGG_COUNT */
+  uint32_t type;          /* HMJ_TYPE_*                                                                          */
+  uint32_t op;            /* HMJ_AGG_*                                                                           */
+  hmj_validity validity;  /* source bitmap, any bit_offset; bits == NULL: the column has no NULL                  */
+} hmj_agg_src;
+typedef struct {
+  void* data;             /* device, caller-owned: n_groups values of the aggregate's output type, aligned to it  */
+  uint64_t* validity;     /* device, caller-owned, or NULL: ceil(n_groups / 64) 64-bit words; Arrow bitmap at bit
+                             offset 0, group g = bit g, padding bits written as 0                                */
+  uint64_t null_count;    /* out: NULL slots of this output column (filled with or without bitmap)               */
+} hmj_agg_dst;
+typedef struct {
+  uint32_t struct_size;   /* size-versioned like the other opts                                                  */
+  uint32_t reserved;
+  uint64_t n_groups;      /* out: the live grouping's groups = the slots written per aggregate                   */
+  float ms_agg;           /* out, with hmj_set_profiling                                                         */
+} hmj_group_agg_opts;
+int hmj_group_agg_device(hmj_ctx* ctx, const hmj_agg_src* src, uint32_t n_aggs, uint64_t n_rows, hmj_agg_dst* dst,
+                         hmj_group_agg_opts* opts);
 
 /* ---- taking fixed-width columns through a row map (Arrow validity out) --------------------------------- */
 /* The joins above return gather maps (r_row / s_row), not columns.  This entry turns a map back into Arrow columns: up to
