@@ -10,8 +10,9 @@ from ._lib import (HMJ_AGG_COUNT, HMJ_AGG_MAX, HMJ_AGG_MEAN, HMJ_AGG_MIN, HMJ_AG
                    HMJ_PATH_EXACT, HMJ_PATH_GLOBAL_TABLE, HMJ_PATH_HOST_PIPELINE, HMJ_PATH_HOT_KEY_HINT, HMJ_PATH_LOOKBACK_TIMEOUT, HMJ_PATH_ORDER_BY_KEY, HMJ_PATH_ORDER_BY_RANK_SORT, HMJ_PATH_ORDER_DEFERRED, HMJ_PATH_ORDERED_EXPANSION, HMJ_PATH_LDS_TABLE,
                    HMJ_PATH_KEY_RANGES, HMJ_PATH_PREPARED, HMJ_PATH_PRESORTED, HMJ_PATH_RANK_RUNS, HMJ_PATH_SORT_MSD, HMJ_PATH_SLAB, HMJ_PATH_SLAB_ONE_PASS, HMJ_PATH_SLAB_PROBE, HMJ_PATH_SORTED_FK, HMJ_PATH_SORTED_FK_HALF, HMJ_PATH_SORTED_FK_WIDE, HMJ_PATH_SORTED_WRITE, HMJ_PATH_SPLIT, HMJ_PATH_UNIQ_WRITE, HMJ_PATH_WINDOW,
                    HMJ_KEY_FIXED, HMJ_KEY_LARGE_STRING, HMJ_MAX_KEY_COLS, HMJ_MAX_TAKE_COLS, HMJ_NULL_EQUAL, HMJ_STR_NO_ROW, HMJ_SUM_PROBE, HMJ_TAKE_NO_ROW, BuildJoinOpts, ColsJoinOpts, ColsKindOpts, ColsRel, ColsResult, ExchangeKindOpts, GroupOpts, GroupResult, HmjError, JoinOpts, JoinResult, KeyCol, KindCounts, MixedCol, MixedOpts, MixedRel, StrJoinOpts, StrKindOpts, StrRel, StrResult, TakeDst, TakeOpts, TakeSrc, TakeStrDst, TakeStrOpts, TakeStrSrc, Timing, Validity,
+                   HMJ_MAX_ORDER_COLS, HMJ_ORDER_DESC, HMJ_ORDER_LARGE_STRING, HMJ_ORDER_NULLS_FIRST, OrderCol, OrderOpts,
                    lib_path, load_library)
-from .join import Executor, HashMergeJoin, cols_key64, expected_group_aggs, expected_groups, expected_mixed_groups, mixed_key64, pack_strings, pack_validity, plan, unpack_strings, unpack_validity
+from .join import Executor, HashMergeJoin, cols_key64, expected_group_aggs, expected_groups, expected_mixed_groups, expected_order_by, mixed_key64, order_stream_bytes, pack_strings, pack_validity, plan, unpack_strings, unpack_validity
 
 __all__ = ["Executor", "HashMergeJoin", "plan", "HmjError", "JoinResult", "Timing", "load_library",
            "lib_path", "HMJ_MATERIALIZE", "HMJ_ORDERED", "HMJ_FIRST_WINS", "HMJ_CHECKSUM",
@@ -29,4 +30,6 @@ __all__ = ["Executor", "HashMergeJoin", "plan", "HmjError", "JoinResult", "Timin
            "expected_groups", "expected_mixed_groups",
            "AggSrc", "AggDst", "GroupAggOpts", "HMJ_AGG_COUNT", "HMJ_AGG_SUM", "HMJ_AGG_MIN", "HMJ_AGG_MAX", "HMJ_AGG_MEAN",
            "HMJ_TYPE_I8", "HMJ_TYPE_I16", "HMJ_TYPE_I32", "HMJ_TYPE_I64", "HMJ_TYPE_U8", "HMJ_TYPE_U16", "HMJ_TYPE_U32",
-           "HMJ_TYPE_U64", "HMJ_TYPE_F32", "HMJ_TYPE_F64", "HMJ_MAX_AGGS", "expected_group_aggs"]
+           "HMJ_TYPE_U64", "HMJ_TYPE_F32", "HMJ_TYPE_F64", "HMJ_MAX_AGGS", "expected_group_aggs",
+           "OrderCol", "OrderOpts", "HMJ_ORDER_LARGE_STRING", "HMJ_ORDER_DESC", "HMJ_ORDER_NULLS_FIRST", "HMJ_MAX_ORDER_COLS",
+           "expected_order_by", "order_stream_bytes"]

@@ -257,6 +257,26 @@ class GroupAggOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("n_groups", C.c_uint64), ("ms_agg", C.c_float)]
 
 
+# hmj_order_by_device: a stable multi-column ORDER BY to a row map; hmj_order_col.type (beside HMJ_TYPE_*) and .flags
+HMJ_ORDER_LARGE_STRING = 16
+HMJ_ORDER_DESC, HMJ_ORDER_NULLS_FIRST = 0x1, 0x2
+HMJ_MAX_ORDER_COLS = 8
+
+
+class OrderCol(C.Structure):
+    """hmj_order_col: one key column on the device -- n values of a HMJ_TYPE_* aligned to their width, or (type
+    HMJ_ORDER_LARGE_STRING) chars and n + 1 64-bit offsets --, its HMJ_ORDER_* flags and its validity bitmap (bits NULL: no
+    NULL in the column)."""
+    _fields_ = [("type", C.c_uint32), ("flags", C.c_uint32), ("data", C.c_void_p), ("offsets", C.c_void_p), ("validity", Validity)]
+
+
+class OrderOpts(C.Structure):
+    """hmj_order_opts: distinct key tuples, tied rows, sort rounds and the phase times (out)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("n_distinct", C.c_uint64), ("n_tied_rows", C.c_uint64),
+                ("n_rounds", C.c_uint32), ("reserved2", C.c_uint32), ("ms_key", C.c_float), ("ms_sort", C.c_float),
+                ("ms_refine", C.c_float), ("ms_map", C.c_float)]
+
+
 # hmj_take_cols_device: fixed-width columns taken through a row map (a join's r_row / s_row)
 HMJ_TAKE_NO_ROW = 0xFFFFFFFFFFFFFFFF
 HMJ_MAX_TAKE_COLS = 64
@@ -462,6 +482,8 @@ def load_library():
     L.hmj_group_mixed_device.argtypes = [vp, C.POINTER(MixedRel), C.c_uint32, C.POINTER(GroupOpts), C.POINTER(GroupResult)]
     L.hmj_group_agg_device.restype = i
     L.hmj_group_agg_device.argtypes = [vp, C.POINTER(AggSrc), C.c_uint32, u, C.POINTER(AggDst), C.POINTER(GroupAggOpts)]
+    L.hmj_order_by_device.restype = i
+    L.hmj_order_by_device.argtypes = [vp, C.POINTER(OrderCol), C.c_uint32, u, vp, C.POINTER(OrderOpts)]
     L.hmj_take_cols_device.restype = i
     L.hmj_take_cols_device.argtypes = [vp, C.POINTER(TakeSrc), C.c_uint32, u, vp, u, C.POINTER(TakeDst), C.POINTER(TakeOpts)]
     L.hmj_take_str_device.restype = i

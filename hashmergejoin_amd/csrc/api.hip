@@ -3132,6 +3132,9 @@ void hmj_destroy(hmj_ctx* c) {
   c->grp_ws.each_buf(free_dev);
   for (auto& e : c->grp_ws.ev)
     if (e) (void)hipEventDestroy(e);
+  c->ord_ws.each_buf(free_dev);
+  for (auto& e : c->ord_ws.ev)
+    if (e) (void)hipEventDestroy(e);
   HostBuf* hosts[] = {&c->h_accum, &c->h_key, &c->h_rval, &c->h_sval};
   for (HostBuf* b : hosts) free_host(*b);
   for (auto& e : c->events)
@@ -3645,7 +3648,8 @@ int hmj_sort_u64_device(hmj_ctx* c, const void* in_aos_dev, uint64_t n, void* ou
   spans_reset(c);
   c->prep.valid = false;  // rbuf[0] is the sort's ping-pong buffer (an empty sort discards too, like every other call)
   if (n == 0) return HMJ_OK;
-  memo_for(c, workload_signature(n, 0, 0, 1));  // (what earlier sorts of this size learnt: the chain's cool-down)
+  // (what earlier sorts of this size learnt: the chain's cool-down; the sorts of hmj_order_by_device under a kind of their own)
+  memo_for(c, workload_signature(n, 0, 0, c->memo_kind ? c->memo_kind : 1));
   RC_TRY(ensure_dev(c, c->rbuf[0], (size_t)n * 16));
   // Digits in which no key differs need no pass (a stable pass on a constant digit is a copy): integer ids below 2^32
   // sort in four passes instead of eight (dense keys, 2^26 rows: 5.58 -> 2.93 ms, 2^28: 21.4 -> 10.8 ms = 24.8 G keys/s,

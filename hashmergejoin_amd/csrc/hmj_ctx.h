@@ -75,6 +75,20 @@ struct GroupWs {
   }
 };
 
+// Workspace of hmj_order_by_device (orderby.hip): no other entry reuses or regrows its buffers.
+struct OrderWs {
+  DevBuf rows, sorted,     // a round's {word, row} rows as keyed, and sorted
+      lst[2], rank[2],     // the active rows, round by round in turn: {sorted position, row}, and the rank of the row's segment
+      heads, act, acth,    // one ballot word per wave of a round's rows: heads, active rows, heads of active segments
+      blk, blk_off,        // active rows (low half) and active segments (high half) per workgroup, and their offsets
+      acc;                 // the counters and the key kernel's report words
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // phase boundaries (profiling)
+  template <class F>
+  void each_buf(F f) {
+    for (DevBuf* b : {&rows, &sorted, &lst[0], &lst[1], &rank[0], &rank[1], &heads, &act, &acth, &blk, &blk_off, &acc}) f(*b);
+  }
+};
+
 enum Kind {
   K_TOTAL = 0, K_H2D, K_D2H, K_HIST, K_SCAN, K_SCATTER, K_OFFSETS, K_PROBE_COUNT, K_OUT_SCAN,
   K_PROBE_WRITE, K_ORDER, K_NKINDS
@@ -169,10 +183,11 @@ struct hmj_ctx {
   // that no call reuses or regrows another's buffers
   hmj_host::KeyJoinWs str_ws, col_ws, mix_ws;
   hmj_host::GroupWs grp_ws;  // hmj_group_cols_device, hmj_group_mixed_device
+  hmj_host::OrderWs ord_ws;  // hmj_order_by_device
   hipEvent_t take_ev[2] = {nullptr, nullptr};  // hmj_take_cols_device: around its launches (profiling)
   hipEvent_t takestr_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // hmj_take_str_device: around its offsets and its bytes phase
   hipEvent_t agg_ev[2] = {nullptr, nullptr};  // hmj_group_agg_device: around its launches (profiling)
-  int memo_kind = 0;  // workload-signature kind of plain inner joins run on behalf of another entry (string, multi-column joins and their kinds)
+  int memo_kind = 0;  // workload-signature kind of plain inner joins run on behalf of another entry (string, multi-column joins and their kinds), and of the sorts hmj_order_by_device runs
   HostBuf h_accum, h_key, h_rval, h_sval;
   int host_threads = 0;  // staging threads for pageable input (0 = default)
   std::vector<hipStream_t> up_streams;

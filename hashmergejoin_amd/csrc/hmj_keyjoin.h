@@ -475,6 +475,9 @@ float elapsed(const hipEvent_t* ev, int a, int b) {
 // promised nothing (a hint would place the partition window as if key64 shared those top bits: partitions would stop
 // being key ranges, and an ordered result is not sorted again).  So this join samples its own keys, and the hint is put
 // back for the caller's next u64 join on every way out.
+// memo_kind is set for the duration of join_device only and is 0 again before anything else runs: hmj_sort_u64_device keys
+// its memo by memo_kind when it is non-zero (hmj_order_by_device's sorts), so the sorts the key joins and group_rows reach
+// (kind_order, hmj_group.h) must find it 0 to stay under the plain sort's kind 1.
 int memo_join(hmj_ctx* c, const void* Rr, u64 nr, const void* Sr, u64 ns, uint32_t flags, int memo, hmj_result* out) {
   spans_reset(c);
   const int st = span_begin(c, K_TOTAL, -1);

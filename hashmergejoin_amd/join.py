@@ -684,6 +684,62 @@ class Executor:
         info = {"n_groups": int(opts.n_groups), "ms_agg": float(opts.ms_agg)}
         return [(outs[k], words[k], int(dst[k].null_count)) for k in range(len(aggs))], info
 
+    # ---- ORDER BY: typed, string and mixed keys to a row map (hmj_order_by_device) ---------------------------
+    def order_by_device(self, cols, n=None):
+        """A stable multi-column ORDER BY (hmj_order_by_device).  cols: a list of (column, flags[, valid[, bit_offset]]) --
+        column a contiguous 1-D device tensor of an integer or float dtype of 1 to 8 bytes (the HMJ_TYPE_* is inferred), or a
+        (chars, offsets) pair as `pack_strings` makes it (an Arrow large_string column: chars uint8 or None, offsets int64
+        [n + 1]); flags HMJ_ORDER_DESC | HMJ_ORDER_NULLS_FIRST bits; valid None or a contiguous 1-D device tensor holding the
+        column's Arrow bitmap (`pack_validity`), row i at bit bit_offset + i.  n: the rows (default: the first column's).
+        Returns (row map: a new int64 device tensor of n entries, map[j] = the row at sorted position j, {"n_distinct",
+        "n_tied_rows", "n_rounds", "ms_key", "ms_sort", "ms_refine", "ms_map"}); `expected_order_by` reproduces the map, and
+        `take_cols_device` / `take_str_device` consume it."""
+        torch = self._torch
+        self._sync_stream()
+        cols = [tuple(c) for c in cols]
+        if n is None and cols:
+            first = cols[0][0]
+            n = first[1].shape[0] - 1 if isinstance(first, (tuple, list)) else first.shape[0]
+        n = int(n or 0)
+        arr = (_lib.OrderCol * max(len(cols), 1))()
+        keep = []
+        for k, c in enumerate(cols):
+            col, flags = c[0], int(c[1]) if len(c) > 1 else 0
+            v = c[2] if len(c) > 2 else None
+            off = int(c[3]) if len(c) > 3 else 0
+            if isinstance(col, (tuple, list)):
+                chars, offsets = col
+                _check_col(offsets, "column %d: offsets" % k)
+                arr[k].type = _lib.HMJ_ORDER_LARGE_STRING
+                cp = _chars_ptr(chars)
+                arr[k].data = cp.value if cp is not None else None
+                arr[k].offsets = offsets.data_ptr()
+                keep += [chars, offsets]
+            else:
+                if not col.is_cuda or not col.is_contiguous() or col.dim() != 1:
+                    raise ValueError("column %d must be a contiguous 1-D device tensor" % k)
+                arr[k].type = self._agg_type(col)
+                arr[k].data = col.data_ptr() if col.shape[0] else None
+                keep.append(col)
+            arr[k].flags = flags & 0xFFFFFFFF
+            if v is not None:
+                if not v.is_cuda or not v.is_contiguous() or v.dim() != 1:
+                    raise ValueError("column %d: valid must be a contiguous 1-D device tensor" % k)
+                if off < 0:
+                    raise ValueError("column %d: bit_offset must not be negative" % k)
+                arr[k].validity.bits = v.data_ptr() if v.shape[0] else None
+                arr[k].validity.bit_offset = off & 0xFFFFFFFFFFFFFFFF
+                keep.append(v)
+        out = torch.empty(n, dtype=torch.int64, device="cuda:%d" % self.device)
+        opts = _lib.OrderOpts()
+        opts.struct_size = C.sizeof(_lib.OrderOpts)
+        self._check(self.L.hmj_order_by_device(self.h, arr, len(cols), n, out.data_ptr() if n else None, C.byref(opts)))
+        del keep
+        info = {"n_distinct": int(opts.n_distinct), "n_tied_rows": int(opts.n_tied_rows), "n_rounds": int(opts.n_rounds)}
+        for k in ("ms_key", "ms_sort", "ms_refine", "ms_map"):
+            info[k] = float(getattr(opts, k))
+        return out, info
+
     # ---- columns through a row map (hmj_take_cols_device) ------------------------------------------------
     def take_cols_device(self, cols, row_map, valid=None, n_out=None, want_validity=True):
         """Take fixed-width columns of one relation through a row map (hmj_take_cols_device): output row i is source row
@@ -1364,6 +1420,83 @@ def expected_group_aggs(group_of_row, n_groups, aggs):
         res["null_count"] = int(ng - np.count_nonzero(res["valid"]))
         out.append(res)
     return out
+
+
+def _order_columns(columns):
+    """(values, flags[, valid]) per column -> [(values, flags, valid bools or None, is_string)], n.  values: a numpy array
+    of an integer or float dtype, or a list of bytes / str (None where the slot is NULL counts as NULL too)."""
+    out, n = [], None
+    for c in columns:
+        c = tuple(c)
+        vals, flags = c[0], int(c[1]) if len(c) > 1 else 0
+        valid = None if len(c) < 3 or c[2] is None else np.asarray(c[2], bool).ravel()
+        is_str = not isinstance(vals, np.ndarray)
+        if is_str:
+            vals = [None if v is None else (v.encode("utf-8") if isinstance(v, str) else bytes(v)) for v in vals]
+            if any(v is None for v in vals):
+                holes = np.array([v is not None for v in vals], bool)
+                valid = holes if valid is None else (valid & holes)
+        if n is None:
+            n = len(vals)
+        if len(vals) != n or (valid is not None and len(valid) != n):
+            raise ValueError("every column and every valid mask must hold n rows")
+        out.append((vals, flags, valid, is_str))
+    return out, (n or 0)
+
+
+def expected_order_by(columns):
+    """The row map hmj_order_by_device returns (include/hmj.h), restated on the host from the order rule: columns is a list
+    of (values, flags[, valid]) -- values a numpy array of an integer or float dtype, or a list of bytes (a string column);
+    flags HMJ_ORDER_* bits; valid None or n bools (True = valid).  Per column every row gets the dense rank of its value
+    among the column's valid values -- integers in their signedness, floats in IEEE order with -0.0 < +0.0 and every NaN one
+    value above +inf, strings as Python orders bytes (unsigned bytes, then length) --, reversed under HMJ_ORDER_DESC; a NULL
+    slot ranks behind all of them, or in front under HMJ_ORDER_NULLS_FIRST.  The map is the stable lexicographic order of
+    the rank tuples (ties keep ascending row index).  What lies under a NULL slot is not read.  Returns n uint64."""
+    cols, n = _order_columns(columns)
+    ranks = []
+    for vals, flags, valid, is_str in cols:
+        ok = np.ones(n, bool) if valid is None else valid
+        idx = np.nonzero(ok)[0]
+        rank = np.zeros(n, np.int64)
+        if is_str:
+            picked = [vals[i] for i in idx]
+            order = {v: k for k, v in enumerate(sorted(set(picked)))}
+            r = np.fromiter((order[v] for v in picked), dtype=np.int64, count=len(picked))
+            distinct = len(order)
+        else:
+            x = np.ascontiguousarray(vals[idx])
+            if x.dtype.kind == "f":
+                keys, nan = _float_order_keys(x)
+                x = np.where(nan, ~keys.dtype.type(0), keys)  # (no number's key is all ones)
+            uniq, r = np.unique(x, return_inverse=True)
+            r = r.astype(np.int64).ravel()
+            distinct = len(uniq)
+        if flags & _lib.HMJ_ORDER_DESC:
+            r = distinct - 1 - r
+        rank[idx] = r
+        rank[~ok] = -1 if flags & _lib.HMJ_ORDER_NULLS_FIRST else distinct
+        ranks.append(rank)
+    if n == 0:
+        return np.zeros(0, np.uint64)
+    return np.lexsort(ranks[::-1]).astype(np.uint64)  # (lexsort: the last key is the primary one; stable)
+
+
+def order_stream_bytes(columns):
+    """The length S of every row's order-preserving byte stream in hmj_order_by_device (include/hmj.h): per column one
+    marker byte when the column has a validity mask, then the value's width for a fixed column, or 8 * max(1, ceil(len / 7))
+    for a valid string and nothing for a NULL one.  hmj_order_opts.n_rounds is at most 1 + ceil(max(0, max S - 8) / 4).
+    columns as `expected_order_by` takes them.  Returns n int64."""
+    cols, n = _order_columns(columns)
+    total = np.zeros(n, np.int64)
+    for vals, _flags, valid, is_str in cols:
+        if valid is not None:
+            total += 1
+        if is_str:
+            ok = np.ones(n, bool) if valid is None else valid
+            total += np.array([8 * max(1, -(-len(vals[i]) // 7)) if ok[i] else 0 for i in range(n)], np.int64).reshape(n)
+        else:
+            total += vals.dtype.itemsize
+    return total
 
 
 def _hash_bytes(b):

@@ -1083,6 +1083,84 @@ typedef struct {
 int hmj_group_agg_device(hmj_ctx* ctx, const hmj_agg_src* src, uint32_t n_aggs, uint64_t n_rows, hmj_agg_dst* dst,
                          hmj_group_agg_opts* opts);
 
+/* ---- ordering rows by typed, string and mixed keys (ORDER BY) -------------------------------------------- */
+/* A stable multi-column ORDER BY: up to HMJ_MAX_ORDER_COLS key columns -- fixed-width columns of the ten HMJ_TYPE_* value
+ * types and Arrow large_string columns (64-bit offsets), each with its own direction, NULL placement and optional validity
+ * bitmap -- give a row map: row_map_out[j] is the index of the row at sorted position j.  The map is what
+ * hmj_take_cols_device and hmj_take_str_device consume, so `GROUP BY name ORDER BY sum(price) DESC, name` stays on the
+ * device: group -> aggregate -> order by the aggregate column and the taken key column -> take.  Every other "ordered" mode
+ * of the library sorts by (key64, tuple as unsigned integers) -- hash order for hashed and string keys; this entry is the
+ * one that orders by value.  Nothing in the reference corresponds beyond its u64 sort (radix_sort.h), which the call uses.
+ * A new entry with structs of its own: no other entry, struct, flag or path bit changes.
+ * cols is a HOST array of n_cols entries (read during the call only); everything it points to is on the device.
+ * row_map_out is caller-owned device memory of n uint64, aligned to 8.  n is at most 2^32 - 1.
+ * Order.  Rows compare column by column in the order of cols.  Within a column: two NULL slots (validity bit 0) are equal; a
+ * NULL slot sorts after every valid value, and before every valid value under HMJ_ORDER_NULLS_FIRST -- absolutely:
+ * HMJ_ORDER_DESC reverses the order of VALID values only.  Integers compare in their own signedness.  Floats compare in IEEE
+ * order with -0.0 < +0.0 (hmj_group_agg_device's rule); every NaN, whatever its sign and payload, is ONE value above +inf
+ * (so first among the valid values under HMJ_ORDER_DESC).  Strings compare as std::string::operator< does: unsigned bytes,
+ * then length; NUL and bytes >= 0x80 are ordinary bytes; a NULL string is not the empty string.  Rows equal in every column
+ * keep ascending row index: the sort is stable and the map is unique.  What lies under a NULL slot is never read (value
+ * bytes, string bytes); a string column's offsets are read for every row and must be non-decreasing under NULL slots too.
+ * Context.  The call runs on the ctx stream in a workspace of its own and returns with the map complete.  It calls
+ * hmj_sort_u64_device and shares its effects: a prepared build side is discarded, and the lifetime of the last JOIN result
+ * ends (take a join's columns before ordering them).  hmj_last_plan / hmj_last_timing keep describing the last join.  The
+ * group result and the live grouping of hmj_group_agg_device are kept.  What the sorts learn is kept under a workload
+ * signature of its own (kind 25).
+ * opts (out): n_distinct -- distinct key tuples; n_tied_rows -- rows whose whole key equals another row's; n_rounds -- sort
+ * rounds run (0 when n <= 1); with hmj_set_profiling ms_key (the key kernel), ms_sort (the first sort), ms_map (heads,
+ * active rows and the map behind the first sort), ms_refine (every later round).
+ * n == 0: HMJ_OK, nothing is written and no argument that is only checked with n > 0 is looked at.  n == 1: the map is
+ * {0}; the columns are not read (no offsets check) and no sort runs, so a prepared build side is still discarded but the
+ * last join result stays as it was.
+ * HMJ_E_ARG, found by the host before any launch (hmj_last_error names what was wrong): NULL ctx / cols / opts; NULL or
+ * misaligned row_map_out with n > 0; n_cols outside 1..HMJ_MAX_ORDER_COLS; an unknown type or flag bit; non-zero reserved /
+ * reserved2; opts->struct_size smaller than through `reserved2`; NULL or misaligned data of a fixed column with n > 0;
+ * offsets set on a fixed column, or NULL / not aligned to 8 on a string column; bit_offset + n overflowing 64 bits; more
+ * than 2^32 - 1 rows; row_map_out overlapping a column's values, offsets or bitmap (address ranges; the extent of a string
+ * column's chars is known on the device only and is not checked).  Found on the device by the key kernel, before anything
+ * follows an offset into chars, in the mixed-key join's wording (lowest-numbered offending column, first offending row):
+ * decreasing offsets, and key bytes of a VALID slot under data == NULL (a NULL slot holds no key bytes, whatever its
+ * offsets span).  The ctx stays usable after any error.
+ * How (DESIGN.md "Ordering rows (ORDER BY)").  Every row has an order-preserving byte stream whose memcmp order is the
+ * requested order: per column a marker byte when the column has a bitmap (0 / 1, the NULL side as flagged), then a fixed
+ * value big-endian (sign bit flipped; floats: negative complemented, else sign bit set, NaN all ones; zeros under a NULL
+ * slot) or a string as 8-byte blocks of 7 data bytes (zero padded) and a control byte (0xFF: the string continues, else
+ * the block's data bytes 0..7; max(1, ceil(len / 7)) blocks; nothing under a NULL slot); HMJ_ORDER_DESC complements the
+ * value bytes.  The stream is prefix-free.  order_key_kernel writes {first 8 stream bytes, row}, checks the offsets and
+ * reduces the longest stream S; hmj_sort_u64_device sorts them stably; heads, active rows (rows of a segment of several
+ * rows with stream bytes left) and active segments are ballots, one scan and one read-back.  A refinement round compacts the
+ * active rows, order_refine_kernel gathers their next b = (64 - s) / 8 stream bytes under the s bits of their segment's
+ * rank (4 <= b <= 8), one stable sort orders all segments at once, and the rows go back to their positions.  Resolved rows
+ * are never read or written again.  At most 1 + ceil(max(0, S - 8) / 4) rounds; a call that has active rows left then is
+ * HMJ_E_HIP ("refinement did not converge").
+ * Known cost: a long prefix shared by many strings costs one round per 4..8 bytes over the rows that share it (no
+ * per-segment common-prefix skip); every round is a full hmj_sort_u64_device call on its rows.
+ * Out of scope: LIMIT / top-k, 32-bit-offset strings, collations and locale, decimal128, host-resident columns, the
+ * exchange path.                                                                                                        */
+#define HMJ_ORDER_LARGE_STRING 16u /* a column type beside HMJ_TYPE_I8 ... HMJ_TYPE_F64: Arrow large_string              */
+#define HMJ_ORDER_DESC        0x1u /* descending among the valid values                                                  */
+#define HMJ_ORDER_NULLS_FIRST 0x2u /* NULL slots before every valid value (default: after)                               */
+#define HMJ_MAX_ORDER_COLS 8
+typedef struct {
+  uint32_t type;            /* HMJ_TYPE_* or HMJ_ORDER_LARGE_STRING                                                      */
+  uint32_t flags;           /* HMJ_ORDER_* bits; any other bit: HMJ_E_ARG                                                */
+  const void* data;         /* fixed: n values aligned to their width; string: chars (NULL legal when all lengths are 0) */
+  const uint64_t* offsets;  /* string: n + 1 non-decreasing offsets, offsets[0] need not be 0; fixed: NULL               */
+  hmj_validity validity;    /* bits == NULL: no NULL in the column; any bit_offset                                       */
+} hmj_order_col;
+typedef struct {
+  uint32_t struct_size;     /* size-versioned like the other opts                                                        */
+  uint32_t reserved;        /* 0                                                                                         */
+  uint64_t n_distinct;      /* out: distinct key tuples (0 when n == 0)                                                  */
+  uint64_t n_tied_rows;     /* out: rows whose whole key equals another row's                                            */
+  uint32_t n_rounds;        /* out: sort rounds run (0 when n <= 1)                                                      */
+  uint32_t reserved2;       /* 0                                                                                         */
+  float ms_key, ms_sort, ms_refine, ms_map; /* out, with hmj_set_profiling                                               */
+} hmj_order_opts;
+int hmj_order_by_device(hmj_ctx* ctx, const hmj_order_col* cols, uint32_t n_cols, uint64_t n, uint64_t* row_map_out,
+                        hmj_order_opts* opts);
+
 /* ---- taking fixed-width columns through a row map (Arrow validity out) --------------------------------- */
 /* The joins above return gather maps (r_row / s_row), not columns.  This entry turns a map back into Arrow columns: up to
  * HMJ_MAX_TAKE_COLS fixed-width columns of ONE relation (n_src rows each; keys, payloads, anything of 1, 2, 4, 8 or 16
