@@ -11,8 +11,9 @@ from ._lib import (HMJ_AGG_COUNT, HMJ_AGG_MAX, HMJ_AGG_MEAN, HMJ_AGG_MIN, HMJ_AG
                    HMJ_PATH_KEY_RANGES, HMJ_PATH_PREPARED, HMJ_PATH_PRESORTED, HMJ_PATH_RANK_RUNS, HMJ_PATH_SORT_MSD, HMJ_PATH_SLAB, HMJ_PATH_SLAB_ONE_PASS, HMJ_PATH_SLAB_PROBE, HMJ_PATH_SORTED_FK, HMJ_PATH_SORTED_FK_HALF, HMJ_PATH_SORTED_FK_WIDE, HMJ_PATH_SORTED_WRITE, HMJ_PATH_SPLIT, HMJ_PATH_UNIQ_WRITE, HMJ_PATH_WINDOW,
                    HMJ_KEY_FIXED, HMJ_KEY_LARGE_STRING, HMJ_MAX_KEY_COLS, HMJ_MAX_TAKE_COLS, HMJ_NULL_EQUAL, HMJ_STR_NO_ROW, HMJ_SUM_PROBE, HMJ_TAKE_NO_ROW, BuildJoinOpts, ColsJoinOpts, ColsKindOpts, ColsRel, ColsResult, ExchangeKindOpts, GroupOpts, GroupResult, HmjError, JoinOpts, JoinResult, KeyCol, KindCounts, MixedCol, MixedOpts, MixedRel, StrJoinOpts, StrKindOpts, StrRel, StrResult, TakeDst, TakeOpts, TakeSrc, TakeStrDst, TakeStrOpts, TakeStrSrc, Timing, Validity,
                    HMJ_MAX_ORDER_COLS, HMJ_ORDER_DESC, HMJ_ORDER_LARGE_STRING, HMJ_ORDER_NULLS_FIRST, OrderCol, OrderOpts,
+                   HMJ_FILTER_LARGE_STRING, HMJ_FILTER_EQ, HMJ_FILTER_NE, HMJ_FILTER_LT, HMJ_FILTER_LE, HMJ_FILTER_GT, HMJ_FILTER_GE, HMJ_FILTER_BETWEEN, HMJ_FILTER_IS_NULL, HMJ_FILTER_IS_NOT_NULL, HMJ_FILTER_STARTS_WITH, HMJ_FILTER_ENDS_WITH, HMJ_FILTER_NOT, HMJ_MAX_FILTER_TERMS, HMJ_MAX_FILTER_LITERAL_BYTES, FilterTerm, FilterOpts,
                    lib_path, load_library)
-from .join import Executor, HashMergeJoin, cols_key64, expected_group_aggs, expected_groups, expected_mixed_groups, expected_order_by, mixed_key64, order_stream_bytes, pack_strings, pack_validity, plan, unpack_strings, unpack_validity
+from .join import Executor, HashMergeJoin, cols_key64, expected_group_aggs, expected_groups, expected_filter, expected_mixed_groups, expected_order_by, mixed_key64, order_stream_bytes, pack_strings, pack_validity, plan, unpack_strings, unpack_validity
 
 __all__ = ["Executor", "HashMergeJoin", "plan", "HmjError", "JoinResult", "Timing", "load_library",
            "lib_path", "HMJ_MATERIALIZE", "HMJ_ORDERED", "HMJ_FIRST_WINS", "HMJ_CHECKSUM",
@@ -32,4 +33,6 @@ __all__ = ["Executor", "HashMergeJoin", "plan", "HmjError", "JoinResult", "Timin
            "HMJ_TYPE_I8", "HMJ_TYPE_I16", "HMJ_TYPE_I32", "HMJ_TYPE_I64", "HMJ_TYPE_U8", "HMJ_TYPE_U16", "HMJ_TYPE_U32",
            "HMJ_TYPE_U64", "HMJ_TYPE_F32", "HMJ_TYPE_F64", "HMJ_MAX_AGGS", "expected_group_aggs",
            "OrderCol", "OrderOpts", "HMJ_ORDER_LARGE_STRING", "HMJ_ORDER_DESC", "HMJ_ORDER_NULLS_FIRST", "HMJ_MAX_ORDER_COLS",
-           "expected_order_by", "order_stream_bytes"]
+           "expected_order_by", "order_stream_bytes",
+           "HMJ_FILTER_LARGE_STRING", "HMJ_FILTER_EQ", "HMJ_FILTER_NE", "HMJ_FILTER_LT", "HMJ_FILTER_LE", "HMJ_FILTER_GT", "HMJ_FILTER_GE", "HMJ_FILTER_BETWEEN",
+           "HMJ_FILTER_IS_NULL", "HMJ_FILTER_IS_NOT_NULL", "HMJ_FILTER_STARTS_WITH", "HMJ_FILTER_ENDS_WITH", "HMJ_FILTER_NOT", "HMJ_MAX_FILTER_TERMS", "HMJ_MAX_FILTER_LITERAL_BYTES", "FilterTerm", "FilterOpts", "expected_filter"]

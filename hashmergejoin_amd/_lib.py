@@ -277,6 +277,34 @@ class OrderOpts(C.Structure):
                 ("ms_refine", C.c_float), ("ms_map", C.c_float)]
 
 
+# hmj_filter_device: a CNF predicate over typed and string columns to a row map (WHERE); hmj_filter_term.type (beside
+# HMJ_TYPE_*), .op and .flags, and the two caps of a call
+HMJ_FILTER_LARGE_STRING = 16
+(HMJ_FILTER_EQ, HMJ_FILTER_NE, HMJ_FILTER_LT, HMJ_FILTER_LE, HMJ_FILTER_GT, HMJ_FILTER_GE, HMJ_FILTER_BETWEEN, HMJ_FILTER_IS_NULL,
+ HMJ_FILTER_IS_NOT_NULL, HMJ_FILTER_STARTS_WITH, HMJ_FILTER_ENDS_WITH) = range(11)
+HMJ_FILTER_NOT = 0x1
+HMJ_MAX_FILTER_TERMS = 16
+HMJ_MAX_FILTER_LITERAL_BYTES = 4096
+
+
+class FilterTerm(C.Structure):
+    """hmj_filter_term: one column on the device -- n_src values of a HMJ_TYPE_* aligned to their width, or (type
+    HMJ_FILTER_LARGE_STRING) chars_bytes chars and n_src + 1 64-bit offsets --, its validity bitmap (bits NULL: no NULL), the
+    row map the term reads it through (NULL: position i reads row i), one HMJ_FILTER_* op with HMJ_FILTER_NOT or not, the
+    clause the term belongs to, and the literals: lit for a fixed column (the value's bits in the low bytes), str_lit /
+    str_len (HOST pointers) for a string column."""
+    _fields_ = [("type", C.c_uint32), ("op", C.c_uint32), ("flags", C.c_uint32), ("clause", C.c_uint32), ("data", C.c_void_p),
+                ("offsets", C.c_void_p), ("chars_bytes", C.c_uint64), ("validity", Validity), ("n_src", C.c_uint64),
+                ("row_map", C.c_void_p), ("lit", C.c_uint64 * 2), ("str_lit", C.c_void_p * 2), ("str_len", C.c_uint64 * 2),
+                ("reserved", C.c_uint64)]
+
+
+class FilterOpts(C.Structure):
+    """hmj_filter_opts: the positions at which the predicate is TRUE and UNKNOWN, and the phase times (out)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("n_out", C.c_uint64), ("n_unknown", C.c_uint64),
+                ("ms_eval", C.c_float), ("ms_write", C.c_float), ("reserved2", C.c_uint64)]
+
+
 # hmj_take_cols_device: fixed-width columns taken through a row map (a join's r_row / s_row)
 HMJ_TAKE_NO_ROW = 0xFFFFFFFFFFFFFFFF
 HMJ_MAX_TAKE_COLS = 64
@@ -484,6 +512,8 @@ def load_library():
     L.hmj_group_agg_device.argtypes = [vp, C.POINTER(AggSrc), C.c_uint32, u, C.POINTER(AggDst), C.POINTER(GroupAggOpts)]
     L.hmj_order_by_device.restype = i
     L.hmj_order_by_device.argtypes = [vp, C.POINTER(OrderCol), C.c_uint32, u, vp, C.POINTER(OrderOpts)]
+    L.hmj_filter_device.restype = i
+    L.hmj_filter_device.argtypes = [vp, C.POINTER(FilterTerm), C.c_uint32, u, vp, vp, C.POINTER(FilterOpts)]
     L.hmj_take_cols_device.restype = i
     L.hmj_take_cols_device.argtypes = [vp, C.POINTER(TakeSrc), C.c_uint32, u, vp, u, C.POINTER(TakeDst), C.POINTER(TakeOpts)]
     L.hmj_take_str_device.restype = i

@@ -3122,7 +3122,8 @@ void hmj_destroy(hmj_ctx* c) {
                     &c->slab_a, &c->slab_br, &c->slab_bs, &c->cnt_a, &c->cnt_br, &c->cnt_bs, &c->lookback, &c->gtab, &c->piece_off,
                     &c->split_r, &c->split_s, &c->split_off, &c->cat_key, &c->cat_rval, &c->cat_sval, &c->msd_off,
                     &c->bmatched, &c->bsweep, &c->take_acc, &c->takestr_acc, &c->takestr_blk,
-                    &c->agg_acc, &c->agg_grp, &c->agg_part};
+                    &c->agg_acc, &c->agg_grp, &c->agg_part,
+                    &c->filter_acc, &c->filter_blk, &c->filter_tile, &c->filter_mask, &c->filter_lit};
   for (DevBuf* b : devs) free_dev(*b);
   for (KeyJoinWs* ws : {&c->str_ws, &c->col_ws, &c->mix_ws}) {
     ws->each_buf(free_dev);
@@ -3147,6 +3148,8 @@ void hmj_destroy(hmj_ctx* c) {
   for (auto& e : c->takestr_ev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : c->agg_ev)
+    if (e) (void)hipEventDestroy(e);
+  for (auto& e : c->filter_ev)
     if (e) (void)hipEventDestroy(e);
   for (auto& st : c->up_streams) (void)hipStreamDestroy(st);
   for (auto& e : c->copy_ev) (void)hipEventDestroy(e);

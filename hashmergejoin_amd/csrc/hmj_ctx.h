@@ -178,7 +178,12 @@ struct hmj_ctx {
       takestr_acc, takestr_blk,
       // hmj_group_agg_device (groupagg.hip): its NULL counters, the accumulator and valid-count slots per group of one
       // launch chunk of aggregates, and the partial slots per wave of the walk -- the only workspace the call owns
-      agg_acc, agg_grp, agg_part;
+      agg_acc, agg_grp, agg_part,
+      // hmj_filter_device (filter.hip): its counters, the {TRUE, UNKNOWN} counts per workgroup of 256 positions (scanned in
+      // place), the totals per scan tile followed by their exclusive scan, the mask words of a call without mask_out, and
+      // the string literals -- the only workspace the call owns
+      filter_acc, filter_blk, filter_tile, filter_mask, filter_lit;
+  std::vector<unsigned char> filter_lit_host;  // the literals on their way to filter_lit (lives until the call's last sync)
   // string joins (strjoin.hip), multi-column joins (coljoin.hip) and mixed-key joins (mixjoin.hip): one workspace each, so
   // that no call reuses or regrows another's buffers
   hmj_host::KeyJoinWs str_ws, col_ws, mix_ws;
@@ -187,6 +192,7 @@ struct hmj_ctx {
   hipEvent_t take_ev[2] = {nullptr, nullptr};  // hmj_take_cols_device: around its launches (profiling)
   hipEvent_t takestr_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // hmj_take_str_device: around its offsets and its bytes phase
   hipEvent_t agg_ev[2] = {nullptr, nullptr};  // hmj_group_agg_device: around its launches (profiling)
+  hipEvent_t filter_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // hmj_filter_device: around its evaluation and its write phase
   int memo_kind = 0;  // workload-signature kind of plain inner joins run on behalf of another entry (string, multi-column joins and their kinds), and of the sorts hmj_order_by_device runs
   HostBuf h_accum, h_key, h_rval, h_sval;
   int host_threads = 0;  // staging threads for pageable input (0 = default)

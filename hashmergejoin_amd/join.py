@@ -740,6 +740,105 @@ class Executor:
             info[k] = float(getattr(opts, k))
         return out, info
 
+    # ---- WHERE: typed and string predicates to a row map (hmj_filter_device) ---------------------------------
+    def filter_device(self, terms, n=None, want_mask=False, out=None):
+        """Select the positions at which a predicate is TRUE (hmj_filter_device).  terms: a list of dicts {"column", "op",
+        "lit", "valid", "bit_offset", "row_map", "clause", "negate"} or of tuples in that order (everything behind op
+        optional).  column: a contiguous 1-D device tensor of an integer or float dtype of 1 to 8 bytes (the HMJ_TYPE_* is
+        inferred), or a (chars, offsets) pair as `pack_strings` makes it; op: an HMJ_FILTER_* code; lit: a number converted
+        to the column's dtype (no cast happens on the device), bytes / str for a string column, a pair of them for
+        HMJ_FILTER_BETWEEN, None for IS_NULL / IS_NOT_NULL; valid: None or the column's Arrow bitmap (`pack_validity`), row i
+        at bit bit_offset + i; row_map: None (position i reads row i), a contiguous 1-D int64 device tensor or a
+        (device_pointer, n) pair -- a result's r_row / s_row --, HMJ_TAKE_NO_ROW entries reading as NULL; clause: terms of
+        one clause are ORed, clauses ANDed, ids never decreasing (default 0); negate: HMJ_FILTER_NOT.  n: the positions
+        (default: the first term's map length, else its column's rows).  out: None, or an int64 device tensor of at least n
+        entries to write the map into.  Returns (the row map trimmed to n_out -- a view of an n-entry tensor, nothing at or
+        behind n_out is written --, an int64 tensor of ceil(n / 64) mask words or None, {"n_out", "n_unknown", "ms_eval",
+        "ms_write"}); `expected_filter` reproduces the map, `take_cols_device` / `take_str_device` consume it."""
+        torch = self._torch
+        self._sync_stream()
+        keys = ("column", "op", "lit", "valid", "bit_offset", "row_map", "clause", "negate")
+        terms = [t if isinstance(t, dict) else dict(zip(keys, t)) for t in terms]
+        arr = (_lib.FilterTerm * max(len(terms), 1))()
+        keep = []
+        names = ("int8", "int16", "int32", "int64", "uint8", "uint16", "uint32", "uint64", "float32", "float64")
+        first_n = None
+        for k, t in enumerate(terms):
+            col, op = t["column"], int(t["op"])
+            lit = t.get("lit")
+            lits = [] if lit is None else (list(lit) if isinstance(lit, (tuple, list)) else [lit])
+            if len(lits) > 2:
+                raise ValueError("term %d: at most two literals" % k)
+            rm = t.get("row_map")
+            if rm is None:
+                map_n = None
+            elif isinstance(rm, tuple):
+                arr[k].row_map, map_n = int(rm[0] or 0) or None, int(rm[1])
+            else:
+                if not rm.is_cuda or not rm.is_contiguous() or rm.dim() != 1 or rm.dtype != torch.int64:
+                    raise ValueError("term %d: row_map must be a contiguous 1-D int64 device tensor" % k)
+                arr[k].row_map, map_n = (rm.data_ptr() if rm.shape[0] else None), rm.shape[0]
+                keep.append(rm)
+            if isinstance(col, (tuple, list)):
+                chars, offsets = col
+                _check_col(offsets, "term %d: offsets" % k)
+                if offsets.shape[0] < 1:
+                    raise ValueError("term %d: offsets must hold n + 1 entries" % k)
+                arr[k].type = _lib.HMJ_FILTER_LARGE_STRING
+                cp = _chars_ptr(chars)
+                arr[k].data = cp.value if cp is not None else None
+                arr[k].chars_bytes = chars.numel() if cp is not None else 0
+                arr[k].offsets = offsets.data_ptr()
+                n_src = offsets.shape[0] - 1
+                keep += [chars, offsets]
+                for j, v in enumerate(lits):
+                    b = v.encode("utf-8") if isinstance(v, str) else bytes(v)
+                    buf = C.create_string_buffer(b, max(len(b), 1))
+                    arr[k].str_lit[j] = C.addressof(buf) if b else None
+                    arr[k].str_len[j] = len(b)
+                    keep.append(buf)
+            else:
+                if not col.is_cuda or not col.is_contiguous() or col.dim() != 1:
+                    raise ValueError("term %d: the column must be a contiguous 1-D device tensor" % k)
+                code = self._agg_type(col)
+                arr[k].type = code
+                arr[k].data = col.data_ptr() if col.shape[0] else None
+                n_src = col.shape[0]
+                keep.append(col)
+                dt = np.dtype(names[code])
+                for j, v in enumerate(lits):
+                    arr[k].lit[j] = int(np.array([v], dtype=dt).view("u%d" % dt.itemsize)[0])
+            arr[k].n_src = n_src
+            arr[k].op = op & 0xFFFFFFFF
+            arr[k].flags = _lib.HMJ_FILTER_NOT if t.get("negate") else 0
+            arr[k].clause = int(t.get("clause") or 0)
+            v, off = t.get("valid"), int(t.get("bit_offset") or 0)
+            if v is not None:
+                if not v.is_cuda or not v.is_contiguous() or v.dim() != 1:
+                    raise ValueError("term %d: valid must be a contiguous 1-D device tensor" % k)
+                if off < 0:
+                    raise ValueError("term %d: bit_offset must not be negative" % k)
+                arr[k].validity.bits = v.data_ptr() if v.shape[0] else None
+                arr[k].validity.bit_offset = off & 0xFFFFFFFFFFFFFFFF
+                keep.append(v)
+            if first_n is None:
+                first_n = n_src if map_n is None else map_n
+        n = int((first_n or 0) if n is None else n)
+        dev = "cuda:%d" % self.device
+        if out is None:
+            out = torch.empty(n, dtype=torch.int64, device=dev)
+        elif not out.is_cuda or not out.is_contiguous() or out.dim() != 1 or out.dtype != torch.int64 or out.shape[0] < n:
+            raise ValueError("out must be a contiguous 1-D int64 device tensor of at least n entries")
+        words = torch.empty((n + 63) // 64, dtype=torch.int64, device=dev) if want_mask else None
+        opts = _lib.FilterOpts()
+        opts.struct_size = C.sizeof(_lib.FilterOpts)
+        self._check(self.L.hmj_filter_device(self.h, arr, len(terms), n, out.data_ptr() if n else None,
+                                             words.data_ptr() if (words is not None and n) else None, C.byref(opts)))
+        del keep
+        info = {"n_out": int(opts.n_out), "n_unknown": int(opts.n_unknown), "ms_eval": float(opts.ms_eval),
+                "ms_write": float(opts.ms_write)}
+        return out[:info["n_out"]], words, info
+
     # ---- columns through a row map (hmj_take_cols_device) ------------------------------------------------
     def take_cols_device(self, cols, row_map, valid=None, n_out=None, want_validity=True):
         """Take fixed-width columns of one relation through a row map (hmj_take_cols_device): output row i is source row
@@ -1497,6 +1596,107 @@ def order_stream_bytes(columns):
         else:
             total += vals.dtype.itemsize
     return total
+
+
+def expected_filter(terms, n):
+    """What hmj_filter_device returns (include/hmj.h), restated on the host: terms as `Executor.filter_device` takes them
+    (dicts, or tuples (column, op, lit, valid, bit_offset, row_map, clause, negate)) with host values -- column a numpy
+    array of an integer or float dtype, or a list of bytes / str (None: a NULL slot); lit as there; valid None or one bool
+    per ROW of the column (True = valid; bit_offset is not looked at); row_map None or n entries (uint64 or int64,
+    HMJ_TAKE_NO_ROW / -1 a NULL slot).  Every term is numpy's own comparison operator on the column's dtype (C's operators:
+    IEEE for floats) or Python's comparison of `bytes` (unsigned bytes, then length), made three-valued -- UNKNOWN on a NULL
+    slot except for IS_NULL / IS_NOT_NULL, negation swapping TRUE and FALSE --; a clause is the maximum of its terms and the
+    predicate the minimum of its clauses under FALSE < UNKNOWN < TRUE.  What lies under a NULL slot is not read.  Returns
+    (the positions at which the predicate is TRUE, ascending, n uint64 at most; the number of UNKNOWN positions)."""
+    keys = ("column", "op", "lit", "valid", "bit_offset", "row_map", "clause", "negate")
+    F, U, T = 0, 1, 2
+    n = int(n)
+    pred = np.full(n, T, np.int8)
+    cl, cl_id = None, None
+    for k, t in enumerate(terms):
+        t = t if isinstance(t, dict) else dict(zip(keys, t))
+        vals, op = t["column"], int(t["op"])
+        lit = t.get("lit")
+        lits = [] if lit is None else (list(lit) if isinstance(lit, (tuple, list)) else [lit])
+        is_str = not isinstance(vals, np.ndarray)
+        n_src = len(vals)
+        rm = t.get("row_map")
+        if rm is None:
+            if n_src < n:
+                raise ValueError("term %d: n_src < n without a row_map" % k)
+            have, rows = np.ones(n, bool), np.arange(n, dtype=np.int64)
+        else:
+            rm = np.asarray(rm).astype(np.uint64)[:n]
+            if len(rm) != n:
+                raise ValueError("term %d: row_map must hold n entries" % k)
+            have = rm != np.uint64(_lib.HMJ_TAKE_NO_ROW)
+            if np.any(have & (rm >= np.uint64(n_src))):
+                raise ValueError("term %d: a row_map entry is >= n_src and not HMJ_TAKE_NO_ROW" % k)
+            rows = np.where(have, rm, np.uint64(0)).astype(np.int64)
+        ok = have.copy()
+        valid = t.get("valid")
+        if is_str:
+            vals = [None if v is None else (v.encode("utf-8") if isinstance(v, str) else bytes(v)) for v in vals]
+            holes = np.array([v is not None for v in vals], bool)
+            valid = holes if valid is None else (np.asarray(valid, bool).ravel() & holes)
+        if valid is not None:
+            valid = np.asarray(valid, bool).ravel()
+            if len(valid) != n_src:
+                raise ValueError("term %d: valid must hold one entry per row of the column" % k)
+            ok[have] = valid[rows[have]]
+        if op == _lib.HMJ_FILTER_IS_NULL:
+            v = np.where(ok, F, T)
+        elif op == _lib.HMJ_FILTER_IS_NOT_NULL:
+            v = np.where(ok, T, F)
+        else:
+            if len(lits) != (2 if op == _lib.HMJ_FILTER_BETWEEN else 1):
+                raise ValueError("term %d: the op takes %d literal(s)" % (k, 2 if op == _lib.HMJ_FILTER_BETWEEN else 1))
+            idx = np.nonzero(ok)[0]
+            res = np.zeros(n, bool)
+            if is_str:
+                ls = [x.encode("utf-8") if isinstance(x, str) else bytes(x) for x in lits]
+                fn = {_lib.HMJ_FILTER_EQ: lambda s: s == ls[0], _lib.HMJ_FILTER_NE: lambda s: s != ls[0],
+                      _lib.HMJ_FILTER_LT: lambda s: s < ls[0], _lib.HMJ_FILTER_LE: lambda s: s <= ls[0],
+                      _lib.HMJ_FILTER_GT: lambda s: s > ls[0], _lib.HMJ_FILTER_GE: lambda s: s >= ls[0],
+                      _lib.HMJ_FILTER_BETWEEN: lambda s: ls[0] <= s and s <= ls[1],
+                      _lib.HMJ_FILTER_STARTS_WITH: lambda s: s.startswith(ls[0]),
+                      _lib.HMJ_FILTER_ENDS_WITH: lambda s: s.endswith(ls[0])}[op]
+                res[idx] = [bool(fn(vals[r])) for r in rows[idx]]
+            else:
+                x = vals[rows[idx]]
+                ls = [np.array([v], dtype=vals.dtype)[0] for v in lits]
+                with np.errstate(invalid="ignore"):
+                    if op == _lib.HMJ_FILTER_EQ:
+                        r = x == ls[0]
+                    elif op == _lib.HMJ_FILTER_NE:
+                        r = x != ls[0]
+                    elif op == _lib.HMJ_FILTER_LT:
+                        r = x < ls[0]
+                    elif op == _lib.HMJ_FILTER_LE:
+                        r = x <= ls[0]
+                    elif op == _lib.HMJ_FILTER_GT:
+                        r = x > ls[0]
+                    elif op == _lib.HMJ_FILTER_GE:
+                        r = x >= ls[0]
+                    elif op == _lib.HMJ_FILTER_BETWEEN:
+                        r = (ls[0] <= x) & (x <= ls[1])
+                    else:
+                        raise ValueError("term %d: op %d does not apply to a fixed-width column" % (k, op))
+                res[idx] = r
+            v = np.where(ok, np.where(res, T, F), U)
+        v = v.astype(np.int8)
+        if t.get("negate"):
+            v = (T - v).astype(np.int8)
+        cid = int(t.get("clause") or 0)
+        if cl is not None and cid != cl_id:
+            if cid < cl_id:
+                raise ValueError("term %d: clause ids must not decrease" % k)
+            pred = np.minimum(pred, cl)
+            cl = None
+        cl, cl_id = (v if cl is None else np.maximum(cl, v)), cid
+    if cl is not None:
+        pred = np.minimum(pred, cl)
+    return np.nonzero(pred == T)[0].astype(np.uint64), int(np.count_nonzero(pred == U))
 
 
 def _hash_bytes(b):

@@ -1286,6 +1286,111 @@ typedef struct {
 typedef struct { uint32_t struct_size, reserved; uint64_t n_no_row; float ms_offsets, ms_chars; } hmj_take_str_opts;
 int hmj_take_str_device(hmj_ctx* ctx, const hmj_take_str_src* src, uint64_t n_src, const uint64_t* row_map,
                         uint64_t n_out, hmj_take_str_dst* dst, hmj_take_str_opts* opts);
+
+/* ---- filtering rows: typed and string predicates to a row map (WHERE) ---------------------------------- */
+/* Selection: a predicate in conjunctive normal form over up to HMJ_MAX_FILTER_TERMS terms -- each one column, one
+ * comparison and its literal(s) -- is evaluated at n input positions, and the positions at which it is TRUE come back as
+ * a row map, the one hmj_take_cols_device and hmj_take_str_device consume, with an optional Arrow bitmap of the same
+ * fact.  Every term reads its column either directly (position i reads row i) or through a row map of its own, so a
+ * predicate behind a join names columns of R through r_row and columns of S through s_row in one call:
+ * `... FULL OUTER JOIN ... WHERE s.key IS NULL` is one IS_NULL term through s_row.  Nothing in the reference corresponds.
+ * A new entry with structs of its own: no other entry, struct, flag or path bit changes.
+ * terms is a HOST array of n_terms entries (read during the call only); everything a term points to is on the device,
+ * except the string literals (host pointers, copied by the call).  n is at most 2^32 - 1.
+ * Outputs.  row_map_out: caller-owned device memory of n uint64, aligned to 8; exactly opts->n_out entries are written,
+ * the passing positions in ascending order (the compaction is stable); no entry at or behind n_out is written.  mask_out:
+ * a device pointer aligned to 8, or NULL; when set, ceil(n / 64) words are written, an Arrow bitmap at bit offset 0 whose
+ * bit i is 1 when position i passes, padding bits 0, exactly as hmj_take_dst's.  opts (out): n_out; n_unknown -- the
+ * positions whose predicate is UNKNOWN (the FALSE count is n - n_out - n_unknown); with hmj_set_profiling ms_eval (the
+ * evaluation and the scan) and ms_write (the map).
+ * A term.  type: HMJ_TYPE_I8 ... HMJ_TYPE_F64 (data: n_src values aligned to their width) or HMJ_FILTER_LARGE_STRING
+ * (data: the chars, chars_bytes of them; offsets: n_src + 1 64-bit offsets, offsets[0] need not be 0).  validity: any
+ * bit_offset; bits == NULL: the column has no NULL.  row_map: NULL -- position i reads row i, and n_src >= n --, or n
+ * entries on the device -- position i reads row row_map[i], HMJ_TAKE_NO_ROW is a NULL slot --; the maps may be the ctx's
+ * own result columns.  op: HMJ_FILTER_EQ, NE, LT, LE, GT, GE, BETWEEN (closed, two literals), IS_NULL, IS_NOT_NULL and, on
+ * strings only, STARTS_WITH and ENDS_WITH.  flags: HMJ_FILTER_NOT.  clause: terms of one clause are ORed, the clauses are
+ * ANDed; clause ids must not decrease along terms; an IN-list is a clause of EQ terms.  Literals: a fixed column's are
+ * lit[0] (and lit[1] for BETWEEN), the value's bits in the column's own type in the low bytes -- no casts are performed,
+ * and bits that do not fit the width are HMJ_E_ARG --; a string column's are str_lit[k] / str_len[k], host pointers (NULL
+ * with length 0 is the empty string), at most HMJ_MAX_FILTER_LITERAL_BYTES over all terms of a call.  The literals of
+ * IS_NULL / IS_NOT_NULL are not looked at.
+ * Semantics.  Three-valued logic: a comparison on a NULL slot is UNKNOWN; IS_NULL and IS_NOT_NULL are never UNKNOWN;
+ * HMJ_FILTER_NOT swaps TRUE and FALSE and leaves UNKNOWN; OR is the maximum and AND the minimum under FALSE < UNKNOWN <
+ * TRUE; a position passes only when the whole predicate is TRUE.  Integers compare in their own signedness.  Floats
+ * compare as C's operators do, which is IEEE: -0.0 == +0.0, and a NaN on either side makes every comparison FALSE except
+ * NE, which is TRUE -- deliberately NOT the total order of hmj_order_by_device (there -0.0 < +0.0 and NaN is one value
+ * above +inf): a caller who writes `x = 0.0` wants both zeros.  BETWEEN lo, hi is lo <= x && x <= hi (lo > hi selects
+ * nothing).  Strings compare as std::string::operator< does: unsigned bytes, then length -- the ORDER BY rule; NUL and
+ * bytes >= 0x80 are ordinary bytes; a NULL string is not the empty string; STARTS_WITH "" is TRUE for every valid slot.
+ * What lies under a NULL slot is never read: value bytes, string bytes and the offsets of that row.
+ * Errors, all HMJ_E_ARG (hmj_last_error names what was wrong; the ctx stays usable).  Found on the host before any
+ * launch: NULL ctx / terms / opts; n_terms outside 1..HMJ_MAX_FILTER_TERMS; an unknown type, op or flag bit; a string-only
+ * op on a fixed column; decreasing clause ids; non-zero reserved fields, opts->struct_size smaller than through
+ * `reserved2`; NULL or misaligned data, offsets, row_map, row_map_out or mask_out where n > 0 needs them (chars need no
+ * alignment and may be NULL when chars_bytes is 0; offsets on a fixed column); bit_offset + n_src overflowing 64 bits; n
+ * or n_src above 2^32 - 1; n_src < n without a map; a literal that does not fit its width; literal bytes over the cap; an
+ * output range (map or mask) that overlaps any input range of the call or the other output (address ranges, as the takes
+ * check them).  Found on the device, and never a fault: a map entry >= n_src that is not HMJ_TAKE_NO_ROW, and a read
+ * valid string row with offsets[r + 1] < offsets[r] or offsets[r + 1] > chars_bytes; each is compared before any address is
+ * formed from it, such a lane counts as UNKNOWN, the write phase does not run, and hmj_last_error gives the counts.  The
+ * outputs are unspecified after an error.  n == 0 is HMJ_OK with nothing written on the device.
+ * Context.  The takes' rules, because the maps may be the live result's own: the call keeps the last join result, a
+ * prepared build side, the group result, the live grouping, hmj_last_plan, hmj_last_timing and the workload memos; its
+ * workspace is its own, kept on the ctx, grown on demand and released by hmj_destroy; it returns with the work complete
+ * on the ctx stream.
+ * How (DESIGN.md "Filtering rows (WHERE)").  filter_eval_kernel: one lane per position in blocks of 256 positions that
+ * start at multiples of 256; a 256-thread workgroup walks 8 consecutive blocks, 4 at a time, so that a lane has 4 loads
+ * in flight at every step; the terms are kernel arguments, the string literals sit in LDS, the term list is unrolled
+ * for 1, 2, 4, 8 or 16 terms; a lane loads each distinct map's entry once (the first four distinct maps; a term on a
+ * later one loads its own), walks the terms with a running clause maximum and predicate minimum, and the wave's ballot of
+ * TRUE is one mask word (to mask_out, or to the workspace); TRUE and UNKNOWN popcounts go to a slot per block, the
+ * error counters take one atomic per workgroup.  A two-level scan of the slots (no workgroup waits on another), one
+ * counter read-back, then filter_write_kernel ranks every set bit of the mask words inside its block, adds the
+ * block's base and stores the position.
+ * Out of scope: LIKE / CONTAINS / regular expressions, column-to-column comparisons, casts, decimal128, 32-bit-offset
+ * strings, host-resident columns, the exchange path.                                                                  */
+#define HMJ_FILTER_LARGE_STRING 16u /* == HMJ_ORDER_LARGE_STRING: a column type beside HMJ_TYPE_I8 ... HMJ_TYPE_F64        */
+#define HMJ_FILTER_EQ 0u
+#define HMJ_FILTER_NE 1u
+#define HMJ_FILTER_LT 2u
+#define HMJ_FILTER_LE 3u
+#define HMJ_FILTER_GT 4u
+#define HMJ_FILTER_GE 5u
+#define HMJ_FILTER_BETWEEN 6u      /* lit[0] <= x && x <= lit[1]                                                          */
+#define HMJ_FILTER_IS_NULL 7u
+#define HMJ_FILTER_IS_NOT_NULL 8u
+#define HMJ_FILTER_STARTS_WITH 9u  /* strings only                                                                        */
+#define HMJ_FILTER_ENDS_WITH 10u   /* strings only                                                                        */
+#define HMJ_FILTER_NOT 0x1u        /* hmj_filter_term.flags: swaps TRUE and FALSE, leaves UNKNOWN                         */
+#define HMJ_MAX_FILTER_TERMS 16
+#define HMJ_MAX_FILTER_LITERAL_BYTES 4096
+typedef struct {
+  uint32_t type;            /* HMJ_TYPE_* or HMJ_FILTER_LARGE_STRING                                                     */
+  uint32_t op;              /* HMJ_FILTER_EQ ... HMJ_FILTER_ENDS_WITH                                                    */
+  uint32_t flags;           /* HMJ_FILTER_NOT; any other bit: HMJ_E_ARG                                                  */
+  uint32_t clause;          /* terms of one clause are ORed, clauses ANDed; never decreasing along terms                 */
+  const void* data;         /* fixed: n_src values aligned to their width; string: chars (NULL legal with chars_bytes 0) */
+  const uint64_t* offsets;  /* string: n_src + 1 offsets, offsets[0] need not be 0; fixed: NULL                          */
+  uint64_t chars_bytes;     /* string: size of the chars buffer, no read row may end behind it; fixed: ignored           */
+  hmj_validity validity;    /* bits == NULL: no NULL in the column; any bit_offset                                       */
+  uint64_t n_src;           /* rows of the column                                                                        */
+  const uint64_t* row_map;  /* NULL: position i reads row i; else n entries, HMJ_TAKE_NO_ROW is a NULL slot              */
+  uint64_t lit[2];          /* fixed: the literal's bits in the column's type, low bytes ([1]: BETWEEN's upper bound)    */
+  const void* str_lit[2];   /* string: HOST pointers to the literal bytes (NULL with length 0: the empty string)         */
+  uint64_t str_len[2];
+  uint64_t reserved;        /* 0                                                                                         */
+} hmj_filter_term;
+typedef struct {
+  uint32_t struct_size;     /* size-versioned like the other opts                                                        */
+  uint32_t reserved;        /* 0                                                                                         */
+  uint64_t n_out;           /* out: positions at which the predicate is TRUE = entries written to row_map_out            */
+  uint64_t n_unknown;       /* out: positions at which the predicate is UNKNOWN                                          */
+  float ms_eval, ms_write;  /* out, with hmj_set_profiling                                                               */
+  uint64_t reserved2;       /* 0                                                                                         */
+} hmj_filter_opts;
+int hmj_filter_device(hmj_ctx* ctx, const hmj_filter_term* terms, uint32_t n_terms, uint64_t n, uint64_t* row_map_out,
+                      uint64_t* mask_out, hmj_filter_opts* opts);
+
 /* Host threads of the optional staged upload (pageable input -> pinned chunks -> PCIe), used only
  * with HMJ_UPLOAD=staged in the environment; by default each relation goes up in one copy straight
  * from the caller's memory (54 GB/s on the MI355X box).  The reference ctor's num_threads argument,
