@@ -3121,35 +3121,21 @@ void hmj_destroy(hmj_ctx* c) {
                     &c->offs64, &c->irregular, &c->ord_key, &c->ord_rval, &c->ord_sval, &c->matched, &c->vparts,
                     &c->slab_a, &c->slab_br, &c->slab_bs, &c->cnt_a, &c->cnt_br, &c->cnt_bs, &c->lookback, &c->gtab, &c->piece_off,
                     &c->split_r, &c->split_s, &c->split_off, &c->cat_key, &c->cat_rval, &c->cat_sval, &c->msd_off,
-                    &c->bmatched, &c->bsweep, &c->take_acc, &c->takestr_acc, &c->takestr_blk,
-                    &c->agg_acc, &c->agg_grp, &c->agg_part,
-                    &c->filter_acc, &c->filter_blk, &c->filter_tile, &c->filter_mask, &c->filter_lit};
+                    &c->bmatched, &c->bsweep};
   for (DevBuf* b : devs) free_dev(*b);
-  for (KeyJoinWs* ws : {&c->str_ws, &c->col_ws, &c->mix_ws}) {
-    ws->each_buf(free_dev);
-    for (auto& e : ws->ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-  c->grp_ws.each_buf(free_dev);
-  for (auto& e : c->grp_ws.ev)
-    if (e) (void)hipEventDestroy(e);
-  c->ord_ws.each_buf(free_dev);
-  for (auto& e : c->ord_ws.ev)
-    if (e) (void)hipEventDestroy(e);
+  for (KeyJoinWs* ws : {&c->str_ws, &c->col_ws, &c->mix_ws}) free_workspace(*ws);
+  free_workspace(c->grp_ws);
+  free_workspace(c->ord_ws);
+  free_workspace(c->take_ws);
+  free_workspace(c->takestr_ws);
+  free_workspace(c->agg_ws);
+  free_workspace(c->filter_ws);
   HostBuf* hosts[] = {&c->h_accum, &c->h_key, &c->h_rval, &c->h_sval};
   for (HostBuf* b : hosts) free_host(*b);
   for (auto& e : c->events)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : c->up_events) (void)hipEventDestroy(e);
   for (auto& e : c->place_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : c->take_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : c->takestr_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : c->agg_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : c->filter_ev)
     if (e) (void)hipEventDestroy(e);
   for (auto& st : c->up_streams) (void)hipStreamDestroy(st);
   for (auto& e : c->copy_ev) (void)hipEventDestroy(e);

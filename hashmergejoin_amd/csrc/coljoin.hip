@@ -591,15 +591,6 @@ int opts_validity(hmj_ctx* c, const hmj_cols_kind_opts* opts, const hmj_cols_rel
   if (any_p) *pp = VP;
   return HMJ_OK;
 }
-// The out fields of a full-size copy o of the caller's opts are cleared from `first_out` on; the in fields that lie behind
-// them (the validity arrays) are the caller's again, as far as its struct_size holds them.
-void clear_out_fields(hmj_cols_kind_opts* o, const hmj_cols_kind_opts* opts, size_t first_out) {
-  using T = hmj_cols_kind_opts;
-  std::memset((char*)o + first_out, 0, sizeof(T) - first_out);
-  const size_t lo = offsetof(T, build_validity), hi = offsetof(T, n_build_null);
-  const size_t have = opts->struct_size < hi ? opts->struct_size : hi;
-  if (have > lo) std::memcpy((char*)o + lo, (const char*)opts + lo, have - lo);
-}
 
 // ---- grouping (hmj_group_cols_device; kernels and the driver, group_rows: hmj_group.h) ------------------------------------
 constexpr KeyJoinNames kGroupNames{"multi-column grouping", "key64", "tuples"};
@@ -619,21 +610,12 @@ int hmj_join_cols_device(hmj_ctx* c, const hmj_cols_rel* build, const hmj_cols_r
   HIP_TRY(hipSetDevice(c->device));
   // the out fields of opts go to a full-size copy first; the caller gets the prefix its struct_size holds
   hmj_cols_join_opts o;
-  std::memset(&o, 0, sizeof(o));
-  std::memcpy(&o, opts, opts->struct_size < sizeof(o) ? opts->struct_size : sizeof(o));
-  std::memset(&o.form, 0, sizeof(o) - offsetof(hmj_cols_join_opts, form));
+  opts_prefix_in(&o, opts);
+  opts_clear_out(&o, opts, offsetof(hmj_cols_join_opts, form));
   const int rc = join_cols(c, build, probe, flags, &o, out);
   if (rc != HMJ_OK) return rc;
-  if (c->profiling) {
-    (void)hipStreamSynchronize(c->stream);
-    o.ms_key = elapsed(c->col_ws.ev, 0, 1);
-    o.ms_join = elapsed(c->col_ws.ev, 1, 2);
-    o.ms_verify = elapsed(c->col_ws.ev, 2, 3);
-    o.ms_order = elapsed(c->col_ws.ev, 3, 4);
-  }
-  const uint32_t room = opts->struct_size < sizeof(o) ? opts->struct_size : (uint32_t)sizeof(o);
-  o.struct_size = opts->struct_size;
-  std::memcpy(opts, &o, room);
+  fill_join_ms(c, o, o.ms_key, c->col_ws.ev);
+  opts_prefix_out(opts, o);
   return HMJ_OK;
 }
 
@@ -657,11 +639,12 @@ int hmj_join_kind_cols_device(hmj_ctx* c, const hmj_cols_rel* build, const hmj_c
   HIP_TRY(hipSetDevice(c->device));
   // the out fields of opts go to a full-size copy first; the caller gets the prefix its struct_size holds
   hmj_cols_kind_opts o;
-  std::memset(&o, 0, sizeof(o));
-  std::memcpy(&o, opts, opts->struct_size < sizeof(o) ? opts->struct_size : sizeof(o));
+  opts_prefix_in(&o, opts);
   o.form = 0;
-  clear_out_fields(&o, opts, offsetof(hmj_cols_kind_opts, counts));
-  if (o.side == HMJ_KIND_PROBE_SIDE && o.kind == HMJ_JOIN_INNER) {  // exactly the inner multi-column join
+  // (out fields: form, and from `counts` on; the validity arrays behind them are in fields)
+  opts_clear_out(&o, opts, offsetof(hmj_cols_kind_opts, counts), offsetof(hmj_cols_kind_opts, build_validity), offsetof(hmj_cols_kind_opts, n_build_null));
+  const bool inner = o.side == HMJ_KIND_PROBE_SIDE && o.kind == HMJ_JOIN_INNER;  // exactly the inner multi-column join
+  if (inner) {
     hmj_cols_join_opts jo;
     std::memset(&jo, 0, sizeof(jo));
     jo.struct_size = sizeof(jo);
@@ -676,27 +659,11 @@ int hmj_join_kind_cols_device(hmj_ctx* c, const hmj_cols_rel* build, const hmj_c
     o.form = total > 8 || o.force_hashed || null_equal ? HMJ_COLS_HASHED : HMJ_COLS_PACKED;
     o.n_key_pairs = jo.n_key_pairs;
     o.n_collisions = jo.n_collisions;
-    if (c->profiling) {
-      (void)hipStreamSynchronize(c->stream);
-      o.ms_key = elapsed(c->col_ws.ev, 0, 1);
-      o.ms_join = elapsed(c->col_ws.ev, 1, 2);
-      o.ms_verify = elapsed(c->col_ws.ev, 2, 3);
-      o.ms_order = elapsed(c->col_ws.ev, 3, 4);
-    }
   } else {
     RC_TRY(join_cols_kind(c, build, probe, flags, &o, out, vb, vp, null_equal));
-    if (c->profiling) {
-      (void)hipStreamSynchronize(c->stream);
-      o.ms_key = elapsed(c->col_ws.ev, 0, 1);
-      o.ms_join = elapsed(c->col_ws.ev, 1, 2);
-      o.ms_verify = elapsed(c->col_ws.ev, 2, 3);
-      o.ms_emit = elapsed(c->col_ws.ev, 3, 4);
-      o.ms_order = elapsed(c->col_ws.ev, 4, 5);
-    }
   }
-  const uint32_t room = opts->struct_size < sizeof(o) ? opts->struct_size : (uint32_t)sizeof(o);
-  o.struct_size = opts->struct_size;
-  std::memcpy(opts, &o, room);
+  fill_kind_ms(c, o, o.ms_key, c->col_ws.ev, !inner);
+  opts_prefix_out(opts, o);
   return HMJ_OK;
 }
 
@@ -724,10 +691,8 @@ int hmj_group_cols_device(hmj_ctx* c, const hmj_cols_rel* rel, uint32_t flags, h
   c->prep.valid = false;  // like any other call, this one discards a prepared build side
   // the out fields of opts go to a full-size copy first; the caller gets the prefix its struct_size holds
   hmj_group_opts o;
-  std::memset(&o, 0, sizeof(o));
-  std::memcpy(&o, opts, opts->struct_size < sizeof(o) ? opts->struct_size : sizeof(o));
-  o.n_null = o.n_collisions = 0;
-  o.ms_key = o.ms_sort = o.ms_groups = o.ms_agg = 0.f;
+  opts_prefix_in(&o, opts);
+  opts_clear_out(&o, opts, offsetof(hmj_group_opts, n_null));
   const bool hashed = any || cols_hashed(rel, o.force_hashed);
   const u32 bits = hashed ? o.hash_bits : 0;
   o.form = hashed ? HMJ_COLS_HASHED : HMJ_COLS_PACKED;
@@ -749,17 +714,9 @@ int hmj_group_cols_device(hmj_ctx* c, const hmj_cols_rel* rel, uint32_t flags, h
       auto key = [&](hmj_ctx* c, u64* rows, u64* acc) { return launch_key(c, A, n, hashed, bits, rows, false, acc); };
       RC_TRY(group_rows(c, kGroupNames, A, n, hashed, mat, key, GroupNoCheck{}, &o, out));
     }
-    if (c->profiling) {
-      (void)hipStreamSynchronize(c->stream);
-      o.ms_key = elapsed(c->grp_ws.ev, 0, 1);
-      o.ms_sort = elapsed(c->grp_ws.ev, 1, 2);
-      o.ms_groups = elapsed(c->grp_ws.ev, 2, 3);
-      o.ms_agg = elapsed(c->grp_ws.ev, 3, 4);
-    }
+    fill_group_ms(c, o);
   }
-  const uint32_t room = opts->struct_size < sizeof(o) ? opts->struct_size : (uint32_t)sizeof(o);
-  o.struct_size = opts->struct_size;
-  std::memcpy(opts, &o, room);
+  opts_prefix_out(opts, o);
   c->grp_ws.live = mat;  // the live grouping of hmj_group_agg_device
   c->grp_ws.live_rows = n;
   c->grp_ws.live_groups = out->n_groups;

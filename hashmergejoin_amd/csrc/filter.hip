@@ -24,7 +24,7 @@
 //                             own mask word and those of the waves in front of it in the block, ranks the set bits of its
 //                             word behind theirs, adds the block's base (tile base + slot) and stores position i at
 //                             row_map_out[base + rank].
-// The call owns five DevBufs (filter_acc, filter_blk, filter_tile, filter_mask, filter_lit) and touches nothing else of the
+// The call owns its FilterWs (hmj_ctx.h: five DevBufs, the literals' host copy, four events) and touches nothing else of the
 // ctx: no result column, no prepared build side, no grouping, no plan, timing or memo.
 #include <hip/hip_runtime.h>
 
@@ -32,7 +32,7 @@
 #include <cstdio>
 #include <cstring>
 
-#include "hmj_ctx.h"
+#include "hmj_entry.h"
 
 using hmj::u32;
 using hmj::u64;
@@ -54,7 +54,7 @@ constexpr int kMapSlots = 4;                        // distinct maps whose entry
 constexpr u32 kLitLds = HMJ_MAX_FILTER_LITERAL_BYTES + 8 * 2 * HMJ_MAX_FILTER_TERMS;  // every literal starts at a multiple of 8
 constexpr u64 kNoRow = HMJ_TAKE_NO_ROW;
 constexpr u32 kString = HMJ_FILTER_LARGE_STRING;
-// filter_acc slots (u64).  The first FA_N_RED are ballot popcounts of the evaluation: map entries >= n_src that are not
+// FilterWs::acc slots (u64).  The first FA_N_RED are ballot popcounts of the evaluation: map entries >= n_src that are not
 // HMJ_TAKE_NO_ROW, read valid string rows whose offsets decrease / end behind chars_bytes; FA_TOTAL is the scan's grand
 // total, TRUE positions in the low half and UNKNOWN positions in the high half (both at most n <= 2^32 - 1: no carry).
 // FA_SAFE: 16 bytes that stay 0, where a lane without a row points its loads (load_or).
@@ -354,15 +354,6 @@ __global__ __launch_bounds__(FL_THREADS) void filter_eval_kernel(FilterTerms<K> 
   }
 }
 
-__device__ __forceinline__ u64 wave_inclusive_scan(u64 v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const u64 t = __shfl_up(v, o, 64);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-
 // Tile t = slots [t kScanTile, min(+ kScanTile, nblk)): their exclusive scan in place, their total to tile_tot[t].  The two
 // halves of a slot never carry into each other (see FA_TOTAL), so one 64-bit scan scans both counts.
 __global__ __launch_bounds__(FL_THREADS) void filter_scan_tiles_kernel(u64* __restrict__ blk, u32 nblk, u64* __restrict__ tile_tot) {
@@ -375,7 +366,7 @@ __global__ __launch_bounds__(FL_THREADS) void filter_scan_tiles_kernel(u64* __re
     v[j] = base + j < nblk ? blk[base + j] : 0ull;
     sum += v[j];
   }
-  const u64 incl = wave_inclusive_scan(sum, lane);
+  const u64 incl = hmj::wave_incl_scan_u64(sum, lane);
   if (lane == 63) wtot[wv] = incl;
   __syncthreads();
   u64 carry = 0, all = 0;
@@ -403,7 +394,7 @@ __global__ __launch_bounds__(kTopThreads) void filter_scan_top_kernel(const u64*
   u64 sum = 0;
   for (u32 j = 0; j < per; j++)
     if (base + j < ntile) sum += tile_tot[base + j];
-  const u64 incl = wave_inclusive_scan(sum, lane);
+  const u64 incl = hmj::wave_incl_scan_u64(sum, lane);
   if (lane == 63) wtot[wv] = incl;
   __syncthreads();
   u64 carry = 0, all = 0;
@@ -466,10 +457,6 @@ __global__ __launch_bounds__(FL_THREADS) void filter_write_kernel(const u64* __r
 // ---- host side -----------------------------------------------------------------------------------------------------------
 const char* const kOpNames[] = {"EQ", "NE", "LT", "LE", "GT", "GE", "BETWEEN", "IS_NULL", "IS_NOT_NULL", "STARTS_WITH", "ENDS_WITH"};
 
-u32 width_of(u32 type) {  // of a fixed HMJ_TYPE_*
-  static const u32 w[10] = {1, 2, 4, 8, 1, 2, 4, 8, 4, 8};
-  return w[type];
-}
 bool reads_literal(u32 op) { return op != HMJ_FILTER_IS_NULL && op != HMJ_FILTER_IS_NOT_NULL; }
 u32 n_literals(u32 op) { return !reads_literal(op) ? 0u : (op == HMJ_FILTER_BETWEEN ? 2u : 1u); }
 
@@ -510,7 +497,7 @@ int check_filter_args(hmj_ctx* c, const hmj_filter_term* terms, u32 n_terms, u64
     if (t.n_src > 0xFFFFFFFFull) return term_fail(c, k, "too many rows (n_src at most 2^32-1)");
     if ((uintptr_t)t.row_map & 7u) return term_fail(c, k, "row_map is not aligned to 8 bytes");
     if (!t.row_map && t.n_src < n) return term_fail(c, k, "n_src < n without a row_map");
-    if (t.validity.bits && t.validity.bit_offset > UINT64_MAX - t.n_src) return term_fail(c, k, "validity bit_offset + n_src overflows 64 bits");
+    if (validity_overflows(t.validity, t.n_src)) return term_fail(c, k, "validity bit_offset + n_src overflows 64 bits");
     const bool rows = n > 0 && t.n_src > 0;  // the call may read a row of the column
     if (str) {
       if (rows && !t.offsets) return term_fail(c, k, "offsets are NULL");
@@ -543,25 +530,12 @@ int check_filter_args(hmj_ctx* c, const hmj_filter_term* terms, u32 n_terms, u64
   for (u32 k = 0; k < n_terms; k++) {
     const hmj_filter_term& t = terms[k];
     const bool str = t.type == kString;
-    const u8* vb = (const u8*)t.validity.bits;
     const Range in[4] = {range_of(t.data, str ? t.chars_bytes : t.n_src * width_of(t.type)),
                          str ? range_of(t.offsets, 8 * (t.n_src + 1)) : Range{0, 0}, range_of(t.row_map, 8 * n),
-                         vb && t.n_src ? range_of(vb + (t.validity.bit_offset >> 3), ((t.validity.bit_offset & 7) + t.n_src + 7) / 8)
-                                       : Range{0, 0}};
-    for (const Range& o : outs)
-      for (const Range& r : in)
-        if (overlap(o, r)) return term_fail(c, k, "row_map_out or mask_out overlaps the column's values, offsets, bitmap or row_map");
+                         validity_range(t.validity, t.n_src)};
+    if (first_overlap(outs, 2, in, 4)) return term_fail(c, k, "row_map_out or mask_out overlaps the column's values, offsets, bitmap or row_map");
   }
   return HMJ_OK;
-}
-
-float elapsed_or_zero(hipEvent_t a, hipEvent_t b) {
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, a, b) != hipSuccess) {
-    (void)hipGetLastError();
-    ms = 0.f;
-  }
-  return ms;
 }
 
 // a fixed column's literal as the kernel compares it
@@ -615,7 +589,7 @@ int launch_eval(hmj_ctx* c, const hmj_filter_term* terms, u32 n_terms, const u64
     }
   }
   hipLaunchKernelGGL(filter_eval_kernel<K>, dim3((nblk + kEvalBlocks - 1) / kEvalBlocks), dim3(FL_THREADS), 0, c->stream, T,
-                     (const u8*)c->filter_lit.p, lit_bytes, n, nblk, mask, blk, acc);
+                     (const u8*)c->filter_ws.lit.p, lit_bytes, n, nblk, mask, blk, acc);
   HIP_TRY(hipGetLastError());
   return HMJ_OK;
 }
@@ -624,18 +598,19 @@ int filter_rows(hmj_ctx* c, const hmj_filter_term* terms, u32 n_terms, u64 n, u6
   const u32 nblk = (u32)((n + FL_THREADS - 1) / FL_THREADS);
   const u32 ntile = (nblk + kScanTile - 1) / kScanTile;
   const u32 per = (ntile + kTopThreads - 1) / kTopThreads;
-  RC_TRY(ensure_dev(c, c->filter_acc, FA_N * sizeof(u64)));
-  RC_TRY(ensure_dev(c, c->filter_blk, (size_t)nblk * sizeof(u64)));
-  RC_TRY(ensure_dev(c, c->filter_tile, (2 * (size_t)ntile + 1) * sizeof(u64)));
-  if (!mask_out) RC_TRY(ensure_dev(c, c->filter_mask, (size_t)((n + 63) / 64) * sizeof(u64)));
-  u64* acc = (u64*)c->filter_acc.p;
-  u64* blk = (u64*)c->filter_blk.p;
-  u64* tile_tot = (u64*)c->filter_tile.p;
+  FilterWs& ws = c->filter_ws;
+  RC_TRY(ensure_dev(c, ws.acc, FA_N * sizeof(u64)));
+  RC_TRY(ensure_dev(c, ws.blk, (size_t)nblk * sizeof(u64)));
+  RC_TRY(ensure_dev(c, ws.tile, (2 * (size_t)ntile + 1) * sizeof(u64)));
+  if (!mask_out) RC_TRY(ensure_dev(c, ws.mask, (size_t)((n + 63) / 64) * sizeof(u64)));
+  u64* acc = (u64*)ws.acc.p;
+  u64* blk = (u64*)ws.blk.p;
+  u64* tile_tot = (u64*)ws.tile.p;
   u64* tile_off = tile_tot + ntile;  // ntile + 1
-  u64* mask = mask_out ? mask_out : (u64*)c->filter_mask.p;
+  u64* mask = mask_out ? mask_out : (u64*)ws.mask.p;
   // the string literals: one block, every literal at a multiple of 8, copied to the device and from there to LDS
   u64 lit_word[2 * HMJ_MAX_FILTER_TERMS] = {0};
-  std::vector<u8>& lits = c->filter_lit_host;
+  std::vector<u8>& lits = ws.lit_host;
   lits.clear();
   for (u32 k = 0; k < n_terms; k++) {
     if (terms[k].type != kString) continue;
@@ -648,15 +623,11 @@ int filter_rows(hmj_ctx* c, const hmj_filter_term* terms, u32 n_terms, u64 n, u6
   }
   const u32 lit_bytes = (u32)lits.size();  // (<= kLitLds: at most 4096 bytes in at most 32 literals)
   if (lit_bytes) {
-    RC_TRY(ensure_dev(c, c->filter_lit, kLitLds));
-    HIP_TRY(hipMemcpyAsync(c->filter_lit.p, lits.data(), lit_bytes, hipMemcpyHostToDevice, c->stream));
+    RC_TRY(ensure_dev(c, ws.lit, kLitLds));
+    HIP_TRY(hipMemcpyAsync(ws.lit.p, lits.data(), lit_bytes, hipMemcpyHostToDevice, c->stream));
   }
   HIP_TRY(hipMemsetAsync(acc, 0, FA_N * sizeof(u64), c->stream));
-  if (c->profiling) {
-    for (auto& e : c->filter_ev)
-      if (!e) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventRecord(c->filter_ev[0], c->stream));
-  }
+  RC_TRY(ws.ev.record(c, 0));
   if (n_terms <= 1) RC_TRY(launch_eval<1>(c, terms, n_terms, lit_word, lit_bytes, n, nblk, mask, blk, acc));
   else if (n_terms <= 2) RC_TRY(launch_eval<2>(c, terms, n_terms, lit_word, lit_bytes, n, nblk, mask, blk, acc));
   else if (n_terms <= 4) RC_TRY(launch_eval<4>(c, terms, n_terms, lit_word, lit_bytes, n, nblk, mask, blk, acc));
@@ -666,11 +637,10 @@ int filter_rows(hmj_ctx* c, const hmj_filter_term* terms, u32 n_terms, u64 n, u6
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(filter_scan_top_kernel, dim3(1), dim3(kTopThreads), 0, c->stream, (const u64*)tile_tot, ntile, per, tile_off, acc);
   HIP_TRY(hipGetLastError());
-  if (c->profiling) HIP_TRY(hipEventRecord(c->filter_ev[1], c->stream));
+  RC_TRY(ws.ev.record(c, 1));
   // the one synchronisation before the write phase: a bad call stops here
   u64 h[FA_N];
-  HIP_TRY(hipMemcpyAsync(h, acc, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  RC_TRY(read_back(c, acc, h, sizeof(h)));
   if (h[FA_BAD_MAP] || h[FA_BAD_DEC] || h[FA_BAD_END]) {
     char msg[288];
     std::snprintf(msg, sizeof(msg),
@@ -681,15 +651,15 @@ int filter_rows(hmj_ctx* c, const hmj_filter_term* terms, u32 n_terms, u64 n, u6
   }
   o->n_out = h[FA_TOTAL] & 0xFFFFFFFFull;
   o->n_unknown = h[FA_TOTAL] >> 32;
-  if (c->profiling) o->ms_eval = elapsed_or_zero(c->filter_ev[0], c->filter_ev[1]);
+  if (c->profiling) o->ms_eval = ws.ev.ms(0, 1);
   if (o->n_out == 0) return HMJ_OK;
-  if (c->profiling) HIP_TRY(hipEventRecord(c->filter_ev[2], c->stream));
+  RC_TRY(ws.ev.record(c, 2));
   hipLaunchKernelGGL(filter_write_kernel, dim3((nblk + kEvalBlocks - 1) / kEvalBlocks), dim3(FL_THREADS), 0, c->stream, (const u64*)mask,
                      (const u64*)blk, (const u64*)tile_off, n, nblk, out);
   HIP_TRY(hipGetLastError());
-  if (c->profiling) HIP_TRY(hipEventRecord(c->filter_ev[3], c->stream));
+  RC_TRY(ws.ev.record(c, 3));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  if (c->profiling) o->ms_write = elapsed_or_zero(c->filter_ev[2], c->filter_ev[3]);
+  if (c->profiling) o->ms_write = ws.ev.ms(2, 3);
   return HMJ_OK;
 }
 
@@ -703,13 +673,13 @@ int hmj_filter_device(hmj_ctx* c, const hmj_filter_term* terms, uint32_t n_terms
   RC_TRY(check_filter_args(c, terms, n_terms, n, (const u64*)row_map_out, (const u64*)mask_out, opts));
   // the out fields of opts go to a full-size copy first; the caller gets the prefix its struct_size holds
   hmj_filter_opts o;
-  std::memset(&o, 0, sizeof(o));
-  o.struct_size = opts->struct_size;
+  opts_prefix_in(&o, opts);
+  opts_clear_out(&o, opts, offsetof(hmj_filter_opts, n_out));
   if (n > 0) {
     HIP_TRY(hipSetDevice(c->device));
     RC_TRY(filter_rows(c, terms, n_terms, n, (u64*)row_map_out, (u64*)mask_out, &o));
   }
-  std::memcpy(opts, &o, opts->struct_size < sizeof(o) ? opts->struct_size : sizeof(o));
+  opts_prefix_out(opts, o);
   return HMJ_OK;
 }
 

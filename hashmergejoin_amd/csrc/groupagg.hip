@@ -24,14 +24,14 @@
 //                       with value bytes 0; a wave's ballot is one word of the output bitmap (one lane stores it), NULLs
 //                       are counted by popcount, one atomic per workgroup and aggregate.
 // The host checks the arguments (address ranges included), loops over the launch chunks and reads the NULL counters back
-// once.  The call owns three DevBufs (agg_acc, agg_grp, agg_part) and touches nothing else of the ctx.
+// once.  The call owns its AggWs (hmj_ctx.h: three DevBufs, two events) and touches nothing else of the ctx.
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <cstdio>
 #include <cstring>
 
-#include "hmj_ctx.h"
+#include "hmj_entry.h"
 
 using hmj::u32;
 using hmj::u64;
@@ -73,7 +73,6 @@ template <class T>
 __device__ __forceinline__ u64 agg_raw(const void* __restrict__ p, u64 r) {
   return (u64) reinterpret_cast<const T*>(p)[r];
 }
-__host__ __device__ __forceinline__ u32 width_of(u32 type) { return type >= HMJ_TYPE_F32 ? 4u << (type - HMJ_TYPE_F32) : 1u << (type & 3u); }
 __device__ __forceinline__ u64 agg_load(const void* __restrict__ p, u32 type, u64 r) {
   u64 x;
   switch (width_of(type)) {  // (uniform)
@@ -225,8 +224,7 @@ __global__ __launch_bounds__(GA_THREADS) void agg_walk_kernel(AggIn T, AggSlots 
         if (a > 0 && (desc_dup(T.desc[a]) & 2u)) {
           bit[a] = bit[a > 0 ? a - 1 : 0];
         } else if (T.vbits[a]) {
-          const u64 b = T.voff[a] + r;
-          bit[a] = (T.vbits[a][b >> 3] >> (b & 7)) & 1u;
+          bit[a] = hmj::valid_bit(T.vbits[a], T.voff[a] + r);
         }
       }
     }
@@ -465,7 +463,7 @@ int check_agg_args(hmj_ctx* c, const hmj_agg_src* src, u32 n_aggs, u64 n_rows, c
       std::snprintf(msg, sizeof(msg), "hmj_group_agg_device: aggregate %u: source data is not aligned to its width (%u)", a, w);
       return fail(c, HMJ_E_ARG, msg);
     }
-    if (s.validity.bits && s.validity.bit_offset > UINT64_MAX - n_rows) {
+    if (validity_overflows(s.validity, n_rows)) {
       std::snprintf(msg, sizeof(msg), "hmj_group_agg_device: aggregate %u: validity bit_offset + n_rows overflows 64 bits", a);
       return fail(c, HMJ_E_ARG, msg);
     }
@@ -485,25 +483,18 @@ int check_agg_args(hmj_ctx* c, const hmj_agg_src* src, u32 n_aggs, u64 n_rows, c
   // A destination the kernels write must not be something they read, nor another destination: address ranges only, as
   // hmj_take_cols_device checks them; without groups nothing is written.
   if (ng == 0) return HMJ_OK;
+  Range in[2 * HMJ_MAX_AGGS], out[2 * HMJ_MAX_AGGS];
   for (u32 a = 0; a < n_aggs; a++) {
-    const Range out[2] = {range_of(dst[a].data, ng * out_width_of(src[a].type, src[a].op)), range_of(dst[a].validity, 8 * ((ng + 63) / 64))};
-    for (int t = 0; t < 2; t++) {
-      const Range& o = out[t];
-      bool hit = false;
-      for (u32 j = 0; j < n_aggs && !hit; j++) {
-        const hmj_validity& v = src[j].validity;
-        const unsigned char* vb = (const unsigned char*)v.bits;
-        hit = overlap(o, range_of(src[j].data, n_rows * width_of(src[j].type))) ||
-              (vb && overlap(o, range_of(vb + (v.bit_offset >> 3), ((v.bit_offset & 7) + n_rows + 7) / 8)));
-        const Range other[2] = {range_of(dst[j].data, ng * out_width_of(src[j].type, src[j].op)), range_of(dst[j].validity, 8 * ((ng + 63) / 64))};
-        for (int u = 0; u < 2 && !hit; u++)
-          if (j != a || u != t) hit = overlap(o, other[u]);
-      }
-      if (hit) {
-        std::snprintf(msg, sizeof(msg), "hmj_group_agg_device: aggregate %u: the destination overlaps a source column, a source bitmap or another destination",
-                      a);
-        return fail(c, HMJ_E_ARG, msg);
-      }
+    in[2 * a] = range_of(src[a].data, n_rows * width_of(src[a].type));
+    in[2 * a + 1] = validity_range(src[a].validity, n_rows);
+    out[2 * a] = range_of(dst[a].data, ng * out_width_of(src[a].type, src[a].op));
+    out[2 * a + 1] = range_of(dst[a].validity, 8 * ((ng + 63) / 64));
+  }
+  for (u32 a = 0; a < n_aggs; a++) {
+    if (first_overlap(out + 2 * a, 2, in, 2 * (int)n_aggs) || first_overlap(out + 2 * a, 2, out, 2 * (int)n_aggs)) {
+      std::snprintf(msg, sizeof(msg), "hmj_group_agg_device: aggregate %u: the destination overlaps a source column, a source bitmap or another destination",
+                    a);
+      return fail(c, HMJ_E_ARG, msg);
     }
   }
   return HMJ_OK;
@@ -527,21 +518,18 @@ int launch_chunk(hmj_ctx* c, const AggIn& T, const AggOut& O, const AggSlots& S,
 int group_agg(hmj_ctx* c, const hmj_agg_src* src, u32 n_aggs, u64 n, hmj_agg_dst* dst, hmj_group_agg_opts* o) {
   const u64 ng = c->grp_ws.live_groups;
   const u64 waves = ((n + 63) / 64 + kWalkChunks - 1) / kWalkChunks;
-  RC_TRY(ensure_dev(c, c->agg_acc, HMJ_MAX_AGGS * sizeof(u64)));
-  RC_TRY(ensure_dev(c, c->agg_grp, AggSlots::grp_bytes(ng)));
-  RC_TRY(ensure_dev(c, c->agg_part, AggSlots::part_bytes(waves)));
-  u64* acc = (u64*)c->agg_acc.p;
+  AggWs& ws = c->agg_ws;
+  RC_TRY(ensure_dev(c, ws.acc, HMJ_MAX_AGGS * sizeof(u64)));
+  RC_TRY(ensure_dev(c, ws.grp, AggSlots::grp_bytes(ng)));
+  RC_TRY(ensure_dev(c, ws.part, AggSlots::part_bytes(waves)));
+  u64* acc = (u64*)ws.acc.p;
   AggSlots S;
   S.ng = ng;
   S.waves = waves;
-  S.grp = (u64*)c->agg_grp.p;
-  S.part = (ulonglong2*)c->agg_part.p;
+  S.grp = (u64*)ws.grp.p;
+  S.part = (ulonglong2*)ws.part.p;
   HIP_TRY(hipMemsetAsync(acc, 0, HMJ_MAX_AGGS * sizeof(u64), c->stream));
-  if (c->profiling) {
-    for (auto& e : c->agg_ev)
-      if (!e) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventRecord(c->agg_ev[0], c->stream));
-  }
+  RC_TRY(ws.ev.record(c, 0));
   for (u32 a0 = 0; a0 < n_aggs; a0 += kAggLaunch) {
     AggIn T;
     AggOut O;
@@ -569,15 +557,11 @@ int group_agg(hmj_ctx* c, const hmj_agg_src* src, u32 n_aggs, u64 n, hmj_agg_dst
     else if (T.k <= 2) RC_TRY(launch_chunk<2>(c, T, O, S, n, acc + a0));
     else RC_TRY(launch_chunk<kAggLaunch>(c, T, O, S, n, acc + a0));
   }
-  if (c->profiling) HIP_TRY(hipEventRecord(c->agg_ev[1], c->stream));
+  RC_TRY(ws.ev.record(c, 1));
   u64 h[HMJ_MAX_AGGS];
-  HIP_TRY(hipMemcpyAsync(h, acc, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  RC_TRY(read_back(c, acc, h, sizeof(h)));
   for (u32 a = 0; a < n_aggs; a++) dst[a].null_count = h[a];
-  if (c->profiling && hipEventElapsedTime(&o->ms_agg, c->agg_ev[0], c->agg_ev[1]) != hipSuccess) {
-    (void)hipGetLastError();
-    o->ms_agg = 0.f;
-  }
+  if (c->profiling) o->ms_agg = ws.ev.ms(0, 1);
   return HMJ_OK;
 }
 
@@ -591,8 +575,8 @@ int hmj_group_agg_device(hmj_ctx* c, const hmj_agg_src* src, uint32_t n_aggs, ui
   RC_TRY(check_agg_args(c, src, n_aggs, n_rows, dst, opts));
   // the out fields of opts go to a full-size copy first; the caller gets the prefix its struct_size holds
   hmj_group_agg_opts o;
-  std::memset(&o, 0, sizeof(o));
-  o.struct_size = opts->struct_size;
+  opts_prefix_in(&o, opts);
+  opts_clear_out(&o, opts, offsetof(hmj_group_agg_opts, n_groups));
   o.n_groups = c->grp_ws.live_groups;
   if (n_rows == 0 || o.n_groups == 0) {
     for (u32 a = 0; a < n_aggs; a++) dst[a].null_count = 0;
@@ -600,7 +584,7 @@ int hmj_group_agg_device(hmj_ctx* c, const hmj_agg_src* src, uint32_t n_aggs, ui
     HIP_TRY(hipSetDevice(c->device));
     RC_TRY(group_agg(c, src, n_aggs, n_rows, dst, &o));
   }
-  std::memcpy(opts, &o, opts->struct_size < sizeof(o) ? opts->struct_size : sizeof(o));
+  opts_prefix_out(opts, o);
   return HMJ_OK;
 }
 

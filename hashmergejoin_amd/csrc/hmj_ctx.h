@@ -8,10 +8,12 @@
 #include <vector>
 
 #include "../../include/hmj.h"
+#include "hmj_args.h"
 #include "hmj_dev.h"
 #include "hmj_launch.h"
 
 struct hmj_comm;  // exchange.hip
+struct hmj_ctx;
 
 namespace hmj_host {
 
@@ -23,6 +25,27 @@ struct HostBuf {
   void* p = nullptr;
   size_t cap = 0;
   bool pinned = true;  // false: pageable memory on transparent huge pages (the result columns)
+};
+// The phase boundaries of one entry (profiling): events created on first use.  record is defined in hmj_entry.h, which every
+// file that records includes (it needs the whole hmj_ctx).
+template <int N>
+struct PhaseEvents {
+  hipEvent_t ev[N] = {};
+  int record(hmj_ctx* c, int k);  // a no-op without profiling
+  float ms(int a, int b) {        // 0 where either event is missing or the query fails
+    float t = 0.f;
+    if (ev[a] && ev[b] && hipEventElapsedTime(&t, ev[a], ev[b]) != hipSuccess) {
+      (void)hipGetLastError();
+      t = 0.f;
+    }
+    return t;
+  }
+  void destroy() {
+    for (hipEvent_t& e : ev) {
+      if (e) (void)hipEventDestroy(e);
+      e = nullptr;
+    }
+  }
 };
 
 // Workspace of one of the joins on {key64, row} rows, all three of them run by hmj_tuplejoin.h's driver on hmj_keyjoin.h's
@@ -37,7 +60,7 @@ struct KeyJoinWs {
                                    // every row of the relation), the valid rows per workgroup of both relations and their offsets
       key, rrow, srow, rval, sval, // the five result columns (the multi-column join's packed form fills rval / sval only)
       ord, kkey, krrow, ksrow, krval, ksval;  // ordered kinds: (key64, index) rows and their sorted copy, the result columns in sorted order
-  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // phase boundaries (profiling)
+  PhaseEvents<6> ev;
   // the buffers a result lives in (hmj_release_result frees them), and every buffer
   template <class F>
   void each_result_buf(F f) {
@@ -58,7 +81,7 @@ struct GroupWs {
       list, runs, acc,        // the collision search's rows and runs, the counters
       start,                  // first sorted position of every group, and n behind the last
       key, first, count, sum, min, max, gmap;  // the result columns
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // phase boundaries (profiling)
+  PhaseEvents<5> ev;
   // The live grouping, what hmj_group_agg_device (groupagg.hip) aggregates over: set when a group call made with
   // HMJ_MATERIALIZE returns HMJ_OK -- sorted, flags, blk_off and start then describe live_rows rows in live_groups groups --,
   // cleared at the entry of either group call, by hmj_release_result and with the ctx.  Nothing else writes these buffers.
@@ -82,10 +105,48 @@ struct OrderWs {
       heads, act, acth,    // one ballot word per wave of a round's rows: heads, active rows, heads of active segments
       blk, blk_off,        // active rows (low half) and active segments (high half) per workgroup, and their offsets
       acc;                 // the counters and the key kernel's report words
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // phase boundaries (profiling)
+  PhaseEvents<5> ev;
   template <class F>
   void each_buf(F f) {
     for (DevBuf* b : {&rows, &sorted, &lst[0], &lst[1], &rank[0], &rank[1], &heads, &act, &acth, &blk, &blk_off, &acc}) f(*b);
+  }
+};
+
+// Workspaces of the row-map operators: each owns its buffers and events, and touches nothing else of the ctx.
+struct TakeWs {  // hmj_take_cols_device (take.hip)
+  DevBuf acc;    // the counters
+  PhaseEvents<2> ev;  // around its launches
+  template <class F>
+  void each_buf(F f) {
+    f(acc);
+  }
+};
+struct TakeStrWs {  // hmj_take_str_device (takestr.hip)
+  DevBuf acc, blk;  // the counters; the bytes per workgroup of 256 output rows followed by their exclusive scan
+  PhaseEvents<4> ev;  // around its offsets and its bytes phase
+  template <class F>
+  void each_buf(F f) {
+    for (DevBuf* b : {&acc, &blk}) f(*b);
+  }
+};
+struct AggWs {  // hmj_group_agg_device (groupagg.hip)
+  DevBuf acc, grp, part;  // the NULL counters; the accumulator and valid-count slots per group of one launch chunk of
+                          // aggregates; the partial slots per wave of the walk
+  PhaseEvents<2> ev;      // around its launches
+  template <class F>
+  void each_buf(F f) {
+    for (DevBuf* b : {&acc, &grp, &part}) f(*b);
+  }
+};
+struct FilterWs {  // hmj_filter_device (filter.hip)
+  DevBuf acc, blk, tile,  // the counters; the {TRUE, UNKNOWN} counts per workgroup of 256 positions (scanned in place); the
+                          // totals per scan tile followed by their exclusive scan
+      mask, lit;          // the mask words of a call without mask_out; the string literals
+  std::vector<unsigned char> lit_host;  // the literals on their way to lit (lives until the call's last sync)
+  PhaseEvents<4> ev;                    // around its evaluation and its write phase
+  template <class F>
+  void each_buf(F f) {
+    for (DevBuf* b : {&acc, &blk, &tile, &mask, &lit}) f(*b);
   }
 };
 
@@ -170,29 +231,16 @@ struct hmj_ctx {
       slab_a, slab_br, slab_bs, cnt_a, cnt_br, cnt_bs, lookback, gtab, piece_off,
       split_r, split_s, split_off, cat_key, cat_rval, cat_sval,  // joins by key ranges: both relations cut, the appended result columns
       msd_off,  // the rank forms' build-side sort: partition offsets of its one MSD pass
-      bmatched, bsweep,  // build-side kinds: one bit per build row slot; the sweep's row counts ([0] all, [1 + p] partition p)
-      // hmj_take_cols_device (take.hip): its counters -- the only workspace the call owns
-      take_acc,
-      // hmj_take_str_device (takestr.hip): its counters, and the bytes per workgroup of 256 output rows followed by their
-      // exclusive scan -- the only workspace the call owns
-      takestr_acc, takestr_blk,
-      // hmj_group_agg_device (groupagg.hip): its NULL counters, the accumulator and valid-count slots per group of one
-      // launch chunk of aggregates, and the partial slots per wave of the walk -- the only workspace the call owns
-      agg_acc, agg_grp, agg_part,
-      // hmj_filter_device (filter.hip): its counters, the {TRUE, UNKNOWN} counts per workgroup of 256 positions (scanned in
-      // place), the totals per scan tile followed by their exclusive scan, the mask words of a call without mask_out, and
-      // the string literals -- the only workspace the call owns
-      filter_acc, filter_blk, filter_tile, filter_mask, filter_lit;
-  std::vector<unsigned char> filter_lit_host;  // the literals on their way to filter_lit (lives until the call's last sync)
+      bmatched, bsweep;  // build-side kinds: one bit per build row slot; the sweep's row counts ([0] all, [1 + p] partition p)
   // string joins (strjoin.hip), multi-column joins (coljoin.hip) and mixed-key joins (mixjoin.hip): one workspace each, so
   // that no call reuses or regrows another's buffers
   hmj_host::KeyJoinWs str_ws, col_ws, mix_ws;
   hmj_host::GroupWs grp_ws;  // hmj_group_cols_device, hmj_group_mixed_device
   hmj_host::OrderWs ord_ws;  // hmj_order_by_device
-  hipEvent_t take_ev[2] = {nullptr, nullptr};  // hmj_take_cols_device: around its launches (profiling)
-  hipEvent_t takestr_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // hmj_take_str_device: around its offsets and its bytes phase
-  hipEvent_t agg_ev[2] = {nullptr, nullptr};  // hmj_group_agg_device: around its launches (profiling)
-  hipEvent_t filter_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // hmj_filter_device: around its evaluation and its write phase
+  hmj_host::TakeWs take_ws;        // hmj_take_cols_device
+  hmj_host::TakeStrWs takestr_ws;  // hmj_take_str_device
+  hmj_host::AggWs agg_ws;          // hmj_group_agg_device
+  hmj_host::FilterWs filter_ws;    // hmj_filter_device
   int memo_kind = 0;  // workload-signature kind of plain inner joins run on behalf of another entry (string, multi-column joins and their kinds), and of the sorts hmj_order_by_device runs
   HostBuf h_accum, h_key, h_rval, h_sval;
   int host_threads = 0;  // staging threads for pageable input (0 = default)
@@ -337,18 +385,18 @@ int fail(hmj_ctx* c, int code, const char* what, hipError_t e = hipSuccess);
     const int _rc = (expr);        \
     if (_rc != HMJ_OK) return _rc; \
   } while (0)
-// address ranges, for the host checks of the entries that write caller-owned columns (take.hip, takestr.hip)
-struct Range {
-  uintptr_t lo, hi;  // [lo, hi); empty when lo == hi
-};
-inline Range range_of(const void* p, uint64_t bytes) { return Range{(uintptr_t)p, (uintptr_t)p + (uintptr_t)(p ? bytes : 0)}; }
-inline bool overlap(const Range& a, const Range& b) { return a.lo < a.hi && b.lo < b.hi && a.lo < b.hi && b.lo < a.hi; }
 // the per-phase times and byte counts of one (sub-)join, added to a call's totals (exchange rounds, key ranges); api.hip
 void add_timing(hmj_timing* acc, const hmj_timing& t);
 int ensure_dev(hmj_ctx* c, DevBuf& b, size_t bytes);
 int ensure_host(hmj_ctx* c, HostBuf& b, size_t bytes, bool pinned = true);
 void free_dev(DevBuf& b);
 void free_host(HostBuf& b);
+// everything a workspace owns on the device: its buffers and its events (hmj_destroy)
+template <class Ws>
+void free_workspace(Ws& ws) {
+  ws.each_buf(free_dev);
+  ws.ev.destroy();
+}
 void spans_reset(hmj_ctx* c);
 void spans_collect(hmj_ctx* c);
 int span_begin(hmj_ctx* c, int kind, int rel, int pass = 0);

@@ -183,6 +183,20 @@ __device__ __forceinline__ u32 wave_incl_scan_u32(u32 v, int /*lane*/) {
 #endif
 }
 
+// Inclusive wave64 scan of 64-bit values: six __shfl_up steps (the row-map operators' scans of byte and row counts).
+__device__ __forceinline__ u64 wave_incl_scan_u64(u64 v, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const u64 t = __shfl_up(v, o, 64);
+    if (lane >= o) v += t;
+  }
+  return v;
+}
+
+// bit `bit` of an Arrow validity bitmap (least-significant bit first); the shift is a byte's, as the compiler narrows it where
+// the expression stands in a kernel's own text
+__device__ __forceinline__ u32 valid_bit(const unsigned char* vbits, u64 bit) { return (u32)(unsigned char)(vbits[bit >> 3] >> (bit & 7)) & 1u; }
+
 __device__ __forceinline__ u64 wave_sum_u64(u64 v) {
 #pragma unroll
   for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);

@@ -354,11 +354,11 @@ int group_rows(hmj_ctx* c, const KeyJoinNames& nm, const Side& A, u64 n, bool ha
   const dim3 G((u32)nblk), T(KJ_THREADS);
   u64 h[GA_N];
   // 1. {key64, row} rows
-  RC_TRY(record(c, ws.ev, 0));
+  RC_TRY(ws.ev.record(c, 0));
   HIP_TRY(hipMemsetAsync(acc, 0, acc_words * sizeof(u64), c->stream));
   if constexpr (Check::kWords != 0) RC_TRY(chk.begin(c, acc + GA_N));
   RC_TRY(key(c, (u64*)ws.rows.p, acc));
-  RC_TRY(record(c, ws.ev, 1));
+  RC_TRY(ws.ev.record(c, 1));
   // 2. the stable u64 sort: rows of one key64 contiguous and ascending by row
   {
     const hmj_plan_desc plan = c->plan;  // (the sort is not a join: hmj_last_plan / hmj_last_timing keep describing the last one)
@@ -368,7 +368,7 @@ int group_rows(hmj_ctx* c, const KeyJoinNames& nm, const Side& A, u64 n, bool ha
     c->timing = timing;
     if (rc != HMJ_OK) return rc;
   }
-  RC_TRY(record(c, ws.ev, 2));
+  RC_TRY(ws.ev.record(c, 2));
   // the key kernel's verdict on its input, before any kernel follows a row into the key columns
   if constexpr (Check::kWords != 0) {
     u64 e[Check::kWords];
@@ -437,7 +437,7 @@ int group_rows(hmj_ctx* c, const KeyJoinNames& nm, const Side& A, u64 n, bool ha
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(group_count_kernel, dim3((u32)blocks_of(ng)), T, 0, c->stream, (const u64*)ws.start.p, ng, cols[2].p, acc);
   HIP_TRY(hipGetLastError());
-  RC_TRY(record(c, ws.ev, 3));
+  RC_TRY(ws.ev.record(c, 3));
   // 6. sum / min / max of the payloads
   if (want & (HMJ_GROUP_SUM | HMJ_GROUP_MIN | HMJ_GROUP_MAX)) {
     const u64 waves = ((n + 63) / 64 + kAggChunks - 1) / kAggChunks;  // a wave walks kAggChunks chunks of 64 positions
@@ -445,7 +445,7 @@ int group_rows(hmj_ctx* c, const KeyJoinNames& nm, const Side& A, u64 n, bool ha
                        (const u64*)ws.blk_off.p, cols[3].p, cols[4].p, cols[5].p);
     HIP_TRY(hipGetLastError());
   }
-  RC_TRY(record(c, ws.ev, 4));
+  RC_TRY(ws.ev.record(c, 4));
   RC_TRY(read_back(c, acc, h, sizeof(h)));
   RC_TRY(collision_errors(c, nm, h[KA_ERR]));
   if constexpr (Check::kWords == 0) o->n_null = null_rows_of(h + GA_NULL);  // (else: the Check's words hold the count)

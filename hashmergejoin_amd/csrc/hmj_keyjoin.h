@@ -16,14 +16,14 @@
 //   sweep_count_kernel / sweep_emit_kernel   the kinds' rows of one relation, selected by their marks
 //   sort_rows_kernel / order_gather_kernel   the ordered kinds: (key64, index) rows for the u64 sort, columns gathered
 // Host side: the launch sequences around them that both joins run (order_collisions, kind_sweeps, kind_order) and the
-// small helpers of both (memo_join, read_back, record / elapsed, blocks_of, collision_errors, kind_counts).
+// small helpers of both (memo_join, blocks_of, collision_errors, kind_counts; read_back and the phase events: hmj_entry.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
 #include <cstring>
 
-#include "hmj_ctx.h"
+#include "hmj_entry.h"
 
 namespace {
 
@@ -447,28 +447,6 @@ __global__ __launch_bounds__(KJ_THREADS) void order_gather_kernel(const u64* __r
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
 u64 blocks_of(u64 n) { return (n + KJ_THREADS - 1) / KJ_THREADS; }
-
-int read_back(hmj_ctx* c, const void* dev, void* host, size_t bytes) {
-  HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return HMJ_OK;
-}
-
-// phase boundaries (profiling only): ev is the workspace's event array
-int record(hmj_ctx* c, hipEvent_t* ev, int k) {
-  if (!c->profiling) return HMJ_OK;
-  if (!ev[k]) HIP_TRY(hipEventCreate(&ev[k]));
-  HIP_TRY(hipEventRecord(ev[k], c->stream));
-  return HMJ_OK;
-}
-float elapsed(const hipEvent_t* ev, int a, int b) {
-  float ms = 0.f;
-  if (ev[a] && ev[b] && hipEventElapsedTime(&ms, ev[a], ev[b]) != hipSuccess) {
-    (void)hipGetLastError();
-    ms = 0.f;
-  }
-  return ms;
-}
 
 // join_device on {key64,row} rows under a workload_signature kind of its own (memo), with its spans collected.
 // hmj_set_key_prefix_bits describes the CALLER'S u64 relations; key64 is a hash or a packed tuple, about which the caller

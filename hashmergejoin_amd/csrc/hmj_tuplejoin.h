@@ -201,7 +201,7 @@ int tuple_join(hmj_ctx* c, const typename P::Side& RS, u64 nb, const typename P:
   u64* acc = (u64*)ws.acc.p;
   u64 h[KA_N];
   // 1. {key64, row} rows of both relations (+ the probe payloads' sum)
-  RC_TRY(record(c, ws.ev, 0));
+  RC_TRY(ws.ev.record(c, 0));
   HIP_TRY(hipMemsetAsync(acc, 0, tuple_acc_bytes<P>(), c->stream));
   RC_TRY(P::keys_begin(c));
   const void *rows_r = ws.rows_r.p, *rows_s = ws.rows_s.p;  // the rows the u64 join takes
@@ -213,13 +213,13 @@ int tuple_join(hmj_ctx* c, const typename P::Side& RS, u64 nb, const typename P:
   } else {  // NULL keys: only the rows that have a key are joined (the inner join walks no relation by row: no dense rows)
     RC_TRY(launch_keys_valid<P>(c, RS, SS, VB, VP, nb, np, *call, false, flags & HMJ_SUM_PROBE, acc, &rows_r, &tot_b, &rows_s, &tot_p));
   }
-  RC_TRY(record(c, ws.ev, 1));
+  RC_TRY(ws.ev.record(c, 1));
   RC_TRY(keys_end<P>(c, call, VB || VP, tot_b, tot_p, nb, np, &nvb, &nvp));
   if (nvb == 0 || nvp == 0) {  // (nothing to join: no plan either)
     std::memset(&c->plan, 0, sizeof(c->plan));
     c->plan.struct_size = sizeof(c->plan);
     std::memset(&c->timing, 0, sizeof(c->timing));
-    for (int k = 2; k < 5; k++) RC_TRY(record(c, ws.ev, k));
+    for (int k = 2; k < 5; k++) RC_TRY(ws.ev.record(c, k));
     if (flags & HMJ_SUM_PROBE) {
       RC_TRY(read_back(c, acc, h, sizeof(h)));
       out->sum_probe_all = h[KA_SUM_P];
@@ -229,7 +229,7 @@ int tuple_join(hmj_ctx* c, const typename P::Side& RS, u64 nb, const typename P:
   // 2. the u64 join of the {key64, row} rows: pairs of equal key64 as (key64, r_row, s_row), ordered by them if asked
   hmj_result inner;
   RC_TRY(memo_join(c, rows_r, nvb, rows_s, nvp, HMJ_MATERIALIZE | (flags & HMJ_ORDERED), P::kMemoInner, &inner));
-  RC_TRY(record(c, ws.ev, 2));
+  RC_TRY(ws.ev.record(c, 2));
   const u64 n_pairs = inner.n_matches;
   call->n_key_pairs = n_pairs;
   const u64 *ik = (const u64*)inner.key, *ir = (const u64*)inner.rval, *is = (const u64*)inner.sval;
@@ -248,7 +248,7 @@ int tuple_join(hmj_ctx* c, const typename P::Side& RS, u64 nb, const typename P:
                          checksum, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
     }
     n_out = n_pairs;
-    RC_TRY(record(c, ws.ev, 3));
+    RC_TRY(ws.ev.record(c, 3));
   } else {
     // 3b. hashed: tuple verification, payload gather, stable compaction (or the count modes' reduction)
     if (n_pairs && mat) {
@@ -271,14 +271,14 @@ int tuple_join(hmj_ctx* c, const typename P::Side& RS, u64 nb, const typename P:
                          nullptr, nullptr, acc, checksum ? 1 : 0, nullptr, nullptr);
       HIP_TRY(hipGetLastError());
     }
-    RC_TRY(record(c, ws.ev, 3));
+    RC_TRY(ws.ev.record(c, 3));
     // 4. ordered: runs of equal key64 with different build tuples, sorted by the tuple
     if (ordered && n_out > 1) {
       u64* cols[5] = {(u64*)ws.key.p, (u64*)ws.rrow.p, (u64*)ws.srow.p, (u64*)ws.rval.p, (u64*)ws.sval.p};
       RC_TRY(order_collisions<false>(c, ws, RS, Side{}, cols, n_out, acc));
     }
   }
-  RC_TRY(record(c, ws.ev, 4));
+  RC_TRY(ws.ev.record(c, 4));
   RC_TRY(read_back(c, acc, h, sizeof(h)));
   RC_TRY(collision_errors(c, P::names(), h[KA_ERR]));
   const u64* a = h + KA_ACC;
@@ -336,7 +336,7 @@ int tuple_join_kind(hmj_ctx* c, const typename P::Side& RS, u64 nb, const typena
   u64 h[kKindAccBlocks * KA_N];
   unsigned char *mark_r = (unsigned char*)ws.mark_r.p, *mark_s = (unsigned char*)ws.mark_s.p;
   // 1. {key64, row} rows of both relations (+ the probe payloads' sum), marks cleared
-  RC_TRY(record(c, ws.ev, 0));
+  RC_TRY(ws.ev.record(c, 0));
   HIP_TRY(hipMemsetAsync(acc, 0, tuple_acc_bytes<P>(), c->stream));
   RC_TRY(P::keys_begin(c));
   // (NULL keys: the dense rows stay indexed by row for the sweeps; the u64 joins take only the rows that have a key)
@@ -351,7 +351,7 @@ int tuple_join_kind(hmj_ctx* c, const typename P::Side& RS, u64 nb, const typena
   }
   if (nb) HIP_TRY(hipMemsetAsync(mark_r, 0, nb, c->stream));
   if (np) HIP_TRY(hipMemsetAsync(mark_s, 0, np, c->stream));
-  RC_TRY(record(c, ws.ev, 1));
+  RC_TRY(ws.ev.record(c, 1));
   RC_TRY(keys_end<P>(c, o, VB || VP, tot_b, tot_p, nb, np, &nvb, &nvp));
   // 2. + 3. the {key64,row} join(s) and the tuple verification, which marks the rows that have a partner
   u64 n_pairs = 0;
@@ -366,7 +366,7 @@ int tuple_join_kind(hmj_ctx* c, const typename P::Side& RS, u64 nb, const typena
     if (nK && nO) {
       hmj_result rep;
       RC_TRY(memo_join(c, rowsO, nO, rowsK, nK, HMJ_MATERIALIZE | HMJ_FIRST_WINS, bside ? P::kMemoBuildRep : P::kMemoProbeRep, &rep));
-      RC_TRY(record(c, ws.ev, 2));
+      RC_TRY(ws.ev.record(c, 2));
       n_pairs = rep.n_matches;  // <= nK
       if (n_pairs && !hashed) {
         hipLaunchKernelGGL((rep_verify_kernel<Side, false>), dim3((u32)blocks_of(n_pairs)), dim3(KJ_THREADS), 0, c->stream,
@@ -394,14 +394,14 @@ int tuple_join_kind(hmj_ctx* c, const typename P::Side& RS, u64 nb, const typena
         }
       }
     } else {
-      RC_TRY(record(c, ws.ev, 2));
+      RC_TRY(ws.ev.record(c, 2));
     }
   } else if (nvb && nvp) {
     RC_TRY(memo_join(c, rows_r, nvb, rows_s, nvp, HMJ_MATERIALIZE | (flags & HMJ_ORDERED), P::kMemoPairs, &inner));
-    RC_TRY(record(c, ws.ev, 2));
+    RC_TRY(ws.ev.record(c, 2));
     n_pairs = inner.n_matches;
   } else {
-    RC_TRY(record(c, ws.ev, 2));
+    RC_TRY(ws.ev.record(c, 2));
   }
   o->n_key_pairs = n_pairs;
   KindRows k;
@@ -421,14 +421,14 @@ int tuple_join_kind(hmj_ctx* c, const typename P::Side& RS, u64 nb, const typena
                          pairs[2], n_pairs, RS, SS, nullptr, nullptr, acc, checksum ? 1 : 0, mark_r, mark_s);
     HIP_TRY(hipGetLastError());
   }
-  RC_TRY(record(c, ws.ev, 3));
+  RC_TRY(ws.ev.record(c, 3));
   // 4. the sweeps (hashed: the pairs' survivors compacted in front of them), 5. ordered: the sort by key64, then -- hashed
   // only: packed, equal key64 is equal tuples, so there is no collision to search for -- runs of equal key64 with several
   // tuples sorted by tuple
   RC_TRY(kind_sweeps(c, ws, P::names(), k, RS, SS, o->probe_fill, o->build_fill, hashed, pairs, acc, acc_p, acc_b));
-  RC_TRY(record(c, ws.ev, 4));
+  RC_TRY(ws.ev.record(c, 4));
   RC_TRY(kind_order(c, ws, k, RS, SS, hashed, acc));
-  RC_TRY(record(c, ws.ev, 5));
+  RC_TRY(ws.ev.record(c, 5));
   RC_TRY(read_back(c, acc, h, sizeof(h)));
   RC_TRY(collision_errors(c, P::names(), h[KA_ERR]));
   kind_report(k, h + KA_ACC, h + KA_N + KA_ACC, h + 2 * KA_N + KA_ACC, out, &o->counts);

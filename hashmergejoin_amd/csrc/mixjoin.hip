@@ -545,30 +545,15 @@ int hmj_join_mixed_device(hmj_ctx* c, const hmj_mixed_rel* build, const hmj_mixe
   }
   // the out fields go to a full-size copy first; the caller gets the prefix its struct_size holds
   hmj_mixed_opts o;
-  std::memset(&o, 0, sizeof(o));
-  std::memcpy(&o, opts, opts->struct_size < sizeof(o) ? opts->struct_size : sizeof(o));
-  std::memset(&o.counts, 0, sizeof(o) - offsetof(hmj_mixed_opts, counts));
+  opts_prefix_in(&o, opts);
+  opts_clear_out(&o, opts, offsetof(hmj_mixed_opts, counts));
   o.counts = call.counts;
   o.n_key_pairs = call.n_key_pairs;
   o.n_collisions = call.n_collisions;
   o.n_build_null = call.n_build_null;
   o.n_probe_null = call.n_probe_null;
-  if (c->profiling) {
-    (void)hipStreamSynchronize(c->stream);
-    const hipEvent_t* ev = c->mix_ws.ev;
-    o.ms_key = elapsed(ev, 0, 1);
-    o.ms_join = elapsed(ev, 1, 2);
-    o.ms_verify = elapsed(ev, 2, 3);
-    if (inner) {
-      o.ms_order = elapsed(ev, 3, 4);
-    } else {
-      o.ms_emit = elapsed(ev, 3, 4);
-      o.ms_order = elapsed(ev, 4, 5);
-    }
-  }
-  const uint32_t room = opts->struct_size < sizeof(o) ? opts->struct_size : (uint32_t)sizeof(o);
-  o.struct_size = opts->struct_size;
-  std::memcpy(opts, &o, room);
+  fill_kind_ms(c, o, o.ms_key, c->mix_ws.ev, !inner);
+  opts_prefix_out(opts, o);
   return HMJ_OK;
 }
 
@@ -597,10 +582,8 @@ int hmj_group_mixed_device(hmj_ctx* c, const hmj_mixed_rel* rel, uint32_t flags,
   c->prep.valid = false;  // like any other call, this one discards a prepared build side
   // the out fields of opts go to a full-size copy first; the caller gets the prefix its struct_size holds
   hmj_group_opts o;
-  std::memset(&o, 0, sizeof(o));
-  std::memcpy(&o, opts, opts->struct_size < sizeof(o) ? opts->struct_size : sizeof(o));
-  o.n_null = o.n_collisions = 0;
-  o.ms_key = o.ms_sort = o.ms_groups = o.ms_agg = 0.f;
+  opts_prefix_in(&o, opts);
+  opts_clear_out(&o, opts, offsetof(hmj_group_opts, n_null));
   o.form = HMJ_COLS_HASHED;  // (force_hashed: ignored)
   const u32 bits = o.hash_bits;
   const u64 n = rel->n;
@@ -623,17 +606,9 @@ int hmj_group_mixed_device(hmj_ctx* c, const hmj_mixed_rel* rel, uint32_t flags,
       };
       RC_TRY(group_rows(c, kGroupNames, A, n, true, mat, key, MixGroupCheck<false>{}, &o, out));
     }
-    if (c->profiling) {
-      (void)hipStreamSynchronize(c->stream);
-      o.ms_key = elapsed(c->grp_ws.ev, 0, 1);
-      o.ms_sort = elapsed(c->grp_ws.ev, 1, 2);
-      o.ms_groups = elapsed(c->grp_ws.ev, 2, 3);
-      o.ms_agg = elapsed(c->grp_ws.ev, 3, 4);
-    }
+    fill_group_ms(c, o);
   }
-  const uint32_t room = opts->struct_size < sizeof(o) ? opts->struct_size : (uint32_t)sizeof(o);
-  o.struct_size = opts->struct_size;
-  std::memcpy(opts, &o, room);
+  opts_prefix_out(opts, o);
   c->grp_ws.live = mat;  // the live grouping of hmj_group_agg_device
   c->grp_ws.live_rows = n;
   c->grp_ws.live_groups = out->n_groups;

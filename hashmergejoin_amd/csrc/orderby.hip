@@ -27,7 +27,7 @@
 #include <cstdio>
 #include <cstring>
 
-#include "hmj_ctx.h"
+#include "hmj_entry.h"
 
 using hmj::u32;
 using hmj::u64;
@@ -54,8 +54,6 @@ struct OrdCols {
   u32 type[kMaxCols], flags[kMaxCols];
   u32 k;
 };
-
-__host__ __device__ __forceinline__ u32 width_of(u32 type) { return type >= HMJ_TYPE_F32 ? 4u << (type - HMJ_TYPE_F32) : 1u << (type & 3u); }
 
 // A valid fixed-width value as an unsigned integer of its own width whose order is the type's: signed integers with the
 // sign bit flipped; floats negative -> complement, else sign bit set, every NaN all ones (above +inf's key).
@@ -101,10 +99,7 @@ __device__ __forceinline__ u64 stream_window(const OrdCols& T, u64 r, bool activ
     if (c < (int)T.k) {  // (kernel arguments: uniform, like every test of T's type, flags and bitmap pointer)
       const u32 bm = T.vb[c] ? 1u : 0u;
       bool valid = active;
-      if (bm && active) {
-        const u64 b = T.voff[c] + r;
-        valid = (T.vb[c][b >> 3] >> (b & 7)) & 1u;
-      }
+      if (bm && active) valid = hmj::valid_bit(T.vb[c], T.voff[c] + r);
       const u32 inv = (T.flags[c] & HMJ_ORDER_DESC) ? 0xFFu : 0u;
       const u32 marker = ((T.flags[c] & HMJ_ORDER_NULLS_FIRST) != 0) == valid ? 1u : 0u;
       u64 L;
@@ -331,27 +326,6 @@ __global__ __launch_bounds__(OB_THREADS) void order_compact_kernel(const ulonglo
 // ---- host side -----------------------------------------------------------------------------------------------------------
 u64 blocks_of(u64 n) { return (n + OB_THREADS - 1) / OB_THREADS; }
 
-int read_back(hmj_ctx* c, const void* dev, void* host, size_t bytes) {
-  HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return HMJ_OK;
-}
-int record(hmj_ctx* c, int k) {
-  if (!c->profiling) return HMJ_OK;
-  hipEvent_t& e = c->ord_ws.ev[k];
-  if (!e) HIP_TRY(hipEventCreate(&e));
-  HIP_TRY(hipEventRecord(e, c->stream));
-  return HMJ_OK;
-}
-float elapsed(hmj_ctx* c, int a, int b) {
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, c->ord_ws.ev[a], c->ord_ws.ev[b]) != hipSuccess) {
-    (void)hipGetLastError();
-    return 0.f;
-  }
-  return ms;
-}
-
 int check_order_args(hmj_ctx* c, const hmj_order_col* cols, u32 n_cols, u64 n, const u64* map, const hmj_order_opts* opts) {
   char msg[192];
   if (!cols || !opts) return fail(c, HMJ_E_ARG, "hmj_order_by_device: cols / opts is NULL");
@@ -400,7 +374,7 @@ int check_order_args(hmj_ctx* c, const hmj_order_col* cols, u32 n_cols, u64 n, c
         return fail(c, HMJ_E_ARG, msg);
       }
     }
-    if (s.validity.bits && s.validity.bit_offset > UINT64_MAX - n) {
+    if (validity_overflows(s.validity, n)) {
       std::snprintf(msg, sizeof(msg), "hmj_order_by_device: column %u: validity bit_offset + n overflows 64 bits", k);
       return fail(c, HMJ_E_ARG, msg);
     }
@@ -412,10 +386,8 @@ int check_order_args(hmj_ctx* c, const hmj_order_col* cols, u32 n_cols, u64 n, c
   for (u32 k = 0; k < n_cols; k++) {
     const hmj_order_col& s = cols[k];
     const bool str = s.type == HMJ_ORDER_LARGE_STRING;
-    const unsigned char* vb = (const unsigned char*)s.validity.bits;
-    const bool hit = (!str && overlap(out, range_of(s.data, n * width_of(s.type)))) || (str && overlap(out, range_of(s.offsets, 8 * (n + 1)))) ||
-                     (vb && overlap(out, range_of(vb + (s.validity.bit_offset >> 3), ((s.validity.bit_offset & 7) + n + 7) / 8)));
-    if (hit) {
+    const Range in[2] = {str ? range_of(s.offsets, 8 * (n + 1)) : range_of(s.data, n * width_of(s.type)), validity_range(s.validity, n)};
+    if (first_overlap(&out, 1, in, 2)) {
       std::snprintf(msg, sizeof(msg), "hmj_order_by_device: column %u: row_map_out overlaps the column's values, offsets or bitmap", k);
       return fail(c, HMJ_E_ARG, msg);
     }
@@ -453,12 +425,12 @@ int order_rows(hmj_ctx* c, const OrdCols& T, u64 fixed_len, u64 n, u64* map, hmj
   const u64 most = (u64)c->num_cus * 8;  // workgroups of the grid-stride kernels
   u64 h[OA_N];
   // round 0: {first 8 stream bytes, row}; the key kernel's verdict on its input before anything else follows an offset
-  RC_TRY(record(c, 0));
+  RC_TRY(ws.ev.record(c, 0));
   HIP_TRY(hipMemsetAsync(acc, 0, OA_N * sizeof(u64), c->stream));
   HIP_TRY(hipMemsetAsync(acc + OA_ERR, 0xFF, kMaxCols * sizeof(u64), c->stream));
   hipLaunchKernelGGL(order_key_kernel, dim3((u32)(nblk < most ? nblk : most)), B, 0, c->stream, T, n, rows, acc);
   HIP_TRY(hipGetLastError());
-  RC_TRY(record(c, 1));
+  RC_TRY(ws.ev.record(c, 1));
   RC_TRY(read_back(c, acc, h, sizeof(h)));
   char msg[192];
   for (int k = 0; k < kMaxCols; k++) {  // the lowest-numbered column first, the mixed-key join's wording
@@ -480,7 +452,7 @@ int order_rows(hmj_ctx* c, const OrdCols& T, u64 fixed_len, u64 n, u64* map, hmj
   for (;;) {
     RC_TRY(sort_round(c, rows, m, sorted));
     rounds++;
-    if (rounds == 1) RC_TRY(record(c, 2));
+    if (rounds == 1) RC_TRY(ws.ev.record(c, 2));
     consumed += b;
     const u64 mblk = blocks_of(m);
     const dim3 G((u32)mblk), W((u32)(mblk < most ? mblk : most));
@@ -513,22 +485,22 @@ int order_rows(hmj_ctx* c, const OrdCols& T, u64 fixed_len, u64 n, u64* map, hmj
     hipLaunchKernelGGL(order_refine_kernel, dim3((u32)blocks_of(m2)), B, 0, c->stream, T, (const ulonglong2*)ws.lst[nxt].p, (const u32*)ws.rank[nxt].p,
                        m2, n, consumed, b, s, rows);
     HIP_TRY(hipGetLastError());
-    if (rounds == 1) RC_TRY(record(c, 3));
+    if (rounds == 1) RC_TRY(ws.ev.record(c, 3));
     m = m2;
     cur = nxt;
   }
-  if (rounds == 1) RC_TRY(record(c, 3));
-  RC_TRY(record(c, 4));
+  if (rounds == 1) RC_TRY(ws.ev.record(c, 3));
+  RC_TRY(ws.ev.record(c, 4));
   if (heads < segs + 1 || heads - segs > n) return fail(c, HMJ_E_HIP, "hmj_order_by_device: the heads' count is not in 1..n");
   o->n_distinct = heads - segs;  // every active segment of a round was counted as a head of the round before
   o->n_tied_rows = tied;
   o->n_rounds = rounds;
   if (c->profiling) {
     HIP_TRY(hipStreamSynchronize(c->stream));
-    o->ms_key = elapsed(c, 0, 1);
-    o->ms_sort = elapsed(c, 1, 2);
-    o->ms_map = elapsed(c, 2, 3);
-    o->ms_refine = elapsed(c, 3, 4);
+    o->ms_key = ws.ev.ms(0, 1);
+    o->ms_sort = ws.ev.ms(1, 2);
+    o->ms_map = ws.ev.ms(2, 3);
+    o->ms_refine = ws.ev.ms(3, 4);
   }
   return HMJ_OK;
 }
@@ -543,8 +515,8 @@ int hmj_order_by_device(hmj_ctx* c, const hmj_order_col* cols, uint32_t n_cols, 
   RC_TRY(check_order_args(c, cols, n_cols, n, (const u64*)row_map_out, opts));
   // the out fields of opts go to a full-size copy first; the caller gets the prefix its struct_size holds
   hmj_order_opts o;
-  std::memset(&o, 0, sizeof(o));
-  o.struct_size = opts->struct_size;
+  opts_prefix_in(&o, opts);
+  opts_clear_out(&o, opts, offsetof(hmj_order_opts, n_distinct));
   if (n > 0) {
     HIP_TRY(hipSetDevice(c->device));
     c->prep.valid = false;  // (as hmj_sort_u64_device, which a call of one row does not reach)
@@ -571,7 +543,7 @@ int hmj_order_by_device(hmj_ctx* c, const hmj_order_col* cols, uint32_t n_cols, 
       RC_TRY(order_rows(c, T, strings ? 0 : fixed_len, n, (u64*)row_map_out, &o));
     }
   }
-  std::memcpy(opts, &o, opts->struct_size < sizeof(o) ? opts->struct_size : sizeof(o));
+  opts_prefix_out(opts, o);
   return HMJ_OK;
 }
 

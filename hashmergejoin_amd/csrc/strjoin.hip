@@ -323,15 +323,6 @@ int opts_validity(hmj_ctx* c, const hmj_str_kind_opts* opts, const hmj_str_rel* 
   }
   return HMJ_OK;
 }
-// The out fields of a full-size copy o of the caller's opts are cleared from `counts` on; the in fields that lie behind them
-// (the validity bitmaps) are the caller's again, as far as its struct_size holds them.
-void clear_out_fields(hmj_str_kind_opts* o, const hmj_str_kind_opts* opts) {
-  using T = hmj_str_kind_opts;
-  std::memset(&o->counts, 0, sizeof(T) - offsetof(T, counts));
-  const size_t lo = offsetof(T, build_validity), hi = offsetof(T, n_build_null);
-  const size_t have = opts->struct_size < hi ? opts->struct_size : hi;
-  if (have > lo) std::memcpy((char*)o + lo, (const char*)opts + lo, have - lo);
-}
 
 }  // namespace
 
@@ -370,23 +361,14 @@ int hmj_join_str_device(hmj_ctx* c, const hmj_str_rel* build, const hmj_str_rel*
   HIP_TRY(hipSetDevice(c->device));
   // the out fields of opts go to a full-size copy first; the caller gets the prefix its struct_size holds
   hmj_str_join_opts o;
-  std::memset(&o, 0, sizeof(o));
-  std::memcpy(&o, opts, opts->struct_size < sizeof(o) ? opts->struct_size : sizeof(o));
+  opts_prefix_in(&o, opts);
   TupleCall call;  // (hmj_str_join_opts carries no bitmap: the call without NULL keys)
   call.bits = o.hash_bits;
   RC_TRY(run_join(c, build, probe, flags, true, &call, out, nullptr, nullptr));
   o.n_hash_pairs = call.n_key_pairs;
   o.n_collisions = call.n_collisions;
-  if (c->profiling) {
-    (void)hipStreamSynchronize(c->stream);
-    o.ms_hash = elapsed(c->str_ws.ev, 0, 1);
-    o.ms_join = elapsed(c->str_ws.ev, 1, 2);
-    o.ms_verify = elapsed(c->str_ws.ev, 2, 3);
-    o.ms_order = elapsed(c->str_ws.ev, 3, 4);
-  }
-  const uint32_t room = opts->struct_size < sizeof(o) ? opts->struct_size : (uint32_t)sizeof(o);
-  o.struct_size = opts->struct_size;
-  std::memcpy(opts, &o, room);
+  fill_join_ms(c, o, o.ms_hash, c->str_ws.ev);
+  opts_prefix_out(opts, o);
   return HMJ_OK;
 }
 
@@ -412,9 +394,9 @@ int hmj_join_kind_str_device(hmj_ctx* c, const hmj_str_rel* build, const hmj_str
   HIP_TRY(hipSetDevice(c->device));
   // the out fields of opts go to a full-size copy first; the caller gets the prefix its struct_size holds
   hmj_str_kind_opts o;
-  std::memset(&o, 0, sizeof(o));
-  std::memcpy(&o, opts, opts->struct_size < sizeof(o) ? opts->struct_size : sizeof(o));
-  clear_out_fields(&o, opts);
+  opts_prefix_in(&o, opts);
+  // (out fields from `counts` on; the validity bitmaps behind them are in fields)
+  opts_clear_out(&o, opts, offsetof(hmj_str_kind_opts, counts), offsetof(hmj_str_kind_opts, build_validity), offsetof(hmj_str_kind_opts, n_build_null));
   TupleCall call;
   call.bits = o.hash_bits;
   call.side = o.side;
@@ -428,22 +410,8 @@ int hmj_join_kind_str_device(hmj_ctx* c, const hmj_str_rel* build, const hmj_str
   o.n_collisions = call.n_collisions;
   o.n_build_null = call.n_build_null;
   o.n_probe_null = call.n_probe_null;
-  if (c->profiling) {
-    (void)hipStreamSynchronize(c->stream);
-    const hipEvent_t* ev = c->str_ws.ev;
-    o.ms_hash = elapsed(ev, 0, 1);
-    o.ms_join = elapsed(ev, 1, 2);
-    o.ms_verify = elapsed(ev, 2, 3);
-    if (inner) {
-      o.ms_order = elapsed(ev, 3, 4);
-    } else {
-      o.ms_emit = elapsed(ev, 3, 4);
-      o.ms_order = elapsed(ev, 4, 5);
-    }
-  }
-  const uint32_t room = opts->struct_size < sizeof(o) ? opts->struct_size : (uint32_t)sizeof(o);
-  o.struct_size = opts->struct_size;
-  std::memcpy(opts, &o, room);
+  fill_kind_ms(c, o, o.ms_hash, c->str_ws.ev, !inner);
+  opts_prefix_out(opts, o);
   return HMJ_OK;
 }
 

@@ -11,15 +11,15 @@
 //                         padding zeros).  Null counts per column, the HMJ_TAKE_NO_ROW entries and the out-of-range entries
 //                         are ballot popcounts, summed over the four waves in LDS, one atomicAdd per workgroup and counter.
 // The host checks the arguments (address ranges included), loops over chunks of kTakeChunk columns and reads the counters
-// back once.  The call owns one DevBuf (take_acc) and touches nothing else of the ctx: no result column, no prepared build
-// side, no plan, timing or memo.
+// back once.  The call owns its TakeWs (hmj_ctx.h: the counters, two events) and touches nothing else of the ctx: no result
+// column, no prepared build side, no plan, timing or memo.
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <cstdio>
 #include <cstring>
 
-#include "hmj_ctx.h"
+#include "hmj_entry.h"
 
 using hmj::u32;
 using hmj::u64;
@@ -31,7 +31,7 @@ constexpr int TK_THREADS = 256;
 constexpr int TK_WAVES = TK_THREADS / 64;
 constexpr int kTakeChunk = 8;  // columns per launch
 constexpr u64 kNoRow = HMJ_TAKE_NO_ROW;
-// take_acc slots (u64): [0] map entries equal to HMJ_TAKE_NO_ROW, [1] map entries >= n_src that are not, [2 + c] NULL slots
+// TakeWs::acc slots (u64): [0] map entries equal to HMJ_TAKE_NO_ROW, [1] map entries >= n_src that are not, [2 + c] NULL slots
 // of output column c (all columns of the call: one read-back)
 enum { TA_NO_ROW = 0, TA_BAD, TA_NULLS = 2, TA_N = TA_NULLS + HMJ_MAX_TAKE_COLS };
 
@@ -93,8 +93,7 @@ __global__ __launch_bounds__(TK_THREADS) void cols_take_kernel(TakeCols T, const
           }
         }
         if (T.vbits[c]) {  // (uniform)
-          const u64 b = T.voff[c] + r;
-          ok[c] = (T.vbits[c][b >> 3] >> (b & 7)) & 1u;
+          ok[c] = hmj::valid_bit(T.vbits[c], T.voff[c] + r);
         }
       }
     }
@@ -176,7 +175,7 @@ int check_take_args(hmj_ctx* c, const hmj_take_src* src, u32 n_cols, u64 n_src, 
       std::snprintf(msg, sizeof(msg), "hmj_take_cols_device: column %u: source data is not aligned to its width (%u)", k, w);
       return fail(c, HMJ_E_ARG, msg);
     }
-    if (s.validity.bits && s.validity.bit_offset > UINT64_MAX - n_src) {
+    if (validity_overflows(s.validity, n_src)) {
       std::snprintf(msg, sizeof(msg), "hmj_take_cols_device: column %u: validity bit_offset + n_src overflows 64 bits", k);
       return fail(c, HMJ_E_ARG, msg);
     }
@@ -196,21 +195,16 @@ int check_take_args(hmj_ctx* c, const hmj_take_src* src, u32 n_cols, u64 n_src, 
   // A destination the kernel writes must not be something it reads: the map, or any source column or source bitmap of the
   // call (a later chunk's source included).  Address ranges only; n_out == 0 writes nothing.
   if (n_out == 0) return HMJ_OK;
-  const Range map = range_of(row_map, 8 * n_out);
+  Range in[1 + 2 * HMJ_MAX_TAKE_COLS] = {range_of(row_map, 8 * n_out)};
+  for (u32 j = 0; j < n_cols; j++) {
+    in[1 + 2 * j] = range_of(src[j].data, n_src * src[j].width);
+    in[2 + 2 * j] = validity_range(src[j].validity, n_src);
+  }
   for (u32 k = 0; k < n_cols; k++) {
     const Range out[2] = {range_of(dst[k].data, n_out * src[k].width), range_of(dst[k].validity, 8 * ((n_out + 63) / 64))};
-    for (const Range& o : out) {
-      bool hit = overlap(o, map);
-      for (u32 j = 0; j < n_cols && !hit; j++) {
-        const hmj_validity& v = src[j].validity;
-        const unsigned char* vb = (const unsigned char*)v.bits;
-        hit = overlap(o, range_of(src[j].data, n_src * src[j].width)) ||
-              (vb && n_src && overlap(o, range_of(vb + (v.bit_offset >> 3), ((v.bit_offset & 7) + n_src + 7) / 8)));
-      }
-      if (hit) {
-        std::snprintf(msg, sizeof(msg), "hmj_take_cols_device: column %u: the destination overlaps the row map or a source column", k);
-        return fail(c, HMJ_E_ARG, msg);
-      }
+    if (first_overlap(out, 2, in, 1 + 2 * (int)n_cols)) {
+      std::snprintf(msg, sizeof(msg), "hmj_take_cols_device: column %u: the destination overlaps the row map or a source column", k);
+      return fail(c, HMJ_E_ARG, msg);
     }
   }
   return HMJ_OK;
@@ -218,14 +212,11 @@ int check_take_args(hmj_ctx* c, const hmj_take_src* src, u32 n_cols, u64 n_src, 
 
 int take_cols(hmj_ctx* c, const hmj_take_src* src, u32 n_cols, u64 n_src, const u64* row_map, u64 n_out, hmj_take_dst* dst,
               hmj_take_opts* o) {
-  RC_TRY(ensure_dev(c, c->take_acc, TA_N * sizeof(u64)));
-  u64* acc = (u64*)c->take_acc.p;
+  TakeWs& ws = c->take_ws;
+  RC_TRY(ensure_dev(c, ws.acc, TA_N * sizeof(u64)));
+  u64* acc = (u64*)ws.acc.p;
   HIP_TRY(hipMemsetAsync(acc, 0, TA_N * sizeof(u64), c->stream));
-  if (c->profiling) {
-    for (auto& e : c->take_ev)
-      if (!e) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventRecord(c->take_ev[0], c->stream));
-  }
+  RC_TRY(ws.ev.record(c, 0));
   const u64 need = (n_out + TK_THREADS - 1) / TK_THREADS, most = (u64)c->num_cus * 16;
   const dim3 grid((u32)(need < most ? need : most));
   for (u32 k0 = 0; k0 < n_cols; k0 += kTakeChunk) {
@@ -254,10 +245,9 @@ int take_cols(hmj_ctx* c, const hmj_take_src* src, u32 n_cols, u64 n_src, const 
                          count_map);
     HIP_TRY(hipGetLastError());
   }
-  if (c->profiling) HIP_TRY(hipEventRecord(c->take_ev[1], c->stream));
+  RC_TRY(ws.ev.record(c, 1));
   u64 h[TA_N];
-  HIP_TRY(hipMemcpyAsync(h, acc, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  RC_TRY(read_back(c, acc, h, sizeof(h)));
   if (h[TA_BAD]) {
     char msg[192];
     std::snprintf(msg, sizeof(msg), "hmj_take_cols_device: %llu row_map entries are >= n_src (%llu) and not HMJ_TAKE_NO_ROW", h[TA_BAD],
@@ -266,10 +256,7 @@ int take_cols(hmj_ctx* c, const hmj_take_src* src, u32 n_cols, u64 n_src, const 
   }
   for (u32 k = 0; k < n_cols; k++) dst[k].null_count = h[TA_NULLS + k];
   o->n_no_row = h[TA_NO_ROW];
-  if (c->profiling && hipEventElapsedTime(&o->ms_take, c->take_ev[0], c->take_ev[1]) != hipSuccess) {
-    (void)hipGetLastError();
-    o->ms_take = 0.f;
-  }
+  if (c->profiling) o->ms_take = ws.ev.ms(0, 1);
   return HMJ_OK;
 }
 
@@ -283,15 +270,15 @@ int hmj_take_cols_device(hmj_ctx* c, const hmj_take_src* src, uint32_t n_cols, u
   RC_TRY(check_take_args(c, src, n_cols, n_src, (const u64*)row_map, n_out, dst, opts));
   // the out fields of opts go to a full-size copy first; the caller gets the prefix its struct_size holds
   hmj_take_opts o;
-  std::memset(&o, 0, sizeof(o));
-  o.struct_size = opts->struct_size;
+  opts_prefix_in(&o, opts);
+  opts_clear_out(&o, opts, offsetof(hmj_take_opts, n_no_row));
   if (n_out == 0) {
     for (u32 k = 0; k < n_cols; k++) dst[k].null_count = 0;
   } else {
     HIP_TRY(hipSetDevice(c->device));
     RC_TRY(take_cols(c, src, n_cols, n_src, (const u64*)row_map, n_out, dst, &o));
   }
-  std::memcpy(opts, &o, opts->struct_size < sizeof(o) ? opts->struct_size : sizeof(o));
+  opts_prefix_out(opts, o);
   return HMJ_OK;
 }
 

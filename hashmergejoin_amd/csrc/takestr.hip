@@ -7,7 +7,7 @@
 //                             and checks the row (decreasing offsets, an end behind chars_bytes) before its length counts.  A
 //                             wave covers 64 rows that start at a multiple of 64: its ballot of "valid" is one bitmap word,
 //                             the counts are ballot popcounts (one atomicAdd per workgroup and counter).  The workgroup's
-//                             exclusive scan of the lengths goes to dst->offsets, its total to takestr_blk.
+//                             exclusive scan of the lengths goes to dst->offsets, its total to TakeStrWs::blk.
 //   (hmj::launch_scan_u64 over the totals, as hmj_keyjoin.h places its per-workgroup counts)
 //   str_take_place_kernel     streaming: adds every workgroup's base to its 256 offsets, writes offsets[n_out] and the total.
 //   -- the host reads the counters back: a bad call stops here, a sizing call is complete --
@@ -19,14 +19,14 @@
 //                             the row), shifts them into place and ORs them into the piece, which leaves in one 16-byte
 //                             store.  The column's last piece is stored bytewise when it is short, so nothing at or behind
 //                             total_bytes is written.
-// The call owns two DevBufs (takestr_acc, takestr_blk) and touches nothing else of the ctx.
+// The call owns its TakeStrWs (hmj_ctx.h: two DevBufs, four events) and touches nothing else of the ctx.
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <cstdio>
 #include <cstring>
 
-#include "hmj_ctx.h"
+#include "hmj_entry.h"
 
 using hmj::u32;
 using hmj::u64;
@@ -42,7 +42,7 @@ constexpr int TS_WAVES = TS_THREADS / 64;
 constexpr u32 kTileBytes = TS_THREADS * 16;  // output bytes per workgroup of the bytes phase: one 16-byte piece per lane
 constexpr u32 kStageRows = 1024;             // rows of a tile whose starts are staged in LDS (16 KiB)
 constexpr u64 kNoRow = HMJ_TAKE_NO_ROW;
-// takestr_acc slots (u64).  The first TS_N_RED are ballot popcounts of the offsets phase: map entries equal to
+// TakeStrWs::acc slots (u64).  The first TS_N_RED are ballot popcounts of the offsets phase: map entries equal to
 // HMJ_TAKE_NO_ROW, map entries >= n_src that are not, taken valid rows whose offsets decrease / end behind chars_bytes, NULL
 // output slots; TS_TOTAL is offsets[n_out].
 enum { TS_NO_ROW = 0, TS_BAD_MAP, TS_BAD_DEC, TS_BAD_END, TS_NULLS, TS_N_RED, TS_TOTAL = TS_N_RED, TS_N };
@@ -69,20 +69,12 @@ __global__ __launch_bounds__(TS_THREADS) void str_take_offsets_kernel(const u64*
   if (have) {
     b = offsets[r];
     e = offsets[r + 1];
-    if (vbits) {  // (uniform)
-      const u64 bit = voff + r;
-      ok = (vbits[bit >> 3] >> (bit & 7)) & 1u;
-    }
+    if (vbits) ok = hmj::valid_bit(vbits, voff + r);  // (uniform)
   }
   const bool dec = ok && e < b, end = ok && !dec && e > chars_bytes;
   ok = ok && !dec && !end;
   const u64 len = ok ? e - b : 0ull;
-  u64 incl = len;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const u64 t = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += t;
-  }
+  const u64 incl = hmj::wave_incl_scan_u64(len, lane);
   const u64 m = __ballot(ok);
   const u32 n_no = (u32)__builtin_popcountll(__ballot(in && r == kNoRow));
   const u32 n_map = (u32)__builtin_popcountll(__ballot(in && !have && r != kNoRow));
@@ -217,7 +209,7 @@ int check_take_str_args(hmj_ctx* c, const hmj_take_str_src* src, u64 n_src, cons
   if (n_src > 0 && !src->offsets) return fail(c, HMJ_E_ARG, "hmj_take_str_device: source offsets are NULL");
   if ((uintptr_t)src->offsets & 7u) return fail(c, HMJ_E_ARG, "hmj_take_str_device: source offsets are not aligned to 8 bytes");
   if (!src->chars && src->chars_bytes) return fail(c, HMJ_E_ARG, "hmj_take_str_device: source chars are NULL with chars_bytes > 0");
-  if (src->validity.bits && src->validity.bit_offset > UINT64_MAX - n_src)
+  if (validity_overflows(src->validity, n_src))
     return fail(c, HMJ_E_ARG, "hmj_take_str_device: validity bit_offset + n_src overflows 64 bits");
   if (n_out > 0 && !dst->offsets) return fail(c, HMJ_E_ARG, "hmj_take_str_device: destination offsets are NULL");
   if ((uintptr_t)dst->offsets & 7u) return fail(c, HMJ_E_ARG, "hmj_take_str_device: destination offsets are not aligned to 8 bytes");
@@ -226,48 +218,32 @@ int check_take_str_args(hmj_ctx* c, const hmj_take_str_src* src, u64 n_src, cons
   // A destination the kernels write must not be something they read, nor another destination.  Address ranges only;
   // n_out == 0 writes nothing.
   if (n_out == 0) return HMJ_OK;
-  const hmj_validity& v = src->validity;
-  const u8* vb = (const u8*)v.bits;
   const Range in[4] = {range_of(row_map, 8 * n_out), range_of(src->offsets, 8 * (n_src + 1)), range_of(src->chars, src->chars_bytes),
-                       vb && n_src ? range_of(vb + (v.bit_offset >> 3), ((v.bit_offset & 7) + n_src + 7) / 8) : Range{0, 0}};
+                       validity_range(src->validity, n_src)};
   const Range out[3] = {range_of(dst->offsets, 8 * (n_out + 1)), range_of(dst->validity, 8 * ((n_out + 63) / 64)),
                         range_of(dst->chars, dst->chars_capacity)};
   for (int a = 0; a < 3; a++) {
-    for (const Range& r : in)
-      if (overlap(out[a], r))
-        return fail(c, HMJ_E_ARG, "hmj_take_str_device: a destination overlaps the row map, the source offsets, chars or bitmap");
-    for (int b = a + 1; b < 3; b++)
-      if (overlap(out[a], out[b])) return fail(c, HMJ_E_ARG, "hmj_take_str_device: two destinations overlap");
+    if (first_overlap(out + a, 1, in, 4))
+      return fail(c, HMJ_E_ARG, "hmj_take_str_device: a destination overlaps the row map, the source offsets, chars or bitmap");
+    if (first_overlap(out + a, 1, out + a + 1, 2 - a)) return fail(c, HMJ_E_ARG, "hmj_take_str_device: two destinations overlap");
   }
   return HMJ_OK;
-}
-
-float elapsed_or_zero(hipEvent_t a, hipEvent_t b) {
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, a, b) != hipSuccess) {
-    (void)hipGetLastError();
-    ms = 0.f;
-  }
-  return ms;
 }
 
 int take_str(hmj_ctx* c, const hmj_take_str_src* src, u64 n_src, const u64* row_map, u64 n_out, hmj_take_str_dst* dst,
              hmj_take_str_opts* o) {
   const u32 nblk = (u32)((n_out + TS_THREADS - 1) / TS_THREADS);
-  RC_TRY(ensure_dev(c, c->takestr_acc, TS_N * sizeof(u64)));
-  RC_TRY(ensure_dev(c, c->takestr_blk, (2 * (size_t)nblk + 1) * sizeof(u64)));
-  u64* acc = (u64*)c->takestr_acc.p;
-  u64* blk_tot = (u64*)c->takestr_blk.p;
+  TakeStrWs& ws = c->takestr_ws;
+  RC_TRY(ensure_dev(c, ws.acc, TS_N * sizeof(u64)));
+  RC_TRY(ensure_dev(c, ws.blk, (2 * (size_t)nblk + 1) * sizeof(u64)));
+  u64* acc = (u64*)ws.acc.p;
+  u64* blk_tot = (u64*)ws.blk.p;
   u64* blk_off = blk_tot + nblk;  // nblk + 1
   const u64* src_off = (const u64*)src->offsets;
   u64* out_off = (u64*)dst->offsets;
   u64* out_val = (u64*)dst->validity;
   HIP_TRY(hipMemsetAsync(acc, 0, TS_N * sizeof(u64), c->stream));
-  if (c->profiling) {
-    for (auto& e : c->takestr_ev)
-      if (!e) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventRecord(c->takestr_ev[0], c->stream));
-  }
+  RC_TRY(ws.ev.record(c, 0));
   hipLaunchKernelGGL(str_take_offsets_kernel, dim3(nblk), dim3(TS_THREADS), 0, c->stream, src_off, src->chars_bytes,
                      (const u8*)src->validity.bits, src->validity.bit_offset, row_map, n_out, n_src, out_off, out_val, blk_tot,
                      acc);
@@ -275,11 +251,10 @@ int take_str(hmj_ctx* c, const hmj_take_str_src* src, u64 n_src, const u64* row_
   HIP_TRY(hmj::launch_scan_u64(blk_tot, blk_off, nblk, c->stream));
   hipLaunchKernelGGL(str_take_place_kernel, dim3(nblk), dim3(TS_THREADS), 0, c->stream, out_off, n_out, blk_off, nblk, acc);
   HIP_TRY(hipGetLastError());
-  if (c->profiling) HIP_TRY(hipEventRecord(c->takestr_ev[1], c->stream));
+  RC_TRY(ws.ev.record(c, 1));
   // the one synchronisation before the bytes phase: a bad call stops here, a sizing call is complete
   u64 h[TS_N];
-  HIP_TRY(hipMemcpyAsync(h, acc, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  RC_TRY(read_back(c, acc, h, sizeof(h)));
   char msg[224];
   if (h[TS_BAD_MAP]) {
     std::snprintf(msg, sizeof(msg), "hmj_take_str_device: %llu row_map entries are >= n_src (%llu) and not HMJ_TAKE_NO_ROW", h[TS_BAD_MAP],
@@ -297,7 +272,7 @@ int take_str(hmj_ctx* c, const hmj_take_str_src* src, u64 n_src, const u64* row_
   dst->null_count = h[TS_NULLS];
   dst->total_bytes = total;
   o->n_no_row = h[TS_NO_ROW];
-  if (c->profiling) o->ms_offsets = elapsed_or_zero(c->takestr_ev[0], c->takestr_ev[1]);
+  if (c->profiling) o->ms_offsets = ws.ev.ms(0, 1);
   if (!dst->chars) return HMJ_OK;  // the sizing call
   if (dst->chars_capacity < total) {
     std::snprintf(msg, sizeof(msg), "hmj_take_str_device: chars_capacity (%llu) is smaller than total_bytes (%llu)",
@@ -307,13 +282,13 @@ int take_str(hmj_ctx* c, const hmj_take_str_src* src, u64 n_src, const u64* row_
   if (total == 0) return HMJ_OK;
   const u64 tiles = (total + kTileBytes - 1) / kTileBytes;
   if (tiles > 0x7FFFFFFFull) return fail(c, HMJ_E_ARG, "hmj_take_str_device: more output bytes than one launch covers (2^43)");
-  if (c->profiling) HIP_TRY(hipEventRecord(c->takestr_ev[2], c->stream));
+  RC_TRY(ws.ev.record(c, 2));
   hipLaunchKernelGGL(str_take_bytes_kernel, dim3((u32)tiles), dim3(TS_THREADS), 0, c->stream, (const u8*)src->chars, src_off, row_map,
                      out_off, n_out, total, (u8*)dst->chars);
   HIP_TRY(hipGetLastError());
-  if (c->profiling) HIP_TRY(hipEventRecord(c->takestr_ev[3], c->stream));
+  RC_TRY(ws.ev.record(c, 3));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  if (c->profiling) o->ms_chars = elapsed_or_zero(c->takestr_ev[2], c->takestr_ev[3]);
+  if (c->profiling) o->ms_chars = ws.ev.ms(2, 3);
   return HMJ_OK;
 }
 
@@ -327,8 +302,8 @@ int hmj_take_str_device(hmj_ctx* c, const hmj_take_str_src* src, uint64_t n_src,
   RC_TRY(check_take_str_args(c, src, n_src, (const u64*)row_map, n_out, dst, opts));
   // the out fields of opts go to a full-size copy first; the caller gets the prefix its struct_size holds
   hmj_take_str_opts o;
-  std::memset(&o, 0, sizeof(o));
-  o.struct_size = opts->struct_size;
+  opts_prefix_in(&o, opts);
+  opts_clear_out(&o, opts, offsetof(hmj_take_str_opts, n_no_row));
   int rc = HMJ_OK;
   if (n_out == 0) {
     dst->null_count = 0;
@@ -337,7 +312,7 @@ int hmj_take_str_device(hmj_ctx* c, const hmj_take_str_src* src, uint64_t n_src,
     HIP_TRY(hipSetDevice(c->device));
     rc = take_str(c, src, n_src, (const u64*)row_map, n_out, dst, &o);
   }
-  if (rc == HMJ_OK) std::memcpy(opts, &o, opts->struct_size < sizeof(o) ? opts->struct_size : sizeof(o));
+  if (rc == HMJ_OK) opts_prefix_out(opts, o);
   return rc;
 }
 
