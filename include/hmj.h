@@ -900,8 +900,9 @@ int hmj_join_mixed_device(hmj_ctx* ctx, const hmj_mixed_rel* build, const hmj_mi
  * through first_row (hmj_take_cols_device) is the DISTINCT table.  The HMJ_GROUP_* bits of opts->want add count, sum / min /
  * max and group_of_row; a column not asked for is NULL.  sum / min / max run over rel->vals, or over the row index where
  * vals is NULL; sum wraps mod 2^64, min / max compare unsigned.  group_of_row[i] is the index of row i's group into the
- * group columns.  The result is owned by the ctx and valid until the next call on it or hmj_release_result;
- * hmj_take_cols_device keeps it.  Like any other call this one discards a prepared build side.
+ * group columns.  The result is owned by the ctx and valid until the next call on it or hmj_release_result; the calls
+ * that say so keep it: hmj_take_cols_device, hmj_take_str_device, hmj_group_agg_device, hmj_filter_device and
+ * hmj_order_by_device.  Like any other call this one discards a prepared build side.
  * Order of groups.  HMJ_ORDERED (implies HMJ_MATERIALIZE): ascending by (key64, the tuple column by column as UNSIGNED
  * integers, NULLS LAST in each column) -- in the packed form plainly ascending tuple order, i.e. GROUP BY ... ORDER BY the
  * keys.  Without it the order is unspecified; all group columns agree with each other and with group_of_row.
