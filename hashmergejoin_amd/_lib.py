@@ -9,7 +9,9 @@ HMJ_FIRST_WINS = 0x04
 HMJ_CHECKSUM = 0x08
 HMJ_SUM_PROBE = 0x10
 HMJ_NULL_EQUAL = 0x20  # NULL key slots match NULL slots of the same column (the column kinds and the mixed entry)
+HMJ_OK, HMJ_E_ARG, HMJ_E_NODEV, HMJ_E_OOM, HMJ_E_HIP, HMJ_E_UNSUPPORTED = 0, -1, -2, -3, -4, -5
 HMJ_E_RCCL, HMJ_E_PEER, HMJ_E_TIMEOUT = -6, -7, -8
+HMJ_ABI_VERSION = 5
 # hmj_timing.path bits
 HMJ_PATH_SLAB, HMJ_PATH_EXACT, HMJ_PATH_UNIQ_WRITE, HMJ_PATH_SPLIT, HMJ_PATH_WINDOW = 0x1, 0x2, 0x4, 0x8, 0x10
 HMJ_PATH_ORDER_DEFERRED, HMJ_PATH_ORDER_BY_KEY, HMJ_PATH_PREPARED, HMJ_PATH_CHUNKED_BUILD = 0x20, 0x40, 0x80, 0x100
@@ -387,13 +389,17 @@ HMJ_REFUSED_PREFIX_VIOLATED, HMJ_REFUSED_EXPANSION_GAVE_UP = 0x4000, 0x8000
 HMJ_COOL_UNIQ_WRITE, HMJ_COOL_SORTED_WRITE, HMJ_COOL_GTABLE, HMJ_COOL_GTABLE_WRITE = 0x1, 0x2, 0x4, 0x8
 HMJ_COOL_RANK_SORT, HMJ_COOL_RANK_SORT_SLAB, HMJ_COOL_EXPANSION, HMJ_COOL_SORT_SLAB = 0x10, 0x20, 0x40, 0x80
 HMJ_COOL_SLAB, HMJ_COOL_SLAB_PROBE, HMJ_COOL_ONE_PASS_WRITE, HMJ_COOL_EXACT_PREFIX = 0x100, 0x200, 0x400, 0x800
-HMJ_COOL_RANK_RUNS = 0x1000
+HMJ_COOL_RANK_RUNS, HMJ_COOL_SORT_MSD = 0x1000, 0x2000
+
+
+HMJ_PLACE_MAX_CAND = 4
 
 
 class PlaceInfo(C.Structure):
     _fields_ = [("name", C.c_char * 16), ("bytes", C.c_uint64), ("fill_TBps", C.c_float), ("candidates", C.c_int),
                 ("ms_search", C.c_float), ("searched", C.c_int), ("aborted", C.c_int), ("budget_ms", C.c_float),
-                ("cand_ms_alloc", C.c_float * 4), ("cand_ms_fill", C.c_float * 4), ("cand_TBps", C.c_float * 4)]
+                ("cand_ms_alloc", C.c_float * HMJ_PLACE_MAX_CAND), ("cand_ms_fill", C.c_float * HMJ_PLACE_MAX_CAND),
+                ("cand_TBps", C.c_float * HMJ_PLACE_MAX_CAND)]
 
 
 def lib_path():
@@ -414,6 +420,8 @@ class ExchangeInfo(C.Structure):
 
 
 HMJ_MAX_RANKS, HMJ_MAX_ROUNDS = 16, 16
+HMJ_UNIQUE_ID_BYTES = 128
+HMJ_OWNER_DIGIT, HMJ_OWNER_SPLIT = 0, 1  # hmj_comm_set_owner_path
 
 
 class DigitPlan(C.Structure):
@@ -433,6 +441,77 @@ class Transport(C.Structure):
                 ("alltoallv", ALLTOALLV_FN)]
 
 
+# every function of include/hmj.h: name -> (restype, argtypes)
+_i, _u, _u32, _vp, _cp, _P = C.c_int, C.c_uint64, C.c_uint32, C.c_void_p, C.c_char_p, C.POINTER
+_SIGNATURES = {
+    "hmj_create": (_i, [_P(_vp), _i]),
+    "hmj_destroy": (None, [_vp]),
+    "hmj_set_stream": (_i, [_vp, _vp]),
+    "hmj_reserve": (_i, [_vp, _u, _u, _u, _u32]),
+    "hmj_set_radix_bits": (_i, [_vp, _i]),
+    "hmj_autotune_radix_bits": (_i, [_vp, _u, _u, _i, _P(_i), _P(C.c_double)]),
+    "hmj_set_key_prefix_bits": (_i, [_vp, _i]),
+    "hmj_plan": (_i, [_u, _P(_i), _P(_i), _P(_i * 4)]),
+    "hmj_set_profiling": (_i, [_vp, _i]),
+    "hmj_last_timing": (_i, [_vp, _P(Timing)]),
+    "hmj_last_plan": (_i, [_vp, _P(PlanDesc)]),
+    "hmj_forget_workloads": (_i, [_vp]),
+    "hmj_placement_info": (_i, [_vp, _P(PlaceInfo), _i]),
+    "hmj_strerror": (_cp, [_i]),
+    "hmj_last_error": (_cp, [_vp]),
+    "hmj_version": (_cp, []),
+    "hmj_abi_version": (_i, []),
+    "hmj_join_u64_device": (_i, [_vp, _vp, _u, _vp, _u, _u32, _P(JoinResult)]),
+    "hmj_join_kind_u64_device": (_i, [_vp, _vp, _u, _vp, _u, _u32, _P(JoinOpts), _P(JoinResult)]),
+    "hmj_join_build_kind_u64_device": (_i, [_vp, _vp, _u, _vp, _u, _u32, _P(BuildJoinOpts), _P(JoinResult)]),
+    "hmj_hash_str_device": (_i, [_vp, _vp, _vp, _u, _u32, _vp]),
+    "hmj_join_str_device": (_i, [_vp, _P(StrRel), _P(StrRel), _u32, _P(StrJoinOpts), _P(StrResult)]),
+    "hmj_join_kind_str_device": (_i, [_vp, _P(StrRel), _P(StrRel), _u32, _P(StrKindOpts), _P(StrResult)]),
+    "hmj_join_cols_device": (_i, [_vp, _P(ColsRel), _P(ColsRel), _u32, _P(ColsJoinOpts), _P(ColsResult)]),
+    "hmj_join_kind_cols_device": (_i, [_vp, _P(ColsRel), _P(ColsRel), _u32, _P(ColsKindOpts), _P(ColsResult)]),
+    "hmj_join_mixed_device": (_i, [_vp, _P(MixedRel), _P(MixedRel), _u32, _P(MixedOpts), _P(ColsResult)]),
+    "hmj_group_cols_device": (_i, [_vp, _P(ColsRel), _u32, _P(GroupOpts), _P(GroupResult)]),
+    "hmj_group_mixed_device": (_i, [_vp, _P(MixedRel), _u32, _P(GroupOpts), _P(GroupResult)]),
+    "hmj_group_agg_device": (_i, [_vp, _P(AggSrc), _u32, _u, _P(AggDst), _P(GroupAggOpts)]),
+    "hmj_order_by_device": (_i, [_vp, _P(OrderCol), _u32, _u, _vp, _P(OrderOpts)]),
+    "hmj_filter_device": (_i, [_vp, _P(FilterTerm), _u32, _u, _vp, _vp, _P(FilterOpts)]),
+    "hmj_take_cols_device": (_i, [_vp, _P(TakeSrc), _u32, _u, _vp, _u, _P(TakeDst), _P(TakeOpts)]),
+    "hmj_take_str_device": (_i, [_vp, _P(TakeStrSrc), _u, _vp, _u, _P(TakeStrDst), _P(TakeStrOpts)]),
+    "hmj_prepare_build_u64_device": (_i, [_vp, _vp, _u, _u]),
+    "hmj_join_u64": (_i, [_vp, _vp, _u, _vp, _u, _u32, _P(JoinResult)]),
+    "hmj_join_u64_rows": (_i, [_vp, _vp, _u, _vp, _u, _u32, _P(JoinResult), _P(_vp)]),
+    "hmj_rows_free": (None, [_vp]),
+    "hmj_host_pool_trim": (_u, [_u]),
+    "hmj_host_pool_bytes": (_u, []),
+    "hmj_set_host_threads": (_i, [_vp, _i]),
+    "hmj_release_result": (None, [_vp]),
+    "hmj_comm_unique_id": (_i, [_vp]),
+    "hmj_comm_init_rank": (_i, [_vp, _i, _i, _vp]),
+    "hmj_comm_set_transport": (_i, [_vp, _P(Transport)]),
+    "hmj_comm_destroy": (_i, [_vp]),
+    "hmj_comm_set_message_bytes": (_i, [_vp, _u, _u]),
+    "hmj_exchange_join_u64_device": (_i, [_vp, _vp, _u, _vp, _u, _u32, _P(JoinResult), _P(JoinResult)]),
+    "hmj_exchange_join_kind_u64_device": (_i, [_vp, _vp, _u, _vp, _u, _u32, _P(ExchangeKindOpts), _P(JoinResult), _P(JoinResult)]),
+    "hmj_owner_split_u64_device": (_i, [_vp, _vp, _u, _i, _U64P, _vp, _vp]),
+    "hmj_last_exchange_info": (_i, [_vp, _P(ExchangeInfo)]),
+    "hmj_comm_set_timeout_ms": (_i, [_vp, _u]),
+    "hmj_comm_get_timeout_ms": (_i, [_vp, _U64P]),
+    "hmj_comm_set_owner_path": (_i, [_vp, _i]),
+    "hmj_comm_set_self_exchange": (_i, [_vp, _i]),
+    "hmj_exchange_digit_plan": (_i, [_i, _U64P, _u, _u32, _P(DigitPlan)]),
+    "hmj_exchange_digit_layout": (_i, [_i, _i, _P(DigitPlan), _U64P, _U64P, _U64P, _U64P, _U64P, _U64P]),
+    "hmj_exchange_rounds": (_u32, [_i, _U64P, _u]),
+    "hmj_exchange_layout": (_i, [_i, _i, _U64P, _u32, _i, _U64P, _U64P, _U64P, _U64P, _U64P]),
+    "hmj_partition_u64_device": (_i, [_vp, _vp, _u, _i, _i, _vp, _vp]),
+    "hmj_sort_u64_device": (_i, [_vp, _vp, _u, _vp]),
+    "hmj_sort_rows_by_u64_host": (_i, [_vp, _vp, _u, _u32, _u32]),
+    "hmj_argsort_u64_host": (_i, [_vp, _vp, _u, _u32, _vp]),
+    "hmj_gen_build_u64_device": (_i, [_vp, _vp, _u, _u, _u]),
+    "hmj_gen_probe_u64_device": (_i, [_vp, _vp, _u, _u, _u, _u, _u]),
+    "hmj_gen_from_cdf_u64_device": (_i, [_vp, _vp, _u, _u, _vp, _u, _u, _u]),
+    "hmj_gen_uniform_domain_u64_device": (_i, [_vp, _vp, _u, _u, _u, _u, _u]),
+}
+
 _LIB = None
 
 
@@ -446,140 +525,13 @@ def load_library():
     if not os.path.exists(path):
         raise HmjError(-100, "HIP extension not built: %s is missing (run `make` at the repo root)" % path)
     L = C.CDLL(path)
-    u, i, vp, cp = C.c_uint64, C.c_int, C.c_void_p, C.c_char_p
-    L.hmj_create.restype = i
-    L.hmj_create.argtypes = [C.POINTER(vp), i]
-    L.hmj_destroy.restype = None
-    L.hmj_destroy.argtypes = [vp]
-    L.hmj_set_stream.restype = i
-    L.hmj_set_stream.argtypes = [vp, vp]
-    L.hmj_reserve.restype = i
-    L.hmj_reserve.argtypes = [vp, u, u, u, C.c_uint32]
-    L.hmj_set_radix_bits.restype = i
-    L.hmj_set_radix_bits.argtypes = [vp, i]
-    L.hmj_autotune_radix_bits.restype = i
-    L.hmj_autotune_radix_bits.argtypes = [vp, u, u, i, C.POINTER(C.c_int), C.POINTER(C.c_double)]
-    L.hmj_set_key_prefix_bits.restype = i
-    L.hmj_set_key_prefix_bits.argtypes = [vp, i]
-    L.hmj_plan.restype = i
-    L.hmj_plan.argtypes = [u, C.POINTER(i), C.POINTER(i), C.POINTER(i * 4)]
-    L.hmj_set_profiling.restype = i
-    L.hmj_set_profiling.argtypes = [vp, i]
-    L.hmj_last_timing.restype = i
-    L.hmj_last_timing.argtypes = [vp, C.POINTER(Timing)]
-    L.hmj_last_plan.restype = i
-    L.hmj_last_plan.argtypes = [vp, C.POINTER(PlanDesc)]
-    L.hmj_forget_workloads.restype = i
-    L.hmj_forget_workloads.argtypes = [vp]
-    L.hmj_placement_info.restype = i
-    L.hmj_placement_info.argtypes = [vp, C.POINTER(PlaceInfo), i]
-    L.hmj_strerror.restype = cp
-    L.hmj_strerror.argtypes = [i]
-    L.hmj_last_error.restype = cp
-    L.hmj_last_error.argtypes = [vp]
-    L.hmj_version.restype = cp
-    L.hmj_version.argtypes = []
-    L.hmj_abi_version.restype = i
-    L.hmj_abi_version.argtypes = []
-    L.hmj_join_u64_device.restype = i
-    L.hmj_join_u64_device.argtypes = [vp, vp, u, vp, u, C.c_uint32, C.POINTER(JoinResult)]
-    L.hmj_join_kind_u64_device.restype = i
-    L.hmj_join_kind_u64_device.argtypes = [vp, vp, u, vp, u, C.c_uint32, C.POINTER(JoinOpts), C.POINTER(JoinResult)]
-    L.hmj_join_build_kind_u64_device.restype = i
-    L.hmj_join_build_kind_u64_device.argtypes = [vp, vp, u, vp, u, C.c_uint32, C.POINTER(BuildJoinOpts), C.POINTER(JoinResult)]
-    L.hmj_hash_str_device.restype = i
-    L.hmj_hash_str_device.argtypes = [vp, vp, vp, u, C.c_uint32, vp]
-    L.hmj_join_str_device.restype = i
-    L.hmj_join_str_device.argtypes = [vp, C.POINTER(StrRel), C.POINTER(StrRel), C.c_uint32, C.POINTER(StrJoinOpts),
-                                      C.POINTER(StrResult)]
-    L.hmj_join_kind_str_device.restype = i
-    L.hmj_join_kind_str_device.argtypes = [vp, C.POINTER(StrRel), C.POINTER(StrRel), C.c_uint32, C.POINTER(StrKindOpts),
-                                           C.POINTER(StrResult)]
-    L.hmj_join_cols_device.restype = i
-    L.hmj_join_cols_device.argtypes = [vp, C.POINTER(ColsRel), C.POINTER(ColsRel), C.c_uint32, C.POINTER(ColsJoinOpts),
-                                       C.POINTER(ColsResult)]
-    L.hmj_join_kind_cols_device.restype = i
-    L.hmj_join_kind_cols_device.argtypes = [vp, C.POINTER(ColsRel), C.POINTER(ColsRel), C.c_uint32, C.POINTER(ColsKindOpts),
-                                            C.POINTER(ColsResult)]
-    L.hmj_join_mixed_device.restype = i
-    L.hmj_join_mixed_device.argtypes = [vp, C.POINTER(MixedRel), C.POINTER(MixedRel), C.c_uint32, C.POINTER(MixedOpts),
-                                        C.POINTER(ColsResult)]
-    L.hmj_group_cols_device.restype = i
-    L.hmj_group_cols_device.argtypes = [vp, C.POINTER(ColsRel), C.c_uint32, C.POINTER(GroupOpts), C.POINTER(GroupResult)]
-    L.hmj_group_mixed_device.restype = i
-    L.hmj_group_mixed_device.argtypes = [vp, C.POINTER(MixedRel), C.c_uint32, C.POINTER(GroupOpts), C.POINTER(GroupResult)]
-    L.hmj_group_agg_device.restype = i
-    L.hmj_group_agg_device.argtypes = [vp, C.POINTER(AggSrc), C.c_uint32, u, C.POINTER(AggDst), C.POINTER(GroupAggOpts)]
-    L.hmj_order_by_device.restype = i
-    L.hmj_order_by_device.argtypes = [vp, C.POINTER(OrderCol), C.c_uint32, u, vp, C.POINTER(OrderOpts)]
-    L.hmj_filter_device.restype = i
-    L.hmj_filter_device.argtypes = [vp, C.POINTER(FilterTerm), C.c_uint32, u, vp, vp, C.POINTER(FilterOpts)]
-    L.hmj_take_cols_device.restype = i
-    L.hmj_take_cols_device.argtypes = [vp, C.POINTER(TakeSrc), C.c_uint32, u, vp, u, C.POINTER(TakeDst), C.POINTER(TakeOpts)]
-    L.hmj_take_str_device.restype = i
-    L.hmj_take_str_device.argtypes = [vp, C.POINTER(TakeStrSrc), u, vp, u, C.POINTER(TakeStrDst), C.POINTER(TakeStrOpts)]
-    L.hmj_prepare_build_u64_device.restype = i
-    L.hmj_prepare_build_u64_device.argtypes = [vp, vp, u, u]
-    L.hmj_join_u64.restype = i
-    L.hmj_join_u64.argtypes = [vp, vp, u, vp, u, C.c_uint32, C.POINTER(JoinResult)]
-    L.hmj_join_u64_rows.restype = i
-    L.hmj_join_u64_rows.argtypes = [vp, vp, u, vp, u, C.c_uint32, C.POINTER(JoinResult), C.POINTER(vp)]
-    L.hmj_rows_free.restype = None
-    L.hmj_rows_free.argtypes = [vp]
-    L.hmj_host_pool_trim.restype = u
-    L.hmj_host_pool_trim.argtypes = [u]
-    L.hmj_host_pool_bytes.restype = u
-    L.hmj_host_pool_bytes.argtypes = []
-    L.hmj_set_host_threads.restype = i
-    L.hmj_set_host_threads.argtypes = [vp, i]
-    L.hmj_release_result.restype = None
-    L.hmj_release_result.argtypes = [vp]
-    L.hmj_comm_unique_id.restype = i
-    L.hmj_comm_unique_id.argtypes = [vp]
-    L.hmj_comm_init_rank.restype = i
-    L.hmj_comm_init_rank.argtypes = [vp, i, i, vp]
-    L.hmj_comm_set_transport.restype = i
-    L.hmj_comm_set_transport.argtypes = [vp, C.POINTER(Transport)]
-    L.hmj_comm_destroy.restype = i
-    L.hmj_comm_destroy.argtypes = [vp]
-    L.hmj_comm_set_message_bytes.restype = i
-    L.hmj_comm_set_message_bytes.argtypes = [vp, u, u]
-    L.hmj_exchange_join_u64_device.restype = i
-    L.hmj_exchange_join_u64_device.argtypes = [vp, vp, u, vp, u, C.c_uint32, C.POINTER(JoinResult), C.POINTER(JoinResult)]
-    L.hmj_exchange_join_kind_u64_device.restype = i
-    L.hmj_exchange_join_kind_u64_device.argtypes = [vp, vp, u, vp, u, C.c_uint32, C.POINTER(ExchangeKindOpts), C.POINTER(JoinResult),
-                                                    C.POINTER(JoinResult)]
-    L.hmj_owner_split_u64_device.restype = i
-    L.hmj_owner_split_u64_device.argtypes = [vp, vp, u, i, _U64P, vp, vp]
-    L.hmj_last_exchange_info.restype = i
-    L.hmj_last_exchange_info.argtypes = [vp, C.POINTER(ExchangeInfo)]
-    L.hmj_comm_set_timeout_ms.restype = i
-    L.hmj_comm_set_timeout_ms.argtypes = [vp, u]
-    L.hmj_comm_get_timeout_ms.restype = i
-    L.hmj_comm_get_timeout_ms.argtypes = [vp, _U64P]
-    L.hmj_comm_set_owner_path.restype = i
-    L.hmj_comm_set_owner_path.argtypes = [vp, i]
-    L.hmj_comm_set_self_exchange.restype = i
-    L.hmj_comm_set_self_exchange.argtypes = [vp, i]
-    L.hmj_exchange_digit_plan.restype = i
-    L.hmj_exchange_digit_plan.argtypes = [i, _U64P, u, C.c_uint32, C.POINTER(DigitPlan)]
-    L.hmj_exchange_digit_layout.restype = i
-    L.hmj_exchange_digit_layout.argtypes = [i, i, C.POINTER(DigitPlan), _U64P, _U64P, _U64P, _U64P, _U64P, _U64P]
-    L.hmj_exchange_rounds.restype = C.c_uint32
-    L.hmj_exchange_rounds.argtypes = [i, _U64P, u]
-    L.hmj_exchange_layout.restype = i
-    L.hmj_exchange_layout.argtypes = [i, i, _U64P, C.c_uint32, i, _U64P, _U64P, _U64P, _U64P, _U64P]
-    L.hmj_partition_u64_device.restype = i
-    L.hmj_partition_u64_device.argtypes = [vp, vp, u, i, i, vp, vp]
-    L.hmj_sort_u64_device.restype = i
-    L.hmj_sort_u64_device.argtypes = [vp, vp, u, vp]
-    L.hmj_gen_build_u64_device.restype = i
-    L.hmj_gen_build_u64_device.argtypes = [vp, vp, u, u, u]
-    L.hmj_gen_probe_u64_device.restype = i
-    L.hmj_gen_probe_u64_device.argtypes = [vp, vp, u, u, u, u, u]
-    L.hmj_gen_from_cdf_u64_device.restype = i
-    L.hmj_gen_from_cdf_u64_device.argtypes = [vp, vp, u, u, vp, u, u, u]
-    L.hmj_gen_uniform_domain_u64_device.restype = i
-    L.hmj_gen_uniform_domain_u64_device.argtypes = [vp, vp, u, u, u, u, u]
+    for name, (restype, argtypes) in _SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _LIB = L
     return L
+
+
+__all__ = sorted(k for k, v in list(globals().items())
+                 if k.startswith("HMJ_") or (isinstance(v, type) and issubclass(v, C.Structure)))
+__all__ += ["HmjError", "lib_path", "load_library"]

@@ -1,17 +1,24 @@
-"""Host-side mirror of the reference's join operator over the C ABI.
+"""The binding proper: `Executor`, one hmj_ctx (one per GPU / per process) with a method per entry of include/hmj.h, and
+`HashMergeJoin`, the mirror of the reference's operator HashMergeJoin<RIter,SIter> (reference hashjoin.h:33-199):
+construct from two relations, iterate (key, rval, sval) in ascending-key order, `clear()`.
 
-`Executor` owns one hmj_ctx (one per GPU / per process).  `HashMergeJoin` mirrors
-HashMergeJoin<RIter,SIter> (reference hashjoin.h:33-199): construct from two relations, iterate
-(key, rval, sval) in ascending-key order, `clear()`.  torch is used only to hold device memory
-and to name the current stream.
+The u64 entries (join_device, exchange_join, sort_device, the generators) call ctypes directly.  The column entries --
+the string, multi-column and mixed-key joins, the groupings and their aggregates, ORDER BY, WHERE and the takes -- marshal
+their arguments through `_marshal`.  `pack_strings` / `unpack_strings` / `pack_validity` / `unpack_validity` are the
+input and output formats of those entries; the host restatements the tests compare them with live in `reference` and
+are re-exported here.  torch is used only to hold device memory and to name the current stream.
 """
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
-from ._lib import (HMJ_CHECKSUM, HMJ_FIRST_WINS, HMJ_MATERIALIZE, HMJ_ORDERED, HMJ_SUM_PROBE,
+from . import _marshal as M
+from ._lib import (HMJ_CHECKSUM, HMJ_FIRST_WINS, HMJ_MATERIALIZE, HMJ_ORDERED, HMJ_SUM_PROBE,  # noqa: F401
                    HmjError, JoinResult, Timing)
+from ._marshal import _memcpy_d2d  # noqa: F401  (bench.py, tools/ and tests import it from here)
+from .reference import (cols_key64, expected_filter, expected_group_aggs, expected_groups,  # noqa: F401
+                        expected_mixed_groups, expected_order_by, mixed_key64, order_stream_bytes)
 
 SEED_B = 0x243F6A8885A308D3
 
@@ -37,6 +44,24 @@ def _dev_ptr(t):
     return t.data_ptr(), t.shape[0]
 
 
+def _dev_ptrs(build, probe):
+    """The (build, n_build, probe, n_probe) arguments of a u64 entry."""
+    bp, nb = _dev_ptr(build)
+    pp, np_ = _dev_ptr(probe)
+    return C.c_void_p(bp), nb, C.c_void_p(pp), np_
+
+
+def _valid_at(entry, at):
+    """The optional (valid[, bit_offset]) tail of an aggregate or an ORDER BY column -> what `_marshal.validity` takes."""
+    if len(entry) <= at or entry[at] is None:
+        return None
+    return entry[at], (entry[at + 1] if len(entry) > at + 1 else 0)
+
+
+_KIND_COUNTERS = ("n_build_matched", "n_build_unmatched", "n_probe_matched", "n_probe_unmatched")
+_JOIN_COLUMNS = ("key64", "r_row", "s_row", "rval", "sval")  # of hmj_cols_result; hmj_str_result: hash first
+
+
 class Executor:
     """One hmj_ctx.  All methods raise HmjError on a nonzero status."""
 
@@ -48,6 +73,7 @@ class Executor:
         if device is None:
             device = torch.cuda.current_device()
         self.device = int(device)
+        self._dev = torch.device("cuda", self.device)  # (what the column entries allocate on: no "cuda:N" to parse per call)
         h = C.c_void_p()
         rc = self.L.hmj_create(C.byref(h), self.device)
         if rc:
@@ -77,6 +103,10 @@ class Executor:
         if self.use_torch_stream:
             s = self._torch.cuda.current_stream(self.device).cuda_stream
             self._check(self.L.hmj_set_stream(self.h, C.c_void_p(s)))
+
+    def _rows(self, res, names, absent=None):
+        """The device columns `names` of a join result -> an [n_matches, len(names)] uint64 array."""
+        return M.read_columns(self._torch, self.device, [getattr(res, k) for k in names], int(res.n_matches), absent)
 
     # ---- configuration -----------------------------------------------------------------------
     def reserve(self, n_build, n_probe, max_matches=0, flags=0):
@@ -130,10 +160,8 @@ class Executor:
         """build/probe: device tensors [n,2] {key,val}.  Returns JoinResult (columns are device
         pointers owned by the executor; see `columns`)."""
         self._sync_stream()
-        bp, nb = _dev_ptr(build)
-        pp, np_ = _dev_ptr(probe)
         res = JoinResult()
-        self._check(self.L.hmj_join_u64_device(self.h, C.c_void_p(bp), nb, C.c_void_p(pp), np_, flags, C.byref(res)))
+        self._check(self.L.hmj_join_u64_device(self.h, *_dev_ptrs(build, probe), flags, C.byref(res)))
         return res
 
     def join_kind_device(self, build, probe, kind, flags=0, outer_fill=0):
@@ -141,29 +169,14 @@ class Executor:
         {"n_probe_matched": .., "n_probe_unmatched": ..}).  SEMI / ANTI results have no rval column: read them with
         `probe_rows_to_numpy`; PROBE_OUTER rows with `columns_to_numpy`.  HMJ_JOIN_INNER is join_device (counters 0)."""
         self._sync_stream()
-        bp, nb = _dev_ptr(build)
-        pp, np_ = _dev_ptr(probe)
         res = JoinResult()
-        opts = _lib.JoinOpts()
-        opts.struct_size = C.sizeof(_lib.JoinOpts)
-        opts.kind = int(kind)
-        opts.outer_fill = int(outer_fill) & 0xFFFFFFFFFFFFFFFF
-        self._check(self.L.hmj_join_kind_u64_device(self.h, C.c_void_p(bp), nb, C.c_void_p(pp), np_, flags, C.byref(opts),
-                                                    C.byref(res)))
-        return res, {"n_probe_matched": int(opts.n_probe_matched), "n_probe_unmatched": int(opts.n_probe_unmatched)}
+        opts = M.new_opts(_lib.JoinOpts, kind=kind, outer_fill=outer_fill)
+        self._check(self.L.hmj_join_kind_u64_device(self.h, *_dev_ptrs(build, probe), flags, C.byref(opts), C.byref(res)))
+        return res, M.read_info(opts, _KIND_COUNTERS[2:])
 
     def probe_rows_to_numpy(self, res):
         """Copy a semi / anti join's device result out as an [n,2] uint64 array of (key, sval)."""
-        n = int(res.n_matches)
-        out = np.empty((n, 2), np.uint64)
-        if n == 0 or not res.key:
-            return out[:0]
-        torch = self._torch
-        tmp = torch.empty(n, dtype=torch.int64, device="cuda:%d" % self.device)
-        for c, ptr in enumerate((res.key, res.sval)):
-            _memcpy_d2d(torch, tmp, ptr, n * 8)
-            out[:, c] = tmp.cpu().numpy().view(np.uint64)
-        return out
+        return self._rows(res, ("key", "sval"))
 
     def join_build_kind_device(self, build, probe, kind, flags=0, build_fill=0, probe_fill=0):
         """Build-side semi / anti / outer join or the full outer join (hmj_join_build_kind_u64_device; kind = HMJ_BUILD_SEMI,
@@ -171,44 +184,28 @@ class Executor:
         "n_probe_matched", "n_probe_unmatched"}).  BUILD_SEMI / BUILD_ANTI results have no sval column: read them with
         `build_rows_to_numpy`; the outer kinds' rows with `columns_to_numpy`."""
         self._sync_stream()
-        bp, nb = _dev_ptr(build)
-        pp, np_ = _dev_ptr(probe)
         res = JoinResult()
-        opts = _lib.BuildJoinOpts()
-        opts.struct_size = C.sizeof(_lib.BuildJoinOpts)
-        opts.kind = int(kind)
-        opts.build_fill = int(build_fill) & 0xFFFFFFFFFFFFFFFF
-        opts.probe_fill = int(probe_fill) & 0xFFFFFFFFFFFFFFFF
-        self._check(self.L.hmj_join_build_kind_u64_device(self.h, C.c_void_p(bp), nb, C.c_void_p(pp), np_, flags,
-                                                          C.byref(opts), C.byref(res)))
-        return res, {k: int(getattr(opts, k)) for k in ("n_build_matched", "n_build_unmatched", "n_probe_matched",
-                                                         "n_probe_unmatched")}
+        opts = M.new_opts(_lib.BuildJoinOpts, kind=kind, build_fill=build_fill, probe_fill=probe_fill)
+        self._check(self.L.hmj_join_build_kind_u64_device(self.h, *_dev_ptrs(build, probe), flags, C.byref(opts),
+                                                          C.byref(res)))
+        return res, M.read_info(opts, _KIND_COUNTERS)
 
     def build_rows_to_numpy(self, res):
         """Copy a build semi / anti join's device result out as an [n,2] uint64 array of (key, rval)."""
-        n = int(res.n_matches)
-        out = np.empty((n, 2), np.uint64)
-        if n == 0 or not res.key:
-            return out[:0]
-        torch = self._torch
-        tmp = torch.empty(n, dtype=torch.int64, device="cuda:%d" % self.device)
-        for c, ptr in enumerate((res.key, res.rval)):
-            _memcpy_d2d(torch, tmp, ptr, n * 8)
-            out[:, c] = tmp.cpu().numpy().view(np.uint64)
-        return out
+        return self._rows(res, ("key", "rval"))
 
     # ---- string keys (hmj_hash_str_device / hmj_join_str_device) ------------------------------------
     def _str_rel(self, rel):
         """(chars uint8, offsets int64 [n + 1], vals int64 [n]) device tensors -> StrRel (chars may be None or empty when
         every key is empty)."""
         chars, offsets, vals = rel
-        _check_col(offsets, "offsets")
-        _check_col(vals, "vals")
+        M.check_col64(offsets, "offsets")
+        M.check_col64(vals, "vals")
         n = vals.shape[0]
         if offsets.shape[0] != n + 1:
             raise ValueError("offsets must hold n + 1 entries")
         r = _lib.StrRel()
-        r.chars = _chars_ptr(chars)
+        r.chars = M.chars_ptr(chars)
         r.offsets = offsets.data_ptr() if n else None
         r.vals = vals.data_ptr() if n else None
         r.n = n
@@ -218,34 +215,15 @@ class Executor:
         """std::hash<std::string> of every key (libstdc++'s _Hash_bytes), computed on the device: int64 tensor [n]
         (read as uint64).  hash_bits 1..63 keeps the top bits only (h >> (64 - hash_bits))."""
         torch = self._torch
-        _check_col(offsets, "offsets")
+        M.check_col64(offsets, "offsets")
         if offsets.shape[0] < 1:
             raise ValueError("offsets must hold n + 1 entries")
         self._sync_stream()
         n = offsets.shape[0] - 1
         out = torch.empty(n, dtype=torch.int64, device=offsets.device)
-        self._check(self.L.hmj_hash_str_device(self.h, _chars_ptr(chars), C.c_void_p(offsets.data_ptr()), max(n, 0),
+        self._check(self.L.hmj_hash_str_device(self.h, M.chars_ptr(chars), C.c_void_p(offsets.data_ptr()), max(n, 0),
                                                int(hash_bits), C.c_void_p(out.data_ptr()) if n > 0 else None))
         return out
-
-    def _str_validity(self, valid, n, name, dst):
-        """A string relation's validity bitmap -> the Validity `dst` embedded in hmj_str_kind_opts; returns what must stay
-        alive for the call.  valid: None (no bitmap on this side), a uint8 device tensor (an Arrow bitmap, LSB first), or
-        (tensor, bit_offset)."""
-        if valid is None:
-            return None
-        t, off = valid if isinstance(valid, tuple) else (valid, 0)
-        off = int(off)
-        if not t.is_cuda or not t.is_contiguous() or t.dim() != 1 or t.element_size() != 1:
-            raise ValueError("%s must be a contiguous 1-D uint8 device tensor" % name)
-        if off < 0:
-            raise ValueError("%s: bit_offset must not be negative" % name)
-        if t.shape[0] and off + n < (1 << 64) and t.shape[0] * 8 < off + n:  # (an overflowing offset is the library's to reject)
-            raise ValueError("%s holds fewer than bit_offset + n bits" % name)
-        # (an empty tensor: bits == NULL, no NULL on this side; n == 0: the pointer is still passed, nothing reads it)
-        dst.bits = t.data_ptr() if t.shape[0] else None
-        dst.bit_offset = off & 0xFFFFFFFFFFFFFFFF
-        return t
 
     def join_str_device(self, build, probe, flags=0, hash_bits=0, build_valid=None, probe_valid=None):
         """Inner join of two string-keyed device relations (hmj_join_str_device).  build / probe: (chars uint8, offsets
@@ -262,28 +240,39 @@ class Executor:
             return res, {k: info[k] for k in keys}
         self._sync_stream()
         rb, rp = self._str_rel(build), self._str_rel(probe)
-        opts = _lib.StrJoinOpts()
-        opts.struct_size = C.sizeof(_lib.StrJoinOpts)
-        opts.hash_bits = int(hash_bits)
+        opts = M.new_opts(_lib.StrJoinOpts, hash_bits=hash_bits)
         res = _lib.StrResult()
         self._check(self.L.hmj_join_str_device(self.h, C.byref(rb), C.byref(rp), flags, C.byref(opts), C.byref(res)))
-        info = {"n_hash_pairs": int(opts.n_hash_pairs), "n_collisions": int(opts.n_collisions), "n_build_null": 0, "n_probe_null": 0}
-        for k in ("ms_hash", "ms_join", "ms_verify", "ms_order"):
-            info[k] = float(getattr(opts, k))
-        return res, info
+        return res, M.read_info(opts, ("n_hash_pairs", "n_collisions"), ("ms_hash", "ms_join", "ms_verify", "ms_order"),
+                                between={"n_build_null": 0, "n_probe_null": 0})
 
     def str_rows_to_numpy(self, res):
         """Copy a string join's device result out as an [n,5] uint64 array of (hash, r_row, s_row, rval, sval)."""
-        n = int(res.n_matches)
-        out = np.empty((n, 5), np.uint64)
-        if n == 0 or not res.hash:
-            return out[:0]
-        torch = self._torch
-        tmp = torch.empty(n, dtype=torch.int64, device="cuda:%d" % self.device)
-        for c, ptr in enumerate((res.hash, res.r_row, res.s_row, res.rval, res.sval)):
-            _memcpy_d2d(torch, tmp, ptr, n * 8)
-            out[:, c] = tmp.cpu().numpy().view(np.uint64)
-        return out
+        return self._rows(res, ("hash",) + _JOIN_COLUMNS[1:])
+
+    def join_kind_str_device(self, build, probe, side, kind, flags=0, hash_bits=0, probe_fill=0, build_fill=0, build_valid=None,
+                             probe_valid=None):
+        """Semi / anti / outer joins of two string-keyed device relations (hmj_join_kind_str_device).  side / kind as for
+        hmj_exchange_kind_opts: HMJ_KIND_PROBE_SIDE with HMJ_JOIN_*, or HMJ_KIND_BUILD_SIDE with HMJ_BUILD_* / HMJ_FULL_OUTER;
+        build / probe and *_valid as for `join_str_device` (a NULL-key row has no partner: ANTI and the outer kinds of its
+        side emit it with hash 0).  Returns (StrResult, {"n_probe_matched", "n_probe_unmatched", "n_build_matched",
+        "n_build_unmatched", "n_hash_pairs", "n_collisions", "n_build_null", "n_probe_null", "ms_hash", "ms_join",
+        "ms_verify", "ms_emit", "ms_order"}); read the rows with `str_kind_rows_to_numpy`."""
+        self._sync_stream()
+        rb, rp = self._str_rel(build), self._str_rel(probe)
+        opts = M.new_opts(_lib.StrKindOpts, side=side, kind=kind, hash_bits=hash_bits, probe_fill=probe_fill, build_fill=build_fill)
+        keep = (M.validity(opts.build_validity, build_valid, int(rb.n), "build_valid", empty_is_absent=True),
+                M.validity(opts.probe_validity, probe_valid, int(rp.n), "probe_valid", empty_is_absent=True))
+        res = _lib.StrResult()
+        self._check(self.L.hmj_join_kind_str_device(self.h, C.byref(rb), C.byref(rp), flags, C.byref(opts), C.byref(res)))
+        del keep
+        return res, M.read_info(opts, ("n_hash_pairs", "n_collisions", "n_build_null", "n_probe_null"),
+                                ("ms_hash", "ms_join", "ms_verify", "ms_emit", "ms_order"))
+
+    def str_kind_rows_to_numpy(self, res):
+        """Copy a string kind join's device result out as an [n,5] uint64 array of (hash, r_row, s_row, rval, sval); a
+        column the kind does not produce reads as HMJ_STR_NO_ROW (row columns) or 0 (value columns)."""
+        return self._rows(res, ("hash",) + _JOIN_COLUMNS[1:], absent=(0, _lib.HMJ_STR_NO_ROW, _lib.HMJ_STR_NO_ROW, 0, 0))
 
     # ---- multi-column fixed-width keys (hmj_join_cols_device) ------------------------------------------
     def _cols_rel(self, cols, vals):
@@ -292,13 +281,12 @@ class Executor:
         the library."""
         cols = list(cols)
         for k, t in enumerate(cols):
-            if not t.is_cuda or not t.is_contiguous() or t.dim() != 1:
-                raise ValueError("key column %d must be a contiguous 1-D device tensor" % k)
+            M.check_column(t, "key column %d must be a contiguous 1-D device tensor", k)
         n = cols[0].shape[0] if cols else (vals.shape[0] if vals is not None else 0)
         if any(t.shape[0] != n for t in cols):
             raise ValueError("key columns must have one length")
         if vals is not None:
-            _check_col(vals, "vals")
+            M.check_col64(vals, "vals")
             if vals.shape[0] != n:
                 raise ValueError("vals must hold one payload per row")
         arr = (_lib.KeyCol * max(len(cols), 1))()
@@ -321,25 +309,8 @@ class Executor:
         valid = list(valid)
         if len(valid) != rel.n_cols:
             raise ValueError("%s: one entry per key column" % name)
-        n = int(rel.n)
         arr = (_lib.Validity * max(len(valid), 1))()
-        keep = [arr]
-        for k, v in enumerate(valid):
-            if v is None:
-                continue
-            t, off = v if isinstance(v, tuple) else (v, 0)
-            off = int(off)
-            if not t.is_cuda or not t.is_contiguous() or t.dim() != 1 or t.element_size() != 1:
-                raise ValueError("%s[%d] must be a contiguous 1-D uint8 device tensor" % (name, k))
-            if off < 0:
-                raise ValueError("%s[%d]: bit_offset must not be negative" % (name, k))
-            if off + n < (1 << 64) and t.shape[0] * 8 < off + n:  # (an overflowing offset is the library's to reject)
-                raise ValueError("%s[%d] holds fewer than bit_offset + n bits" % (name, k))
-            # (n == 0: the pointer is still passed; nothing reads it)
-            arr[k].bits = t.data_ptr() if t.shape[0] else None
-            arr[k].bit_offset = off & 0xFFFFFFFFFFFFFFFF
-            keep.append(t)
-        return arr, keep
+        return arr, [arr] + [M.validity(arr[k], v, int(rel.n), "%s[%d]", name, k) for k, v in enumerate(valid)]
 
     def join_cols_device(self, build_cols, build_vals, probe_cols, probe_vals, flags=0, hash_bits=0, force_hashed=False,
                          build_valid=None, probe_valid=None):
@@ -361,31 +332,16 @@ class Executor:
         self._sync_stream()
         rb, keep_b = self._cols_rel(build_cols, build_vals)
         rp, keep_p = self._cols_rel(probe_cols, probe_vals)
-        opts = _lib.ColsJoinOpts()
-        opts.struct_size = C.sizeof(_lib.ColsJoinOpts)
-        opts.hash_bits = int(hash_bits)
-        opts.force_hashed = 1 if force_hashed else 0
+        opts = M.new_opts(_lib.ColsJoinOpts, hash_bits=hash_bits, force_hashed=bool(force_hashed))
         res = _lib.ColsResult()
         self._check(self.L.hmj_join_cols_device(self.h, C.byref(rb), C.byref(rp), flags, C.byref(opts), C.byref(res)))
         del keep_b, keep_p
-        info = {"form": int(opts.form), "n_key_pairs": int(opts.n_key_pairs), "n_collisions": int(opts.n_collisions),
-                "n_build_null": 0, "n_probe_null": 0}
-        for k in ("ms_key", "ms_join", "ms_verify", "ms_order"):
-            info[k] = float(getattr(opts, k))
-        return res, info
+        return res, M.read_info(opts, ("form", "n_key_pairs", "n_collisions"), ("ms_key", "ms_join", "ms_verify", "ms_order"),
+                                between={"n_build_null": 0, "n_probe_null": 0})
 
     def cols_rows_to_numpy(self, res):
         """Copy a multi-column join's device result out as an [n,5] uint64 array of (key64, r_row, s_row, rval, sval)."""
-        n = int(res.n_matches)
-        out = np.empty((n, 5), np.uint64)
-        if n == 0 or not res.key64:
-            return out[:0]
-        torch = self._torch
-        tmp = torch.empty(n, dtype=torch.int64, device="cuda:%d" % self.device)
-        for c, ptr in enumerate((res.key64, res.r_row, res.s_row, res.rval, res.sval)):
-            _memcpy_d2d(torch, tmp, ptr, n * 8)
-            out[:, c] = tmp.cpu().numpy().view(np.uint64)
-        return out
+        return self._rows(res, _JOIN_COLUMNS)
 
     def join_kind_cols_device(self, build_cols, build_vals, probe_cols, probe_vals, side, kind, flags=0, hash_bits=0,
                               force_hashed=False, probe_fill=0, build_fill=0, build_valid=None, probe_valid=None):
@@ -401,14 +357,8 @@ class Executor:
         self._sync_stream()
         rb, keep_b = self._cols_rel(build_cols, build_vals)
         rp, keep_p = self._cols_rel(probe_cols, probe_vals)
-        opts = _lib.ColsKindOpts()
-        opts.struct_size = C.sizeof(_lib.ColsKindOpts)
-        opts.side = int(side)
-        opts.kind = int(kind)
-        opts.hash_bits = int(hash_bits)
-        opts.force_hashed = 1 if force_hashed else 0
-        opts.probe_fill = int(probe_fill) & 0xFFFFFFFFFFFFFFFF
-        opts.build_fill = int(build_fill) & 0xFFFFFFFFFFFFFFFF
+        opts = M.new_opts(_lib.ColsKindOpts, side=side, kind=kind, hash_bits=hash_bits, force_hashed=bool(force_hashed),
+                          probe_fill=probe_fill, build_fill=build_fill)
         vb, keep_vb = self._validity(build_valid, rb, "build_valid")
         vp, keep_vp = self._validity(probe_valid, rp, "probe_valid")
         if vb is not None:
@@ -418,30 +368,14 @@ class Executor:
         res = _lib.ColsResult()
         self._check(self.L.hmj_join_kind_cols_device(self.h, C.byref(rb), C.byref(rp), flags, C.byref(opts), C.byref(res)))
         del keep_b, keep_p, keep_vb, keep_vp
-        info = opts.counts.as_dict()
-        info.update({"form": int(opts.form), "n_key_pairs": int(opts.n_key_pairs), "n_collisions": int(opts.n_collisions),
-                     "n_build_null": int(opts.n_build_null), "n_probe_null": int(opts.n_probe_null)})
-        for k in ("ms_key", "ms_join", "ms_verify", "ms_emit", "ms_order"):
-            info[k] = float(getattr(opts, k))
-        return res, info
+        return res, M.read_info(opts, ("form", "n_key_pairs", "n_collisions", "n_build_null", "n_probe_null"),
+                                ("ms_key", "ms_join", "ms_verify", "ms_emit", "ms_order"))
 
     def cols_kind_rows_to_numpy(self, res):
         """Copy a multi-column kind join's device result out as an [n,5] uint64 array of (key64, r_row, s_row, rval, sval);
         a column the kind does not produce (r_row / rval of probe SEMI / ANTI, s_row / sval of BUILD_SEMI / BUILD_ANTI)
         reads as 0."""
-        n = int(res.n_matches)
-        out = np.empty((n, 5), np.uint64)
-        if n == 0 or not res.key64:
-            return out[:0]
-        torch = self._torch
-        tmp = torch.empty(n, dtype=torch.int64, device="cuda:%d" % self.device)
-        for c, ptr in enumerate((res.key64, res.r_row, res.s_row, res.rval, res.sval)):
-            if not ptr:
-                out[:, c] = 0
-                continue
-            _memcpy_d2d(torch, tmp, ptr, n * 8)
-            out[:, c] = tmp.cpu().numpy().view(np.uint64)
-        return out
+        return self._rows(res, _JOIN_COLUMNS, absent=0)
 
     # ---- grouping rows by multi-column keys (hmj_group_cols_device) ----------------------------------------
     def group_cols_device(self, cols, vals=None, valid=None, flags=0, want=_lib.HMJ_GROUP_COUNT, hash_bits=0, force_hashed=False):
@@ -453,11 +387,7 @@ class Executor:
         `group_rows_to_numpy`, reproduce them with `expected_groups`."""
         self._sync_stream()
         rel, keep = self._cols_rel(cols, vals)
-        opts = _lib.GroupOpts()
-        opts.struct_size = C.sizeof(_lib.GroupOpts)
-        opts.want = int(want)
-        opts.hash_bits = int(hash_bits)
-        opts.force_hashed = 1 if force_hashed else 0
+        opts = M.new_opts(_lib.GroupOpts, want=want, hash_bits=hash_bits, force_hashed=bool(force_hashed))
         v, keep_v = self._validity(valid, rel, "valid")
         if v is not None:
             opts.validity = v
@@ -467,25 +397,16 @@ class Executor:
         if flags & (HMJ_MATERIALIZE | HMJ_ORDERED):
             self._group_rows, self._group_groups = int(res.n_rows), int(res.n_groups)
         del keep, keep_v
-        info = {"form": int(opts.form), "n_null": int(opts.n_null), "n_collisions": int(opts.n_collisions)}
-        for k in ("ms_key", "ms_sort", "ms_groups", "ms_agg"):
-            info[k] = float(getattr(opts, k))
-        return res, info
+        return res, M.read_info(opts, ("form", "n_null", "n_collisions"), ("ms_key", "ms_sort", "ms_groups", "ms_agg"))
 
     def group_rows_to_numpy(self, res):
         """Copy a grouping's device result out: {"key64", "first_row", "count", "sum", "min", "max", "group_of_row"} -> a
         uint64 array (n_groups entries; group_of_row: n_rows), or None for a column the call did not produce."""
-        torch = self._torch
         out = {}
         for name in ("key64", "first_row", "count", "sum", "min", "max", "group_of_row"):
             ptr = getattr(res, name)
             n = int(res.n_rows if name == "group_of_row" else res.n_groups)
-            if not ptr:
-                out[name] = None
-                continue
-            tmp = torch.empty(n, dtype=torch.int64, device="cuda:%d" % self.device)
-            _memcpy_d2d(torch, tmp, ptr, n * 8)
-            out[name] = tmp.cpu().numpy().view(np.uint64)
+            out[name] = M.read_columns(self._torch, self.device, (ptr,), n)[:, 0] if ptr else None
         return out
 
     # ---- mixed keys: string and fixed-width columns in one tuple (hmj_join_mixed_device) ------------------
@@ -498,13 +419,12 @@ class Executor:
         n = None
         for k, col in enumerate(cols):
             if isinstance(col, (tuple, list)):
-                _check_col(col[1], "%s column %d: offsets" % (name, k))
+                M.check_col64(col[1], "%s column %d: offsets", name, k)
                 if col[1].shape[0] < 1:
                     raise ValueError("%s column %d: offsets must hold n + 1 entries" % (name, k))
                 m = col[1].shape[0] - 1
             else:
-                if not col.is_cuda or not col.is_contiguous() or col.dim() != 1:
-                    raise ValueError("%s column %d must be a contiguous 1-D device tensor" % (name, k))
+                M.check_column(col, "%s column %d must be a contiguous 1-D device tensor", name, k)
                 m = col.shape[0]
             if n is None:
                 n = m
@@ -513,10 +433,11 @@ class Executor:
         if n is None:
             n = vals.shape[0] if vals is not None else 0
         if vals is not None:
-            _check_col(vals, "vals")
+            M.check_col64(vals, "vals")
             if vals.shape[0] != n:
                 raise ValueError("vals must hold one payload per row")
-        if valid is not None and len(list(valid)) != len(cols):
+        valid = [None] * len(cols) if valid is None else list(valid)
+        if len(valid) != len(cols):
             raise ValueError("%s_valid: one entry per key column" % name)
         arr = (_lib.MixedCol * max(len(cols), 1))()
         keep = [arr, cols]
@@ -524,14 +445,13 @@ class Executor:
             if isinstance(col, (tuple, list)):
                 arr[k].type = _lib.HMJ_KEY_LARGE_STRING
                 arr[k].width = 0
-                arr[k].data = _chars_ptr(col[0])
+                arr[k].data = M.chars_ptr(col[0])
                 arr[k].offsets = col[1].data_ptr()
             else:
                 arr[k].type = _lib.HMJ_KEY_FIXED
                 arr[k].width = col.element_size()
                 arr[k].data = col.data_ptr() if n else None
-            if valid is not None and list(valid)[k] is not None:
-                keep.append(self._str_validity(list(valid)[k], n, "%s_valid[%d]" % (name, k), arr[k].validity))
+            keep.append(M.validity(arr[k].validity, valid[k], n, "%s_valid[%d]", name, k, empty_is_absent=True))
         r = _lib.MixedRel()
         r.cols = arr
         r.n_cols = len(cols)
@@ -556,22 +476,12 @@ class Executor:
         self._sync_stream()
         rb, keep_b = self._mixed_rel(build_cols, build_vals, build_valid, "build")
         rp, keep_p = self._mixed_rel(probe_cols, probe_vals, probe_valid, "probe")
-        opts = _lib.MixedOpts()
-        opts.struct_size = C.sizeof(_lib.MixedOpts)
-        opts.side = int(side)
-        opts.kind = int(kind)
-        opts.hash_bits = int(hash_bits)
-        opts.probe_fill = int(probe_fill) & 0xFFFFFFFFFFFFFFFF
-        opts.build_fill = int(build_fill) & 0xFFFFFFFFFFFFFFFF
+        opts = M.new_opts(_lib.MixedOpts, side=side, kind=kind, hash_bits=hash_bits, probe_fill=probe_fill, build_fill=build_fill)
         res = _lib.ColsResult()
         self._check(self.L.hmj_join_mixed_device(self.h, C.byref(rb), C.byref(rp), flags, C.byref(opts), C.byref(res)))
         del keep_b, keep_p
-        info = opts.counts.as_dict()
-        info.update({"n_key_pairs": int(opts.n_key_pairs), "n_collisions": int(opts.n_collisions),
-                     "n_build_null": int(opts.n_build_null), "n_probe_null": int(opts.n_probe_null)})
-        for k in ("ms_key", "ms_join", "ms_verify", "ms_emit", "ms_order"):
-            info[k] = float(getattr(opts, k))
-        return res, info
+        return res, M.read_info(opts, ("n_key_pairs", "n_collisions", "n_build_null", "n_probe_null"),
+                                ("ms_key", "ms_join", "ms_verify", "ms_emit", "ms_order"))
 
     def mixed_rows_to_numpy(self, res):
         """Copy a mixed-key join's device result out as an [n,5] uint64 array of (key64, r_row, s_row, rval, sval); a column
@@ -587,29 +497,18 @@ class Executor:
         the columns with `group_rows_to_numpy`, reproduce them with `expected_mixed_groups`."""
         self._sync_stream()
         rel, keep = self._mixed_rel(cols, vals, valid, "grouped")
-        opts = _lib.GroupOpts()
-        opts.struct_size = C.sizeof(_lib.GroupOpts)
-        opts.want = int(want)
-        opts.hash_bits = int(hash_bits)
+        opts = M.new_opts(_lib.GroupOpts, want=want, hash_bits=hash_bits)
         res = _lib.GroupResult()
         self._group_rows = self._group_groups = 0  # (group_agg_device: the library drops its live grouping here)
         self._check(self.L.hmj_group_mixed_device(self.h, C.byref(rel), flags, C.byref(opts), C.byref(res)))
         if flags & (HMJ_MATERIALIZE | HMJ_ORDERED):
             self._group_rows, self._group_groups = int(res.n_rows), int(res.n_groups)
         del keep
-        info = {"form": int(opts.form), "n_null": int(opts.n_null), "n_collisions": int(opts.n_collisions)}
-        for k in ("ms_key", "ms_sort", "ms_groups", "ms_agg"):
-            info[k] = float(getattr(opts, k))
-        return res, info
+        return res, M.read_info(opts, ("form", "n_null", "n_collisions"), ("ms_key", "ms_sort", "ms_groups", "ms_agg"))
 
     # ---- typed columns aggregated over the live grouping (hmj_group_agg_device) ----------------------------
     def _agg_type(self, t):
-        torch = self._torch
-        names = ("int8", "int16", "int32", "int64", "uint8", "uint16", "uint32", "uint64", "float32", "float64")
-        for code, name in enumerate(names):
-            if getattr(torch, name, None) is t.dtype:
-                return code
-        raise ValueError("no HMJ_TYPE_* for %s" % (t.dtype,))
+        return M.type_code(t.dtype)
 
     def group_agg_device(self, aggs, want_validity=True, n_rows=None):
         """Aggregate typed value columns over the executor's live grouping (hmj_group_agg_device): the last successful
@@ -625,41 +524,30 @@ class Executor:
         torch = self._torch
         self._sync_stream()
         aggs = [tuple(a) for a in aggs]
-        wants = [bool(want_validity)] * len(aggs) if isinstance(want_validity, (bool, int)) else [bool(w) for w in want_validity]
-        if len(wants) != len(aggs):
-            raise ValueError("want_validity: one entry per aggregate")
+        wants = M.want_flags(want_validity, len(aggs), "aggregate")
         if n_rows is None:
             lens = [a[1].shape[0] for a in aggs if a[1] is not None]
             n_rows = lens[0] if lens else getattr(self, "_group_rows", 0)
         n_rows = int(n_rows)
         # the groups size the outputs: an HMJ_E_ARG call must still reach the library, so any count will do for it
         n_groups = int(getattr(self, "_group_groups", 0))
-        dev = "cuda:%d" % self.device
+        dev = self._dev
         src = (_lib.AggSrc * max(len(aggs), 1))()
         dst = (_lib.AggDst * max(len(aggs), 1))()
         outs, words, keep = [], [], []
         f64, i64 = torch.float64, torch.int64
         u64 = getattr(torch, "uint64", i64)
         for k, a in enumerate(aggs):
-            op, t, v = int(a[0]), a[1], a[2] if len(a) > 2 else None
-            off = int(a[3]) if len(a) > 3 else 0
+            op, t = int(a[0]), a[1]
             code = _lib.HMJ_TYPE_U64
             if t is not None:
-                if not t.is_cuda or not t.is_contiguous() or t.dim() != 1:
-                    raise ValueError("aggregate %d: the column must be a contiguous 1-D device tensor" % k)
-                code = self._agg_type(t)
+                M.check_column(t, "aggregate %d: the column must be a contiguous 1-D device tensor", k)
+                code = M.type_code(t.dtype)
                 src[k].data = t.data_ptr() if t.shape[0] else None
                 keep.append(t)
             src[k].type = code
             src[k].op = op & 0xFFFFFFFF
-            if v is not None:
-                if not v.is_cuda or not v.is_contiguous() or v.dim() != 1:
-                    raise ValueError("aggregate %d: valid must be a contiguous 1-D device tensor" % k)
-                if off < 0:
-                    raise ValueError("aggregate %d: bit_offset must not be negative" % k)
-                src[k].validity.bits = v.data_ptr() if v.shape[0] else None
-                src[k].validity.bit_offset = off & 0xFFFFFFFFFFFFFFFF
-                keep.append(v)
+            keep.append(M.validity(src[k].validity, _valid_at(a, 2), n_rows, "aggregate %d", k, any_width=True))
             if op == _lib.HMJ_AGG_COUNT:
                 dt = u64
             elif op == _lib.HMJ_AGG_MEAN:
@@ -674,15 +562,14 @@ class Executor:
             dst[k].validity = w.data_ptr() if (w is not None and n_groups) else None
             outs.append(o)
             words.append(w)
-        opts = _lib.GroupAggOpts()
-        opts.struct_size = C.sizeof(_lib.GroupAggOpts)
+        opts = M.new_opts(_lib.GroupAggOpts)
         self._check(self.L.hmj_group_agg_device(self.h, src, len(aggs), n_rows, dst, C.byref(opts)))
         del keep
         if int(opts.n_groups) != n_groups:
             raise RuntimeError("the live grouping has %d groups, the executor sized the outputs for %d: group through this "
                                "executor's group_cols_device / group_mixed_device" % (int(opts.n_groups), n_groups))
-        info = {"n_groups": int(opts.n_groups), "ms_agg": float(opts.ms_agg)}
-        return [(outs[k], words[k], int(dst[k].null_count)) for k in range(len(aggs))], info
+        return ([(outs[k], words[k], int(dst[k].null_count)) for k in range(len(aggs))],
+                M.read_info(opts, ("n_groups",), ("ms_agg",)))
 
     # ---- ORDER BY: typed, string and mixed keys to a row map (hmj_order_by_device) ---------------------------
     def order_by_device(self, cols, n=None):
@@ -705,40 +592,24 @@ class Executor:
         keep = []
         for k, c in enumerate(cols):
             col, flags = c[0], int(c[1]) if len(c) > 1 else 0
-            v = c[2] if len(c) > 2 else None
-            off = int(c[3]) if len(c) > 3 else 0
             if isinstance(col, (tuple, list)):
-                chars, offsets = col
-                _check_col(offsets, "column %d: offsets" % k)
+                M.check_col64(col[1], "column %d: offsets", k)  # (an offsets tensor without entries is the library's to refuse)
                 arr[k].type = _lib.HMJ_ORDER_LARGE_STRING
-                cp = _chars_ptr(chars)
-                arr[k].data = cp.value if cp is not None else None
-                arr[k].offsets = offsets.data_ptr()
-                keep += [chars, offsets]
+                arr[k].data = M.chars_ptr(col[0])
+                arr[k].offsets = col[1].data_ptr()
+                keep += [col[0], col[1]]
             else:
-                if not col.is_cuda or not col.is_contiguous() or col.dim() != 1:
-                    raise ValueError("column %d must be a contiguous 1-D device tensor" % k)
-                arr[k].type = self._agg_type(col)
+                M.check_column(col, "column %d must be a contiguous 1-D device tensor", k)
+                arr[k].type = M.type_code(col.dtype)
                 arr[k].data = col.data_ptr() if col.shape[0] else None
                 keep.append(col)
             arr[k].flags = flags & 0xFFFFFFFF
-            if v is not None:
-                if not v.is_cuda or not v.is_contiguous() or v.dim() != 1:
-                    raise ValueError("column %d: valid must be a contiguous 1-D device tensor" % k)
-                if off < 0:
-                    raise ValueError("column %d: bit_offset must not be negative" % k)
-                arr[k].validity.bits = v.data_ptr() if v.shape[0] else None
-                arr[k].validity.bit_offset = off & 0xFFFFFFFFFFFFFFFF
-                keep.append(v)
-        out = torch.empty(n, dtype=torch.int64, device="cuda:%d" % self.device)
-        opts = _lib.OrderOpts()
-        opts.struct_size = C.sizeof(_lib.OrderOpts)
+            keep.append(M.validity(arr[k].validity, _valid_at(c, 2), n, "column %d", k, any_width=True))
+        out = torch.empty(n, dtype=torch.int64, device=self._dev)
+        opts = M.new_opts(_lib.OrderOpts)
         self._check(self.L.hmj_order_by_device(self.h, arr, len(cols), n, out.data_ptr() if n else None, C.byref(opts)))
         del keep
-        info = {"n_distinct": int(opts.n_distinct), "n_tied_rows": int(opts.n_tied_rows), "n_rounds": int(opts.n_rounds)}
-        for k in ("ms_key", "ms_sort", "ms_refine", "ms_map"):
-            info[k] = float(getattr(opts, k))
-        return out, info
+        return out, M.read_info(opts, ("n_distinct", "n_tied_rows", "n_rounds"), ("ms_key", "ms_sort", "ms_refine", "ms_map"))
 
     # ---- WHERE: typed and string predicates to a row map (hmj_filter_device) ---------------------------------
     def filter_device(self, terms, n=None, want_mask=False, out=None):
@@ -761,7 +632,6 @@ class Executor:
         terms = [t if isinstance(t, dict) else dict(zip(keys, t)) for t in terms]
         arr = (_lib.FilterTerm * max(len(terms), 1))()
         keep = []
-        names = ("int8", "int16", "int32", "int64", "uint8", "uint16", "uint32", "uint64", "float32", "float64")
         first_n = None
         for k, t in enumerate(terms):
             col, op = t["column"], int(t["op"])
@@ -769,28 +639,16 @@ class Executor:
             lits = [] if lit is None else (list(lit) if isinstance(lit, (tuple, list)) else [lit])
             if len(lits) > 2:
                 raise ValueError("term %d: at most two literals" % k)
-            rm = t.get("row_map")
-            if rm is None:
-                map_n = None
-            elif isinstance(rm, tuple):
-                arr[k].row_map, map_n = int(rm[0] or 0) or None, int(rm[1])
-            else:
-                if not rm.is_cuda or not rm.is_contiguous() or rm.dim() != 1 or rm.dtype != torch.int64:
-                    raise ValueError("term %d: row_map must be a contiguous 1-D int64 device tensor" % k)
-                arr[k].row_map, map_n = (rm.data_ptr() if rm.shape[0] else None), rm.shape[0]
+            map_n = None
+            if t.get("row_map") is not None:
+                arr[k].row_map, map_n, rm = M.row_map(t["row_map"], torch.int64,
+                                                      "term %d: row_map must be a contiguous 1-D int64 device tensor", k)
                 keep.append(rm)
             if isinstance(col, (tuple, list)):
-                chars, offsets = col
-                _check_col(offsets, "term %d: offsets" % k)
-                if offsets.shape[0] < 1:
-                    raise ValueError("term %d: offsets must hold n + 1 entries" % k)
                 arr[k].type = _lib.HMJ_FILTER_LARGE_STRING
-                cp = _chars_ptr(chars)
-                arr[k].data = cp.value if cp is not None else None
-                arr[k].chars_bytes = chars.numel() if cp is not None else 0
-                arr[k].offsets = offsets.data_ptr()
-                n_src = offsets.shape[0] - 1
-                keep += [chars, offsets]
+                arr[k].data, arr[k].chars_bytes, arr[k].offsets = M.str_column(col[0], col[1], "term %d: offsets", k)
+                n_src = col[1].shape[0] - 1
+                keep += [col[0], col[1]]
                 for j, v in enumerate(lits):
                     b = v.encode("utf-8") if isinstance(v, str) else bytes(v)
                     buf = C.create_string_buffer(b, max(len(b), 1))
@@ -798,45 +656,35 @@ class Executor:
                     arr[k].str_len[j] = len(b)
                     keep.append(buf)
             else:
-                if not col.is_cuda or not col.is_contiguous() or col.dim() != 1:
-                    raise ValueError("term %d: the column must be a contiguous 1-D device tensor" % k)
-                code = self._agg_type(col)
+                M.check_column(col, "term %d: the column must be a contiguous 1-D device tensor", k)
+                code = M.type_code(col.dtype)
                 arr[k].type = code
                 arr[k].data = col.data_ptr() if col.shape[0] else None
                 n_src = col.shape[0]
                 keep.append(col)
-                dt = np.dtype(names[code])
+                dt = np.dtype(M.TYPE_NAMES[code])
                 for j, v in enumerate(lits):
                     arr[k].lit[j] = int(np.array([v], dtype=dt).view("u%d" % dt.itemsize)[0])
             arr[k].n_src = n_src
             arr[k].op = op & 0xFFFFFFFF
             arr[k].flags = _lib.HMJ_FILTER_NOT if t.get("negate") else 0
             arr[k].clause = int(t.get("clause") or 0)
-            v, off = t.get("valid"), int(t.get("bit_offset") or 0)
-            if v is not None:
-                if not v.is_cuda or not v.is_contiguous() or v.dim() != 1:
-                    raise ValueError("term %d: valid must be a contiguous 1-D device tensor" % k)
-                if off < 0:
-                    raise ValueError("term %d: bit_offset must not be negative" % k)
-                arr[k].validity.bits = v.data_ptr() if v.shape[0] else None
-                arr[k].validity.bit_offset = off & 0xFFFFFFFFFFFFFFFF
-                keep.append(v)
+            if t.get("valid") is not None:
+                keep.append(M.validity(arr[k].validity, (t["valid"], t.get("bit_offset") or 0), n_src, "term %d", k, any_width=True))
             if first_n is None:
                 first_n = n_src if map_n is None else map_n
         n = int((first_n or 0) if n is None else n)
-        dev = "cuda:%d" % self.device
+        dev = self._dev
         if out is None:
             out = torch.empty(n, dtype=torch.int64, device=dev)
         elif not out.is_cuda or not out.is_contiguous() or out.dim() != 1 or out.dtype != torch.int64 or out.shape[0] < n:
             raise ValueError("out must be a contiguous 1-D int64 device tensor of at least n entries")
         words = torch.empty((n + 63) // 64, dtype=torch.int64, device=dev) if want_mask else None
-        opts = _lib.FilterOpts()
-        opts.struct_size = C.sizeof(_lib.FilterOpts)
+        opts = M.new_opts(_lib.FilterOpts)
         self._check(self.L.hmj_filter_device(self.h, arr, len(terms), n, out.data_ptr() if n else None,
                                              words.data_ptr() if (words is not None and n) else None, C.byref(opts)))
         del keep
-        info = {"n_out": int(opts.n_out), "n_unknown": int(opts.n_unknown), "ms_eval": float(opts.ms_eval),
-                "ms_write": float(opts.ms_write)}
+        info = M.read_info(opts, ("n_out", "n_unknown"), ("ms_eval", "ms_write"))
         return out[:info["n_out"]], words, info
 
     # ---- columns through a row map (hmj_take_cols_device) ------------------------------------------------
@@ -854,12 +702,7 @@ class Executor:
         torch = self._torch
         self._sync_stream()
         cols = list(cols)
-        if isinstance(row_map, tuple):
-            map_ptr, map_n = int(row_map[0] or 0), int(row_map[1])
-        else:
-            if not row_map.is_cuda or not row_map.is_contiguous() or row_map.dim() != 1 or row_map.dtype != torch.int64:
-                raise ValueError("row_map must be a contiguous 1-D int64 device tensor")
-            map_ptr, map_n = (row_map.data_ptr() if row_map.shape[0] else 0), row_map.shape[0]
+        map_ptr, map_n, keep_map = M.row_map(row_map, torch.int64, "row_map must be a contiguous 1-D int64 device tensor")
         n_out = map_n if n_out is None else int(n_out)
         if not 0 <= n_out <= map_n:
             raise ValueError("n_out must be in 0..len(row_map)")
@@ -872,43 +715,29 @@ class Executor:
         n_src = cols[0].shape[0] if cols else 0
         if any(t.shape[0] != n_src for t in cols):
             raise ValueError("columns must have one length")
-        if valid is not None and len(list(valid)) != len(cols):
+        valid = [None] * len(cols) if valid is None else list(valid)
+        if len(valid) != len(cols):
             raise ValueError("valid: one entry per column")
-        wants = [bool(want_validity)] * len(cols) if isinstance(want_validity, (bool, int)) else [bool(w) for w in want_validity]
-        if len(wants) != len(cols):
-            raise ValueError("want_validity: one entry per column")
-        dev = "cuda:%d" % self.device
+        wants = M.want_flags(want_validity, len(cols), "column")
+        dev = self._dev
         src = (_lib.TakeSrc * max(len(cols), 1))()
         dst = (_lib.TakeDst * max(len(cols), 1))()
         outs, words, keep = [], [], []
         for k, t in enumerate(cols):
             src[k].data = t.data_ptr() if n_src else None
             src[k].width = widths[k]
-            v = None if valid is None else list(valid)[k]
-            if v is not None:
-                b, off = v if isinstance(v, tuple) else (v, 0)
-                off = int(off)
-                if not b.is_cuda or not b.is_contiguous() or b.dim() != 1 or b.element_size() != 1:
-                    raise ValueError("valid[%d] must be a contiguous 1-D uint8 device tensor" % k)
-                if off < 0:
-                    raise ValueError("valid[%d]: bit_offset must not be negative" % k)
-                if off + n_src < (1 << 64) and b.shape[0] * 8 < off + n_src:  # (an overflowing offset is the library's to reject)
-                    raise ValueError("valid[%d] holds fewer than bit_offset + n bits" % k)
-                src[k].validity.bits = b.data_ptr() if b.shape[0] else None
-                src[k].validity.bit_offset = off & 0xFFFFFFFFFFFFFFFF
-                keep.append(b)
+            if valid[k] is not None:
+                keep.append(M.validity(src[k].validity, valid[k], n_src, "valid[%d]", k))
             o = torch.empty((n_out,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev)
             w = torch.empty((n_out + 63) // 64, dtype=torch.int64, device=dev) if wants[k] else None
             dst[k].data = o.data_ptr() if n_out else None
             dst[k].validity = w.data_ptr() if (w is not None and n_out) else None
             outs.append(o)
             words.append(w)
-        opts = _lib.TakeOpts()
-        opts.struct_size = C.sizeof(_lib.TakeOpts)
-        self._check(self.L.hmj_take_cols_device(self.h, src, len(cols), n_src, C.c_void_p(map_ptr or None), n_out, dst, C.byref(opts)))
-        del keep
-        info = {"null_count": [int(dst[k].null_count) for k in range(len(cols))], "n_no_row": int(opts.n_no_row),
-                "ms_take": float(opts.ms_take)}
+        opts = M.new_opts(_lib.TakeOpts)
+        self._check(self.L.hmj_take_cols_device(self.h, src, len(cols), n_src, C.c_void_p(map_ptr), n_out, dst, C.byref(opts)))
+        del keep, keep_map
+        info = M.read_info(opts, ("n_no_row",), ("ms_take",), first={"null_count": [int(dst[k].null_count) for k in range(len(cols))]})
         return outs, (words if any(wants) or not cols else None), info
 
     # ---- a string column through a row map (hmj_take_str_device) -----------------------------------------
@@ -926,36 +755,24 @@ class Executor:
         are those of the last call made.  `unpack_strings` and `unpack_validity` read the outputs."""
         torch = self._torch
         self._sync_stream()
-        if isinstance(row_map, tuple):
-            map_ptr, map_n = int(row_map[0] or 0), int(row_map[1])
-        else:
-            if not row_map.is_cuda or not row_map.is_contiguous() or row_map.dim() != 1 or row_map.dtype != torch.int64:
-                raise ValueError("row_map must be a contiguous 1-D int64 device tensor")
-            map_ptr, map_n = (row_map.data_ptr() if row_map.shape[0] else 0), row_map.shape[0]
+        map_ptr, map_n, keep_map = M.row_map(row_map, torch.int64, "row_map must be a contiguous 1-D int64 device tensor")
         n_out = map_n if n_out is None else int(n_out)
         if not 0 <= n_out <= map_n:
             raise ValueError("n_out must be in 0..len(row_map)")
-        _check_col(offsets, "offsets")
-        if offsets.shape[0] < 1:
-            raise ValueError("offsets must hold n + 1 entries")
-        n_src = offsets.shape[0] - 1
         src = _lib.TakeStrSrc()
-        cp = _chars_ptr(chars)
-        src.chars = cp.value if cp is not None else None
-        src.chars_bytes = chars.numel() if cp is not None else 0
-        src.offsets = offsets.data_ptr()
-        keep = self._str_validity(valid, n_src, "valid", src.validity)
-        dev = "cuda:%d" % self.device
+        src.chars, src.chars_bytes, src.offsets = M.str_column(chars, offsets, "offsets")
+        n_src = offsets.shape[0] - 1
+        keep = M.validity(src.validity, valid, n_src, "valid", empty_is_absent=True)
+        dev = self._dev
         off_out = torch.zeros(n_out + 1, dtype=torch.int64, device=dev)  # (n_out == 0 writes nothing: offsets[0] = 0 is ours)
         words = torch.empty((n_out + 63) // 64, dtype=torch.int64, device=dev) if want_validity else None
         dst = _lib.TakeStrDst()
         dst.offsets = off_out.data_ptr()
         dst.validity = words.data_ptr() if (words is not None and n_out) else None
-        opts = _lib.TakeStrOpts()
-        opts.struct_size = C.sizeof(_lib.TakeStrOpts)
+        opts = M.new_opts(_lib.TakeStrOpts)
 
         def call():
-            self._check(self.L.hmj_take_str_device(self.h, C.byref(src), n_src, C.c_void_p(map_ptr or None), n_out, C.byref(dst),
+            self._check(self.L.hmj_take_str_device(self.h, C.byref(src), n_src, C.c_void_p(map_ptr), n_out, C.byref(dst),
                                                    C.byref(opts)))
 
         if capacity is None:
@@ -966,10 +783,10 @@ class Executor:
         dst.chars = chars_out.data_ptr()
         dst.chars_capacity = capacity
         call()
-        del keep
+        del keep, keep_map
         total = int(dst.total_bytes)
-        info = {"null_count": int(dst.null_count), "n_no_row": int(opts.n_no_row), "total_bytes": total,
-                "ms_offsets": float(opts.ms_offsets), "ms_chars": float(opts.ms_chars)}
+        info = M.read_info(opts, ("n_no_row",), ("ms_offsets", "ms_chars"), first={"null_count": int(dst.null_count)},
+                           between={"total_bytes": total})
         return chars_out[:total], off_out, words, info
 
     def prepare_build(self, build, n_probe_hint):
@@ -990,19 +807,14 @@ class Executor:
 
     def columns_to_numpy(self, res, host):
         """Copy the result columns out as an [n,3] uint64 array of (key, rval, sval)."""
+        if not host:
+            return self._rows(res, ("key", "rval", "sval"))
         n = int(res.n_matches)
         out = np.empty((n, 3), np.uint64)
         if n == 0 or not res.key:
-            return out[:0] if not res.key else out
-        if host:
-            for c, ptr in enumerate((res.key, res.rval, res.sval)):
-                out[:, c] = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint64)), shape=(n,))
-        else:
-            torch = self._torch
-            tmp = torch.empty(n, dtype=torch.int64, device="cuda:%d" % self.device)
-            for c, ptr in enumerate((res.key, res.rval, res.sval)):
-                _memcpy_d2d(torch, tmp, ptr, n * 8)
-                out[:, c] = tmp.cpu().numpy().view(np.uint64)
+            return out[:0]
+        for c, ptr in enumerate((res.key, res.rval, res.sval)):
+            out[:, c] = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint64)), shape=(n,))
         return out
 
     def release_result(self):
@@ -1062,10 +874,8 @@ class Executor:
     def exchange_join(self, build_shard, probe_shard, flags=0):
         """Distributed join of row shards (collective).  Returns (local JoinResult, global JoinResult)."""
         self._sync_stream()
-        bp, nb = _dev_ptr(build_shard)
-        pp, np_ = _dev_ptr(probe_shard)
         loc, glob = JoinResult(), JoinResult()
-        self._check(self.L.hmj_exchange_join_u64_device(self.h, C.c_void_p(bp), nb, C.c_void_p(pp), np_, flags,
+        self._check(self.L.hmj_exchange_join_u64_device(self.h, *_dev_ptrs(build_shard, probe_shard), flags,
                                                         C.byref(loc), C.byref(glob)))
         return loc, glob
 
@@ -1075,16 +885,9 @@ class Executor:
         JoinResult, {"local": counters, "global": counters}) with the counters of hmj_kind_counts.  The local columns are
         read as those of the single-GPU kind: `probe_rows_to_numpy`, `build_rows_to_numpy` or `columns_to_numpy`."""
         self._sync_stream()
-        bp, nb = _dev_ptr(build_shard)
-        pp, np_ = _dev_ptr(probe_shard)
         loc, glob = JoinResult(), JoinResult()
-        opts = _lib.ExchangeKindOpts()
-        opts.struct_size = C.sizeof(_lib.ExchangeKindOpts)
-        opts.side = int(side)
-        opts.kind = int(kind)
-        opts.probe_fill = int(probe_fill) & 0xFFFFFFFFFFFFFFFF
-        opts.build_fill = int(build_fill) & 0xFFFFFFFFFFFFFFFF
-        self._check(self.L.hmj_exchange_join_kind_u64_device(self.h, C.c_void_p(bp), nb, C.c_void_p(pp), np_, flags,
+        opts = M.new_opts(_lib.ExchangeKindOpts, side=side, kind=kind, probe_fill=probe_fill, build_fill=build_fill)
+        self._check(self.L.hmj_exchange_join_kind_u64_device(self.h, *_dev_ptrs(build_shard, probe_shard), flags,
                                                              C.byref(opts), C.byref(loc), C.byref(glob)))
         return loc, glob, {"local": opts.local.as_dict(), "global": getattr(opts, "global").as_dict()}
 
@@ -1153,68 +956,6 @@ class Executor:
         self._check(self.L.hmj_gen_uniform_domain_u64_device(self.h, C.c_void_p(t.data_ptr()), n, start, domain, seed, zseed))
         return t
 
-    def join_kind_str_device(self, build, probe, side, kind, flags=0, hash_bits=0, probe_fill=0, build_fill=0, build_valid=None,
-                             probe_valid=None):
-        """Semi / anti / outer joins of two string-keyed device relations (hmj_join_kind_str_device).  side / kind as for
-        hmj_exchange_kind_opts: HMJ_KIND_PROBE_SIDE with HMJ_JOIN_*, or HMJ_KIND_BUILD_SIDE with HMJ_BUILD_* / HMJ_FULL_OUTER;
-        build / probe and *_valid as for `join_str_device` (a NULL-key row has no partner: ANTI and the outer kinds of its
-        side emit it with hash 0).  Returns (StrResult, {"n_probe_matched", "n_probe_unmatched", "n_build_matched",
-        "n_build_unmatched", "n_hash_pairs", "n_collisions", "n_build_null", "n_probe_null", "ms_hash", "ms_join",
-        "ms_verify", "ms_emit", "ms_order"}); read the rows with `str_kind_rows_to_numpy`."""
-        self._sync_stream()
-        rb, rp = self._str_rel(build), self._str_rel(probe)
-        opts = _lib.StrKindOpts()
-        opts.struct_size = C.sizeof(_lib.StrKindOpts)
-        opts.side = int(side)
-        opts.kind = int(kind)
-        opts.hash_bits = int(hash_bits)
-        opts.probe_fill = int(probe_fill) & 0xFFFFFFFFFFFFFFFF
-        opts.build_fill = int(build_fill) & 0xFFFFFFFFFFFFFFFF
-        keep = (self._str_validity(build_valid, int(rb.n), "build_valid", opts.build_validity),
-                self._str_validity(probe_valid, int(rp.n), "probe_valid", opts.probe_validity))
-        res = _lib.StrResult()
-        self._check(self.L.hmj_join_kind_str_device(self.h, C.byref(rb), C.byref(rp), flags, C.byref(opts), C.byref(res)))
-        del keep
-        info = opts.counts.as_dict()
-        info["n_hash_pairs"] = int(opts.n_hash_pairs)
-        info["n_collisions"] = int(opts.n_collisions)
-        info["n_build_null"] = int(opts.n_build_null)
-        info["n_probe_null"] = int(opts.n_probe_null)
-        for k in ("ms_hash", "ms_join", "ms_verify", "ms_emit", "ms_order"):
-            info[k] = float(getattr(opts, k))
-        return res, info
-
-    def str_kind_rows_to_numpy(self, res):
-        """Copy a string kind join's device result out as an [n,5] uint64 array of (hash, r_row, s_row, rval, sval); a
-        column the kind does not produce reads as HMJ_STR_NO_ROW (row columns) or 0 (value columns)."""
-        n = int(res.n_matches)
-        out = np.empty((n, 5), np.uint64)
-        if n == 0 or not res.hash:
-            return out[:0]
-        torch = self._torch
-        tmp = torch.empty(n, dtype=torch.int64, device="cuda:%d" % self.device)
-        for c, ptr in enumerate((res.hash, res.r_row, res.s_row, res.rval, res.sval)):
-            if not ptr:
-                out[:, c] = _lib.HMJ_STR_NO_ROW if c in (1, 2) else 0
-                continue
-            _memcpy_d2d(torch, tmp, ptr, n * 8)
-            out[:, c] = tmp.cpu().numpy().view(np.uint64)
-        return out
-
-
-def _check_col(t, name):
-    """A column the string entries read on the device: contiguous, 1-D, 64-bit, on the GPU."""
-    if not t.is_cuda or not t.is_contiguous() or t.element_size() != 8 or t.dim() != 1:
-        raise ValueError("%s must be a contiguous 1-D 64-bit device tensor" % name)
-
-
-def _chars_ptr(chars):
-    if chars is None or chars.numel() == 0:
-        return None
-    if not chars.is_cuda or not chars.is_contiguous() or chars.element_size() != 1:
-        raise ValueError("chars must be a contiguous 1-byte device tensor")
-    return C.c_void_p(chars.data_ptr())
-
 
 def pack_strings(keys, device=None):
     """Keys (str, encoded as UTF-8, or bytes) -> (chars uint8 [total bytes], offsets int64 [n + 1]): the Arrow
@@ -1275,518 +1016,6 @@ def unpack_validity(words, n):
     if n < 0 or raw.size * 8 < n:
         raise ValueError("the words hold fewer than n bits")
     return np.unpackbits(raw, bitorder="little")[:n].astype(bool)
-
-
-def _mix64(x):
-    x = x ^ (x >> np.uint64(30))
-    x = x * np.uint64(0xBF58476D1CE4E5B9)
-    x = x ^ (x >> np.uint64(27))
-    x = x * np.uint64(0x94D049BB133111EB)
-    return x ^ (x >> np.uint64(31))
-
-
-def _null_masks(valid, k, n):
-    """`valid` of cols_key64 / mixed_key64 -> one bool array [n] per column, True = NULL."""
-    if valid is None:
-        return [np.zeros(n, bool) for _ in range(k)]
-    valid = list(valid)
-    if len(valid) != k:
-        raise ValueError("valid: one entry per key column")
-    out = []
-    for v in valid:
-        m = np.zeros(n, bool) if v is None else ~np.asarray(v, bool).ravel()
-        if len(m) != n:
-            raise ValueError("valid: one entry per row")
-        out.append(m)
-    return out
-
-
-def _null_equal_chain(vs, nulls, hash_bits):
-    """key64 under HMJ_NULL_EQUAL: the hash chain with v_c = 0 under a NULL slot, then -- rows with a NULL slot only -- one
-    more step over m = the sum of 2^c over the row's NULL columns."""
-    n = len(vs[0])
-    h = np.full(n, len(vs), np.uint64)
-    m = np.zeros(n, np.uint64)
-    with np.errstate(over="ignore"):
-        for c, (v, nl) in enumerate(zip(vs, nulls)):
-            h = _mix64(h + np.where(nl, np.uint64(0), v) + np.uint64(0x9E3779B97F4A7C15))
-            m = m | np.where(nl, np.uint64(1 << c), np.uint64(0))
-        h = np.where(m != 0, _mix64(h + m + np.uint64(0x9E3779B97F4A7C15)), h)
-    return h >> np.uint64(64 - int(hash_bits)) if hash_bits else h
-
-
-def cols_key64(columns, widths, hash_bits=0, force_hashed=False, valid=None, null_equal=False):
-    """The 64-bit join key hmj_join_cols_device gives every row (include/hmj.h), restated on the host: uint64 array [n].
-    columns: one numpy array per key column (any dtype of widths[c] bytes, or integers that fit it); widths: bytes per
-    column (1, 2, 4 or 8).  Packed form (widths sum to <= 8, not force_hashed): the columns concatenated, column 0 most
-    significant.  Hashed form: h = k; h = mix64(h + v_c + 0x9E3779B97F4A7C15) per column; hash_bits 1..63 keeps the top bits.
-    null_equal=True: the key of a HMJ_NULL_EQUAL call that passes a bitmap -- always the hashed form; valid: None, or one
-    entry per column, None or n bools (True = valid); a NULL slot has v_c = 0 whatever lies under it, and a row with NULL
-    slots takes one more step h = mix64(h + m + 0x9E3779B97F4A7C15), m = the sum of 2^c over its NULL columns.  Without
-    null_equal, valid is not read (a NULL-key row of a SQL-semantics call has key64 0 where it is emitted)."""
-    widths = [int(w) for w in widths]
-    if len(columns) != len(widths) or not 1 <= len(widths) <= _lib.HMJ_MAX_KEY_COLS:
-        raise ValueError("1..%d columns, one width each" % _lib.HMJ_MAX_KEY_COLS)
-    if any(w not in (1, 2, 4, 8) for w in widths):
-        raise ValueError("widths must be 1, 2, 4 or 8")
-    if not 0 <= int(hash_bits) <= 63:
-        raise ValueError("hash_bits must be in 0..63")
-    vs = []
-    for col, w in zip(columns, widths):
-        a = np.ascontiguousarray(col)
-        if a.dtype.itemsize == w and a.dtype.kind != "u":
-            a = a.view("u%d" % w)  # signed integers and floats: their bytes
-        vs.append(a.astype(np.uint64) & np.uint64((1 << (8 * w)) - 1))
-    n = len(vs[0])
-    if null_equal:
-        return _null_equal_chain(vs, _null_masks(valid, len(vs), n), hash_bits)
-    if sum(widths) <= 8 and not force_hashed:
-        key = np.zeros(n, np.uint64)
-        for v, w in zip(vs, widths):
-            key = v if w == 8 else ((key << np.uint64(8 * w)) | v)
-        return key
-    h = np.full(n, len(widths), np.uint64)
-    for v in vs:
-        h = _mix64(h + v + np.uint64(0x9E3779B97F4A7C15))
-    return h >> np.uint64(64 - int(hash_bits)) if hash_bits else h
-
-
-def expected_groups(columns, widths, vals=None, valid=None, hash_bits=0, force_hashed=False, ordered=False):
-    """What hmj_group_cols_device returns (include/hmj.h), restated on the host in plain numpy.  columns / widths as
-    `cols_key64`; vals: n integers (taken mod 2^64) or None (the payload of row i is i); valid: None, or one entry per
-    column, None or n bools (True = valid) -- an entry that is not None is a bitmap passed, which makes the form hashed
-    even when every bit is set.  Two rows are one group when in every column both slots are NULL or both are valid and
-    equal; what lies under a NULL slot is not read.  Returns a dict: "form", "n_groups", "n_rows", "max_count", "n_null",
-    "n_collisions" (groups minus distinct key64), "max_mixed_run" (rows of the largest run of equal key64 that holds
-    several tuples: the call is HMJ_E_UNSUPPORTED beyond 1024), the uint64 group columns "key64", "first_row", "count",
-    "sum", "min", "max", and "group_of_row" [n].  ordered: groups ascending by (key64, the tuple column by column as
-    unsigned integers, NULLS LAST per column) as HMJ_ORDERED gives them; else ascending by first_row, the order in which
-    an unordered result is compared."""
-    widths = [int(w) for w in widths]
-    k = len(widths)
-    n = len(np.ascontiguousarray(columns[0])) if k else 0
-    bitmap = valid is not None and any(v is not None for v in valid)
-    nulls = _null_masks(valid, k, n)
-    hashed = bitmap or sum(widths) > 8 or bool(force_hashed)
-    if bitmap:
-        key64 = cols_key64(columns, widths, hash_bits, valid=valid, null_equal=True)
-    else:
-        key64 = cols_key64(columns, widths, hash_bits, force_hashed)
-    # the tuple as the order and the grouping rule see it: per column (is NULL, value or 0 under a NULL slot)
-    canon = np.zeros((n, 2 * k), np.uint64)
-    for c, (col, w) in enumerate(zip(columns, widths)):
-        a = np.ascontiguousarray(col)
-        if a.dtype.itemsize == w and a.dtype.kind != "u":
-            a = a.view("u%d" % w)
-        v = a.astype(np.uint64) & np.uint64((1 << (8 * w)) - 1)
-        canon[:, 2 * c] = nulls[c]
-        canon[:, 2 * c + 1] = np.where(nulls[c], np.uint64(0), v)
-    return _group_table(canon, key64, _group_payloads(vals, n), nulls, hashed, ordered)
-
-
-def _group_payloads(vals, n):
-    """`vals` of expected_groups / expected_mixed_groups -> the n payloads as uint64."""
-    if vals is None:
-        return np.arange(n, dtype=np.uint64)
-    pay = np.asarray(vals)
-    if pay.dtype.kind == "i":
-        pay = pay.astype(np.int64).view(np.uint64)
-    elif pay.dtype.kind == "u":
-        pay = pay.astype(np.uint64)
-    else:  # Python integers beyond int64
-        pay = np.array([int(x) & 0xFFFFFFFFFFFFFFFF for x in pay.ravel()], np.uint64)
-    if len(pay) != n:
-        raise ValueError("vals: one payload per row")
-    return pay
-
-
-def _group_table(canon, key64, pay, nulls, hashed, ordered):
-    """The result dict of expected_groups / expected_mixed_groups from the canonical tuples: canon [n, 2k] uint64, per
-    column (is NULL, a number that orders and equals as the column's values do, 0 under a NULL slot)."""
-    n, k = canon.shape[0], canon.shape[1] // 2
-    out = {"form": _lib.HMJ_COLS_HASHED if hashed else _lib.HMJ_COLS_PACKED, "n_rows": n,
-           "n_null": int(np.count_nonzero(np.any(np.stack(nulls), axis=0))) if k and n else 0}
-    empty = np.zeros(0, np.uint64)
-    if n == 0:
-        out.update({"n_groups": 0, "max_count": 0, "n_collisions": 0, "max_mixed_run": 0, "group_of_row": empty})
-        out.update({name: empty for name in ("key64", "first_row", "count", "sum", "min", "max")})
-        return out
-    # groups in tuple order (numpy.unique sorts rows lexicographically; return_index: the first, i.e. smallest, row)
-    _, first, inv, count = np.unique(canon, axis=0, return_index=True, return_inverse=True, return_counts=True)
-    inv = inv.reshape(-1)
-    gkey = key64[first]
-    order = np.lexsort((np.arange(len(first)), gkey)) if ordered else np.argsort(first, kind="stable")
-    rank = np.empty(len(first), np.int64)
-    rank[order] = np.arange(len(first))
-    group_of_row = rank[inv]
-    by_group = np.argsort(group_of_row, kind="stable")
-    starts = np.concatenate([[0], np.cumsum(count[order])[:-1]]).astype(np.int64)
-    sorted_pay = pay[by_group]
-    with np.errstate(over="ignore"):
-        gsum = np.add.reduceat(sorted_pay, starts)
-    ukey, kinv = np.unique(key64, return_inverse=True)
-    tuples_per_key = np.bincount(kinv.reshape(-1)[first], minlength=len(ukey))
-    rows_per_key = np.bincount(kinv.reshape(-1), minlength=len(ukey))
-    mixed = rows_per_key[tuples_per_key > 1]
-    out.update({"n_groups": len(first), "max_count": int(count.max()), "n_collisions": int(len(first) - len(ukey)),
-                "max_mixed_run": int(mixed.max()) if len(mixed) else 0,
-                "key64": gkey[order], "first_row": first[order].astype(np.uint64), "count": count[order].astype(np.uint64),
-                "sum": gsum.astype(np.uint64), "min": np.minimum.reduceat(sorted_pay, starts),
-                "max": np.maximum.reduceat(sorted_pay, starts), "group_of_row": group_of_row.astype(np.uint64)})
-    return out
-
-
-def _float_order_keys(a):
-    """Floats (float32 / float64) -> (unsigned keys whose integer order is IEEE order with -0.0 < +0.0, is-NaN mask)."""
-    bits = a.view("u%d" % a.dtype.itemsize)
-    top = bits.dtype.type(1 << (8 * a.dtype.itemsize - 1))
-    keys = np.where(bits & top, ~bits, bits | top)
-    return keys, (bits & ~top) > (bits.dtype.type(0x7F800000) if a.dtype.itemsize == 4 else bits.dtype.type(0x7FF0000000000000))
-
-
-def expected_group_aggs(group_of_row, n_groups, aggs):
-    """What hmj_group_agg_device returns (include/hmj.h), restated on the host from group_of_row alone -- no key logic.
-    group_of_row: n integers in 0..n_groups-1; aggs: a list of (op, values, valid): op an HMJ_AGG_* code, values a numpy
-    array of n integers or floats of the column's dtype (None for HMJ_AGG_COUNT), valid None or n bools (True = valid).
-    What lies under a NULL slot is not read.  Returns one dict per aggregate: "values" (n_groups entries of the output
-    dtype: COUNT uint64, SUM int64 / uint64 / float64, MIN / MAX the source dtype, MEAN float64; 0 in a NULL slot),
-    "valid" (n_groups bools), "null_count", "count" (the valid values per group, int64) and "abs_sum" (float64: the sum of
-    |x| over the group's valid values for float SUM and for MEAN, each x converted to double; None otherwise).  Float sums
-    are math.fsum per group, i.e. correctly rounded: the device's differ from them by at most gamma_k * abs_sum."""
-    import math
-
-    gmap = np.asarray(group_of_row).astype(np.int64).ravel()
-    n, ng = len(gmap), int(n_groups)
-    if n and (gmap.min() < 0 or gmap.max() >= ng):
-        raise ValueError("group_of_row: entries must be in 0..n_groups-1")
-    out = []
-    for op, vals, valid in [tuple(a)[:3] if len(tuple(a)) > 2 else tuple(a) + (None,) for a in aggs]:
-        op = int(op)
-        ok = np.ones(n, bool) if valid is None else np.asarray(valid, bool).ravel()
-        if len(ok) != n:
-            raise ValueError("valid: one entry per row")
-        count = np.bincount(gmap[ok], minlength=ng).astype(np.int64)
-        res = {"count": count, "abs_sum": None}
-        if op == _lib.HMJ_AGG_COUNT:
-            res.update({"values": count.astype(np.uint64), "valid": np.ones(ng, bool)})
-        else:
-            a = np.ascontiguousarray(vals).ravel()
-            if len(a) != n or a.dtype.kind not in "iuf" or a.dtype.itemsize > 8 or a.dtype == np.float16:
-                raise ValueError("values: n integers or floats of 1 to 8 bytes")
-            g, x = gmap[ok], a[ok]
-            is_float = a.dtype.kind == "f"
-            if op == _lib.HMJ_AGG_MEAN or (op == _lib.HMJ_AGG_SUM and is_float):
-                xd = x.astype(np.float64)
-                order = np.argsort(g, kind="stable")
-                ends = np.cumsum(count)
-                sums, abss = np.zeros(ng), np.zeros(ng)
-                with np.errstate(all="ignore"):
-                    for k in range(ng):
-                        seg = xd[order[ends[k] - count[k]:ends[k]]]
-                        try:
-                            sums[k] = math.fsum(seg)
-                        except (OverflowError, ValueError):  # an intermediate overflow, inf - inf: as IEEE addition has it
-                            sums[k] = float(np.sum(seg))
-                        abss[k] = float(np.sum(np.abs(seg)))
-                    v = sums / np.maximum(count, 1) if op == _lib.HMJ_AGG_MEAN else sums
-                res["abs_sum"] = abss
-            elif op == _lib.HMJ_AGG_SUM:
-                wide = x.astype(np.int64).view(np.uint64) if a.dtype.kind == "i" else x.astype(np.uint64)
-                acc = np.zeros(ng, np.uint64)
-                np.add.at(acc, g, wide)  # (wraps mod 2^64)
-                v = acc.view(np.int64) if a.dtype.kind == "i" else acc
-            elif op in (_lib.HMJ_AGG_MIN, _lib.HMJ_AGG_MAX):
-                low = op == _lib.HMJ_AGG_MIN
-                if is_float:
-                    keys, nan = _float_order_keys(x)
-                    ident = keys.dtype.type(np.iinfo(keys.dtype).max if low else 0)
-                    acc = np.full(ng, ident, keys.dtype)
-                    (np.minimum if low else np.maximum).at(acc, g[~nan], keys[~nan])
-                    numbers = np.bincount(g[~nan], minlength=ng) > 0
-                    top = keys.dtype.type(1 << (8 * a.dtype.itemsize - 1))
-                    v = np.where(acc & top, acc ^ top, ~acc).view(a.dtype).copy()
-                    v[~numbers] = np.nan  # (numpy's default NaN is the canonical quiet one)
-                else:
-                    info = np.iinfo(a.dtype)
-                    acc = np.full(ng, info.max if low else info.min, a.dtype)
-                    (np.minimum if low else np.maximum).at(acc, g, x)
-                    v = acc
-            else:
-                raise ValueError("unknown op %d" % op)
-            v = np.array(v)
-            v[count == 0] = 0
-            res.update({"values": v, "valid": count > 0})
-        res["null_count"] = int(ng - np.count_nonzero(res["valid"]))
-        out.append(res)
-    return out
-
-
-def _order_columns(columns):
-    """(values, flags[, valid]) per column -> [(values, flags, valid bools or None, is_string)], n.  values: a numpy array
-    of an integer or float dtype, or a list of bytes / str (None where the slot is NULL counts as NULL too)."""
-    out, n = [], None
-    for c in columns:
-        c = tuple(c)
-        vals, flags = c[0], int(c[1]) if len(c) > 1 else 0
-        valid = None if len(c) < 3 or c[2] is None else np.asarray(c[2], bool).ravel()
-        is_str = not isinstance(vals, np.ndarray)
-        if is_str:
-            vals = [None if v is None else (v.encode("utf-8") if isinstance(v, str) else bytes(v)) for v in vals]
-            if any(v is None for v in vals):
-                holes = np.array([v is not None for v in vals], bool)
-                valid = holes if valid is None else (valid & holes)
-        if n is None:
-            n = len(vals)
-        if len(vals) != n or (valid is not None and len(valid) != n):
-            raise ValueError("every column and every valid mask must hold n rows")
-        out.append((vals, flags, valid, is_str))
-    return out, (n or 0)
-
-
-def expected_order_by(columns):
-    """The row map hmj_order_by_device returns (include/hmj.h), restated on the host from the order rule: columns is a list
-    of (values, flags[, valid]) -- values a numpy array of an integer or float dtype, or a list of bytes (a string column);
-    flags HMJ_ORDER_* bits; valid None or n bools (True = valid).  Per column every row gets the dense rank of its value
-    among the column's valid values -- integers in their signedness, floats in IEEE order with -0.0 < +0.0 and every NaN one
-    value above +inf, strings as Python orders bytes (unsigned bytes, then length) --, reversed under HMJ_ORDER_DESC; a NULL
-    slot ranks behind all of them, or in front under HMJ_ORDER_NULLS_FIRST.  The map is the stable lexicographic order of
-    the rank tuples (ties keep ascending row index).  What lies under a NULL slot is not read.  Returns n uint64."""
-    cols, n = _order_columns(columns)
-    ranks = []
-    for vals, flags, valid, is_str in cols:
-        ok = np.ones(n, bool) if valid is None else valid
-        idx = np.nonzero(ok)[0]
-        rank = np.zeros(n, np.int64)
-        if is_str:
-            picked = [vals[i] for i in idx]
-            order = {v: k for k, v in enumerate(sorted(set(picked)))}
-            r = np.fromiter((order[v] for v in picked), dtype=np.int64, count=len(picked))
-            distinct = len(order)
-        else:
-            x = np.ascontiguousarray(vals[idx])
-            if x.dtype.kind == "f":
-                keys, nan = _float_order_keys(x)
-                x = np.where(nan, ~keys.dtype.type(0), keys)  # (no number's key is all ones)
-            uniq, r = np.unique(x, return_inverse=True)
-            r = r.astype(np.int64).ravel()
-            distinct = len(uniq)
-        if flags & _lib.HMJ_ORDER_DESC:
-            r = distinct - 1 - r
-        rank[idx] = r
-        rank[~ok] = -1 if flags & _lib.HMJ_ORDER_NULLS_FIRST else distinct
-        ranks.append(rank)
-    if n == 0:
-        return np.zeros(0, np.uint64)
-    return np.lexsort(ranks[::-1]).astype(np.uint64)  # (lexsort: the last key is the primary one; stable)
-
-
-def order_stream_bytes(columns):
-    """The length S of every row's order-preserving byte stream in hmj_order_by_device (include/hmj.h): per column one
-    marker byte when the column has a validity mask, then the value's width for a fixed column, or 8 * max(1, ceil(len / 7))
-    for a valid string and nothing for a NULL one.  hmj_order_opts.n_rounds is at most 1 + ceil(max(0, max S - 8) / 4).
-    columns as `expected_order_by` takes them.  Returns n int64."""
-    cols, n = _order_columns(columns)
-    total = np.zeros(n, np.int64)
-    for vals, _flags, valid, is_str in cols:
-        if valid is not None:
-            total += 1
-        if is_str:
-            ok = np.ones(n, bool) if valid is None else valid
-            total += np.array([8 * max(1, -(-len(vals[i]) // 7)) if ok[i] else 0 for i in range(n)], np.int64).reshape(n)
-        else:
-            total += vals.dtype.itemsize
-    return total
-
-
-def expected_filter(terms, n):
-    """What hmj_filter_device returns (include/hmj.h), restated on the host: terms as `Executor.filter_device` takes them
-    (dicts, or tuples (column, op, lit, valid, bit_offset, row_map, clause, negate)) with host values -- column a numpy
-    array of an integer or float dtype, or a list of bytes / str (None: a NULL slot); lit as there; valid None or one bool
-    per ROW of the column (True = valid; bit_offset is not looked at); row_map None or n entries (uint64 or int64,
-    HMJ_TAKE_NO_ROW / -1 a NULL slot).  Every term is numpy's own comparison operator on the column's dtype (C's operators:
-    IEEE for floats) or Python's comparison of `bytes` (unsigned bytes, then length), made three-valued -- UNKNOWN on a NULL
-    slot except for IS_NULL / IS_NOT_NULL, negation swapping TRUE and FALSE --; a clause is the maximum of its terms and the
-    predicate the minimum of its clauses under FALSE < UNKNOWN < TRUE.  What lies under a NULL slot is not read.  Returns
-    (the positions at which the predicate is TRUE, ascending, n uint64 at most; the number of UNKNOWN positions)."""
-    keys = ("column", "op", "lit", "valid", "bit_offset", "row_map", "clause", "negate")
-    F, U, T = 0, 1, 2
-    n = int(n)
-    pred = np.full(n, T, np.int8)
-    cl, cl_id = None, None
-    for k, t in enumerate(terms):
-        t = t if isinstance(t, dict) else dict(zip(keys, t))
-        vals, op = t["column"], int(t["op"])
-        lit = t.get("lit")
-        lits = [] if lit is None else (list(lit) if isinstance(lit, (tuple, list)) else [lit])
-        is_str = not isinstance(vals, np.ndarray)
-        n_src = len(vals)
-        rm = t.get("row_map")
-        if rm is None:
-            if n_src < n:
-                raise ValueError("term %d: n_src < n without a row_map" % k)
-            have, rows = np.ones(n, bool), np.arange(n, dtype=np.int64)
-        else:
-            rm = np.asarray(rm).astype(np.uint64)[:n]
-            if len(rm) != n:
-                raise ValueError("term %d: row_map must hold n entries" % k)
-            have = rm != np.uint64(_lib.HMJ_TAKE_NO_ROW)
-            if np.any(have & (rm >= np.uint64(n_src))):
-                raise ValueError("term %d: a row_map entry is >= n_src and not HMJ_TAKE_NO_ROW" % k)
-            rows = np.where(have, rm, np.uint64(0)).astype(np.int64)
-        ok = have.copy()
-        valid = t.get("valid")
-        if is_str:
-            vals = [None if v is None else (v.encode("utf-8") if isinstance(v, str) else bytes(v)) for v in vals]
-            holes = np.array([v is not None for v in vals], bool)
-            valid = holes if valid is None else (np.asarray(valid, bool).ravel() & holes)
-        if valid is not None:
-            valid = np.asarray(valid, bool).ravel()
-            if len(valid) != n_src:
-                raise ValueError("term %d: valid must hold one entry per row of the column" % k)
-            ok[have] = valid[rows[have]]
-        if op == _lib.HMJ_FILTER_IS_NULL:
-            v = np.where(ok, F, T)
-        elif op == _lib.HMJ_FILTER_IS_NOT_NULL:
-            v = np.where(ok, T, F)
-        else:
-            if len(lits) != (2 if op == _lib.HMJ_FILTER_BETWEEN else 1):
-                raise ValueError("term %d: the op takes %d literal(s)" % (k, 2 if op == _lib.HMJ_FILTER_BETWEEN else 1))
-            idx = np.nonzero(ok)[0]
-            res = np.zeros(n, bool)
-            if is_str:
-                ls = [x.encode("utf-8") if isinstance(x, str) else bytes(x) for x in lits]
-                fn = {_lib.HMJ_FILTER_EQ: lambda s: s == ls[0], _lib.HMJ_FILTER_NE: lambda s: s != ls[0],
-                      _lib.HMJ_FILTER_LT: lambda s: s < ls[0], _lib.HMJ_FILTER_LE: lambda s: s <= ls[0],
-                      _lib.HMJ_FILTER_GT: lambda s: s > ls[0], _lib.HMJ_FILTER_GE: lambda s: s >= ls[0],
-                      _lib.HMJ_FILTER_BETWEEN: lambda s: ls[0] <= s and s <= ls[1],
-                      _lib.HMJ_FILTER_STARTS_WITH: lambda s: s.startswith(ls[0]),
-                      _lib.HMJ_FILTER_ENDS_WITH: lambda s: s.endswith(ls[0])}[op]
-                res[idx] = [bool(fn(vals[r])) for r in rows[idx]]
-            else:
-                x = vals[rows[idx]]
-                ls = [np.array([v], dtype=vals.dtype)[0] for v in lits]
-                with np.errstate(invalid="ignore"):
-                    if op == _lib.HMJ_FILTER_EQ:
-                        r = x == ls[0]
-                    elif op == _lib.HMJ_FILTER_NE:
-                        r = x != ls[0]
-                    elif op == _lib.HMJ_FILTER_LT:
-                        r = x < ls[0]
-                    elif op == _lib.HMJ_FILTER_LE:
-                        r = x <= ls[0]
-                    elif op == _lib.HMJ_FILTER_GT:
-                        r = x > ls[0]
-                    elif op == _lib.HMJ_FILTER_GE:
-                        r = x >= ls[0]
-                    elif op == _lib.HMJ_FILTER_BETWEEN:
-                        r = (ls[0] <= x) & (x <= ls[1])
-                    else:
-                        raise ValueError("term %d: op %d does not apply to a fixed-width column" % (k, op))
-                res[idx] = r
-            v = np.where(ok, np.where(res, T, F), U)
-        v = v.astype(np.int8)
-        if t.get("negate"):
-            v = (T - v).astype(np.int8)
-        cid = int(t.get("clause") or 0)
-        if cl is not None and cid != cl_id:
-            if cid < cl_id:
-                raise ValueError("term %d: clause ids must not decrease" % k)
-            pred = np.minimum(pred, cl)
-            cl = None
-        cl, cl_id = (v if cl is None else np.maximum(cl, v)), cid
-    if cl is not None:
-        pred = np.minimum(pred, cl)
-    return np.nonzero(pred == T)[0].astype(np.uint64), int(np.count_nonzero(pred == U))
-
-
-def _hash_bytes(b):
-    """libstdc++'s _Hash_bytes (64-bit size_t, seed 0xc70f6907): std::hash<std::string> of the bytes b."""
-    M, mask = 0xc6a4a7935bd1e995, 0xFFFFFFFFFFFFFFFF
-    n = len(b)
-    h = (0xc70f6907 ^ (n * M)) & mask
-    for k in range(0, n & ~7, 8):
-        d = (int.from_bytes(b[k:k + 8], "little") * M) & mask
-        d = ((d ^ (d >> 47)) * M) & mask
-        h = ((h ^ d) * M) & mask
-    if n & 7:
-        h = ((h ^ int.from_bytes(b[n & ~7:], "little")) * M) & mask
-    h = ((h ^ (h >> 47)) * M) & mask
-    return h ^ (h >> 47)
-
-
-def mixed_key64(columns, hash_bits=0, valid=None, null_equal=False):
-    """The 64-bit join key hmj_join_mixed_device gives every row (include/hmj.h), restated on the host: uint64 array [n].
-    columns: one entry per key column -- a numpy integer array (a fixed-width column: its values zero-extended from the
-    dtype's width) or a list of `bytes` (a string column: libstdc++'s _Hash_bytes of every slot, all 64 bits).
-    h = k; h = mix64(h + v_c + 0x9E3779B97F4A7C15) per column; hash_bits 1..63 keeps the top bits.  valid / null_equal as
-    for `cols_key64`: under HMJ_NULL_EQUAL a NULL slot has v_c = 0 (a NULL string slot may hold None), and a row with NULL
-    slots takes the extra step over its NULL columns' mask."""
-    if not 1 <= len(columns) <= _lib.HMJ_MAX_KEY_COLS:
-        raise ValueError("1..%d columns" % _lib.HMJ_MAX_KEY_COLS)
-    if not 0 <= int(hash_bits) <= 63:
-        raise ValueError("hash_bits must be in 0..63")
-    vs = []
-    for col in columns:
-        if isinstance(col, np.ndarray):
-            a = np.ascontiguousarray(col)
-            if a.dtype.itemsize not in (1, 2, 4, 8):
-                raise ValueError("a fixed-width column has 1, 2, 4 or 8 bytes per value")
-            vs.append(a.view("u%d" % a.dtype.itemsize).astype(np.uint64))
-        else:
-            vs.append(np.array([0 if b is None else _hash_bytes(bytes(b)) for b in col], np.uint64))
-    if any(len(v) != len(vs[0]) for v in vs):
-        raise ValueError("columns must have one length")
-    if null_equal:
-        return _null_equal_chain(vs, _null_masks(valid, len(vs), len(vs[0])), hash_bits)
-    h = np.full(len(vs[0]), len(vs), np.uint64)
-    with np.errstate(over="ignore"):
-        for v in vs:
-            h = _mix64(h + v + np.uint64(0x9E3779B97F4A7C15))
-    return h >> np.uint64(64 - int(hash_bits)) if hash_bits else h
-
-
-def expected_mixed_groups(columns, vals=None, valid=None, hash_bits=0, ordered=False):
-    """What hmj_group_mixed_device returns (include/hmj.h), restated on the host.  columns as `mixed_key64` takes them: a
-    numpy integer array per fixed-width column, a list of `bytes` per string column (None is fine under a NULL slot);
-    vals / valid / ordered as for `expected_groups`.  The form is always hashed and key64 is `mixed_key64(columns,
-    hash_bits, valid, null_equal=True)`.  Two rows are one group when in every column both slots are NULL or both are
-    valid and equal (strings: length and bytes; a NULL string is not the empty string); what lies under a NULL slot is not
-    read.  Returns `expected_groups`' dict, "max_mixed_run" included.  ordered: ascending by (key64, the tuple column by
-    column, NULLS LAST per column): fixed columns as unsigned integers, strings as Python orders `bytes`, which is
-    std::string::operator<."""
-    k = len(columns)
-    n = len(columns[0]) if k else 0
-    nulls = _null_masks(valid, k, n)
-    key64 = mixed_key64(columns, hash_bits, valid, null_equal=True) if k else np.zeros(0, np.uint64)
-    canon = np.zeros((n, 2 * k), np.uint64)
-    for c, col in enumerate(columns):
-        if isinstance(col, np.ndarray):
-            a = np.ascontiguousarray(col)
-            v = a.view("u%d" % a.dtype.itemsize).astype(np.uint64)
-        else:  # a string's number: its rank among the column's distinct valid strings in bytes order
-            slots = [b"" if (nulls[c][i] or b is None) else bytes(b) for i, b in enumerate(col)]
-            rank = {b: r for r, b in enumerate(sorted(set(slots)))}
-            v = np.array([rank[b] for b in slots], np.uint64)
-        canon[:, 2 * c] = nulls[c]
-        canon[:, 2 * c + 1] = np.where(nulls[c], np.uint64(0), v)
-    return _group_table(canon, key64, _group_payloads(vals, n), nulls, True, ordered)
-
-
-def _memcpy_d2d(torch, dst_tensor, src_ptr, nbytes):
-    """Copy nbytes from a raw device pointer into a torch tensor (plumbing only)."""
-    hip = C.CDLL(None)  # the HIP runtime torch already loaded
-    fn = getattr(hip, "hipMemcpy", None)
-    if fn is None:
-        import ctypes.util
-
-        hip = C.CDLL("libamdhip64.so")
-        fn = hip.hipMemcpy
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    torch.cuda.synchronize()
-    rc = fn(C.c_void_p(dst_tensor.data_ptr()), C.c_void_p(src_ptr), nbytes, 3)  # hipMemcpyDeviceToDevice
-    if rc:
-        raise HmjError(-4, "hipMemcpy d2d failed: %d" % rc)
 
 
 class HashMergeJoin:
