@@ -354,6 +354,13 @@ void spans_reset(hmj_ctx* c) {
   c->ev_used = 0;
   std::memset(&c->timing, 0, sizeof(c->timing));
 }
+// forget an abandoned attempt's phase spans (the enclosing total / h2d spans stay)
+static void drop_attempt_spans(hmj_ctx* c) {
+  std::vector<Span> keep;
+  for (const Span& s : c->spans)
+    if (s.kind == K_TOTAL || s.kind == K_H2D) keep.push_back(s);
+  c->spans.swap(keep);
+}
 void spans_collect(hmj_ctx* c) {  // call after the stream is synchronized
   hmj_timing& t = c->timing;
   for (const Span& s : c->spans) {
@@ -387,23 +394,6 @@ void spans_collect(hmj_ctx* c) {  // call after the stream is synchronized
 // Partition count: enough most-significant key bits that an average build partition holds
 // <= PB_TARGET_AVG rows and so fits the LDS table of probe.hip (the reference's optimal_partition,
 // radix_hash.h:38-57, sizes for CPU caches instead).  Passes: LSD order, <= RP_MAX_BITS each.
-// The most probe rows ANY of P partitions is expected to hold in a foreign-key join: a partition gets N ~ Poisson(lam)
-// build keys (lam = avg_np / f) and about f probe rows for each.  N's upper quantile at 0.05 / P is found by summing
-// the Poisson tail (the normal approximation "mean + 5 sigma" is 15 % short at lam = 8: fan-out 256 was planned into
-// partitions that did not fit, and the whole join fell back to the two-step ordered form); the rows-per-key noise is
-// added in quadrature.
-double fk_probe_rows_hi(double avg_np, double f, double P) {
-  if (avg_np <= 0.0 || f <= 0.0) return 0.0;
-  const double lam = avg_np / f, p_tail = 0.05 / (P > 1.0 ? P : 1.0);
-  const double step = lam > 256.0 ? std::floor(std::sqrt(lam) / 8.0) : 1.0;
-  double k = std::floor(lam);
-  for (const double k_end = lam + 40.0 * std::sqrt(lam) + 100.0; k < k_end; k += step) {
-    const double lp = -lam + (k + 1.0) * std::log(lam) - std::lgamma(k + 2.0);  // log P(N = k + 1)
-    if (std::exp(lp) / (1.0 - lam / (k + 2.0)) <= p_tail) break;                // (geometric bound on P(N > k))
-  }
-  const double z = (k - lam) / std::sqrt(lam), from_keys = (k - lam) * f, from_rows = z * std::sqrt(avg_np);
-  return avg_np + std::sqrt(from_keys * from_keys + from_rows * from_rows);
-}
 
 void plan_bits(u64 n_build, int force, int* total, int* passes, int pass_bits[4]) {
   int B = 0;
@@ -2053,10 +2043,6 @@ int try_global_table(hmj_ctx* c, const void* R, uint64_t n_build, const void* S,
 // i + 1's, because a pass-B worker belongs to one value of the previous digit and the values in use carry all its rows.  Skew
 // the sizes do not cover overflows a slab: *ok = false, the input is untouched, the error word is cleared, the chain's spans
 // are dropped.  One read-back.
-struct ChainDigit {
-  int shift, bits;
-  double dens;
-};
 static int slab_chain(hmj_ctx* c, const void* dense_in, u32 n, const ChainDigit* dg, int nd, int rel, bool* ok_out, u32* pc_n,
                       u32* pc_cap, int* pc_which) {
   *ok_out = false;
@@ -2147,6 +2133,65 @@ static int slab_chain(hmj_ctx* c, const void* dense_in, u32 n, const ChainDigit*
   *ok_out = ok;
   return HMJ_OK;
 }
+// The sorted pieces a chain left (n != 0): their offsets in the output, for the kernel that expands or compacts them.
+struct ChainPieces {
+  u32 n = 0, cap = 0;
+  int which = 0;
+  DevBuf& slabs(hmj_ctx* c) const { return which ? c->slab_bs : c->slab_a; }
+  DevBuf& counts(hmj_ctx* c) const { return which ? c->cnt_bs : c->cnt_a; }
+};
+static int piece_offsets(hmj_ctx* c, const ChainPieces& pc) {
+  RC_TRY(ensure_dev(c, c->piece_off, (size_t)pc.n * 8));
+  HIP_TRY(hmj::launch_piece_offsets((const u32*)pc.counts(c).p, pc.n, (u64*)c->piece_off.p, c->stream));
+  return HMJ_OK;
+}
+
+// The rows in 2^(ba + bb) partitions by two slab passes -- A on the key bits [shift_a, shift_a + ba), B on the bb bits above --
+// and the partitions' offsets (c->part_out_off) for one LDS sort per partition: the rank-run form of the ordered small-build
+// join and the MSD form of hmj_sort_u64_device.  The six buffers are ensured here, and behind them the join's result columns
+// (result_rows of them; 0: the caller has its output).  lookup: pass A reads the PROBE rows, looks their rank up in the
+// global table and partitions on the rank (radix.hip, radix_slab_a_rank_kernel).  The passes' spans carry span_rel; the
+// offsets scan has a span of its own only for the join (scan_span).  Overflows show in the error word, which the caller reads.
+// A launch of these passes fails under its launcher's name (the span around it is closed first), as the rank-run form always
+// reported it; the sort's MSD form reported the call expression's text before it shared these steps.
+static int launched(hmj_ctx* c, hipError_t e, const char* what) { return e == hipSuccess ? HMJ_OK : fail(c, HMJ_E_HIP, what, e); }
+struct RankLookup {
+  int log_cap, cut, pre;
+  bool extra;
+  u64 svmin, span, mult;
+};
+static int msd_partition(hmj_ctx* c, const void* src, u32 n, int shift_a, int ba, int bb, const hmj::SlabGeom& g, int span_rel,
+                         bool scan_span, size_t result_rows, const RankLookup* lookup) {
+  const u32 P = 1u << (ba + bb);
+  RC_TRY(ensure_dev(c, c->slab_a, g.rows_a * 16));
+  RC_TRY(ensure_dev(c, c->cnt_a, ((size_t)g.WA << ba) * 4));
+  RC_TRY(ensure_dev(c, c->slab_bs, g.rows_b * 16));
+  RC_TRY(ensure_dev(c, c->cnt_bs, (size_t)P * g.KB * 4));
+  RC_TRY(ensure_dev(c, c->part_out_off, ((size_t)P + 1) * 8));
+  RC_TRY(ensure_dev(c, c->part_count, ((size_t)P / 1024 + 1) * 8));  // (chunk totals of the offsets scan)
+  if (result_rows) {
+    RC_TRY(ensure_dev(c, c->out_key, result_rows * 8));
+    RC_TRY(ensure_dev(c, c->out_rval, result_rows * 8));
+    RC_TRY(ensure_dev(c, c->out_sval, result_rows * 8));
+  }
+  u64* acc = (u64*)c->accum.p;
+  int sp = span_begin(c, K_SCATTER, span_rel, 0);
+  hipError_t e = lookup ? hmj::launch_slab_a_ranks(src, n, shift_a, ba, g, c->slab_a.p, c->slab_a.cap / 16, (u32*)c->cnt_a.p, c->cnt_a.cap / 4, acc,
+                                                   c->gtab.p, lookup->log_cap, lookup->extra, lookup->cut, lookup->svmin, lookup->span, lookup->pre,
+                                                   lookup->mult, c->stream)
+                        : hmj::launch_slab_a(src, n, shift_a, ba, g, c->slab_a.p, c->slab_a.cap / 16, (u32*)c->cnt_a.p, c->cnt_a.cap / 4, acc, c->stream);
+  span_end(c, sp);
+  RC_TRY(launched(c, e, lookup ? "launch_slab_a_ranks" : "launch_slab_a"));
+  sp = span_begin(c, K_SCATTER, span_rel, 1);
+  e = hmj::launch_slab_b(c->slab_a.p, (const u32*)c->cnt_a.p, ba, shift_a + ba, bb, g, c->slab_bs.p, c->slab_bs.cap / 16, (u32*)c->cnt_bs.p,
+                         c->cnt_bs.cap / 4, acc, c->stream);
+  span_end(c, sp);
+  RC_TRY(launched(c, e, "launch_slab_b"));
+  sp = scan_span ? span_begin(c, K_OUT_SCAN, -1) : -1;
+  e = hmj::launch_slab_offsets((const u32*)c->cnt_bs.p, P, (u64*)c->part_out_off.p, (u64*)c->part_count.p, c->stream);
+  span_end(c, sp);
+  return launched(c, e, "launch_slab_offsets");
+}
 
 // Ordered result of a SMALL build side under a LONG probe side (fan-outs in the hundreds and thousands: a dimension table of a
 // few thousand rows under a fact table), unique build keys.  The operator's order (key, rval, sval) is then the probe rows
@@ -2156,229 +2201,142 @@ static int slab_chain(hmj_ctx* c, const void* dense_in, u32 n, const ChainDigit*
 // The partitioned paths rank every probe row inside its key's run, linear in the run length, and plan 18 bits for these
 // shapes: 2^16 x 2^26 rows 14-22 ms, 2^10 x 2^22 6 ms.  Anything else -- duplicate build keys, payloads too wide, a table
 // that gives up -- leaves *done false and the partitioned paths run (8 joins of cool-down).
-// ns per probe row of the partitioned one-pass ordered foreign-key write at fan-out f (profiles/r04u_side_fk_payload_buckets.txt)
-static double ordered_part_ns(const OrderedCostModel& m, double f, double n_probe) {
-  if (f > 700.0) return m.part_epilogue_ns;  // (runs beyond the kernel's partitions: write + order epilogue)
-  // ... and so are a few keys too many in one partition of the finest plan there is (18 bits): 2^19 x 2^28 rows -- two keys
-  // of 512 probe rows per partition on average, twelve in the fullest of 2^18 -- overflowed the write's 6144-row shape,
-  // the exact path took over with the order epilogue: 137 ms, against 19 ms on the composites and 15 ms for 2^20 x 2^28
-  // (profiles/r05s_*).  The plan's own estimate of the fullest partition (fk_probe_rows_hi) says when.
-  const double P18 = (double)(1u << (2 * hmj::SLAB_MAX_BITS));
-  if (fk_probe_rows_hi(n_probe / P18, f, P18) > 6144.0) return m.part_epilogue_ns;
-  const double lin = m.part_ns + m.part_ns_per_f * f;
-  if (f < 24.0) return lin;
-  const double bucketed = m.part_bucket_ns + (f > 128.0 ? m.part_bucket_ns_per_f * (f - 128.0) : 0.0);
-  return lin < bucketed ? lin : bucketed;
+// The path is a ladder of forms -- rank runs with the lookup inside pass A -> emit + pass A -> composites sorted by a chain of
+// slab passes -> by exact passes -- walked by one function per step over this state (the arithmetic: hmj_smallplan.h).
+struct SmallOrdered {
+  const void *R, *S;  // the call
+  uint64_t n_build, n_probe;
+  uint32_t flags;
+  hmj_result* out;
+  bool to_host;
+  u32 nb, np;
+  bool extra;                   // checksums or the probe-payload sum are asked for
+  double part_ns;               // the gate's estimate of the partitioned write
+  int run_tb, run_level;        // the rank-run form: rank_runs_fit's cut and level ...
+  bool use_runs;                // ... and whether it is tried
+  u64 key_diff, svmin, svmax;   // step 1: the bits the build keys differ in, the probe payloads' range
+  int range_bits, rank_bits;
+  bool wide;                    // rank and payload do not fit one word
+  bool have_range;              // svmin / svmax are exact (cut runs take a sample's: rows outside it go to the end pieces)
+  u32 range_every;
+  const void* sortedR;          // step 2: the build side in key order
+  int log_cap;                  // step 3: the key -> rank table's slots
+  int sp;                       // the open K_PROBE_COUNT span (table build, and the emit where there is one)
+  u64 n;                        // result rows
+  u64* hh;                      // the last read-back of the accumulators
+  bool runs_done;               // the rank-run form delivered
+  const char* why;              // ... or why it did not
+  int which, n_passes;          // steps 4-6: the sorted composites lie in sbuf[which] after n_passes passes ...
+  const void* sorted;
+  ChainPieces pc;               // ... or as the pieces of the chain's last pass
+};
+constexpr int kPathGaveUp = 1010;  // internal: this path is off for the join (*done stays false) -> the partitioned paths
+enum RunPasses { kRunsDone = 0, kRunsGaveUp = 1, kRunsTableGaveUp = 2, kRunsDuplicateKeys = 3 };  // rank_run_passes; < 0: an error
+
+// what the planning arithmetic (hmj_smallplan.h) needs of the context
+static RankRunKnobs rank_run_knobs(const hmj_ctx* c) {
+  RankRunKnobs k;
+  k.rank_runs_mode = c->rank_runs_mode;
+  k.slab_mode = c->slab_mode != 0;
+  k.rank_runs_wave = c->rank_runs_wave;
+  k.max_level = c->rank_runs_max_level;
+  k.max_group = c->rank_runs_max_group;
+  k.max_cut = c->rank_runs_max_cut;
+  k.chunk_rows = hmj::RANK_PASS_CHUNK_ROWS;
+  k.slab_max_bits = hmj::SLAB_MAX_BITS;
+  k.lds = c->lds_sort;
+  return k;
 }
-// The rank-run form (gtable.hip): every partition of probe rows must fit one workgroup's LDS sort with room for its
-// spread (mean + 8 sigma of a run of a uniform foreign key), both digits of the partition number must be slab passes, and
-// the partitions must be long enough for a workgroup each to pay.  A partition is a rank's whole run up to fan-outs of
-// ~1700 (*tb = 0); beyond, a run is cut into 2^tb partitions by the position of the payload in the payloads' range.
-static bool rank_runs_fit(const hmj_ctx* c, uint64_t n_build, uint64_t n_probe, int* tb, int* level) {
-  *tb = 0;
-  *level = 0;
-  if (!c->rank_runs_mode || !c->slab_mode || n_build < 4 || n_probe > 0xFFFFFFFFull ||
-      n_probe < (1u << 16))  // (a slab pass wants a few dozen tiles of rows)
-    return false;
-  const int rank_bits = 64 - __builtin_clzll(n_build - 1), max_bits = 2 * hmj::SLAB_MAX_BITS;
-  if (rank_bits < 2) return false;
-  const double f0 = (double)n_probe / (double)n_build;
-  if (f0 < 16.0) return false;
-  auto fits = [](double m, int lv) { return m + 8.0 * std::sqrt(m) + 24.0 <= (double)hmj::rank_sort_max_run(lv); };
-  if (rank_bits > max_bits) {
-    // more ranks than two slab passes tell apart: 2^gb consecutive ranks to a partition (*tb = -gb), sorted there by (rank's
-    // low bits, payload) as one word -- where 2^gb runs still fit one workgroup's sort
-    const int gb = rank_bits - max_bits;
-    if (gb > c->rank_runs_max_group) return false;
-    const double m = f0 * (double)(1u << gb);
-    int lv = c->rank_runs_wave ? -1 : 0;
-    while (lv <= c->rank_runs_max_level && !fits(m, lv)) lv++;
-    if (lv > c->rank_runs_max_level) return false;
-    *tb = -gb;
-    *level = lv;
-    return true;
-  }
-  // the smallest workgroup shape (the fastest: most sorters per CU) whose cut stays within two slab passes; the wave
-  // shape (level -1: 512 rows) only for whole runs -- cutting a run further to reach it would only add partitions
-  if (c->rank_runs_wave && fits(f0, -1)) {
-    *level = -1;
-    return true;
-  }
-  for (int lv = 0; lv <= c->rank_runs_max_level; lv++) {
-    double f = f0;
-    int t = 0;
-    while (!fits(f, lv)) {
-      f *= 0.5;
-      t++;
-    }
-    if (rank_bits + t > max_bits || t > c->rank_runs_max_cut) continue;
-    if (t > 0) {
-      // Payloads that grow with the row's position (row ids, timestamps): a worker of pass A reads `places` chunks from all
-      // over the probe side (radix.hip, slab_a_body's strided form), each inside ONE piece; the fullest of its slabs must
-      // still be within a slab's capacity (slab_geometry: mean + 8 sqrt(mean) + 24), or the attempt is known to overflow.
-      const int TB = rank_bits + t, ba = TB - TB / 2;
-      const double tile = ba > 8 ? 4096.0 : 2048.0, tiles = std::ceil((double)n_probe / tile), tpw = std::ceil(tiles / 2048.0);
-      const double rpw = tpw * tile, places = rpw / (double)hmj::RANK_PASS_CHUNK_ROWS, pieces = (double)(1u << t);
-      const double skew = places >= pieces ? std::ceil(places / pieces) / (places / pieces) : pieces / places;
-      const double mean = rpw / (double)(1u << ba);
-      if (skew * mean + 4.0 * std::sqrt(skew * mean) > mean + 8.0 * std::sqrt(mean) + 24.0) return false;
-    }
-    *tb = t;
-    *level = lv;
-    return true;
-  }
-  return false;
-}
-// (what a workload's memo says on top: the form rests after it gave up; cut runs exist only with the lookup inside pass A)
-static bool rank_runs_rested(const hmj_ctx* c, int tb) {
-  return c->wm->rank_runs_cooldown == 0 && (tb <= 0 || c->wm->rank_lookup_cooldown == 0);
+static SmallOrderedKnobs small_ordered_knobs(const hmj_ctx* c, const void* R, uint64_t n_build) {
+  SmallOrderedKnobs k;
+  k.available = c->gtable_mode && c->gtable_sort_mode && !c->prepare_only && c->force_bits < 0 && c->arrive_ev.empty() &&
+                !(c->prep.valid && c->prep.ptr == R && c->prep.n == (u32)n_build);
+  k.gtable_max_rows = c->gtable_max_rows;
+  k.gtable_sort_fanout = c->gtable_sort_fanout;
+  k.chain_mode = c->gtable_sort_slab && c->slab_mode;
+  k.gtable_sort_slab_min = c->gtable_sort_slab_min;
+  k.runs = rank_run_knobs(c);
+  return k;
 }
 
-int try_small_build_ordered(hmj_ctx* c, const void* R, uint64_t n_build, const void* S, uint64_t n_probe, uint32_t flags,
-                            hmj_result* out, bool to_host, bool* done) {
-  *done = false;
-  if (!c->gtable_mode || !c->gtable_sort_mode || !(flags & HMJ_ORDERED) || c->prepare_only || c->force_bits >= 0 ||
-      !c->arrive_ev.empty() || n_build == 0 || n_build > 16 * c->gtable_max_rows || n_probe > 0xFFFFFFFFull ||
-      n_probe < (uint64_t)c->gtable_sort_fanout * n_build ||
-      (c->prep.valid && c->prep.ptr == R && c->prep.n == (u32)n_build))
-    return HMJ_OK;
-  {
-    // Which is faster is a matter of fan-out AND size (profiles/r04i_*, r04l_*: both paths over a grid of sizes).  This path:
-    // ~0.65 ms of dependent launches and read-backs + 0.06-0.09 ns per probe row (below).  The
-    // partitioned one-pass ordered write: ~0.15 ms + (0.030 + 0.00023 f) ns per row up to fan-out ~200, 0.00041 f ns beyond
-    // (the plan changes), and from ~700 rows per key on it declines (runs beyond its capacity) and the write + order
-    // epilogue takes over at 0.25 ns per row and more.  HMJ_GTABLE_SORT_FANOUT=1 (the experiments) skips the model.
-    const double f = (double)n_probe / (double)n_build, rows = (double)n_probe * 1e-6;
-    // (later in round 4 the one-pass write learned to rank inside (build rank, payload position) buckets from fan-out 24 on:
-    //  0.043 ns per row up to fan-out ~130, + 0.0001 per further probe row per key -- 2^18 x 2^26: 7.5 -> 3.9 ms, 2^20 x 2^28:
-    //  29.3 -> 15.8 -- so this path is now for fan-outs beyond ~500 and for runs the kernel's partitions cannot hold)
-    const OrderedCostModel& m = c->ordered_model;
-    const double part_ns = ordered_part_ns(m, f, (double)n_probe);
-    // (round 4, later: 0.060 where the composites' passes are the chain of slab passes below, 0.072 on exact passes, + 0.02
-    //  where the table leaves the L2 -- profiles/r04p_side_rank_sort_slab_chain.txt)
-    const bool chain = c->gtable_sort_slab && c->slab_mode && c->wm->gtable_sort_slab_cooldown == 0 && n_probe >= c->gtable_sort_slab_min;
-    // (round 5: runs that fit one workgroup's LDS sort -- fan-out up to ~1700 -- are partitioned by rank with two slab passes
-    //  and sorted run by run, rank_runs_fit, whatever the payloads' width;
-    //  measured over 2^12 ... 2^18 build x 2^22 ... 2^28 probe rows, profiles/r05k_sweep_ordered_small_build.txt: 0.25 ms of
-    //  launches and read-backs + 0.0215 ns per probe row + 7.5 ns per RUN -- a workgroup's load -> sort -> store chain per key.
-    //  Longer runs are cut into 2^tb pieces by the position of the payload in the payloads' range.  Row ids and timestamps
-    //  are monotone in the row's POSITION, so a worker of a slab pass that reads one contiguous range of the probe side sees
-    //  one piece only and its slab for that digit overflows, whichever digit the piece bits go into: the pass with the
-    //  lookup reads 4 KiB chunks from all over the relation instead (radix.hip, RankXform::kStrided); + one pass over the
-    //  payloads for their range)
-    int run_tb = 0, run_level = 0;
-    const bool runs = rank_runs_fit(c, n_build, n_probe, &run_tb, &run_level) && rank_runs_rested(c, run_tb);
-    // (2^20 ... 2^21 build rows: the rank-run form only -- there for the joins whose fullest 18-bit partition outgrows the
-    //  one-pass ordered write: 2^21 x 2^29 rows took 166 ms on the exact path with the order epilogue, profiles/r05y_*)
-    const double P18 = (double)(1u << (2 * hmj::SLAB_MAX_BITS));
-    if (n_build > 8 * c->gtable_max_rows && (!runs || fk_probe_rows_hi((double)n_probe / P18, f, P18) <= 6144.0)) return HMJ_OK;
-    const double rank_ns = (chain ? m.comp_ns_chain : m.comp_ns_exact) + (n_build > c->gtable_max_rows ? m.comp_ns_beyond_l2 : 0.0);
-    const double n_parts = run_tb >= 0 ? (double)(n_build << run_tb) : (double)(n_build >> -run_tb);
-    const double lb = std::log2((double)n_build) - 14.0;
-    const bool wave = run_level < 0;
-    const double rank_ms = runs ? m.runs_fixed_ms + (m.runs_ns + (wave ? m.runs_wave_ns : 0.0) + (run_tb > 0 ? m.runs_range_ns : 0.0) +
-                                                    (lb > 0.0 ? lb * m.runs_ns_per_log2_build : 0.0)) * rows +
-                                      (wave ? m.runs_wave_ns_per_run : m.runs_ns_per_run) * n_parts * 1e-6
-                                : m.comp_fixed_ms + rank_ns * rows;
-    if (c->gtable_sort_fanout > 1 && rank_ms >= m.part_fixed_ms + part_ns * rows) {
-      c->plan.refused |= HMJ_REFUSED_RANK_SORT_MODEL;
-      return HMJ_OK;
-    }
-  }
-  if (c->wm->gtable_sort_cooldown > 0) {
-    c->wm->gtable_sort_cooldown--;
-    c->plan.refused |= HMJ_REFUSED_RANK_SORT_COOLING;
-    return HMJ_OK;
-  }
-  if (!out) return fail(c, HMJ_E_ARG, "out is NULL");
-  RC_TRY(check_rel(c, R, n_build, "build_aos is NULL"));
-  RC_TRY(check_rel(c, S, n_probe, "probe_aos is NULL"));
-  const u32 nb = (u32)n_build, np = (u32)n_probe;
-  const bool extra = flags & (HMJ_CHECKSUM | HMJ_SUM_PROBE);
-  c->prep.valid = false;  // rbuf is the build side's sort buffer
-  RC_TRY(ensure_dev(c, c->rbuf[0], (size_t)nb * 16));
-  RC_TRY(ensure_dev(c, c->rbuf[1], (size_t)nb * 16));
-  RC_TRY(ensure_dev(c, c->sbuf[0], (size_t)np * 16));
-  RC_TRY(ensure_dev(c, c->sbuf[1], (size_t)np * 16));
-  RC_TRY(ensure_dev(c, c->accum, 8 * sizeof(u64)));
-  RC_TRY(ensure_dev(c, c->offs64, 8 * sizeof(u64)));
-  RC_TRY(ensure_host(c, c->h_accum, 8 * sizeof(u64)));
-  u64* hh = (u64*)c->h_accum.p;
-  auto give_up = [&](const char* why) {
-    c->wm->gtable_sort_cooldown = 8;
-    c->plan.refused |= HMJ_REFUSED_RANK_SORT_GAVE_UP;
-    std::vector<Span> keep;  // forget the abandoned attempt's spans
-    for (const Span& s2 : c->spans)
-      if (s2.kind == K_TOTAL || s2.kind == K_H2D) keep.push_back(s2);
-    c->spans.swap(keep);
-    c->timing.path = 0;  // (only what this attempt set: its path bits and pass bytes)
-    c->timing.bytes_scatter = c->timing.bytes_hist = 0;
-    c->timing.n_scatter_launches = 0;
-    if (c->trace) std::fprintf(stderr, "[hmj] join nb=%u np=%u ordered: sort-by-rank path gave up (%s) -> partitioned path\n", nb, np, why);
-    return HMJ_OK;
-  };
-  // ---- 1. which 8-bit digits the build keys differ in, and -- for the composite form -- the range of the probe payloads
-  // (one read-back)
-  int run_tb = 0, run_level = 0;
-  bool use_runs = rank_runs_fit(c, n_build, n_probe, &run_tb, &run_level);
-  if (use_runs && !rank_runs_rested(c, run_tb)) {
+// the whole path gives up: the workload skips it for its next 8 joins, and nothing of the attempt stays in the timing
+static int give_up(hmj_ctx* c, const SmallOrdered& s, const char* why) {
+  c->wm->gtable_sort_cooldown = 8;
+  c->plan.refused |= HMJ_REFUSED_RANK_SORT_GAVE_UP;
+  drop_attempt_spans(c);
+  c->timing.path = 0;  // (only what this attempt set: its path bits and pass bytes)
+  c->timing.bytes_scatter = c->timing.bytes_hist = 0;
+  c->timing.n_scatter_launches = 0;
+  if (c->trace) std::fprintf(stderr, "[hmj] join nb=%u np=%u ordered: sort-by-rank path gave up (%s) -> partitioned path\n", s.nb, s.np, why);
+  return kPathGaveUp;
+}
+// one form gives way to the next: its spans and pass bytes go (timing.path stays as it is)
+static void drop_attempt(hmj_ctx* c) {
+  drop_attempt_spans(c);
+  c->timing.bytes_scatter = 0;
+}
+static void set_payload_range(SmallOrdered& s, u64 lo, u64 hi) {
+  s.svmin = lo;
+  s.svmax = hi;
+  s.range_bits = hi > lo ? 64 - __builtin_clzll(hi - lo) : 0;
+  // rank and payload in ONE word where they fit; else as two (payloads that are hashes, doubles, pointers): sorted by the
+  // payload's varying digits first, then stably by the rank -- up to 8 + 3 passes instead of 4-5, still well under the
+  // partitioned paths' run ranking at these fan-outs (a wide-payload join needs twice the fan-out to take this path)
+  s.wide = s.rank_bits + s.range_bits > 64;
+}
+
+// ---- 1. which 8-bit digits the build keys differ in, and -- for the composite form -- the range of the probe payloads
+// (one read-back)
+static int survey_keys_and_payloads(hmj_ctx* c, SmallOrdered& s) {
+  if (s.use_runs && !rank_runs_rested(c->wm->rank_runs_cooldown, c->wm->rank_lookup_cooldown, s.run_tb)) {
     if (c->wm->rank_runs_cooldown > 0)
       c->wm->rank_runs_cooldown--;
     else
       c->wm->rank_lookup_cooldown--;
-    use_runs = false;
+    s.use_runs = false;
   }
-  bool have_range = !use_runs;  // (the exact range; cut runs take a sample's: rows outside it go to the end pieces)
-  const u32 range_every = (use_runs && run_tb > 0 && np >= (1u << 18)) ? ((np >> 17) | 1u) : 1u;
-  {
-    const u64 init[5] = {0, ~0ull, 0, ~0ull, 0};
-    HIP_TRY(hipMemcpyAsync(c->offs64.p, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hmj::launch_key_exact(R, nb, nullptr, 0u, 0, (u64*)c->offs64.p, c->num_cus, c->stream, true));
-    if (have_range || (use_runs && run_tb > 0)) HIP_TRY(hmj::launch_sval_range(S, np, (u64*)c->offs64.p + 3, c->num_cus, c->stream, range_every));
-    HIP_TRY(hipMemcpyAsync(hh, c->offs64.p, 5 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+  s.have_range = !s.use_runs;  // (the exact range; cut runs take a sample's: rows outside it go to the end pieces)
+  const bool any_range = s.have_range || (s.use_runs && s.run_tb > 0);
+  s.range_every = (s.use_runs && s.run_tb > 0 && s.np >= (1u << 18)) ? ((s.np >> 17) | 1u) : 1u;
+  const u64 init[5] = {0, ~0ull, 0, ~0ull, 0};
+  HIP_TRY(hipMemcpyAsync(c->offs64.p, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hmj::launch_key_exact(s.R, s.nb, nullptr, 0u, 0, (u64*)c->offs64.p, c->num_cus, c->stream, true));
+  if (any_range) HIP_TRY(hmj::launch_sval_range(s.S, s.np, (u64*)c->offs64.p + 3, c->num_cus, c->stream, s.range_every));
+  HIP_TRY(hipMemcpyAsync(s.hh, c->offs64.p, 5 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  s.key_diff = s.hh[0];
+  s.have_range = s.have_range || (any_range && s.range_every == 1);
+  s.rank_bits = s.nb > 1 ? 32 - __builtin_clz(s.nb - 1) : 0;
+  set_payload_range(s, (s.np && any_range) ? s.hh[3] : 0, (s.np && any_range) ? s.hh[4] : 0);
+  // (the cost model again, for two-word composites; no refused bit, and nothing of the timing to clean yet)
+  if (s.wide && !s.use_runs && c->gtable_sort_fanout > 1 && wide_composites_refused(c->ordered_model, s.n_probe, s.part_ns)) {
+    c->wm->gtable_sort_cooldown = 8;
+    return kPathGaveUp;
   }
-  const u64 key_diff = hh[0];
-  const bool any_range = have_range || (use_runs && run_tb > 0);
-  u64 svmin = (np && any_range) ? hh[3] : 0, svmax = (np && any_range) ? hh[4] : 0;
-  have_range = have_range || (any_range && range_every == 1);
-  int range_bits = svmax > svmin ? 64 - __builtin_clzll(svmax - svmin) : 0;
-  const int rank_bits = nb > 1 ? 32 - __builtin_clz(nb - 1) : 0;
-  // rank and payload in ONE word where they fit; else as two (payloads that are hashes, doubles, pointers): sorted by the
-  // payload's varying digits first, then stably by the rank -- up to 8 + 3 passes instead of 4-5, still well under the
-  // partitioned paths' run ranking at these fan-outs (a wide-payload join needs twice the fan-out to take this path)
-  bool wide = rank_bits + range_bits > 64;
-  if (wide && !use_runs && c->gtable_sort_fanout > 1) {  // (ten passes instead of four or five: about 1.6 x the time per row; the rank-run form does not care)
-    const double f = (double)n_probe / (double)n_build, rows = (double)n_probe * 1e-6;
-    const OrderedCostModel& m = c->ordered_model;
-    const double part_ns = ordered_part_ns(m, f, (double)n_probe);
-    if (m.comp_fixed_ms + m.comp_ns_wide * rows >= m.part_fixed_ms + part_ns * rows) {
-      c->wm->gtable_sort_cooldown = 8;
-      return HMJ_OK;
-    }
-  }
-  if (nb > 1 && key_diff == 0) return give_up("duplicate build keys");
-  // ---- 2. the build side in key order.  MSD: ONE exact pass on the top varying key bits -- partitions of ~512 rows -- and a
-  // stable LDS sort of every partition on the rest (gtable.hip, sort_runs_write_kernel on dense partitions): 4 launches
-  // instead of the 24 of eight LSD passes, which were 0.3 of the 2.4 ms of a 2^16 x 2^26-row join (profiles/r05u_small16_ord_*).
-  // Keys crowded into few partitions or clustered inside one raise ERR_FASTPATH (one 8-byte read-back): the LSD passes run.
-  const void* sortedR = R;
-  bool build_sorted = false;
-  if (c->build_sort_msd && key_diff != 0 && nb >= 2) {
-    const int hb = 63 - __builtin_clzll(key_diff);
+  if (s.nb > 1 && s.key_diff == 0) return give_up(c, s, "duplicate build keys");
+  return HMJ_OK;
+}
+
+// ---- 2. the build side in key order.  MSD: ONE exact pass on the top varying key bits -- partitions of ~512 rows -- and a
+// stable LDS sort of every partition on the rest (gtable.hip, sort_runs_write_kernel on dense partitions): 4 launches
+// instead of the 24 of eight LSD passes, which were 0.3 of the 2.4 ms of a 2^16 x 2^26-row join (profiles/r05u_small16_ord_*).
+// Keys crowded into few partitions or clustered inside one raise ERR_FASTPATH (one 8-byte read-back): the LSD passes run.
+static int sort_build_side(hmj_ctx* c, SmallOrdered& s) {
+  const u32 nb = s.nb;
+  s.sortedR = s.R;
+  if (c->build_sort_msd && s.key_diff != 0 && nb >= 2) {
+    const int hb = 63 - __builtin_clzll(s.key_diff);
     int h = 0;
     while (h < hmj::RP_MAX_BITS && ((u64)nb >> h) > 512) h++;
     if (h > hb + 1) h = hb + 1;
-    const double mean = (double)nb / (double)(1u << h);
-    int level = 0;
-    while (level < 2 && mean + 8.0 * std::sqrt(mean) + 24.0 > (double)hmj::rank_sort_max_run(level)) level++;
-    if (mean + 8.0 * std::sqrt(mean) + 24.0 <= (double)hmj::rank_sort_max_run(level)) {
+    const int level = lds_sort_level((double)nb / (double)(1u << h), 0, 2, c->lds_sort.max_run);
+    if (level <= 2) {
       const u32 P = 1u << h;
       RC_TRY(ensure_dev(c, c->msd_off, ((size_t)P + 1) * 8));
       HIP_TRY(hipMemsetAsync(c->accum.p, 0, 8 * sizeof(u64), c->stream));
-      const void* parted = R;
+      const void* parted = s.R;
       if (h > 0) {
-        RC_TRY(radix_pass(c, R, c->rbuf[0].p, nb, hb + 1 - h, h, 0, (u64*)c->msd_off.p, 0));
+        RC_TRY(radix_pass(c, s.R, c->rbuf[0].p, nb, hb + 1 - h, h, 0, (u64*)c->msd_off.p, 0));
         parted = c->rbuf[0].p;
       } else {
         const u64 off01[2] = {0, nb};
@@ -2388,286 +2346,311 @@ int try_small_build_ordered(hmj_ctx* c, const void* R, uint64_t n_build, const v
       HIP_TRY(hmj::launch_sort_runs_write(parted, nullptr, 0, P, (const u64*)c->msd_off.p, c->rbuf[1].p, (u64*)c->accum.p, level, c->num_cus,
                                           c->stream));
       span_end(c, so);
-      HIP_TRY(hipMemcpyAsync(hh, (u64*)c->accum.p + hmj::ACC_ERR, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipMemcpyAsync(s.hh, (u64*)c->accum.p + hmj::ACC_ERR, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
       HIP_TRY(hipStreamSynchronize(c->stream));
-      if (!(hh[0] & hmj::ERR_FASTPATH)) {
-        sortedR = c->rbuf[1].p;
-        build_sorted = true;
+      if (!(s.hh[0] & hmj::ERR_FASTPATH)) {
+        s.sortedR = c->rbuf[1].p;
+        return HMJ_OK;
       }
     }
   }
-  if (!build_sorted) {
-    u32 digits = 0;
-    for (int i = 0; i < 8; i++) digits |= ((key_diff >> (8 * i)) & 0xFFu) ? (1u << i) : 0u;
-    int k = 0;
-    for (int d = 0; d < 8; d++) {
-      if (!(digits & (1u << d))) continue;
-      void* dst = c->rbuf[k & 1].p;
-      RC_TRY(radix_pass(c, sortedR, dst, nb, 8 * d, 8, 0, nullptr, k ? 1 : 0));
-      sortedR = dst;
-      k++;
-    }
+  // LSD passes on the digits that vary, from R again (not from the partitioned copy in rbuf[0])
+  const u32 digits = varying_digits(s.key_diff);
+  int k = 0;
+  for (int d = 0; d < 8; d++) {
+    if (!(digits & (1u << d))) continue;
+    void* dst = c->rbuf[k & 1].p;
+    RC_TRY(radix_pass(c, s.sortedR, dst, nb, 8 * d, 8, 0, nullptr, k ? 1 : 0));
+    s.sortedR = dst;
+    k++;
   }
-  // ---- 3. key -> rank
+  return HMJ_OK;
+}
+
+// ---- 3. key -> rank.  The K_PROBE_COUNT span opened here closes right after the build where pass A does the lookup, and
+// after the emit on the emit routes.
+static int build_rank_table(hmj_ctx* c, SmallOrdered& s) {
+  const u32 nb = s.nb;
   int log_cap = 10;
   while (((u64)1 << log_cap) < (u64)c->gtable_slots_per_row * nb) log_cap++;
   while (log_cap > c->gtable_max_log_cap && ((u64)1 << (log_cap - 1)) >= (nb > c->gtable_max_rows ? 2 : 4) * (u64)nb) log_cap--;
+  s.log_cap = log_cap;
   const size_t tab_bytes = (size_t)16 << log_cap;
   RC_TRY(ensure_dev(c, c->gtab, tab_bytes));
   HIP_TRY(hipMemsetAsync(c->accum.p, 0, 8 * sizeof(u64), c->stream));
   HIP_TRY(hipMemsetAsync(c->gtab.p, 0xFF, tab_bytes, c->stream));
-  int sp = span_begin(c, K_PROBE_COUNT, -1);
-  HIP_TRY(hmj::launch_gtable_build(sortedR, nb, c->gtab.p, log_cap, (u64*)c->accum.p, true, c->num_cus, c->stream));
-  // ---- 4a. the rank-run form: {rank, sval} rows, two slab passes on the rank's digits, every rank's run sorted in LDS and
-  // written at its offset (gtable.hip).  First with the rank lookup INSIDE pass A (radix.hip, radix_slab_a_rank_kernel: the
-  // probe rows are read once, nothing is emitted in between); a probe row without its build row cannot be dropped from the
-  // middle of a tile there, so that attempt gives way to emit + pass A.  A slab that overflows or a run beyond the kernel
-  // (a hot foreign key) leaves the table as it is; the composite form below starts over from the emit, and the workload
-  // skips what gave up for its next 8 joins.
-  bool runs_done = false;
-  u64 n = 0;
-  if (use_runs) {
-    // the partition number: rank << tb | piece of the run (hmj_dev.h, rank_run_bucket); tb < 0: rank >> -tb
-    const int TB = rank_bits + run_tb, gb = run_tb < 0 ? -run_tb : 0, cut = run_tb > 0 ? run_tb : 0;
-    const int bb = TB / 2, ba = TB - bb;  // LSD: pass A on the low digit, pass B on the high one
-    const u32 P = 1u << TB;
-    const int pre = range_bits > 32 ? range_bits - 32 : 0;
-    const u64 mult = cut ? ((u64)1 << (cut + 32)) / (((svmax - svmin) >> pre) + 1) : 0;
-    u64* acc = (u64*)c->accum.p;
-    const char* why = "";
-    // rows -> partitions (fused: straight from the probe rows) -> offsets -> sorted runs; 0 ok, 1 gave up, < 0 error
-    auto passes = [&](u64 rows, bool fused) -> int {
-      hmj::SlabGeom g;
-      if (rows == 0 || !hmj::slab_geometry((u32)rows, ba, bb, &g, 0, 1.0, (double)(1u << rank_bits) / (double)nb)) {
-        why = "no slab geometry";
-        return 1;
-      }
-      int r2;
-      if ((r2 = ensure_dev(c, c->slab_a, g.rows_a * 16)) != HMJ_OK) return r2;
-      if ((r2 = ensure_dev(c, c->cnt_a, ((size_t)g.WA << ba) * 4)) != HMJ_OK) return r2;
-      if ((r2 = ensure_dev(c, c->slab_bs, g.rows_b * 16)) != HMJ_OK) return r2;
-      if ((r2 = ensure_dev(c, c->cnt_bs, (size_t)P * g.KB * 4)) != HMJ_OK) return r2;
-      if ((r2 = ensure_dev(c, c->part_out_off, ((size_t)P + 1) * 8)) != HMJ_OK) return r2;
-      if ((r2 = ensure_dev(c, c->part_count, ((size_t)P / 1024 + 1) * 8)) != HMJ_OK) return r2;  // (chunk totals of the offsets scan)
-      const size_t bytes = (size_t)rows * 8;
-      if ((r2 = ensure_dev(c, c->out_key, bytes)) != HMJ_OK) return r2;
-      if ((r2 = ensure_dev(c, c->out_rval, bytes)) != HMJ_OK) return r2;
-      if ((r2 = ensure_dev(c, c->out_sval, bytes)) != HMJ_OK) return r2;
-      auto launch = [&](hipError_t e, const char* what) { return e == hipSuccess ? HMJ_OK : fail(c, HMJ_E_HIP, what, e); };
-      int s2 = span_begin(c, K_SCATTER, 1, 0);
-      if (fused)
-        r2 = launch(hmj::launch_slab_a_ranks(S, np, gb, ba, g, c->slab_a.p, c->slab_a.cap / 16, (u32*)c->cnt_a.p, c->cnt_a.cap / 4, acc, c->gtab.p,
-                                             log_cap, extra, cut, svmin, svmax - svmin, pre, mult, c->stream), "launch_slab_a_ranks");
-      else
-        r2 = launch(hmj::launch_slab_a(c->sbuf[0].p, (u32)rows, gb, ba, g, c->slab_a.p, c->slab_a.cap / 16, (u32*)c->cnt_a.p, c->cnt_a.cap / 4,
-                                       acc, c->stream), "launch_slab_a");
-      span_end(c, s2);
-      if (r2 != HMJ_OK) return r2;
-      s2 = span_begin(c, K_SCATTER, 1, 1);
-      r2 = launch(hmj::launch_slab_b(c->slab_a.p, (const u32*)c->cnt_a.p, ba, gb + ba, bb, g, c->slab_bs.p, c->slab_bs.cap / 16, (u32*)c->cnt_bs.p,
-                                     c->cnt_bs.cap / 4, acc, c->stream), "launch_slab_b");
-      span_end(c, s2);
-      if (r2 != HMJ_OK) return r2;
-      s2 = span_begin(c, K_OUT_SCAN, -1);
-      r2 = launch(hmj::launch_slab_offsets((const u32*)c->cnt_bs.p, P, (u64*)c->part_out_off.p, (u64*)c->part_count.p, c->stream), "launch_slab_offsets");
-      span_end(c, s2);
-      if (r2 != HMJ_OK) return r2;
-      s2 = span_begin(c, K_PROBE_WRITE, -1);
-      r2 = launch(hmj::launch_rank_sort_write(c->slab_bs.p, (const u32*)c->cnt_bs.p, g.CB, P, (const u64*)c->part_out_off.p, sortedR, nb,
-                                              run_tb, (u64*)c->out_key.p, (u64*)c->out_rval.p, (u64*)c->out_sval.p, acc, extra, run_level, c->num_cus, c->stream),
-                  "launch_rank_sort_write");
-      span_end(c, s2);
-      if (r2 != HMJ_OK) return r2;
-      RC_TRY(read_accum(c, &hh));
-      if (hh[hmj::ACC_ERR] & hmj::ERR_GTABLE) return 2;
-      if (hh[hmj::ACC_PAD] != 0) return 3;
-      if (hh[hmj::ACC_ERR] & (hmj::ERR_SLAB | hmj::ERR_FASTPATH)) {
-        why = (hh[hmj::ACC_ERR] & hmj::ERR_SLAB) ? "a slab overflowed" : fused ? "a probe row without its build row, or a run beyond the kernel" : "a run beyond the kernel";
-        return 1;
-      }
-      c->timing.bytes_scatter += 2 * 32ull * rows - (fused ? 16ull * rows : 0ull);
-      c->timing.path |= HMJ_PATH_SLAB | HMJ_PATH_RANK_RUNS | (fused ? HMJ_PATH_RANK_LOOKUP_IN_PASS : 0u);
-      c->timing.radix_bits = TB;
-      c->timing.radix_passes = 2;
-      return 0;
-    };
-    auto drop_attempt = [&]() {
-      std::vector<Span> keep;
-      for (const Span& s3 : c->spans)
-        if (s3.kind == K_TOTAL || s3.kind == K_H2D) keep.push_back(s3);
-      c->spans.swap(keep);
-      c->timing.bytes_scatter = 0;
-    };
-    int st = 1;
-    if (c->wm->rank_lookup_cooldown > 0) {
-      c->wm->rank_lookup_cooldown--;
-    } else {
-      span_end(c, sp);  // (the table build)
-      st = passes(np, true);
-      if (st < 0) return st;
-      if (st == 2) return give_up("the table gave up");
-      if (st == 3) return give_up("duplicate build keys");
-      if (st == 1) {
-        c->wm->rank_lookup_cooldown = 8;
-        if (c->trace) std::fprintf(stderr, "[hmj] join nb=%u np=%u ordered: rank lookup inside pass A gave up (%s) -> emit + pass A\n", nb, np, why);
-        drop_attempt();
-        // (the table stays; the accumulators start over, with the build kernel's verdict -- no duplicates, no give-up -- known)
-        HIP_TRY(hipMemsetAsync(c->accum.p, 0, 8 * sizeof(u64), c->stream));
-        sp = span_begin(c, K_PROBE_COUNT, -1);
-      } else {
-        n = hh[hmj::ACC_N];
-        runs_done = true;
-      }
-    }
-    if (!runs_done && run_tb <= 0) {  // (cut runs: the emit below writes ranks, not partition numbers -- on to the composites)
-      HIP_TRY(hmj::launch_gtable_emit_ranks(S, np, c->gtab.p, log_cap, (u64*)c->accum.p, c->sbuf[0].p, extra, c->num_cus, c->gtable_wg_per_cu, c->stream));
-      span_end(c, sp);
-      RC_TRY(read_accum(c, &hh));
-      if (hh[hmj::ACC_ERR] & hmj::ERR_GTABLE) return give_up("the table gave up");
-      if (hh[hmj::ACC_PAD] != 0) return give_up("duplicate build keys");
-      n = hh[hmj::ACC_N];
-      if (n == 0) {
-        runs_done = true;  // no probe row matched: an empty result
-      } else {
-        st = passes(n, false);
-        if (st < 0) return st;
-        runs_done = st == 0;
-      }
-    }
-    if (!runs_done) {
-      // start over on the composite form: the table stays, the accumulators and the emit are redone with the payload range
-      c->wm->rank_runs_cooldown = 8;
-      if (c->trace) std::fprintf(stderr, "[hmj] join nb=%u np=%u ordered: rank-run form gave up (%s) -> composite sort\n", nb, np, why);
-      drop_attempt();
-      use_runs = false;
-      if (!have_range) {
-        const u64 init2[2] = {~0ull, 0};
-        HIP_TRY(hipMemcpyAsync((u64*)c->offs64.p + 3, init2, sizeof(init2), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hmj::launch_sval_range(S, np, (u64*)c->offs64.p + 3, c->num_cus, c->stream));
-        HIP_TRY(hipMemcpyAsync(hh, (u64*)c->offs64.p + 3, 2 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        svmin = np ? hh[0] : 0;
-        svmax = np ? hh[1] : 0;
-        range_bits = svmax > svmin ? 64 - __builtin_clzll(svmax - svmin) : 0;
-        wide = rank_bits + range_bits > 64;
-        have_range = true;
-      }
-      HIP_TRY(hipMemsetAsync(c->accum.p, 0, 8 * sizeof(u64), c->stream));
-      sp = span_begin(c, K_PROBE_COUNT, -1);
-    }
+  s.sp = span_begin(c, K_PROBE_COUNT, -1);
+  HIP_TRY(hmj::launch_gtable_build(s.sortedR, nb, c->gtab.p, log_cap, (u64*)c->accum.p, true, c->num_cus, c->stream));
+  return HMJ_OK;
+}
+
+// rows -> partitions (fused: straight from the probe rows, the rank lookup inside pass A; else from the emitted {rank, sval}
+// rows in sbuf[0]) -> offsets -> sorted runs, one read-back.  The partition number: rank << tb | piece of the run (hmj_dev.h,
+// rank_run_bucket); tb < 0: rank >> -tb.  A RunPasses code, or an error.
+static int rank_run_passes(hmj_ctx* c, SmallOrdered& s, u64 rows, bool fused) {
+  const int TB = s.rank_bits + s.run_tb, gb = s.run_tb < 0 ? -s.run_tb : 0, cut = s.run_tb > 0 ? s.run_tb : 0;
+  const int bb = TB / 2, ba = TB - bb;  // LSD: pass A on the low digit, pass B on the high one
+  const int pre = s.range_bits > 32 ? s.range_bits - 32 : 0;
+  const RankLookup lookup = {s.log_cap, cut, pre, s.extra, s.svmin, s.svmax - s.svmin, cut ? ((u64)1 << (cut + 32)) / (((s.svmax - s.svmin) >> pre) + 1) : 0};
+  hmj::SlabGeom g;
+  if (rows == 0 || !hmj::slab_geometry((u32)rows, ba, bb, &g, 0, 1.0, (double)(1u << s.rank_bits) / (double)s.nb)) {
+    s.why = "no slab geometry";
+    return kRunsGaveUp;
   }
-  int which = 0, n_passes = 0;  // `sorted` lies in sbuf[which]
-  u32 pc_n = 0, pc_cap = 0;  // the sorted composites as pieces (pc_n != 0): c->slab_* / c->cnt_* [pc_which]
-  int pc_which = 0;
-  const void* sorted = c->sbuf[0].p;
-  if (!runs_done) {
-  // ---- 4. one composite per matching probe row
-  HIP_TRY(hmj::launch_gtable_emit(S, np, c->gtab.p, log_cap, svmin, range_bits, (u64*)c->accum.p, c->sbuf[0].p, extra, wide,
-                                  c->num_cus, c->gtable_wg_per_cu, c->stream));
+  RC_TRY(msd_partition(c, fused ? s.S : c->sbuf[0].p, fused ? s.np : (u32)rows, gb, ba, bb, g, 1, true, (size_t)rows, fused ? &lookup : nullptr));
+  const int sp = span_begin(c, K_PROBE_WRITE, -1);
+  const hipError_t e = hmj::launch_rank_sort_write(c->slab_bs.p, (const u32*)c->cnt_bs.p, g.CB, 1u << TB, (const u64*)c->part_out_off.p, s.sortedR, s.nb,
+                                                   s.run_tb, (u64*)c->out_key.p, (u64*)c->out_rval.p, (u64*)c->out_sval.p, (u64*)c->accum.p, s.extra,
+                                                   s.run_level, c->num_cus, c->stream);
   span_end(c, sp);
-  RC_TRY(read_accum(c, &hh));
-  if (hh[hmj::ACC_ERR] & hmj::ERR_GTABLE) return give_up("the table gave up");
-  if (hh[hmj::ACC_PAD] != 0) return give_up("duplicate build keys");
-  n = hh[hmj::ACC_N];
-  // ---- 5. sort the composites: only their rank_bits + range_bits low bits differ
-  auto lsd = [&](int total) -> int {  // stable LSD passes over the key word's bits [0, total), 9-bit digits at most
-    if (total <= 0 || n <= 1) return HMJ_OK;
-    const int passes = (total + hmj::RP_MAX_BITS - 1) / hmj::RP_MAX_BITS;
-    int shift = 0;
-    for (int i = 0; i < passes; i++) {
-      const int bits = total / passes + (i < total % passes ? 1 : 0);
-      void* dst = c->sbuf[which ^ 1].p;
-      const int r2 = radix_pass(c, sorted, dst, (u32)n, shift, bits, 1, nullptr, n_passes ? 1 : 0);
-      if (r2 != HMJ_OK) return r2;
-      sorted = dst;
-      which ^= 1;
-      shift += bits;
-      n_passes++;
-    }
+  RC_TRY(launched(c, e, "launch_rank_sort_write"));
+  RC_TRY(read_accum(c, &s.hh));
+  if (s.hh[hmj::ACC_ERR] & hmj::ERR_GTABLE) return kRunsTableGaveUp;
+  if (s.hh[hmj::ACC_PAD] != 0) return kRunsDuplicateKeys;
+  if (s.hh[hmj::ACC_ERR] & (hmj::ERR_SLAB | hmj::ERR_FASTPATH)) {
+    s.why = (s.hh[hmj::ACC_ERR] & hmj::ERR_SLAB) ? "a slab overflowed" : fused ? "a probe row without its build row, or a run beyond the kernel" : "a run beyond the kernel";
+    return kRunsGaveUp;
+  }
+  c->timing.bytes_scatter += 2 * 32ull * rows - (fused ? 16ull * rows : 0ull);
+  c->timing.path |= HMJ_PATH_SLAB | HMJ_PATH_RANK_RUNS | (fused ? HMJ_PATH_RANK_LOOKUP_IN_PASS : 0u);
+  c->timing.radix_bits = TB;
+  c->timing.radix_passes = 2;
+  return kRunsDone;
+}
+// the rank lookup INSIDE pass A (radix.hip, radix_slab_a_rank_kernel: the probe rows are read once, nothing is emitted in
+// between); a probe row without its build row cannot be dropped from the middle of a tile there, so the attempt gives way to
+// emit + pass A: the table stays, the accumulators start over, with the build kernel's verdict -- no duplicates, no give-up -- known
+static int rank_runs_fused(hmj_ctx* c, SmallOrdered& s) {
+  span_end(c, s.sp);  // (the table build)
+  const int st = rank_run_passes(c, s, s.np, true);
+  if (st < 0) return st;
+  if (st == kRunsTableGaveUp) return give_up(c, s, "the table gave up");
+  if (st == kRunsDuplicateKeys) return give_up(c, s, "duplicate build keys");
+  if (st == kRunsDone) {
+    s.n = s.hh[hmj::ACC_N];
+    s.runs_done = true;
     return HMJ_OK;
-  };
-  // The narrow form's passes as a chain of histogram-free slab passes (slab_chain above): 32 instead of 48 B per row and pass,
-  // the last pass's pieces expanded in place (gtable_expand_pieces_kernel).  The digits that hold the payload range's and the
-  // rank's top bits are sized for how much of their range is in use.  An overflow (skewed payload bits, a hot key): the exact
-  // passes run from the dense composites, which the chain has not touched, and the chain is left alone for the next 8 such joins.
-  if (c->wm->gtable_sort_slab_cooldown > 0 && !wide) c->wm->gtable_sort_slab_cooldown--;
-  else if (!wide && c->slab_mode && c->gtable_sort_slab && n >= c->gtable_sort_slab_min && rank_bits + range_bits > 0) {
-    const int total = rank_bits + range_bits;
-    const int passes = (total + hmj::RP_MAX_BITS - 1) / hmj::RP_MAX_BITS;
-    const double dens_range = range_bits ? std::ldexp(1.0, range_bits) / ((double)(svmax - svmin) + 1.0) : 1.0;
-    const double dens_rank = rank_bits ? std::ldexp(1.0, rank_bits) / (double)nb : 1.0;
+  }
+  c->wm->rank_lookup_cooldown = 8;
+  if (c->trace) std::fprintf(stderr, "[hmj] join nb=%u np=%u ordered: rank lookup inside pass A gave up (%s) -> emit + pass A\n", s.nb, s.np, s.why);
+  drop_attempt(c);
+  HIP_TRY(hipMemsetAsync(c->accum.p, 0, 8 * sizeof(u64), c->stream));
+  s.sp = span_begin(c, K_PROBE_COUNT, -1);
+  return HMJ_OK;
+}
+// emit + pass A: {rank, sval} rows of the matching probe rows into sbuf[0], then the passes over those
+static int rank_runs_from_emit(hmj_ctx* c, SmallOrdered& s) {
+  HIP_TRY(hmj::launch_gtable_emit_ranks(s.S, s.np, c->gtab.p, s.log_cap, (u64*)c->accum.p, c->sbuf[0].p, s.extra, c->num_cus, c->gtable_wg_per_cu, c->stream));
+  span_end(c, s.sp);
+  RC_TRY(read_accum(c, &s.hh));
+  if (s.hh[hmj::ACC_ERR] & hmj::ERR_GTABLE) return give_up(c, s, "the table gave up");
+  if (s.hh[hmj::ACC_PAD] != 0) return give_up(c, s, "duplicate build keys");
+  s.n = s.hh[hmj::ACC_N];
+  if (s.n == 0) {
+    s.runs_done = true;  // no probe row matched: an empty result
+    return HMJ_OK;
+  }
+  const int st = rank_run_passes(c, s, s.n, false);
+  if (st < 0) return st;
+  s.runs_done = st == kRunsDone;
+  return HMJ_OK;
+}
+// start over on the composite form: the table stays, the accumulators and the emit are redone with the payload range (read
+// now where only a sample's was known: a second synchronise; the wide-payload model test is not repeated)
+static int hand_over_to_composites(hmj_ctx* c, SmallOrdered& s) {
+  c->wm->rank_runs_cooldown = 8;
+  if (c->trace) std::fprintf(stderr, "[hmj] join nb=%u np=%u ordered: rank-run form gave up (%s) -> composite sort\n", s.nb, s.np, s.why);
+  drop_attempt(c);
+  s.use_runs = false;
+  if (!s.have_range) {
+    const u64 init2[2] = {~0ull, 0};
+    HIP_TRY(hipMemcpyAsync((u64*)c->offs64.p + 3, init2, sizeof(init2), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hmj::launch_sval_range(s.S, s.np, (u64*)c->offs64.p + 3, c->num_cus, c->stream));
+    HIP_TRY(hipMemcpyAsync(s.hh, (u64*)c->offs64.p + 3, 2 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    set_payload_range(s, s.np ? s.hh[0] : 0, s.np ? s.hh[1] : 0);
+    s.have_range = true;
+  }
+  HIP_TRY(hipMemsetAsync(c->accum.p, 0, 8 * sizeof(u64), c->stream));
+  s.sp = span_begin(c, K_PROBE_COUNT, -1);
+  return HMJ_OK;
+}
+// ---- 4a. the rank-run form: {rank, sval} rows, two slab passes on the rank's digits, every rank's run sorted in LDS and
+// written at its offset (gtable.hip).  First with the rank lookup inside pass A, then -- whole runs only: cut runs need the
+// partition number, and the emit writes ranks -- by emit + pass A.  A slab that overflows or a run beyond the kernel (a hot
+// foreign key) leaves the table as it is; the composite form starts over from the emit, and the workload skips what gave up
+// for its next 8 joins.  HMJ_OK: s.runs_done, or the composites are next.
+static int try_rank_runs(hmj_ctx* c, SmallOrdered& s) {
+  s.why = "";
+  if (c->wm->rank_lookup_cooldown > 0)
+    c->wm->rank_lookup_cooldown--;
+  else
+    RC_TRY(rank_runs_fused(c, s));
+  if (!s.runs_done && s.run_tb <= 0) RC_TRY(rank_runs_from_emit(c, s));
+  if (!s.runs_done) RC_TRY(hand_over_to_composites(c, s));
+  return HMJ_OK;
+}
+
+// ---- 4. one composite per matching probe row
+static int emit_composites(hmj_ctx* c, SmallOrdered& s) {
+  HIP_TRY(hmj::launch_gtable_emit(s.S, s.np, c->gtab.p, s.log_cap, s.svmin, s.range_bits, (u64*)c->accum.p, c->sbuf[0].p, s.extra, s.wide,
+                                  c->num_cus, c->gtable_wg_per_cu, c->stream));
+  span_end(c, s.sp);
+  RC_TRY(read_accum(c, &s.hh));
+  if (s.hh[hmj::ACC_ERR] & hmj::ERR_GTABLE) return give_up(c, s, "the table gave up");
+  if (s.hh[hmj::ACC_PAD] != 0) return give_up(c, s, "duplicate build keys");
+  s.n = s.hh[hmj::ACC_N];
+  return HMJ_OK;
+}
+// stable LSD passes over the key word's bits [0, total), 9-bit digits at most: sbuf[which] -> sbuf[which ^ 1] and back
+static int composite_lsd_passes(hmj_ctx* c, SmallOrdered& s, int total) {
+  if (total <= 0 || s.n <= 1) return HMJ_OK;
+  const int passes = lsd_passes(total, hmj::RP_MAX_BITS);
+  int shift = 0;
+  for (int i = 0; i < passes; i++) {
+    const int bits = lsd_digit_bits(total, passes, i);
+    void* dst = c->sbuf[s.which ^ 1].p;
+    RC_TRY(radix_pass(c, s.sorted, dst, (u32)s.n, shift, bits, 1, nullptr, s.n_passes ? 1 : 0));
+    s.sorted = dst;
+    s.which ^= 1;
+    shift += bits;
+    s.n_passes++;
+  }
+  return HMJ_OK;
+}
+// ---- 5. sort the composites: only their rank_bits + range_bits low bits differ.
+// The narrow form's passes as a chain of histogram-free slab passes (slab_chain above): 32 instead of 48 B per row and pass,
+// the last pass's pieces expanded in place (gtable_expand_pieces_kernel).  The digits that hold the payload range's and the
+// rank's top bits are sized for how much of their range is in use.  An overflow (skewed payload bits, a hot key): the exact
+// passes run from the dense composites, which the chain has not touched, and the chain is left alone for the next 8 such joins.
+static int sort_composites(hmj_ctx* c, SmallOrdered& s) {
+  s.which = s.n_passes = 0;
+  s.sorted = c->sbuf[0].p;
+  if (c->wm->gtable_sort_slab_cooldown > 0 && !s.wide) c->wm->gtable_sort_slab_cooldown--;
+  else if (!s.wide && c->slab_mode && c->gtable_sort_slab && s.n >= c->gtable_sort_slab_min && s.rank_bits + s.range_bits > 0) {
     ChainDigit dg[8];
-    int shift = 0;
-    for (int i = 0; i < passes; i++) {
-      dg[i].shift = shift;
-      dg[i].bits = total / passes + (i < total % passes ? 1 : 0);
-      dg[i].dens = 1.0;
-      if (range_bits && shift <= range_bits - 1 && range_bits - 1 < shift + dg[i].bits) dg[i].dens *= dens_range;
-      if (rank_bits && i == passes - 1) dg[i].dens *= dens_rank;
-      shift += dg[i].bits;
-    }
+    const int passes = composite_chain_digits(s.rank_bits, s.range_bits, s.svmin, s.svmax, s.nb, hmj::RP_MAX_BITS, dg);
     bool ok = false;
-    RC_TRY(slab_chain(c, c->sbuf[0].p, (u32)n, dg, passes, 1, &ok, &pc_n, &pc_cap, &pc_which));
+    RC_TRY(slab_chain(c, c->sbuf[0].p, (u32)s.n, dg, passes, 1, &ok, &s.pc.n, &s.pc.cap, &s.pc.which));
     if (ok) {
-      n_passes = passes;
+      s.n_passes = passes;
       c->timing.path |= HMJ_PATH_SLAB;
     } else {
       c->wm->gtable_sort_slab_cooldown = 8;
-      if (c->trace) std::fprintf(stderr, "[hmj] join nb=%u np=%u ordered: a slab of the composite sort's chain overflowed -> exact passes\n", nb, np);
+      if (c->trace) std::fprintf(stderr, "[hmj] join nb=%u np=%u ordered: a slab of the composite sort's chain overflowed -> exact passes\n", s.nb, s.np);
     }
   }
-  if (pc_n) {
-    // (sorted: the pieces of the chain's last pass)
-  } else if (!wide) {
-    RC_TRY(lsd(rank_bits + range_bits));
+  if (s.pc.n) return HMJ_OK;  // (sorted: the pieces of the chain's last pass)
+  if (!s.wide) return composite_lsd_passes(c, s, s.rank_bits + s.range_bits);
+  RC_TRY(composite_lsd_passes(c, s, s.range_bits));  // {payload, rank} by payload
+  if (s.n) {
+    HIP_TRY(hmj::launch_gtable_swap(s.sorted, c->sbuf[s.which ^ 1].p, s.n, c->num_cus, c->stream));  // -> {rank, payload}
+    s.sorted = c->sbuf[s.which ^ 1].p;
+    s.which ^= 1;
+  }
+  return composite_lsd_passes(c, s, s.rank_bits);  // stably by rank
+}
+// ---- 6. composites -> result rows
+static int expand_composites(hmj_ctx* c, SmallOrdered& s) {
+  if (!s.n) return HMJ_OK;
+  const size_t bytes = (size_t)s.n * 8;
+  RC_TRY(ensure_dev(c, c->out_key, bytes));
+  RC_TRY(ensure_dev(c, c->out_rval, bytes));
+  RC_TRY(ensure_dev(c, c->out_sval, bytes));
+  const int sp = span_begin(c, K_PROBE_WRITE, -1);
+  if (s.pc.n) {
+    RC_TRY(piece_offsets(c, s.pc));
+    HIP_TRY(hmj::launch_gtable_expand_pieces(s.pc.slabs(c).p, (const u32*)s.pc.counts(c).p, (const u64*)c->piece_off.p, s.pc.n, s.pc.cap, s.sortedR, s.svmin,
+                                             s.range_bits, (u64*)c->out_key.p, (u64*)c->out_rval.p, (u64*)c->out_sval.p, (u64*)c->accum.p, s.extra,
+                                             c->num_cus, c->stream));
   } else {
-    RC_TRY(lsd(range_bits));  // {payload, rank} by payload
-    if (n) {
-      HIP_TRY(hmj::launch_gtable_swap(sorted, c->sbuf[which ^ 1].p, n, c->num_cus, c->stream));  // -> {rank, payload}
-      sorted = c->sbuf[which ^ 1].p;
-      which ^= 1;
-    }
-    RC_TRY(lsd(rank_bits));  // stably by rank
+    HIP_TRY(hmj::launch_gtable_expand(s.sorted, s.n, s.sortedR, s.svmin, s.range_bits, (u64*)c->out_key.p, (u64*)c->out_rval.p,
+                                      (u64*)c->out_sval.p, (u64*)c->accum.p, s.extra, s.wide, c->num_cus, c->stream));
   }
-  // ---- 6. composites -> result rows
-  if (n) {
-    const size_t bytes = (size_t)n * 8;
-    RC_TRY(ensure_dev(c, c->out_key, bytes));
-    RC_TRY(ensure_dev(c, c->out_rval, bytes));
-    RC_TRY(ensure_dev(c, c->out_sval, bytes));
-    sp = span_begin(c, K_PROBE_WRITE, -1);
-    if (pc_n) {
-      DevBuf& so = pc_which ? c->slab_bs : c->slab_a;
-      DevBuf& co = pc_which ? c->cnt_bs : c->cnt_a;
-      RC_TRY(ensure_dev(c, c->piece_off, (size_t)pc_n * 8));
-      HIP_TRY(hmj::launch_piece_offsets((const u32*)co.p, pc_n, (u64*)c->piece_off.p, c->stream));
-      HIP_TRY(hmj::launch_gtable_expand_pieces(so.p, (const u32*)co.p, (const u64*)c->piece_off.p, pc_n, pc_cap, sortedR, svmin, range_bits,
-                                               (u64*)c->out_key.p, (u64*)c->out_rval.p, (u64*)c->out_sval.p, (u64*)c->accum.p, extra,
-                                               c->num_cus, c->stream));
-    } else {
-      HIP_TRY(hmj::launch_gtable_expand(sorted, n, sortedR, svmin, range_bits, (u64*)c->out_key.p, (u64*)c->out_rval.p,
-                                        (u64*)c->out_sval.p, (u64*)c->accum.p, extra, wide, c->num_cus, c->stream));
-    }
-    span_end(c, sp);
-    RC_TRY(read_accum(c, &hh));
-  }
-  }  // (!runs_done)
-  std::memset(out, 0, sizeof(*out));
-  result_sums(out, hh);
-  out->n_matches = n;  // (the rows the emit counted)
+  span_end(c, sp);
+  return read_accum(c, &s.hh);
+}
+// the result's sums (from the last read-back: on the run path without a matching row that is the emit's), the timing fields
+// that are not times, the columns
+static int finish_small_ordered(hmj_ctx* c, SmallOrdered& s) {
+  std::memset(s.out, 0, sizeof(*s.out));
+  result_sums(s.out, s.hh);
+  s.out->n_matches = s.n;  // (the rows the emit counted)
   c->timing.path |= HMJ_PATH_GLOBAL_TABLE | HMJ_PATH_ORDER_BY_RANK_SORT;
-  if (!runs_done) {
-    c->timing.radix_bits = rank_bits + range_bits;
-    c->timing.radix_passes = n_passes;
+  if (!s.runs_done) {
+    c->timing.radix_bits = s.rank_bits + s.range_bits;
+    c->timing.radix_passes = s.n_passes;
   }
   c->timing.n_probe_items = 1;
-  c->timing.bytes_probe_write = 16ull * (n_build + n_probe) + 24ull * n;
-  if (n) RC_TRY(deliver_columns(c, out, to_host, c->out_key.p, c->out_rval.p, c->out_sval.p, (size_t)n * 8, false));
-  if (c->trace) std::fprintf(stderr, "[hmj] join nb=%u np=%u flags=%#x: ordered by a sort on (rank, payload): %d + %d bits\n", nb, np, flags,
-                             rank_bits, range_bits);
+  c->timing.bytes_probe_write = 16ull * (s.n_build + s.n_probe) + 24ull * s.n;
+  if (s.n) RC_TRY(deliver_columns(c, s.out, s.to_host, c->out_key.p, c->out_rval.p, c->out_sval.p, (size_t)s.n * 8, false));
+  if (c->trace) std::fprintf(stderr, "[hmj] join nb=%u np=%u flags=%#x: ordered by a sort on (rank, payload): %d + %d bits\n", s.nb, s.np, s.flags,
+                             s.rank_bits, s.range_bits);
+  return HMJ_OK;
+}
+// the ladder: HMJ_OK (delivered), kPathGaveUp, or an error
+static int run_small_ordered(hmj_ctx* c, SmallOrdered& s) {
+  RC_TRY(survey_keys_and_payloads(c, s));
+  RC_TRY(sort_build_side(c, s));
+  RC_TRY(build_rank_table(c, s));
+  if (s.use_runs) RC_TRY(try_rank_runs(c, s));
+  if (!s.runs_done) {
+    RC_TRY(emit_composites(c, s));
+    RC_TRY(sort_composites(c, s));
+    RC_TRY(expand_composites(c, s));
+  }
+  return finish_small_ordered(c, s);
+}
+
+int try_small_build_ordered(hmj_ctx* c, const void* R, uint64_t n_build, const void* S, uint64_t n_probe, uint32_t flags,
+                            hmj_result* out, bool to_host, bool* done) {
+  *done = false;
+  // nothing of the context is written before the gate admits the join, but the model's refusal
+  const SmallOrderedCooldowns cool = {c->wm->gtable_sort_cooldown, c->wm->gtable_sort_slab_cooldown, c->wm->rank_runs_cooldown,
+                                      c->wm->rank_lookup_cooldown};
+  const SmallGateResult gate = small_ordered_gate(small_ordered_knobs(c, R, n_build), c->ordered_model, n_build, n_probe,
+                                                  (flags & HMJ_ORDERED) != 0, cool);
+  if (gate.verdict == SmallGate::RefusedByModel) c->plan.refused |= HMJ_REFUSED_RANK_SORT_MODEL;
+  if (gate.verdict != SmallGate::Eligible) return HMJ_OK;
+  if (c->wm->gtable_sort_cooldown > 0) {
+    c->wm->gtable_sort_cooldown--;
+    c->plan.refused |= HMJ_REFUSED_RANK_SORT_COOLING;
+    return HMJ_OK;
+  }
+  if (!out) return fail(c, HMJ_E_ARG, "out is NULL");
+  RC_TRY(check_rel(c, R, n_build, "build_aos is NULL"));
+  RC_TRY(check_rel(c, S, n_probe, "probe_aos is NULL"));
+  SmallOrdered s = {};
+  s.R = R;
+  s.S = S;
+  s.n_build = n_build;
+  s.n_probe = n_probe;
+  s.flags = flags;
+  s.out = out;
+  s.to_host = to_host;
+  s.nb = (u32)n_build;
+  s.np = (u32)n_probe;
+  s.extra = flags & (HMJ_CHECKSUM | HMJ_SUM_PROBE);
+  s.part_ns = gate.part_ns;
+  s.run_tb = gate.run_tb;
+  s.run_level = gate.run_level;
+  s.use_runs = gate.fit;
+  c->prep.valid = false;  // rbuf is the build side's sort buffer
+  RC_TRY(ensure_dev(c, c->rbuf[0], (size_t)s.nb * 16));
+  RC_TRY(ensure_dev(c, c->rbuf[1], (size_t)s.nb * 16));
+  RC_TRY(ensure_dev(c, c->sbuf[0], (size_t)s.np * 16));
+  RC_TRY(ensure_dev(c, c->sbuf[1], (size_t)s.np * 16));
+  RC_TRY(ensure_dev(c, c->accum, 8 * sizeof(u64)));
+  RC_TRY(ensure_dev(c, c->offs64, 8 * sizeof(u64)));
+  RC_TRY(ensure_host(c, c->h_accum, 8 * sizeof(u64)));
+  s.hh = (u64*)c->h_accum.p;
+  const int rc = run_small_ordered(c, s);
+  if (rc == kPathGaveUp) return HMJ_OK;
+  RC_TRY(rc);
   *done = true;
   return HMJ_OK;
 }
+
 
 static int join_device_planned(hmj_ctx* c, const void* R, uint64_t n_build, const void* S, uint64_t n_probe, uint32_t flags,
                                hmj_result* out, bool to_host);
@@ -2693,7 +2676,7 @@ static bool key_ranges_wanted(const hmj_ctx* c, uint64_t nb, uint64_t np, uint32
   auto held = [&](double b, double p) {  // does one plan hold a join of b x p rows: the one-pass ordered write, or the rank-run form
     if (fk_probe_rows_hi(p / P18, p / b, P18) <= 6144.0) return true;
     int tb = 0, lv = 0;
-    return b <= 16.0 * (double)c->gtable_max_rows && rank_runs_fit(c, (uint64_t)b, (uint64_t)p, &tb, &lv);
+    return b <= 16.0 * (double)c->gtable_max_rows && rank_runs_fit(rank_run_knobs(c), (uint64_t)b, (uint64_t)p, &tb, &lv);
   };
   if (held((double)nb, (double)np)) return false;
   // (a range's share of the rows is not exactly 1 / 2^h: a twentieth of room)
@@ -2889,11 +2872,7 @@ static int join_device_planned(hmj_ctx* c, const void* R, uint64_t n_build, cons
                    : rc == kRetryMoreBits ? " -> retry with one more radix bit (a partition did not fit the ordered expansion)" : "");
     if (rc == kRetryNoSlab || rc == kRetryNoPrefix || rc == kRetryNoFastWrite || rc == kRetryNoWinOrdered || rc == kRetryNoSlabProbe ||
         rc == kRetryMoreBits) {
-      // forget the abandoned attempt's phase spans (the enclosing total / h2d spans stay)
-      std::vector<Span> keep;
-      for (const Span& sp : c->spans)
-        if (sp.kind == K_TOTAL || sp.kind == K_H2D) keep.push_back(sp);
-      c->spans.swap(keep);
+      drop_attempt_spans(c);
       std::memset(&c->timing, 0, sizeof(c->timing));
       if (rc == kRetryNoSlab) slab = false;
       else if (rc == kRetryMoreBits) {  // once per join: the next attempt plans the bits asked for
@@ -2978,6 +2957,7 @@ int hmj_create(hmj_ctx** out, int device_id) {
   if (device_id >= ndev) return HMJ_E_ARG;
   if (hipSetDevice(device_id) != hipSuccess) return HMJ_E_NODEV;
   hmj_ctx* c = new hmj_ctx();
+  for (int lv = -1; lv <= 2; lv++) c->lds_sort.max_run[lv + 1] = hmj::rank_sort_max_run(lv);
   c->device = device_id;
   if (const char* e = getenv("HMJ_SLAB")) c->slab_mode = atoi(e);
   if (const char* e = getenv("HMJ_ONE_PASS_SLAB")) c->one_pass_slab = atoi(e) != 0;  // 0: mid-size build sides keep the exact one-pass plan
@@ -3629,6 +3609,135 @@ int hmj_partition_u64_device(hmj_ctx* c, const void* in_aos_dev, uint64_t n, int
   return HMJ_OK;
 }
 
+
+// ---- hmj_sort_u64_device: a ladder like the small-build join's -- the MSD form -> a chain of slab passes -> exact passes --,
+// one function per form (the arithmetic: hmj_smallplan.h)
+struct SortKeys {
+  u32 digits = 0xFFu;                        // bit d: the 8-bit digit d varies
+  u64 diff = ~0ull, kmin = 0, kmax = ~0ull;  // the bits in which keys differ; exact (with the extremes) when != ~0
+  u64 sdiff = ~0ull;                         // the bits in which the SAMPLED keys differ
+};
+// Digits in which no key differs need no pass (a stable pass on a constant digit is a copy): integer ids below 2^32
+// sort in four passes instead of eight (dense keys, 2^26 rows: 5.58 -> 2.93 ms, 2^28: 21.4 -> 10.8 ms = 24.8 G keys/s,
+// tools/exp_cliffs_sort.py; from 2^22 rows on -- below, the two host round trips cost more than the passes saved).  A sample of the keys
+// says whether that can be the case at all -- uniform 64-bit keys then pay nothing --, one pass over all keys (16 of a
+// radix pass's 48 bytes per row) makes it exact.
+static int survey_sort_digits(hmj_ctx* c, const void* in, u32 n, SortKeys* k) {
+  RC_TRY(ensure_dev(c, c->offs64, 8 * sizeof(u64)));
+  RC_TRY(ensure_host(c, c->h_accum, 8 * sizeof(u64)));
+  u64* h = (u64*)c->h_accum.p;
+  HIP_TRY(hmj::launch_key_sample(in, n, nullptr, 0u, (u64*)c->offs64.p, c->stream));
+  HIP_TRY(hipMemcpyAsync(h, c->offs64.p, 8 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  k->sdiff = h[0];
+  if (varying_digits(h[0]) == 0xFFu) return HMJ_OK;
+  const u64 init[3] = {0, ~0ull, 0};
+  HIP_TRY(hipMemcpyAsync(c->offs64.p, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hmj::launch_key_exact(in, n, nullptr, 0u, 0, (u64*)c->offs64.p, c->num_cus, c->stream, true));
+  HIP_TRY(hipMemcpyAsync(h, c->offs64.p, 3 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  k->digits = varying_digits(h[0]);
+  k->diff = h[0];
+  k->kmin = h[1];
+  k->kmax = h[2];
+  return HMJ_OK;
+}
+// Round 5, out-of-place sorts from 2^22 rows on: MSD.  The join's two slab passes partition the rows on the TOP 12 ... 18
+// varying key bits, one workgroup per partition sorts its run on the remaining bits in LDS and writes it at the partition's
+// offset (gtable.hip, sort_runs_write_kernel): 3 x 32 B per row whatever the key width, against one 32-byte pass per varying
+// digit + a compaction in the chain below (uniform 64-bit keys: 9 x 32 B).  The window's top is the highest bit in which
+// keys differ (exact), or bit 63 when only the sample is known; partitions hold ~1000 rows and at most 2048.  Keys that
+// crowd into few partitions, or runs with many equal keys, raise an error word: the input is untouched, the chain runs,
+// and this size is left alone for 8 sorts.
+static int try_sort_msd(hmj_ctx* c, const void* in, u64 n, void* out, const SortKeys& k, bool* done) {
+  if (c->wm->sort_msd_cooldown > 0) {
+    c->wm->sort_msd_cooldown--;
+    return HMJ_OK;
+  }
+  if (!(c->sort_msd && c->slab_mode && out != in && n >= c->sort_msd_min && n < 0xFFFFFFF0ull)) return HMJ_OK;
+  const SortMsdWindow w = sort_msd_window(n, k.diff, k.sdiff, k.kmin, k.kmax, c->sort_msd_max_bits, c->sort_msd_mean, c->rank_runs_max_level,
+                                          c->lds_sort, hmj::SLAB_MAX_BITS);
+  const int bb = w.TB / 2, ba = w.TB - bb;
+  hmj::SlabGeom g;
+  if (!w.ok || !hmj::slab_geometry((u32)n, ba, bb, &g, 0, 1.0, w.dens)) return HMJ_OK;
+  RC_TRY(ensure_dev(c, c->accum, 8 * sizeof(u64)));
+  RC_TRY(ensure_host(c, c->h_accum, 8 * sizeof(u64)));
+  HIP_TRY(hipMemsetAsync(c->accum.p, 0, 8 * sizeof(u64), c->stream));
+  RC_TRY(msd_partition(c, in, (u32)n, w.hi - w.TB, ba, bb, g, -1, false, 0, nullptr));
+  const int sp = span_begin(c, K_ORDER, -1);
+  HIP_TRY(hmj::launch_sort_runs_write(c->slab_bs.p, (const u32*)c->cnt_bs.p, g.CB, 1u << w.TB, (const u64*)c->part_out_off.p, out, (u64*)c->accum.p,
+                                      w.level, c->num_cus, c->stream));
+  span_end(c, sp);
+  u64* hh = nullptr;
+  RC_TRY(read_accum(c, &hh));
+  if (hh[hmj::ACC_ERR] & (hmj::ERR_SLAB | hmj::ERR_FASTPATH)) {
+    c->wm->sort_msd_cooldown = 8;
+    HIP_TRY(hipMemsetAsync((u64*)c->accum.p + hmj::ACC_ERR, 0, sizeof(u64), c->stream));  // (only the error word)
+    c->spans.clear();  // ALL spans go, K_TOTAL and K_H2D included -- unlike drop_attempt_spans; kept as it was
+    if (c->trace) std::fprintf(stderr, "[hmj] sort n=%llu: MSD form gave up (%s) -> chain of LSD passes\n", (unsigned long long)n,
+                               (hh[hmj::ACC_ERR] & hmj::ERR_SLAB) ? "a slab overflowed" : "a run beyond the kernel, or many equal keys");
+    return HMJ_OK;
+  }
+  c->timing.bytes_scatter += 2 * 32ull * n;
+  c->timing.path |= HMJ_PATH_SLAB | HMJ_PATH_SORT_MSD;
+  c->timing.radix_bits = w.TB;
+  c->timing.radix_passes = 2;
+  *done = true;
+  return HMJ_OK;
+}
+// From 2^25 rows on the passes are a CHAIN of histogram-free slab passes (slab_chain: 32 instead of 48 B per row and pass)
+// and one compaction of the last pass's pieces into the output (32 B per row): uniform 64-bit keys 9 x 32 instead of 8 x 48
+// B per row.  A digit is trimmed to the bits that vary inside it (ids below 2^28: 8 + 8 + 8 + 4 bits), the top digit's slabs
+// are sized for the share of its values in use; digits that are not evenly filled overflow a slab -> the exact passes
+// (the input is untouched: the chain writes only its own buffers), and the chain is left alone for the next 8 sorts.
+static int try_sort_chain(hmj_ctx* c, const void* in, u64 n, void* out, const SortKeys& k, bool* done) {
+  if (c->wm->sort_slab_cooldown > 0) {
+    c->wm->sort_slab_cooldown--;
+    return HMJ_OK;
+  }
+  if (!(__builtin_popcount(k.digits) >= 2 && c->slab_mode && c->sort_slab && n >= c->sort_slab_min && n < 0xFFFFFFF0ull)) return HMJ_OK;
+  ChainDigit dg[8];
+  const int nd = sort_chain_digits(k.diff, k.sdiff, k.kmin, k.kmax, dg);
+  bool ok = false;
+  ChainPieces pc;
+  RC_TRY(slab_chain(c, in, (u32)n, dg, nd, -1, &ok, &pc.n, &pc.cap, &pc.which));
+  if (!ok) {
+    c->wm->sort_slab_cooldown = 8;
+    return HMJ_OK;
+  }
+  RC_TRY(piece_offsets(c, pc));
+  const int sp = span_begin(c, K_SCATTER, -1, nd);
+  HIP_TRY(hmj::launch_pieces_compact(pc.slabs(c).p, (const u32*)pc.counts(c).p, (const u64*)c->piece_off.p, pc.n, pc.cap, out, c->num_cus, c->stream));
+  span_end(c, sp);
+  c->timing.bytes_scatter += 32ull * n;
+  c->timing.path |= HMJ_PATH_SLAB;
+  *done = true;
+  return HMJ_OK;
+}
+// one exact LSD pass per varying digit
+static int sort_exact_passes(hmj_ctx* c, const void* in, u64 n, void* out, u32 digits) {
+  const int k = __builtin_popcount(digits);
+  if (k == 0) {  // one distinct key: the input order is the sorted order
+    if (out != in) HIP_TRY(hipMemcpyAsync(out, in, (size_t)n * 16, hipMemcpyDeviceToDevice, c->stream));
+    return HMJ_OK;
+  }
+  // the passes alternate between the caller's output and the scratch buffer and end in the output -- except in place
+  // with an odd number of passes (the first pass must not write what it reads): those end in the scratch buffer
+  void* const tmp = c->rbuf[0].p;
+  const bool end_in_out = !(out == in && (k & 1));
+  const void* src = in;
+  int left = k;
+  for (int d = 0; d < 8; d++) {  // LSD: bits [8 d, 8 d + 8)
+    if (!(digits & (1u << d))) continue;
+    void* dst = ((left & 1) == (end_in_out ? 1 : 0)) ? out : tmp;
+    RC_TRY(radix_pass(c, src, dst, (u32)n, 8 * d, 8, -1, nullptr));
+    src = dst;
+    left--;
+  }
+  if (!end_in_out) HIP_TRY(hipMemcpyAsync(out, tmp, (size_t)n * 16, hipMemcpyDeviceToDevice, c->stream));
+  return HMJ_OK;
+}
+
 int hmj_sort_u64_device(hmj_ctx* c, const void* in_aos_dev, uint64_t n, void* out_aos_dev) {
   if (!c) return HMJ_E_ARG;
   RC_TRY(check_rel(c, in_aos_dev, n, "in_aos is NULL"));
@@ -3640,188 +3749,16 @@ int hmj_sort_u64_device(hmj_ctx* c, const void* in_aos_dev, uint64_t n, void* ou
   // (what earlier sorts of this size learnt: the chain's cool-down; the sorts of hmj_order_by_device under a kind of their own)
   memo_for(c, workload_signature(n, 0, 0, c->memo_kind ? c->memo_kind : 1));
   RC_TRY(ensure_dev(c, c->rbuf[0], (size_t)n * 16));
-  // Digits in which no key differs need no pass (a stable pass on a constant digit is a copy): integer ids below 2^32
-  // sort in four passes instead of eight (dense keys, 2^26 rows: 5.58 -> 2.93 ms, 2^28: 21.4 -> 10.8 ms = 24.8 G keys/s,
-  // tools/exp_cliffs_sort.py; from 2^22 rows on -- below, the two host round trips cost more than the passes saved).  A sample of the keys
-  // says whether that can be the case at all -- uniform 64-bit keys then pay nothing --, one pass over all keys (16 of a
-  // radix pass's 48 bytes per row) makes it exact.
-  u32 digits = 0xFFu;  // bit d: the 8-bit digit d varies
-  u64 diff = ~0ull, kmin = 0, kmax = ~0ull;  // the bits in which keys differ; exact (with the extremes) when != ~0
-  u64 sdiff = ~0ull;                          // the bits in which the SAMPLED keys differ
-  if (n >= (1u << 22)) {
-    RC_TRY(ensure_dev(c, c->offs64, 8 * sizeof(u64)));
-    RC_TRY(ensure_host(c, c->h_accum, 8 * sizeof(u64)));
-    u64* h = (u64*)c->h_accum.p;
-    HIP_TRY(hmj::launch_key_sample(in_aos_dev, (u32)n, nullptr, 0u, (u64*)c->offs64.p, c->stream));
-    HIP_TRY(hipMemcpyAsync(h, c->offs64.p, 8 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    auto varying = [](u64 mask) {
-      u32 d = 0;
-      for (int i = 0; i < 8; i++) d |= ((mask >> (8 * i)) & 0xFFu) ? (1u << i) : 0u;
-      return d;
-    };
-    sdiff = h[0];
-    if (varying(h[0]) != 0xFFu) {
-      const u64 init[3] = {0, ~0ull, 0};
-      HIP_TRY(hipMemcpyAsync(c->offs64.p, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
-      HIP_TRY(hmj::launch_key_exact(in_aos_dev, (u32)n, nullptr, 0u, 0, (u64*)c->offs64.p, c->num_cus, c->stream, true));
-      HIP_TRY(hipMemcpyAsync(h, c->offs64.p, 3 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      digits = varying(h[0]);
-      diff = h[0];
-      kmin = h[1];
-      kmax = h[2];
-    }
+  SortKeys k;
+  if (n >= (1u << 22)) RC_TRY(survey_sort_digits(c, in_aos_dev, (u32)n, &k));
+  bool done = false;
+  RC_TRY(try_sort_msd(c, in_aos_dev, n, out_aos_dev, k, &done));
+  if (done) {  // (its read-back has synchronised)
+    if (c->profiling) spans_collect(c);
+    return HMJ_OK;
   }
-  const int k = __builtin_popcount(digits);
-  void* const tmp = c->rbuf[0].p;
-  // From 2^25 rows on the passes are a CHAIN of histogram-free slab passes (slab_chain: 32 instead of 48 B per row and pass)
-  // and one compaction of the last pass's pieces into the output (32 B per row): uniform 64-bit keys 9 x 32 instead of 8 x 48
-  // B per row.  A digit is trimmed to the bits that vary inside it (ids below 2^28: 8 + 8 + 8 + 4 bits), the top digit's slabs
-  // are sized for the share of its values in use; digits that are not evenly filled overflow a slab -> the exact passes below
-  // (the input is untouched: the chain writes only its own buffers), and the chain is left alone for the next 8 sorts.
-  bool chained = false;
-  // Round 5, out-of-place sorts from 2^22 rows on: MSD.  The join's two slab passes partition the rows on the TOP 12 ... 18
-  // varying key bits, one workgroup per partition sorts its run on the remaining bits in LDS and writes it at the partition's
-  // offset (gtable.hip, sort_runs_write_kernel): 3 x 32 B per row whatever the key width, against one 32-byte pass per varying
-  // digit + a compaction in the chain below (uniform 64-bit keys: 9 x 32 B).  The window's top is the highest bit in which
-  // keys differ (exact), or bit 63 when only the sample is known; partitions hold ~1000 rows and at most 2048.  Keys that
-  // crowd into few partitions, or runs with many equal keys, raise an error word: the input is untouched, the chain runs,
-  // and this size is left alone for 8 sorts.
-  if (c->wm->sort_msd_cooldown > 0) c->wm->sort_msd_cooldown--;
-  else if (c->sort_msd && c->slab_mode && out_aos_dev != in_aos_dev && n >= c->sort_msd_min && n < 0xFFFFFFF0ull) {
-    const bool exact = diff != ~0ull;
-    const int hi = exact ? (diff ? 64 - __builtin_clzll(diff) : 0) : 64;  // keys agree in every bit from `hi` up
-    // how much of the window's top digit is in use: exact -> from the extremes; sampled -> a top bit the sample never saw
-    // varying halves it (63-bit keys)
-    // the narrowest window whose partitions average <= 1200 rows, counting that the keys may fill only part of it
-    int TB = 1;
-    double dens = 1.0, mean = (double)n;
-    do {
-      TB++;
-      if (TB > hi) break;
-      if (exact) {
-        const u64 in_use = (kmax >> (hi - TB)) - (kmin >> (hi - TB)) + 1;
-        dens = std::ldexp(1.0, TB) / (double)in_use;
-      } else if (sdiff != ~0ull) {
-        dens = std::ldexp(1.0, __builtin_clzll(sdiff));  // (the sample's top varying bit is below bit 63)
-        if (dens > 64.0) dens = 64.0;
-      }
-      mean = dens * (double)n / std::ldexp(1.0, TB);
-      // (a 17th / 18th bit makes a pass a 9-bit pass -- 1.95 / 2.17 ms per 2^28 rows against 1.5 / 1.6 -- and is only worth
-      //  partitions beyond the 512-thread sort's comfort: 2^27 / 2^28 rows 3.43 / 7.06 -> 3.32 / 6.84 ms, profiles/r05ad_*)
-    } while (TB < c->sort_msd_max_bits && mean > (TB >= 16 ? 2.0 : 1.0) * c->sort_msd_mean);
-    if (TB > hi) TB = 0;
-    // (beyond 4.5 * 10^8 rows the 2^18 partitions outgrow the 256-thread sort: 512 / 1024 threads hold 4096 / 8192 rows)
-    int level = 0;
-    while (level < c->rank_runs_max_level && mean + 8.0 * std::sqrt(mean) + 24.0 > (double)hmj::rank_sort_max_run(level)) level++;
-    const int bb = TB / 2, ba = TB - bb, shift_a = hi - TB, shift_b = shift_a + ba;
-    hmj::SlabGeom g;
-    if (TB >= 2 && ba <= hmj::SLAB_MAX_BITS && mean + 8.0 * std::sqrt(mean) + 24.0 <= (double)hmj::rank_sort_max_run(level) &&
-        hmj::slab_geometry((u32)n, ba, bb, &g, 0, 1.0, dens)) {
-      const u32 P = 1u << TB;
-      RC_TRY(ensure_dev(c, c->accum, 8 * sizeof(u64)));
-      RC_TRY(ensure_host(c, c->h_accum, 8 * sizeof(u64)));
-      RC_TRY(ensure_dev(c, c->slab_a, g.rows_a * 16));
-      RC_TRY(ensure_dev(c, c->cnt_a, ((size_t)g.WA << ba) * 4));
-      RC_TRY(ensure_dev(c, c->slab_bs, g.rows_b * 16));
-      RC_TRY(ensure_dev(c, c->cnt_bs, (size_t)P * g.KB * 4));
-      RC_TRY(ensure_dev(c, c->part_out_off, ((size_t)P + 1) * 8));
-      RC_TRY(ensure_dev(c, c->part_count, ((size_t)P / 1024 + 1) * 8));
-      u64* acc = (u64*)c->accum.p;
-      u64* hh = (u64*)c->h_accum.p;
-      HIP_TRY(hipMemsetAsync(c->accum.p, 0, 8 * sizeof(u64), c->stream));
-      int sp = span_begin(c, K_SCATTER, -1, 0);
-      HIP_TRY(hmj::launch_slab_a(in_aos_dev, (u32)n, shift_a, ba, g, c->slab_a.p, c->slab_a.cap / 16, (u32*)c->cnt_a.p, c->cnt_a.cap / 4, acc, c->stream));
-      span_end(c, sp);
-      sp = span_begin(c, K_SCATTER, -1, 1);
-      HIP_TRY(hmj::launch_slab_b(c->slab_a.p, (const u32*)c->cnt_a.p, ba, shift_b, bb, g, c->slab_bs.p, c->slab_bs.cap / 16, (u32*)c->cnt_bs.p,
-                                 c->cnt_bs.cap / 4, acc, c->stream));
-      span_end(c, sp);
-      HIP_TRY(hmj::launch_slab_offsets((const u32*)c->cnt_bs.p, P, (u64*)c->part_out_off.p, (u64*)c->part_count.p, c->stream));
-      sp = span_begin(c, K_ORDER, -1);
-      HIP_TRY(hmj::launch_sort_runs_write(c->slab_bs.p, (const u32*)c->cnt_bs.p, g.CB, P, (const u64*)c->part_out_off.p, out_aos_dev, acc, level,
-                                          c->num_cus, c->stream));
-      span_end(c, sp);
-      RC_TRY(read_accum(c, &hh));
-      if (hh[hmj::ACC_ERR] & (hmj::ERR_SLAB | hmj::ERR_FASTPATH)) {
-        c->wm->sort_msd_cooldown = 8;
-        HIP_TRY(hipMemsetAsync((u64*)c->accum.p + hmj::ACC_ERR, 0, sizeof(u64), c->stream));
-        std::vector<Span> keep;
-        c->spans.swap(keep);
-        if (c->trace) std::fprintf(stderr, "[hmj] sort n=%llu: MSD form gave up (%s) -> chain of LSD passes\n", (unsigned long long)n,
-                                   (hh[hmj::ACC_ERR] & hmj::ERR_SLAB) ? "a slab overflowed" : "a run beyond the kernel, or many equal keys");
-      } else {
-        c->timing.bytes_scatter += 2 * 32ull * n;
-        c->timing.path |= HMJ_PATH_SLAB | HMJ_PATH_SORT_MSD;
-        c->timing.radix_bits = TB;
-        c->timing.radix_passes = 2;
-        if (c->profiling) spans_collect(c);
-        return HMJ_OK;
-      }
-    }
-  }
-  if (c->wm->sort_slab_cooldown > 0) c->wm->sort_slab_cooldown--;
-  else if (k >= 2 && c->slab_mode && c->sort_slab && n >= c->sort_slab_min && n < 0xFFFFFFF0ull) {
-    // exact: `diff` holds every bit in which keys differ (digits are trimmed to them).  Otherwise the sample saw all eight
-    // digits vary and `sdiff` holds the bits IT saw varying: every digit keeps its eight bits (a bit the sample missed must
-    // still be sorted on), but a bit of a digit that (as far as the sample tells) never varies halves the values in use, so
-    // the rows crowd into the others -- 63-bit keys fill half of the top digit -- and the slabs are sized for that.
-    const bool exact = diff != ~0ull || sdiff == ~0ull;
-    hmj_host::ChainDigit dg[8];
-    int nd = 0;
-    for (int d = 0; d < 8; d++) {
-      const u32 sub = (u32)((exact ? diff : sdiff) >> (8 * d)) & 0xFFu;
-      if (exact && !sub) continue;
-      const int lo = exact ? __builtin_ctz(sub) : 0, hi = exact ? 31 - __builtin_clz(sub) : 7;
-      dg[nd].shift = 8 * d + lo;
-      dg[nd].bits = hi - lo + 1;
-      dg[nd].dens = std::ldexp(1.0, dg[nd].bits - __builtin_popcount(sub));
-      nd++;
-    }
-    if (exact && diff != ~0ull && nd) {  // (kmin / kmax are the keys' extremes, all bits above the top digit agree)
-      const hmj_host::ChainDigit& t = dg[nd - 1];
-      const u64 in_use = (kmax >> t.shift) - (kmin >> t.shift) + 1;
-      const double dt = std::ldexp(1.0, t.bits) / (double)in_use;
-      if (dt > dg[nd - 1].dens) dg[nd - 1].dens = dt;
-    }
-    bool ok = false;
-    u32 pc_n = 0, pc_cap = 0;
-    int pc_which = 0;
-    RC_TRY(hmj_host::slab_chain(c, in_aos_dev, (u32)n, dg, nd, -1, &ok, &pc_n, &pc_cap, &pc_which));
-    if (ok) {
-      DevBuf& so = pc_which ? c->slab_bs : c->slab_a;
-      DevBuf& co = pc_which ? c->cnt_bs : c->cnt_a;
-      RC_TRY(ensure_dev(c, c->piece_off, (size_t)pc_n * 8));
-      HIP_TRY(hmj::launch_piece_offsets((const u32*)co.p, pc_n, (u64*)c->piece_off.p, c->stream));
-      const int sp = span_begin(c, K_SCATTER, -1, nd);
-      HIP_TRY(hmj::launch_pieces_compact(so.p, (const u32*)co.p, (const u64*)c->piece_off.p, pc_n, pc_cap, out_aos_dev, c->num_cus, c->stream));
-      span_end(c, sp);
-      c->timing.bytes_scatter += 32ull * n;
-      c->timing.path |= HMJ_PATH_SLAB;
-      chained = true;
-    } else {
-      c->wm->sort_slab_cooldown = 8;
-    }
-  }
-  if (chained) {
-  } else if (k == 0) {  // one distinct key: the input order is the sorted order
-    if (out_aos_dev != in_aos_dev) HIP_TRY(hipMemcpyAsync(out_aos_dev, in_aos_dev, (size_t)n * 16, hipMemcpyDeviceToDevice, c->stream));
-  } else {
-    // the passes alternate between the caller's output and the scratch buffer and end in the output -- except in place
-    // with an odd number of passes (the first pass must not write what it reads): those end in the scratch buffer
-    const bool end_in_out = !(out_aos_dev == in_aos_dev && (k & 1));
-    const void* src = in_aos_dev;
-    int left = k;
-    for (int d = 0; d < 8; d++) {  // LSD: bits [8 d, 8 d + 8)
-      if (!(digits & (1u << d))) continue;
-      void* dst = ((left & 1) == (end_in_out ? 1 : 0)) ? out_aos_dev : tmp;
-      RC_TRY(radix_pass(c, src, dst, (u32)n, 8 * d, 8, -1, nullptr));
-      src = dst;
-      left--;
-    }
-    if (!end_in_out) HIP_TRY(hipMemcpyAsync(out_aos_dev, tmp, (size_t)n * 16, hipMemcpyDeviceToDevice, c->stream));
-  }
+  RC_TRY(try_sort_chain(c, in_aos_dev, n, out_aos_dev, k, &done));
+  if (!done) RC_TRY(sort_exact_passes(c, in_aos_dev, n, out_aos_dev, k.digits));
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (c->profiling) spans_collect(c);
   return HMJ_OK;

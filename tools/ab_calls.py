@@ -11,8 +11,9 @@ identical files:
     HMJ_LIB=<change .so> python tools/ab_calls.py change.jsonl   # a process each
     cmp parent.jsonl change.jsonl
 
-A second argument chooses the calls: `u64` (the u64 driver's plans), `keyed` (the string, column and mixed entries:
-keyed_section) or `all` (the default).
+A second argument chooses the calls: `u64` (the u64 driver's plans), `small` (the ordered join of a small build side and
+hmj_sort_u64_device, branch by branch: small_section), `keyed` (the string, column and mixed entries: keyed_section) or
+`all` (the default).
 """
 import ctypes as C
 import json
@@ -28,7 +29,7 @@ from hashmergejoin_amd.join import _memcpy_d2d
 
 M, O, F, CK, SP = H.HMJ_MATERIALIZE, H.HMJ_ORDERED, H.HMJ_FIRST_WINS, H.HMJ_CHECKSUM, H.HMJ_SUM_PROBE
 TIMING = ("path", "radix_bits", "radix_passes", "key_prefix_bits", "key_window_low", "n_probe_items", "n_split_retries",
-          "bytes_scatter", "bytes_hist", "bytes_probe_count", "bytes_probe_write")
+          "n_scatter_launches", "bytes_scatter", "bytes_hist", "bytes_probe_count", "bytes_probe_write")
 SUMS = ("n_matches", "sum_r", "sum_s", "xor_fold", "mix_sum", "sum_probe_all")
 out_f = open(sys.argv[1], "w") if len(sys.argv) > 1 else sys.stdout
 n_records = 0
@@ -208,9 +209,140 @@ def keyed_section():
     kx.close()
 
 
-SECTION = sys.argv[2] if len(sys.argv) > 2 else "all"  # all | u64 | keyed
-if SECTION == "keyed":
-    keyed_section()
+def record_sort(name, ex, a, inplace=False, repeat=3):
+    """record()'s sibling for hmj_sort_u64_device on the rows `a` (numpy, [n, 2]): return code, hmj_last_error, the timing fields
+    that are not times, hmj_last_plan and a hash of the output row sequence."""
+    global n_records
+    for i in range(repeat):
+        rec = {"call": name, "i": i}
+        try:
+            got = to_np(ex.sort_device(to_dev(a), inplace=inplace))
+            rec["rc"] = 0
+            with np.errstate(over="ignore"):
+                h = (got[:, 0] * np.uint64(0x9E3779B97F4A7C15)) ^ (got[:, 1] * np.uint64(0xC2B2AE3D27D4EB4F))
+                h ^= h >> np.uint64(29)
+                rec["rows_seq"] = int((h * (np.arange(len(h), dtype=np.uint64) * np.uint64(2) + np.uint64(1))).sum(dtype=np.uint64))
+        except H.HmjError as e:
+            rec["rc"] = e.code
+        rec["last_error"] = ex.L.hmj_last_error(ex.h).decode()
+        t = ex.last_timing()
+        rec["timing"] = {k: int(t[k]) for k in TIMING}
+        rec["plan"] = ex.last_plan()
+        out_f.write(json.dumps(rec, sort_keys=True) + "\n")
+        out_f.flush()
+        n_records += 1
+
+
+def small_section():
+    """The ordered join of a small build side under a long probe side (try_small_build_ordered) and hmj_sort_u64_device,
+    one call per branch of their fallback ladders; shapes from tests/test_gpu_join.py at the smallest size that reaches the
+    branch.  A case whose point is a cool-down (a give-way, a give-up, an overflow) is issued ten times."""
+    rng = np.random.default_rng(77)
+    M64 = 0xFFFFFFFFFFFFFFFF
+
+    def relations(ex, nb, npb, miss, pay):
+        B = to_np(ex.gen_build(nb)).copy()
+        P = to_np(ex.gen_uniform_domain(npb, nb) if miss == 0 else ex.gen_probe(npb, nb, miss_mod=miss)).copy()
+        if pay == "hot":  # a third of the probe rows carry one key
+            P[::3, 0] = B[17, 0]
+            P[:, 1] = rng.permutation(npb).astype(np.uint64)
+        elif pay == "ties7":
+            P[:, 1] = rng.integers(0, 7, size=npb, dtype=np.uint64) * np.uint64(0x0123456789ABCDEF)
+        elif pay == "extremes":
+            P[:, 1] = rng.integers(0, 1 << 62, size=npb, dtype=np.uint64)
+            P[::5, 1] = np.uint64(0)
+            P[1::5, 1] = np.uint64(M64)
+        elif pay == "clustered":  # all build keys but three below 4000, three near 2^60
+            order = np.argsort(B[:, 0], kind="stable")
+            sk = B[order, 0].copy()
+            newk = np.arange(nb, dtype=np.uint64)
+            newk[-3:] = np.uint64(1 << 60) + np.arange(3, dtype=np.uint64) * np.uint64(0x1000000000)
+            P[:, 0] = newk[np.searchsorted(sk, P[:, 0])]
+            B[order, 0] = newk
+        if pay in ("ids", "clustered"):
+            P[:, 1] = rng.permutation(npb).astype(np.uint64)
+        elif pay == "rowid":
+            P[:, 1] = np.uint64(0x0000123400000000) + np.arange(npb, dtype=np.uint64) * np.uint64(3)
+        elif pay == "offset":
+            P[:, 1] = np.uint64(0xFEDCBA9800000000) + rng.integers(0, 1 << 30, size=npb, dtype=np.uint64)
+        elif pay == "wide":
+            P[:, 1] = rng.integers(0, 1 << 63, size=npb, dtype=np.uint64) * np.uint64(2)
+        elif pay == "stride":  # the first pass's digit is the same for every row
+            P[:, 1] = rng.permutation(npb).astype(np.uint64) * np.uint64(1024)
+        elif pay == "dupbuild":
+            B[1::3, 0] = B[0::3, 0][: len(B[1::3])]
+        return B, P
+
+    def ordered(ex, cases, flag_list=(O, O | CK | SP)):
+        for nb, npb, miss, pay, repeat in cases:
+            B, P = relations(ex, nb, npb, miss, pay)
+            joins("small %d x %d miss=%d %s" % (nb, npb, miss, pay), ex, to_dev(B), to_dev(P), flag_list, repeat=repeat)
+            ex.release_result()
+
+    exs = executor(HMJ_GTABLE_SORT_FANOUT=1)  # (the cost model switched off, as in the tests)
+    exs.set_profiling(True)
+    ordered(exs, [(1, 5000, 0, "ids", 3), (300, 5000, 0, "ids", 3),  # no run form
+                  (7, 70000, 0, "ids", 3),                            # rank runs
+                  (1000, 300001, 3, "offset", 10),                    # the fused attempt gives way to emit + pass A
+                  (1000, 200000, 0, "wide", 3),
+                  (2000, 700000, 0, "ties7", 3),
+                  (1500, 500000, 0, "extremes", 10),                  # runs give up -> composites
+                  (3000, 400000, 2, "dupbuild", 10),                  # full give-up
+                  (4000, 2200001, 0, "clustered", 3),                 # the build side's MSD sort gives up -> LSD
+                  (4000, 1200000, 0, "hot", 10),                      # a run beyond the kernel -> composites
+                  (37, 1 << 20, 0, "rowid", 3),                       # cut runs, strided pass
+                  (100, 1 << 21, 0, "ties7", 10),                     # cut runs -> composites
+                  (300000, 1 << 23, 0, "rowid", 3),                   # grouped ranks
+                  (280000, 5000000, 0, "wide", 10)])                  # grouped ranks, no room -> composites
+    exs.close()
+    exc = executor(HMJ_GTABLE_SORT_FANOUT=1, HMJ_GTABLE_SORT_SLAB_MIN_LOG2=20, HMJ_RANK_RUNS=0)
+    exc.set_profiling(True)
+    ordered(exc, [(1000, (1 << 22) + 5, 0, "ids", 3),                 # the composites' chain succeeds
+                  (4097, 1 << 22, 0, "stride", 10)])                  # ... overflows -> exact passes
+    exc.close()
+    exd = H.Executor(0)  # the gate: refused by the model, admitted; the host entry on the admitted shape
+    exd.set_profiling(True)
+    ordered(exd, [(1000, 300000, 0, "uniform", 3), (1000, 1 << 23, 0, "uniform", 3)], (O | CK,))
+    B, P = relations(exd, 1000, 1 << 23, 0, "uniform")
+    host_join("small gate", exd, B, P, O)
+    exd.release_result()
+    # ---- hmj_sort_u64_device
+    srng = np.random.default_rng(17)
+
+    def rows(keys):
+        return np.stack([keys.astype(np.uint64), np.arange(len(keys), dtype=np.uint64)], 1)
+
+    for n in (12345, 1 << 16):  # no survey
+        record_sort("sort uniform n=%d" % n, exd, rows(srng.integers(0, 1 << 63, n, dtype=np.uint64)))
+    n = (1 << 22) + 4099
+    record_sort("sort uniform", exd, rows(srng.integers(0, 1 << 63, n, dtype=np.uint64) * np.uint64(2) + srng.integers(0, 2, n, dtype=np.uint64)))  # MSD
+    exd.forget_workloads()
+    record_sort("sort few_values", exd, rows(srng.integers(0, 5, n).astype(np.uint64) * np.uint64(0x0101010101010101)), repeat=10)  # MSD gives up
+    exd.forget_workloads()
+    record_sort("sort sorted", exd, rows(np.sort(srng.integers(0, 1 << 63, n, dtype=np.uint64))), repeat=10)
+    exd.forget_workloads()
+    n = (1 << 22) + 77
+    d16 = (srng.integers(0, 256, n).astype(np.uint64) << np.uint64(8)) | (srng.integers(0, 200, n).astype(np.uint64) << np.uint64(48))
+    # (a permutation: three digits vary -- in place an odd number of passes, which end in the scratch buffer)
+    for name, keys in (("digits_1_6", d16), ("one_key", np.full(n, 0x1234567890ABCDEF, np.uint64)), ("dense", srng.permutation(n))):
+        record_sort("sort " + name, exd, rows(keys))
+        record_sort("sort %s in place" % name, exd, rows(keys), inplace=True)
+    exd.close()
+    exl = executor(HMJ_SORT_SLAB_MIN_LOG2=20, HMJ_SORT_MSD=0)
+    exl.set_profiling(True)
+    # The chain's success: a permutation of 2^22 + 77 rows, not of 2^20 + 77 -- below 2^22 rows there is no digit survey, the
+    # chain sorts on all eight digits and a permutation's constant top digits overflow a slab.  Without a survey the chain
+    # succeeds on uniform 64-bit keys (2^20 + 77 rows), and overflows on sixteen copies per key.
+    record_sort("sort chain permutation", exl, rows(srng.permutation(n)))  # (surveyed: digits trimmed to the bits that vary)
+    n = (1 << 20) + 77  # (no survey: eight digits of eight bits)
+    record_sort("sort chain uniform", exl, rows(srng.integers(0, 1 << 63, n, dtype=np.uint64) * np.uint64(2) + srng.integers(0, 2, n, dtype=np.uint64)))
+    record_sort("sort chain 16 copies", exl, rows(srng.integers(0, 1 << 63, n >> 4, dtype=np.uint64)[srng.integers(0, n >> 4, n)]), repeat=10)
+    exl.close()
+
+
+SECTION = sys.argv[2] if len(sys.argv) > 2 else "all"  # all | u64 | small | keyed
+if SECTION in ("keyed", "small"):
+    keyed_section() if SECTION == "keyed" else small_section()
     print("ab_calls: %d records from %s" % (n_records, _lib.lib_path()), file=sys.stderr)
     sys.exit(0)
 
@@ -324,5 +456,6 @@ record("too many rows", ex, lambda: raw_join(C.c_void_p(R1.data_ptr()), 1 << 33)
 ex.close()
 exp.close()
 if SECTION == "all":
+    small_section()
     keyed_section()
 print("ab_calls: %d records from %s" % (n_records, _lib.lib_path()), file=sys.stderr)
