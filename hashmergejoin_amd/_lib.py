@@ -279,6 +279,13 @@ class OrderOpts(C.Structure):
                 ("ms_refine", C.c_float), ("ms_map", C.c_float)]
 
 
+# hmj_window_device: window functions over ordered partitions (OVER); hmj_window_fn.op and the cap of a call.  The struct
+# mirrors (WindowFn, WindowDst, WindowOpts) live in _window.py.
+(HMJ_WIN_ROW_NUMBER, HMJ_WIN_RANK, HMJ_WIN_DENSE_RANK, HMJ_WIN_CUM_COUNT, HMJ_WIN_CUM_SUM, HMJ_WIN_CUM_MIN, HMJ_WIN_CUM_MAX,
+ HMJ_WIN_LAG, HMJ_WIN_LEAD) = range(9)
+HMJ_MAX_WINDOW_FNS = 32
+
+
 # hmj_filter_device: a CNF predicate over typed and string columns to a row map (WHERE); hmj_filter_term.type (beside
 # HMJ_TYPE_*), .op and .flags, and the two caps of a call
 HMJ_FILTER_LARGE_STRING = 16
@@ -474,6 +481,7 @@ _SIGNATURES = {
     "hmj_group_mixed_device": (_i, [_vp, _P(MixedRel), _u32, _P(GroupOpts), _P(GroupResult)]),
     "hmj_group_agg_device": (_i, [_vp, _P(AggSrc), _u32, _u, _P(AggDst), _P(GroupAggOpts)]),
     "hmj_order_by_device": (_i, [_vp, _P(OrderCol), _u32, _u, _vp, _P(OrderOpts)]),
+    "hmj_window_device": (_i, [_vp, _P(OrderCol), _u32, _u, _vp, _u32, _vp, _vp, _vp]),
     "hmj_filter_device": (_i, [_vp, _P(FilterTerm), _u32, _u, _vp, _vp, _P(FilterOpts)]),
     "hmj_take_cols_device": (_i, [_vp, _P(TakeSrc), _u32, _u, _vp, _u, _P(TakeDst), _P(TakeOpts)]),
     "hmj_take_str_device": (_i, [_vp, _P(TakeStrSrc), _u, _vp, _u, _P(TakeStrDst), _P(TakeStrOpts)]),

@@ -150,6 +150,16 @@ struct FilterWs {  // hmj_filter_device (filter.hip)
     for (DevBuf* b : {&acc, &blk, &tile, &mask, &lit}) f(*b);
   }
 };
+struct WindowWs {  // hmj_window_device (window.hip)
+  DevBuf acc, phw, ghw,  // the counters; one ballot word per 64 sorted positions: partition heads, peer heads
+      state,             // per word {partitions in front, dense rank carried in, last partition head, last peer head}
+      rec, top;          // the carry: four aggregates per wave range (scanned in place), four totals per carry tile
+  PhaseEvents<4> ev;     // around the order, the heads and the functions' launches
+  template <class F>
+  void each_buf(F f) {
+    for (DevBuf* b : {&acc, &phw, &ghw, &state, &rec, &top}) f(*b);
+  }
+};
 
 enum Kind {
   K_TOTAL = 0, K_H2D, K_D2H, K_HIST, K_SCAN, K_SCATTER, K_OFFSETS, K_PROBE_COUNT, K_OUT_SCAN,
@@ -216,6 +226,7 @@ struct hmj_ctx {
   hmj_host::TakeStrWs takestr_ws;  // hmj_take_str_device
   hmj_host::AggWs agg_ws;          // hmj_group_agg_device
   hmj_host::FilterWs filter_ws;    // hmj_filter_device
+  hmj_host::WindowWs window_ws;    // hmj_window_device
   int memo_kind = 0;  // workload-signature kind of plain inner joins run on behalf of another entry (string, multi-column joins and their kinds), and of the sorts hmj_order_by_device runs
   HostBuf h_accum, h_key, h_rval, h_sval;
   int host_threads = 0;  // staging threads for pageable input (0 = default)

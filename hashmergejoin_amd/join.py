@@ -17,8 +17,9 @@ from . import _marshal as M
 from ._lib import (HMJ_CHECKSUM, HMJ_FIRST_WINS, HMJ_MATERIALIZE, HMJ_ORDERED, HMJ_SUM_PROBE,  # noqa: F401
                    HmjError, JoinResult, Timing)
 from ._marshal import _memcpy_d2d  # noqa: F401  (bench.py, tools/ and tests import it from here)
+from ._window import WindowDst, WindowFn, WindowOpts
 from .reference import (cols_key64, expected_filter, expected_group_aggs, expected_groups,  # noqa: F401
-                        expected_mixed_groups, expected_order_by, mixed_key64, order_stream_bytes)
+                        expected_mixed_groups, expected_order_by, expected_window, mixed_key64, order_stream_bytes)
 
 SEED_B = 0x243F6A8885A308D3
 
@@ -572,17 +573,8 @@ class Executor:
                 M.read_info(opts, ("n_groups",), ("ms_agg",)))
 
     # ---- ORDER BY: typed, string and mixed keys to a row map (hmj_order_by_device) ---------------------------
-    def order_by_device(self, cols, n=None):
-        """A stable multi-column ORDER BY (hmj_order_by_device).  cols: a list of (column, flags[, valid[, bit_offset]]) --
-        column a contiguous 1-D device tensor of an integer or float dtype of 1 to 8 bytes (the HMJ_TYPE_* is inferred), or a
-        (chars, offsets) pair as `pack_strings` makes it (an Arrow large_string column: chars uint8 or None, offsets int64
-        [n + 1]); flags HMJ_ORDER_DESC | HMJ_ORDER_NULLS_FIRST bits; valid None or a contiguous 1-D device tensor holding the
-        column's Arrow bitmap (`pack_validity`), row i at bit bit_offset + i.  n: the rows (default: the first column's).
-        Returns (row map: a new int64 device tensor of n entries, map[j] = the row at sorted position j, {"n_distinct",
-        "n_tied_rows", "n_rounds", "ms_key", "ms_sort", "ms_refine", "ms_map"}); `expected_order_by` reproduces the map, and
-        `take_cols_device` / `take_str_device` consume it."""
-        torch = self._torch
-        self._sync_stream()
+    def _order_cols(self, cols, n):
+        """The key columns of `order_by_device` and `window_device` -> (the hmj_order_col array, its entries, n, what must stay alive)."""
         cols = [tuple(c) for c in cols]
         if n is None and cols:
             first = cols[0][0]
@@ -605,11 +597,85 @@ class Executor:
                 keep.append(col)
             arr[k].flags = flags & 0xFFFFFFFF
             keep.append(M.validity(arr[k].validity, _valid_at(c, 2), n, "column %d", k, any_width=True))
+        return arr, len(cols), n, keep
+
+    def order_by_device(self, cols, n=None):
+        """A stable multi-column ORDER BY (hmj_order_by_device).  cols: a list of (column, flags[, valid[, bit_offset]]) --
+        column a contiguous 1-D device tensor of an integer or float dtype of 1 to 8 bytes (the HMJ_TYPE_* is inferred), or a
+        (chars, offsets) pair as `pack_strings` makes it (an Arrow large_string column: chars uint8 or None, offsets int64
+        [n + 1]); flags HMJ_ORDER_DESC | HMJ_ORDER_NULLS_FIRST bits; valid None or a contiguous 1-D device tensor holding the
+        column's Arrow bitmap (`pack_validity`), row i at bit bit_offset + i.  n: the rows (default: the first column's).
+        Returns (row map: a new int64 device tensor of n entries, map[j] = the row at sorted position j, {"n_distinct",
+        "n_tied_rows", "n_rounds", "ms_key", "ms_sort", "ms_refine", "ms_map"}); `expected_order_by` reproduces the map, and
+        `take_cols_device` / `take_str_device` consume it."""
+        torch = self._torch
+        self._sync_stream()
+        arr, n_cols, n, keep = self._order_cols(cols, n)
         out = torch.empty(n, dtype=torch.int64, device=self._dev)
         opts = M.new_opts(_lib.OrderOpts)
-        self._check(self.L.hmj_order_by_device(self.h, arr, len(cols), n, out.data_ptr() if n else None, C.byref(opts)))
+        self._check(self.L.hmj_order_by_device(self.h, arr, n_cols, n, out.data_ptr() if n else None, C.byref(opts)))
         del keep
         return out, M.read_info(opts, ("n_distinct", "n_tied_rows", "n_rounds"), ("ms_key", "ms_sort", "ms_refine", "ms_map"))
+
+    # ---- OVER: window functions over ordered partitions (hmj_window_device) -----------------------------------
+    def window_device(self, keys, n_partition_cols, fns, n=None, want_validity=True):
+        """Window functions over ordered partitions (hmj_window_device).  keys: as `order_by_device` takes its columns (may be
+        empty: one partition in row order); the first n_partition_cols of them are PARTITION BY, the rest ORDER BY.  fns: a
+        list of (op, column_or_None, valid=None, bit_offset=0, offset=0) -- op an HMJ_WIN_* code; column a contiguous 1-D
+        device tensor of an integer or float dtype of 1 to 8 bytes (the HMJ_TYPE_* is inferred), None where the op reads no
+        value; valid None or the column's Arrow bitmap on the device (uint8 bytes or 64-bit words), row i at bit bit_offset
+        + i; offset the rows HMJ_WIN_LAG / HMJ_WIN_LEAD look away.  n: the rows (default: the first key column's, else the
+        first function column's).  want_validity: True, False, or one bool per function.  The outputs are new tensors in
+        SORTED order -- slot j belongs to row row_map[j] --: uint64 for the ranking functions and CUM_COUNT, int64 / uint64 /
+        float64 for CUM_SUM, the source dtype otherwise.  Returns (row_map, [(values, validity words or None, null_count),
+        ...], {"n_partitions", "n_peer_groups", "max_partition_rows", "n_rounds", "ms_order", "ms_heads", "ms_scan"});
+        `expected_window` reproduces everything."""
+        torch = self._torch
+        self._sync_stream()
+        fns = [tuple(f) for f in fns]
+        wants = M.want_flags(want_validity, len(fns), "function")
+        if n is None and not keys:
+            lens = [f[1].shape[0] for f in fns if len(f) > 1 and f[1] is not None]
+            n = lens[0] if lens else 0
+        arr, n_keys, n, keep = self._order_cols(keys, n)
+        dev = self._dev
+        src = (WindowFn * max(len(fns), 1))()
+        dst = (WindowDst * max(len(fns), 1))()
+        outs, words = [], []
+        f64, i64 = torch.float64, torch.int64
+        u64 = getattr(torch, "uint64", i64)
+        for k, f in enumerate(fns):
+            op, t = int(f[0]), f[1] if len(f) > 1 else None
+            code = _lib.HMJ_TYPE_U64
+            if t is not None:
+                M.check_column(t, "function %d: the column must be a contiguous 1-D device tensor", k)
+                code = M.type_code(t.dtype)
+                src[k].data = t.data_ptr() if t.shape[0] else None
+                keep.append(t)
+            src[k].type = code
+            src[k].op = op & 0xFFFFFFFF
+            src[k].offset = (int(f[4]) if len(f) > 4 else 0) & M.U64_MASK
+            keep.append(M.validity(src[k].validity, _valid_at(f, 2), n, "function %d", k, any_width=True))
+            if op == _lib.HMJ_WIN_CUM_SUM:
+                dt = f64 if code >= _lib.HMJ_TYPE_F32 else (i64 if code <= _lib.HMJ_TYPE_I64 else u64)
+            elif op in (_lib.HMJ_WIN_CUM_MIN, _lib.HMJ_WIN_CUM_MAX, _lib.HMJ_WIN_LAG, _lib.HMJ_WIN_LEAD) and t is not None:
+                dt = t.dtype
+            else:
+                dt = u64
+            o = torch.empty(n, dtype=dt, device=dev)
+            w = torch.empty((n + 63) // 64, dtype=i64, device=dev) if wants[k] else None
+            dst[k].data = o.data_ptr() if n else None
+            dst[k].validity = w.data_ptr() if (w is not None and n) else None
+            outs.append(o)
+            words.append(w)
+        row_map = torch.empty(n, dtype=i64, device=dev)
+        opts = M.new_opts(WindowOpts, n_partition_cols=n_partition_cols)
+        self._check(self.L.hmj_window_device(self.h, arr, n_keys, n, src, len(fns), dst,
+                                             row_map.data_ptr() if n else None, C.byref(opts)))
+        del keep
+        return (row_map, [(outs[k], words[k], int(dst[k].null_count)) for k in range(len(fns))],
+                M.read_info(opts, ("n_partitions", "n_peer_groups", "max_partition_rows", "n_rounds"),
+                            ("ms_order", "ms_heads", "ms_scan")))
 
     # ---- WHERE: typed and string predicates to a row map (hmj_filter_device) ---------------------------------
     def filter_device(self, terms, n=None, want_mask=False, out=None):

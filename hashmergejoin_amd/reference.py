@@ -1,6 +1,9 @@
 """Host restatements of what the column entries compute (include/hmj.h), in plain numpy: the 64-bit keys of the
-multi-column and mixed-key joins, the groupings and their aggregates, ORDER BY's row map and byte streams, and WHERE.
+multi-column and mixed-key joins, the groupings and their aggregates, ORDER BY's row map and byte streams, WHERE, and the
+window functions.
 The tests and tools compare the device's results with them; nothing here touches ctypes or a GPU."""
+from fractions import Fraction
+
 import numpy as np
 
 from . import _lib
@@ -272,15 +275,9 @@ def _order_columns(columns):
     return out, (n or 0)
 
 
-def expected_order_by(columns):
-    """The row map hmj_order_by_device returns (include/hmj.h), restated on the host from the order rule: columns is a list
-    of (values, flags[, valid]) -- values a numpy array of an integer or float dtype, or a list of bytes (a string column);
-    flags HMJ_ORDER_* bits; valid None or n bools (True = valid).  Per column every row gets the dense rank of its value
-    among the column's valid values -- integers in their signedness, floats in IEEE order with -0.0 < +0.0 and every NaN one
-    value above +inf, strings as Python orders bytes (unsigned bytes, then length) --, reversed under HMJ_ORDER_DESC; a NULL
-    slot ranks behind all of them, or in front under HMJ_ORDER_NULLS_FIRST.  The map is the stable lexicographic order of
-    the rank tuples (ties keep ascending row index).  What lies under a NULL slot is not read.  Returns n uint64."""
-    cols, n = _order_columns(columns)
+def _order_ranks(cols, n):
+    """`_order_columns`' columns -> per column the int64 rank of every row under the order rule (see `expected_order_by`):
+    equal ranks are equal slots, and the stable lexicographic order of the rank tuples is the row map."""
     ranks = []
     for vals, flags, valid, is_str in cols:
         ok = np.ones(n, bool) if valid is None else valid
@@ -304,9 +301,168 @@ def expected_order_by(columns):
         rank[idx] = r
         rank[~ok] = -1 if flags & _lib.HMJ_ORDER_NULLS_FIRST else distinct
         ranks.append(rank)
+    return ranks
+
+
+def expected_order_by(columns):
+    """The row map hmj_order_by_device returns (include/hmj.h), restated on the host from the order rule: columns is a list
+    of (values, flags[, valid]) -- values a numpy array of an integer or float dtype, or a list of bytes (a string column);
+    flags HMJ_ORDER_* bits; valid None or n bools (True = valid).  Per column every row gets the dense rank of its value
+    among the column's valid values -- integers in their signedness, floats in IEEE order with -0.0 < +0.0 and every NaN one
+    value above +inf, strings as Python orders bytes (unsigned bytes, then length) --, reversed under HMJ_ORDER_DESC; a NULL
+    slot ranks behind all of them, or in front under HMJ_ORDER_NULLS_FIRST.  The map is the stable lexicographic order of
+    the rank tuples (ties keep ascending row index).  What lies under a NULL slot is not read.  Returns n uint64."""
+    cols, n = _order_columns(columns)
+    ranks = _order_ranks(cols, n)
     if n == 0:
         return np.zeros(0, np.uint64)
     return np.lexsort(ranks[::-1]).astype(np.uint64)  # (lexsort: the last key is the primary one; stable)
+
+
+def expected_window(key_columns, n_partition_cols, fns, n=None):
+    """What hmj_window_device returns (include/hmj.h), restated on the host.  key_columns as `expected_order_by` takes them
+    (may be empty: one partition in row order; n then comes from the first function column, or from `n`); the first
+    n_partition_cols are PARTITION BY, the rest ORDER BY.  fns: a list of (op, values[, valid[, bit_offset[, offset]]]) as
+    `Executor.window_device` takes them, with host values -- op an HMJ_WIN_* code; values a numpy array of n integers or
+    floats, or None where the op reads no value; valid None or n bools per ROW (True = valid; bit_offset is not looked at);
+    offset the rows LAG / LEAD look away.  The order is `expected_order_by`'s; two neighbours of it are in one partition
+    (peer group) when their ranks are equal in every partition (every) column; everything else is a walk over the sorted
+    positions.  What lies under a NULL slot is not read.  Returns {"row_map" (n uint64), "n_partitions", "n_peer_groups",
+    "max_partition_rows", "outputs"}; outputs holds one dict per function, in SORTED order: "values" (n entries of the
+    output dtype, 0 in a NULL slot), "valid" (n bools), "null_count"; a float CUM_SUM also has "count" (the prefix's valid
+    values, int64) and "abs_sum" (float64: the prefix's sum of |x|) for the error bound, and its values are the correctly
+    rounded exact prefix sums where the partition's values are finite, sequential IEEE additions where they are not."""
+    cols, nk = _order_columns(key_columns)
+    fns = [tuple(f) for f in fns]
+    if cols:
+        n = nk
+    elif n is None:
+        lens = [len(f[1]) for f in fns if len(f) > 1 and f[1] is not None]
+        n = lens[0] if lens else 0
+    n = int(n)
+    npc = int(n_partition_cols)
+    if not 0 <= npc <= len(cols):
+        raise ValueError("n_partition_cols must be in 0..len(key_columns)")
+    ranks = _order_ranks(cols, n)
+    row_map = np.lexsort(ranks[::-1]).astype(np.int64) if (cols and n) else np.arange(n, dtype=np.int64)
+    pos = np.arange(n, dtype=np.int64)
+    phead, ghead = np.zeros(n, bool), np.zeros(n, bool)
+    if n:
+        phead[0] = True
+        for k, r in enumerate(ranks):
+            s = r[row_map]
+            d = s[1:] != s[:-1]
+            if k < npc:
+                phead[1:] |= d
+            ghead[1:] |= d
+        ghead |= phead
+    pid = np.cumsum(phead) - 1
+    starts = np.nonzero(phead)[0]
+    ps = starts[pid] if n else pos
+    plen = np.bincount(pid, minlength=len(starts)) if n else np.zeros(0, np.int64)
+    pe = ps + plen[pid] if n else pos  # one behind the partition's last position
+    gs = np.maximum.accumulate(np.where(ghead, pos, 0)) if n else pos
+    gcum = np.cumsum(ghead)
+    res = {"row_map": row_map.astype(np.uint64), "n_partitions": int(len(starts)), "n_peer_groups": int(np.count_nonzero(ghead)),
+           "max_partition_rows": int(plen.max()) if n else 0, "outputs": []}
+    for k, f in enumerate(fns):
+        op = int(f[0])
+        vals = f[1] if len(f) > 1 else None
+        valid = None if len(f) < 3 or f[2] is None else np.asarray(f[2], bool).ravel()
+        off = int(f[4]) if len(f) > 4 else 0
+        out = {}
+        if op == _lib.HMJ_WIN_ROW_NUMBER:
+            v, ok = pos - ps + 1, np.ones(n, bool)
+        elif op == _lib.HMJ_WIN_RANK:
+            v, ok = gs - ps + 1, np.ones(n, bool)
+        elif op == _lib.HMJ_WIN_DENSE_RANK:
+            v, ok = (gcum - gcum[ps] + 1) if n else pos, np.ones(n, bool)
+        else:
+            if valid is not None and len(valid) != n:
+                raise ValueError("function %d: valid must hold n entries" % k)
+            have = (np.ones(n, bool) if valid is None else valid)[row_map]
+            cnt = np.cumsum(have)
+            cnt = (cnt - (cnt[ps] - have[ps])) if n else cnt  # the prefix's valid values
+            if op == _lib.HMJ_WIN_CUM_COUNT:
+                v, ok = cnt, np.ones(n, bool)
+            else:
+                if vals is None:
+                    raise ValueError("function %d: the op reads values" % k)
+                a = np.ascontiguousarray(vals).ravel()
+                if len(a) != n or a.dtype.kind not in "iuf" or a.dtype.itemsize > 8 or a.dtype == np.float16:
+                    raise ValueError("function %d: values: n integers or floats of 1 to 8 bytes" % k)
+                x = a[row_map]
+                is_float = a.dtype.kind == "f"
+                if op in (_lib.HMJ_WIN_LAG, _lib.HMJ_WIN_LEAD):
+                    off = min(off, n)  # (n rows away is outside every partition, like anything beyond it)
+                    jj = pos - off if op == _lib.HMJ_WIN_LAG else pos + off
+                    ok = (jj >= ps) & (jj < pe)
+                    at = np.where(ok, jj, 0).astype(np.int64)
+                    ok = ok & have[at] if n else ok
+                    v = np.where(ok, x[at] if n else x, a.dtype.type(0))
+                elif op == _lib.HMJ_WIN_CUM_SUM and not is_float:
+                    wide = x.astype(np.int64).view(np.uint64) if a.dtype.kind == "i" else x.astype(np.uint64)
+                    wide = np.where(have, wide, np.uint64(0))
+                    cs = np.cumsum(wide, dtype=np.uint64)  # (wraps mod 2^64)
+                    v = (cs - (cs[ps] - wide[ps])) if n else cs
+                    v = v.view(np.int64) if a.dtype.kind == "i" else v
+                    ok = cnt > 0
+                elif op == _lib.HMJ_WIN_CUM_SUM:
+                    xd = np.where(have, x.astype(np.float64), 0.0)
+                    v, abss = np.zeros(n), np.zeros(n)
+                    with np.errstate(all="ignore"):
+                        for s0, ln in zip(starts, plen):
+                            seg, hv = xd[s0:s0 + ln], have[s0:s0 + ln]
+                            abss[s0:s0 + ln] = np.cumsum(np.abs(seg))
+                            if np.all(np.isfinite(seg)):
+                                run, exact = Fraction(0), []
+                                for y, h in zip(seg.tolist(), hv.tolist()):
+                                    if h:
+                                        run += Fraction(y)
+                                    exact.append(run)
+                                try:
+                                    v[s0:s0 + ln] = [float(e) for e in exact]
+                                except OverflowError:
+                                    v[s0:s0 + ln] = np.cumsum(seg)
+                            else:  # as IEEE addition has it, in order
+                                run = None
+                                for i, (y, h) in enumerate(zip(seg, hv)):
+                                    if h:
+                                        run = y if run is None else run + y
+                                    v[s0 + i] = 0.0 if run is None else run
+                    ok = cnt > 0
+                    out.update({"count": cnt.astype(np.int64), "abs_sum": abss})
+                elif op in (_lib.HMJ_WIN_CUM_MIN, _lib.HMJ_WIN_CUM_MAX):
+                    low = op == _lib.HMJ_WIN_CUM_MIN
+                    acc_fn = np.minimum.accumulate if low else np.maximum.accumulate
+                    if is_float:
+                        keys, nan = _float_order_keys(x)
+                        ident = keys.dtype.type(np.iinfo(keys.dtype).max if low else 0)
+                        keys = np.where(have & ~nan, keys, ident)
+                        numbers = np.cumsum(have & ~nan)
+                        numbers = (numbers - (numbers[ps] - (have & ~nan)[ps])) if n else numbers
+                        acc = keys.copy()
+                        for s0, ln in zip(starts, plen):
+                            acc[s0:s0 + ln] = acc_fn(keys[s0:s0 + ln])
+                        top = keys.dtype.type(1 << (8 * a.dtype.itemsize - 1))
+                        v = np.where(acc & top, acc ^ top, ~acc).view(a.dtype).copy()
+                        v[numbers == 0] = np.nan  # (numpy's default NaN is the canonical quiet one)
+                    else:
+                        info = np.iinfo(a.dtype)
+                        y = np.where(have, x, a.dtype.type(info.max if low else info.min))
+                        v = y.copy()
+                        for s0, ln in zip(starts, plen):
+                            v[s0:s0 + ln] = acc_fn(y[s0:s0 + ln])
+                    ok = cnt > 0
+                else:
+                    raise ValueError("function %d: unknown op %d" % (k, op))
+        if op <= _lib.HMJ_WIN_CUM_COUNT:
+            v = np.asarray(v).astype(np.uint64)
+        v = np.array(v)
+        v[~ok] = 0
+        out.update({"values": v, "valid": ok, "null_count": int(n - np.count_nonzero(ok))})
+        res["outputs"].append(out)
+    return res
 
 
 def order_stream_bytes(columns):

@@ -1162,6 +1162,117 @@ typedef struct {
 int hmj_order_by_device(hmj_ctx* ctx, const hmj_order_col* cols, uint32_t n_cols, uint64_t n, uint64_t* row_map_out,
                         hmj_order_opts* opts);
 
+/* ---- window functions over ordered partitions (OVER) ------------------------------------------------------ */
+/* A value for EVERY row that depends on the row's neighbours in an ordered partition: up to HMJ_MAX_WINDOW_FNS functions --
+ * ROW_NUMBER, RANK, DENSE_RANK, running COUNT / SUM / MIN / MAX, LAG and LEAD -- over one OVER (PARTITION BY keys[0 ..
+ * n_partition_cols) ORDER BY the rest of keys) clause, in one call.  Every other entry answers with one row per group or
+ * with a row map.  "Top 3 per group" is ROW_NUMBER here followed by hmj_filter_device on the output column (the top k of the
+ * whole table is the first k entries of hmj_order_by_device's map).  Nothing in the reference corresponds.  A new entry with
+ * structs of its own: no other entry, struct, flag or path bit changes.
+ * keys is a HOST array of n_keys entries, 0 <= n_keys <= HMJ_MAX_ORDER_COLS, exactly what hmj_order_by_device takes; fns
+ * and dst are HOST arrays of n_fns entries (read during the call only; dst[a].null_count is written); everything they point
+ * to is on the device and caller-owned.  n is at most 2^32 - 1.
+ * Order.  The rows are ordered by all keys under hmj_order_by_device's rule: stable, ties keep ascending row index, so the
+ * order is total and every output is a function of the inputs alone.  n_keys == 0 is the identity order: one partition of
+ * all rows, and no sort runs.  n_partition_cols == n_keys gives partitions whose rows keep the input's order (pandas'
+ * groupby(k).cumsum()).  HMJ_ORDER_DESC / HMJ_ORDER_NULLS_FIRST on a partition column only decide where the partitions lie in
+ * the map.
+ * Partitions and peers.  Two rows are in one partition when they are equal in every partition column under the ORDER BY's
+ * own equality: two NULL slots are equal; every NaN is one value; -0.0 and +0.0 differ; strings are equal in length and
+ * bytes.  Rows that this equality joins are exactly the rows the sort leaves next to each other, so a partition is one
+ * contiguous run of sorted positions.  Peers are rows of one partition that are equal in every order column under the same
+ * rule; without order columns a whole partition is one peer group.
+ * Output layout.  Slot j of every output belongs to the row at sorted position j, row row_map_out[j]: the outputs are
+ * written coalesced, in partition order.  row_map_out is caller-owned device memory of n uint64, aligned to 8, required
+ * when n > 0.  Other columns are lined up with the outputs by a take through row_map_out.  A caller who wants the input's
+ * row order takes the outputs through the inverse map, which is hmj_order_by_device on row_map_out as one HMJ_TYPE_U64
+ * column.  dst[a].validity != NULL: ceil(n / 64) 64-bit words are written exactly as hmj_agg_dst's (slot j = bit j & 63 of
+ * word j >> 6, padding bits 0).  dst[a].null_count is filled with or without a bitmap.  The value bytes of a NULL slot are 0.
+ * Frame.  The cumulative functions use ROWS BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW: the partition's first row through
+ * this row.  That is NOT SQL's default RANGE frame: peers do not share a value.
+ * Values.  Validity, sign and zero extension, wrapping 64-bit integer sums and float sums in double follow
+ * hmj_group_agg_device word for word, and so do MIN / MAX: in the source type and signedness, floats in IEEE order with
+ * -0.0 < +0.0, a NaN losing against any number, a prefix whose valid values are all NaN giving the canonical quiet NaN.
+ * CUM_SUM / CUM_MIN / CUM_MAX are NULL until the partition's first valid value.  CUM_COUNT is never NULL; its data may be
+ * NULL.  ROW_NUMBER, RANK and DENSE_RANK read no source: data, type beyond being a known one, validity and offset are
+ * ignored.  LAG / LEAD: the slot is NULL when the position `offset` rows away lies outside the partition or the source slot
+ * there is NULL; offset is any uint64, 0 is the row itself, and j + offset is never formed where it could wrap.  A partition
+ * boundary resets every carry by selection: a NaN or an infinity of one partition never reaches another, nothing is
+ * multiplied away.
+ * Float sums are deterministic as hmj_group_agg_device's: the same inputs give the same bits whatever ran before on the ctx
+ * and whatever other functions share the call.  The order of the additions is fixed by sorted position in a fixed shape (a
+ * segmented scan inside chunks of 64 positions, the chunks of a wave's 512 positions in ascending order, the waves'
+ * aggregates in tiles of 2048 -- 8 per lane, a wave scan, the waves in order --, the tiles' totals the same way); there is
+ * no atomic on a value.  |got - exact| <= gamma_k * sum|x| over the prefix, gamma_k = k u / (1 - k u), u = 2^-53, k the
+ * prefix's valid count, as for any bracketing.
+ * Context.  The call has a workspace of its own.  The order comes from hmj_order_by_device on row_map_out, and the call
+ * shares that entry's effects and nothing more: a prepared build side is discarded; the lifetime of the last JOIN result
+ * ends where a sort runs; what the sorts learn is kept under signature kind 25; hmj_last_plan / hmj_last_timing are left
+ * alone; the group result and the live grouping are kept.  It returns with the work complete on the ctx stream.
+ * opts (out): n_partitions, n_peer_groups, max_partition_rows (the longest partition); n_rounds of the internal ORDER BY
+ * (0 where none ran); with hmj_set_profiling ms_order (the ORDER BY), ms_heads (heads, their carry and the positions'
+ * state), ms_scan (every function's launches).
+ * n == 0: HMJ_OK, the counters and null counts are 0, nothing is written on the device, and no argument that is only
+ * checked with n > 0 is looked at.
+ * HMJ_E_ARG, found by the host before any launch (hmj_last_error names what was wrong): NULL ctx / fns / dst / opts; NULL
+ * keys with n_keys > 0; n_keys > HMJ_MAX_ORDER_COLS; n_partition_cols > n_keys; opts->struct_size smaller than through
+ * `reserved`; non-zero reserved; n_fns outside 1..HMJ_MAX_WINDOW_FNS; an unknown op or type; more than 2^32 - 1 rows; with
+ * n > 0: NULL or misaligned source data of a function that reads values (CUM_SUM / CUM_MIN / CUM_MAX / LAG / LEAD), NULL or
+ * misaligned dst[a].data, a dst[a].validity not aligned to 8, NULL or misaligned row_map_out, bit_offset + n overflowing 64
+ * bits, a destination range (data, bitmap, map) that overlaps a source column, a key column, a bitmap or another
+ * destination (address ranges).  Everything hmj_order_by_device rejects in keys is HMJ_E_ARG in that entry's wording, its
+ * device-found offset errors included.  The ctx stays usable after any error.
+ * How (DESIGN.md "Window functions over ordered partitions").  window_heads_kernel: a wave walks 8 chunks of 64 sorted
+ * positions, a lane compares rows map[j] and map[j - 1] column by column (validity, then value; strings by length, then
+ * bytes) -- a row's fixed-width keys are gathered once, by the lane of its position, and reach the lane above by __shfl_up
+ * --, the ballots of "partition head" and "peer head" are one word each per chunk, partitions and peer
+ * groups are counted by popcount (one atomic per workgroup), and the wave stores one aggregate of the positions' state.
+ * window_carry_kernel scans the waves' aggregates -- four slots of {accumulator, valid count, saw a head}, a head selecting
+ * the right operand -- in tiles, and once more over the tiles' totals; window_state_kernel gives every chunk its
+ * {partitions in front, dense rank carried in, last partition head, last peer head} and finds the longest partition.
+ * window_rank_kernel, up to 4 functions per launch: ROW_NUMBER, RANK and DENSE_RANK from that state and the two words,
+ * LAG / LEAD by comparing the partition of position j -+ offset and one gather.  window_scan_kernel, up to 4 functions per
+ * launch, runs twice: a wave walks its 8 chunks, loads the map entry and the head word once for all functions, issues every
+ * gather before the segmented __shfl_up scan and stores its aggregates; behind the carry the same walk starts from the
+ * carried value and writes the outputs, a bitmap word per ballot, NULLs counted by popcount.  One read-back of the counters.
+ * Known cost: the cumulative functions gather their sources twice; window_heads_kernel reads both neighbours' strings whole.
+ * Out of scope: RANGE and sliding frames; NTILE / PERCENT_RANK / FIRST_VALUE / LAST_VALUE; string-valued LAG / LEAD;
+ * whole-partition aggregates (group, aggregate, then a take through group_of_row); the exchange path, host-resident
+ * columns.                                                                                                              */
+#define HMJ_WIN_ROW_NUMBER 0u  /* -> uint64, 1-based position in the partition; never NULL; reads no source               */
+#define HMJ_WIN_RANK       1u  /* -> uint64, ROW_NUMBER of the first row of this row's peer group                          */
+#define HMJ_WIN_DENSE_RANK 2u  /* -> uint64, peer groups of the partition up to and including this row's                   */
+#define HMJ_WIN_CUM_COUNT  3u  /* -> uint64, valid source values from the partition's first row through this row           */
+#define HMJ_WIN_CUM_SUM    4u  /* -> int64 / uint64 / double, as HMJ_AGG_SUM                                               */
+#define HMJ_WIN_CUM_MIN    5u  /* -> the source type, as HMJ_AGG_MIN                                                       */
+#define HMJ_WIN_CUM_MAX    6u
+#define HMJ_WIN_LAG        7u  /* -> the source type: the value `offset` rows earlier in the partition                     */
+#define HMJ_WIN_LEAD       8u  /* ... `offset` rows later                                                                   */
+#define HMJ_MAX_WINDOW_FNS 32
+typedef struct {
+  const void* data;       /* device: n values of `type`, aligned to their width; NULL legal where the op reads no value */
+  uint32_t type;          /* HMJ_TYPE_*                                                                              */
+  uint32_t op;            /* HMJ_WIN_*                                                                               */
+  hmj_validity validity;  /* source bitmap, any bit_offset; bits == NULL: the column has no NULL                     */
+  uint64_t offset;        /* HMJ_WIN_LAG / HMJ_WIN_LEAD: rows away; any value                                        */
+} hmj_window_fn;
+typedef struct {
+  void* data;             /* device, caller-owned: n values of the function's output type, aligned to it             */
+  uint64_t* validity;     /* device, caller-owned, or NULL: ceil(n / 64) 64-bit words, padding bits written as 0     */
+  uint64_t null_count;    /* out: NULL slots of this output column (filled with or without bitmap)                   */
+} hmj_window_dst;
+typedef struct {
+  uint32_t struct_size;        /* size-versioned like the other opts                                                 */
+  uint32_t n_partition_cols;   /* in: the first n_partition_cols of keys are PARTITION BY, the rest ORDER BY         */
+  uint64_t n_partitions, n_peer_groups, max_partition_rows;  /* out                                                  */
+  uint32_t n_rounds;           /* out: hmj_order_opts.n_rounds of the internal ORDER BY (0 where none ran)           */
+  uint32_t reserved;           /* 0                                                                                  */
+  float ms_order, ms_heads, ms_scan;  /* out, with hmj_set_profiling                                                 */
+} hmj_window_opts;
+int hmj_window_device(hmj_ctx* ctx, const hmj_order_col* keys, uint32_t n_keys, uint64_t n,
+                      const hmj_window_fn* fns, uint32_t n_fns, hmj_window_dst* dst,
+                      uint64_t* row_map_out, hmj_window_opts* opts);
+
 /* ---- taking fixed-width columns through a row map (Arrow validity out) --------------------------------- */
 /* The joins above return gather maps (r_row / s_row), not columns.  This entry turns a map back into Arrow columns: up to
  * HMJ_MAX_TAKE_COLS fixed-width columns of ONE relation (n_src rows each; keys, payloads, anything of 1, 2, 4, 8 or 16
