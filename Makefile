@@ -4,12 +4,12 @@ HIPCC    ?= /opt/rocm/bin/hipcc
 ARCH     ?= gfx950
 HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-function
 CSRC     := hashmergejoin_amd/csrc
-OBJS     := $(CSRC)/radix.o $(CSRC)/probe.o $(CSRC)/gen.o $(CSRC)/gtable.o $(CSRC)/api.o $(CSRC)/exchange.o $(CSRC)/strjoin.o $(CSRC)/coljoin.o $(CSRC)/mixjoin.o $(CSRC)/take.o $(CSRC)/takestr.o $(CSRC)/groupagg.o $(CSRC)/orderby.o $(CSRC)/filter.o $(CSRC)/window.o
+OBJS     := $(CSRC)/radix.o $(CSRC)/probe.o $(CSRC)/gen.o $(CSRC)/gtable.o $(CSRC)/api.o $(CSRC)/exchange.o $(CSRC)/strjoin.o $(CSRC)/coljoin.o $(CSRC)/mixjoin.o $(CSRC)/take.o $(CSRC)/takestr.o $(CSRC)/groupagg.o $(CSRC)/orderby.o $(CSRC)/filter.o $(CSRC)/window.o $(CSRC)/topk.o
 LIB      := hashmergejoin_amd/libhmj_hip.so
 
 all: $(LIB) oracle cpptest tests/cpp/strgen_bench examples/hashjoin_bench_hip examples/exchange_join
 
-$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/hmj_dev.h $(CSRC)/hmj_launch.h $(CSRC)/hmj_ctx.h $(CSRC)/hmj_args.h $(CSRC)/hmj_smallplan.h $(CSRC)/hmj_winplan.h $(CSRC)/hmj_entry.h $(CSRC)/hmj_keyjoin.h $(CSRC)/hmj_tuplejoin.h $(CSRC)/hmj_group.h $(CSRC)/hmj_strkey.h include/hmj.h
+$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/hmj_dev.h $(CSRC)/hmj_launch.h $(CSRC)/hmj_ctx.h $(CSRC)/hmj_args.h $(CSRC)/hmj_smallplan.h $(CSRC)/hmj_winplan.h $(CSRC)/hmj_topkplan.h $(CSRC)/hmj_order.h $(CSRC)/hmj_entry.h $(CSRC)/hmj_keyjoin.h $(CSRC)/hmj_tuplejoin.h $(CSRC)/hmj_group.h $(CSRC)/hmj_strkey.h include/hmj.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(LIB): $(OBJS)

@@ -7,12 +7,13 @@ library or a GPU is missing, calls raise.
 """
 from . import _lib
 from ._lib import *  # noqa: F401,F403  (_lib.__all__: the HMJ_* constants, the struct mirrors, HmjError, lib_path, load_library)
+from ._topk import TopKOpts
 from ._window import WindowDst, WindowFn, WindowOpts
 from .join import Executor, HashMergeJoin, pack_strings, pack_validity, plan, unpack_strings, unpack_validity
 from .reference import (cols_key64, expected_filter, expected_group_aggs, expected_groups, expected_mixed_groups,
-                        expected_order_by, expected_window, mixed_key64, order_stream_bytes)
+                        expected_order_by, expected_top_k, expected_window, mixed_key64, order_stream_bytes)
 
 __all__ = _lib.__all__ + ["Executor", "HashMergeJoin", "plan", "pack_strings", "unpack_strings", "pack_validity",
                           "unpack_validity", "cols_key64", "mixed_key64", "expected_groups", "expected_mixed_groups",
                           "expected_group_aggs", "expected_order_by", "order_stream_bytes", "expected_filter", "expected_window",
-                          "WindowFn", "WindowDst", "WindowOpts"]
+                          "WindowFn", "WindowDst", "WindowOpts", "expected_top_k", "TopKOpts"]

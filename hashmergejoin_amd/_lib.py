@@ -285,6 +285,10 @@ class OrderOpts(C.Structure):
  HMJ_WIN_LAG, HMJ_WIN_LEAD) = range(9)
 HMJ_MAX_WINDOW_FNS = 32
 
+# hmj_top_k_device: ORDER BY ... LIMIT k [OFFSET o]; hmj_top_k_opts.plan / .plan_taken.  The struct mirror (TopKOpts) lives
+# in _topk.py.
+HMJ_TOPK_AUTO, HMJ_TOPK_SELECT, HMJ_TOPK_FULL = 0, 1, 2
+
 
 # hmj_filter_device: a CNF predicate over typed and string columns to a row map (WHERE); hmj_filter_term.type (beside
 # HMJ_TYPE_*), .op and .flags, and the two caps of a call
@@ -482,6 +486,7 @@ _SIGNATURES = {
     "hmj_group_agg_device": (_i, [_vp, _P(AggSrc), _u32, _u, _P(AggDst), _P(GroupAggOpts)]),
     "hmj_order_by_device": (_i, [_vp, _P(OrderCol), _u32, _u, _vp, _P(OrderOpts)]),
     "hmj_window_device": (_i, [_vp, _P(OrderCol), _u32, _u, _vp, _u32, _vp, _vp, _vp]),
+    "hmj_top_k_device": (_i, [_vp, _P(OrderCol), _u32, _u, _u, _vp, _vp]),
     "hmj_filter_device": (_i, [_vp, _P(FilterTerm), _u32, _u, _vp, _vp, _P(FilterOpts)]),
     "hmj_take_cols_device": (_i, [_vp, _P(TakeSrc), _u32, _u, _vp, _u, _P(TakeDst), _P(TakeOpts)]),
     "hmj_take_str_device": (_i, [_vp, _P(TakeStrSrc), _u, _vp, _u, _P(TakeStrDst), _P(TakeStrOpts)]),

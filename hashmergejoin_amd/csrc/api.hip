@@ -3111,6 +3111,7 @@ void hmj_destroy(hmj_ctx* c) {
   free_workspace(c->agg_ws);
   free_workspace(c->filter_ws);
   free_workspace(c->window_ws);
+  free_workspace(c->topk_ws);
   HostBuf* hosts[] = {&c->h_accum, &c->h_key, &c->h_rval, &c->h_sval};
   for (HostBuf* b : hosts) free_host(*b);
   for (auto& e : c->events)

@@ -99,7 +99,8 @@ struct GroupWs {
   }
 };
 
-// Workspace of hmj_order_by_device (orderby.hip): no other entry reuses or regrows its buffers.
+// Workspace of hmj_order_by_device (orderby.hip).  hmj_top_k_device (topk.hip) runs the same ORDER BY code in it -- whole, or
+// the refinement loop over its candidates, which it writes into `rows` --; no other entry reuses or regrows its buffers.
 struct OrderWs {
   DevBuf rows, sorted,     // a round's {word, row} rows as keyed, and sorted
       lst[2], rank[2],     // the active rows, round by round in turn: {sorted position, row}, and the rank of the row's segment
@@ -158,6 +159,19 @@ struct WindowWs {  // hmj_window_device (window.hip)
   template <class F>
   void each_buf(F f) {
     for (DevBuf* b : {&acc, &phw, &ghw, &state, &rec, &top}) f(*b);
+  }
+};
+struct TopkWs {  // hmj_top_k_device (topk.hip)
+  DevBuf acc,            // the counters, then a level's histogram bins (one read-back)
+      below, tied,       // one ballot word per 64 rows of the window's population: below the threshold, tied with it
+      blk, blk_off,      // both counts per tile of 256 rows in the halves of one word, and their offsets
+      tie[2], words,     // windows behind the first: the tie list {first stream word, row}, window by window in turn, and
+                         // its rows' words of the current window
+      map;               // the ordered candidates (SELECT), or the whole ORDER BY (FULL); the call copies its slice out
+  PhaseEvents<4> ev;     // around select, emit and order
+  template <class F>
+  void each_buf(F f) {
+    for (DevBuf* b : {&acc, &below, &tied, &blk, &blk_off, &tie[0], &tie[1], &words, &map}) f(*b);
   }
 };
 
@@ -227,7 +241,8 @@ struct hmj_ctx {
   hmj_host::AggWs agg_ws;          // hmj_group_agg_device
   hmj_host::FilterWs filter_ws;    // hmj_filter_device
   hmj_host::WindowWs window_ws;    // hmj_window_device
-  int memo_kind = 0;  // workload-signature kind of plain inner joins run on behalf of another entry (string, multi-column joins and their kinds), and of the sorts hmj_order_by_device runs
+  hmj_host::TopkWs topk_ws;        // hmj_top_k_device
+  int memo_kind = 0;  // workload-signature kind of plain inner joins run on behalf of another entry (string, multi-column joins and their kinds), and of the sorts hmj_order_by_device and hmj_top_k_device run
   HostBuf h_accum, h_key, h_rval, h_sval;
   int host_threads = 0;  // staging threads for pageable input (0 = default)
   std::vector<hipStream_t> up_streams;

@@ -1,6 +1,6 @@
 // Ordering rows by typed, string and mixed keys (hmj_order_by_device; include/hmj.h): a stable multi-column ORDER BY that
 // returns a row map for hmj_take_cols_device / hmj_take_str_device.  Nothing in the reference corresponds beyond its u64
-// sort, which the call uses (hmj_sort_u64_device).  Every row has an order-preserving byte stream (stream_window below)
+// sort, which the call uses (hmj_sort_u64_device).  Every row has an order-preserving byte stream (stream_window, hmj_order.h)
 // whose memcmp order is the requested order; the rows are sorted by that stream, up to eight bytes of it per round:
 //   order_key_kernel      round 0, one lane per row (workgroups walk tiles of 256 rows, grid-stride, as the heads and mark
 //                         kernels do): checks the string columns' offsets (no decrease, no bytes under
@@ -20,7 +20,8 @@
 //                         only.  Resolved rows are never read or written again.
 // The host loop is bounded by 1 + ceil(max(0, S - 8) / 4) rounds (every round consumes at least four bytes).  No device-side
 // spin, no inline assembly; the counters (longest stream, heads, tied rows) take one atomic per workgroup, the offsets'
-// verdict one per wave and column, and only in a wave that holds an offending row.
+// verdict one per wave and column, and only in a wave that holds an offending row.  hmj_top_k_device (topk.hip) shares the
+// stream, the argument checks and the refinement loop (order_refine_rows) through hmj_order.h.
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -28,141 +29,17 @@
 #include <cstring>
 
 #include "hmj_entry.h"
+#include "hmj_order.h"
 
 using hmj::u32;
 using hmj::u64;
 using namespace hmj_host;
 
+using namespace hmj_order;
+
 namespace {
 
-constexpr int OB_THREADS = 256;
-constexpr int OB_WAVES = OB_THREADS / 64;
-constexpr int kMaxCols = HMJ_MAX_ORDER_COLS;
 constexpr int kMemoOrder = 25;  // workload_signature kind of the call's sorts (mixjoin.hip lists the others)
-constexpr u64 kNone = ~0ull;
-
-// acc words: heads and tied rows of a round (cleared per round), the longest stream, and the key kernel's report -- per
-// column the first row whose offsets decrease (~0: none) and the waves that hold key bytes under chars == NULL
-enum { OA_HEADS = 0, OA_TIED, OA_MAXLEN, OA_ERR, OA_NODATA = OA_ERR + kMaxCols, OA_N = OA_NODATA + kMaxCols };
-
-// The key columns, passed to the kernels by value; every loop over them is fully unrolled with a `c < k` guard.
-struct OrdCols {
-  const void* p[kMaxCols];            // values, or a string column's chars
-  const u64* off[kMaxCols];           // string columns: n + 1 offsets
-  const unsigned char* vb[kMaxCols];  // NULL: the column holds no NULL
-  u64 voff[kMaxCols];
-  u32 type[kMaxCols], flags[kMaxCols];
-  u32 k;
-};
-
-// A valid fixed-width value as an unsigned integer of its own width whose order is the type's: signed integers with the
-// sign bit flipped; floats negative -> complement, else sign bit set, every NaN all ones (above +inf's key).
-__device__ __forceinline__ u64 enc_fixed(const void* __restrict__ p, u32 type, u64 r) {
-  const u32 w = width_of(type);
-  u64 x;
-  switch (w) {  // (uniform)
-    case 1: x = reinterpret_cast<const unsigned char*>(p)[r]; break;
-    case 2: x = reinterpret_cast<const unsigned short*>(p)[r]; break;
-    case 4: x = reinterpret_cast<const u32*>(p)[r]; break;
-    default: x = reinterpret_cast<const u64*>(p)[r];
-  }
-  if (type <= HMJ_TYPE_I64) return x ^ (1ull << (8u * w - 1u));
-  if (type == HMJ_TYPE_F32) {
-    const u32 b = (u32)x;
-    if ((b & 0x7fffffffu) > 0x7f800000u) return 0xffffffffull;
-    return (u64)((b >> 31) ? ~b : (b | 0x80000000u));
-  }
-  if (type == HMJ_TYPE_F64) {
-    if ((x & ~(1ull << 63)) > 0x7ff0000000000000ull) return ~0ull;
-    return (x >> 63) ? ~x : (x | (1ull << 63));
-  }
-  return x;
-}
-
-// Bytes [cursor, cursor + nb) of row r's stream, the first one in the top byte of the result, zeros behind the stream's
-// end (nb <= 8; nb == 0: the length alone); len: the stream's length.  Per column: a marker byte when the column has a
-// bitmap (the NULL side as flagged), then
-//   fixed   the key of enc_fixed big-endian, complemented under HMJ_ORDER_DESC; zeros under a NULL slot (no load);
-//   string  nothing under a NULL slot (no byte is read); else max(1, ceil(len / 7)) blocks of 7 data bytes, zero padded,
-//           and a control byte -- 0xFF: the string continues, else the data bytes of this block, 0..7 -- all eight
-//           complemented under HMJ_ORDER_DESC.  Prefix-free, and ordered as (bytes, then length): a shorter string meets
-//           the longer one's 0xFF with its count, or its zero padding with equal data and a smaller count.
-// CHECK (order_key_kernel; every lane of the wave calls, `active` says which hold a row): a string column's offsets are
-// tested before a byte is read, a row that fails reads none and is reported in acc.
-template <bool CHECK>
-__device__ __forceinline__ u64 stream_window(const OrdCols& T, u64 r, bool active, u64 cursor, u32 nb, u64& len, u64* __restrict__ acc) {
-  const int lane = threadIdx.x & 63;
-  u64 pos = 0, out = 0;
-  u32 cnt = 0;
-#pragma unroll
-  for (int c = 0; c < kMaxCols; c++) {
-    if (c < (int)T.k) {  // (kernel arguments: uniform, like every test of T's type, flags and bitmap pointer)
-      const u32 bm = T.vb[c] ? 1u : 0u;
-      bool valid = active;
-      if (bm && active) valid = hmj::valid_bit(T.vb[c], T.voff[c] + r);
-      const u32 inv = (T.flags[c] & HMJ_ORDER_DESC) ? 0xFFu : 0u;
-      const u32 marker = ((T.flags[c] & HMJ_ORDER_NULLS_FIRST) != 0) == valid ? 1u : 0u;
-      u64 L;
-      if (T.type[c] != HMJ_ORDER_LARGE_STRING) {
-        const u32 w = width_of(T.type[c]);
-        L = (u64)(bm + w);
-        if (active && cnt < nb && cursor < pos + L) {
-          const u64 x = valid ? enc_fixed(T.p[c], T.type[c], r) : 0ull;
-          for (u32 j = cursor > pos ? (u32)(cursor - pos) : 0u; j < (u32)L && cnt < nb; j++) {
-            u32 byte = marker;
-            if (!bm || j) {
-              byte = (u32)(x >> (8u * (w - 1u - (j - bm)))) & 0xFFu;
-              if (valid) byte ^= inv;
-            }
-            out |= (u64)byte << (56u - 8u * cnt);
-            cnt++;
-          }
-        }
-      } else {
-        const unsigned char* chars = (const unsigned char*)T.p[c];
-        u64 o0 = 0, o1 = 0;
-        if (active) {
-          o0 = T.off[c][r];
-          o1 = T.off[c][r + 1];
-        }
-        bool usable = true;
-        if (CHECK) {
-          const bool bad = active && o1 < o0;
-          const u64 bad_mask = __ballot(bad);
-          if (bad_mask && lane == (int)__builtin_ctzll(bad_mask)) atomicMin(&acc[OA_ERR + c], r);
-          const bool nodata = valid && !bad && !chars && o1 > o0;  // (a NULL slot holds no key bytes, whatever its offsets span)
-          const u64 nd_mask = __ballot(nodata);
-          if (nd_mask && lane == (int)__builtin_ctzll(nd_mask)) atomicAdd(&acc[OA_NODATA + c], 1ull);
-          usable = !bad && !nodata;
-        }
-        const u64 slen = usable && o1 > o0 ? o1 - o0 : 0ull;
-        const u64 blocks = slen ? (slen + 6) / 7 : 1ull;
-        L = (u64)bm + (valid ? 8ull * blocks : 0ull);
-        if (active && cnt < nb && cursor < pos + L) {
-          for (u64 j = cursor > pos ? cursor - pos : 0ull; j < L && cnt < nb; j++) {
-            u32 byte = marker;
-            if (!bm || j) {
-              const u64 q = j - bm, blk = q >> 3;
-              const u32 in = (u32)(q & 7);
-              if (in < 7) {
-                const u64 at = blk * 7 + in;
-                byte = at < slen ? (u32)chars[o0 + at] : 0u;
-              } else {
-                byte = blk + 1 < blocks ? 0xFFu : (u32)(slen - blk * 7);
-              }
-              byte ^= inv;
-            }
-            out |= (u64)byte << (56u - 8u * cnt);
-            cnt++;
-          }
-        }
-      }
-      pos += L;
-    }
-  }
-  len = pos;
-  return out;
-}
 
 // Round 0.  A workgroup walks tiles of OB_THREADS rows, one lane per row (grid-stride: a grid of a few workgroups per CU
 // keeps the counters at one atomic per workgroup -- one per tile put 2^16 atomics of a 2^24-row call on one address, which
@@ -326,19 +203,49 @@ __global__ __launch_bounds__(OB_THREADS) void order_compact_kernel(const ulonglo
 // ---- host side -----------------------------------------------------------------------------------------------------------
 u64 blocks_of(u64 n) { return (n + OB_THREADS - 1) / OB_THREADS; }
 
-int check_order_args(hmj_ctx* c, const hmj_order_col* cols, u32 n_cols, u64 n, const u64* map, const hmj_order_opts* opts) {
+// the stable u64 sort of a round; it is not a join: hmj_last_plan / hmj_last_timing keep describing the last one
+int sort_round(hmj_ctx* c, const void* in, u64 m, void* out) {
+  const hmj_plan_desc plan = c->plan;
+  const hmj_timing timing = c->timing;
+  c->memo_kind = kMemoOrder;
+  const int rc = hmj_sort_u64_device(c, in, m, out);
+  c->memo_kind = 0;
+  c->plan = plan;
+  c->timing = timing;
+  return rc;
+}
+
+}  // namespace
+
+namespace hmj_order {
+
+void order_cols_of(const hmj_order_col* cols, u32 n_cols, OrdCols* T, u64* fixed_len) {
+  std::memset(T, 0, sizeof(*T));
+  T->k = n_cols;
+  u64 len = 0;
+  bool strings = false;
+  for (u32 k = 0; k < n_cols; k++) {
+    T->p[k] = cols[k].data;
+    T->off[k] = (const u64*)cols[k].offsets;
+    T->vb[k] = (const unsigned char*)cols[k].validity.bits;
+    T->voff[k] = cols[k].validity.bit_offset;
+    T->type[k] = cols[k].type;
+    T->flags[k] = cols[k].flags;
+    if (cols[k].type == HMJ_ORDER_LARGE_STRING) strings = true;
+    else len += (T->vb[k] ? 1u : 0u) + width_of(cols[k].type);
+  }
+  *fixed_len = strings ? 0 : len;
+}
+
+int order_check_cols(hmj_ctx* c, const hmj_order_col* cols, u32 n_cols, u64 n, const u64* map, u64 map_entries) {
   char msg[192];
-  if (!cols || !opts) return fail(c, HMJ_E_ARG, "hmj_order_by_device: cols / opts is NULL");
-  if (opts->struct_size < offsetof(hmj_order_opts, reserved2) + sizeof(opts->reserved2))
-    return fail(c, HMJ_E_ARG, "hmj_order_opts.struct_size too small");
-  if (opts->reserved || opts->reserved2) return fail(c, HMJ_E_ARG, "hmj_order_opts: reserved must be 0");
   if (n_cols < 1 || n_cols > HMJ_MAX_ORDER_COLS) {
     std::snprintf(msg, sizeof(msg), "hmj_order_by_device: n_cols must be in 1..%d", HMJ_MAX_ORDER_COLS);
     return fail(c, HMJ_E_ARG, msg);
   }
   if (n > 0xFFFFFFFFull) return fail(c, HMJ_E_ARG, "hmj_order_by_device: more than 2^32 - 1 rows");
-  if (n > 0 && !map) return fail(c, HMJ_E_ARG, "hmj_order_by_device: row_map_out is NULL");
-  if (n > 0 && ((uintptr_t)map & 7u)) return fail(c, HMJ_E_ARG, "hmj_order_by_device: row_map_out is not aligned to 8 bytes");
+  if (map_entries > 0 && !map) return fail(c, HMJ_E_ARG, "hmj_order_by_device: row_map_out is NULL");
+  if (map_entries > 0 && ((uintptr_t)map & 7u)) return fail(c, HMJ_E_ARG, "hmj_order_by_device: row_map_out is not aligned to 8 bytes");
   for (u32 k = 0; k < n_cols; k++) {
     const hmj_order_col& s = cols[k];
     const bool str = s.type == HMJ_ORDER_LARGE_STRING;
@@ -381,8 +288,8 @@ int check_order_args(hmj_ctx* c, const hmj_order_col* cols, u32 n_cols, u64 n, c
   }
   // The map must not be something the kernels read: address ranges, as hmj_take_cols_device checks them.  The extent of a
   // string column's chars is known on the device only.
-  if (n == 0) return HMJ_OK;
-  const Range out = range_of(map, 8 * n);
+  if (n == 0 || map_entries == 0) return HMJ_OK;
+  const Range out = range_of(map, 8 * map_entries);
   for (u32 k = 0; k < n_cols; k++) {
     const hmj_order_col& s = cols[k];
     const bool str = s.type == HMJ_ORDER_LARGE_STRING;
@@ -395,43 +302,7 @@ int check_order_args(hmj_ctx* c, const hmj_order_col* cols, u32 n_cols, u64 n, c
   return HMJ_OK;
 }
 
-// the stable u64 sort of a round; it is not a join: hmj_last_plan / hmj_last_timing keep describing the last one
-int sort_round(hmj_ctx* c, const void* in, u64 m, void* out) {
-  const hmj_plan_desc plan = c->plan;
-  const hmj_timing timing = c->timing;
-  c->memo_kind = kMemoOrder;
-  const int rc = hmj_sort_u64_device(c, in, m, out);
-  c->memo_kind = 0;
-  c->plan = plan;
-  c->timing = timing;
-  return rc;
-}
-
-int order_rows(hmj_ctx* c, const OrdCols& T, u64 fixed_len, u64 n, u64* map, hmj_order_opts* o) {
-  OrderWs& ws = c->ord_ws;
-  const u64 nblk = blocks_of(n);
-  RC_TRY(ensure_dev(c, ws.acc, OA_N * sizeof(u64)));
-  RC_TRY(ensure_dev(c, ws.rows, 16 * n));
-  RC_TRY(ensure_dev(c, ws.sorted, 16 * n));
-  RC_TRY(ensure_dev(c, ws.heads, (nblk * OB_WAVES + 1) * sizeof(u64)));
-  RC_TRY(ensure_dev(c, ws.act, nblk * OB_WAVES * sizeof(u64)));
-  RC_TRY(ensure_dev(c, ws.acth, nblk * OB_WAVES * sizeof(u64)));
-  RC_TRY(ensure_dev(c, ws.blk, nblk * sizeof(u64)));
-  RC_TRY(ensure_dev(c, ws.blk_off, (nblk + 1) * sizeof(u64)));
-  u64* acc = (u64*)ws.acc.p;
-  ulonglong2* rows = (ulonglong2*)ws.rows.p;
-  ulonglong2* sorted = (ulonglong2*)ws.sorted.p;
-  const dim3 B(OB_THREADS);
-  const u64 most = (u64)c->num_cus * 8;  // workgroups of the grid-stride kernels
-  u64 h[OA_N];
-  // round 0: {first 8 stream bytes, row}; the key kernel's verdict on its input before anything else follows an offset
-  RC_TRY(ws.ev.record(c, 0));
-  HIP_TRY(hipMemsetAsync(acc, 0, OA_N * sizeof(u64), c->stream));
-  HIP_TRY(hipMemsetAsync(acc + OA_ERR, 0xFF, kMaxCols * sizeof(u64), c->stream));
-  hipLaunchKernelGGL(order_key_kernel, dim3((u32)(nblk < most ? nblk : most)), B, 0, c->stream, T, n, rows, acc);
-  HIP_TRY(hipGetLastError());
-  RC_TRY(ws.ev.record(c, 1));
-  RC_TRY(read_back(c, acc, h, sizeof(h)));
+int order_offsets_verdict(hmj_ctx* c, const u64* h) {
   char msg[192];
   for (int k = 0; k < kMaxCols; k++) {  // the lowest-numbered column first, the mixed-key join's wording
     if (h[OA_ERR + k] != kNone) {
@@ -444,9 +315,47 @@ int order_rows(hmj_ctx* c, const OrdCols& T, u64 fixed_len, u64 n, u64* map, hmj
       return fail(c, HMJ_E_ARG, msg);
     }
   }
-  const u64 S = h[OA_MAXLEN];
+  return HMJ_OK;
+}
+
+int order_rows(hmj_ctx* c, const OrdCols& T, u64 fixed_len, u64 n, u64* map, hmj_order_opts* o) {
+  OrderWs& ws = c->ord_ws;
+  const u64 nblk = blocks_of(n);
+  RC_TRY(ensure_dev(c, ws.acc, OA_N * sizeof(u64)));
+  RC_TRY(ensure_dev(c, ws.rows, 16 * n));
+  u64* acc = (u64*)ws.acc.p;
+  const u64 most = (u64)c->num_cus * 8;  // workgroups of the grid-stride kernels
+  u64 h[OA_N];
+  // round 0: {first 8 stream bytes, row}; the key kernel's verdict on its input before anything else follows an offset
+  RC_TRY(ws.ev.record(c, 0));
+  HIP_TRY(hipMemsetAsync(acc, 0, OA_N * sizeof(u64), c->stream));
+  HIP_TRY(hipMemsetAsync(acc + OA_ERR, 0xFF, kMaxCols * sizeof(u64), c->stream));
+  hipLaunchKernelGGL(order_key_kernel, dim3((u32)(nblk < most ? nblk : most)), dim3(OB_THREADS), 0, c->stream, T, n, (ulonglong2*)ws.rows.p, acc);
+  HIP_TRY(hipGetLastError());
+  RC_TRY(ws.ev.record(c, 1));
+  RC_TRY(read_back(c, acc, h, sizeof(h)));
+  RC_TRY(order_offsets_verdict(c, h));
+  return order_refine_rows(c, T, fixed_len, h[OA_MAXLEN], n, n, map, o);
+}
+
+int order_refine_rows(hmj_ctx* c, const OrdCols& T, u64 fixed_len, u64 S, u64 n_rows, u64 m0, u64* map, hmj_order_opts* o) {
+  OrderWs& ws = c->ord_ws;
+  const u64 nblk = blocks_of(m0);
+  RC_TRY(ensure_dev(c, ws.acc, OA_N * sizeof(u64)));
+  RC_TRY(ensure_dev(c, ws.sorted, 16 * m0));
+  RC_TRY(ensure_dev(c, ws.heads, (nblk * OB_WAVES + 1) * sizeof(u64)));
+  RC_TRY(ensure_dev(c, ws.act, nblk * OB_WAVES * sizeof(u64)));
+  RC_TRY(ensure_dev(c, ws.acth, nblk * OB_WAVES * sizeof(u64)));
+  RC_TRY(ensure_dev(c, ws.blk, nblk * sizeof(u64)));
+  RC_TRY(ensure_dev(c, ws.blk_off, (nblk + 1) * sizeof(u64)));
+  u64* acc = (u64*)ws.acc.p;
+  ulonglong2* rows = (ulonglong2*)ws.rows.p;
+  ulonglong2* sorted = (ulonglong2*)ws.sorted.p;
+  const dim3 B(OB_THREADS);
+  const u64 most = (u64)c->num_cus * 8;  // workgroups of the grid-stride kernels
+  u64 h[2];
   const u64 bound = 1 + (S > 8 ? (S - 8 + 3) / 4 : 0);
-  u64 m = n, consumed = 0, heads = 0, segs = 0, tied = 0;
+  u64 m = m0, consumed = 0, heads = 0, segs = 0, tied = 0;
   u32 b = 8, rounds = 0;
   int cur = -1;  // the list of the round's rows; -1: every row, at its position
   for (;;) {
@@ -458,9 +367,9 @@ int order_rows(hmj_ctx* c, const OrdCols& T, u64 fixed_len, u64 n, u64* map, hmj
     const dim3 G((u32)mblk), W((u32)(mblk < most ? mblk : most));
     const ulonglong2* lst = cur < 0 ? nullptr : (const ulonglong2*)ws.lst[cur].p;
     HIP_TRY(hipMemsetAsync(acc, 0, 2 * sizeof(u64), c->stream));  // OA_HEADS, OA_TIED
-    hipLaunchKernelGGL(order_heads_kernel, W, B, 0, c->stream, (const ulonglong2*)sorted, m, n, lst, map, (u64*)ws.heads.p, acc);
+    hipLaunchKernelGGL(order_heads_kernel, W, B, 0, c->stream, (const ulonglong2*)sorted, m, m0, lst, map, (u64*)ws.heads.p, acc);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(order_mark_kernel, W, B, 0, c->stream, T, (const ulonglong2*)sorted, m, n, (const u64*)ws.heads.p, consumed, fixed_len,
+    hipLaunchKernelGGL(order_mark_kernel, W, B, 0, c->stream, T, (const ulonglong2*)sorted, m, n_rows, (const u64*)ws.heads.p, consumed, fixed_len,
                        (u64*)ws.act.p, (u64*)ws.acth.p, (u64*)ws.blk.p, acc);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hmj::launch_scan_u64((const u64*)ws.blk.p, (u64*)ws.blk_off.p, (u32)mblk, c->stream));
@@ -483,7 +392,7 @@ int order_rows(hmj_ctx* c, const OrdCols& T, u64 fixed_len, u64 n, u64* map, hmj
     const u32 s = nseg > 1 ? 64u - (u32)__builtin_clzll(nseg - 1) : 0u;  // bits of a segment's rank (<= 31: 2 nseg <= m2 < 2^32)
     b = (64u - s) / 8u;
     hipLaunchKernelGGL(order_refine_kernel, dim3((u32)blocks_of(m2)), B, 0, c->stream, T, (const ulonglong2*)ws.lst[nxt].p, (const u32*)ws.rank[nxt].p,
-                       m2, n, consumed, b, s, rows);
+                       m2, n_rows, consumed, b, s, rows);
     HIP_TRY(hipGetLastError());
     if (rounds == 1) RC_TRY(ws.ev.record(c, 3));
     m = m2;
@@ -491,7 +400,7 @@ int order_rows(hmj_ctx* c, const OrdCols& T, u64 fixed_len, u64 n, u64* map, hmj
   }
   if (rounds == 1) RC_TRY(ws.ev.record(c, 3));
   RC_TRY(ws.ev.record(c, 4));
-  if (heads < segs + 1 || heads - segs > n) return fail(c, HMJ_E_HIP, "hmj_order_by_device: the heads' count is not in 1..n");
+  if (heads < segs + 1 || heads - segs > m0) return fail(c, HMJ_E_HIP, "hmj_order_by_device: the heads' count is not in 1..n");
   o->n_distinct = heads - segs;  // every active segment of a round was counted as a head of the round before
   o->n_tied_rows = tied;
   o->n_rounds = rounds;
@@ -505,14 +414,18 @@ int order_rows(hmj_ctx* c, const OrdCols& T, u64 fixed_len, u64 n, u64* map, hmj
   return HMJ_OK;
 }
 
-}  // namespace
+}  // namespace hmj_order
 
 extern "C" {
 
 int hmj_order_by_device(hmj_ctx* c, const hmj_order_col* cols, uint32_t n_cols, uint64_t n, uint64_t* row_map_out,
                         hmj_order_opts* opts) {
   if (!c) return HMJ_E_ARG;
-  RC_TRY(check_order_args(c, cols, n_cols, n, (const u64*)row_map_out, opts));
+  if (!cols || !opts) return fail(c, HMJ_E_ARG, "hmj_order_by_device: cols / opts is NULL");
+  if (opts->struct_size < offsetof(hmj_order_opts, reserved2) + sizeof(opts->reserved2))
+    return fail(c, HMJ_E_ARG, "hmj_order_opts.struct_size too small");
+  if (opts->reserved || opts->reserved2) return fail(c, HMJ_E_ARG, "hmj_order_opts: reserved must be 0");
+  RC_TRY(order_check_cols(c, cols, n_cols, n, (const u64*)row_map_out, n));
   // the out fields of opts go to a full-size copy first; the caller gets the prefix its struct_size holds
   hmj_order_opts o;
   opts_prefix_in(&o, opts);
@@ -526,21 +439,9 @@ int hmj_order_by_device(hmj_ctx* c, const hmj_order_col* cols, uint32_t n_cols, 
       o.n_distinct = 1;
     } else {
       OrdCols T;
-      std::memset(&T, 0, sizeof(T));
-      T.k = n_cols;
       u64 fixed_len = 0;
-      bool strings = false;
-      for (u32 k = 0; k < n_cols; k++) {
-        T.p[k] = cols[k].data;
-        T.off[k] = (const u64*)cols[k].offsets;
-        T.vb[k] = (const unsigned char*)cols[k].validity.bits;
-        T.voff[k] = cols[k].validity.bit_offset;
-        T.type[k] = cols[k].type;
-        T.flags[k] = cols[k].flags;
-        if (cols[k].type == HMJ_ORDER_LARGE_STRING) strings = true;
-        else fixed_len += (T.vb[k] ? 1u : 0u) + width_of(cols[k].type);
-      }
-      RC_TRY(order_rows(c, T, strings ? 0 : fixed_len, n, (u64*)row_map_out, &o));
+      order_cols_of(cols, n_cols, &T, &fixed_len);
+      RC_TRY(order_rows(c, T, fixed_len, n, (u64*)row_map_out, &o));
     }
   }
   opts_prefix_out(opts, o);

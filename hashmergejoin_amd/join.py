@@ -17,9 +17,11 @@ from . import _marshal as M
 from ._lib import (HMJ_CHECKSUM, HMJ_FIRST_WINS, HMJ_MATERIALIZE, HMJ_ORDERED, HMJ_SUM_PROBE,  # noqa: F401
                    HmjError, JoinResult, Timing)
 from ._marshal import _memcpy_d2d  # noqa: F401  (bench.py, tools/ and tests import it from here)
+from ._topk import TopKOpts
 from ._window import WindowDst, WindowFn, WindowOpts
 from .reference import (cols_key64, expected_filter, expected_group_aggs, expected_groups,  # noqa: F401
-                        expected_mixed_groups, expected_order_by, expected_window, mixed_key64, order_stream_bytes)
+                        expected_mixed_groups, expected_order_by, expected_top_k, expected_window, mixed_key64,
+                        order_stream_bytes)
 
 SEED_B = 0x243F6A8885A308D3
 
@@ -616,6 +618,34 @@ class Executor:
         self._check(self.L.hmj_order_by_device(self.h, arr, n_cols, n, out.data_ptr() if n else None, C.byref(opts)))
         del keep
         return out, M.read_info(opts, ("n_distinct", "n_tied_rows", "n_rounds"), ("ms_key", "ms_sort", "ms_refine", "ms_map"))
+
+    # ---- ORDER BY ... LIMIT k [OFFSET o] (hmj_top_k_device) ----------------------------------------------------
+    _TOPK_PLANS = {"auto": _lib.HMJ_TOPK_AUTO, "select": _lib.HMJ_TOPK_SELECT, "full": _lib.HMJ_TOPK_FULL}
+
+    def top_k_device(self, cols, k, offset=0, n=None, plan="auto", max_tie_rows=0):
+        """Entries offset .. offset + k of `order_by_device(cols)`'s map without sorting the rows the cut rejects
+        (hmj_top_k_device).  cols and n as `order_by_device` takes them; k and offset are any integers in 0 .. 2^64 - 1 (the
+        sum saturates); plan "auto", "select" (radix selection, then the candidates are ordered) or "full" (the whole ORDER
+        BY, then the slice), or an HMJ_TOPK_* code; max_tie_rows: a set of rows tied with the cut that is larger is narrowed by
+        a further level (0: the library's default).  Returns (row map: a new int64 device tensor of n_out = min(k, n - min(n,
+        offset)) entries, {"n_out", "n_candidates", "n_tie_rows", "plan_taken", "n_levels", "n_rounds", "ms_select",
+        "ms_emit", "ms_order"}); `expected_top_k` reproduces the map."""
+        torch = self._torch
+        self._sync_stream()
+        arr, n_cols, n, keep = self._order_cols(cols, n)
+        k, offset = int(k), int(offset)
+        if not (0 <= k <= M.U64_MASK and 0 <= offset <= M.U64_MASK):
+            raise ValueError("k and offset must be in 0 .. 2^64 - 1")
+        lo = min(offset, n)
+        n_out = min(k, n - lo)
+        out = torch.empty(n_out, dtype=torch.int64, device=self._dev)
+        opts = M.new_opts(TopKOpts, plan=self._TOPK_PLANS.get(plan, plan), offset=offset, max_tie_rows=max_tie_rows)
+        self._check(self.L.hmj_top_k_device(self.h, arr, n_cols, n, k, out.data_ptr() if n_out else None, C.byref(opts)))
+        del keep
+        if int(opts.n_out) != n_out:
+            raise RuntimeError("hmj_top_k_device wrote %d entries, the executor sized the map for %d" % (int(opts.n_out), n_out))
+        return out, M.read_info(opts, ("n_out", "n_candidates", "n_tie_rows", "plan_taken", "n_levels", "n_rounds"),
+                                ("ms_select", "ms_emit", "ms_order"))
 
     # ---- OVER: window functions over ordered partitions (hmj_window_device) -----------------------------------
     def window_device(self, keys, n_partition_cols, fns, n=None, want_validity=True):

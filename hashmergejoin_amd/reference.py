@@ -319,6 +319,16 @@ def expected_order_by(columns):
     return np.lexsort(ranks[::-1]).astype(np.uint64)  # (lexsort: the last key is the primary one; stable)
 
 
+def expected_top_k(columns, k, offset=0):
+    """The row map hmj_top_k_device returns (include/hmj.h): entries offset .. offset + k of `expected_order_by(columns)`,
+    the sum saturating as the library's does (k and offset are any values below 2^64).  Returns min(k, n - min(n, offset))
+    uint64."""
+    full = expected_order_by(columns)
+    n = full.shape[0]
+    lo = min(int(offset), n)
+    return full[lo:min(n, lo + min(int(k), n - lo))]
+
+
 def expected_window(key_columns, n_partition_cols, fns, n=None):
     """What hmj_window_device returns (include/hmj.h), restated on the host.  key_columns as `expected_order_by` takes them
     (may be empty: one partition in row order; n then comes from the first function column, or from `n`); the first

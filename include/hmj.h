@@ -406,7 +406,7 @@ int hmj_exchange_join_kind_u64_device(hmj_ctx* ctx, const void* build_shard_dev,
  * differently simply partitions R again) skips re-partitioning R; any other call discards the prepared state.  The caller promises the build rows do not change in between.
  * "Any other call" is every call that runs on the device or touches the workspace: the joins of every kind (u64, string,
  * multi-column -- hmj_join_cols_device, hmj_join_kind_cols_device --, mixed-key -- hmj_join_mixed_device --, host-resident, exchange), hmj_sort_u64_device, hmj_sort_rows_by_u64_host, hmj_argsort_u64_host, hmj_partition_u64_device,
- * hmj_hash_str_device (each of them also when given no rows), hmj_reserve and hmj_autotune_radix_bits.  Left out are the calls that read or write no workspace buffer: hmj_set_stream,
+ * hmj_hash_str_device (each of them also when given no rows), hmj_top_k_device (where it has entries to return), hmj_reserve and hmj_autotune_radix_bits.  Left out are the calls that read or write no workspace buffer: hmj_set_stream,
  * hmj_set_radix_bits / hmj_set_key_prefix_bits (the join then plans other bits and partitions R again), hmj_set_profiling,
  * hmj_forget_workloads, hmj_release_result (result columns only), the hmj_last_* / hmj_placement_info queries, the
  * hmj_gen_* generators, hmj_take_cols_device and hmj_take_str_device (their only workspace is small buffers of their own); a call refused with HMJ_E_ARG before it started may leave the prepared state in place as well.
@@ -1137,7 +1137,7 @@ int hmj_group_agg_device(hmj_ctx* ctx, const hmj_agg_src* src, uint32_t n_aggs, 
  * HMJ_E_HIP ("refinement did not converge").
  * Known cost: a long prefix shared by many strings costs one round per 4..8 bytes over the rows that share it (no
  * per-segment common-prefix skip); every round is a full hmj_sort_u64_device call on its rows.
- * Out of scope: LIMIT / top-k, 32-bit-offset strings, collations and locale, decimal128, host-resident columns, the
+ * Out of scope: 32-bit-offset strings (LIMIT / OFFSET: hmj_top_k_device below), collations and locale, decimal128, host-resident columns, the
  * exchange path.                                                                                                        */
 #define HMJ_ORDER_LARGE_STRING 16u /* a column type beside HMJ_TYPE_I8 ... HMJ_TYPE_F64: Arrow large_string              */
 #define HMJ_ORDER_DESC        0x1u /* descending among the valid values                                                  */
@@ -1167,7 +1167,7 @@ int hmj_order_by_device(hmj_ctx* ctx, const hmj_order_col* cols, uint32_t n_cols
  * ROW_NUMBER, RANK, DENSE_RANK, running COUNT / SUM / MIN / MAX, LAG and LEAD -- over one OVER (PARTITION BY keys[0 ..
  * n_partition_cols) ORDER BY the rest of keys) clause, in one call.  Every other entry answers with one row per group or
  * with a row map.  "Top 3 per group" is ROW_NUMBER here followed by hmj_filter_device on the output column (the top k of the
- * whole table is the first k entries of hmj_order_by_device's map).  Nothing in the reference corresponds.  A new entry with
+ * whole table is hmj_top_k_device).  Nothing in the reference corresponds.  A new entry with
  * structs of its own: no other entry, struct, flag or path bit changes.
  * keys is a HOST array of n_keys entries, 0 <= n_keys <= HMJ_MAX_ORDER_COLS, exactly what hmj_order_by_device takes; fns
  * and dst are HOST arrays of n_fns entries (read during the call only; dst[a].null_count is written); everything they point
@@ -1272,6 +1272,82 @@ typedef struct {
 int hmj_window_device(hmj_ctx* ctx, const hmj_order_col* keys, uint32_t n_keys, uint64_t n,
                       const hmj_window_fn* fns, uint32_t n_fns, hmj_window_dst* dst,
                       uint64_t* row_map_out, hmj_window_opts* opts);
+
+/* ---- the first rows of an order: ORDER BY ... LIMIT k [OFFSET o] (top-k) ---------------------------------------- */
+/* Entries offset .. offset + k of the map hmj_order_by_device returns for the same columns, without sorting the rows the cut
+ * rejects: "the ten largest sums" reads the key column a few times and sorts ten rows.  Nothing in the reference
+ * corresponds.  A new entry with structs of its own: no other entry, struct, flag or path bit changes.
+ * Result.  row_map_out[j], j < n_out, equals entry offset + j of hmj_order_by_device's map of cols: the order is total and
+ * stable (ties keep ascending row index), so the answer is unique and every plan returns the same entries.  Entries from
+ * n_out on are not written.  cols is exactly what hmj_order_by_device takes (a HOST array of n_cols entries, everything
+ * behind it on the device), and the value rules -- directions, NULL placement, integers, floats, NaN, strings -- are that
+ * entry's word for word.  n is at most 2^32 - 1; k and offset are any uint64.
+ * Offset arithmetic.  offset + k saturates: the cut is K = min(n, offset + k) and n_out = min(k, n - min(n, offset)),
+ * computed without wrapping for any pair of values.
+ * Empty results.  n_out == 0 -- k == 0, offset >= n or n == 0 --: HMJ_OK, nothing is written, no kernel is launched,
+ * plan_taken = 0, the ctx is as it was.  The host argument checks still run, except those hmj_order_by_device makes only
+ * with n > 0.  row_map_out is required when n_out > 0, must then be aligned to 8, and its 8 * n_out bytes must not overlap a
+ * column's values, offsets or bitmap.  n == 1 with n_out == 1: the map is {0}; no column is read, no kernel runs
+ * (plan_taken = 0, n_candidates = 1).
+ * Plans.  HMJ_TOPK_SELECT: a radix selection over the rows' byte streams finds the K-th row's place without materialising
+ * the rows it rejects; the candidates -- every row before the cut, and the rows still tied with it -- are ordered by
+ * hmj_order_by_device's own refinement loop.  HMJ_TOPK_FULL: hmj_order_by_device into a workspace map, then the slice.
+ * HMJ_TOPK_AUTO takes FULL where selection cannot pay: n below 2^23 rows, or K above n / 256 (DESIGN.md records where these
+ * come from).  max_tie_rows: a set of rows tied with the cut that is larger than this is narrowed by a further level before
+ * it is ordered; 0 is the library's default (2^14).
+ * Context.  The effects are hmj_order_by_device's and nothing more: a prepared build side is discarded; the lifetime of the
+ * last JOIN result ends where a sort runs (a call whose candidates are one row sorts nothing); hmj_last_plan /
+ * hmj_last_timing are left alone; the group result and the live grouping are kept; the sorts learn under signature kind
+ * 25.  The call has a workspace of its own beside hmj_order_by_device's, runs on the ctx stream and returns with the map
+ * complete.
+ * opts (out): n_out; n_candidates -- rows the final ordering sorted (SELECT: K <= n_candidates <= n; FULL: n); n_tie_rows --
+ * rows still tied with the cut when selection stopped, before trimming (0 where the whole tie set lies before the cut);
+ * plan_taken; n_levels -- histogram levels run (0 under FULL); n_rounds -- sort rounds of the final ordering; with
+ * hmj_set_profiling ms_select (the first window's levels), ms_emit (marks, writes and every later window), ms_order (the
+ * final ordering and the slice; under FULL the whole ORDER BY).
+ * HMJ_E_ARG, found by the host before any launch: NULL ctx / cols / opts; an unknown plan; non-zero reserved;
+ * opts->struct_size smaller than through `max_tie_rows`; a NULL, misaligned or overlapping row_map_out with n_out > 0; and
+ * everything hmj_order_by_device rejects in cols, in that entry's wording.  Found on the device by the first kernel that
+ * computes a stream, before any kernel follows an offset into chars, again in that entry's wording: decreasing offsets, and
+ * key bytes of a valid slot under data == NULL.  The ctx stays usable after any error.
+ * How (DESIGN.md "Top-k (ORDER BY ... LIMIT)").  A row's order is the memcmp order of its stream (above); selection walks
+ * it one 8-byte window at a time.  A LEVEL (topk_hist_kernel, one lane per row) counts the rows whose word agrees with
+ * the threshold prefix decided so far into an LDS histogram of the next 11-bit digit -- a wave whose lanes share one bin
+ * adds their popcount once, a workgroup flushes its non-zero bins with one global atomic each --, the host reads the bins
+ * back and picks the digit that holds the K-th row: the rows in smaller bins are definite, the bin is the new tie set.  The
+ * call's first level also makes hmj_order_by_device's offset checks and reduces the longest stream and the bits in which
+ * the words differ, so that later digits start at the highest varying bit.  Selection stops when the tie set is at most
+ * max_tie_rows, when all of it lies before the cut, or when the window's bits are used up.  topk_mark_kernel ballots
+ * "below the threshold" and "tied", one scan places both, topk_write_kernel writes {first stream word, row} of the rows
+ * below, then of the tied rows, each class in ascending row order: rows of equal whole keys share a class, so the stable
+ * sorts behind keep them in row order.  Tied rows whose stream is used up are equal in every column: only the first of
+ * them by row index that the cut takes are written (ORDER BY status LIMIT 10 sorts ten rows).  Tied rows with bytes left
+ * and more than max_tie_rows of them become a list; its next 8 stream bytes are gathered and the same levels, marks and
+ * writes run over the list, window by window.
+ * Known cost: the final ordering also refines ties that lie wholly behind the cut; every level is one launch and one
+ * read-back, and reads the key columns (window 0) or the list's words again; FULL and a SELECT whose candidates are most
+ * of the table cost an ORDER BY plus the levels.
+ * Out of scope: WITH TIES; top-k per partition (ROW_NUMBER and hmj_filter_device); pruning the refinement behind the cut;
+ * 32-bit-offset strings; the exchange path; host-resident columns.                                                     */
+#define HMJ_TOPK_AUTO   0u   /* the library chooses */
+#define HMJ_TOPK_SELECT 1u   /* radix selection, then the candidates are ordered */
+#define HMJ_TOPK_FULL   2u   /* the full ORDER BY into a workspace map, then the slice */
+typedef struct {
+  uint32_t struct_size;   /* size-versioned like the other opts */
+  uint32_t plan;          /* in: HMJ_TOPK_*; exists so callers and tests can pin a path (as force_hashed does) */
+  uint64_t offset;        /* in: rows skipped in front (OFFSET) */
+  uint64_t max_tie_rows;  /* in: 0 = the library's default; a tie set larger than this is narrowed by a further level */
+  uint64_t n_out;         /* out: map entries written = min(k, n - min(n, offset)) */
+  uint64_t n_candidates;  /* out: rows the final ordering sorted (SELECT: K <= n_candidates <= n; FULL: n) */
+  uint64_t n_tie_rows;    /* out: rows still tied with the cut when selection stopped, before trimming */
+  uint32_t plan_taken;    /* out: HMJ_TOPK_SELECT / HMJ_TOPK_FULL; 0 where no kernel ran */
+  uint32_t n_levels;      /* out: histogram levels run (0 under FULL) */
+  uint32_t n_rounds;      /* out: sort rounds of the final ordering */
+  uint32_t reserved;      /* 0 */
+  float ms_select, ms_emit, ms_order; /* out, with hmj_set_profiling */
+} hmj_top_k_opts;
+int hmj_top_k_device(hmj_ctx* ctx, const hmj_order_col* cols, uint32_t n_cols, uint64_t n, uint64_t k,
+                     uint64_t* row_map_out, hmj_top_k_opts* opts);
 
 /* ---- taking fixed-width columns through a row map (Arrow validity out) --------------------------------- */
 /* The joins above return gather maps (r_row / s_row), not columns.  This entry turns a map back into Arrow columns: up to
