@@ -9,7 +9,7 @@ LIB      := hashmergejoin_amd/libhmj_hip.so
 
 all: $(LIB) oracle cpptest tests/cpp/strgen_bench examples/hashjoin_bench_hip examples/exchange_join
 
-$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/hmj_dev.h $(CSRC)/hmj_launch.h $(CSRC)/hmj_ctx.h $(CSRC)/hmj_args.h $(CSRC)/hmj_smallplan.h $(CSRC)/hmj_winplan.h $(CSRC)/hmj_topkplan.h $(CSRC)/hmj_order.h $(CSRC)/hmj_entry.h $(CSRC)/hmj_keyjoin.h $(CSRC)/hmj_tuplejoin.h $(CSRC)/hmj_group.h $(CSRC)/hmj_strkey.h include/hmj.h
+$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/hmj_dev.h $(CSRC)/hmj_launch.h $(CSRC)/hmj_ctx.h $(CSRC)/hmj_args.h $(CSRC)/hmj_smallplan.h $(CSRC)/hmj_probekeys.h $(CSRC)/hmj_winplan.h $(CSRC)/hmj_topkplan.h $(CSRC)/hmj_order.h $(CSRC)/hmj_entry.h $(CSRC)/hmj_keyjoin.h $(CSRC)/hmj_tuplejoin.h $(CSRC)/hmj_group.h $(CSRC)/hmj_strkey.h include/hmj.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(LIB): $(OBJS)

@@ -34,6 +34,7 @@ HMJ_PATH_SORTED_FK_HALF = 0x8000
 HMJ_PATH_LOOKBACK_TIMEOUT = 0x10000
 HMJ_PATH_SORTED_FK_WIDE = 0x20000
 HMJ_PATH_PRESORTED = 0x40000
+HMJ_PATH_PROBE_KEYS = 0x10000000  # plain count join: the probe side went through the slab passes as 8-byte keys
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _U64P = C.POINTER(C.c_uint64)
@@ -397,10 +398,12 @@ HMJ_REFUSED_SLAB_SHAPE, HMJ_REFUSED_SLAB_COOLING, HMJ_REFUSED_SLAB_SORTED_INPUT,
 HMJ_REFUSED_FAST_WRITE_COOLING, HMJ_REFUSED_FAST_WRITE_GAVE_UP = 0x400, 0x800
 HMJ_REFUSED_SLAB_PROBE_COOLING, HMJ_REFUSED_SLAB_PROBE_OVERFLOW = 0x1000, 0x2000
 HMJ_REFUSED_PREFIX_VIOLATED, HMJ_REFUSED_EXPANSION_GAVE_UP = 0x4000, 0x8000
+HMJ_REFUSED_PROBE_KEYS_GAVE_UP, HMJ_REFUSED_PROBE_KEYS_COOLING = 0x10000, 0x20000
 HMJ_COOL_UNIQ_WRITE, HMJ_COOL_SORTED_WRITE, HMJ_COOL_GTABLE, HMJ_COOL_GTABLE_WRITE = 0x1, 0x2, 0x4, 0x8
 HMJ_COOL_RANK_SORT, HMJ_COOL_RANK_SORT_SLAB, HMJ_COOL_EXPANSION, HMJ_COOL_SORT_SLAB = 0x10, 0x20, 0x40, 0x80
 HMJ_COOL_SLAB, HMJ_COOL_SLAB_PROBE, HMJ_COOL_ONE_PASS_WRITE, HMJ_COOL_EXACT_PREFIX = 0x100, 0x200, 0x400, 0x800
 HMJ_COOL_RANK_RUNS, HMJ_COOL_SORT_MSD = 0x1000, 0x2000
+HMJ_COOL_PROBE_KEYS = 0x4000
 
 
 HMJ_PLACE_MAX_CAND = 4

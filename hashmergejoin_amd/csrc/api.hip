@@ -90,7 +90,8 @@ uint32_t WorkloadMemo::cooling() const {
          (gtable_sort_slab_cooldown ? HMJ_COOL_RANK_SORT_SLAB : 0u) | (expand_cooldown ? HMJ_COOL_EXPANSION : 0u) |
          (sort_slab_cooldown ? HMJ_COOL_SORT_SLAB : 0u) | (slab_cooldown ? HMJ_COOL_SLAB : 0u) | (slab_probe_cooldown ? HMJ_COOL_SLAB_PROBE : 0u) |
          (one_pass_write_cooldown ? HMJ_COOL_ONE_PASS_WRITE : 0u) | (exact_prefix_joins ? HMJ_COOL_EXACT_PREFIX : 0u) |
-         (rank_runs_cooldown ? HMJ_COOL_RANK_RUNS : 0u) | (sort_msd_cooldown ? HMJ_COOL_SORT_MSD : 0u);
+         (rank_runs_cooldown ? HMJ_COOL_RANK_RUNS : 0u) | (sort_msd_cooldown ? HMJ_COOL_SORT_MSD : 0u) |
+         (probe_keys_cooldown ? HMJ_COOL_PROBE_KEYS : 0u);
 }
 
 int wait_arrival(hmj_ctx* c, hipEvent_t ev) {
@@ -653,9 +654,11 @@ static hmj::ProbeArgs slab_probe_args(hmj_ctx* c, const hmj::SlabGeom* build_sla
 // Slab pass A of one relation: its rows into the worker-private slabs c->slab_a / c->cnt_a (allocated by the caller) by the
 // `bits`-bit digit at `low`.  arriving: the probe rows are still arriving over the links (exchange.hip) -- pass-A workers own
 // contiguous input ranges, so the workers whose rows are complete start after each round's event.
-static int slab_pass_a(hmj_ctx* c, const void* in, u32 n, int rel, int low, int bits, const hmj::SlabGeom& g, bool arriving) {
+// keys: the pass writes 8-byte key rows and sums the payloads (a count join's probe side, hmj_probekeys.h; never arriving).
+static int slab_pass_a(hmj_ctx* c, const void* in, u32 n, int rel, int low, int bits, const hmj::SlabGeom& g, bool arriving,
+                       bool keys = false) {
   u64* acc = (u64*)c->accum.p;
-  const u64 a_rows = c->slab_a.cap / 16, a_cnt = c->cnt_a.cap / 4;  // what is allocated: the launchers check it
+  const u64 a_rows = c->slab_a.cap / (keys ? 8 : 16), a_cnt = c->cnt_a.cap / 4;  // what is allocated: the launchers check it
   const int sp = span_begin(c, K_SCATTER, rel, 0);
   if (arriving) {
     u32 w_done = 0;
@@ -669,22 +672,22 @@ static int slab_pass_a(hmj_ctx* c, const void* in, u32 n, int rel, int low, int 
       }
     }
   } else {
-    HIP_TRY(hmj::launch_slab_a(in, n, low, bits, g, c->slab_a.p, a_rows, (u32*)c->cnt_a.p, a_cnt, acc, c->stream));
+    HIP_TRY(hmj::launch_slab_a(in, n, low, bits, g, c->slab_a.p, a_rows, (u32*)c->cnt_a.p, a_cnt, acc, c->stream, 0, 0xFFFFFFFFu, keys));
   }
   span_end(c, sp);
-  c->timing.bytes_scatter += 32ull * n;
+  c->timing.bytes_scatter += (keys ? 24ull : 32ull) * n;  // rows read; rows or keys written
   return HMJ_OK;
 }
 // Both slab passes of one relation: pass A (above), then pass B out of c->slab_a into the slab / count pair `sb` / `cb`
 // (allocated by the caller) by the bb-bit digit above pass A's.
 static int slab_passes(hmj_ctx* c, const void* in, u32 n, int rel, int low, int ba, int bb, const hmj::SlabGeom& g, DevBuf& sb,
-                       DevBuf& cb, bool arriving) {
-  RC_TRY(slab_pass_a(c, in, n, rel, low, ba, g, arriving));
+                       DevBuf& cb, bool arriving, bool keys = false) {
+  RC_TRY(slab_pass_a(c, in, n, rel, low, ba, g, arriving, keys));
   const int sp = span_begin(c, K_SCATTER, rel, 1);
-  HIP_TRY(hmj::launch_slab_b(c->slab_a.p, (const u32*)c->cnt_a.p, ba, low + ba, bb, g, sb.p, sb.cap / 16, (u32*)cb.p, cb.cap / 4,
-                             (u64*)c->accum.p, c->stream));
+  HIP_TRY(hmj::launch_slab_b(c->slab_a.p, (const u32*)c->cnt_a.p, ba, low + ba, bb, g, sb.p, sb.cap / (keys ? 8 : 16), (u32*)cb.p,
+                             cb.cap / 4, (u64*)c->accum.p, c->stream, keys));
   span_end(c, sp);
-  c->timing.bytes_scatter += 32ull * n;
+  c->timing.bytes_scatter += (keys ? 16ull : 32ull) * n;
   return HMJ_OK;
 }
 
@@ -1422,10 +1425,65 @@ static int run_slab_join(hmj_ctx* c, const JoinCall& j, const JoinPlan& p) {
   RC_TRY(ensure_dev(c, c->slab_bs, gs.rows_b * 16));
   RC_TRY(ensure_dev(c, c->cnt_br, (size_t)P * gr.KB * 4));
   RC_TRY(ensure_dev(c, c->cnt_bs, (size_t)P * gs.KB * 4));
+  // Plain count joins: the probe side as bare keys (hmj_probekeys.h) -- decided before anything runs, from the call, the
+  // plan's digits, the switches and what the workload's earlier joins found.
+  namespace pk = hmj_host;
+  const pk::ProbeKeysVerdict keys_verdict =
+      pk::probe_keys_decide(pk::ProbeKeysState{c->probe_keys_mode, c->probe_keys_min_log2, c->wm->probe_keys_cooldown,
+                                               c->wm->probe_keys_clean, c->wm->probe_keys_dirty},
+                            pk::ProbeKeysJoin{j.flags, (u64)np, {ba, bb}, c->prepare_only, !c->arrive_ev.empty()});
   // (a reused build side is already in slab_br / cnt_br; hmj_prepare_build partitions the build side only)
   if (!reuse) RC_TRY(slab_passes(c, j.R, nb, 0, p.low, ba, bb, gr, c->slab_br, c->cnt_br, false));
-  if (!c->prepare_only) RC_TRY(slab_passes(c, j.S, np, 1, p.low, ba, bb, gs, c->slab_bs, c->cnt_bs, !c->arrive_ev.empty()));
   u64* hh;
+  bool probe_keys = keys_verdict == pk::ProbeKeysVerdict::Attempt;
+  if (keys_verdict == pk::ProbeKeysVerdict::Pilot) {
+    // a few thousand probe rows looked up in the build slabs, and the one host sync this costs: a join that is not of the
+    // "every probe row meets exactly one build row" kind pays for this, not for two wasted passes
+    HIP_TRY(hmj::launch_probe_keys_pilot(j.S, np, c->slab_br.p, (const u32*)c->cnt_br.p, gr.CB, p.low, ba + bb, (u64*)c->accum.p,
+                                         c->stream));
+    RC_TRY(read_accum(c, &hh));
+    if (hh[hmj::ACC_ERR] & hmj::ERR_SLAB) {  // (the build side overflowed a slab: known a little earlier than without a pilot)
+      c->wm->slab_cooldown = 8;
+      return kRetryNoSlab;
+    }
+    probe_keys = !(hh[hmj::ACC_ERR] & hmj::ERR_PROBE_PILOT);
+    if (!probe_keys) {
+      c->wm->probe_keys_dirty = true;
+      c->wm->probe_keys_dirty_age = 0;
+    }
+  }
+  if (probe_keys) {
+    // key rows: the same slab counts and buffers, capacities rounded up to whole lines of 16 keys (half the bytes: they fit)
+    hmj::SlabGeom gk = gs;
+    gk.CA = pk::probe_keys_slab_cap(gs.CA);
+    gk.CB = pk::probe_keys_slab_cap(gs.CB);
+    RC_TRY(slab_passes(c, j.S, np, 1, p.low, ba, bb, gk, c->slab_bs, c->cnt_bs, false, true));
+    hmj::ProbeArgs ka = slab_probe_args(c, &gr, nullptr, c->slab_bs, c->cnt_bs, gk.CB, P, 1);
+    ka.s_rows = c->slab_bs.cap / 8;
+    const int sp = span_begin(c, K_PROBE_COUNT, -1);
+    HIP_TRY(hmj::launch_probe_count_slab_keys(ka, c->num_cus, c->stream));
+    span_end(c, sp);
+    c->timing.bytes_probe_count += 16ull * nb + 8ull * np;
+    RC_TRY(read_accum(c, &hh));
+    if (hh[hmj::ACC_ERR] & hmj::ERR_SLAB) {  // skewed digits: the usual route
+      c->wm->slab_cooldown = 8;
+      return kRetryNoSlab;
+    }
+    if (!(hh[hmj::ACC_ERR] & hmj::ERR_PROBE_KEYS)) {  // verified: sum_s is pass A's sum of all probe payloads
+      c->wm->probe_keys_clean = true;
+      c->timing.path |= HMJ_PATH_PROBE_KEYS;
+      result_sums(j.out, hh);
+      return HMJ_OK;
+    }
+    // A probe row without exactly one build row: the probe side again with whole rows, inside this plan (slab_br / cnt_br
+    // are still valid; no buffer grows), and the workload keeps whole rows for a while.
+    c->plan.refused |= HMJ_REFUSED_PROBE_KEYS_GAVE_UP;
+    c->wm->probe_keys_clean = false;
+    c->wm->probe_keys_cooldown = pk::kProbeKeysCooldown;
+    if (c->trace) std::fprintf(stderr, "[hmj]   key-only probe side gave up (a probe row without exactly one build row) -> whole rows\n");
+    HIP_TRY(hipMemsetAsync(c->accum.p, 0, 8 * sizeof(u64), c->stream));
+  }
+  if (!c->prepare_only) RC_TRY(slab_passes(c, j.S, np, 1, p.low, ba, bb, gs, c->slab_bs, c->cnt_bs, !c->arrive_ev.empty()));
   if (c->prepare_only) {
     RC_TRY(read_accum(c, &hh));
     if (hh[hmj::ACC_ERR] & hmj::ERR_SLAB) {
@@ -1455,11 +1513,19 @@ static int run_slab_join(hmj_ctx* c, const JoinCall& j, const JoinPlan& p) {
     HIP_TRY(hmj::launch_probe_count_slab(sa, c->num_cus, c->stream));
   }
   span_end(c, sp);
-  c->timing.bytes_probe_count = 16ull * ((u64)nb + np);
+  c->timing.bytes_probe_count += 16ull * ((u64)nb + np);  // (+: on top of a key-only probe that was redone)
   RC_TRY(read_accum(c, &hh));
   if (hh[hmj::ACC_ERR] & hmj::ERR_SLAB) {  // skewed digits: remember, and take the exact path
     c->wm->slab_cooldown = 8;
     return kRetryNoSlab;
+  }
+  // The slab path has produced this join's result with whole probe rows: only now does the join count as one of the
+  // workload's cooling joins, or as one that went without a pilot (an attempt that ends on the exact path uses up neither).
+  if (keys_verdict == pk::ProbeKeysVerdict::SkipCooling) {
+    c->plan.refused |= HMJ_REFUSED_PROBE_KEYS_COOLING;
+    c->wm->probe_keys_cooldown--;
+  } else if (keys_verdict == pk::ProbeKeysVerdict::SkipDirty && ++c->wm->probe_keys_dirty_age >= pk::kProbeKeysDirtyJoins) {
+    c->wm->probe_keys_dirty = false;  // the next join of the workload asks the pilot again
   }
   result_sums(j.out, hh);
   return HMJ_OK;
@@ -3007,6 +3073,11 @@ int hmj_create(hmj_ctx** out, int device_id) {
   if (const char* e = getenv("HMJ_SLAB_MIN_LOG2")) {
     const int l = atoi(e);
     if (l >= 16 && l <= 31) c->slab_min_rows = 1u << l;
+  }
+  if (const char* e = getenv("HMJ_PROBE_KEYS")) c->probe_keys_mode = atoi(e) == 0 ? 0 : atoi(e) == 1 ? 1 : -1;  // (2: pilot first)
+  if (const char* e = getenv("HMJ_PROBE_KEYS_MIN_LOG2")) {
+    const int l = atoi(e);
+    if (l >= hmj_host::kProbeKeysMinLog2Floor && l <= 31) c->probe_keys_min_log2 = l;
   }
   if (const char* e = getenv("HMJ_SLAB_PROBE_KB")) {
     const int k = atoi(e);

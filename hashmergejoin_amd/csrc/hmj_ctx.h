@@ -11,6 +11,7 @@
 #include "hmj_args.h"
 #include "hmj_dev.h"
 #include "hmj_launch.h"
+#include "hmj_probekeys.h"
 #include "hmj_smallplan.h"
 
 struct hmj_comm;  // exchange.hip
@@ -209,6 +210,10 @@ struct WorkloadMemo {
   int slab_cooldown = 0;            // histogram-free slab partitioning of both sides (after a slab overflowed: skewed keys)
   int slab_probe_cooldown = 0;      // ... of the probe side only (probe-heavy count joins, one-pass slab walk)
   int one_pass_write_cooldown = 0;  // materialising on the one-pass slab walk (after duplicate build keys)
+  int probe_keys_cooldown = 0;      // plain count joins: the probe side as bare keys (after a probe row without exactly one build row)
+  bool probe_keys_clean = false;    // ... the workload's last such join was verified clean: the next one starts without a pilot
+  bool probe_keys_dirty = false;    // ... its pilot met such a row (nothing was wasted, nothing cools): whole rows without a pilot,
+  int probe_keys_dirty_age = 0;     //     and the pilot is asked again every 64 joins
   int exact_prefix_joins = 0;       // ordered joins that still take the shared key prefix from a pass over ALL keys: the
                                     // sample of an earlier join missed a few keys above an otherwise dense range
   uint32_t cooling() const;         // HMJ_COOL_* bits of the non-zero counters (hmj_plan_desc.cooling)
@@ -332,6 +337,8 @@ struct hmj_ctx {
   bool sort_slab = true;           // hmj_sort_u64_device: LSD passes as a chain of slab passes + one compaction (HMJ_SORT_SLAB=0: exact passes)
   u64 sort_slab_min = 1ull << 25;  // ... from this many rows on (HMJ_SORT_SLAB_MIN_LOG2)
   int slab_mode = 1;      // 1 = try the histogram-free slab path for plain count joins (HMJ_SLAB=0 disables)
+  int probe_keys_mode = hmj_host::kProbeKeysModeDefault;      // plain count joins on that path, probe side as bare keys (hmj_probekeys.h): -1 pilot first, 0 never, 1 attempt without a pilot (HMJ_PROBE_KEYS)
+  int probe_keys_min_log2 = hmj_host::kProbeKeysMinLog2Default;  // ... from 2^this many probe rows on (HMJ_PROBE_KEYS_MIN_LOG2): below, a first join's pilot and its sync cost more than the passes save
   bool staged_upload = false;  // HMJ_UPLOAD=staged
   bool host_pipeline = true;   // HMJ_HOST_PIPELINE=0: host entry points upload, join and download one after the other
   hipStream_t copy_stream = nullptr;  // host entry points: uploads run here, beside the partitioning on `stream`

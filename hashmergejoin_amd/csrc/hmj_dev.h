@@ -135,6 +135,9 @@ constexpr u64 ERR_SORTED = 64;   // one-pass ordered write met duplicate keys / 
 constexpr u64 ERR_FASTPATH = 8;  // unique-key write mode met duplicate build keys / an oversized partition
 constexpr u64 ERR_GTABLE = 128;  // global-table path: a build row walked too far (duplicates / clustering hash) or has the empty marker as its key
 constexpr u64 ERR_PREFIX = 4;  // a key does not carry the sampled common prefix (ordered mode re-plans)
+// (bits 128 .. 2048 are also the one-pass ordered write's reasons beside ERR_SORTED)
+constexpr u64 ERR_PROBE_KEYS = 1ull << 16;   // key-only probe side: a probe row did not meet exactly one build row -> whole rows
+constexpr u64 ERR_PROBE_PILOT = 1ull << 17;  // ... its pilot: a sampled probe row did not (the key-only passes are not started)
 
 __device__ __forceinline__ u64 mix64(u64 x) {  // same constants as oracle/hmj_oracle.c
   x ^= x >> 30;

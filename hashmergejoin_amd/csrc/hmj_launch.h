@@ -66,9 +66,13 @@ u32 slab_capacity(double mean, double fan);
 // what the kernel and its grid will touch for this geometry and refuse (hipErrorInvalidValue) instead of launching
 // a kernel that would write past a buffer.
 hipError_t launch_slab_a(const void* in, u32 n, int shift, int bits, const SlabGeom& g, void* slab_a, u64 slab_a_rows,
-                         u32* cnt_a, u64 cnt_a_n, u64* accum, hipStream_t st, u32 w_begin = 0, u32 w_end = 0xFFFFFFFFu);
+                         u32* cnt_a, u64 cnt_a_n, u64* accum, hipStream_t st, u32 w_begin = 0, u32 w_end = 0xFFFFFFFFu,
+                         bool keys = false);
 hipError_t launch_slab_b(const void* slab_a, const u32* cnt_a, int bits_a, int shift, int bits,
-                         const SlabGeom& g, void* slab_b, u64 slab_b_rows, u32* cnt_b, u64 cnt_b_n, u64* accum, hipStream_t st);
+                         const SlabGeom& g, void* slab_b, u64 slab_b_rows, u32* cnt_b, u64 cnt_b_n, u64* accum, hipStream_t st,
+                         bool keys = false);
+// keys = true: the passes of a count join's probe side as 8-byte KEY rows (radix.hip, hmj_probekeys.h): pass A reads rows,
+// writes keys and sums the payloads into accum[ACC_SUM_S]; pass B moves keys.  Digits of <= 8 bits, g.CA / g.CB multiples of 16.
 hipError_t launch_key_sample(const void* R, u32 nb, const void* S, u32 np, u64* out, hipStream_t st);
 hipError_t launch_key_exact(const void* R, u32 nb, const void* S, u32 np, u64 ref, u64* out, int num_cus, hipStream_t st,
                             bool ref_is_first_key = false);
@@ -115,6 +119,15 @@ struct ProbeArgs {
 hipError_t launch_probe(const ProbeArgs& a, int mode, bool first_wins, bool extra, int grid,
                         hipStream_t st);
 int probe_default_grid(int num_cus);
+// Count join whose probe side went through the slab passes as 8-byte KEY rows (launch_slab_a / _b with keys = true): a.S holds
+// keys, a.s_cap / a.s_rows count key rows.  n_matches and sum_r as launch_probe_count_slab; ACC_SUM_S is left alone (pass A put
+// the sum of all probe payloads there); a probe row that does not meet exactly one build row raises ERR_PROBE_KEYS.
+hipError_t launch_probe_count_slab_keys(const ProbeArgs& a, int num_cus, hipStream_t st);
+// The pilot in front of those passes: hmj_host::kProbeKeysPilotRows probe rows, sampled by hmj_host::probe_keys_sample_index
+// (hmj_probekeys.h), each looked up by one wave in the build side's pass-B slabs (partition = the `bits` key bits from `low`;
+// SLAB_KB pieces of r_cap rows).  A sampled row that does not meet exactly one build row raises ERR_PROBE_PILOT in accum[ACC_ERR].
+hipError_t launch_probe_keys_pilot(const void* S, u32 np, const void* slab_br, const u32* cnt_br, u32 r_cap, int low, int bits,
+                                   u64* accum, hipStream_t st);
 // join kinds (semi / anti / probe-side outer; kind = HMJ_JOIN_* of hmj.h): the generic walk over contiguous partitions,
 // emitting by hit / miss.  mode 0 / 1 / 2 as launch_probe's; a.matched: one bit per probe row slot, zeroed before each
 // pass; accum[ACC_PAD] (+=) counts the rows emitted with `fill`.  Build slices are not allowed (r_end / s_end may only cut

@@ -11,6 +11,7 @@
 // the probe partition per chunk.
 #include "hmj_dev.h"
 #include "hmj_launch.h"
+#include "hmj_probekeys.h"
 #include <type_traits>
 
 namespace hmj {
@@ -1031,16 +1032,43 @@ __device__ __forceinline__ void fp_load_slab(Tup (&t)[ROWS], const Tup* __restri
 // quarter, so its piece -- base and row count -- is wave-uniform and the address is base + row.  A piece may
 // hold up to FP_ROWS * T/4 rows (1280; the slabs' capacity is mean + 8 sigma = 1304 at the headline size:
 // beyond 1280 the partition is reported like any other that does not fit).
-template <int THREADS>
-__device__ __forceinline__ void fp_load_pieces(Tup (&t)[FP_ROWS], const Tup* __restrict__ base, u32 cap, u32 cnt_mine, int tid) {
+// (Row: Tup, or u64 where the probe side went through the slab passes as bare keys -- PKEYS below)
+__device__ __forceinline__ u64 prow_key(const Tup& t) { return t.key; }
+__device__ __forceinline__ u64 prow_key(u64 k) { return k; }
+__device__ __forceinline__ u64 prow_val(const Tup& t) { return t.val; }
+__device__ __forceinline__ u64 prow_val(u64) { return 0; }
+template <int THREADS, typename Row>
+__device__ __forceinline__ void fp_load_pieces(Row (&t)[FP_ROWS], const Row* __restrict__ base, u32 cap, u32 cnt_mine, int tid) {
   constexpr int QT = THREADS / 4;
   const u32 g = (u32)tid / QT, l = (u32)tid % QT;
-  const Tup* __restrict__ piece = base + (u64)g * cap;
+  const Row* __restrict__ piece = base + (u64)g * cap;
   const u32 last = cnt_mine ? cnt_mine - 1 : 0;
 #pragma unroll
   for (int k = 0; k < FP_ROWS; k++) {
     const u32 r = l + (u32)k * QT;
     t[k] = piece[r < last ? r : last];  // clamped, unpredicated: the five loads issue back to back
+  }
+}
+
+// Key rows (PKEYS below): the same split into quarters, but a lane takes TWO consecutive keys per load -- 16 bytes, as for
+// whole rows (five 8-byte loads per lane ran the kernel SLOWER than whole rows, 1.59 against 1.55 ms at 2^28 rows: the
+// memory pipeline moves 8-byte accesses at 0.54-0.70 of the 16-byte rate) -- three loads, six keys: slot k of thread tid
+// is key 2 * (l + (k / 2) * T/4) + k % 2 of its quarter's piece.  A piece starts on a 128-byte line and its capacity is
+// even, so the pair of a piece's last key lies inside the slab.
+constexpr int FP_KEY_ROWS = 6;
+static_assert(FP_KEY_ROWS >= FP_ROWS && FP_KEY_ROWS % 2 == 0, "key pairs must cover a piece of FP_ROWS * T/4 rows");
+template <int THREADS>
+__device__ __forceinline__ void fp_load_key_pieces(u64 (&t)[FP_KEY_ROWS], const u64* __restrict__ base, u32 cap, u32 cnt_mine, int tid) {
+  constexpr int QT = THREADS / 4;
+  const u32 g = (u32)tid / QT, l = (u32)tid % QT;
+  const u64* __restrict__ piece = base + (u64)g * cap;
+  const u32 last = cnt_mine ? (cnt_mine - 1) >> 1 : 0;  // the last pair that holds a key
+#pragma unroll
+  for (int k = 0; k < FP_KEY_ROWS / 2; k++) {
+    const u32 q = l + (u32)k * QT;
+    const u64x2_t v = *reinterpret_cast<const u64x2_t*>(piece + 2 * (u64)(q < last ? q : last));  // clamped, unpredicated
+    t[2 * k] = v.x;
+    t[2 * k + 1] = v.y;
   }
 }
 
@@ -1052,17 +1080,25 @@ __device__ __forceinline__ void fp_load_pieces(Tup (&t)[FP_ROWS], const Tup* __r
 //       a.item_base[p]; no count pass, no output atomics): (key, rval, sval) columns are written in probe
 //       order, the row count goes to a.part_count[p].  A probe row with two matches (duplicate build
 //       keys) or a partition that does not fit raises ERR_FASTPATH: the caller re-runs the general path.
-template <int THREADS, int LOG_NB, bool PCOUNT, bool SLAB, int OUT>
+// PKEYS (the piece loader only): the probe side's slabs hold bare KEYS (radix.hip's key-row passes; hmj_probekeys.h).  pr / pq
+//       are keys -- 20 registers fewer -- and the walk counts every probe row's hits: n_matches and sum_r as ever, acc_s stays
+//       zero (pass A put the sum of ALL probe payloads into ACC_SUM_S, which is the join's sum_s exactly when every probe row
+//       meets exactly one build row), and a probe row with any other hit count raises ERR_PROBE_KEYS: the caller redoes the
+//       probe side with whole rows.
+template <int THREADS, int LOG_NB, bool PCOUNT, bool SLAB, int OUT, bool PKEYS = false>
 __global__ __launch_bounds__(THREADS, 4) void probe_count_fast_kernel(
     ProbeArgs a, u32* __restrict__ irregular, u32* __restrict__ n_irregular) {
   typedef FastSmem<THREADS, LOG_NB> Smem;
+  typedef typename std::conditional<PKEYS, u64, Tup>::type PRow;
   constexpr u32 CAP = Smem::CAP, NB = 1u << LOG_NB;
   constexpr bool PIECES = SLAB && OUT == 0 && !PCOUNT && HMJ_PROBE_PIECES;  // rows are taken piece by piece (see fp_load_pieces)
+  static_assert(!PKEYS || PIECES, "key-only probe rows: slab layout, plain count mode");
+  constexpr int PROWS = PKEYS ? FP_KEY_ROWS : FP_ROWS;  // probe rows per thread
   constexpr u32 QT = THREADS / 4, PIECE_CAP = FP_ROWS * QT;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   Smem& sm = *reinterpret_cast<Smem*>(smem_raw);
   const Tup* __restrict__ R = static_cast<const Tup*>(a.R);
-  const Tup* __restrict__ S = static_cast<const Tup*>(a.S);
+  const PRow* __restrict__ S = static_cast<const PRow*>(a.S);
   const u32* __restrict__ r_off = a.r_off;
   const u32* __restrict__ s_off = a.s_off;
   // end of partition p: the next partition's start, unless oversized probe partitions were split into
@@ -1072,7 +1108,7 @@ __global__ __launch_bounds__(THREADS, 4) void probe_count_fast_kernel(
   const u32 P = a.P;
   const int tid = threadIdx.x;
   u64 acc_n = 0, acc_r = 0, acc_s = 0, acc_x = 0, acc_m = 0, acc_p = 0;
-  bool pfx_bad = false, giveup = false;
+  bool pfx_bad = false, giveup = false, keys_bad = false;
   for (u32 i = tid; i < NB; i += THREADS) sm.head[i] = 0;
   if (tid < 2) sm.itemcnt[tid] = 0;
   u32 epoch = 0;
@@ -1084,12 +1120,17 @@ __global__ __launch_bounds__(THREADS, 4) void probe_count_fast_kernel(
   u32 p = blockIdx.x;
   u32 rb = 0, nb = 0, sb = 0, np = 0;
   bool regular = false;
-  Tup br[FP_ROWS], pr[FP_ROWS], pq[FP_ROWS];
+  Tup br[FP_ROWS];
+  PRow pr[PROWS], pq[PROWS];
   // slab layout: piece prefix sums of the current (r1..3, s1..3) and next (…n) partition
   u32 r1 = 0, r2 = 0, r3 = 0, s1 = 0, s2 = 0, s3 = 0, r1n = 0, r2n = 0, r3n = 0, s1n = 0, s2n = 0, s3n = 0;
   // PIECES: rows of this thread's quarter's piece, current (rm, sm_) and next (rmn, smn) partition
   u32 rm = 0, sm_ = 0, rmn = 0, smn = 0;
   const u32 my_piece = (u32)tid / QT;
+  // PIECES: which row of its quarter's piece slot k of this thread holds (key rows: pairs, see fp_load_key_pieces)
+  auto piece_row = [](int t_, int k) -> u32 {
+    return PKEYS ? 2u * ((u32)t_ % QT + (u32)(k >> 1) * QT) + (u32)(k & 1) : (u32)t_ % QT + (u32)k * QT;
+  };
   bool slab_bad = false;
   if (p < P) {
     if (SLAB) {
@@ -1113,10 +1154,11 @@ __global__ __launch_bounds__(THREADS, 4) void probe_count_fast_kernel(
     }
     regular = nb && np && nb <= CAP && np <= CAP;
     if (regular) {
-      if (PIECES) {
+      if constexpr (PIECES) {
         fp_load_pieces<THREADS>(br, R + (u64)p * SLAB_KB * a.r_cap, a.r_cap, rm, tid);
-        fp_load_pieces<THREADS>(pr, S + (u64)p * SLAB_KB * a.s_cap, a.s_cap, sm_, tid);
-      } else if (SLAB) {
+        if constexpr (PKEYS) fp_load_key_pieces<THREADS>(pr, S + (u64)p * SLAB_KB * a.s_cap, a.s_cap, sm_, tid);
+        else fp_load_pieces<THREADS>(pr, S + (u64)p * SLAB_KB * a.s_cap, a.s_cap, sm_, tid);
+      } else if constexpr (SLAB) {
         fp_load_slab<THREADS>(br, R + (u64)p * SLAB_KB * a.r_cap, a.r_cap, r1, r2, r3, nb, tid);
         if (OUT == 0) fp_load_slab<THREADS>(pr, S + (u64)p * SLAB_KB * a.s_cap, a.s_cap, s1, s2, s3, np, tid);
       } else {
@@ -1130,6 +1172,7 @@ __global__ __launch_bounds__(THREADS, 4) void probe_count_fast_kernel(
   // `if` the compiler cannot count them, and every wait for older rows becomes s_waitcnt vmcnt(0) -- i.e. the
   // probe walk of partition p waited for partition p + G's rows, which had only just been requested.
   const Tup* __restrict__ dummy = reinterpret_cast<const Tup*>(a.accum);
+  const PRow* __restrict__ dummy_p = reinterpret_cast<const PRow*>(a.accum);  // (the same row, as the probe side's row type)
   auto load_build = [&](Tup (&t)[FP_ROWS], bool ok, u32 pp, u32 rb_, u32 nb_, u32 q1, u32 q2, u32 q3, u32 mine) {
     if (PIECES)
       fp_load_pieces<THREADS>(t, ok ? R + (u64)pp * SLAB_KB * a.r_cap : dummy, ok ? a.r_cap : 0u, ok ? mine : 1u, tid);
@@ -1139,10 +1182,12 @@ __global__ __launch_bounds__(THREADS, 4) void probe_count_fast_kernel(
     else
       fp_load<THREADS>(t, ok ? R + rb_ : dummy, ok ? nb_ : 1u, tid);
   };
-  auto load_probe = [&](Tup (&t)[FP_ROWS], bool ok, u32 pp, u32 sb_, u32 np_, u32 q1, u32 q2, u32 q3, u32 mine) {
-    if (PIECES)
-      fp_load_pieces<THREADS>(t, ok ? S + (u64)pp * SLAB_KB * a.s_cap : dummy, ok ? a.s_cap : 0u, ok ? mine : 1u, tid);
-    else if (SLAB)
+  auto load_probe = [&](PRow (&t)[PROWS], bool ok, u32 pp, u32 sb_, u32 np_, u32 q1, u32 q2, u32 q3, u32 mine) {
+    if constexpr (PKEYS)
+      fp_load_key_pieces<THREADS>(t, ok ? S + (u64)pp * SLAB_KB * a.s_cap : dummy_p, ok ? a.s_cap : 0u, ok ? mine : 1u, tid);
+    else if constexpr (PIECES)
+      fp_load_pieces<THREADS>(t, ok ? S + (u64)pp * SLAB_KB * a.s_cap : dummy_p, ok ? a.s_cap : 0u, ok ? mine : 1u, tid);
+    else if constexpr (SLAB)
       fp_load_slab<THREADS>(t, ok ? S + (u64)pp * SLAB_KB * a.s_cap : dummy, ok ? a.s_cap : 0u, ok ? q1 : 1u, ok ? q2 : 1u,
                             ok ? q3 : 1u, ok ? np_ : 1u, tid);
     else
@@ -1187,7 +1232,7 @@ __global__ __launch_bounds__(THREADS, 4) void probe_count_fast_kernel(
       }
       regular2 = nb2 && np2 && nb2 <= CAP && np2 <= CAP;
     }
-    if (OUT == 0) {
+    if constexpr (OUT == 0) {
       load_probe(pq, regular2, pn, sb2, np2, s1n, s2n, s3n, smn);  // next partition's probe rows, a whole partition ahead
     } else if (regular) {  // write mode keeps fewer rows in flight (registers): this partition's probe rows
       if (SLAB)
@@ -1237,45 +1282,46 @@ __global__ __launch_bounds__(THREADS, 4) void probe_count_fast_kernel(
       const u64 n_before = acc_n;
       if (!HMJ_ABLATE(1u)) {
         // probe: walk the five chains in lockstep so their LDS latencies overlap
-        u32 cur[FP_ROWS];
-        u32 cnt[FP_ROWS], first[FP_ROWS];  // OUT == 1
+        u32 cur[PROWS];
+        u32 cnt[PROWS], first[PROWS];  // OUT == 1; PKEYS: hits per probe row
 #pragma unroll
-        for (int k = 0; k < FP_ROWS; k++) {
+        for (int k = 0; k < PROWS; k++) {
           const u32 j = k * THREADS + tid;
           cur[k] = NIL;
           cnt[k] = 0;
           first[k] = OUT == 2 ? NIL : 0;
-          if (PIECES ? ((u32)tid % QT + (u32)k * QT < sm_) : (j < np)) {
-            if (a.pfx_shift && (pr[k].key >> a.pfx_shift) != a.pfx_val) pfx_bad = true;
-            if (OUT >= 1 && (a.extra & 1u)) acc_p += pr[k].val;
-            const u32 hv = sm.head[fast_hash<LOG_NB>(pr[k].key)];
+          if (PIECES ? (piece_row(tid, k) < sm_) : (j < np)) {
+            if (a.pfx_shift && (prow_key(pr[k]) >> a.pfx_shift) != a.pfx_val) pfx_bad = true;
+            if (OUT >= 1 && (a.extra & 1u)) acc_p += prow_val(pr[k]);
+            const u32 hv = sm.head[fast_hash<LOG_NB>(prow_key(pr[k]))];
             cur[k] = ((hv >> 16) == epoch) ? (hv & 0xFFFFu) : NIL;
           }
         }
         for (; !HMJ_ABLATE(2u);) {
           bool any = false;
 #pragma unroll
-          for (int k = 0; k < FP_ROWS; k++) any |= (cur[k] != NIL);
+          for (int k = 0; k < PROWS; k++) any |= (cur[k] != NIL);
           if (!__any(any)) break;
 #pragma unroll
-          for (int k = 0; k < FP_ROWS; k++) {
+          for (int k = 0; k < PROWS; k++) {
             if (cur[k] != NIL) {
               const u32 i = cur[k];
               const u64 kk = sm.key[i], vv = sm.val[i];  // val read unconditionally: one LDS
               cur[k] = sm.next[i];                       // round trip per chain step, not two
-              if (kk == pr[k].key) {
+              if (kk == prow_key(pr[k])) {
                 if (OUT == 2 && (a.extra & 2u)) {  // first wins: smallest position = first in input order
                   first[k] = i < first[k] ? i : first[k];
                 } else {
                   acc_n++;
                   acc_r += vv;
-                  acc_s += pr[k].val;
+                  acc_s += prow_val(pr[k]);
                   if (OUT == 1) {
                     if (cnt[k] == 0) first[k] = i;
                     cnt[k]++;
                   }
+                  if (PKEYS) cnt[k]++;
                   if (OUT >= 1 && (a.extra & 1u)) {
-                    const u64 m = tmix(kk, vv, pr[k].val);
+                    const u64 m = tmix(kk, vv, prow_val(pr[k]));
                     acc_x ^= m;
                     acc_m += m;
                   }
@@ -1284,6 +1330,10 @@ __global__ __launch_bounds__(THREADS, 4) void probe_count_fast_kernel(
             }
           }
         }
+        if constexpr (PKEYS) {  // every probe row of the partition must have met exactly one build row
+#pragma unroll
+          for (int k = 0; k < PROWS; k++) keys_bad |= piece_row(tid, k) < sm_ && cnt[k] != 1;
+        }
         if (OUT == 2 && (a.extra & 2u)) {
 #pragma unroll
           for (int k = 0; k < FP_ROWS; k++) {
@@ -1291,9 +1341,9 @@ __global__ __launch_bounds__(THREADS, 4) void probe_count_fast_kernel(
               const u64 vv = sm.val[first[k]];
               acc_n++;
               acc_r += vv;
-              acc_s += pr[k].val;
+              acc_s += prow_val(pr[k]);
               if (a.extra & 1u) {
-                const u64 m = tmix(pr[k].key, vv, pr[k].val);
+                const u64 m = tmix(prow_key(pr[k]), vv, prow_val(pr[k]));
                 acc_x ^= m;
                 acc_m += m;
               }
@@ -1344,9 +1394,9 @@ __global__ __launch_bounds__(THREADS, 4) void probe_count_fast_kernel(
             for (int k = 0; k < FP_ROWS; k++) {
               if (cnt[k]) {
                 const u64 d = o + ((ex >> (12 * k)) & 0xFFFu);
-                a.out_key[d] = pr[k].key;
+                a.out_key[d] = prow_key(pr[k]);
                 a.out_rval[d] = sm.val[first[k]];
-                a.out_sval[d] = pr[k].val;
+                a.out_sval[d] = prow_val(pr[k]);
               }
               const u32 tk = (u32)((tot >> (12 * k)) & 0xFFFu);
               o += tk;
@@ -1357,7 +1407,7 @@ __global__ __launch_bounds__(THREADS, 4) void probe_count_fast_kernel(
         }
       } else {
 #pragma unroll
-        for (int k = 0; k < FP_ROWS; k++) acc_r += pr[k].key;
+        for (int k = 0; k < FP_ROWS; k++) acc_r += prow_key(pr[k]);
       }
       if (PCOUNT) {
         const u32 mine = (u32)(acc_n - n_before);
@@ -1369,16 +1419,17 @@ __global__ __launch_bounds__(THREADS, 4) void probe_count_fast_kernel(
     } else {
       if ((PCOUNT || OUT == 1) && tid == 0 && !(nb && np)) a.part_count[p] = 0;  // empty side: no rows
       if (OUT == 1 && nb && np) giveup = true;  // does not fit the pipeline: general path
+      if (PKEYS && np && !nb) keys_bad = true;  // probe rows without a build row
       if (OUT >= 1 && (a.extra & 1u) && !nb) {  // probe rows without a build partition still count in sum_probe_all
         if (SLAB) {
-          const Tup* base = S + (u64)p * SLAB_KB * a.s_cap;
+          const PRow* base = S + (u64)p * SLAB_KB * a.s_cap;
           for (u32 j = tid; j < np; j += THREADS) {
             const u32 pc = (j >= s1) + (j >= s2) + (j >= s3);
             const u32 pre = pc == 0 ? 0 : pc == 1 ? s1 : pc == 2 ? s2 : s3;
-            acc_p += base[(u64)pc * a.s_cap + (j - pre)].val;
+            acc_p += prow_val(base[(u64)pc * a.s_cap + (j - pre)]);
           }
         } else {
-          for (u32 j = tid; j < np; j += THREADS) acc_p += S[sb + j].val;
+          for (u32 j = tid; j < np; j += THREADS) acc_p += prow_val(S[sb + j]);
         }
       }
       if (OUT != 1 && !SLAB && tid == 0 && nb && np) irregular[atomicAdd(n_irregular, 1u)] = p;
@@ -1386,7 +1437,7 @@ __global__ __launch_bounds__(THREADS, 4) void probe_count_fast_kernel(
     }
     if (OUT == 0) {
 #pragma unroll
-      for (int k = 0; k < FP_ROWS; k++) pr[k] = pq[k];
+      for (int k = 0; k < PROWS; k++) pr[k] = pq[k];
     }
     p = pn; rb = rb2; nb = nb2; sb = sb2; np = np2; regular = regular2;
     r1 = r1n; r2 = r2n; r3 = r3n; s1 = s1n; s2 = s2n; s3 = s3n;
@@ -1394,6 +1445,7 @@ __global__ __launch_bounds__(THREADS, 4) void probe_count_fast_kernel(
   }
   if (SLAB && slab_bad && tid == 0) atomicOr(&a.accum[ACC_ERR], ERR_SLAB);
   if (OUT == 1 && __any(giveup) && (tid & 63) == 0) atomicOr(&a.accum[ACC_ERR], ERR_FASTPATH);
+  if (PKEYS && __any(keys_bad) && (tid & 63) == 0) atomicOr(&a.accum[ACC_ERR], ERR_PROBE_KEYS);
   if (__any(pfx_bad) && (tid & 63) == 0) atomicOr(&a.accum[ACC_ERR], ERR_PREFIX);
   lds_barrier();
   if (PCOUNT && prev_p != 0xFFFFFFFFu && tid == 0) a.part_count[prev_p] = sm.itemcnt[parity ^ 1];
@@ -2747,15 +2799,15 @@ static hipError_t launch_probe_t(const ProbeArgs& a, int grid, hipStream_t st) {
   return hipGetLastError();
 }
 
-template <int THREADS, int LOG_NB, bool PCOUNT, bool SLAB = false, int OUT = 0>
+template <int THREADS, int LOG_NB, bool PCOUNT, bool SLAB = false, int OUT = 0, bool PKEYS = false>
 static hipError_t launch_fast_t(const ProbeArgs& a, u32* irregular, u32* n_irregular, int grid,
                                 hipStream_t st) {
   typedef FastSmem<THREADS, LOG_NB> Smem;
   static SmemAttrOnce attr_once;
-  if (hipError_t e = ensure_max_smem(attr_once, reinterpret_cast<const void*>(probe_count_fast_kernel<THREADS, LOG_NB, PCOUNT, SLAB, OUT>), (size_t)sizeof(Smem)); e != hipSuccess) return e;
+  if (hipError_t e = ensure_max_smem(attr_once, reinterpret_cast<const void*>(probe_count_fast_kernel<THREADS, LOG_NB, PCOUNT, SLAB, OUT, PKEYS>), (size_t)sizeof(Smem)); e != hipSuccess) return e;
   if ((u32)grid > a.P) grid = (int)a.P;
   if (grid < 1) grid = 1;
-  hipLaunchKernelGGL((probe_count_fast_kernel<THREADS, LOG_NB, PCOUNT, SLAB, OUT>), dim3(grid), dim3(THREADS),
+  hipLaunchKernelGGL((probe_count_fast_kernel<THREADS, LOG_NB, PCOUNT, SLAB, OUT, PKEYS>), dim3(grid), dim3(THREADS),
                      sizeof(Smem), st, a, irregular, n_irregular);
   return hipGetLastError();
 }
@@ -2872,6 +2924,45 @@ hipError_t launch_probe_count_ext(const ProbeArgs& a, u32* irregular, u32* n_irr
 hipError_t launch_probe_count_slab(const ProbeArgs& a, int num_cus, hipStream_t st) {
   if (!slab_operands_ok(a)) return hipErrorInvalidValue;
   return launch_fast_t<1024, BIG_LOG_NB, false, true>(a, nullptr, nullptr, num_cus * 4, st);
+}
+
+// the same with the probe side's slabs holding bare keys (a.s_cap / a.s_rows count key rows)
+hipError_t launch_probe_count_slab_keys(const ProbeArgs& a, int num_cus, hipStream_t st) {
+  if (!slab_operands_ok(a) || a.pfx_shift) return hipErrorInvalidValue;
+  return launch_fast_t<1024, BIG_LOG_NB, false, true, 0, true>(a, nullptr, nullptr, num_cus * 4, st);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Pilot of the key-only probe side (hmj_probekeys.h): is this the join in which every probe row meets exactly one build row?
+// kProbeKeysPilotRows probe rows, evenly spaced over the UNPARTITIONED probe side, one wave each: the wave derives the row's
+// partition from the plan's window, scans that partition's SLAB_KB build pieces (already in the pass-B slabs) and counts the
+// keys equal to the sampled one.  Any count but 1 raises ERR_PROBE_PILOT.  Reads ~16 B x partition size per sample.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void probe_keys_pilot_kernel(const Tup* __restrict__ S, u32 np, const Tup* __restrict__ R,
+                                                              const u32* __restrict__ r_cnt, u32 r_cap, int low, u32 pmask,
+                                                              u64* __restrict__ accum) {
+  const u32 wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
+  if (wave >= hmj_host::probe_keys_sample_count(np)) return;  // (wave-uniform)
+  const u64 key = S[hmj_host::probe_keys_sample_index(wave, np)].key;
+  const u32 p = (u32)(key >> low) & pmask;
+  u32 hits = 0;
+#pragma unroll
+  for (int j = 0; j < SLAB_KB; j++) {
+    u32 c = r_cnt[(u64)p * SLAB_KB + j];
+    c = c < r_cap ? c : r_cap;  // (an overflowed slab says so in ACC_ERR; never read past a piece)
+    const Tup* __restrict__ piece = R + ((u64)p * SLAB_KB + j) * r_cap;
+    for (u32 i = lane; i < c; i += 64) hits += piece[i].key == key ? 1u : 0u;
+  }
+  const u32 total = (u32)wave_sum_u64((u64)hits);
+  if (lane == 0 && total != 1) atomicOr(reinterpret_cast<unsigned long long*>(&accum[ACC_ERR]), (unsigned long long)ERR_PROBE_PILOT);
+}
+hipError_t launch_probe_keys_pilot(const void* S, u32 np, const void* slab_br, const u32* cnt_br, u32 r_cap, int low, int bits,
+                                   u64* accum, hipStream_t st) {
+  if (!S || !slab_br || !cnt_br || !accum || np == 0 || bits < 1 || bits > 31 || low < 0 || low + bits > 64) return hipErrorInvalidValue;
+  const u32 waves = hmj_host::probe_keys_sample_count(np);
+  hipLaunchKernelGGL(probe_keys_pilot_kernel, dim3((waves + 3) / 4), dim3(256), 0, st, static_cast<const Tup*>(S), np,
+                     static_cast<const Tup*>(slab_br), cnt_br, r_cap, low, (1u << bits) - 1u, accum);
+  return hipGetLastError();
 }
 
 hipError_t launch_probe(const ProbeArgs& a, int mode, bool first_wins, bool extra, int grid,

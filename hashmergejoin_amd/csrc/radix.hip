@@ -293,7 +293,50 @@ __global__ __launch_bounds__(RP_THREADS, 4) void radix_scatter_kernel(
 // 2 per (worker, digit).
 // ---------------------------------------------------------------------------------------------
 constexpr int WC_ITEMS = 4;
-constexpr int WC_LINE = 8;  // rows per 128-byte line
+constexpr int WC_LINE = 8;  // Tup rows per 128-byte line (WcSmem::LINE: of whichever row)
+static_assert(WC_LINE * sizeof(Tup) == 128, "one line");
+// The tile code below is generic in the OUTPUT ROW: Tup (16 bytes, 8 rows to a line) or a bare u64 key (8 bytes, 16 to a
+// line -- the probe side of a count join whose payloads the result does not need, hmj_probekeys.h).  Both forms stage
+// 32 KiB tiles and keep 32 KiB of carry lines; a key row halves the instructions per row of every per-tile phase.
+__device__ __forceinline__ u64 row_key(const Tup& t) { return t.key; }
+__device__ __forceinline__ u64 row_key(u64 k) { return k; }
+__device__ __forceinline__ void row_set_key(Tup& t, u64 k) { t.key = k; }
+__device__ __forceinline__ void row_set_key(u64& t, u64 k) { t = k; }
+__device__ __forceinline__ u64 row_val(const Tup& t) { return t.val; }
+__device__ __forceinline__ u64 row_val(u64) { return 0; }
+template <typename Row>
+__device__ __forceinline__ Row make_row(u64 k, u64 v);
+template <>
+__device__ __forceinline__ Tup make_row<Tup>(u64 k, u64 v) {
+  Tup t;
+  t.key = k;
+  t.val = v;
+  return t;
+}
+template <>
+__device__ __forceinline__ u64 make_row<u64>(u64 k, u64) { return k; }
+__device__ __forceinline__ void store_stream(u64* p, u64 v) {  // (worker-boundary partial lines only)
+#if HMJ_STREAM_POLICY >= 1
+  __builtin_nontemporal_store(v, p);
+#else
+  *p = v;
+#endif
+}
+__device__ __forceinline__ u64 load_stream(const u64* p) {
+#if HMJ_STREAM_POLICY >= 2
+  return __builtin_nontemporal_load(p);
+#else
+  return *p;
+#endif
+}
+__device__ __forceinline__ void store_stream2(u64* p, u64 a, u64 b) {  // two consecutive keys, p 16-byte aligned
+#if HMJ_STREAM_POLICY >= 1
+  u64x2_t x = {a, b};
+  __builtin_nontemporal_store(x, reinterpret_cast<u64x2_t*>(p));
+#else
+  *reinterpret_cast<u64x2_t*>(p) = u64x2_t{a, b};
+#endif
+}
 
 // Developer builds (-DHMJ_STAMPS): shader-clock stamps around the phases of wc_tile, summed over all waves of
 // a launch into g_wc_stamps[phase] (read and reset by hmj_dev_stamps, api.hip).  Phases: 0 wait for the tile's
@@ -340,19 +383,25 @@ struct WcStamps {
 #define WC_VMWAIT()
 #endif
 
-template <int THREADS, int MAXD>
+template <int THREADS, int MAXD, typename Row = Tup, int ITEMS = WC_ITEMS>
 struct WcSmem {
-  static constexpr int TILE = THREADS * WC_ITEMS;
+  typedef Row row_type;
+  static constexpr int TILE = THREADS * ITEMS;
   static constexpr int WAVES = THREADS / kWave;
-  static constexpr int ZROWS = WAVES * MAXD * 8 / 16;  // tile rows aliased by the lane masks
-  static constexpr int MAXLINES = TILE / WC_LINE + 2 * MAXD;
+  static constexpr int LINE = 128 / (int)sizeof(Row);           // rows per 128-byte line: 8 or 16
+  static constexpr int LINE_SHIFT = LINE == 8 ? 3 : 4;
+  static constexpr int CARRY_ITEMS = MAXD * LINE / THREADS;     // carry slots per thread
+  static constexpr int ZROWS = WAVES * MAXD * 8 / (int)sizeof(Row);  // tile rows aliased by the lane masks
+  static constexpr int MAXLINES = TILE / LINE + 2 * MAXD;
+  static_assert(sizeof(Row) == 16 || sizeof(Row) == 8, "rows of 16 bytes (Tup) or 8 (a key)");
   static_assert(ZROWS <= TILE && ZROWS % THREADS == 0, "lane masks must alias whole row slabs");
-  static_assert(MAXD <= THREADS && MAXD * WC_LINE == TILE, "one digit per thread; carry == tile slots");
+  static_assert(MAXD <= THREADS && (MAXD * LINE) % THREADS == 0 && TILE < 65536, "one digit per thread; whole carry rounds");
+  static_assert(sizeof(Row) == 8 || MAXD * LINE == TILE, "Tup rows: carry == tile slots");
   union {
-    Tup stage[TILE];
+    Row stage[TILE];
     u64 lanemask[WAVES][MAXD];
   };
-  Tup carry[MAXD][WC_LINE];
+  Row carry[MAXD][LINE];
   u16 wcnt[WAVES][MAXD];
   u32 tile_off[MAXD];  // start of digit d's new rows inside the staged tile
   u32 cflush[MAXD];    // global row where digit d's next unflushed row belongs
@@ -379,12 +428,15 @@ struct WcSmem {
 struct NoLimit {
   __device__ __forceinline__ u32 operator()(u32) const { return 0xFFFFFFFFu; }
 };
-template <int THREADS, int MAXD, bool HI, bool ALLVALID, bool LIMIT, typename Prefetch, typename Limit>
-__device__ __forceinline__ void wc_tile(WcSmem<THREADS, MAXD>& sm, Tup (&t)[WC_ITEMS], u32 tile_n,
-                                        Tup* __restrict__ out, int shift, u32 mask, u32 D,
+template <int THREADS, int MAXD, bool HI, bool ALLVALID, bool LIMIT, typename Row, int ITEMS, typename Prefetch, typename Limit>
+__device__ __forceinline__ void wc_tile(WcSmem<THREADS, MAXD, Row, ITEMS>& sm, Row (&t)[ITEMS], u32 tile_n,
+                                        Row* __restrict__ out, int shift, u32 mask, u32 D,
                                         Prefetch&& prefetch, const Limit& limit, bool* ovf WC_STAMP_ARG) {
-  typedef WcSmem<THREADS, MAXD> Smem;
+  typedef WcSmem<THREADS, MAXD, Row, ITEMS> Smem;
   constexpr int WAVES = Smem::WAVES;
+  constexpr int WC_ITEMS = ITEMS;                                    // (this tile's rows per thread ...
+  constexpr int WC_LINE = Smem::LINE, LSH = Smem::LINE_SHIFT;        //  ... and rows per line shadow the Tup constants)
+  constexpr int CARRY_ITEMS = Smem::CARRY_ITEMS;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   u16* wc = &sm.wcnt[w][0];
   u64* lm = &sm.lanemask[w][0];
@@ -404,7 +456,7 @@ __device__ __forceinline__ void wc_tile(WcSmem<THREADS, MAXD>& sm, Tup (&t)[WC_I
   for (int r = 0; r < WC_ITEMS; r++) {
     u32 d = 0, rank = 0;
     if (ALLVALID || wbase + r * 64 < tile_n) {
-      d = digit_of<HI>(t[r].key, shift, mask);
+      d = digit_of<HI>(row_key(t[r]), shift, mask);
       __hip_atomic_fetch_or(&lm[d], lanebit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       const u64 m = __hip_atomic_load(&lm[d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       const u32 old = __hip_atomic_load(&wc[d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -455,7 +507,7 @@ __device__ __forceinline__ void wc_tile(WcSmem<THREADS, MAXD>& sm, Tup (&t)[WC_I
         }
         const u32 tail = (cf[j] + avail) & (WC_LINE - 1);  // rows past the last whole line
         fl[j] = (tail >= avail) ? 0u : avail - tail;
-        nl[j] = fl[j] ? (((cf[j] & (WC_LINE - 1)) + fl[j] + WC_LINE - 1) >> 3) : 0u;
+        nl[j] = fl[j] ? (((cf[j] & (WC_LINE - 1)) + fl[j] + WC_LINE - 1) >> LSH) : 0u;
         sm.pend[d] = avail - fl[j];
         sm.cflush[d] = cf[j] + fl[j];
       }
@@ -499,7 +551,7 @@ __device__ __forceinline__ void wc_tile(WcSmem<THREADS, MAXD>& sm, Tup (&t)[WC_I
       }
       const u32 tail = (cf + avail) & (WC_LINE - 1);  // rows past the last whole line
       fl = (tail >= avail) ? 0u : avail - tail;
-      nl = fl ? (((cf & (WC_LINE - 1)) + fl + WC_LINE - 1) >> 3) : 0u;
+      nl = fl ? (((cf & (WC_LINE - 1)) + fl + WC_LINE - 1) >> LSH) : 0u;
       sm.pend[tid] = avail - fl;
       sm.cflush[tid] = cf + fl;
     }
@@ -536,7 +588,7 @@ __device__ __forceinline__ void wc_tile(WcSmem<THREADS, MAXD>& sm, Tup (&t)[WC_I
 
   // copy out WHOLE LINES: 8 consecutive lanes own one 128-byte line (carried rows first, then
   // this tile's rows), so every line leaves in a single store instruction
-  {
+  if constexpr (sizeof(Row) == 16) {
     const u32 TL = sm.total_lines, k = (u32)tid & (WC_LINE - 1);
     for (u32 L = (u32)tid >> 3; L < TL; L += THREADS / WC_LINE) {
       const u32 d = sm.line_tab[L];
@@ -548,13 +600,40 @@ __device__ __forceinline__ void wc_tile(WcSmem<THREADS, MAXD>& sm, Tup (&t)[WC_I
       const u32 j = grow - cfd;  // wraps (huge) for the slots before an unaligned segment start
       if (j < fl) store_stream(&out[grow], (j < pd) ? sm.carry[d][j] : sm.stage[sm.tile_off[d] + j - pd]);
     }
+  } else {
+    // key rows: a line is 16 keys and STILL leaves in one 16-byte store per lane -- eight lanes own a line, each carries
+    // two consecutive keys of the digit's run (8-byte stores would double the store instructions per byte).  Only the
+    // first line of a segment that starts off a line boundary has lanes with one key or none.
+    const u32 TL = sm.total_lines, k = ((u32)tid & 7u) * 2u;
+    for (u32 L = (u32)tid >> 3; L < TL; L += THREADS / 8) {  // (THREADS / 8 lines a round)
+      const u32 d = sm.line_tab[L];
+      const u32 pl = sm.plan[d], fl = pl >> 8, pd = pl & 0xFFu;
+      u32 cfd;
+      if constexpr (Smem::HAS_CF_TILE) cfd = sm.cf_tile[d];
+      else cfd = sm.cflush[d] - fl;
+      const u32 grow = (cfd & ~(u32)(WC_LINE - 1)) + (L - sm.line_off[d]) * WC_LINE + k;
+      const u32 j0 = grow - cfd, j1 = j0 + 1u;  // wrap (huge) before an unaligned segment start; j1 wraps back to 0
+      const u32 toff = sm.tile_off[d] - pd;     // (only ever added to a j >= pd)
+      const bool v0 = j0 < fl, v1 = j1 < fl;
+      u64 k0 = 0, k1 = 0;
+      if (v0) k0 = (j0 < pd) ? sm.carry[d][j0] : sm.stage[toff + j0];
+      if (v1) k1 = (j1 < pd) ? sm.carry[d][j1] : sm.stage[toff + j1];
+      if (v0 && v1) store_stream2(&out[grow], k0, k1);
+      else if (v0) store_stream(&out[grow], k0);
+      else if (v1) store_stream(&out[grow + 1], k1);
+    }
   }
   // rows that stay behind (each digit's new partial line): stage -> registers
-  u64 keep_k[WC_ITEMS], keep_v[WC_ITEMS];
+  u64 keep_k[CARRY_ITEMS], keep_v[CARRY_ITEMS];  // (two scalar arrays: an array of Tup goes to scratch)
   u32 has = 0;
+  // key rows: eight carry slots per thread.  Their LDS addresses are the same in every tile, and hoisted out of the tile loop
+  // they are fourteen more live registers than the kernel has: spilled, and reloaded here behind the prefetch in the vmcnt
+  // queue.  An opaque thread index makes them this phase's own arithmetic again.
+  int tid_c = tid;
+  if constexpr (sizeof(Row) == 8) asm volatile("" : "+v"(tid_c));
 #pragma unroll
-  for (int q = 0; q < WC_ITEMS; q++) {
-    const u32 s = q * THREADS + tid, d = s >> 3, k = s & (WC_LINE - 1);
+  for (int q = 0; q < CARRY_ITEMS; q++) {
+    const u32 s = q * THREADS + tid_c, d = s >> LSH, k = s & (WC_LINE - 1);
     u32 idx = 0;
     if (d < D && k < sm.pend[d]) {
       const u32 pl = sm.plan[d], fl = pl >> 8, pd = pl & 0xFFu;
@@ -563,32 +642,31 @@ __device__ __forceinline__ void wc_tile(WcSmem<THREADS, MAXD>& sm, Tup (&t)[WC_I
         has |= 1u << q;
       }
     }
-    const Tup kv = sm.stage[idx];  // unconditional read (row 0 when nothing stays)
-    keep_k[q] = kv.key;
-    keep_v[q] = kv.val;
+    const Row kv = sm.stage[idx];  // unconditional read (row 0 when nothing stays)
+    keep_k[q] = row_key(kv);
+    keep_v[q] = row_val(kv);
   }
   WC_MARK(7);
   lds_barrier();
   WC_MARK(8);
 #pragma unroll
-  for (int q = 0; q < WC_ITEMS; q++) {
-    const u32 s = q * THREADS + tid;
-    if (has & (1u << q)) {
-      Tup kv;
-      kv.key = keep_k[q];
-      kv.val = keep_v[q];
-      sm.carry[s >> 3][s & (WC_LINE - 1)] = kv;
-    }
+  for (int q = 0; q < CARRY_ITEMS; q++) {
+    const u32 s = q * THREADS + tid_c;
+    if (has & (1u << q)) sm.carry[s >> LSH][s & (WC_LINE - 1)] = make_row<Row>(keep_k[q], keep_v[q]);
   }
 #if HMJ_WC_NOBAR5
   // every wave hands its OWN lane-mask slab (aliased on the tile buffer) and its own digit counters back as
   // zeros: the next tile's ranking touches only those, so no barrier is needed between here and there.
   // (The carry rows written above are next read after three more barriers, or behind wc_flush_carry's.)
   {
-    constexpr int ZR = MAXD * 8 / 16;  // tile rows aliased by one wave's lane masks
-    Tup z;
-    z.key = 0;
-    z.val = 0;
+    constexpr int ZR = MAXD * 8 / (int)sizeof(Row);  // tile rows aliased by one wave's lane masks
+    Row z;
+    if constexpr (sizeof(Row) == 16) {
+      z.key = 0;
+      z.val = 0;
+    } else {
+      z = 0;
+    }
 #pragma unroll
     for (int r = 0; r < ZR / kWave; r++) sm.stage[w * ZR + r * kWave + lane] = z;
     u32* wz = reinterpret_cast<u32*>(&sm.wcnt[w][0]);
@@ -600,10 +678,14 @@ __device__ __forceinline__ void wc_tile(WcSmem<THREADS, MAXD>& sm, Tup (&t)[WC_I
 #else
 #pragma unroll
   for (int r = 0; r < WC_ITEMS; r++) {
-    if (r * THREADS < Smem::ZROWS) {  // hand the slab back to the lane masks as zeros
-      Tup z;
-      z.key = 0;
-      z.val = 0;
+    if (r * THREADS < Smem::ZROWS) {  // hand the slab back to the lane masks as zeros (field by field, as below)
+      Row z;
+      if constexpr (sizeof(Row) == 16) {
+        z.key = 0;
+        z.val = 0;
+      } else {
+        z = 0;
+      }
       sm.stage[r * THREADS + tid] = z;
     }
   }
@@ -615,20 +697,21 @@ __device__ __forceinline__ void wc_tile(WcSmem<THREADS, MAXD>& sm, Tup (&t)[WC_I
 }
 
 // worker done: whatever still waits in the carry buffers ends this worker's digit segments
-template <int THREADS, int MAXD>
-__device__ __forceinline__ void wc_flush_carry(WcSmem<THREADS, MAXD>& sm, Tup* __restrict__ out, u32 D) {
+template <int THREADS, int MAXD, typename Row, int ITEMS>
+__device__ __forceinline__ void wc_flush_carry(WcSmem<THREADS, MAXD, Row, ITEMS>& sm, Row* __restrict__ out, u32 D) {
+  typedef WcSmem<THREADS, MAXD, Row, ITEMS> Smem;
   const int tid = threadIdx.x;
   lds_barrier();  // the last tile's carry rows are complete
 #pragma unroll
-  for (int q = 0; q < WC_ITEMS; q++) {
-    const u32 s = q * THREADS + tid, d = s >> 3, k = s & (WC_LINE - 1);
+  for (int q = 0; q < Smem::CARRY_ITEMS; q++) {
+    const u32 s = q * THREADS + tid, d = s >> Smem::LINE_SHIFT, k = s & (Smem::LINE - 1);
     if (d < D && k < sm.pend[d]) store_stream(&out[sm.cflush[d] + k], sm.carry[d][k]);
   }
 }
 
-template <int THREADS, int MAXD>
-__device__ __forceinline__ void wc_clear(WcSmem<THREADS, MAXD>& sm) {
-  constexpr int WAVES = WcSmem<THREADS, MAXD>::WAVES;
+template <int THREADS, int MAXD, typename Row, int ITEMS>
+__device__ __forceinline__ void wc_clear(WcSmem<THREADS, MAXD, Row, ITEMS>& sm) {
+  constexpr int WAVES = WcSmem<THREADS, MAXD, Row, ITEMS>::WAVES;
   const int tid = threadIdx.x;
   for (int i = tid; i < WAVES * MAXD / 2; i += THREADS) reinterpret_cast<u32*>(&sm.wcnt[0][0])[i] = 0;
   for (int i = tid; i < WAVES * MAXD; i += THREADS) (&sm.lanemask[0][0])[i] = 0;
@@ -719,11 +802,21 @@ __global__ __launch_bounds__(THREADS, (THREADS * (MAXD <= 256 ? 2 : 1)) / 256) v
 struct NoXform {
   static constexpr bool kStrided = false;
 };
-template <int THREADS, int MAXD, bool HI, typename Xform>
+// Row: what the pass writes.  Tup: the rows it read.  u64: their KEYS only (a count join's probe side, hmj_probekeys.h) --
+// the pass still reads whole rows, but 4096 to a tile, eight per thread (with 2048-row tiles the pass took as long as the
+// Tup form, 1.53 against 1.52 ms at 2^28 rows: a tile's plan, barriers, carry and copy-out cost the same for half the
+// bytes), stages and writes keys, and adds every row's payload into a per-thread sum that ends in accum[ACC_SUM_S]: when
+// every probe row turns out to match exactly one build row, that IS the join's sum_s (the key-only probe kernel verifies
+// it and leaves ACC_SUM_S alone).
+template <int THREADS, int MAXD, bool HI, typename Xform, typename Row = Tup>
 __device__ __forceinline__ void slab_a_body(const Tup* __restrict__ in, u32 n, int shift, int bits, u32 rows_per_worker,
-                                            Tup* __restrict__ slab, u32 CA, u32 WA, u32* __restrict__ cnt_out,
+                                            Row* __restrict__ slab, u32 CA, u32 WA, u32* __restrict__ cnt_out,
                                             u64* __restrict__ accum, u32 worker_base, Xform& xf) {
-  typedef WcSmem<THREADS, MAXD> Smem;
+  constexpr bool KEYS = !std::is_same<Row, Tup>::value;
+  constexpr int WC_ITEMS = KEYS ? 2 * hmj::WC_ITEMS : hmj::WC_ITEMS;  // rows per thread and tile
+  typedef WcSmem<THREADS, MAXD, Row, WC_ITEMS> Smem;
+  static_assert(!KEYS || std::is_same<Xform, NoXform>::value, "key rows: the join's plain pass A only");
+  u64 val_sum = 0;  // KEYS: this thread's share of the sum of all payloads
   constexpr int TILE = Smem::TILE;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   Smem& sm = *reinterpret_cast<Smem*>(smem_raw);
@@ -816,15 +909,40 @@ __device__ __forceinline__ void slab_a_body(const Tup* __restrict__ in, u32 n, i
       };
       if constexpr (!std::is_same<Xform, NoXform>::value) xf(t, tile_n, wbase);
       // whole tiles (all but a worker's last) run the predicate-free instantiation
-      if (HMJ_WC_FULLTILE && tile_n == (u32)TILE)
-        wc_tile<THREADS, MAXD, HI, true, true>(sm, t, tile_n, slab, shift, mask, D, prefetch, limit, &ovf WC_STAMP_PASS);
-      else
-        wc_tile<THREADS, MAXD, HI, false, true>(sm, t, tile_n, slab, shift, mask, D, prefetch, limit, &ovf WC_STAMP_PASS);
+      if constexpr (KEYS) {
+        u64 tk[WC_ITEMS];  // (the prefetch refills t while the keys leave)
+#pragma unroll
+        for (int r = 0; r < WC_ITEMS; r++) {
+          tk[r] = t[r].key;
+          val_sum += (wbase + (u32)r * 64 < tile_n) ? t[r].val : 0ull;  // (slots past the tile hold a clamped load's copy)
+        }
+        if (HMJ_WC_FULLTILE && tile_n == (u32)TILE)
+          wc_tile<THREADS, MAXD, HI, true, true>(sm, tk, tile_n, slab, shift, mask, D, prefetch, limit, &ovf WC_STAMP_PASS);
+        else
+          wc_tile<THREADS, MAXD, HI, false, true>(sm, tk, tile_n, slab, shift, mask, D, prefetch, limit, &ovf WC_STAMP_PASS);
+      } else {
+        if (HMJ_WC_FULLTILE && tile_n == (u32)TILE)
+          wc_tile<THREADS, MAXD, HI, true, true>(sm, t, tile_n, slab, shift, mask, D, prefetch, limit, &ovf WC_STAMP_PASS);
+        else
+          wc_tile<THREADS, MAXD, HI, false, true>(sm, t, tile_n, slab, shift, mask, D, prefetch, limit, &ovf WC_STAMP_PASS);
+      }
     }
     wc_flush_carry(sm, slab, D);
   }
   if ((u32)tid < D) cnt_out[(u32)tid * WA + worker] = sm.cflush[tid] + sm.pend[tid] - ((u32)tid * WA + worker) * CA;
   if (ovf) atomicOr(&accum[ACC_ERR], ERR_SLAB);
+  if constexpr (KEYS) {  // one atomic per worker: the waves' sums meet in LDS (scratch is free once the last tile is planned)
+    const u64 ws = wave_sum_u64(val_sum);
+    u64* red = reinterpret_cast<u64*>(sm.plan);  // (plan[] is read by the copy-out only; 8-byte aligned, MAXD >= 2 * waves)
+    __syncthreads();
+    if (lane == 0) red[w] = ws;
+    __syncthreads();
+    if (tid == 0) {
+      u64 tot = 0;
+      for (int k = 0; k < THREADS / kWave; k++) tot += red[k];
+      if (tot) atomicAdd(reinterpret_cast<unsigned long long*>(&accum[ACC_SUM_S]), (unsigned long long)tot);
+    }
+  }
 #ifdef HMJ_STAMPS
   stamps.flush();
 #endif
@@ -847,13 +965,17 @@ static bool g_b_addr_alt = false;  // launch the slab lookup that is NOT the def
 // (SLAB_KB, hmj_dev.h: pass-B workers per bucket == pieces per final partition of the full slab path)
 constexpr int SLAB_MAXSEG = 512;  // A-slabs one pass-B worker gathers (WA / KB <= 512)
 
-template <int THREADS, int MAXD, bool HI, int ADDR>
+// Row = Tup: rows in, rows out.  Row = u64: pass A wrote keys (radix_slab_a_kernel<.., u64>); a thread takes 8 of them per
+// tile -- 4096 keys, the same 32 KiB stage -- and everything below counts in rows of whichever kind.
+template <int THREADS, int MAXD, bool HI, int ADDR, typename Row = Tup>
 __global__ __launch_bounds__(THREADS, (THREADS * (MAXD <= 256 ? 2 : 1)) / 256) void radix_slab_b_kernel(
-    const Tup* __restrict__ slab_a, const u32* __restrict__ cnt_a, u32 CA, u32 WA, int bits_a, int shift,
-    int bits, Tup* __restrict__ slab_b, u32 CB, u32* __restrict__ cnt_b, u64* __restrict__ accum, u32 KB) {
-  typedef WcSmem<THREADS, MAXD> Smem;
+    const Row* __restrict__ slab_a, const u32* __restrict__ cnt_a, u32 CA, u32 WA, int bits_a, int shift,
+    int bits, Row* __restrict__ slab_b, u32 CB, u32* __restrict__ cnt_b, u64* __restrict__ accum, u32 KB) {
+  constexpr int WC_ITEMS = 64 / (int)sizeof(Row);  // rows per thread and tile: 4 Tup or 8 keys
+  typedef WcSmem<THREADS, MAXD, Row, WC_ITEMS> Smem;
   constexpr int TILE = Smem::TILE;
   static_assert(SLAB_MAXSEG <= THREADS, "one A-slab count per thread in the prologue scan");
+  static_assert(ADDR == 2 || sizeof(Row) == 16, "the per-round lookups (ADDR 0 / 1) plan four rounds of Tup rows");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   Smem& sm = *reinterpret_cast<Smem*>(smem_raw);
   u32* pre = reinterpret_cast<u32*>(smem_raw + sizeof(Smem));  // SLAB_MAXSEG + 1 prefix sums
@@ -883,14 +1005,14 @@ __global__ __launch_bounds__(THREADS, (THREADS * (MAXD <= 256 ? 2 : 1)) / 256) v
 #endif
   const u32 wbase = (u32)w * (WC_ITEMS * 64) + lane;
   (void)wbase;
-  const Tup* __restrict__ bucket = slab_a + (u64)(dA * WA + w0) * CA;  // A-slab j of this worker: + j*CA
+  const Row* __restrict__ bucket = slab_a + (u64)(dA * WA + w0) * CA;  // A-slab j of this worker: + j*CA
   bool ovf = false;
 #ifdef HMJ_STAMPS
   WcStamps stamps = {};
   stamps.base = 16;
 #endif
   if (total) {
-    Tup t[WC_ITEMS];
+    Row t[WC_ITEMS];
     if constexpr (ADDR != 0) {
     // Row q of the worker's input (the concatenation of its A-slabs) lives in slab s = the last one with
     // pre[s] <= q, at bucket[s * CA + (q - pre[s])].  A wave reads 4 ROUNDS of 64 consecutive rows per tile;
@@ -1028,7 +1150,9 @@ __global__ __launch_bounds__(THREADS, (THREADS * (MAXD <= 256 ? 2 : 1)) / 256) v
       u_b4 = (u32)__builtin_amdgcn_readlane((int)win_v, (int)j + 4);
     };
     auto issue2 = [&](u32 tile_begin) {
-      u64 off[WC_ITEMS];
+      // (row offsets inside the bucket are below 2^32 -- launch_slab_b checks the slabs' total -- and key rows, eight to a
+      //  thread, have no registers to spare for 64-bit ones)
+      typename std::conditional<sizeof(Row) == 8, u32, u64>::type off[WC_ITEMS];
       const u32 wq0 = tile_begin + wq;
       u32 wlast = wq0 + WC_ITEMS * 64 - 1;
       wlast = wlast < total ? wlast : total - 1;
@@ -1092,7 +1216,7 @@ __global__ __launch_bounds__(THREADS, (THREADS * (MAXD <= 256 ? 2 : 1)) / 256) v
       if (abl == 1 || abl == 4) {  // never-written slab tails hold zero keys: give them spread digits (the rank phase waits for the rows anyway)
 #pragma unroll
         for (int r = 0; r < WC_ITEMS; r++)
-          if (t[r].key == 0) t[r].key = (u64)(tile + (u32)tid + r * THREADS + blockIdx.x * 7919u + 1) * 0x9E3779B97F4A7C15ull;
+          if (row_key(t[r]) == 0) row_set_key(t[r], (u64)(tile + (u32)tid + r * THREADS + blockIdx.x * 7919u + 1) * 0x9E3779B97F4A7C15ull);
       }
 #endif
       if (HMJ_WC_FULLTILE && tile_n == (u32)TILE)
@@ -1279,12 +1403,12 @@ __global__ __launch_bounds__(1024) void key_sample_kernel(const Tup* __restrict_
 // Two shapes per slab kernel: digits of up to 8 bits run 512 threads x 2048-row tiles, two workgroups per CU (74 KiB
 // LDS); a 9-bit digit needs 512 carry lines (64 KiB) beside a 4096-row tile and runs 1024 threads, one workgroup per
 // CU (157 + 2 KiB) -- the shape radix_scatter_wc_kernel<1024, 512> has on the exact path.
-template <int THREADS, int MAXD, bool HI>
+template <int THREADS, int MAXD, bool HI, typename Row = Tup>
 __global__ __launch_bounds__(THREADS, (THREADS * (MAXD <= 256 ? 2 : 1)) / 256) void radix_slab_a_kernel(
-    const Tup* __restrict__ in, u32 n, int shift, int bits, u32 rows_per_worker, Tup* __restrict__ slab,
+    const Tup* __restrict__ in, u32 n, int shift, int bits, u32 rows_per_worker, Row* __restrict__ slab,
     u32 CA, u32 WA, u32* __restrict__ cnt_out, u64* __restrict__ accum, u32 worker_base) {
   NoXform xf;
-  slab_a_body<THREADS, MAXD, HI, NoXform>(in, n, shift, bits, rows_per_worker, slab, CA, WA, cnt_out, accum, worker_base, xf);
+  slab_a_body<THREADS, MAXD, HI, NoXform, Row>(in, n, shift, bits, rows_per_worker, slab, CA, WA, cnt_out, accum, worker_base, xf);
 }
 
 // Pass A with the rank lookup in front (the rank-run form of ordered small-build joins, gtable.hip / api.hip): the rows
@@ -1374,30 +1498,31 @@ __global__ __launch_bounds__(THREADS, (THREADS * (MAXD <= 256 ? 2 : 1)) / 256) v
     if (rows) atomicAdd(reinterpret_cast<unsigned long long*>(&accum[ACC_N]), (unsigned long long)rows);
   }
 }
-template <int THREADS, int MAXD, bool HI>
+template <int THREADS, int MAXD, bool HI, typename Row = Tup>
 static hipError_t launch_slab_a_t(const void* in, u32 n, int shift, int bits, u32 rpw, void* slab, u32 CA,
                                   u32 WA, u32* cnt, u64* accum, hipStream_t st, u32 w_begin, u32 w_end) {
-  typedef WcSmem<THREADS, MAXD> Smem;
+  typedef WcSmem<THREADS, MAXD, Row, (sizeof(Row) == 8 ? 2 : 1) * WC_ITEMS> Smem;  // (as slab_a_body)
   const size_t smem = sizeof(Smem);
   static_assert(sizeof(Smem) <= 160 * 1024, "slab pass A: LDS");
   static SmemAttrOnce attr_once;
-  if (hipError_t e = ensure_max_smem(attr_once, reinterpret_cast<const void*>(radix_slab_a_kernel<THREADS, MAXD, HI>), (size_t)smem); e != hipSuccess) return e;
+  if (hipError_t e = ensure_max_smem(attr_once, reinterpret_cast<const void*>(radix_slab_a_kernel<THREADS, MAXD, HI, Row>), (size_t)smem); e != hipSuccess) return e;
   if (w_end > WA) w_end = WA;
   if (w_begin >= w_end) return hipSuccess;
-  hipLaunchKernelGGL((radix_slab_a_kernel<THREADS, MAXD, HI>), dim3(w_end - w_begin), dim3(THREADS), smem, st,
-                     static_cast<const Tup*>(in), n, shift, bits, rpw, static_cast<Tup*>(slab), CA, WA, cnt,
+  hipLaunchKernelGGL((radix_slab_a_kernel<THREADS, MAXD, HI, Row>), dim3(w_end - w_begin), dim3(THREADS), smem, st,
+                     static_cast<const Tup*>(in), n, shift, bits, rpw, static_cast<Row*>(slab), CA, WA, cnt,
                      accum, w_begin);
   return hipGetLastError();
 }
 
-template <int THREADS, int MAXD, bool HI>
+template <int THREADS, int MAXD, bool HI, typename Row = Tup>
 static hipError_t launch_slab_b_t(const void* slab_a, const u32* cnt_a, u32 CA, u32 WA, int bits_a, int shift,
                                   int bits, void* slab_b, u32 CB, u32* cnt_b, u64* accum, hipStream_t st, u32 KB) {
-  typedef WcSmem<THREADS, MAXD> Smem;
+  typedef WcSmem<THREADS, MAXD, Row, 64 / (int)sizeof(Row)> Smem;
   const size_t smem = sizeof(Smem) + (SLAB_MAXSEG + 1) * sizeof(u32);
   static_assert(sizeof(Smem) + (SLAB_MAXSEG + 1) * sizeof(u32) <= 160 * 1024, "slab pass B: LDS");
+  static_assert(HMJ_B_ADDR == 2 || sizeof(Row) == 16, "key rows: the wave-uniform lookup only");
 #ifdef HMJ_DEV
-  if (g_b_addr_alt) {  // the other lookup, for A/B timing inside one process (hmj_dev_set_b_addr_alt)
+  if (g_b_addr_alt && sizeof(Row) == 16) {  // the other lookup, for A/B timing inside one process (hmj_dev_set_b_addr_alt)
     constexpr int ALT = HMJ_B_ADDR == 2 ? 1 : 2;
     static SmemAttrOnce attr_alt;
     if (hipError_t e = ensure_max_smem(attr_alt, reinterpret_cast<const void*>(radix_slab_b_kernel<THREADS, MAXD, HI, ALT>), (size_t)smem); e != hipSuccess) return e;
@@ -1408,10 +1533,10 @@ static hipError_t launch_slab_b_t(const void* slab_a, const u32* cnt_a, u32 CA, 
   }
 #endif
   static SmemAttrOnce attr_once;
-  if (hipError_t e = ensure_max_smem(attr_once, reinterpret_cast<const void*>(radix_slab_b_kernel<THREADS, MAXD, HI, HMJ_B_ADDR>), (size_t)smem); e != hipSuccess) return e;
-  hipLaunchKernelGGL((radix_slab_b_kernel<THREADS, MAXD, HI, HMJ_B_ADDR>), dim3((1u << bits_a) * KB), dim3(THREADS), smem, st,
-                     static_cast<const Tup*>(slab_a), cnt_a, CA, WA, bits_a, shift, bits,
-                     static_cast<Tup*>(slab_b), CB, cnt_b, accum, KB);
+  if (hipError_t e = ensure_max_smem(attr_once, reinterpret_cast<const void*>(radix_slab_b_kernel<THREADS, MAXD, HI, HMJ_B_ADDR, Row>), (size_t)smem); e != hipSuccess) return e;
+  hipLaunchKernelGGL((radix_slab_b_kernel<THREADS, MAXD, HI, HMJ_B_ADDR, Row>), dim3((1u << bits_a) * KB), dim3(THREADS), smem, st,
+                     static_cast<const Row*>(slab_a), cnt_a, CA, WA, bits_a, shift, bits,
+                     static_cast<Row*>(slab_b), CB, cnt_b, accum, KB);
   return hipGetLastError();
 }
 
@@ -1479,14 +1604,21 @@ bool slab_geometry_one_pass(u32 n, int bits, double keys_per_digit, u32 max_work
 }
 
 // workers [w_begin, w_end) of the pass (default: all): worker w reads input rows [w * g.rpw, (w + 1) * g.rpw)
+// keys: the pass writes the rows' KEYS (8-byte rows; slab_a_rows counts those) and adds their payloads into
+// accum[ACC_SUM_S]; g.CA must then be a multiple of 16 so that every slab starts on a 128-byte line (digits of <= 8 bits)
 hipError_t launch_slab_a(const void* in, u32 n, int shift, int bits, const SlabGeom& g, void* slab_a, u64 slab_a_rows,
-                         u32* cnt_a, u64 cnt_a_n, u64* accum, hipStream_t st, u32 w_begin, u32 w_end) {
+                         u32* cnt_a, u64 cnt_a_n, u64* accum, hipStream_t st, u32 w_begin, u32 w_end, bool keys) {
   // worker w writes slab [d][w][CA] and cnt[d * WA + w] for every digit d < 2^bits, and reads rows [w * rpw, ...)
   if (bits < 1 || bits > SLAB_MAX_BITS || g.WA == 0 || g.CA == 0 || (u64)g.WA * g.rpw < n) return hipErrorInvalidValue;
   if (slab_a_rows < ((u64)g.WA << bits) * g.CA || cnt_a_n < ((u64)g.WA << bits)) return hipErrorInvalidValue;
   if (((u64)g.WA << bits) * g.CA >= 0xFFFFFFF0ull) return hipErrorInvalidValue;  // (u32 row indices inside the kernel)
   const bool hi = shift >= 32;
 #define HMJ_SLAB_A(T, M, H) launch_slab_a_t<T, M, H>(in, n, shift, bits, g.rpw, slab_a, g.CA, g.WA, cnt_a, accum, st, w_begin, w_end)
+  if (keys) {
+    if (bits > 8 || (g.CA & 15u)) return hipErrorInvalidValue;
+    return hi ? launch_slab_a_t<512, 256, true, u64>(in, n, shift, bits, g.rpw, slab_a, g.CA, g.WA, cnt_a, accum, st, w_begin, w_end)
+              : launch_slab_a_t<512, 256, false, u64>(in, n, shift, bits, g.rpw, slab_a, g.CA, g.WA, cnt_a, accum, st, w_begin, w_end);
+  }
   if (bits > 8) return hi ? HMJ_SLAB_A(1024, 512, true) : HMJ_SLAB_A(1024, 512, false);
   return hi ? HMJ_SLAB_A(512, 256, true) : HMJ_SLAB_A(512, 256, false);
 #undef HMJ_SLAB_A
@@ -1534,8 +1666,10 @@ hipError_t launch_slab_a_ranks(const void* in, u32 n, int shift, int bits, const
   return hipGetLastError();
 }
 
+// keys: both slab sets hold 8-byte key rows (g.CA and g.CB multiples of 16, digits of <= 8 bits; slab_b_rows counts key rows)
 hipError_t launch_slab_b(const void* slab_a, const u32* cnt_a, int bits_a, int shift, int bits,
-                         const SlabGeom& g, void* slab_b, u64 slab_b_rows, u32* cnt_b, u64 cnt_b_n, u64* accum, hipStream_t st) {
+                         const SlabGeom& g, void* slab_b, u64 slab_b_rows, u32* cnt_b, u64 cnt_b_n, u64* accum, hipStream_t st,
+                         bool keys) {
   // worker (dA, k) writes piece (d << bits_a | dA) * KB + k of every digit d < 2^bits: P * KB pieces of CB rows, one
   // count each; it gathers the A-slabs [k * WA / KB, (k + 1) * WA / KB) -- at most SLAB_MAXSEG of them
   if (bits < 1 || bits > SLAB_MAX_BITS || bits_a < 1 || bits_a > SLAB_MAX_BITS || g.KB == 0 || g.WA < g.KB ||
@@ -1545,6 +1679,11 @@ hipError_t launch_slab_b(const void* slab_a, const u32* cnt_a, int bits_a, int s
   if (slab_b_rows < pieces * g.CB || cnt_b_n < pieces || pieces * g.CB >= 0xFFFFFFF0ull) return hipErrorInvalidValue;
   const bool hi = shift >= 32;
 #define HMJ_SLAB_B(T, M, H) launch_slab_b_t<T, M, H>(slab_a, cnt_a, g.CA, g.WA, bits_a, shift, bits, slab_b, g.CB, cnt_b, accum, st, g.KB)
+  if (keys) {
+    if (bits > 8 || bits_a > 8 || ((g.CA | g.CB) & 15u)) return hipErrorInvalidValue;
+    return hi ? launch_slab_b_t<512, 256, true, u64>(slab_a, cnt_a, g.CA, g.WA, bits_a, shift, bits, slab_b, g.CB, cnt_b, accum, st, g.KB)
+              : launch_slab_b_t<512, 256, false, u64>(slab_a, cnt_a, g.CA, g.WA, bits_a, shift, bits, slab_b, g.CB, cnt_b, accum, st, g.KB);
+  }
   if (bits > 8) return hi ? HMJ_SLAB_B(1024, 512, true) : HMJ_SLAB_B(1024, 512, false);
   return hi ? HMJ_SLAB_B(512, 256, true) : HMJ_SLAB_B(512, 256, false);
 #undef HMJ_SLAB_B

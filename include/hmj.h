@@ -135,6 +135,9 @@ typedef struct {
 #define HMJ_PATH_LDS_TABLE 0x800000u /* ... of <= 2048 build rows (1024 with HMJ_CHECKSUM / HMJ_SUM_PROBE) under >= 2^16 probe rows, count modes: that table in LDS, one copy per workgroup */
 #define HMJ_PATH_GLOBAL_TABLE 0x100000u /* small build side: one global hash table, the probe side streamed unpartitioned */
 #define HMJ_PATH_HOST_PIPELINE 0x4000u /* host entry: build side partitioned while the probe side was uploading   */
+#define HMJ_PATH_PROBE_KEYS 0x10000000u /* plain count join on the slab path whose probe side went through the passes as 8-byte KEYS:
+                                          every probe row met exactly one build row (verified by the probe kernel), so sum_s is the
+                                          sum of all probe payloads, added up by pass A.  Set only when the result came from that form */
 
 /* How the last join on this ctx was planned, and why (hmj_last_plan).  The planner chooses among the formulations listed
  * at hmj_join_u64_device from the sizes, the flags, a key sample and what EARLIER JOINS OF THE SAME WORKLOAD taught it:
@@ -173,6 +176,9 @@ typedef struct {
 #define HMJ_REFUSED_SLAB_PROBE_OVERFLOW 0x2000u
 #define HMJ_REFUSED_PREFIX_VIOLATED 0x4000u     /* a row outside the sampled key prefix: the join re-planned              */
 #define HMJ_REFUSED_EXPANSION_GAVE_UP 0x8000u   /* ordered expansion: a partition beyond the kernel's capacity            */
+#define HMJ_REFUSED_PROBE_KEYS_GAVE_UP 0x10000u /* key-only probe side tried by this join: a probe row without exactly one  */
+                                                /* build row; the probe side was redone with whole rows (build slabs kept)  */
+#define HMJ_REFUSED_PROBE_KEYS_COOLING 0x20000u /* ... skipped: an earlier join of this workload gave up on it             */
 #define HMJ_COOL_UNIQ_WRITE 0x001u
 #define HMJ_COOL_SORTED_WRITE 0x002u
 #define HMJ_COOL_GTABLE 0x004u
@@ -187,6 +193,7 @@ typedef struct {
 #define HMJ_COOL_EXACT_PREFIX 0x800u
 #define HMJ_COOL_RANK_RUNS 0x1000u
 #define HMJ_COOL_SORT_MSD 0x2000u
+#define HMJ_COOL_PROBE_KEYS 0x4000u
 
 /* ---- lifecycle ------------------------------------------------------------------------------- */
 /* Replaces: nothing in the reference (no device); one ctx per GPU. device_id < 0 = current.     */
@@ -277,6 +284,12 @@ const char* hmj_version(void);
  * Which formulation runs is the executor's choice (hmj_timing.path says which; results are the same):
  *   - two radix passes + LDS build/probe per partition (the default from ~2^21 rows per side on; histogram-free slab
  *     passes of up to 9 bits, so up to 2^30 rows per side stay at 32 B per row and pass);
+ *   - ... flags = 0, >= 2^25 probe rows, passes of <= 8 bits, and EVERY probe row meets exactly one build row (a foreign key
+ *     into a unique dimension key): the probe side goes through the slab passes as 8-byte keys -- 48 instead of 80 bytes per
+ *     probe row -- while its first pass adds up the payloads, which then ARE sum_s; HMJ_PATH_PROBE_KEYS.  A pilot over 4096
+ *     sampled probe rows decides whether a workload's first join starts that way, the probe kernel verifies every probe
+ *     row's match count, and a join that fails the check redoes its probe side with whole rows inside the same plan
+ *     (HMJ_REFUSED_PROBE_KEYS_GAVE_UP; the workload then keeps whole rows for 8 joins, HMJ_COOL_PROBE_KEYS);
  *   - count modes and unordered HMJ_MATERIALIZE, build side of <= 2^17 rows (or a join of <= 2^21 rows in all): ONE global
  *     hash table, the probe side streamed unpartitioned -- the reference's BM_hash_join_raw formulation
  *     (hashjoin_bench.cc:29-63), HMJ_PATH_GLOBAL_TABLE (count modes, <= 2048 build rows: the table in LDS, HMJ_PATH_LDS_TABLE);
